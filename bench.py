@@ -1,7 +1,16 @@
 #!/usr/bin/env python
 """Hot-path benchmark: denoising-step frames/sec of TokenFlow's hook layer on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2] [--graph] [--per-chunk]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2] [--graph] [--per-chunk] [--full]
+                    [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step` = wall time of
+one timed step, the event-bracketed `roofline` of the timed launches).  `--full` adds everything else after the timed
+region: `parity`, `roofline_other`, `other_configs`, `yardstick` and `cpu_baseline` below (each can still be dropped
+with its --no-* switch).  `--dump-outputs DIR` writes what the timed path computed in its LAST timed step as
+DIR/attn_bNN.npy (the extended-attention output of block NN) and DIR/prop_bNN.npy (its propagated chunks: NN search +
+gather / blend / residual), float32; a tensor above 2^18 elements is written as a fixed, seeded sample of that many
+elements (seed = 16 x kind + block).  N > 1: rank 0's frames.
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment re-launches itself through
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1` (one rank per GPU, RCCL);
@@ -26,7 +35,7 @@ small grids split the key sequence and merge in fp32; held to the oracle's bound
 `ms_per_step` report the faster of the two and `value_form` names it.  The step then follows the reference's call order: the pivotal pass over all 16 blocks, then the
 propagation of all blocks (the halo of a block travels under the rest of the pivotal pass).
 
-Prints ONE JSON line (rank 0):
+Prints ONE JSON line (rank 0); `parity`, `roofline_other`, `other_configs`, `yardstick` and `cpu_baseline` only with --full:
   roofline      the dominant kernel: the head-dim-40 extended attention of level 0 WITHOUT q/k injection
                 (ext_attn_kernel<.., MODE_ALL>), HIP events on the launch stream around every such call inside the
                 timed region (the bracket includes the V^T pre-pass launch); `roofline_inject` the same for the
@@ -56,6 +65,7 @@ import argparse
 import json
 import os
 import socket
+import subprocess
 import sys
 import time
 
@@ -100,6 +110,13 @@ def parse():
                     help="N = 1: capture the two step variants (injection on / off) into HIP graphs and time the "
                          "replays (launch-bound configurations: cfg1); the roofline bracket is then measured in a "
                          "separate eager pass after the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure and check everything beyond the headline: parity against "
+                         "the oracle, the other kernels' rooflines, the other configurations, the vendor-library "
+                         "yardsticks and the CPU baseline (the --no-* switches below drop single legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last timed step to DIR/<name>.npy (float32; "
+                         "attn_bNN / prop_bNN per block, large tensors as a fixed seeded sample)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-ref-l0", action="store_true",
                     help="--cpu-baseline-only with the reference mounted: run level 0 for real (minutes, ~13 GB)")
@@ -150,12 +167,16 @@ class Block:
         self.attn_flops_inject = self.attn_flops - 2.0 * Kl * S * D * (cfg.K * S)
 
 
-def run_step(cfg, blocks, shard, inject_on, w, events=None, exchange=None, per_chunk=False):
+def run_step(cfg, blocks, shard, inject_on, w, events=None, exchange=None, per_chunk=False, collect=None):
+    """One step over `blocks`; returns the last propagation output.  `collect` (a list): receives per block
+    (attention output, [propagation outputs]) -- what a caller of the path gets back (--dump-outputs)."""
     n = cfg.chunk
     outs = None
     two_pass = shard.world > 1 and not per_chunk
     pending = []
     for blk in blocks:
+        if collect is not None:
+            collect.append([None, []])
         inj = inject_on and blk.injected and cfg.pnp
         timed = events is not None and blk.lvl <= 1      # level 0 = `roofline`, level 1 = its `roofline_other` entries
         if timed:
@@ -172,6 +193,7 @@ def run_step(cfg, blocks, shard, inject_on, w, events=None, exchange=None, per_c
             # the last local keyframe), which has the rest of the pivotal pass to arrive.
             pending.append((blk, shard.pivotal_block(blk.q, blk.k, blk.v, blk.h, scale, inj, blk.ext, mode=exchange,
                                                      inv_norm=True)))
+            kf_out = None
         else:
             # the pivots' halo (features + inverse norms of the last local keyframe -> rank r+1) does not depend on
             # the attention: issued first, it travels under it
@@ -180,6 +202,8 @@ def run_step(cfg, blocks, shard, inject_on, w, events=None, exchange=None, per_c
         if timed:
             e1.record()
             events.append((e0, e1, inj, blk.lvl))
+        if collect is not None:
+            collect[-1][0] = kf_out
         if two_pass:
             continue
         if per_chunk or shard.world == 1:
@@ -193,11 +217,42 @@ def run_step(cfg, blocks, shard, inject_on, w, events=None, exchange=None, per_c
             for j in range(shard.Kl):
                 outs = shard.propagate(j, blk.tgt[j * nS:(j + 1) * nS], res[:, j].reshape(3 * n, blk.S, blk.D),
                                        piv_e, inv_e, kfo_e, w, n)
+                if collect is not None:
+                    collect[-1][1].append(outs)
         else:
             outs = shard.propagate_all(blk.tgt, blk.res, piv_e, inv_e, kfo_e, w, n)
-    for blk, (piv_e, inv_e, kfo_e, reqs) in pending:
-        outs, _ = shard.propagate_all(blk.tgt, blk.res, piv_e, inv_e, kfo_e, w, n, halo_reqs=reqs)
+            if collect is not None:
+                collect[-1][1].append(outs)
+    for b_, (blk, (piv_e, inv_e, kfo_e, reqs)) in enumerate(pending):
+        outs, rest = shard.propagate_all(blk.tgt, blk.res, piv_e, inv_e, kfo_e, w, n, halo_reqs=reqs)
+        if collect is not None:
+            # the attention output of the local keyframes sits in slots 1.. of the halo-extended buffer
+            collect[b_][0] = kfo_e.view(3, -1, blk.S, blk.D)[:, 1:]
+            collect[b_][1] += [outs] + ([rest] if rest is not None else [])
     return outs
+
+
+DUMP_CAP = 1 << 18      # elements per dumped array: 32 arrays of at most 1 MiB of float32
+
+
+def dump_outputs(path, rec):
+    """--dump-outputs: per block b the attention output (attn_bNN.npy) and the propagation outputs of all its chunks
+    (prop_bNN.npy, flattened in call order) of one step, float32.  A tensor above DUMP_CAP elements is flattened and
+    sampled at DUMP_CAP positions drawn with seed 16 * kind + b (kind 0 = attention, 1 = propagation): the same
+    positions for the same shapes, whichever build computed the values."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for b, (attn, props) in enumerate(rec):
+        for kind, (name, parts) in enumerate((("attn", [attn]), ("prop", props))):
+            if len(parts) == 1 and parts[0].numel() <= DUMP_CAP:
+                arr = parts[0].float()
+            else:
+                arr = torch.cat([t.reshape(-1).float() for t in parts])
+                if arr.numel() > DUMP_CAP:
+                    g = torch.Generator().manual_seed(16 * kind + b)
+                    pos = torch.randint(arr.numel(), (DUMP_CAP,), generator=g).sort().values
+                    arr = arr[pos.to(arr.device)]
+            np.save(os.path.join(path, "%s_b%02d.npy" % (name, b)), arr.cpu().numpy())
 
 
 def blend_w(n, dev):
@@ -698,7 +753,8 @@ def self_launch(args):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    os.execv(sys.executable, cmd)
+    # a fresh child process: this one has already asked the HIP runtime for its devices
+    sys.exit(subprocess.call(cmd))
 
 
 def cpu_leg(cfg, levels, full_l0=False):
@@ -796,19 +852,28 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def step(i, events=None, sh=None):
+    def step(i, events=None, sh=None, collect=None):
         return run_step(cfg, input_sets[i % n_sets], sh or shard, i % 2 == 0, w, events, exchange=exchange,
-                        per_chunk=args.per_chunk)
+                        per_chunk=args.per_chunk, collect=collect)
 
+    def step_rec(i):
+        rec = []
+        step(i, collect=rec)
+        return rec
+
+    dump = args.dump_outputs is not None
     for i in range(args.warmup):
-        step(i)
+        # --dump-outputs: the last warm-up step holds on to its outputs as the last timed step will, so the allocator
+        # has that memory cached before the timed region
+        step(i, collect=[] if dump and i == args.warmup - 1 else None)
     graphs = None
     if use_graph:
         from tokenflow_amd.graphs import GraphCache
         graphs = GraphCache(warmup=0)
         for i in range(max(2, n_sets)):   # capture every (input set, injection state) before the timed region
-            graphs.run(("step", i % max(2, n_sets)), lambda i=i: step(i))
+            graphs.run(("step", i % max(2, n_sets)), lambda i=i: step_rec(i) if dump else step(i))
     events, marks = [], []
+    last = None                          # --dump-outputs: per block (attention output, propagation outputs)
     barrier()
     t0 = time.perf_counter()
     for i in range(args.steps):
@@ -816,14 +881,17 @@ def main():
         m.record()
         marks.append(m)
         if use_graph:
-            graphs.run(("step", i % max(2, n_sets)), None)
+            last = graphs.run(("step", i % max(2, n_sets)), None)
         else:
-            step(i, events)
+            last = [] if dump and i == args.steps - 1 else None
+            step(i, events, collect=last)
     m = torch.cuda.Event(enable_timing=True)
     m.record()
     marks.append(m)
     barrier()
     elapsed = time.perf_counter() - t0
+    if dump and rank == 0 and last is not None:
+        dump_outputs(args.dump_outputs, last)
     if world > 1:
         t = torch.tensor([elapsed], device="cpu" if hip_comm is not None else dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -936,20 +1004,21 @@ def main():
     }
     if plain is not None and dual is not None:
         out["roofline_inject"] = dual
+    full = world == 1 and args.full     # the legs beyond the headline: --full only
     if rank == 0:
-        if world == 1 and not args.no_parity:
+        if full and not args.no_parity:
             out["parity"] = parity_check(cfg, blocks, w)
-        if world == 1 and not args.no_parity:
+        if full and not args.no_parity:
             out["roofline_other"] = other_rooflines(cfg, blocks, w, events)
-        if world == 1 and not args.no_other_configs and args.config == "cfg2":
+        if full and not args.no_other_configs and args.config == "cfg2":
             del input_sets[1:]              # the rotating input sets are no longer needed: room for the cfg4 / cfg5 tensors
             torch.cuda.empty_cache()
             out.setdefault("roofline_other", []).extend(other_config_rooflines(dev))
             out["other_configs"] = other_config_steps(dev, lambda n: blend_w(n, dev))
-        if world == 1 and not args.no_yardstick:
+        if full and not args.no_yardstick:
             out["yardstick"] = yardstick(cfg)
             out["yardstick"]["power_state"] = power_state(blocks)
-        if world == 1 and not args.no_cpu_baseline:
+        if full and not args.no_cpu_baseline:
             lv = [int(x) for x in args.cpu_sample_levels.split(",") if x != ""]
             out["cpu_baseline"] = cpu_leg(cfg, lv)
         print(json.dumps(out), flush=True)

@@ -33,6 +33,9 @@ Fixtures
                  runnable stand-in UNet (tests/driver_seam.py), 3 timesteps (q/k + feature injection, feature
                  injection only, none): the hook-call trace, the `pivotal_idx` draws, the UNet's noise prediction
                  and every transformer block's output of every UNet call, the latents after each step.
+  driver_cut.pt  the same driver methods over THIS repository's drop-in hooks with the oracle-backed fp32 ops: the
+                 run the restated driver of tests/driver_seam.py must reproduce where the reference is absent
+                 (`python oracle/make_golden.py driver_cut` writes this file alone).
   adazero.pt     TokenFlowBlock.forward on an AdaLayerNormZero block (use_ada_layer_norm_zero:
                  gate_msa on the cached / selected attention outputs, 362-366; scale/shift/gate
                  on the feed-forward, 417-424): pivotal pass and chunks 0..K-1.
@@ -273,7 +276,45 @@ def gen_driver(tfu):
     return out
 
 
+CUT_STRIDES = dict(x=31, unet=61, block=4999)
+
+
+def gen_driver_cut():
+    """The verbatim driver methods over THIS repository's drop-in hooks with the oracle-backed fp32 ops
+    (tests/fake_ops.py) -- the run tests/test_driver_seam.py::test_restated_driver_equals_the_verbatim_cut holds the
+    restated driver to.  Digests with wider strides than driver.pt's (CUT_STRIDES) keep the fixture small."""
+    import tempfile
+    import warnings
+    import tokenflow_utils as dropin
+    from oracle import driver_cut
+    from tests import driver_seam as ds
+    from tests.fake_ops import FakeOps
+    from tokenflow_amd import hooks
+    saved, hooks.ops = hooks.ops, FakeOps(round16=False)
+    out = {}
+    try:
+        for kind in ("pnp", "sdedit"):
+            log = []
+            methods = driver_cut.load_reference_driver(kind, ds.traced(dropin, log))
+            with tempfile.TemporaryDirectory() as d, warnings.catch_warnings():
+                warnings.simplefilter("ignore")
+                rec = ds.run_driver(kind, methods, d, keep_tensors=True)
+            for s in rec["steps"]:
+                s["x"] = digest(s["x"], CUT_STRIDES["x"])
+                for c in s["calls"]:
+                    c["unet"] = digest(c["unet"], CUT_STRIDES["unet"])
+                    c["blocks"] = [digest(b, CUT_STRIDES["block"]) for b in c["blocks"]]
+            rec["trace"] = log
+            out[kind] = rec
+    finally:
+        hooks.ops = saved
+    return out
+
+
 def main():
+    if sys.argv[1:] == ["driver_cut"]:       # this fixture alone
+        torch.save(gen_driver_cut(), os.path.join(GOLDEN, "driver_cut.pt"))
+        return
     tfu, util = ref_loader.load()
     os.makedirs(GOLDEN, exist_ok=True)
     torch.save(gen_attn_core(tfu), os.path.join(GOLDEN, "attn_core.pt"))
@@ -282,6 +323,7 @@ def main():
     torch.save(gen_adazero(tfu), os.path.join(GOLDEN, "adazero.pt"))
     torch.save(gen_inversion(), os.path.join(GOLDEN, "inversion.pt"))
     torch.save(gen_driver(tfu), os.path.join(GOLDEN, "driver.pt"))
+    torch.save(gen_driver_cut(), os.path.join(GOLDEN, "driver_cut.pt"))
     for f in sorted(os.listdir(GOLDEN)):
         print(f, os.path.getsize(os.path.join(GOLDEN, f)) // 1024, "KiB")
 

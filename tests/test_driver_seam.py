@@ -8,7 +8,8 @@ THIS repository's `tokenflow_utils`:
 * on the CPU with the oracle-backed ops (`-m "not gpu"`): same hook-call trace, same `pivotal_idx` draws, every block
   output / noise prediction / latent within fp32 re-association distance of the golden;
 * the restated driver of tests/driver_seam.py (what the GPU box runs, where /root/reference does not exist) is proven
-  equal to the verbatim cut: same trace, same draws, same bits (build container only);
+  equal to the verbatim cut: same trace, same draws, same bits where the reference is mounted, and held to the cut's
+  recorded run (tests/golden/driver_cut.pt) everywhere;
 * on the GPU (`-m gpu`) over the HIP kernels.
 """
 import warnings
@@ -83,21 +84,34 @@ def test_driver_over_dropin_hooks_matches_reference_golden_cpu(kind, tmp_path, m
     print(f"driver seam cpu {kind} ({which}): worst fraction of range {worst}")
 
 
-@pytest.mark.skipif(not ref_loader.available(), reason="/root/reference not mounted")
+# the recorded cut against a run on another host: fp32 re-association of that host's CPU kernels, as a fraction of range
+# (1.6e-6 measured between two hosts; the hooks-against-hooks bound above is 2e-5)
+CUT_TOL = 1e-5
+
+
 @pytest.mark.parametrize("kind", KINDS)
 def test_restated_driver_equals_the_verbatim_cut(kind, tmp_path, monkeypatch):
     """The restatement the GPU box runs IS the reference driver as far as the hooks can tell: same calls in the same
-    order with the same argument types and values, same `pivotal_idx`, bit-equal tensors."""
+    order with the same argument types and values, same `pivotal_idx`, bit-equal tensors.  Where the reference is
+    mounted the two run side by side; everywhere the restatement is also held to the cut's recorded run
+    (tests/golden/driver_cut.pt, oracle/make_golden.py::gen_driver_cut): the same trace and draws exactly, every
+    tensor within CUT_TOL of range of the recorded digests."""
     monkeypatch.setattr(hooks, "ops", FakeOps(round16=False))
-    log_v, log_r = [], []
-    rec_v = _run(kind, _methods(kind, log_v)[0], tmp_path, keep_tensors=True)
+    log_r = []
     rec_r = _run(kind, _methods(kind, log_r, prefer_verbatim=False)[0], tmp_path, keep_tensors=True)
-    assert log_v == log_r
-    for sv, sr in zip(rec_v["steps"], rec_r["steps"]):
-        assert torch.equal(sv["x"], sr["x"])
-        for cv, cr in zip(sv["calls"], sr["calls"]):
-            assert torch.equal(cv["indices"], cr["indices"]) and torch.equal(cv["unet"], cr["unet"])
-            assert all(torch.equal(a, b) for a, b in zip(cv["blocks"], cr["blocks"]))
+    if ref_loader.available():
+        log_v = []
+        rec_v = _run(kind, _methods(kind, log_v)[0], tmp_path, keep_tensors=True)
+        assert log_v == log_r
+        for sv, sr in zip(rec_v["steps"], rec_r["steps"]):
+            assert torch.equal(sv["x"], sr["x"])
+            for cv, cr in zip(sv["calls"], sr["calls"]):
+                assert torch.equal(cv["indices"], cr["indices"]) and torch.equal(cv["unet"], cr["unet"])
+                assert all(torch.equal(a, b) for a, b in zip(cv["blocks"], cr["blocks"]))
+    cut = load_golden("driver_cut.pt")[kind]
+    assert log_r == cut["trace"], "hook-call trace differs from the recorded verbatim cut's"
+    worst = _compare(rec_r, cut, CUT_TOL, CUT_TOL, CUT_TOL, f"{kind}/restated vs recorded cut")
+    print(f"restated driver {kind} vs recorded verbatim cut: worst fraction of range {worst}")
 
 
 def _tensor_compare(rec, ref, tol, what):

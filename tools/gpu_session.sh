@@ -171,9 +171,9 @@ for stage in "$@"; do
     rankstep)   timeout 600 python tools/rank_step_microbench.py --native --only split,auto > $O/rank_step_native.txt 2>&1; tail -14 $O/rank_step_native.txt
                 timeout 300 python tools/rank_step_microbench.py --native --only split,auto --no-copies --no-levels > $O/rank_step_native_nocopies.txt 2>&1; tail -3 $O/rank_step_native_nocopies.txt
                 timeout 300 python tools/rank_step_microbench.py --native --only onepass,auto --no-levels > $O/rank_step_native_onepass.txt 2>&1; tail -3 $O/rank_step_native_onepass.txt ;;
-    bench)      timeout 900 python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; python -c "import json;d=json.load(open('$O/bench.json'));print(d['ms_per_step'],d['value'],d['roofline']['frac'],d.get('parity',{}).get('attn_linf'),[ (l['attn_linf'],l['attn_linf_fp32_out']) for l in d.get('parity',{}).get('by_level',[])])" ;;
-    benchquick) timeout 600 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-yardstick > $O/bench_quick.json 2> $O/bench_quick.err; python -c "import json;d=json.load(open('$O/bench_quick.json'));print(d['ms_per_step'],d['value'],d['roofline']['frac'],[ (l['attn_linf'],l['attn_linf_fp32_out']) for l in d.get('parity',{}).get('by_level',[])])" ;;
-    cfg1)       timeout 600 python bench.py --config cfg1 --steps 50 --warmup 10 --no-cpu-baseline --no-yardstick > $O/bench_cfg1.json 2> $O/bench_cfg1.err; python -c "import json;d=json.load(open('$O/bench_cfg1.json'));print('cfg1',d['ms_per_step'],[ (l['attn_linf'],l['attn_linf_fp32_out']) for l in d.get('parity',{}).get('by_level',[])])"
+    bench)      timeout 900 python bench.py --steps 20 --warmup 5 --full > $O/bench.json 2> $O/bench.err; python -c "import json;d=json.load(open('$O/bench.json'));print(d['ms_per_step'],d['value'],d['roofline']['frac'],d.get('parity',{}).get('attn_linf'),[ (l['attn_linf'],l['attn_linf_fp32_out']) for l in d.get('parity',{}).get('by_level',[])])" ;;
+    benchquick) timeout 600 python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-yardstick > $O/bench_quick.json 2> $O/bench_quick.err; python -c "import json;d=json.load(open('$O/bench_quick.json'));print(d['ms_per_step'],d['value'],d['roofline']['frac'],[ (l['attn_linf'],l['attn_linf_fp32_out']) for l in d.get('parity',{}).get('by_level',[])])" ;;
+    cfg1)       timeout 600 python bench.py --config cfg1 --steps 50 --warmup 10 --full --no-cpu-baseline --no-yardstick > $O/bench_cfg1.json 2> $O/bench_cfg1.err; python -c "import json;d=json.load(open('$O/bench_cfg1.json'));print('cfg1',d['ms_per_step'],[ (l['attn_linf'],l['attn_linf_fp32_out']) for l in d.get('parity',{}).get('by_level',[])])"
                 timeout 600 python bench.py --config cfg1 --steps 50 --warmup 10 --graph --no-cpu-baseline --no-yardstick --no-parity > $O/bench_cfg1_graph.json 2> $O/bench_cfg1_graph.err; python -c "import json;d=json.load(open('$O/bench_cfg1_graph.json'));print('cfg1 graph',d['ms_per_step'])" ;;
     proxy)      timeout 300 tools/ubench/attn_loop_proxy > $O/attn_loop_proxy.txt 2>&1; cat $O/attn_loop_proxy.txt ;;
     ranktimeline) rm -rf /tmp/rt; ( cd /tmp && timeout 600 rocprofv3 --kernel-trace --memory-copy-trace -d /tmp/rt -- python $GRAFT_REPO_ROOT/tools/rank_step_microbench.py --native --only split,auto --reps 6 --no-levels > /dev/null 2>$GRAFT_REPO_ROOT/$O/ranktimeline.err )
@@ -188,7 +188,7 @@ for stage in "$@"; do
                 head -3 $O/pmc_attn_FETCH_SIZE.csv | cut -c1-200 ;;
     cfg1trace)  rm -rf /tmp/kt1; ( cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/kt1 -- python $GRAFT_REPO_ROOT/bench.py --config cfg1 --no-cpu-baseline --no-parity --no-yardstick --steps 40 --warmup 5 > /dev/null 2>&1 )
                 python tools/rocpd_stats.py $(find /tmp/kt1 -name "*_results.db" | head -1) > $O/cfg1_kernel_stats.csv; head -30 $O/cfg1_kernel_stats.csv | cut -c1-190 ;;
-    othercfgs)  for cfg in cfg4 cfg5; do timeout 600 python bench.py --config $cfg --no-cpu-baseline --no-yardstick --steps 3 --warmup 1 > $O/bench_$cfg.json 2>$O/bench_$cfg.err; python -c "import json;d=json.load(open('$O/bench_$cfg.json'));print('$cfg',d['ms_per_step'],d['parity']['attn_linf'],d['parity']['attn_linf_fp32_out'],d['parity']['nn_mismatch_rate'])"; done ;;
+    othercfgs)  for cfg in cfg4 cfg5; do timeout 600 python bench.py --config $cfg --full --no-cpu-baseline --no-yardstick --steps 3 --warmup 1 > $O/bench_$cfg.json 2>$O/bench_$cfg.err; python -c "import json;d=json.load(open('$O/bench_$cfg.json'));print('$cfg',d['ms_per_step'],d['parity']['attn_linf'],d['parity']['attn_linf_fp32_out'],d['parity']['nn_mismatch_rate'])"; done ;;
     hooks)      for a in "" "--graph" "--graph --all-chunks"; do timeout 600 python tools/hooks_bench.py cfg2 6 $a >> $O/hooks_bench.txt 2>/dev/null; done
                 for a in "--ranks 8" "--ranks 8 --wire-less" "--ranks 8 --graph" "--ranks 8 --wire-less --graph"; do timeout 600 python tools/hooks_bench.py cfg2 10 $a >> $O/hooks_bench.txt 2>>$O/hooks_bench.err; done; cat $O/hooks_bench.txt ;;
     hookranks)  for a in "--ranks 8" "--ranks 8 --wire-less" "--ranks 8 --graph" "--ranks 8 --wire-less --graph"; do timeout 600 python tools/hooks_bench.py cfg2 10 $a >> $O/hooks_ranks.txt 2>>$O/hooks_ranks.err; done; cat $O/hooks_ranks.txt; grep -v amdgpu.ids $O/hooks_ranks.err | tail -20 ;;
