@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define TF_ABI_VERSION 7
+#define TF_ABI_VERSION 8
 
 /* Every entry point below is exported with default visibility; the library itself is built with -fvisibility=hidden, so
  * its exported symbols are exactly the declarations of this header (checked by tests/test_hooks_cpu.py). */
@@ -58,7 +58,10 @@ extern "C" {
 #define TF_ATTN_PRECISE_P (1 << 15)                  /* fused kernel, bf16: carry P as hi + lo whatever the size */
 #define TF_ATTN_NO_PRECISE_P (1 << 16)               /* fused kernel: P in one 16-bit value whatever the size */
 #define TF_ATTN_HINT_MIX (1 << 18)                   /* Dh = 40 streaming kernel: the mixed-MFMA-shape form whatever the launch size (it is the
-                                                        default for launches of >= 1024 workgroups outside the bit-stable mode); tests, measurements */
+                                                        default for launches of >= 1024 workgroups outside the bit-stable mode) wherever the
+                                                        frames admit the interleaved kernel, S % 64 == 0 and S >= 256 (a no-op on ragged
+                                                        frames); it applies to the ALL launch and to the SOURCE launch beside the dual-V
+                                                        kernel; tests, measurements */
 
 /* argument errors */
 #define TF_ERR_NULL (-1)
@@ -142,6 +145,19 @@ TF_API int tf_ext_attn_fwd_strided(const void* q, const void* k, const void* v, 
                             int K, int Kq, int q_frame0, int S, int H, int Dh, int64_t ld, const int64_t* strides,
                             float scale, int inject, int dtype, void* ws, size_t ws_bytes, void* stream);
 
+/* Launch plan of tf_ext_attn_fwd for dense tensors of this shape and these flags (host only: touches no device,
+ * allocates nothing; computed by the launch code itself, not by a model of it).  Returns the number of launches, or a
+ * TF_ERR_* (TF_ERR_WORKSPACE: `buf` is too small).  buf receives one ';'-separated token per launch in launch order,
+ * naming the kernel and its template parameters:
+ *   vt_pack                          the V^T pre-pass
+ *   il<Dh,NW,MODE,MINW,DMA>          half-tile interleaved kernel (DMA 3: the Dh = 40 mixed-MFMA-shape form)
+ *   one<Dh,QT,NW,MODE,MINW,fqF[,kt128][,sb]>   one-tile streaming kernel
+ *   pp<Dh,MODE>                      ping-pong kernel
+ *   merge[nseg=N]                    merge of the split form's N partial results
+ *   fused[qw=.,kw=.,qb=.,prec=.]     fused small-problem kernel
+ * MODE is ALL, DUAL or SOURCE. */
+TF_API int tf_ext_attn_plan(int K, int Kq, int S, int H, int Dh, int flags, int dtype, char* buf, size_t len);
+
 /* ------------------------------------------------------------------------
  * Frames <-> heads re-sharding of the multi-GPU pivotal pass (no counterpart in the single-process reference;
  * tokenflow_amd/sharded.py).  Rank r sends head group w of its Kl keyframes' slabs to rank w:
@@ -184,6 +200,12 @@ TF_API size_t tf_nn_search_workspace_bytes(int64_t n_tgt, int S, int D, int P);
 TF_API int tf_nn_search(const void* tgt, const void* piv, const float* inv_norm, int32_t* idx,
                  int64_t n_tgt, int S, int D, int P, int kf0, int kf1, int dtype,
                  void* ws, size_t ws_bytes, void* stream);
+
+/* Launch plan of tf_nn_search (C = 1) or of the search launches of tf_nn_gather_blend_chunks over C > 1 chunks of
+ * n_tgt targets (P = 2; the gather merges the splits itself, no finalize).  Host only, as tf_ext_attn_plan.  Tokens:
+ *   rb / rbs<TJ=2|4> / rbg<TT=1|2> / glds / wide / bk64 / bk128 / deep, each followed by [splits=N] (",chunks" added
+ *   when C > 1), and finalize (the merge of the per-split candidates of tf_nn_search). */
+TF_API int tf_nn_search_plan(int64_t n_tgt, int S, int D, int P, int C, char* buf, size_t len);
 
 /* ------------------------------------------------------------------------
  * Gather + blend + residual  --  replaces tokenflow_utils.py:362-397

@@ -655,8 +655,9 @@ def test_head_pack_unpack(W, Kl, S, D, dtype):
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("gain", [0.0, 3.0, 12.0])
 def test_ext_attn_interleaved_form_full_oracle(dtype, gain):
-    """ext_attn_il40_kernel (Dh = 40, fp32 scaling, grids of >= 768 workgroups, S % 64 == 0: the cfg2 level-0 form)
-    against the full oracle, K = 4 x S = 2048 x 8 heads.  gain > 0 plants spikes (one strongly aligned key per
+    """The Dh = 40 interleaved kernel in its LDS-DMA form (il<40,8,ALL,4,2>: fp32 scaling, grids of >= 256 eight-wave
+    workgroups, S % 64 == 0; 768 here, below the 1024 from which the mixed-shape form is the default) against the full
+    oracle, K = 4 x S = 2048 x 8 heads, without injection (the injected forms: tests/test_kernel_forms_gpu.py).  gain > 0 plants spikes (one strongly aligned key per
     query, in LATE tiles of the bank): gain 3 keeps the score bound tight enough that no half tile looks at its
     maximum, gain 12 breaks it so that the deferred shift moves in the middle of the software pipeline -- the
     half tile whose P.V runs beside that softmax was exponentiated against the OLD shift and must be rescaled
@@ -675,6 +676,7 @@ def test_ext_attn_interleaved_form_full_oracle(dtype, gain):
     q, k, v = rnd(q), rnd(k), rnd(v)
     refs = attn_ref(q, k, v, h, d ** -0.5, False, need_sigma=False)
     dq, dk, dv = (t.to(dtype).cuda() for t in (q, k, v))
+    assert ops.attn_plan(K, K, S, h, d, False, dtype=dtype) == ["vt_pack", "il<40,8,ALL,4,2>"]
     out = ops.ext_attn(dq, dk, dv, h, d ** -0.5, False)
     assert bool(torch.isfinite(out.float()).all())
     assert_attn_close(out, refs, f"interleaved gain={gain} {dtype}", dtype=dtype)

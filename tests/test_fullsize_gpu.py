@@ -246,7 +246,7 @@ def test_nn_search_lds_dma_kernel(n, S, D, ids, flavour, dtype):
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
 def test_nn_search_two_target_tile_kernel_ragged(dtype):
-    """A D = 320 search that takes `nn_search_rbg_kernel<.., 2>` (round 6: two 32-target tiles per wave, >= 1024 workgroups of
+    """A D = 320 search that takes `nn_search_rbs_kernel` with four target tiles (rbs<TJ=4>: two 32-target tiles per wave, >= 1024 workgroups of
     256 targets, >= 24 pivot tiles per workgroup) with a RAGGED last target panel (65 856 = 257.25 panels) and a pivot range
     split over two workgroups (49 tiles -> 25 + 24): every row of the last two panels and 2 048 sampled rows against the fp32
     oracle, tie-aware; exact-duplicate pivots: the first index wins; and bit-identical to the one-tile kernel
@@ -258,6 +258,7 @@ def test_nn_search_two_target_tile_kernel_ragged(dtype):
     ln = torch.nn.functional.layer_norm
     piv = ln(torch.randn(2, S, D, generator=g, device="cuda"), (D,)).to(dtype)
     tgt = ln(torch.randn(n * S, D, generator=g, device="cuda"), (D,)).to(dtype)
+    assert ops.nn_plan(n * S, S, D, 2) == ["rbs<TJ=4>[splits=2]", "finalize"]
     piv[:, S - 9] = piv[:, 11]
     tgt[-64:] = piv[1, 11].float().to(dtype)            # in the ragged last panel
     inv = ops.pivot_inv_norm(piv)

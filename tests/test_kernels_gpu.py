@@ -120,8 +120,9 @@ def test_ext_attn_vs_oracle_and_golden(name, dtype, fused, golden_attn):
 
 @pytest.mark.parametrize("K,S,h,d", [(2, 256, 2, 40), (3, 136, 2, 64), (2, 200, 1, 80), (1, 16, 2, 160),
                                      (4, 64, 8, 40), (13, 64, 2, 64),
-                                     # S >= 512 at Dh = 64 takes the ping-pong kernel: one tile, odd / even tile
-                                     # counts, ragged last tile, several keyframes
+                                     # S >= 512 at Dh = 64: the interleaved kernel where S % 64 == 0 (512, 576, 640),
+                                     # the ping-pong kernel on ragged frames (520, 515) without injection in one pass;
+                                     # one tile, odd / even tile counts, ragged last tile, several keyframes
                                      (1, 512, 1, 64), (2, 576, 2, 64), (2, 520, 1, 64), (3, 640, 2, 64),
                                      # S >= 256 at Dh = 40 / 80: 8-wave geometry and the dual (shared-softmax) form
                                      (2, 328, 2, 40), (2, 264, 1, 80),
@@ -254,7 +255,9 @@ def test_ext_attn_mixed_mfma_shapes(K, S, h, dtype, gain):
     take it (the full-size tests and bench.py's parity leg); TF_ATTN_HINT_MIX forces it here on small grids: N(0,1) and
     peaked logits (the deferred shift moves in late tiles: O rescaled through the row swap), plain and q/k-injected (the
     source launch in the mixed form beside the dual-V kernel), one-pass and split (the partial results' layout), bf16 and
-    f16, against the oracle -- and against the non-mixed kernel within the same bound."""
+    f16, against the oracle -- and against the non-mixed kernel within the same bound.  The hint opens the interleaved
+    kernel on any grid whose frames admit it (S % 64 == 0, S >= 256), so every configuration here runs the mixed form:
+    its launch plan is asserted first."""
     ops = _ops()
     from tokenflow_amd import _lib
     d = 40
@@ -270,6 +273,9 @@ def test_ext_attn_mixed_mfma_shapes(K, S, h, dtype, gain):
     for inject in (False, True):
         refs = attn_ref(q, k, v, h, d ** -0.5, inject)
         for no_split in (True, False):
+            plan = ops.attn_plan(K, K, S, h, d, inject, dtype=dtype, no_split=no_split, fused=False,
+                                 hints=_lib.TF_ATTN_HINT_MIX)
+            assert ("il<40,8,SOURCE,4,3>" if inject else "il<40,8,ALL,4,3>") in plan, plan
             out = ops.ext_attn(dq, dk, dv, h, d ** -0.5, inject, fused=False, no_split=no_split, hints=_lib.TF_ATTN_HINT_MIX)
             assert torch.isfinite(out.float()).all()
             assert_attn_close(out, refs, f"mixed shapes K{K} S{S} h{h} {dtype} gain={gain} inject={inject} no_split={no_split}",
@@ -280,6 +286,8 @@ def test_ext_attn_mixed_mfma_shapes(K, S, h, dtype, gain):
     if gain == 0.0 and S >= 576:
         refs = attn_ref(q, k, v, h, d ** -0.5, False)
         for hints in (0, _lib.TF_ATTN_HINT_MIX):
+            plan = ops.attn_plan(K, K, S, h, d, False, dtype=dtype, fused=False, out_dtype=torch.float32, hints=hints)
+            assert ("il<40,8,ALL,4,3>" in plan) == bool(hints), plan
             o32 = ops.ext_attn(dq, dk, dv, h, d ** -0.5, False, fused=False, out_dtype=torch.float32, hints=hints)
             assert float((o32.cpu() - refs[0]).abs().max()) < 1e-3
 

@@ -12,7 +12,7 @@ TF_ATTN_OUT_F32 = 32
 TF_ATTN_FOLD_SCALE = 64
 TF_ATTN_NO_FUSED, TF_ATTN_FUSED = 128, 1 << 17
 TF_ATTN_HINT_QB2, TF_ATTN_PRECISE_P, TF_ATTN_NO_PRECISE_P = 1 << 14, 1 << 15, 1 << 16
-TF_ATTN_HINT_MIX = 1 << 18   # Dh = 40 streaming kernel: the mixed-MFMA-shape form whatever the launch size
+TF_ATTN_HINT_MIX = 1 << 18   # Dh = 40 streaming kernel: the mixed-MFMA-shape form whatever the launch size (S % 64 == 0, S >= 256)
 
 
 def attn_hint(qw: int = 0, kw: int = 0, qb: int = 1) -> int:
@@ -22,7 +22,7 @@ def attn_hint(qw: int = 0, kw: int = 0, qb: int = 1) -> int:
     return (code[qw] << 8) | (code[kw] << 11) | (TF_ATTN_HINT_QB2 if qb == 2 else 0)
 
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 TF_RANK_HEADS, TF_RANK_BANK, TF_RANK_SLOTS, TF_RANK_NO_HALO, TF_RANK_INV_NORM = 0, 1, 64, 16, 32
 TF_ERR_COMM = -6
 
@@ -31,6 +31,9 @@ _SIGNATURES = {
     "tf_abi_version": (_c.c_int, []),
     "tf_last_error": (_c.c_char_p, []),
     "tf_ext_attn_workspace_bytes": (_c.c_size_t, [_c.c_int] * 5),
+    # launch plans (host only: no device, no allocation; tests/test_kernel_plan_cpu.py)
+    "tf_ext_attn_plan": (_c.c_int, [_c.c_int] * 7 + [_c.c_char_p, _c.c_size_t]),
+    "tf_nn_search_plan": (_c.c_int, [_c.c_int64] + [_c.c_int] * 4 + [_c.c_char_p, _c.c_size_t]),
     "tf_ext_attn_fwd": (_c.c_int, [_c.c_void_p] * 4 + [_c.c_int] * 6 + [_c.c_int64, _c.c_float, _c.c_int, _c.c_int,
                                    _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "tf_ext_attn_fwd_strided": (_c.c_int, [_c.c_void_p] * 4 + [_c.c_int] * 6 + [_c.c_int64, _c.c_void_p, _c.c_float,

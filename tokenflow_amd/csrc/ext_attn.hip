@@ -66,6 +66,7 @@ struct AttnCfg {
 };
 
 enum { MODE_ALL = 0, MODE_SOURCE = 1, MODE_DUAL = 2 };
+static inline const char* mode_name(int mode) { return mode == MODE_ALL ? "ALL" : mode == MODE_DUAL ? "DUAL" : "SOURCE"; }
 
 // Head dims whose streaming kernels use the Cauchy-Schwarz score bound |q.k| <= |q| max|k| (per-block key norms from the
 // pre-pass) to skip the per-tile maximum: Dh = 40 since round 2, Dh = 64 since round 6 (A/B switch TF_TUNE_NO_BOUND64).
@@ -90,7 +91,8 @@ struct AttnParams {
     int out_f32;       // TF_ATTN_OUT_F32: `out` is float (the normalised fp32 accumulator, no 16-bit rounding)
     int nseg;          // > 1: every bank problem is split into nseg runs of bank frames (small grids, see split_plan)
     int bit_stable;    // TF_ATTN_NO_SPLIT: kernel choice and arithmetic are functions of the shape alone
-    int mix;           // TF_ATTN_HINT_MIX: the mixed-MFMA-shape form (Dh = 40) whatever the launch size
+    int mix;           // TF_ATTN_HINT_MIX: the mixed-MFMA-shape form (Dh = 40) whatever the launch size, where the frames
+                       // admit the interleaved kernel (S % 64 == 0, S >= 256); no effect on ragged frames
     float* partials;   // [2 banks][Kq][H][S][nseg][Dh + 8] fp32: unnormalised O, l, log2-domain shift  // K bank frames; queries = frames q_frame0 .. +Kq
     int64_t ld;      // token stride of k and v
     int64_t ld_q;    // token stride of q (its own: a rank's q may be a column slab of the fused projection while the
@@ -2026,6 +2028,7 @@ int launch_il(AttnParams p, hipStream_t st) {
     constexpr size_t lds = DMA == 1            ? 2 * (size_t)(64 * DH + C::MT * 32 * 64) * 2 + 16   // dense images (+ the K over-read)
                            : MODE == MODE_DUAL ? 2 * (size_t)(C::K_ELEMS + ((2 * DH + 31) / 32) * 32 * C::VROW) * 2   // packed dual-V image
                                                : C::lds_bytes(1);
+    if (tf_plan_note("il<%d,%d,%s,%d,%d>", DH, NW, mode_name(MODE), MINW, DMA)) return 0;
     auto kern = ext_attn_il_kernel<T, DH, NW, MODE, MINW, DMA>;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)lds);
@@ -2043,6 +2046,7 @@ template <typename T, int DH, int MODE, int MINW>
 int launch_pp(AttnParams p, hipStream_t st) {
     typedef AttnCfg<DH, 64> C;
     constexpr size_t lds = C::lds_bytes(1);
+    if (tf_plan_note("pp<%d,%s>", DH, mode_name(MODE))) return 0;
     auto kern = ext_attn_pp_kernel<T, DH, MODE, MINW>;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)lds);
@@ -2060,6 +2064,9 @@ int launch_one(AttnParams p, hipStream_t st) {
     typedef AttnCfg<DH, KT> C;
     constexpr size_t lds = ((MODE == MODE_DUAL && DH == 40) ? 2 * (size_t)(C::K_ELEMS + 96 * C::VROW) * 2   // PACK
                                                              : C::lds_bytes(MODE == MODE_DUAL ? 2 : 1)) / (SB ? 2 : 1);
+    if (tf_plan_note("one<%d,%d,%d,%s,%d,fq%d%s%s>", DH, QT, NW, mode_name(MODE), MINW, FQ ? 1 : 0, KT != 64 ? ",kt128" : "",
+                     SB ? ",sb" : ""))
+        return 0;
     auto kern = ext_attn_kernel<T, DH, QT, NW, MODE, MINW, KT, FQ, SB>;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)lds);
@@ -2088,11 +2095,13 @@ int launch_attn(const AttnParams& p, const void* v, hipStream_t st) {
         const size_t lds = (size_t)64 * (DH + 2) * sizeof(E);
         // the Dh = 40 kernels also need the key norm bounds (score bound, see BOUND)
         const bool bound = attn_has_bound(DH);
-        hipLaunchKernelGGL(vt_pack_kernel<T>, grid, dim3(256), lds, st, reinterpret_cast<const E*>(v),
-                           reinterpret_cast<E*>(const_cast<void*>(p.vt)),
-                           bound ? reinterpret_cast<const E*>(p.k) : nullptr, const_cast<float*>(p.knorm2),
-                           p.inject, b_lo * p.K, p.K, p.S, p.H, DH, p.Spad, p.ld, p.v_bs, p.v_fs, p.k_bs, p.k_fs);
-        TF_LAUNCH_CHECK("tf_ext_attn_fwd(vt_pack)");
+        if (!tf_plan_note("vt_pack")) {
+            hipLaunchKernelGGL(vt_pack_kernel<T>, grid, dim3(256), lds, st, reinterpret_cast<const E*>(v),
+                               reinterpret_cast<E*>(const_cast<void*>(p.vt)),
+                               bound ? reinterpret_cast<const E*>(p.k) : nullptr, const_cast<float*>(p.knorm2),
+                               p.inject, b_lo * p.K, p.K, p.S, p.H, DH, p.Spad, p.ld, p.v_bs, p.v_fs, p.k_bs, p.k_fs);
+            TF_LAUNCH_CHECK("tf_ext_attn_fwd(vt_pack)");
+        }
     }
     // Every head dim has three forms: ALL (one launch, bank problems then source problems), DUAL (injection:
     // uncond + cond share QK^T and the softmax; pays from S = 256 on) and SOURCE (the source branch alone).
@@ -2100,6 +2109,7 @@ int launch_attn(const AttnParams& p, const void* v, hipStream_t st) {
     // call is SOURCE alone.
     auto merge = [&]() -> int {   // split form: fold the per-run partial results into the output
         if (p.nseg <= 1) return 0;
+        if (tf_plan_note("merge[nseg=%d]", p.nseg)) return 0;
         const int64_t total = (int64_t)2 * p.Kq * p.H * p.S * (DH / 4);
         const int64_t blocks = (total + 255) / 256;
         hipLaunchKernelGGL(attn_merge_kernel<T>, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, st,
@@ -2127,9 +2137,10 @@ int launch_attn(const AttnParams& p, const void* v, hipStream_t st) {
 #define TF_TUNE_IL40_MIN_WGS 256   // one 8-wave workgroup per CU: a W = 8 rank's one-pass level 0 (384 workgroups) runs
 #endif                             // 586 us interleaved against 672 us in the plain 4-wave form (profiles/r03_rank_shard.txt)
 #ifndef TF_TUNE_NO_IL40
-            // half-tile interleaved form (ext_attn_il_kernel)
+            // half-tile interleaved form (ext_attn_il_kernel); TF_ATTN_HINT_MIX (p.mix) opens it on any grid its shape
+            // requirement admits, so that the mixed-shape form it selects below is taken whatever the launch size
             const bool il = p.S >= 256 && p.S % 64 == 0 &&
-                            (int64_t)3 * p.Kq * ((p.S + 255) / 256) * p.H * p.nseg >= TF_TUNE_IL40_MIN_WGS;
+                            (p.mix || (int64_t)3 * p.Kq * ((p.S + 255) / 256) * p.H * p.nseg >= TF_TUNE_IL40_MIN_WGS);
 #else
             const bool il = false;
 #endif
@@ -2424,6 +2435,26 @@ extern "C" int tf_ext_attn_fwd_strided(const void* q, const void* k, const void*
     p.c = (float)((double)scale * 1.4426950408889634);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     return dtype == TF_BF16 ? dispatch_dh<BF16>(Dh, p, v, st) : dispatch_dh<F16>(Dh, p, v, st);
+}
+
+// Launch plan of tf_ext_attn_fwd for dense tensors (ld = H*Dh): the entry point itself runs under the plan recorder
+// (csrc/tf_common.h), so the fused-kernel decision, the split plan and the kernel choice are the ones a real call makes.
+// The pointers it is given are placeholders: every launch is recorded instead of issued, nothing is dereferenced.
+extern "C" int tf_ext_attn_plan(int K, int Kq, int S, int H, int Dh, int flags, int dtype, char* buf, size_t len) {
+    TF_ARG(K > 0 && S > 0 && H > 0 && Kq > 0 && Kq <= K, TF_ERR_SHAPE, "tf_ext_attn_plan: K=%d Kq=%d S=%d H=%d", K, Kq, S,
+           H);
+    void* const ph = reinterpret_cast<void*>((uintptr_t)1 << 12);
+    const int64_t ld = (int64_t)H * Dh, fs = (int64_t)S * ld;
+    const int64_t strides[9] = {Kq * fs, fs, K * fs, fs, K * fs, fs, Kq * fs, fs, ld};
+    TfPlanRec rec{buf, len, 0, 0};
+    if (buf && len) buf[0] = 0;
+    tf_plan_rec = &rec;
+    const int rc = tf_ext_attn_fwd_strided(ph, ph, ph, ph, K, Kq, 0, S, H, Dh, ld, strides, 1.0f, flags,
+                                           dtype, ph, tf_ext_attn_workspace_bytes(K, S, H, Dh, dtype), nullptr);
+    tf_plan_rec = nullptr;
+    if (rc) return rc;
+    TF_ARG(rec.used < len, TF_ERR_WORKSPACE, "tf_ext_attn_plan: the plan needs %zu bytes", rec.used + 1);
+    return rec.n;
 }
 
 extern "C" int tf_ext_attn_fwd(const void* q, const void* k, const void* v, void* out, int K, int Kq, int q_frame0,

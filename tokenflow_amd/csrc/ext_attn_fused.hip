@@ -605,6 +605,7 @@ int launch_fused(const FusedParams& p, unsigned grid, hipStream_t st) {
     constexpr int NW = QW * KW;
     constexpr int STAGE_BYTES = KW * (C::K_ELEMS + 32 * C::VS) * 2;
     constexpr int lds = STAGE_BYTES > merge_bytes<NW, KW>() ? STAGE_BYTES : merge_bytes<NW, KW>();
+    if (tf_plan_note("fused[qw=%d,kw=%d,qb=1,prec=%d]", QW, KW, PREC ? 1 : 0)) return 0;
     auto kern = ext_attn_fused_kernel<T, DH, QW, KW, PREC>;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NW), lds, st, p);
@@ -617,6 +618,7 @@ int launch_fused_wp(const FusedParams& p, unsigned grid, hipStream_t st) {
     typedef FusedCfg<DH> C;
     constexpr int STAGE_BYTES = (KW * 32 * C::VS + (DH == 160 ? C::K_ELEMS : 0)) * 2;
     constexpr int lds = STAGE_BYTES > merge_bytes<KW, KW>() ? STAGE_BYTES : merge_bytes<KW, KW>();
+    if (tf_plan_note("fused[qw=1,kw=%d,qb=%d,prec=%d]", KW, QB, PREC ? 1 : 0)) return 0;
     auto kern = ext_attn_fused_wp_kernel<T, DH, KW, QB, PREC>;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * KW), lds, st, p);

@@ -1099,6 +1099,7 @@ static NnPlan nn_plan(int64_t n_tgt, int S, int D, int P, int C = 1) {
 }
 
 static int finalize(const NnPartial* part, int32_t* idx, int64_t total, int splits, hipStream_t st) {
+    if (tf_plan_note("finalize")) return 0;
     hipLaunchKernelGGL(nn_finalize_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, part, idx, total,
                        splits);
     TF_LAUNCH_CHECK("tf_nn_search(finalize)");
@@ -1116,6 +1117,9 @@ int launch_nn(const void* tgt, const void* piv, const float* inv_norm, int32_t* 
     const NnPlan pl = nn_plan(n_tgt, S, D, P, C);
     const int splits = pl.splits, tps = pl.tiles_per_split;
     dim3 grid((unsigned)(pl.panels * C), (unsigned)P, (unsigned)splits);
+    if (tf_plan_note("%s[splits=%d%s]", pl.kern == NN_WIDE ? "wide" : pl.kern == NN_DEEP ? "deep" : pl.kern == NN_BK128 ? "bk128" : "bk64",
+                     splits, C > 1 ? ",chunks" : ""))
+        return (fin && splits > 1) ? finalize(ws, idx, n_tgt * C * P, splits, st) : 0;
     auto kern = nn_search_kernel<T, WN, BK, TM>;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     const NnChunks ch{n_tgt, (int)pl.panels, first_single};
@@ -1134,6 +1138,7 @@ int launch_nn_glds(const void* tgt, const void* piv, const float* inv_norm, int3
     const NnPlan pl = nn_plan(n_tgt, S, D, P, C);
     const int splits = pl.splits, tps = pl.tiles_per_split;
     dim3 grid((unsigned)(pl.panels * C), (unsigned)P, (unsigned)splits);
+    if (tf_plan_note("glds[splits=%d%s]", splits, C > 1 ? ",chunks" : "")) return (fin && splits > 1) ? finalize(ws, idx, n_tgt * C * P, splits, st) : 0;
 #ifndef TF_TUNE_NN_NO_GLDS_SH
     auto kern = nn_search_glds_kernel<T, true>;    // short MFMAs (round 6, last session)
 #else
@@ -1160,6 +1165,7 @@ int launch_nn_rb(const void* tgt, const void* piv, const float* inv_norm, int32_
     if (pl.kern == NN_RB2) {   // 256-target panels, two target tiles per wave (the plan has checked S % 32 == 0)
         const size_t lds_g = 2 * 32 * D * 2 + 2 * 32 * 4;
 #ifndef TF_TUNE_NN_NO_RBS
+        if (tf_plan_note("rbs<TJ=4>[splits=%d%s]", splits, C > 1 ? ",chunks" : "")) return (fin && splits > 1) ? finalize(ws, idx, n_tgt * C * P, splits, st) : 0;
         // round 6, last session: the same kernel with short MFMAs (16x16x32), see nn_search_rbs_kernel
         hipLaunchKernelGGL((nn_search_rbs_kernel<T, DK>), grid, dim3(256), lds_g, st,
                            reinterpret_cast<const typename T::elem*>(tgt), reinterpret_cast<const typename T::elem*>(piv),
@@ -1167,6 +1173,7 @@ int launch_nn_rb(const void* tgt, const void* piv, const float* inv_norm, int32_
         TF_LAUNCH_CHECK("tf_nn_search");
         return (fin && splits > 1) ? finalize(ws, idx, n_tgt * C * P, splits, st) : 0;
 #endif
+        if (tf_plan_note("rbg<TT=2>[splits=%d%s]", splits, C > 1 ? ",chunks" : "")) return (fin && splits > 1) ? finalize(ws, idx, n_tgt * C * P, splits, st) : 0;
         hipLaunchKernelGGL((nn_search_rbg_kernel<T, DK, 2>), grid, dim3(256), lds_g, st,
                            reinterpret_cast<const typename T::elem*>(tgt), reinterpret_cast<const typename T::elem*>(piv),
                            inv_norm, idx, (splits > 1 || !fin) ? ws : nullptr, n_tgt * C, S, kf0, kf1, tps, ch);
@@ -1179,18 +1186,21 @@ int launch_nn_rb(const void* tgt, const void* piv, const float* inv_norm, int32_
     if (dma && S % 32 == 0) {
         const size_t lds_g = 2 * 32 * D * 2 + 2 * 32 * 4;
 #ifndef TF_TUNE_NN_NO_RBS
+        if (tf_plan_note("rbs<TJ=2>[splits=%d%s]", splits, C > 1 ? ",chunks" : "")) return (fin && splits > 1) ? finalize(ws, idx, n_tgt * C * P, splits, st) : 0;
         hipLaunchKernelGGL((nn_search_rbs_kernel<T, DK, 2>), grid, dim3(256), lds_g, st,
                            reinterpret_cast<const typename T::elem*>(tgt), reinterpret_cast<const typename T::elem*>(piv),
                            inv_norm, idx, (splits > 1 || !fin) ? ws : nullptr, n_tgt * C, S, kf0, kf1, tps, ch);
         TF_LAUNCH_CHECK("tf_nn_search");
         return (fin && splits > 1) ? finalize(ws, idx, n_tgt * C * P, splits, st) : 0;
 #endif
+        if (tf_plan_note("rbg<TT=1>[splits=%d%s]", splits, C > 1 ? ",chunks" : "")) return (fin && splits > 1) ? finalize(ws, idx, n_tgt * C * P, splits, st) : 0;
         hipLaunchKernelGGL((nn_search_rbg_kernel<T, DK>), grid, dim3(256), lds_g, st,
                            reinterpret_cast<const typename T::elem*>(tgt), reinterpret_cast<const typename T::elem*>(piv),
                            inv_norm, idx, (splits > 1 || !fin) ? ws : nullptr, n_tgt * C, S, kf0, kf1, tps, ch);
         TF_LAUNCH_CHECK("tf_nn_search");
         return (fin && splits > 1) ? finalize(ws, idx, n_tgt * C * P, splits, st) : 0;
     }
+    if (tf_plan_note("rb[splits=%d%s]", splits, C > 1 ? ",chunks" : "")) return (fin && splits > 1) ? finalize(ws, idx, n_tgt * C * P, splits, st) : 0;
     hipLaunchKernelGGL((nn_search_rb_kernel<T, DK>), grid, dim3(256), lds, st,
                        reinterpret_cast<const typename T::elem*>(tgt), reinterpret_cast<const typename T::elem*>(piv),
                        inv_norm, idx, (splits > 1 || !fin) ? ws : nullptr, n_tgt * C, S, kf0, kf1, tps, ch);
@@ -1236,6 +1246,21 @@ extern "C" int tf_pivot_inv_norm(const void* piv, float* inv_norm, int64_t rows,
                            reinterpret_cast<const _Float16*>(piv), inv_norm, rows, D);
     TF_LAUNCH_CHECK("tf_pivot_inv_norm");
     return 0;
+}
+
+// Launch plan of tf_nn_search (C = 1) or of the search launches of tf_nn_gather_blend_chunks (C > 1, P = 2): the real
+// dispatch under the plan recorder (csrc/tf_common.h).  No device, no allocation.
+extern "C" int tf_nn_search_plan(int64_t n_tgt, int S, int D, int P, int C, char* buf, size_t len) {
+    TF_ARG(n_tgt > 0 && S > 0 && D > 0 && D % 8 == 0 && (P == 1 || P == 2) && C >= 1 && (C == 1 || P == 2), TF_ERR_SHAPE,
+           "tf_nn_search_plan: n_tgt=%lld S=%d D=%d P=%d C=%d", (long long)n_tgt, S, D, P, C);
+    TfPlanRec rec{buf, len, 0, 0};
+    if (buf && len) buf[0] = 0;
+    tf_plan_rec = &rec;
+    const int rc = dispatch_nn<BF16>(nullptr, nullptr, nullptr, nullptr, nullptr, n_tgt, S, D, P, 0, 1, nullptr, C == 1, C, 0);
+    tf_plan_rec = nullptr;
+    if (rc) return rc;
+    TF_ARG(rec.used < len, TF_ERR_WORKSPACE, "tf_nn_search_plan: the plan needs %zu bytes", rec.used + 1);
+    return rec.n;
 }
 
 extern "C" size_t tf_nn_search_workspace_bytes(int64_t n_tgt, int S, int D, int P) {

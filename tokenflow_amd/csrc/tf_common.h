@@ -119,6 +119,20 @@ size_t tf_nn_partials_bytes(int64_t n_tgt, int S, int D, int P, int C = 1);
 // ---- host-side error plumbing ------------------------------------------------
 void tf_set_error(const char* fmt, ...);
 
+// ---- launch-plan recorder (tf_ext_attn_plan / tf_nn_search_plan) --------------
+// While a recorder is set on the calling thread, every launcher appends one token naming its kernel and template
+// parameters and returns 0 instead of launching (before hipFuncSetAttribute or any other runtime call): the plan
+// queries run the real dispatch code, never a copy of it.
+struct TfPlanRec {
+    char* buf;     // ';'-separated tokens, NUL-terminated (may be NULL with len 0: count only)
+    size_t len;
+    size_t used;   // characters the full plan needs (without the NUL)
+    int n;         // launches recorded
+};
+extern thread_local TfPlanRec* tf_plan_rec;
+// Appends a token when a plan is being recorded and returns true; false (nothing done) otherwise.
+bool tf_plan_note(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
+
 #define TF_ARG(cond, code, ...)            \
     do {                                   \
         if (!(cond)) {                     \

@@ -106,6 +106,43 @@ FOLD_SCALE = os.environ.get("TOKENFLOW_FOLD_SCALE", "0") not in ("", "0")
 NO_SPLIT = os.environ.get("TOKENFLOW_ATTN_NO_SPLIT", "0") not in ("", "0")
 
 
+def _attn_flags(inject: bool, part: str, out_f32: bool, fold_scale: Optional[bool], no_split: Optional[bool],
+                fused: Optional[bool], hints: int) -> int:
+    """The TF_ATTN_* bit mask of an ext_attn / ext_attn_views / attn_plan call."""
+    flags = (1 if inject else 0) | (_lib.TF_ATTN_FOLD_SCALE if (FOLD_SCALE if fold_scale is None else fold_scale) else 0)
+    if out_f32:
+        flags |= _lib.TF_ATTN_OUT_F32
+    flags |= {"all": 0, "bank": _lib.TF_ATTN_BANK_ONLY, "source": _lib.TF_ATTN_SOURCE_ONLY}[part]
+    if NO_SPLIT if no_split is None else no_split:
+        flags |= _lib.TF_ATTN_NO_SPLIT
+    return flags | int(hints) | (0 if fused is None else _lib.TF_ATTN_FUSED if fused else _lib.TF_ATTN_NO_FUSED)
+
+
+def _plan_tokens(what: str, fn, *args) -> list:
+    buf = ctypes.create_string_buffer(4096)
+    n = fn(*args, buf, len(buf))
+    if n < 0:
+        _lib.check(n, what)
+    toks = buf.value.decode().split(";") if n else []
+    assert len(toks) == n, (toks, n)
+    return toks
+
+
+def attn_plan(K: int, Kq: int, S: int, heads: int, dh: int, inject: bool, dtype: torch.dtype = torch.bfloat16,
+              part: str = "all", out_dtype: Optional[torch.dtype] = None, fold_scale: Optional[bool] = None,
+              no_split: Optional[bool] = None, fused: Optional[bool] = None, hints: int = 0) -> list:
+    """The launches `ext_attn` makes for dense [3K,S,heads*dh] / [3Kq,S,heads*dh] tensors with these arguments, as
+    tokens (tf_ext_attn_plan: e.g. ['vt_pack', 'il<40,8,ALL,4,3>']).  Host only: needs no GPU."""
+    flags = _attn_flags(inject, part, out_dtype == torch.float32, fold_scale, no_split, fused, hints)
+    return _plan_tokens("tf_ext_attn_plan", _lib.load().tf_ext_attn_plan, K, Kq, S, heads, dh, flags, _DT[dtype])
+
+
+def nn_plan(n_tgt: int, S: int, D: int, P: int, C: int = 1) -> list:
+    """The search launches of `nn_search` (C = 1) or of `propagate_chunks` over C > 1 chunks of n_tgt targets (P = 2),
+    as tokens (tf_nn_search_plan: e.g. ['glds[splits=2]', 'finalize']).  Host only: needs no GPU."""
+    return _plan_tokens("tf_nn_search_plan", _lib.load().tf_nn_search_plan, int(n_tgt), S, D, P, C)
+
+
 def ext_attn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, scale: float,
              inject: bool, out: Optional[torch.Tensor] = None, q_frame0: int = 0,
              fold_scale: Optional[bool] = None, part: str = "all",
@@ -151,13 +188,7 @@ def ext_attn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, scal
         out = torch.empty(Bq, S, D, dtype=out_dtype, device=q.device)
     elif out.dtype != out_dtype or not out.is_contiguous() or out.shape != (Bq, S, D):
         raise ValueError("ext_attn: `out` must be a contiguous [3Kq,S,D] tensor of out_dtype")
-    flags = (1 if inject else 0) | (_lib.TF_ATTN_FOLD_SCALE if (FOLD_SCALE if fold_scale is None else fold_scale) else 0)
-    if out_dtype == torch.float32:
-        flags |= _lib.TF_ATTN_OUT_F32
-    flags |= {"all": 0, "bank": _lib.TF_ATTN_BANK_ONLY, "source": _lib.TF_ATTN_SOURCE_ONLY}[part]
-    if NO_SPLIT if no_split is None else no_split:
-        flags |= _lib.TF_ATTN_NO_SPLIT
-    flags |= int(hints) | (0 if fused is None else _lib.TF_ATTN_FUSED if fused else _lib.TF_ATTN_NO_FUSED)
+    flags = _attn_flags(inject, part, out_dtype == torch.float32, fold_scale, no_split, fused, hints)
     key = (K, S, heads, dh, dt)
     nbytes = _attn_ws_bytes.get(key)
     if nbytes is None:
@@ -203,13 +234,7 @@ def ext_attn_views(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch
         raise ValueError("ext_attn_views: k and v need one token stride, out a dense one; frames of v = frames of k")
     if out.dtype not in (q.dtype, torch.float32):
         raise TypeError("ext_attn_views: out dtype")
-    flags = (1 if inject else 0) | (_lib.TF_ATTN_FOLD_SCALE if (FOLD_SCALE if fold_scale is None else fold_scale) else 0)
-    flags |= {"all": 0, "bank": _lib.TF_ATTN_BANK_ONLY, "source": _lib.TF_ATTN_SOURCE_ONLY}[part]
-    if NO_SPLIT if no_split is None else no_split:
-        flags |= _lib.TF_ATTN_NO_SPLIT
-    if out.dtype == torch.float32:
-        flags |= _lib.TF_ATTN_OUT_F32
-    flags |= int(hints) | (0 if fused is None else _lib.TF_ATTN_FUSED if fused else _lib.TF_ATTN_NO_FUSED)
+    flags = _attn_flags(inject, part, out.dtype == torch.float32, fold_scale, no_split, fused, hints)
     key = (K, S, heads, dh, dt)
     nbytes = _attn_ws_bytes.get(key)
     if nbytes is None:
