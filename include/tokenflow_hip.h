@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define TF_ABI_VERSION 8
+#define TF_ABI_VERSION 9
 
 /* Every entry point below is exported with default visibility; the library itself is built with -fvisibility=hidden, so
  * its exported symbols are exactly the declarations of this header (checked by tests/test_hooks_cpu.py). */
@@ -157,6 +157,62 @@ TF_API int tf_ext_attn_fwd_strided(const void* q, const void* k, const void* v, 
  *   fused[qw=.,kw=.,qb=.,prec=.]     fused small-problem kernel
  * MODE is ALL, DUAL or SOURCE. */
 TF_API int tf_ext_attn_plan(int K, int Kq, int S, int H, int Dh, int flags, int dtype, char* buf, size_t len);
+
+/* ------------------------------------------------------------------------
+ * Extended attention over a bank that arrives in pieces: "run + merge" (ABI 9).
+ *
+ * The bank branches (uncond, cond) of Kq query frames are computed one RUN of bank frames [run_f0, run_f0 + run_n) at a
+ * time; every run leaves, for each (bank branch, query frame, head, query), the unnormalised fp32 output, the softmax
+ * denominator and the log2-domain shift -- what one segment of the split form leaves -- in its own slots of the workspace,
+ * and tf_ext_attn_runs_merge folds the slots of all n_runs runs into `out`:
+ *     out = sum_r O_r 2^(s_r - M) / sum_r l_r 2^(s_r - M),   M = max_r s_r,
+ * reduced in slot order (run 0 first), so the result is a function of the runs alone: not of the order in which the run
+ * calls were issued, nor of the streams they ran on.  A host that receives keyframes from peers starts on the frames it
+ * holds while the others travel (csrc/rank_exec.hip, TF_RANK_BANK_RUNS).
+ *
+ *   q, out, K, Kq, q_frame0, S, H, Dh, ld, strides, scale, dtype: as tf_ext_attn_fwd_strided.
+ *   k, v: addressed as the full bank is -- frame f of branch b at base + b*branch_stride + f*frame_stride -- but only the
+ *     run's frames are read: a caller whose run lives in another buffer passes base = (the run's first frame) -
+ *     run_f0*frame_stride - ..., formed as the text above describes for branches.  Nothing outside the run's frames is
+ *     touched, prefetches included.
+ *   run, n_runs: this call fills the slots of run `run`.  The runs of one set must PARTITION [0, K) (each frame in exactly
+ *     one run) and use the same K, Kq, q_frame0, S, H, Dh, n_runs, dtype and workspace; the library cannot check that across
+ *     calls.  1 <= n_runs <= K.
+ *   flags: TF_ATTN_INJECT, TF_ATTN_FOLD_SCALE, TF_ATTN_OUT_F32, TF_ATTN_HINT_MIX, TF_ATTN_NO_SPLIT as above (the same in
+ *     every call of a set, the merge included).  TF_ATTN_BANK_ONLY: the bank branches only.  WITHOUT it the call also
+ *     computes the source branch of the query frames, final, into `out` -- by the kernel the TF_ATTN_SOURCE_ONLY |
+ *     TF_ATTN_NO_SPLIT | TF_ATTN_NO_FUSED call takes, bit for bit -- which needs [q_frame0, q_frame0 + Kq) inside the run
+ *     (TF_ERR_SHAPE otherwise): exactly one run of a set is issued without TF_ATTN_BANK_ONLY.
+ *     TF_ATTN_SOURCE_ONLY, TF_ATTN_FUSED and the fused kernel's hints: TF_ERR_SHAPE.  The fused small-problem kernel has no
+ *     partial output: run calls take the streaming kernels at every size, as TF_ATTN_NO_FUSED does.
+ *   A run may split itself over further workgroups by the rule of the split form; how many slots it owns and fills is
+ *     hidden in the workspace layout and is a function of the call's arguments alone.
+ *   ws: ONE workspace per set, tf_ext_attn_runs_workspace_bytes; the runs write disjoint parts of it (their frames'
+ *     positions in the V^T image and the key norm table, their own slots) and may execute concurrently on different streams.
+ *   tf_ext_attn_runs_merge reads the slots of all n_runs runs and writes the bank branches 1, 2 of `out` (element
+ *     (b, f, s, c) at out[b*out_branch_stride + f*out_frame_stride + s*H*Dh + c]; 16-bit, or float with TF_ATTN_OUT_F32).
+ *     Ordering it behind the run calls -- stream order or events -- is the caller's job.
+ *   No call allocates, synchronises or keeps state outside `ws`.
+ *   Identity: the merge re-associates fp32 sums as the split form's does.  A run set equals the oracle within the attention
+ *   bound and equals, bit for bit, any other execution of the same runs; it does NOT equal the one-call form bit for bit.
+ *
+ * tf_ext_attn_run_plan: the launches of one run call over run_n frames (the tokens of tf_ext_attn_plan; launches that
+ * leave partial results carry ",run" as their last parameter, e.g. il<40,8,ALL,4,2,run>) followed by the merge,
+ * merge[runs=N].  Host only.
+ * ------------------------------------------------------------------------ */
+TF_API size_t tf_ext_attn_runs_workspace_bytes(int K, int Kq, int S, int H, int Dh, int n_runs, int dtype);
+
+TF_API int tf_ext_attn_run(const void* q, const void* k, const void* v, void* out,
+                    int K, int Kq, int q_frame0, int run_f0, int run_n, int run, int n_runs,
+                    int S, int H, int Dh, int64_t ld, const int64_t* strides,
+                    float scale, int flags, int dtype, void* ws, size_t ws_bytes, void* stream);
+
+TF_API int tf_ext_attn_runs_merge(void* out, int K, int Kq, int S, int H, int Dh, int n_runs,
+                           int64_t out_branch_stride, int64_t out_frame_stride,
+                           int flags, int dtype, void* ws, size_t ws_bytes, void* stream);
+
+TF_API int tf_ext_attn_run_plan(int K, int Kq, int run_n, int n_runs, int S, int H, int Dh,
+                         int flags, int dtype, char* buf, size_t len);
 
 /* ------------------------------------------------------------------------
  * Frames <-> heads re-sharding of the multi-GPU pivotal pass (no counterpart in the single-process reference;
@@ -420,6 +476,8 @@ TF_API int tf_sendrecv_pivot(tf_comm* comm, const void* const* send, const int64
  *                  (tf_head_unpack); needs H % W == 0 and one token stride for q, k, v;
  *   TF_RANK_BANK   gathers the K/V slabs of all ranks (tf_allgather_rows) and computes its own keyframes' queries
  *                  against the gathered bank: one collective, 4x the bytes; any head count;
+ *   TF_RANK_BANK_RUNS  the bank form in runs of keyframes (below): two thirds of TF_RANK_BANK's bytes, the rank's own
+ *                  keyframes attended to before the gather lands; any head count; a weaker identity guarantee;
  * then sends its last keyframe's pivot features, inverse norms and attention output to rank r+1 (tf_sendrecv_pivot on
  * the halo communicator and a stream of its own: chunk c of the propagation reads keyframes c and c-1, 331-333).
  *
@@ -441,6 +499,13 @@ TF_API int tf_sendrecv_pivot(tf_comm* comm, const void* const* send, const int64
  * ------------------------------------------------------------------------ */
 #define TF_RANK_HEADS 0
 #define TF_RANK_BANK 1
+#define TF_RANK_BANK_RUNS 2  /* the bank form in RUNS (ABI 9; any head count): only the slabs peers read are gathered ([k1, k2, v1, v2];
+                                under injection [k0, v1, v2]), the LOCAL run -- the source branch of the rank's frames and their bank
+                                branches against the rank's own keyframes, read from q / k / v in place -- starts on the auxiliary
+                                compute stream before the gather, the remote runs (the frames left, then right of the rank's own)
+                                follow behind it, and tf_ext_attn_runs_merge folds them: runs local, left, right in that slot order,
+                                whatever the schedule.  Equal bit for bit to tf_ext_attn_run + merge on the full tensors with the
+                                same runs, and to the oracle within the attention bound -- NOT to the one-call forms above. */
 #define TF_RANK_NO_HALO 16   /* or-ed into `mode`: the attention alone -- kfo_ext is a plain [3, Kl, S, H*Dh] output, piv_ext /
                                 inv_ext are not read (NULL allowed), no neighbour exchange (hosts whose cached attention
                                 output is not this one: the hook path caches it after the to_out projection) */

@@ -91,9 +91,16 @@ struct AttnParams {
     int out_f32;       // TF_ATTN_OUT_F32: `out` is float (the normalised fp32 accumulator, no 16-bit rounding)
     int nseg;          // > 1: every bank problem is split into nseg runs of bank frames (small grids, see split_plan)
     int bit_stable;    // TF_ATTN_NO_SPLIT: kernel choice and arithmetic are functions of the shape alone
+    int Kb;            // frames of the V^T image and of the key norm table (their row strides).  = K in a one-call launch; a run
+                       // launch (tf_ext_attn_run) has K = the run's frames, Kb = the whole bank, and k / vt / knorm2 pointing at
+                       // the run's first frame
+    int pslots;        // partial-result slots per (bank, query frame, head, query) row: nseg in the split form, 0 when the launch
+                       // writes the final output; a run launch: the slots of ALL runs (partials points at this run's first slot)
+    int run;           // host only: a run launch (partials always, no merge, the ping-pong kernel's partial form)
+    int* run_hdr;      // host only: where the pre-pass leaves the number of slots this run filled (read by the runs merge)
     int mix;           // TF_ATTN_HINT_MIX: the mixed-MFMA-shape form (Dh = 40) whatever the launch size, where the frames
                        // admit the interleaved kernel (S % 64 == 0, S >= 256); no effect on ragged frames
-    float* partials;   // [2 banks][Kq][H][S][nseg][Dh + 8] fp32: unnormalised O, l, log2-domain shift  // K bank frames; queries = frames q_frame0 .. +Kq
+    float* partials;   // [2 banks][Kq][H][S][pslots][Dh + 8] fp32: unnormalised O, l, log2-domain shift  // K bank frames; queries = frames q_frame0 .. +Kq
     int64_t ld;      // token stride of k and v
     int64_t ld_q;    // token stride of q (its own: a rank's q may be a column slab of the fused projection while the
                      // bank arrives from a collective as dense slabs)
@@ -136,7 +143,7 @@ __device__ __forceinline__ void store_out4(void* out, int64_t elem_off, f32x4 x,
 __device__ __forceinline__ int swap23(int x) { return (x & ~12) | ((x & 4) << 1) | ((x & 8) >> 1); }
 
 // V [3,K,S,H*DH] (token stride ld) -> Vt [3][H][DH][K*Spad + 64], position = f*Spad + swap23(key in frame),
-// zero for keys >= S.  grid = (Spad/64, H, 3*K), 256 threads; one workgroup = 64 keys x DH of one head.
+// zero for keys >= S.  grid = (Spad/64, H, branches * frames), 256 threads; one workgroup = 64 keys x DH of one head.
 // 16-byte global accesses on both sides (rows of V in, 8 consecutive positions of one V^T row out); the
 // transpose itself is 2-byte LDS reads of a [64][DH+2] tile (odd dword stride: conflict-free columns).
 // With k != nullptr (Dh = 40 kernels) the same workgroup also writes max |k|^2 over its 64 keys of this head to
@@ -145,21 +152,26 @@ template <typename T>
 __global__ __launch_bounds__(256) void vt_pack_kernel(const typename T::elem* __restrict__ v,
                                                       typename T::elem* __restrict__ vt,
                                                       const typename T::elem* __restrict__ k,
-                                                      float* __restrict__ knorm2, int inject, int bf0, int K,
+                                                      float* __restrict__ knorm2, int inject, int b0, int nf, int K,
                                                       int S, int H, int DH, int Spad, int64_t ld, int64_t v_bs,
-                                                      int64_t v_fs, int64_t k_bs, int64_t k_fs) {
+                                                      int64_t v_fs, int64_t k_bs, int64_t k_fs, int* __restrict__ run_hdr,
+                                                      int run_slots) {
     typedef typename T::elem E;
     typedef typename T::vec8 vec8;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     E* tile = reinterpret_cast<E*>(smem);  // [64][DH + 2]
     const int row = DH + 2;
     const int ppr = DH >> 3;               // 16-B pieces per V row
-    const int tt = blockIdx.x, h = blockIdx.y, bf = blockIdx.z + bf0;  // bf = b*K + f; bf0 = first (branch, frame)
-    const int b = bf / K, f = bf - b * K;
+    // blockIdx.z = (branch - b0) * nf + frame: nf frames of every branch from b0 on.  K = frames of the IMAGE (row stride of
+    // vt, of knorm2): a run launch packs its nf < K frames with v / vt / k / knorm2 pointing at the run's first frame
+    const int tt = blockIdx.x, h = blockIdx.y;
+    const int b = b0 + (int)blockIdx.z / nf, f = (int)blockIdx.z % nf;
+    // run launches: the number of partial-result slots the run fills, for tf_ext_attn_runs_merge
+    if (run_hdr != nullptr && (blockIdx.x | blockIdx.y | blockIdx.z | threadIdx.x) == 0) *run_hdr = run_slots;
     const E* src = v + b * v_bs + f * v_fs + h * DH;
     // keys of branch b without injection; with injection every branch reads the SOURCE keys, whose norms the
     // first packed branch computes
-    if (k != nullptr && (!inject || b == bf0 / K) && threadIdx.x < 64) {   // wave 0: one key per lane
+    if (k != nullptr && (!inject || b == b0) && threadIdx.x < 64) {   // wave 0: one key per lane
         const int kb = inject ? 0 : b;
         const int kk = tt * 64 + (int)threadIdx.x;
         float acc = 0.f;
@@ -303,7 +315,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void ext_attn_kernel(AttnParams p) {
     f = u / p.nQT;
     qt = u - f * p.nQT;
     const int bq = (p.inject && b > 0) ? 0 : b;  // branch whose q and k are used (tokenflow_utils.py:124-130)
-    const bool split = nseg > 1 && b > 0;
+    const bool split = p.pslots > 0 && b > 0;
     const int f_lo = b == 0 ? p.q_frame0 + f : (seg * K) / nseg;
     const int n_fr = b == 0 ? 1 : ((seg + 1) * K) / nseg - f_lo;
     const int tpf = (S + KT - 1) / KT;  // staged tiles per frame
@@ -312,7 +324,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void ext_attn_kernel(AttnParams p) {
 
     const E* qg = reinterpret_cast<const E*>(p.q);
     const E* kg = reinterpret_cast<const E*>(p.k) + bq * p.k_bs + h * DH;
-    const int64_t vt_row = vt_row_stride(K, p.Spad);
+    const int64_t vt_row = vt_row_stride(p.Kb, p.Spad);
     const E* vg[NB];
 #pragma unroll
     for (int vb = 0; vb < NB; ++vb)
@@ -363,7 +375,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void ext_attn_kernel(AttnParams p) {
     float s_bound[QT] = {};   // BOUND: upper bound of q.k*c (log2 units) over every key of the bank (1.001 covers fp32 rounding)
     if constexpr (BOUND) {
         const int ppf = p.Spad / 64;   // 64-key blocks per frame; this problem sees frames f_lo .. f_lo + n_fr - 1
-        const float* part = p.knorm2 + ((int64_t)(bq * H + h) * K + f_lo) * ppf;
+        const float* part = p.knorm2 + ((int64_t)(bq * H + h) * p.Kb + f_lo) * ppf;
         float kn2 = 0.f;
         for (int i = lane; i < n_fr * ppf; i += 64) kn2 = fmaxf(kn2, part[i]);
 #pragma unroll
@@ -655,7 +667,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void ext_attn_kernel(AttnParams p) {
                 const float lshift = FOLD ? m_run[qi] : m_run[qi] * c;
                 auto row_ptr = [&](int vb) {
                     const int64_t R = (((int64_t)(b - 1 + vb) * Kq + f) * H + h) * S + q_row[qi];
-                    return p.partials + (R * nseg + seg) * PS;
+                    return p.partials + (R * p.pslots + seg) * PS;
                 };
                 if constexpr (PACK) {
 #pragma unroll
@@ -766,6 +778,48 @@ __global__ __launch_bounds__(256) void attn_merge_kernel(const float* __restrict
     }
 }
 
+// Runs form (tf_ext_attn_run / tf_ext_attn_runs_merge), merge: the same sum over the slots of EVERY run of the bank.  Run r owns
+// slots [r * spr, (r + 1) * spr) of a row and filled the first hdr[r] of them (left by the run's pre-pass: a run splits itself
+// by split_plan's rule on its own frame count).  The slots are reduced in ascending order, whatever the order or the streams
+// in which the runs executed: the result is a function of the runs alone.
+template <typename T>
+__global__ __launch_bounds__(256) void attn_runs_merge_kernel(const float* __restrict__ partials, const int* __restrict__ hdr,
+                                                              void* __restrict__ out, int Kq, int S, int H, int DH, int n_runs,
+                                                              int spr, int out_f32, int64_t o_bs, int64_t o_fs) {
+    typedef typename T::elem E;
+    typedef typename T::vec4 vec4;
+    const int PS = DH + 8, dq = DH >> 2;
+    const int64_t total = (int64_t)2 * Kq * H * S * dq;
+    for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < total; g += (int64_t)gridDim.x * 256) {
+        const int64_t R = g / dq;                 // ((vbank*Kq + f)*H + h)*S + q
+        const int d0 = (int)(g - R * dq) * 4;
+        const float* pr = partials + R * ((int64_t)n_runs * spr) * PS;
+        float M = -INFINITY;
+        for (int r = 0; r < n_runs; ++r) {
+            const int ns = min(hdr[r], spr);
+            for (int sg = 0; sg < ns; ++sg) M = fmaxf(M, pr[(r * spr + sg) * PS + DH + 1]);
+        }
+        f32x4 num = {0.f, 0.f, 0.f, 0.f};
+        float den = 0.f;
+        for (int r = 0; r < n_runs; ++r) {
+            const int ns = min(hdr[r], spr);
+            for (int sg = 0; sg < ns; ++sg) {
+                const float* ps = pr + (r * spr + sg) * PS;
+                const float w = __builtin_amdgcn_exp2f(ps[DH + 1] - M);
+                num += *reinterpret_cast<const f32x4*>(ps + d0) * w;
+                den = fmaf(ps[DH], w, den);
+            }
+        }
+        const float inv = 1.0f / den;
+        const int q = (int)(R % S);
+        int64_t t = R / S;
+        const int h = (int)(t % H);
+        t /= H;
+        const int f = (int)(t % Kq), vbank = (int)(t / Kq);
+        store_out4<E, vec4>(out, (1 + vbank) * o_bs + f * o_fs + (int64_t)q * (H * DH) + h * DH + d0, num * inv, out_f32);
+    }
+}
+
 // How many runs of bank frames a bank problem is split into.  The grid of a sharded rank or of a small level has
 // too few waves to fill the chip (8-GPU rank at cfg2 level 0: 2 waves per SIMD, level 1: 0.5; single GPU at the
 // 16x16 level: 1): split until it has `occ` waves per SIMD, while a run keeps at least 2 tiles.
@@ -842,7 +896,10 @@ struct PpSchedule {
 // gaps of the other stream's MFMAs.  K(t) lives in Kbuf[t&1], V(t) in Vbuf[t&1]; K(t+1) and V(t) are
 // written at the top of R1(t) from registers loaded one iteration earlier; ONE barrier per tile
 // (between R1 and R2) orders all LDS hazards (see the per-line comments).
-template <typename T, int DH, int MODE, int MINW, bool FQ = false>
+// RUN (tf_ext_attn_run): bank problems only; the epilogue leaves the unnormalised O, the denominator and the shift in the
+// run's partial-result slot (one slot: this kernel has no split form) instead of the output.  A template parameter, not a
+// run-time one: the kernel sits at 250 VGPRs and the one-call instantiation must not change.
+template <typename T, int DH, int MODE, int MINW, bool FQ = false, bool RUN = false>
 __global__ __launch_bounds__(256, MINW) void ext_attn_pp_kernel(AttnParams p) {
     typedef AttnCfg<DH, 64> C;
     typedef typename T::elem E;
@@ -900,7 +957,7 @@ __global__ __launch_bounds__(256, MINW) void ext_attn_pp_kernel(AttnParams p) {
 
     const E* qg = reinterpret_cast<const E*>(p.q);
     const E* kg = reinterpret_cast<const E*>(p.k) + bq * p.k_bs + h * DH;
-    const int64_t vt_row = vt_row_stride(K, p.Spad);
+    const int64_t vt_row = vt_row_stride(p.Kb, p.Spad);
     const E* vg = reinterpret_cast<const E*>(p.vt) + ((int64_t)(b * H + h) * DH) * vt_row;
 
     // ---- LDS init: everything zero (the pipeline touches Kbuf[1] / Vbuf[1] before they are staged:
@@ -935,7 +992,7 @@ __global__ __launch_bounds__(256, MINW) void ext_attn_pp_kernel(AttnParams p) {
     float s_bound[2] = {0.f, 0.f};   // BOUND: upper bound of q.k*c (log2 units) over every key this problem sees
     if constexpr (BOUND && !FOLD) {
         const int ppf = p.Spad / 64;
-        const float* part = p.knorm2 + ((int64_t)(bq * H + h) * K + f_lo) * ppf;
+        const float* part = p.knorm2 + ((int64_t)(bq * H + h) * p.Kb + f_lo) * ppf;
         float kn2 = 0.f;
         for (int i = lane; i < n_fr * ppf; i += 64) kn2 = fmaxf(kn2, part[i]);
 #pragma unroll
@@ -1219,6 +1276,30 @@ __global__ __launch_bounds__(256, MINW) void ext_attn_pp_kernel(AttnParams p) {
             l_tot = __shfl(o[qi][C::MT - 1][ONES_R], l31);
         else
             l_tot = l_run[qi] + __shfl_xor(l_run[qi], 32);
+        if constexpr (RUN) {
+            if (q_ok[qi]) {
+                constexpr int PS = DH + 8;
+                const int64_t R = (((int64_t)(b - 1) * Kq + f) * H + h) * S + q_row[qi];
+                float* row = p.partials + R * p.pslots * PS;
+#pragma unroll
+                for (int mt = 0; mt < C::MT; ++mt)
+#pragma unroll
+                    for (int rg = 0; rg < 4; ++rg) {
+                        const int d0 = mt * 32 + 8 * rg + 4 * hi;
+                        if (d0 < DH) {
+                            f32x4 w;
+#pragma unroll
+                            for (int i = 0; i < 4; ++i) w[i] = o[qi][mt][rg * 4 + i];
+                            *reinterpret_cast<f32x4*>(row + d0) = w;
+                        }
+                    }
+                if (hi == 0) {
+                    row[DH] = l_tot;
+                    row[DH + 1] = FOLD ? m_run[qi] : m_run[qi] * c;
+                }
+            }
+            continue;
+        }
         const float inv_l = 1.0f / l_tot;
         if (q_ok[qi]) {
             const int64_t op = b * p.o_bs + f * p.o_fs + (int64_t)q_row[qi] * (H * DH) + h * DH;
@@ -1405,7 +1486,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void ext_attn_il_kernel(AttnParams p
     f = u / p.nQT;
     qt = u - f * p.nQT;
     const int bq = (p.inject && b > 0) ? 0 : b;
-    const bool split = nseg > 1 && b > 0;
+    const bool split = p.pslots > 0 && b > 0;
     const int f_lo = b == 0 ? p.q_frame0 + f : (seg * K) / nseg;
     const int n_fr = b == 0 ? 1 : ((seg + 1) * K) / nseg - f_lo;
     const int tpf = S >> 6;
@@ -1413,7 +1494,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void ext_attn_il_kernel(AttnParams p
 
     const E* qg = reinterpret_cast<const E*>(p.q);
     const E* kg = reinterpret_cast<const E*>(p.k) + bq * p.k_bs + h * DH;
-    const int64_t vt_row = vt_row_stride(K, p.Spad);
+    const int64_t vt_row = vt_row_stride(p.Kb, p.Spad);
     const E* vg = reinterpret_cast<const E*>(p.vt) + ((int64_t)(b * H + h) * DH) * vt_row;
 
     // ---- LDS init: zero everything (pads; the V^T rows past DH), then the denominator row DH of both V^T images
@@ -1439,7 +1520,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void ext_attn_il_kernel(AttnParams p
     float s_bound = 0.f;
     if constexpr (BOUND) {
         const int ppf = p.Spad / 64;
-        const float* part = p.knorm2 + ((int64_t)(bq * H + h) * K + f_lo) * ppf;
+        const float* part = p.knorm2 + ((int64_t)(bq * H + h) * p.Kb + f_lo) * ppf;
         float kn2 = 0.f;
         for (int i = lane; i < n_fr * ppf; i += 64) kn2 = fmaxf(kn2, part[i]);
 #pragma unroll
@@ -1941,7 +2022,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void ext_attn_il_kernel(AttnParams p
                 const int qr = qt * (32 * NW) + wave * 32 + 16 * t + n16;
                 if (qr < S) {
                     const int64_t R = (((int64_t)(b - 1) * Kq + f) * H + h) * S + qr;
-                    float* row = p.partials + (R * nseg + seg) * PS;
+                    float* row = p.partials + (R * p.pslots + seg) * PS;
 #pragma unroll
                     for (int d = 0; d < NT16; ++d)
                         if (16 * d + 4 * g < DH) *reinterpret_cast<f32x4*>(row + 16 * d + 4 * g) = o16[d][t];
@@ -1950,7 +2031,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void ext_attn_il_kernel(AttnParams p
             }
             if (hi == 0 && q_ok) {   // the shift is this lane's own query's (l & 31)
                 const int64_t R = (((int64_t)(b - 1) * Kq + f) * H + h) * S + q_row;
-                p.partials[(R * nseg + seg) * PS + DH + 1] = m_run * c;
+                p.partials[(R * p.pslots + seg) * PS + DH + 1] = m_run * c;
             }
         } else {
 #pragma unroll
@@ -1981,7 +2062,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void ext_attn_il_kernel(AttnParams p
             constexpr int PS = DH + 8;
             auto row_ptr = [&](int vb) {
                 const int64_t R = (((int64_t)(b - 1 + vb) * Kq + f) * H + h) * S + q_row;
-                return p.partials + (R * nseg + seg) * PS;
+                return p.partials + (R * p.pslots + seg) * PS;
             };
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt)
@@ -2022,13 +2103,18 @@ __global__ __launch_bounds__(64 * NW, MINW) void ext_attn_il_kernel(AttnParams p
     }
 }
 
+// Plan-token mark of a launch that leaves partial results for tf_ext_attn_runs_merge (a run call's SOURCE launch writes the
+// final output and carries no mark)
+template <int MODE>
+static inline const char* run_mark(const AttnParams& p) { return (p.run && MODE != MODE_SOURCE) ? ",run" : ""; }
+
 template <typename T, int DH, int NW, int MODE, int MINW, int DMA = 0>
 int launch_il(AttnParams p, hipStream_t st) {
     typedef AttnCfg<DH, 64> C;
     constexpr size_t lds = DMA == 1            ? 2 * (size_t)(64 * DH + C::MT * 32 * 64) * 2 + 16   // dense images (+ the K over-read)
                            : MODE == MODE_DUAL ? 2 * (size_t)(C::K_ELEMS + ((2 * DH + 31) / 32) * 32 * C::VROW) * 2   // packed dual-V image
                                                : C::lds_bytes(1);
-    if (tf_plan_note("il<%d,%d,%s,%d,%d>", DH, NW, mode_name(MODE), MINW, DMA)) return 0;
+    if (tf_plan_note("il<%d,%d,%s,%d,%d%s>", DH, NW, mode_name(MODE), MINW, DMA, run_mark<MODE>(p))) return 0;
     auto kern = ext_attn_il_kernel<T, DH, NW, MODE, MINW, DMA>;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)lds);
@@ -2037,23 +2123,30 @@ int launch_il(AttnParams p, hipStream_t st) {
     const unsigned grid = (unsigned)(MODE == MODE_ALL    ? (2 * p.nseg + (p.part == TF_ATTN_BANK_ONLY ? 0 : 1)) * per_branch
                                      : MODE == MODE_DUAL ? p.nseg * per_branch
                                                          : per_branch);
+    // Run launches (p.K = the run's frames): a problem stages tiles 0 .. ntiles-1 of ITS frames and nothing else.  K(t+2) is
+    // fetched under `t + 2 < ntiles`, K(1) under `ntiles > 1`, V(t+1) inside the loop over `t + 1 < ntiles` -- register staging
+    // and LDS-DMA alike, the last tile is peeled and fetches nothing; S % 64 == 0 here, so every tile lies inside one frame of
+    // the caller's k and inside the frame's Spad positions of the V^T image.  No fetch passes the run's last tile.
     hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NW), lds, st, p);
     TF_LAUNCH_CHECK("tf_ext_attn_fwd");
     return 0;
 }
 
-template <typename T, int DH, int MODE, int MINW>
+template <typename T, int DH, int MODE, int MINW, bool RUN = false>
 int launch_pp(AttnParams p, hipStream_t st) {
     typedef AttnCfg<DH, 64> C;
     constexpr size_t lds = C::lds_bytes(1);
-    if (tf_plan_note("pp<%d,%s>", DH, mode_name(MODE))) return 0;
-    auto kern = ext_attn_pp_kernel<T, DH, MODE, MINW>;
+    if (tf_plan_note("pp<%d,%s%s>", DH, mode_name(MODE), RUN ? ",run" : "")) return 0;
+    auto kern = ext_attn_pp_kernel<T, DH, MODE, MINW, false, RUN>;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)lds);
     p.nQT = (p.S + 255) / 256;
     const int per_branch = p.Kq * p.nQT * p.H;
     // bank problems are decoded first: a bank-only launch simply stops before the source problems
     const unsigned grid = (unsigned)(MODE == MODE_ALL ? (p.part == TF_ATTN_BANK_ONLY ? 2 : 3) * per_branch : per_branch);
+    // Run launches: K(1) is fetched under `ntiles > 1`, K(t+2) under `t + 2 < ntiles`, V(t+1) under `t + 1 < ntiles`; a short
+    // last tile clamps its K rows to the frame's last key.  The dead S_A(n) behind the last tile multiplies what is already in
+    // LDS (K(n-1) again) and is never used.  No fetch passes the run's last tile.
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, p);
     TF_LAUNCH_CHECK("tf_ext_attn_fwd");
     return 0;
@@ -2064,8 +2157,8 @@ int launch_one(AttnParams p, hipStream_t st) {
     typedef AttnCfg<DH, KT> C;
     constexpr size_t lds = ((MODE == MODE_DUAL && DH == 40) ? 2 * (size_t)(C::K_ELEMS + 96 * C::VROW) * 2   // PACK
                                                              : C::lds_bytes(MODE == MODE_DUAL ? 2 : 1)) / (SB ? 2 : 1);
-    if (tf_plan_note("one<%d,%d,%d,%s,%d,fq%d%s%s>", DH, QT, NW, mode_name(MODE), MINW, FQ ? 1 : 0, KT != 64 ? ",kt128" : "",
-                     SB ? ",sb" : ""))
+    if (tf_plan_note("one<%d,%d,%d,%s,%d,fq%d%s%s%s>", DH, QT, NW, mode_name(MODE), MINW, FQ ? 1 : 0, KT != 64 ? ",kt128" : "",
+                     SB ? ",sb" : "", run_mark<MODE>(p)))
         return 0;
     auto kern = ext_attn_kernel<T, DH, QT, NW, MODE, MINW, KT, FQ, SB>;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -2076,6 +2169,9 @@ int launch_one(AttnParams p, hipStream_t st) {
     const int ns = MODE == MODE_SOURCE ? 1 : p.nseg;
     const unsigned grid = (unsigned)(MODE == MODE_ALL ? (2 * ns + (p.part == TF_ATTN_BANK_ONLY ? 0 : 1)) * per_branch
                                                       : ns * per_branch);
+    // Run launches: the one staging site inside the loop is `if (has_next) stage_load()`, has_next = tile + 1 < ntiles, and the
+    // prologue loads tile 0; rows past S of a short last tile are clamped to the frame's last key.  No fetch passes the run's
+    // last tile, in the caller's k or in the V^T image.
     hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NW), lds, st, p);
     TF_LAUNCH_CHECK("tf_ext_attn_fwd");
     return 0;
@@ -2089,8 +2185,13 @@ template <typename T, int DH>
 int launch_attn(const AttnParams& p, const void* v, hipStream_t st) {
     typedef typename T::elem E;
     const bool src_only = p.part == TF_ATTN_SOURCE_ONLY, bank_only = p.part == TF_ATTN_BANK_ONLY;
+    // The kernel FAMILY of a run launch is the one the unsplit call of the same (Kq, S, H) takes, however the run splits
+    // itself: the source branch out of a run call is then bit for bit the source-only call's (same kernel, same keys).
+    const int ns_sel = p.run ? 1 : p.nseg;
     {   // pre-pass: V -> transposed, key-permuted, per-frame padded bank (only the branches this call computes)
         const int b_lo = bank_only ? 1 : 0, b_hi = src_only ? 1 : 3;
+        // (a run launch: the run's p.K frames only, at their positions in the image of the whole bank -- p.vt, p.knorm2, p.k and v
+        // point at the run's first frame, so the runs of one bank fill disjoint parts of one workspace)
         dim3 grid((unsigned)(p.Spad / 64), (unsigned)p.H, (unsigned)((b_hi - b_lo) * p.K));
         const size_t lds = (size_t)64 * (DH + 2) * sizeof(E);
         // the Dh = 40 kernels also need the key norm bounds (score bound, see BOUND)
@@ -2099,7 +2200,8 @@ int launch_attn(const AttnParams& p, const void* v, hipStream_t st) {
             hipLaunchKernelGGL(vt_pack_kernel<T>, grid, dim3(256), lds, st, reinterpret_cast<const E*>(v),
                                reinterpret_cast<E*>(const_cast<void*>(p.vt)),
                                bound ? reinterpret_cast<const E*>(p.k) : nullptr, const_cast<float*>(p.knorm2),
-                               p.inject, b_lo * p.K, p.K, p.S, p.H, DH, p.Spad, p.ld, p.v_bs, p.v_fs, p.k_bs, p.k_fs);
+                               p.inject, b_lo, p.K, p.Kb, p.S, p.H, DH, p.Spad, p.ld, p.v_bs, p.v_fs, p.k_bs, p.k_fs,
+                               p.run_hdr, p.nseg);
             TF_LAUNCH_CHECK("tf_ext_attn_fwd(vt_pack)");
         }
     }
@@ -2108,7 +2210,7 @@ int launch_attn(const AttnParams& p, const void* v, hipStream_t st) {
     // A full call is ALL, or DUAL followed by SOURCE; a bank-only call drops the source part, a source-only
     // call is SOURCE alone.
     auto merge = [&]() -> int {   // split form: fold the per-run partial results into the output
-        if (p.nseg <= 1) return 0;
+        if (p.nseg <= 1 || p.run) return 0;   // (a run's partial results wait for tf_ext_attn_runs_merge)
         if (tf_plan_note("merge[nseg=%d]", p.nseg)) return 0;
         const int64_t total = (int64_t)2 * p.Kq * p.H * p.S * (DH / 4);
         const int64_t blocks = (total + 255) / 256;
@@ -2131,7 +2233,7 @@ int launch_attn(const AttnParams& p, const void* v, hipStream_t st) {
         // 8-wave (256-query) workgroups while they still give 3 workgroups per CU (split runs included: measured
         // -8..11 % on a sharded rank's level 0 against the 4-wave form); below that the 4-wave form (twice the
         // workgroups).  S < 256: always 4 waves.
-        const bool big = p.S >= 256 && (int64_t)3 * p.Kq * ((p.S + 255) / 256) * p.H * p.nseg >= 768;
+        const bool big = p.S >= 256 && (int64_t)3 * p.Kq * ((p.S + 255) / 256) * p.H * ns_sel >= 768;
         if (!p.fold) {   // fp32 score scaling: the default
 #ifndef TF_TUNE_IL40_MIN_WGS
 #define TF_TUNE_IL40_MIN_WGS 256   // one 8-wave workgroup per CU: a W = 8 rank's one-pass level 0 (384 workgroups) runs
@@ -2140,7 +2242,7 @@ int launch_attn(const AttnParams& p, const void* v, hipStream_t st) {
             // half-tile interleaved form (ext_attn_il_kernel); TF_ATTN_HINT_MIX (p.mix) opens it on any grid its shape
             // requirement admits, so that the mixed-shape form it selects below is taken whatever the launch size
             const bool il = p.S >= 256 && p.S % 64 == 0 &&
-                            (p.mix || (int64_t)3 * p.Kq * ((p.S + 255) / 256) * p.H * p.nseg >= TF_TUNE_IL40_MIN_WGS);
+                            (p.mix || (int64_t)3 * p.Kq * ((p.S + 255) / 256) * p.H * ns_sel >= TF_TUNE_IL40_MIN_WGS);
 #else
             const bool il = false;
 #endif
@@ -2168,7 +2270,7 @@ int launch_attn(const AttnParams& p, const void* v, hipStream_t st) {
 #endif
 #ifndef TF_TUNE_NO_IL40_MIX
             const int64_t per_branch = (int64_t)p.Kq * ((p.S + 255) / 256) * p.H;
-            const bool mix_all = p.mix || (!p.bit_stable && per_branch * (2 * p.nseg + (bank_only ? 0 : 1)) >= TF_TUNE_IL40_MIX_MIN_WGS);
+            const bool mix_all = p.mix || (!p.bit_stable && per_branch * (2 * ns_sel + (bank_only ? 0 : 1)) >= TF_TUNE_IL40_MIX_MIN_WGS);
             const bool mix_src = p.mix || (!p.bit_stable && per_branch >= TF_TUNE_IL40_MIX_MIN_WGS);
 #else
             const bool mix_all = false, mix_src = false;
@@ -2203,7 +2305,7 @@ int launch_attn(const AttnParams& p, const void* v, hipStream_t st) {
 #ifdef TF_TUNE_IL40_NW4_SMALL
                                // A/B switch: fewer than two 8-wave workgroups per CU (a rank's one-pass level 0: 256) as
                                // twice as many 4-wave workgroups -- two barrier groups per CU instead of one
-                               if (il && (int64_t)(p.part == TF_ATTN_BANK_ONLY ? 2 : 3) * p.Kq * ((p.S + 255) / 256) * p.H * p.nseg < 512)
+                               if (il && (int64_t)(p.part == TF_ATTN_BANK_ONLY ? 2 : 3) * p.Kq * ((p.S + 255) / 256) * p.H * ns_sel < 512)
                                    return launch_il<T, 40, 4, MODE_ALL, 4>(p, st);
 #endif
                                return il    ? launch_il<T, 40, 8, MODE_ALL, 4>(p, st)
@@ -2254,17 +2356,26 @@ int launch_attn(const AttnParams& p, const void* v, hipStream_t st) {
 #else
         const bool il = false;
 #endif
+        // A run through the ping-pong kernel: its bank problems in the partial form, then the source branch through the kernel
+        // the source-only call takes (the ping-pong kernel's own source problems are a different arithmetic)
+        auto run_pp = [&]() -> int {
+            AttnParams pb = p;
+            pb.part = TF_ATTN_BANK_ONLY;
+            const int rc = launch_pp<T, DH, MODE_ALL, 2, true>(pb, st);
+            return (rc || bank_only) ? rc : launch_one<T, DH, 1, 4, MODE_SOURCE, 2>(p, st);
+        };
 #ifdef TF_TUNE_IL64_MIX
         // A/B switch: the mixed MFMA shapes at Dh = 64 (P.V as 16x16x32 over four 16-row M-tiles: the same matrix-pipe clocks, no
         // padding to remove here; the question is the short shape's power efficiency), launches of >= 1024 workgroups
         const int64_t per_branch64 = (int64_t)p.Kq * ((p.S + 255) / 256) * p.H;
-        const bool mix64 = il && (p.mix || (!p.bit_stable && per_branch64 * (2 * p.nseg + (bank_only ? 0 : 1)) >= 1024));
+        const bool mix64 = il && (p.mix || (!p.bit_stable && per_branch64 * (2 * ns_sel + (bank_only ? 0 : 1)) >= 1024));
         const bool mix64s = il && (p.mix || (!p.bit_stable && per_branch64 >= 1024));
 #else
         const bool mix64 = false, mix64s = false;
 #endif
         return compose([&] { return mix64 ? launch_il<T, DH, TF_TUNE_IL64_NW, MODE_ALL, TF_TUNE_IL64_MINW, 3>(p, st)
                                   : il ? launch_il<T, DH, TF_TUNE_IL64_NW, MODE_ALL, TF_TUNE_IL64_MINW, TF_TUNE_IL64_DMA>(p, st)
+                                  : (p.S >= 512 && p.nseg == 1 && p.run) ? run_pp()
                                   : (p.S >= 512 && p.nseg == 1) ? launch_pp<T, DH, MODE_ALL, 2>(p, st)   // ragged frames: ping-pong
                                                                 : launch_one<T, DH, 1, 4, MODE_ALL, 2>(p, st); },
                        [&] {
@@ -2417,6 +2528,8 @@ extern "C" int tf_ext_attn_fwd_strided(const void* q, const void* k, const void*
     p.fold = (inject & TF_ATTN_FOLD_SCALE) ? 1 : 0;
     p.out_f32 = (inject & TF_ATTN_OUT_F32) ? 1 : 0;
     p.nseg = split_plan(K, Kq, S, H, Dh, p.inject != 0, p.part, !(inject & TF_ATTN_NO_SPLIT));
+    p.Kb = K;
+    p.pslots = p.nseg > 1 ? p.nseg : 0;
     p.bit_stable = (inject & TF_ATTN_NO_SPLIT) ? 1 : 0;
     p.mix = (inject & TF_ATTN_HINT_MIX) ? 1 : 0;
     p.partials = reinterpret_cast<float*>(
@@ -2435,6 +2548,188 @@ extern "C" int tf_ext_attn_fwd_strided(const void* q, const void* k, const void*
     p.c = (float)((double)scale * 1.4426950408889634);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     return dtype == TF_BF16 ? dispatch_dh<BF16>(Dh, p, v, st) : dispatch_dh<F16>(Dh, p, v, st);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Runs form: attention over a bank that arrives in pieces (include/tokenflow_hip.h, "run + merge").
+//
+// Workspace of one run SET: V^T image of the whole bank | key norm bounds of the whole bank | slots filled per run (n_runs
+// ints) | partial results [2 banks][Kq][H][S][n_runs * spr][Dh + 8] fp32.  Every run writes only the positions of its own
+// frames in the first two, its own int in the third and its own spr slots in the last: the runs of one bank may execute
+// concurrently.
+namespace {
+
+struct RunsLayout {
+    int Spad, spr;   // spr = slots per run
+    size_t knorm_off, hdr_off, part_off, bytes;
+};
+
+// Slots a run owns: the largest split any run of this bank can take (split_plan never grows when the frame count shrinks).
+static int runs_slots_per_run(int K, int Kq, int S, int H, int Dh) {
+    const int a = split_plan(K, Kq, S, H, Dh, false, 0, true), b = split_plan(K, Kq, S, H, Dh, true, 0, true);
+    return a > b ? a : b;
+}
+
+static RunsLayout runs_layout(int K, int Kq, int S, int H, int Dh, int n_runs) {
+    RunsLayout L;
+    L.Spad = ((S + 127) / 128) * 128;
+    L.spr = runs_slots_per_run(K, Kq, S, H, Dh);
+    L.knorm_off = (vt_bytes(K, L.Spad, H, Dh) + 255) & ~(size_t)255;
+    L.hdr_off = L.knorm_off + (((size_t)3 * H * K * (L.Spad / 64) * sizeof(float) + 255) & ~(size_t)255);
+    L.part_off = L.hdr_off + (((size_t)n_runs * sizeof(int) + 255) & ~(size_t)255);
+    L.bytes = L.part_off + (size_t)2 * Kq * H * S * n_runs * L.spr * (Dh + 8) * sizeof(float);
+    return L;
+}
+
+static int runs_check_shape(const char* fn, int K, int Kq, int S, int H, int Dh, int n_runs, int dtype) {
+    TF_ARG(dtype == TF_BF16 || dtype == TF_F16, TF_ERR_DTYPE, "%s: dtype %d (bf16/f16 only)", fn, dtype);
+    TF_ARG(Dh == 40 || Dh == 64 || Dh == 80 || Dh == 160, TF_ERR_SHAPE, "%s: head dim %d not in {40,64,80,160}", fn, Dh);
+    TF_ARG(K > 0 && S > 0 && H > 0 && Kq > 0 && Kq <= K, TF_ERR_SHAPE, "%s: K=%d Kq=%d S=%d H=%d", fn, K, Kq, S, H);
+    TF_ARG(n_runs >= 1 && n_runs <= K, TF_ERR_SHAPE, "%s: %d runs over a bank of %d frames", fn, n_runs, K);
+    return 0;
+}
+
+// flag bits a run call refuses: it always takes the streaming kernels, and the source branch alone has no bank to run over
+constexpr int RUN_REFUSED = TF_ATTN_SOURCE_ONLY | TF_ATTN_FUSED | TF_ATTN_HINT_QW(7) | TF_ATTN_HINT_KW(7) | TF_ATTN_HINT_QB2 |
+                            TF_ATTN_PRECISE_P | TF_ATTN_NO_PRECISE_P;
+
+}  // namespace
+
+extern "C" size_t tf_ext_attn_runs_workspace_bytes(int K, int Kq, int S, int H, int Dh, int n_runs, int dtype) {
+    if (K <= 0 || Kq <= 0 || Kq > K || S <= 0 || H <= 0 || n_runs <= 0 || n_runs > K || dtype == TF_F32) return 0;
+    if (!(Dh == 40 || Dh == 64 || Dh == 80 || Dh == 160)) return 0;
+    return runs_layout(K, Kq, S, H, Dh, n_runs).bytes;
+}
+
+extern "C" int tf_ext_attn_run(const void* q, const void* k, const void* v, void* out, int K, int Kq, int q_frame0,
+                               int run_f0, int run_n, int run, int n_runs, int S, int H, int Dh, int64_t ld,
+                               const int64_t* strides, float scale, int flags, int dtype, void* ws, size_t ws_bytes,
+                               void* stream) {
+    TF_ARG(q && k && v && out && ws && strides, TF_ERR_NULL, "tf_ext_attn_run: null pointer");
+    if (const int rc = runs_check_shape("tf_ext_attn_run", K, Kq, S, H, Dh, n_runs, dtype)) return rc;
+    TF_ARG(ld >= (int64_t)H * Dh && ld % 8 == 0, TF_ERR_SHAPE, "tf_ext_attn_run: ld=%lld (a multiple of 8, >= H*Dh)",
+           (long long)ld);
+    TF_ARG(q_frame0 >= 0 && q_frame0 + Kq <= K, TF_ERR_SHAPE,
+           "tf_ext_attn_run: query frames [%d, %d) outside the %d-frame bank", q_frame0, q_frame0 + Kq, K);
+    TF_ARG(run >= 0 && run < n_runs, TF_ERR_SHAPE, "tf_ext_attn_run: run %d of %d", run, n_runs);
+    TF_ARG(run_n >= 1 && run_f0 >= 0 && run_f0 <= K - run_n, TF_ERR_SHAPE,
+           "tf_ext_attn_run: run of frames [%d, %d) empty or outside the %d-frame bank", run_f0, run_f0 + run_n, K);
+    TF_ARG(!(flags & RUN_REFUSED), TF_ERR_SHAPE,
+           "tf_ext_attn_run: flags 0x%x -- TF_ATTN_SOURCE_ONLY, TF_ATTN_FUSED and the fused kernel's hints have no run form",
+           flags & RUN_REFUSED);
+    const bool bank_only = (flags & TF_ATTN_BANK_ONLY) != 0;
+    TF_ARG(bank_only || (q_frame0 >= run_f0 && q_frame0 + Kq <= run_f0 + run_n), TF_ERR_SHAPE,
+           "tf_ext_attn_run: the source branch needs the query frames [%d, %d) inside the run [%d, %d) "
+           "(TF_ATTN_BANK_ONLY for the other runs)", q_frame0, q_frame0 + Kq, run_f0, run_f0 + run_n);
+    const int64_t ld_q = strides[8];
+    TF_ARG(ld_q >= (int64_t)H * Dh && ld_q % 8 == 0, TF_ERR_SHAPE,
+           "tf_ext_attn_run: q token stride %lld (a multiple of 8, >= H*Dh)", (long long)ld_q);
+    for (int i = 0; i < 8; ++i)
+        TF_ARG(strides[i] % 8 == 0 &&
+                   (i & 1 ? strides[i] >= (int64_t)(S - 1) * (i < 2 ? ld_q : i < 6 ? ld : (int64_t)H * Dh) : true),
+               TF_ERR_SHAPE, "tf_ext_attn_run: stride %d = %lld (multiples of 8 elements; a frame holds S token rows)", i,
+               (long long)strides[i]);
+    TF_ARG(tf_aligned16(q) && tf_aligned16(k) && tf_aligned16(v) && tf_aligned16(out) && tf_aligned16(ws), TF_ERR_ALIGN,
+           "tf_ext_attn_run: tensors not 16-byte aligned");
+    const RunsLayout L = runs_layout(K, Kq, S, H, Dh, n_runs);
+    TF_ARG(ws_bytes >= L.bytes, TF_ERR_WORKSPACE, "tf_ext_attn_run: workspace %zu < %zu bytes", ws_bytes, L.bytes);
+
+    unsigned char* const w8 = static_cast<unsigned char*>(ws);
+    const int ppf = L.Spad / 64;
+    AttnParams p{};
+    // the frame window is folded into K and the base pointers: the kernels see a bank of run_n frames that starts at run_f0
+    // (frame f of the caller's k / v lives at base + f * frame stride; the V^T image and the norm table keep the whole
+    // bank's row strides, p.Kb)
+    p.q = q;
+    p.k = static_cast<const unsigned char*>(k) + (int64_t)run_f0 * strides[3] * 2;
+    const void* v_run = static_cast<const unsigned char*>(v) + (int64_t)run_f0 * strides[5] * 2;
+    p.vt = w8 + (size_t)run_f0 * L.Spad * 2;
+    p.knorm2 = reinterpret_cast<const float*>(w8 + L.knorm_off) + (size_t)run_f0 * ppf;
+    p.out = out;
+    p.K = run_n;
+    p.Kb = K;
+    p.Kq = Kq;
+    p.q_frame0 = bank_only ? 0 : q_frame0 - run_f0;
+    p.S = S;
+    p.H = H;
+    p.Spad = L.Spad;
+    p.nQT = (S + 127) / 128;
+    p.inject = (flags & TF_ATTN_INJECT) ? 1 : 0;
+    p.part = bank_only ? TF_ATTN_BANK_ONLY : 0;
+    p.fold = (flags & TF_ATTN_FOLD_SCALE) ? 1 : 0;
+    p.out_f32 = (flags & TF_ATTN_OUT_F32) ? 1 : 0;
+    const int ns = split_plan(run_n, Kq, S, H, Dh, p.inject != 0, p.part, !(flags & TF_ATTN_NO_SPLIT));
+    p.nseg = ns < L.spr ? ns : L.spr;
+    p.pslots = n_runs * L.spr;
+    p.run = 1;
+    p.run_hdr = reinterpret_cast<int*>(w8 + L.hdr_off) + run;
+    p.bit_stable = 1;   // the kernel choice of a run is a function of its arguments: the mixed-shape form only on TF_ATTN_HINT_MIX
+    p.mix = (flags & TF_ATTN_HINT_MIX) ? 1 : 0;
+    p.partials = reinterpret_cast<float*>(w8 + L.part_off) + (size_t)run * L.spr * (Dh + 8);
+    p.ld = ld;
+    p.ld_q = ld_q;
+    p.q_bs = strides[0];
+    p.q_fs = strides[1];
+    p.k_bs = strides[2];
+    p.k_fs = strides[3];
+    p.v_bs = strides[4];
+    p.v_fs = strides[5];
+    p.o_bs = strides[6];
+    p.o_fs = strides[7];
+    p.c = (float)((double)scale * 1.4426950408889634);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    return dtype == TF_BF16 ? dispatch_dh<BF16>(Dh, p, v_run, st) : dispatch_dh<F16>(Dh, p, v_run, st);
+}
+
+extern "C" int tf_ext_attn_runs_merge(void* out, int K, int Kq, int S, int H, int Dh, int n_runs, int64_t out_branch_stride,
+                                      int64_t out_frame_stride, int flags, int dtype, void* ws, size_t ws_bytes,
+                                      void* stream) {
+    TF_ARG(out && ws, TF_ERR_NULL, "tf_ext_attn_runs_merge: null pointer");
+    if (const int rc = runs_check_shape("tf_ext_attn_runs_merge", K, Kq, S, H, Dh, n_runs, dtype)) return rc;
+    TF_ARG(out_branch_stride % 8 == 0 && out_frame_stride % 8 == 0 && out_frame_stride >= (int64_t)(S - 1) * H * Dh,
+           TF_ERR_SHAPE, "tf_ext_attn_runs_merge: out strides %lld, %lld (multiples of 8 elements; a frame holds S token rows)",
+           (long long)out_branch_stride, (long long)out_frame_stride);
+    TF_ARG(tf_aligned16(out) && tf_aligned16(ws), TF_ERR_ALIGN, "tf_ext_attn_runs_merge: tensors not 16-byte aligned");
+    const RunsLayout L = runs_layout(K, Kq, S, H, Dh, n_runs);
+    TF_ARG(ws_bytes >= L.bytes, TF_ERR_WORKSPACE, "tf_ext_attn_runs_merge: workspace %zu < %zu bytes", ws_bytes, L.bytes);
+    if (tf_plan_note("merge[runs=%d]", n_runs)) return 0;
+    unsigned char* const w8 = static_cast<unsigned char*>(ws);
+    const int64_t total = (int64_t)2 * Kq * H * S * (Dh / 4);
+    const int64_t blocks = (total + 255) / 256;
+    const dim3 grid((unsigned)(blocks < 8192 ? blocks : 8192));
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const float* part = reinterpret_cast<const float*>(w8 + L.part_off);
+    const int* hdr = reinterpret_cast<const int*>(w8 + L.hdr_off);
+    const int f32 = (flags & TF_ATTN_OUT_F32) ? 1 : 0;
+    if (dtype == TF_BF16)
+        hipLaunchKernelGGL(attn_runs_merge_kernel<BF16>, grid, dim3(256), 0, st, part, hdr, out, Kq, S, H, Dh, n_runs, L.spr, f32,
+                           out_branch_stride, out_frame_stride);
+    else
+        hipLaunchKernelGGL(attn_runs_merge_kernel<F16>, grid, dim3(256), 0, st, part, hdr, out, Kq, S, H, Dh, n_runs, L.spr, f32,
+                           out_branch_stride, out_frame_stride);
+    TF_LAUNCH_CHECK("tf_ext_attn_runs_merge");
+    return 0;
+}
+
+// Launch plan of ONE run call over run_n of the bank's K frames (dense tensors, the run and the query frames at frame 0)
+// followed by the merge of n_runs runs, recorded by the entry points themselves as tf_ext_attn_plan does.
+extern "C" int tf_ext_attn_run_plan(int K, int Kq, int run_n, int n_runs, int S, int H, int Dh, int flags, int dtype, char* buf,
+                                    size_t len) {
+    if (const int rc = runs_check_shape("tf_ext_attn_run_plan", K, Kq, S, H, Dh, n_runs, dtype)) return rc;
+    void* const ph = reinterpret_cast<void*>((uintptr_t)1 << 12);
+    const int64_t ld = (int64_t)H * Dh, fs = (int64_t)S * ld;
+    const int64_t strides[9] = {Kq * fs, fs, K * fs, fs, K * fs, fs, Kq * fs, fs, ld};
+    const size_t wsb = tf_ext_attn_runs_workspace_bytes(K, Kq, S, H, Dh, n_runs, dtype);
+    TfPlanRec rec{buf, len, 0, 0};
+    if (buf && len) buf[0] = 0;
+    tf_plan_rec = &rec;
+    int rc = tf_ext_attn_run(ph, ph, ph, ph, K, Kq, 0, 0, run_n, 0, n_runs, S, H, Dh, ld, strides, 1.0f, flags, dtype, ph, wsb,
+                             nullptr);
+    if (!rc) rc = tf_ext_attn_runs_merge(ph, K, Kq, S, H, Dh, n_runs, Kq * fs, fs, flags, dtype, ph, wsb, nullptr);
+    tf_plan_rec = nullptr;
+    if (rc) return rc;
+    TF_ARG(rec.used < len, TF_ERR_WORKSPACE, "tf_ext_attn_run_plan: the plan needs %zu bytes", rec.used + 1);
+    return rec.n;
 }
 
 // Launch plan of tf_ext_attn_fwd for dense tensors (ld = H*Dh): the entry point itself runs under the plan recorder

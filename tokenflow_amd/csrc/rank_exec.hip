@@ -16,6 +16,8 @@
 // collectives of ONE RCCL communicator execute in issue order, and a 10 MB halo message in front of the next block's
 // all-to-all would sit on the critical path); it has the rest of the pass to arrive.  All ordering is by events; no
 // host synchronisation anywhere.
+// TF_RANK_BANK_RUNS uses the same auxiliary compute stream for the LOCAL run of the bank (the rank's own keyframes: source
+// branch + bank branches, forked behind the pack and in front of the gather, joined in front of the merge).
 #include <stdlib.h>
 
 #include <new>
@@ -78,6 +80,19 @@ struct Layout {   // exchange buffers of one call inside the caller's workspace
     size_t ws_bank_bytes, ws_src_bytes;
 };
 
+// TF_RANK_BANK_RUNS: the runs of the bank a rank computes, in SLOT order -- its own keyframes, the frames to their left, the
+// frames to their right (the empty ones dropped).  The order fixes the arithmetic of the merge, whatever the schedule.
+struct Runs {
+    int n, f0[3], len[3];
+};
+Runs rank_runs(const tf_rank* rk) {
+    Runs r{};
+    r.f0[r.n] = rk->kf0, r.len[r.n] = rk->Kl, ++r.n;
+    if (rk->kf0 > 0) r.f0[r.n] = 0, r.len[r.n] = rk->kf0, ++r.n;
+    if (rk->kf0 + rk->Kl < rk->K) r.f0[r.n] = rk->kf0 + rk->Kl, r.len[r.n] = rk->K - rk->kf0 - rk->Kl, ++r.n;
+    return r;
+}
+
 Layout layout(const tf_rank* rk, int S, int H, int Dh, int dtype, int mode) {
     const size_t eb = 2;
     const int W = rk->world, Kl = rk->Kl, K = rk->K;
@@ -99,6 +114,12 @@ Layout layout(const tf_rank* rk, int S, int H, int Dh, int dtype, int mode) {
         L.ws_src_bytes = tf_ext_attn_workspace_bytes(Kl, S, H, Dh, dtype);
         L.ws_bank = take(L.ws_bank_bytes);
         L.ws_src = take(L.ws_src_bytes);
+    } else if (mode == TF_RANK_BANK_RUNS) {
+        // only what peers read travels: [k1, k2, v1, v2], under injection [k0, v1, v2] (sized for the former)
+        L.send = take((size_t)Kl * 4 * S * D * eb);
+        L.recv = take((size_t)K * 4 * S * D * eb);
+        L.ws_bank_bytes = tf_ext_attn_runs_workspace_bytes(K, Kl, S, H, Dh, rank_runs(rk).n, dtype);
+        L.ws_bank = take(L.ws_bank_bytes);
     } else {
         L.send = take((size_t)Kl * 6 * S * D * eb);
         L.recv = take((size_t)K * 6 * S * D * eb);
@@ -170,7 +191,9 @@ extern "C" size_t tf_rank_pivotal_workspace_bytes(const tf_rank* rk, int S, int 
     if (rk->world == 1) return up256(tf_ext_attn_workspace_bytes(rk->K, S, H, Dh, dtype));
     const size_t bank = layout(rk, S, H, Dh, dtype, TF_RANK_BANK).total;
     const size_t heads = H % rk->world == 0 ? layout(rk, S, H, Dh, dtype, TF_RANK_HEADS).total : 0;
-    return bank > heads ? bank : heads;
+    const size_t runs = layout(rk, S, H, Dh, dtype, TF_RANK_BANK_RUNS).total;   // hosts size ONE workspace for every mode
+    const size_t two = bank > heads ? bank : heads;
+    return two > runs ? two : runs;
 }
 
 extern "C" int tf_rank_pivotal(tf_rank* rk, const void* q, const void* k, const void* v, const int64_t* st_in,
@@ -182,7 +205,8 @@ extern "C" int tf_rank_pivotal(tf_rank* rk, const void* q, const void* k, const 
     TF_ARG(rk && q && k && v && st_in && kfo_ext && ws && (no_halo || (piv_ext && inv_ext)), TF_ERR_NULL,
            "tf_rank_pivotal: null pointer");
     TF_ARG(dtype == TF_BF16 || dtype == TF_F16, TF_ERR_DTYPE, "tf_rank_pivotal: dtype %d (bf16/f16 only)", dtype);
-    TF_ARG(mode == TF_RANK_HEADS || mode == TF_RANK_BANK, TF_ERR_SHAPE, "tf_rank_pivotal: mode %d", mode);
+    TF_ARG(mode == TF_RANK_HEADS || mode == TF_RANK_BANK || mode == TF_RANK_BANK_RUNS, TF_ERR_SHAPE,
+           "tf_rank_pivotal: mode %d", mode);
     TF_ARG(slot >= 0 && slot < TF_RANK_SLOTS, TF_ERR_SHAPE, "tf_rank_pivotal: slot %d outside [0, %d)", slot, TF_RANK_SLOTS);
     TF_ARG(!(want_inv && no_halo), TF_ERR_SHAPE, "tf_rank_pivotal: TF_RANK_INV_NORM needs the propagation state (no TF_RANK_NO_HALO)");
     TF_ARG(!(flags & (TF_ATTN_BANK_ONLY | TF_ATTN_SOURCE_ONLY)), TF_ERR_SHAPE,
@@ -323,6 +347,64 @@ extern "C" int tf_rank_pivotal(tf_rank* rk, const void* q, const void* k, const 
         void* dsts[2] = {out_loc + o_bs, out_loc + 2 * o_bs};
         const int64_t dfs[2] = {SD, SD};
         if (const int rc = tf_head_unpack(recv2, dsts, dfs, 2, W, Kl, S, (int)hd, D, 2, stream)) return rc;
+    } else if (mode == TF_RANK_BANK_RUNS) {
+        // ---- the bank in runs: the local run starts before the gather lands (tf_ext_attn_run / tf_ext_attn_runs_merge)
+        const Layout L = layout(rk, S, H, Dh, dtype, TF_RANK_BANK_RUNS);
+        E* send = reinterpret_cast<E*>(wsb + L.send);
+        E* recv = reinterpret_cast<E*>(wsb + L.recv);
+        void* wsr = wsb + L.ws_bank;
+        const Runs R = rank_runs(rk);
+        // 1. pack only what PEERS read: the source branch's k and v stay at home (2 of 6 slabs; 1 of 4 under injection, where
+        //    the source k IS the bank's k)
+        const void* slabs[4];
+        int64_t fss[4];
+        int ns;
+        if (inject) {
+            ns = 3;
+            slabs[0] = ke, slabs[1] = ve + v_bs, slabs[2] = ve + 2 * v_bs;
+            fss[0] = k_fs, fss[1] = fss[2] = v_fs;
+        } else {
+            ns = 4;
+            slabs[0] = ke + k_bs, slabs[1] = ke + 2 * k_bs, slabs[2] = ve + v_bs, slabs[3] = ve + 2 * v_bs;
+            fss[0] = fss[1] = k_fs, fss[2] = fss[3] = v_fs;
+        }
+        if (const int rc = tf_head_pack_norm(slabs, fss, ns, send, 1, Kl, S, (int)D, ld, 2, piv_loc, inv_loc,
+                                             (int64_t)Kl * S, (int)D, dtype, stream))
+            return rc;
+        // 2. the LOCAL run on the auxiliary compute stream, forked behind the pack and in FRONT of the gather: the source
+        //    branch of the rank's frames and their bank branches against the rank's OWN keyframes, read from the caller's
+        //    q / k / v in place.  Bank frame f of the caller's k / v lives at base + (f - kf0) * frame stride: the shifted
+        //    base is formed as an integer (it may lie in front of the tensor; only the run's frames are dereferenced).
+        auto shifted = [](const E* base, int64_t elems) {
+            return reinterpret_cast<const E*>(reinterpret_cast<uintptr_t>(base) + (uintptr_t)(elems * (int64_t)sizeof(E)));
+        };
+        const int run_flags = flags & (TF_ATTN_INJECT | TF_ATTN_FOLD_SCALE | TF_ATTN_HINT_MIX | TF_ATTN_NO_SPLIT);
+        {
+            if (const int rc = order(rk, st, rk->as, "tf_rank_pivotal")) return rc;
+            const int64_t strides[9] = {q_bs, q_fs, k_bs, k_fs, v_bs, v_fs, o_bs, SD, ld_q};
+            if (const int rc = tf_ext_attn_run(q, shifted(ke, -(int64_t)rk->kf0 * k_fs), shifted(ve, -(int64_t)rk->kf0 * v_fs),
+                                               out_loc, K, Kl, rk->kf0, R.f0[0], R.len[0], 0, R.n, S, H, Dh, ld, strides,
+                                               scale, run_flags, dtype, wsr, L.ws_bank_bytes, rk->as))
+                return rc;
+        }
+        // 3. the gather stays on the caller's stream: every collective of a communicator on ONE stream (see the heads form)
+        if (const int rc = tf_allgather_rows(rk->comm, send, recv, cnt, ns * SD, dtype, st)) return rc;
+        // 4. behind it the remote runs, read from the receive buffer [K][slabs][S][D] in place (bank branches only: the
+        //    base of a tensor whose branch 0 does not exist lies one slab in front of its first slab)
+        const int64_t fs_r = ns * SD;
+        const E* kb = inject ? recv : shifted(recv, -SD);            // [k0 | ...] or [k1, k2 | ...]
+        const E* vb = inject ? recv : shifted(recv, SD);             // [k0, v1, v2] or [k1, k2, v1, v2]
+        const int64_t rstrides[9] = {q_bs, q_fs, SD, fs_r, SD, fs_r, o_bs, SD, ld_q};
+        for (int r = 1; r < R.n; ++r)
+            if (const int rc = tf_ext_attn_run(q, kb, vb, out_loc, K, Kl, rk->kf0, R.f0[r], R.len[r], r, R.n, S, H, Dh, D,
+                                               rstrides, scale, run_flags | TF_ATTN_BANK_ONLY, dtype, wsr, L.ws_bank_bytes,
+                                               stream))
+                return rc;
+        //    join the local run, merge into the local slots of kfo_ext
+        if (const int rc = order(rk, rk->as, st, "tf_rank_pivotal")) return rc;
+        if (const int rc = tf_ext_attn_runs_merge(out_loc, K, Kl, S, H, Dh, R.n, o_bs, SD, run_flags, dtype, wsr,
+                                                  L.ws_bank_bytes, stream))
+            return rc;
     } else {
         // ---- ONE collective: the slabs the attention reads across frames, gathered into [K][slabs][S][D]
         const Layout L = layout(rk, S, H, Dh, dtype, TF_RANK_BANK);

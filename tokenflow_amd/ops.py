@@ -137,6 +137,16 @@ def attn_plan(K: int, Kq: int, S: int, heads: int, dh: int, inject: bool, dtype:
     return _plan_tokens("tf_ext_attn_plan", _lib.load().tf_ext_attn_plan, K, Kq, S, heads, dh, flags, _DT[dtype])
 
 
+def attn_run_plan(K: int, Kq: int, run_n: int, n_runs: int, S: int, heads: int, dh: int, inject: bool,
+                  dtype: torch.dtype = torch.bfloat16, bank_only: bool = False, out_dtype: Optional[torch.dtype] = None,
+                  fold_scale: Optional[bool] = None, no_split: bool = False, hints: int = 0) -> list:
+    """The launches of ONE run call of `ext_attn_runs` over run_n of the bank's K frames, followed by the merge of n_runs
+    runs, as tokens (tf_ext_attn_run_plan: e.g. ['vt_pack', 'il<40,8,ALL,4,2,run>', 'merge[runs=3]']).  Host only."""
+    flags = _run_flags(inject, bank_only, out_dtype == torch.float32, fold_scale, no_split, hints)
+    return _plan_tokens("tf_ext_attn_run_plan", _lib.load().tf_ext_attn_run_plan, K, Kq, run_n, n_runs, S, heads, dh, flags,
+                        _DT[dtype])
+
+
 def nn_plan(n_tgt: int, S: int, D: int, P: int, C: int = 1) -> list:
     """The search launches of `nn_search` (C = 1) or of `propagate_chunks` over C > 1 chunks of n_tgt targets (P = 2),
     as tokens (tf_nn_search_plan: e.g. ['glds[splits=2]', 'finalize']).  Host only: needs no GPU."""
@@ -244,6 +254,116 @@ def ext_attn_views(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch
     _launch(dev, "tf_ext_attn_fwd_strided", lib.tf_ext_attn_fwd_strided, qp, kp, vp, op, K, Kq, int(q_frame0), S, heads,
             dh, ld, ctypes.cast(strides, ctypes.c_void_p), float(scale), flags, dt, ws.data_ptr(), ws.numel(),
             stream=stream)
+    return out
+
+
+def _run_flags(inject: bool, bank_only: bool, out_f32: bool, fold_scale: Optional[bool], no_split: bool, hints: int) -> int:
+    """The TF_ATTN_* bit mask of a run / merge call (the module default TOKENFLOW_ATTN_NO_SPLIT does not apply: a run set is
+    a split form by construction; no_split=True only keeps a run from splitting itself further)."""
+    return ((1 if inject else 0) | (_lib.TF_ATTN_FOLD_SCALE if (FOLD_SCALE if fold_scale is None else fold_scale) else 0) |
+            (_lib.TF_ATTN_OUT_F32 if out_f32 else 0) | (_lib.TF_ATTN_BANK_ONLY if bank_only else 0) |
+            (_lib.TF_ATTN_NO_SPLIT if no_split else 0) | int(hints))
+
+
+def ext_attn_runs_views(q: torch.Tensor, kv_runs: Sequence, out: torch.Tensor, heads: int, scale: float, inject: bool,
+                        runs: Sequence, K: int, branch0=(0, 0), q_frame0: int = 0, streams: Optional[Sequence] = None,
+                        fold_scale: Optional[bool] = None, no_split: bool = False, hints: int = 0,
+                        order: Optional[Sequence[int]] = None) -> torch.Tensor:
+    """Extended attention over a K-frame bank held in pieces (tf_ext_attn_run + tf_ext_attn_runs_merge).
+    runs: [(f0, n), ...] partitions [0, K); run 0 holds the query frames q_frame0 .. +Kq-1 and computes their source
+    branch, the others compute bank branches only.  kv_runs[r] = (k_view, v_view, k_branch0, v_branch0): strided 4-D
+    views [branches, n, S, D] of run r's frames only, wherever they live (the caller's own projection output, the
+    receive buffer of a collective), holding the branches k_branch0.. / v_branch0.. as in `ext_attn_views`.
+    q, out: views [branches, Kq, S, D] with first branches branch0 = (q, out); out dense in its last two dims.
+    streams: None, or one entry per run -- a torch.cuda.Stream to issue that run on (None = the current stream); the
+    runs are forked behind the current stream and joined in front of the merge, which runs on the current stream.
+    order: the order in which the run calls are issued (default 0, 1, ...); the result does not depend on it.
+    ONE workspace serves the whole run set."""
+    dev = _need_gpu(q, out, *[t for kv in kv_runs for t in kv[:2]])
+    lib = _lib.load()
+    S, D = q.shape[2], q.shape[3]
+    Kq, dh, n_runs = q.shape[1], D // heads, len(runs)
+    dt = _DT.get(q.dtype)
+    if dt is None or dt == _lib.TF_F32 or D % heads or len(kv_runs) != n_runs:
+        raise TypeError("ext_attn_runs_views: q/k/v must share dtype bf16 or f16; one (k, v) pair of views per run")
+    if sorted(f for f0, n in runs for f in range(f0, f0 + n)) != list(range(K)) or any(n < 1 for _, n in runs):
+        raise ValueError(f"ext_attn_runs_views: runs {list(runs)} do not partition the {K}-frame bank")
+    if out.dtype not in (q.dtype, torch.float32) or out.shape[1] != Kq:
+        raise TypeError("ext_attn_runs_views: out dtype / frames")
+    qp, q_bs, q_fs, ld_q = _view_base(q, branch0[0], S, "q")
+    op, o_bs, o_fs, ld_o = _view_base(out, branch0[1], S, "out")
+    if ld_o != D:
+        raise ValueError("ext_attn_runs_views: out needs a dense token stride")
+    out_f32 = out.dtype == torch.float32
+    nbytes = lib.tf_ext_attn_runs_workspace_bytes(K, Kq, S, heads, dh, n_runs, dt)
+    ws = _workspace(nbytes, q.device, tag="attn_runs")     # one per run SET: keyed by the current stream, not by the runs' streams
+    cur = torch.cuda.current_stream(dev)
+    fork = None
+    used = []
+    for r in (range(n_runs) if order is None else order):
+        f0, n = runs[r]
+        kv, vv, kb0, vb0 = kv_runs[r]
+        if kv.dtype != q.dtype or vv.dtype != q.dtype or kv.shape[1] != n or vv.shape[1] != n:
+            raise TypeError("ext_attn_runs_views: a run's k / v views hold that run's frames in the dtype of q")
+        kp, k_bs, k_fs, ld = _view_base(kv, kb0, S, "k")
+        vp, v_bs, v_fs, ld_v = _view_base(vv, vb0, S, "v")
+        if ld_v != ld:
+            raise ValueError("ext_attn_runs_views: k and v of a run need one token stride")
+        es = kv.element_size()
+        strides = (ctypes.c_int64 * 9)(q_bs, q_fs, k_bs, k_fs, v_bs, v_fs, o_bs, o_fs, ld_q)
+        flags = _run_flags(inject, r != 0, out_f32, fold_scale, no_split, hints)
+        st = streams[r] if streams is not None else None
+        if st is not None:
+            if fork is None:
+                fork = torch.cuda.Event()
+                fork.record(cur)
+            st.wait_event(fork)
+            used.append(st)
+        # frame f of the bank at base + f * frame stride: the views start at the run's first frame
+        _launch(dev, "tf_ext_attn_run", lib.tf_ext_attn_run, qp, kp - f0 * k_fs * es, vp - f0 * v_fs * es, op, K, Kq,
+                int(q_frame0), f0, n, r, n_runs, S, heads, dh, ld, ctypes.cast(strides, ctypes.c_void_p), float(scale),
+                flags, dt, ws.data_ptr(), ws.numel(), stream=None if st is None else st.cuda_stream)
+    for st in used:
+        ev = torch.cuda.Event()
+        ev.record(st)
+        cur.wait_event(ev)
+    _launch(dev, "tf_ext_attn_runs_merge", lib.tf_ext_attn_runs_merge, op, K, Kq, S, heads, dh, n_runs, o_bs, o_fs,
+            _run_flags(inject, False, out_f32, fold_scale, no_split, hints), dt, ws.data_ptr(), ws.numel())
+    return out
+
+
+def ext_attn_runs(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, scale: float, inject: bool,
+                  runs: Sequence, q_frame0: int = 0, out: Optional[torch.Tensor] = None,
+                  out_dtype: Optional[torch.dtype] = None, streams: Optional[Sequence] = None,
+                  fold_scale: Optional[bool] = None, no_split: bool = False, hints: int = 0,
+                  order: Optional[Sequence[int]] = None) -> torch.Tensor:
+    """`ext_attn` computed run by run over the bank: k, v [3K,S,D], q [3Kq,S,D] (the queries of keyframes q_frame0 ..),
+    runs = [(f0, n), ...] a partition of the K bank frames whose FIRST entry contains the query frames and computes
+    the source branch.  Returns [3Kq,S,D] (fp32 with out_dtype=torch.float32).  The result is a function of the runs
+    alone (not of `order` or `streams`); it equals the oracle within the attention bound, not `ext_attn` bit for bit:
+    the merge re-associates fp32 sums as the split form's does."""
+    _need_gpu(q, k, v, out)
+    B, S, D = k.shape
+    Bq = q.shape[0]
+    if B % 3 or Bq % 3 or D % heads or q.shape[1:] != k.shape[1:] or v.shape != k.shape:
+        raise ValueError(f"ext_attn_runs: bad shapes q{tuple(q.shape)} k{tuple(k.shape)} v{tuple(v.shape)} heads {heads}")
+    K, Kq = B // 3, Bq // 3
+    if q.dtype not in (torch.bfloat16, torch.float16) or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise TypeError(f"ext_attn_runs: q/k/v must share dtype bf16 or f16, got {q.dtype},{k.dtype},{v.dtype}")
+    q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+    if out_dtype is None:
+        out_dtype = out.dtype if out is not None else q.dtype
+    if out_dtype not in (q.dtype, torch.float32):
+        raise TypeError(f"ext_attn_runs: out_dtype {out_dtype} (the input dtype or float32)")
+    if out is None:
+        out = torch.empty(Bq, S, D, dtype=out_dtype, device=q.device)
+    elif out.dtype != out_dtype or not out.is_contiguous() or out.shape != (Bq, S, D):
+        raise ValueError("ext_attn_runs: `out` must be a contiguous [3Kq,S,D] tensor of out_dtype")
+    k4, v4 = k.view(3, K, S, D), v.view(3, K, S, D)
+    kv_runs = [(k4[:, f0:f0 + n], v4[:, f0:f0 + n], 0, 0) for f0, n in runs]
+    ext_attn_runs_views(q.view(3, Kq, S, D), kv_runs, out.view(3, Kq, S, D), heads, scale, inject, runs, K,
+                        q_frame0=q_frame0, streams=streams, fold_scale=fold_scale, no_split=no_split, hints=hints,
+                        order=order)
     return out
 
 

@@ -29,6 +29,15 @@ side stream ordered against the compute stream with events):
         one pack and one attention call per block instead of two collectives, pack, unpack and two
         calls: chosen per block (`auto_mode`) where the exchange is latency-bound (the mid block),
         and whenever the heads do not divide over the ranks.
+    "bank_runs" (opt-in: `bank_runs=True` / TOKENFLOW_SHARD_BANK_RUNS=1 lets `auto_mode` answer it in place of "bank"
+        for S >= BANK_RUNS_MIN_S; or mode="bank_runs"): the bank form in RUNS of keyframes.  Only the slabs PEERS read
+        are gathered (4 instead of 6; 3 instead of 4 with injection: the source branch's k and v stay at home), the
+        LOCAL run -- source branch + bank branches against the rank's own keyframes, read in place -- needs nothing
+        from the gather and starts in front of it (NativeShard: on the auxiliary compute stream), the remote runs
+        (frames left of the rank's own, then right) follow when the gather has landed, and one merge folds the runs'
+        partial results in the fixed order local, left, right (`ops.ext_attn_runs_views`).  The merge re-associates
+        fp32 sums: this mode equals a single-process `ops.ext_attn_runs` with the same runs bit for bit and the
+        oracle within the attention bound -- NOT the bit-stable single-GPU call.
 
  2. propagation passes -- chunk c needs keyframes c and c-1 (331-333): the first local chunk's
     left neighbour lives on rank r-1, so each rank sends its LAST keyframe's pivot features,
@@ -121,8 +130,21 @@ class FrameShard:
     """K keyframes (= chunks) over the ranks of `group` in contiguous runs; the first K % W ranks hold one more
     (cfg5's 25 chunks over 8 ranks -> 4,3,3,3,3,3,3,3)."""
 
+    # `auto_mode` under the bank_runs opt-in: "bank_runs" in place of "bank" from this many tokens per frame on.  A run set is
+    # three pre-passes, three launches and a merge where "bank" is one of each, so the coarse levels keep the one-call form.
+    # profiles/r07_rank_bank_runs_ab.txt (cfg5, rank 0 and 1 of 8, native executor on the loopback transport): levels 0 and 1
+    # (S = 4096, 1024) are ahead of "bank" under both wire models AND with the wire off; level 2 (S = 256) only under the wire
+    # model (not measured without), level 3 a tie; a step with this threshold equals the forced "bank_runs" step within the spread.
+    BANK_RUNS_MIN_S = 1024
+
     def __init__(self, K: int, group: Optional[dist.ProcessGroup] = None, comm=None,
-                 attn_split: Optional[bool] = None, halo_group: Optional[dist.ProcessGroup] = None, halo_comm=None):
+                 attn_split: Optional[bool] = None, halo_group: Optional[dist.ProcessGroup] = None, halo_comm=None,
+                 bank_runs: Optional[bool] = None):
+        # bank_runs: opt-in for `auto_mode` (mode=None callers, the hook path): "bank_runs" where it would answer "bank"
+        # and S >= BANK_RUNS_MIN_S.  None reads TOKENFLOW_SHARD_BANK_RUNS.  Off: today's answers.
+        if bank_runs is None:
+            bank_runs = os.environ.get("TOKENFLOW_SHARD_BANK_RUNS", "0") not in ("", "0")
+        self.bank_runs = bool(bank_runs)
         # attn_split: let the attention split a rank's small grid over extra workgroups and merge (faster: -15..40 %
         # on a rank's attention at 8 GPUs, DESIGN.md 4.1; results then agree with the single-GPU ones within the
         # output rounding).  Default False: one pass per bank problem, arithmetic independent of the grid, sharded
@@ -233,14 +255,17 @@ class FrameShard:
         return None
 
     # ------------------------------------------------------------------ pivotal pass
-    def _bank_gather(self, k_local: torch.Tensor, v_local: torch.Tensor, inject: bool):
+    def _bank_gather(self, k_local: torch.Tensor, v_local: torch.Tensor, inject: bool, peers_only: bool = False):
         """ONE collective per block: the slabs of the local keyframes that the attention reads across frames --
         without injection k and v of all three branches ([k0,k1,k2,v0,v1,v2]: the source slabs ride along so that the
         gathered buffer is the whole [3,K,S,D] bank of ONE attention call), with injection [k0,v0,v1,v2] -- are packed
         frame-major by one `tf_head_pack` launch (W = 1: a plain slab pack), gathered straight into
         [K (global frame order), slabs, S, D], and read there in place through strided views.  Runs of different
         lengths (K % W != 0) use the row form of the all-gather (no padding, no compaction copies).
-        Returns (k view [3 or 1, K, S, D], v view [3, K, S, D])."""
+        Returns (k view [3 or 1, K, S, D], v view [3, K, S, D]).
+        peers_only (the "bank_runs" form): only the slabs PEERS read travel -- [k1,k2,v1,v2], with injection [k0,v1,v2];
+        returns (k view [2 or 1, K, S, D] = branches 1.. or 0, v view [2, K, S, D] = branches 1.., local k view
+        [3, Kl, S, D], local v view): the rank's own frames are read where they are."""
         B, S, D = k_local.shape
         Kl, K, W = self.Kl, self.K, self.world
         dev, dt = k_local.device, k_local.dtype
@@ -252,10 +277,14 @@ class FrameShard:
         k3, v3 = frames(k_local), frames(v_local)
         if k3.stride(2) != v3.stride(2):
             k3, v3 = k3.contiguous(), v3.contiguous()
-        slabs = [k3[0], v3[0], v3[1], v3[2]] if inject else [k3[0], k3[1], k3[2], v3[0], v3[1], v3[2]]
+        if peers_only:
+            slabs = [k3[0], v3[1], v3[2]] if inject else [k3[1], k3[2], v3[1], v3[2]]
+        else:
+            slabs = [k3[0], v3[0], v3[1], v3[2]] if inject else [k3[0], k3[1], k3[2], v3[0], v3[1], v3[2]]
         ns = len(slabs)
-        send = ops.head_pack(slabs, 1, out=self._buf("bank_send", (1, Kl, ns, S, D), dt, dev)).view(Kl, ns * S * D)
-        recv = self._buf("bank_recv", (K, ns * S * D), dt, dev)
+        tag = "runs" if peers_only else "bank"
+        send = ops.head_pack(slabs, 1, out=self._buf(tag + "_send", (1, Kl, ns, S, D), dt, dev)).view(Kl, ns * S * D)
+        recv = self._buf(tag + "_recv", (K, ns * S * D), dt, dev)
         comm = getattr(self, "comm", None)
         if self.even:
             if comm is None:
@@ -288,6 +317,8 @@ class FrameShard:
         else:
             self._side([recv, send], lambda st: comm.allgather_rows(send, recv, self.counts, stream=st)).wait()
         rp = recv.view(K, ns, S, D).permute(1, 0, 2, 3)        # [ns, K, S, D] views: frame stride ns*S*D
+        if peers_only:
+            return ((rp[0:1], rp[1:3]) if inject else (rp[0:2], rp[2:4])) + (k3, v3)
         return (rp[0:1], rp[1:4]) if inject else (rp[0:3], rp[3:6])
 
     def auto_mode(self, heads: int, S: int) -> str:
@@ -296,14 +327,15 @@ class FrameShard:
         is ONE collective and ONE attention call instead of two collectives, a pack, an unpack and two calls: the
         choice where a block is a few tens of microseconds of work (S <= 64: the mid block) and the exchange is
         latency-, not volume-bound -- and the only one when the heads do not divide over the ranks."""
-        if heads % self.world:
-            return "bank"
-        return "bank" if S <= 64 else "heads"
+        mode = "bank" if (heads % self.world or S <= 64) else "heads"
+        if mode == "bank" and getattr(self, "bank_runs", False) and S >= self.BANK_RUNS_MIN_S:
+            return "bank_runs"     # opt-in (bank_runs=True / TOKENFLOW_SHARD_BANK_RUNS=1): the bank in runs, see the module text
+        return mode
 
     def pivotal_attention(self, q_local, k_local, v_local, heads: int, scale: float, inject: bool,
                           mode: Optional[str] = None, out4: Optional[torch.Tensor] = None):
         """Extended attention for the local keyframes against all K keyframes -> [3*Kl,S,D].
-        mode: "heads" | "bank" | None (= `auto_mode`, chosen per block).
+        mode: "heads" | "bank" | "bank_runs" | None (= `auto_mode`, chosen per block).
         out4: a [3,Kl,S,D] view (dense frames, free branch stride) the result is written into in place -- the
         keyframe slots 1.. of a halo-extended buffer (`ext_alloc`); returned as is."""
         if self.world == 1:
@@ -319,7 +351,39 @@ class FrameShard:
             mode = self.auto_mode(heads, q_local.shape[1])
         if mode == "heads":
             return self._pivotal_heads(q_local, k_local, v_local, heads, scale, inject, out4)
+        if mode == "bank_runs":
+            return self._pivotal_bank_runs(q_local, k_local, v_local, heads, scale, inject, out4)
         return self._pivotal_bank(q_local, k_local, v_local, heads, scale, inject, out4)
+
+    def bank_runs_of_rank(self):
+        """The runs of the bank this rank computes in the "bank_runs" form, in SLOT order: its own keyframes, the frames
+        to their left, the frames to their right (empty ones dropped).  The order fixes the merge's arithmetic."""
+        runs = [(self.kf0, self.Kl)]
+        if self.kf0 > 0:
+            runs.append((0, self.kf0))
+        if self.kf0 + self.Kl < self.K:
+            runs.append((self.kf0 + self.Kl, self.K - self.kf0 - self.Kl))
+        return runs
+
+    def _pivotal_bank_runs(self, q_local, k_local, v_local, heads: int, scale: float, inject: bool, out4=None):
+        """The bank form in runs (module text): the same packing, runs and slot order as the native executor's
+        TF_RANK_BANK_RUNS -- the same bits on the same transport.  The schedule here does not overlap (the gather is
+        waited for before the first run is issued; through gloo it is staged through the host anyway)."""
+        B, S, D = q_local.shape
+        Kl = self.Kl
+        kr, vr, k3, v3 = self._bank_gather(k_local, v_local, inject, peers_only=True)
+        q = q_local
+        if q.stride(2) != 1 or q.stride(0) != S * q.stride(1):
+            q = q.contiguous()
+        q4 = q.view(3, Kl, S, D) if q.is_contiguous() else q.unflatten(0, (3, Kl))
+        out = torch.empty(3, Kl, S, D, dtype=q.dtype, device=q.device) if out4 is None else out4
+        runs = self.bank_runs_of_rank()
+        kv_runs = [(k3, v3, 0, 0)]          # the local run: the caller's own projections, in place
+        for f0, n in runs[1:]:              # remote runs: the receive buffer in place; k holds branch 0 alone under injection
+            kv_runs.append((kr[:, f0:f0 + n], vr[:, f0:f0 + n], 0 if inject else 1, 1))
+        ops.ext_attn_runs_views(q4, kv_runs, out, heads, scale, inject, runs, self.K, q_frame0=self.kf0,
+                                no_split=not self.attn_split)
+        return out.view(3 * Kl, S, D) if out4 is None else out4
 
     def _pivotal_bank(self, q_local, k_local, v_local, heads: int, scale: float, inject: bool, out4=None):
         """One gather (`_bank_gather`), one attention call on the gathered buffer in place; q keeps its own layout
@@ -586,8 +650,8 @@ class NativeShard(FrameShard):
     Only the in-place two-pass API (`ext_alloc`, `pivotal_block`, `propagate_all(..., halo_reqs=)`) goes native; the
     other methods are `FrameShard`'s own on the same communicator."""
 
-    def __init__(self, K: int, comm, halo_comm=None, attn_split: Optional[bool] = None):
-        super().__init__(K, comm=comm, attn_split=attn_split, halo_comm=halo_comm)
+    def __init__(self, K: int, comm, halo_comm=None, attn_split: Optional[bool] = None, bank_runs: Optional[bool] = None):
+        super().__init__(K, comm=comm, attn_split=attn_split, halo_comm=halo_comm, bank_runs=bank_runs)
         from . import _lib
         lib = _lib.load()
         h = ctypes.c_void_p()
@@ -667,7 +731,8 @@ class NativeShard(FrameShard):
         slot = self._slot
         if not no_halo:
             self._slot = (slot + 1) % _lib.TF_RANK_SLOTS
-        m = ((_lib.TF_RANK_HEADS if mode == "heads" else _lib.TF_RANK_BANK) | (_lib.TF_RANK_NO_HALO if no_halo else 0)
+        m = ({"heads": _lib.TF_RANK_HEADS, "bank_runs": _lib.TF_RANK_BANK_RUNS}.get(mode, _lib.TF_RANK_BANK)
+             | (_lib.TF_RANK_NO_HALO if no_halo else 0)
              | (_lib.TF_RANK_INV_NORM if inv_norm else 0))
         rc = lib.tf_rank_pivotal(self._rk, q3.data_ptr(), k3.data_ptr(), v3.data_ptr(), strides,
                                  None if piv is None else piv.data_ptr(), None if inv is None else inv.data_ptr(),

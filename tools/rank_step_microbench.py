@@ -122,7 +122,8 @@ def main():
                     help="single-GPU step to quote ratios against (default: ms_per_step of the newest BENCH_r*.json the "
                          "driver left at the repository root)")
     ap.add_argument("--profile", action="store_true", help="cProfile of the host side of 5 steps (first configuration)")
-    ap.add_argument("--only", default="", help="e.g. 'split,auto': run one configuration (split|onepass , auto|heads|bank)")
+    ap.add_argument("--only", default="", help="e.g. 'split,auto': run one configuration (split|onepass , "
+                                               "auto|heads|bank|bank_runs|auto+runs; auto+runs = auto_mode with the bank_runs opt-in)")
     ap.add_argument("--no-levels", action="store_true", help="skip the per-level isolated blocks (profiling runs)")
     ap.add_argument("--no-copies", action="store_true",
                     help="--native: the loopback exchanges move nothing (tf_comm_loopback_copies(0)): the rank step with the "
@@ -141,9 +142,11 @@ def main():
     torch.cuda.set_device(dev)
     w = bench.blend_w(cfg.chunk, dev)
     for split in (True, False):
-        for mode in (None, "heads", "bank"):
-            if args.only and args.only != f"{'split' if split else 'onepass'},{mode or 'auto'}":
+        for mode_name in ("auto", "heads", "bank", "bank_runs", "auto+runs"):
+            if args.only and args.only != f"{'split' if split else 'onepass'},{mode_name}":
                 continue
+            opt_in = mode_name == "auto+runs"       # FrameShard(bank_runs=True): auto_mode may answer "bank_runs"
+            mode = None if mode_name in ("auto", "auto+runs") else mode_name
             wire = tuple(float(x) for x in args.wire_model.split(",")) if args.wire_model else None
             if args.native:
                 from tokenflow_amd import _lib
@@ -151,10 +154,10 @@ def main():
                 comm = HipComm.loopback(args.rank, args.world, copies=not args.no_copies, wire=wire)
                 comm.bytes = 0
                 hcomm = HipComm.loopback(args.rank, args.world, copies=not args.no_copies, wire=wire)
-                shard = sharded.NativeShard(cfg.K, comm, hcomm, attn_split=split)
+                shard = sharded.NativeShard(cfg.K, comm, hcomm, attn_split=split, bank_runs=opt_in)
             else:
                 comm = LocalComm(args.rank, args.world)
-                shard = sharded.FrameShard(cfg.K, comm=comm, attn_split=split)
+                shard = sharded.FrameShard(cfg.K, comm=comm, attn_split=split, bank_runs=opt_in)
             if mode == "heads" and any(l[2] % args.world for l in cfg.levels):
                 continue
             gen = torch.Generator(device=dev).manual_seed(1234 + args.rank)
