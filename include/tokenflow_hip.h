@@ -18,7 +18,8 @@
  *     all launches are asynchronous on that stream.
  *   - tensors are dense row-major unless a leading dimension is given.
  *   - branch layout everywhere is the reference's [source | uncond | cond]
- *     (tokenflow_utils.py:117,312  `n_frames = batch_size // 3`).
+ *     (tokenflow_utils.py:117,312  `n_frames = batch_size // 3`); the *_edits entry points (ABI 10) take a MULTI-EDIT
+ *     batch of E edits of one source video, B = 1 + 2E branches [source | uncond_1 | cond_1 | ... | uncond_E | cond_E].
  */
 #ifndef TOKENFLOW_HIP_H
 #define TOKENFLOW_HIP_H
@@ -30,7 +31,7 @@
 extern "C" {
 #endif
 
-#define TF_ABI_VERSION 9
+#define TF_ABI_VERSION 10
 
 /* Every entry point below is exported with default visibility; the library itself is built with -fvisibility=hidden, so
  * its exported symbols are exactly the declarations of this header (checked by tests/test_hooks_cpu.py). */
@@ -62,6 +63,13 @@ extern "C" {
                                                         frames admit the interleaved kernel, S % 64 == 0 and S >= 256 (a no-op on ragged
                                                         frames); it applies to the ALL launch and to the SOURCE launch beside the dual-V
                                                         kernel; tests, measurements */
+
+/* tf_ext_attn_fwd_edits only: the four-bank shared-softmax form for pairs of edits (below) forced on / off */
+#define TF_ATTN_MULTI_V (1 << 19)
+#define TF_ATTN_NO_MULTI_V (1 << 20)
+
+/* most edits of one multi-edit batch (the *_edits entry points) */
+#define TF_MAX_EDITS 8
 
 /* argument errors */
 #define TF_ERR_NULL (-1)
@@ -157,6 +165,49 @@ TF_API int tf_ext_attn_fwd_strided(const void* q, const void* k, const void* v, 
  *   fused[qw=.,kw=.,qb=.,prec=.]     fused small-problem kernel
  * MODE is ALL, DUAL or SOURCE. */
 TF_API int tf_ext_attn_plan(int K, int Kq, int S, int H, int Dh, int flags, int dtype, char* buf, size_t len);
+
+/* ------------------------------------------------------------------------
+ * Extended attention of a multi-edit batch (ABI 10): several prompts on one source video in one pass.
+ *
+ * Semantics: B = 1 + 2*n_edits branches, branch-major [source | uncond_1 | cond_1 | ... | uncond_E | cond_E]; the slices of
+ * the result that belong to edit e (source, uncond_e, cond_e) are what tf_ext_attn_fwd_strided computes on
+ * [source | uncond_e | cond_e].  Nothing mixes edits.  n_edits = 1 IS tf_ext_attn_fwd_strided; 1 <= n_edits <= TF_MAX_EDITS.
+ *
+ *   q, k, v, out, K, Kq, q_frame0, S, H, Dh, ld, strides, scale, dtype: as tf_ext_attn_fwd_strided; branch b of a tensor
+ *     lives at base + b * branch_stride, b < B.
+ *   flags: TF_ATTN_INJECT, TF_ATTN_FOLD_SCALE, TF_ATTN_OUT_F32, TF_ATTN_NO_SPLIT, TF_ATTN_NO_FUSED / TF_ATTN_FUSED, the hints:
+ *     as tf_ext_attn_fwd, applied to every part.  TF_ATTN_BANK_ONLY / TF_ATTN_SOURCE_ONLY: TF_ERR_SHAPE.
+ *   ws: tf_ext_attn_edits_workspace_bytes (the V^T image and key norms of all B branches; the split form's partial results
+ *     once: the edits run one behind the other on the stream).
+ *
+ * Composition: ONE V^T pre-pass covers every branch that a streaming launch reads; every edit's bank branches run through
+ * the launches a TF_ATTN_BANK_ONLY call on that edit's slabs takes (DUAL under injection, the split form, the fused
+ * small-problem kernel), the source branch runs once through those of a TF_ATTN_SOURCE_ONLY call.
+ * Identity: edit e's bank branches equal that TF_ATTN_BANK_ONLY call, and the source branch the TF_ATTN_SOURCE_ONLY call,
+ * BIT FOR BIT (same kernels, same values) -- with one exception:
+ *
+ * The four-bank form (TF_ATTN_INJECT, Dh = 40, fp32 score scaling, n_edits >= 2).  Under injection the uncond and cond
+ * branches of EVERY edit use the source's q and k, so softmax(QK^T) is the same for all 2E bank branches.  One workgroup
+ * then computes a PAIR of edits: QK^T and the online softmax once, four P.V products against the four V banks out of one
+ * packed V^T image (160 value rows + the ones row of the common denominator; plan token one<40,1,4,MV4,2,fq0>); an odd
+ * last edit takes the DUAL launch.  Always one-pass launches (no split, no fused kernel) for the bank branches; any S >= 1.
+ * Its result is held to the oracle within the attention bound; it is NOT bit-identical to the DUAL composition (another
+ * kernel: other tile shapes and summation order).  TF_ATTN_MULTI_V forces it on wherever it exists, TF_ATTN_NO_MULTI_V
+ * off; without a hint the library takes it only for the shape classes where it was measured faster than the composition
+ * by more than the run-to-run spread (profiles/r08_attn_edits_ab.txt): Kq = K, H = 8, 4 <= K <= 8, 1024 <= S <= 4096; the
+ * composition everywhere else (other grids were not measured).
+ *
+ * tf_ext_attn_edits_plan: the launches of the call for dense tensors, as tf_ext_attn_plan (host only); the four-bank launch
+ * is the token one<40,1,4,MV4,2,fq0>.
+ * ------------------------------------------------------------------------ */
+TF_API size_t tf_ext_attn_edits_workspace_bytes(int K, int S, int H, int Dh, int n_edits, int dtype);
+
+TF_API int tf_ext_attn_fwd_edits(const void* q, const void* k, const void* v, void* out, int K, int Kq, int q_frame0,
+                          int S, int H, int Dh, int64_t ld, const int64_t* strides, float scale, int flags, int dtype,
+                          int n_edits, void* ws, size_t ws_bytes, void* stream);
+
+TF_API int tf_ext_attn_edits_plan(int K, int Kq, int S, int H, int Dh, int n_edits, int flags, int dtype, char* buf,
+                           size_t len);
 
 /* ------------------------------------------------------------------------
  * Extended attention over a bank that arrives in pieces: "run + merge" (ABI 9).
@@ -348,6 +399,35 @@ TF_API int tf_nn_gather_blend_chunks_norm(const void* tgt, const void* piv, cons
                                    void* stream);
 
 /* ------------------------------------------------------------------------
+ * The chunk forms for a multi-edit batch (ABI 10): the arguments of tf_nn_gather_blend_chunks[_norm] plus n_edits
+ * (1 .. TF_MAX_EDITS); B = 1 + 2*n_edits branches.
+ *   kf_out : [B, K, S, D];   resid, out, norm_out : [B, C*n, S, D];   everything else as the chunk forms.
+ *   C >= 1.  C = 1 runs the one-chunk form: with first_single the one-keyframe chunk 0 of the video (P = 1; `w` may be
+ *   NULL, out_dtype must equal single_dtype), else one two-keyframe chunk.
+ * The NN search reads the source branch only, so ONE search is issued -- the launches of tf_nn_search_plan(n*S, S, D, 2, C)
+ * (without its finalize; of P = 1 for the one-keyframe chunk alone) -- and the gather loops the B branches on the same
+ * candidates.  Branch b of the result is BIT-IDENTICAL to the same branch of the single-edit call on
+ * [source | uncond_e | cond_e].  Workspace: tf_nn_gather_blend_chunks_workspace_bytes (C = 1 with first_single:
+ * tf_nn_gather_blend_workspace_bytes(n*S, S, D, 1)) -- the search is unchanged.
+ * tf_nn_gather_blend_edits_plan: the launches of the call (host only): the search tokens of tf_nn_search_plan followed by
+ * gather[branches=B].
+ * ------------------------------------------------------------------------ */
+TF_API int tf_nn_gather_blend_chunks_edits(const void* tgt, const void* piv, const float* inv_norm, const void* kf_out,
+                                    const float* w, const void* resid, void* out, int K, int n, int C, int S, int D,
+                                    int slot0, int first_single, int search_dtype, int in_dtype, int res_dtype,
+                                    int out_dtype, int single_dtype, int n_edits, void* ws, size_t ws_bytes,
+                                    void* stream);
+
+TF_API int tf_nn_gather_blend_chunks_norm_edits(const void* tgt, const void* piv, const float* inv_norm,
+                                         const void* kf_out, const float* w, const void* resid, void* out, int K, int n,
+                                         int C, int S, int D, int slot0, int first_single, int search_dtype,
+                                         int in_dtype, int res_dtype, int out_dtype, int single_dtype, int n_edits,
+                                         const void* gamma, const void* beta, float eps, int w_dtype, void* norm_out,
+                                         int norm_dtype, void* ws, size_t ws_bytes, void* stream);
+
+TF_API int tf_nn_gather_blend_edits_plan(int n, int C, int S, int D, int first_single, int n_edits, char* buf, size_t len);
+
+/* ------------------------------------------------------------------------
  * Row LayerNorm producer  --  the `norm1` call of TokenFlowBlock.forward
  * (tokenflow_utils.py:313-323; also norm2 / norm3 of the same forward, 399-417)
  * when the block runs in 16 bit:  out[r] = (x[r] - mean) / sqrt(var + eps) * gamma + beta
@@ -391,6 +471,10 @@ TF_API int tf_ddim_step(const void* x, const void* eps, void* out, int64_t n, fl
  * elem_bytes = bytes per element; elems_per_branch*elem_bytes multiple of 16.
  * ------------------------------------------------------------------------ */
 TF_API int tf_inject_copy(void* x, int64_t elems_per_branch, int elem_bytes, void* stream);
+
+/* The same for a multi-edit batch: x viewed as [n_branches, elems_per_branch], x[b] = x[0] for every b >= 1 (in place);
+ * n_branches = 1 + 2E, 3 .. 1 + 2*TF_MAX_EDITS.  Bit-exact copies. */
+TF_API int tf_inject_copy_edits(void* x, int64_t elems_per_branch, int n_branches, int elem_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
  * Multi-GPU exchange steps over RCCL (one process per GPU).  The reference is single-process (no

@@ -12,6 +12,7 @@ TF_ATTN_OUT_F32 = 32
 TF_ATTN_FOLD_SCALE = 64
 TF_ATTN_NO_FUSED, TF_ATTN_FUSED = 128, 1 << 17
 TF_ATTN_HINT_QB2, TF_ATTN_PRECISE_P, TF_ATTN_NO_PRECISE_P = 1 << 14, 1 << 15, 1 << 16
+TF_ATTN_MULTI_V, TF_ATTN_NO_MULTI_V = 1 << 19, 1 << 20   # ext_attn_edits: the four-bank form for pairs of edits forced on / off
 TF_ATTN_HINT_MIX = 1 << 18   # Dh = 40 streaming kernel: the mixed-MFMA-shape form whatever the launch size (S % 64 == 0, S >= 256)
 
 
@@ -22,7 +23,8 @@ def attn_hint(qw: int = 0, kw: int = 0, qb: int = 1) -> int:
     return (code[qw] << 8) | (code[kw] << 11) | (TF_ATTN_HINT_QB2 if qb == 2 else 0)
 
 
-ABI_VERSION = 9
+ABI_VERSION = 10
+TF_MAX_EDITS = 8
 TF_RANK_HEADS, TF_RANK_BANK, TF_RANK_SLOTS, TF_RANK_NO_HALO, TF_RANK_INV_NORM = 0, 1, 64, 16, 32
 TF_RANK_BANK_RUNS = 2
 TF_ERR_COMM = -6
@@ -39,6 +41,18 @@ _SIGNATURES = {
                                    _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "tf_ext_attn_fwd_strided": (_c.c_int, [_c.c_void_p] * 4 + [_c.c_int] * 6 + [_c.c_int64, _c.c_void_p, _c.c_float,
                                            _c.c_int, _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    # multi-edit batches (ABI 10)
+    "tf_ext_attn_edits_workspace_bytes": (_c.c_size_t, [_c.c_int] * 6),
+    "tf_ext_attn_fwd_edits": (_c.c_int, [_c.c_void_p] * 4 + [_c.c_int] * 6 + [_c.c_int64, _c.c_void_p, _c.c_float,
+                                         _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "tf_ext_attn_edits_plan": (_c.c_int, [_c.c_int] * 8 + [_c.c_char_p, _c.c_size_t]),
+    "tf_nn_gather_blend_chunks_edits": (_c.c_int, [_c.c_void_p] * 7 + [_c.c_int] * 13 + [_c.c_void_p, _c.c_size_t,
+                                                   _c.c_void_p]),
+    "tf_nn_gather_blend_chunks_norm_edits": (_c.c_int, [_c.c_void_p] * 7 + [_c.c_int] * 13 + [_c.c_void_p, _c.c_void_p,
+                                                        _c.c_float, _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p,
+                                                        _c.c_size_t, _c.c_void_p]),
+    "tf_nn_gather_blend_edits_plan": (_c.c_int, [_c.c_int] * 6 + [_c.c_char_p, _c.c_size_t]),
+    "tf_inject_copy_edits": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int, _c.c_int, _c.c_void_p]),
     # attention over a bank that arrives in pieces: run + merge (ABI 9)
     "tf_ext_attn_runs_workspace_bytes": (_c.c_size_t, [_c.c_int] * 7),
     "tf_ext_attn_run": (_c.c_int, [_c.c_void_p] * 4 + [_c.c_int] * 10 + [_c.c_int64, _c.c_void_p, _c.c_float, _c.c_int,

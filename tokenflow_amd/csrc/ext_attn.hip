@@ -65,8 +65,10 @@ struct AttnCfg {
     static constexpr size_t lds_bytes(int nb) { return 2 * (size_t)(K_ELEMS + nb * V_ELEMS) * 2; }
 };
 
-enum { MODE_ALL = 0, MODE_SOURCE = 1, MODE_DUAL = 2 };
-static inline const char* mode_name(int mode) { return mode == MODE_ALL ? "ALL" : mode == MODE_DUAL ? "DUAL" : "SOURCE"; }
+enum { MODE_ALL = 0, MODE_SOURCE = 1, MODE_DUAL = 2, MODE_MV4 = 3 };
+static inline const char* mode_name(int mode) {
+    return mode == MODE_ALL ? "ALL" : mode == MODE_DUAL ? "DUAL" : mode == MODE_MV4 ? "MV4" : "SOURCE";
+}
 
 // Head dims whose streaming kernels use the Cauchy-Schwarz score bound |q.k| <= |q| max|k| (per-block key norms from the
 // pre-pass) to skip the per-tile maximum: Dh = 40 since round 2, Dh = 64 since round 6 (A/B switch TF_TUNE_NO_BOUND64).
@@ -109,6 +111,9 @@ struct AttnParams {
     // the output written in the layout the next collective sends (tf_ext_attn_fwd_strided, sharded.py).
     int64_t q_bs, q_fs, k_bs, k_fs, v_bs, v_fs, o_bs, o_fs;
     float c;  // scale * log2(e)
+    // host only, multi-edit batches (tf_ext_attn_fwd_edits): the composing call has packed V^T for all branches already /
+    // the bank launch is the four-bank shared-softmax form (MODE_MV4) / the DUAL form at any S (the odd edit beside it)
+    int no_pack, mv4, force_dual;
 };
 
 // max over the two lanes (l, l ^ 32) that share a query: v_permlane32_swap instead of an LDS round trip
@@ -122,8 +127,8 @@ __device__ __forceinline__ float max_with_lane_xor32(float x) {
 // would then all map to the same memory channel and the tile loads serialise.  The 128-byte skew spreads them.
 __host__ __device__ __forceinline__ int64_t vt_row_stride(int K, int Spad) { return (int64_t)K * Spad + 64; }
 
-static inline size_t vt_bytes(int K, int Spad, int H, int Dh) {
-    return (size_t)3 * H * Dh * (size_t)vt_row_stride(K, Spad) * 2;
+static inline size_t vt_bytes(int K, int Spad, int H, int Dh, int branches = 3) {
+    return (size_t)branches * H * Dh * (size_t)vt_row_stride(K, Spad) * 2;
 }
 
 // 4 consecutive output features of one query: rounded to the 16-bit I/O type, or, with TF_ATTN_OUT_F32, the
@@ -216,6 +221,9 @@ __global__ __launch_bounds__(256) void vt_pack_kernel(const typename T::elem* __
 //        MODE_DUAL:   q/k injection active -- uncond and cond share q, k, the scores and P
 //                     (tokenflow_utils.py:124-130), so ONE workgroup computes both: QK^T and the softmax
 //                     once, two P.V products against the two V banks (NB = 2).
+//        MODE_MV4:    multi-edit batch under injection (Dh = 40): the uncond and cond branches of TWO edits share the
+//                     source q and k, so one workgroup does QK^T and the softmax once and FOUR P.V products (NB = 4)
+//                     against the banks of branches b .. b + 3 of the V^T image.
 // MINW = min waves per SIMD for the register allocator
 // FQ   = fold the softmax scale into Q (see FOLD below; opt-in, TF_ATTN_FOLD_SCALE); false = the default, fp32
 //        scaling of the scores as the reference does (tokenflow_utils.py:173-175 `* self.scale` on the bmm output)
@@ -228,14 +236,18 @@ __global__ __launch_bounds__(64 * NW, MINW) void ext_attn_kernel(AttnParams p) {
     typedef typename T::vec8 vec8;
     typedef typename T::vec4 vec4;
     constexpr int NT = 64 * NW;
-    constexpr int NB = MODE == MODE_DUAL ? 2 : 1;   // V banks handled by this workgroup
+    constexpr int NB = MODE == MODE_DUAL ? 2 : MODE == MODE_MV4 ? 4 : 1;   // V banks handled by this workgroup
+    constexpr bool SHARED = MODE == MODE_DUAL || MODE == MODE_MV4;          // one softmax feeds NB P.V products
+    static_assert(MODE != MODE_MV4 || DH == 40, "the four-bank form exists in the packed image only");
     constexpr int NPK = C::npk(NT), NPV = C::npv(NT);
     constexpr int NBUFS = SB ? 1 : 2;
     // PACK (dual-V at Dh = 40): the two banks' V^T rows share ONE LDS image of 3 M-tiles -- rows 0-39 uncond,
     // 40-79 cond, row 80 = 1.0 (the common denominator row), 81-95 zero -- instead of two images of 2 M-tiles
     // with 24 idle rows each: 12 instead of 16 P.V MFMAs per 64-key tile (18 instead of 22 with QK^T).
-    constexpr bool PACK = MODE == MODE_DUAL && DH == 40;
-    constexpr int VIMG_ROWS = PACK ? 96 : NB * C::VROWS;       // V^T rows of one LDS buffer
+    // Four banks: rows 0-159 the banks, row 160 = 1.0, 161-191 zero -- 6 M-tiles, 24 P.V MFMAs for four outputs.
+    constexpr bool PACK = SHARED && DH == 40;
+    constexpr int NG = (NB * DH + 1 + 31) / 32;                // PACK: M-tiles of the packed image (3 / 6)
+    constexpr int VIMG_ROWS = PACK ? NG * 32 : NB * C::VROWS;  // V^T rows of one LDS buffer
     constexpr int VB_ROWS = PACK ? DH : C::VROWS;              // row offset between the banks inside it
     constexpr int BUF_ELEMS = C::K_ELEMS + VIMG_ROWS * C::VROW;
     // When the head dim is not a multiple of 32 the last PV M-tile has unused rows: row DH of the
@@ -305,7 +317,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void ext_attn_kernel(AttnParams p) {
             u -= nbank;
             b = 0;
         }
-    } else if constexpr (MODE == MODE_DUAL) {
+    } else if constexpr (SHARED) {
         b = 1;
         seg = u % nseg;
         u /= nseg;
@@ -611,11 +623,11 @@ __global__ __launch_bounds__(64 * NW, MINW) void ext_attn_kernel(AttnParams p) {
                     if constexpr (!ONES) l_run[qi] += lsum;
                 }
                 // ---- O^T += V^T . P  (once per V bank)
-                if constexpr (PACK) {   // 3 M-tiles over the packed image: accumulators o[0][.][0], o[0][.][1], o[1][.][0]
+                if constexpr (PACK) {   // NG M-tiles over the packed image: accumulators o[0][.][0], o[0][.][1], o[1][.][0] ...
 #pragma unroll
                     for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
-                        for (int g = 0; g < 3; ++g) {
+                        for (int g = 0; g < NG; ++g) {
                             const E* vrow = sV(buf, 0) + (g * 32 + l31) * C::VROW + sub * 64 + 8 * hi;
                             o[g >> 1][qi][g & 1] = T::mfma32(__builtin_bit_cast(vec8, ld16(vrow + 16 * ks)), pf[ks],
                                                              o[g >> 1][qi][g & 1]);
@@ -652,9 +664,13 @@ __global__ __launch_bounds__(64 * NW, MINW) void ext_attn_kernel(AttnParams p) {
 #pragma unroll
     for (int qi = 0; qi < QT; ++qi) {
         float l_tot;
-        if constexpr (PACK)
-            l_tot = __shfl(o[1][qi][0][8], l31);   // image row 80 = row 16 of the third M-tile: register 8, lane half 0
-        else if constexpr (ONES)
+        if constexpr (PACK) {
+            // the ones row NB*DH of the image: two banks, row 80 = row 16 of the third M-tile, register 8; four banks, row 160 =
+            // row 0 of the sixth M-tile, register 0 -- lane half 0 in both
+            constexpr int LG = (NB * DH) / 32, LR = (NB * DH) % 32;
+            static_assert((LR & 4) == 0, "the ones row must live in lane half 0");
+            l_tot = __shfl(o[LG >> 1][qi][LG & 1][(LR & 3) + 4 * (LR >> 3)], l31);
+        } else if constexpr (ONES)
             l_tot = __shfl(o[0][qi][C::MT - 1][ONES_R], l31);  // row DH lives in lane half 0 of the last M-tile
         else
             l_tot = l_run[qi] + __shfl_xor(l_run[qi], 32);
@@ -671,12 +687,12 @@ __global__ __launch_bounds__(64 * NW, MINW) void ext_attn_kernel(AttnParams p) {
                 };
                 if constexpr (PACK) {
 #pragma unroll
-                    for (int g = 0; g < 3; ++g)
+                    for (int g = 0; g < NG; ++g)
 #pragma unroll
                         for (int rg = 0; rg < 4; ++rg) {
                             const int R = g * 32 + 8 * rg + 4 * hi;
                             if (R < NB * DH) {
-                                const int vb = R >= DH ? 1 : 0;
+                                const int vb = R / DH;
                                 f32x4 w;
 #pragma unroll
                                 for (int i = 0; i < 4; ++i) w[i] = o[g >> 1][qi][g & 1][rg * 4 + i];
@@ -711,12 +727,12 @@ __global__ __launch_bounds__(64 * NW, MINW) void ext_attn_kernel(AttnParams p) {
             const int64_t op0 = b * p.o_bs + f * p.o_fs + (int64_t)q_row[qi] * (H * DH) + h * DH;
             const int64_t branch = p.o_bs;
 #pragma unroll
-            for (int g = 0; g < 3; ++g)
+            for (int g = 0; g < NG; ++g)
 #pragma unroll
                 for (int rg = 0; rg < 4; ++rg) {
                     const int R = g * 32 + 8 * rg + 4 * hi;    // image row of this group of 4 (never straddles a bank)
                     if (R < NB * DH) {
-                        const int vb = R >= DH ? 1 : 0;
+                        const int vb = R / DH;
                         f32x4 w;
 #pragma unroll
                         for (int i = 0; i < 4; ++i) w[i] = o[g >> 1][qi][g & 1][rg * 4 + i] * inv_l;
@@ -2155,7 +2171,8 @@ int launch_pp(AttnParams p, hipStream_t st) {
 template <typename T, int DH, int QT, int NW, int MODE, int MINW, bool FQ = true, int KT = 64, bool SB = false>
 int launch_one(AttnParams p, hipStream_t st) {
     typedef AttnCfg<DH, KT> C;
-    constexpr size_t lds = ((MODE == MODE_DUAL && DH == 40) ? 2 * (size_t)(C::K_ELEMS + 96 * C::VROW) * 2   // PACK
+    constexpr size_t lds = ((MODE == MODE_DUAL && DH == 40)  ? 2 * (size_t)(C::K_ELEMS + 96 * C::VROW) * 2    // PACK
+                            : (MODE == MODE_MV4 && DH == 40) ? 2 * (size_t)(C::K_ELEMS + 192 * C::VROW) * 2   // PACK, four banks
                                                              : C::lds_bytes(MODE == MODE_DUAL ? 2 : 1)) / (SB ? 2 : 1);
     if (tf_plan_note("one<%d,%d,%d,%s,%d,fq%d%s%s%s>", DH, QT, NW, mode_name(MODE), MINW, FQ ? 1 : 0, KT != 64 ? ",kt128" : "",
                      SB ? ",sb" : "", run_mark<MODE>(p)))
@@ -2177,33 +2194,39 @@ int launch_one(AttnParams p, hipStream_t st) {
     return 0;
 }
 
+// The V^T pre-pass over branches [b_lo, b_hi) of v (a multi-edit batch: once for all 1 + 2E branches)
+template <typename T>
+int launch_vt_pack(const AttnParams& p, const void* v, int DH, int b_lo, int b_hi, hipStream_t st) {
+    typedef typename T::elem E;
+    dim3 grid((unsigned)(p.Spad / 64), (unsigned)p.H, (unsigned)((b_hi - b_lo) * p.K));
+    const size_t lds = (size_t)64 * (DH + 2) * sizeof(E);
+    // the Dh = 40 kernels also need the key norm bounds (score bound, see BOUND)
+    const bool bound = attn_has_bound(DH);
+    if (!tf_plan_note("vt_pack")) {
+        hipLaunchKernelGGL(vt_pack_kernel<T>, grid, dim3(256), lds, st, reinterpret_cast<const E*>(v),
+                           reinterpret_cast<E*>(const_cast<void*>(p.vt)),
+                           bound ? reinterpret_cast<const E*>(p.k) : nullptr, const_cast<float*>(p.knorm2),
+                           p.inject, b_lo, p.K, p.Kb, p.S, p.H, DH, p.Spad, p.ld, p.v_bs, p.v_fs, p.k_bs, p.k_fs,
+                           p.run_hdr, p.nseg);
+        TF_LAUNCH_CHECK("tf_ext_attn_fwd(vt_pack)");
+    }
+    return 0;
+}
+
 // Geometry per head dim (A/B-measured on MI355X, tools/attn_microbench.py): what matters is the number of
 // INDEPENDENT waves per SIMD (softmax VALU of one wave overlaps MFMAs of another) and how many waves share
 // one staged tile.  Dh=40: 1 query tile/wave, 8 waves/workgroup, 111 VGPRs -> 4 waves/SIMD.
 // Dh=64: 2 query tiles/wave (each LDS fragment feeds 2 MFMAs).  Dh=80/160: register-bound, 1 tile/wave.
 template <typename T, int DH>
 int launch_attn(const AttnParams& p, const void* v, hipStream_t st) {
-    typedef typename T::elem E;
     const bool src_only = p.part == TF_ATTN_SOURCE_ONLY, bank_only = p.part == TF_ATTN_BANK_ONLY;
     // The kernel FAMILY of a run launch is the one the unsplit call of the same (Kq, S, H) takes, however the run splits
     // itself: the source branch out of a run call is then bit for bit the source-only call's (same kernel, same keys).
     const int ns_sel = p.run ? 1 : p.nseg;
-    {   // pre-pass: V -> transposed, key-permuted, per-frame padded bank (only the branches this call computes)
-        const int b_lo = bank_only ? 1 : 0, b_hi = src_only ? 1 : 3;
+    if (!p.no_pack) {   // pre-pass: V -> transposed, key-permuted, per-frame padded bank (only the branches this call computes)
         // (a run launch: the run's p.K frames only, at their positions in the image of the whole bank -- p.vt, p.knorm2, p.k and v
         // point at the run's first frame, so the runs of one bank fill disjoint parts of one workspace)
-        dim3 grid((unsigned)(p.Spad / 64), (unsigned)p.H, (unsigned)((b_hi - b_lo) * p.K));
-        const size_t lds = (size_t)64 * (DH + 2) * sizeof(E);
-        // the Dh = 40 kernels also need the key norm bounds (score bound, see BOUND)
-        const bool bound = attn_has_bound(DH);
-        if (!tf_plan_note("vt_pack")) {
-            hipLaunchKernelGGL(vt_pack_kernel<T>, grid, dim3(256), lds, st, reinterpret_cast<const E*>(v),
-                               reinterpret_cast<E*>(const_cast<void*>(p.vt)),
-                               bound ? reinterpret_cast<const E*>(p.k) : nullptr, const_cast<float*>(p.knorm2),
-                               p.inject, b_lo, p.K, p.Kb, p.S, p.H, DH, p.Spad, p.ld, p.v_bs, p.v_fs, p.k_bs, p.k_fs,
-                               p.run_hdr, p.nseg);
-            TF_LAUNCH_CHECK("tf_ext_attn_fwd(vt_pack)");
-        }
+        if (const int rc = launch_vt_pack<T>(p, v, DH, bank_only ? 1 : 0, src_only ? 1 : 3, st)) return rc;
     }
     // Every head dim has three forms: ALL (one launch, bank problems then source problems), DUAL (injection:
     // uncond + cond share QK^T and the softmax; pays from S = 256 on) and SOURCE (the source branch alone).
@@ -2221,7 +2244,7 @@ int launch_attn(const AttnParams& p, const void* v, hipStream_t st) {
     };
     auto compose = [&](auto all, auto dual, auto source) -> int {
         if (src_only) return source();
-        if (!p.inject || p.S < 256) {   // short frames: the ALL form reads the source q, k itself
+        if (!p.inject || (p.S < 256 && !p.force_dual)) {   // short frames: the ALL form reads the source q, k itself
             const int rc = all();
             return rc ? rc : merge();
         }
@@ -2234,6 +2257,9 @@ int launch_attn(const AttnParams& p, const void* v, hipStream_t st) {
         // -8..11 % on a sharded rank's level 0 against the 4-wave form); below that the 4-wave form (twice the
         // workgroups).  S < 256: always 4 waves.
         const bool big = p.S >= 256 && (int64_t)3 * p.Kq * ((p.S + 255) / 256) * p.H * ns_sel >= 768;
+        // multi-edit batch under injection: two edits' bank branches in one launch (tf_ext_attn_fwd_edits), 4-wave workgroups,
+        // two per CU (70 KB of tiles each)
+        if (p.mv4) return launch_one<T, DH, 1, 4, MODE_MV4, 2, false>(p, st);
         if (!p.fold) {   // fp32 score scaling: the default
 #ifndef TF_TUNE_IL40_MIN_WGS
 #define TF_TUNE_IL40_MIN_WGS 256   // one 8-wave workgroup per CU: a W = 8 rank's one-pass level 0 (384 workgroups) runs
@@ -2455,7 +2481,9 @@ int dispatch_dh(int Dh, const AttnParams& p, const void* v, hipStream_t st) {
 
 }  // namespace
 
-extern "C" size_t tf_ext_attn_workspace_bytes(int K, int S, int H, int Dh, int dtype) {
+// Workspace of a call over `branches` branches: V^T image | key norm bounds | split-form partial results (of one edit: the
+// edits of a multi-edit batch run one behind the other on the stream and reuse them)
+static size_t attn_ws_bytes(int K, int S, int H, int Dh, int dtype, int branches) {
     if (K <= 0 || S <= 0 || H <= 0 || Dh <= 0 || dtype == TF_F32) return 0;
     const size_t Spad = (size_t)((S + 127) / 128) * 128;   // frames padded to the largest staged tile
     size_t part_elems = 0;   // split form: worst case over the number of query frames a caller may pass
@@ -2465,14 +2493,48 @@ extern "C" size_t tf_ext_attn_workspace_bytes(int K, int S, int H, int Dh, int d
             const size_t e = ns > 1 ? (size_t)2 * Kq * H * S * ns * (Dh + 8) : 0;
             part_elems = e > part_elems ? e : part_elems;
         }
-    return ((vt_bytes(K, (int)Spad, H, Dh) + 255) & ~(size_t)255) +
-           (((size_t)3 * H * K * (Spad / 64) * sizeof(float) + 255) & ~(size_t)255) +
+    return ((vt_bytes(K, (int)Spad, H, Dh, branches) + 255) & ~(size_t)255) +
+           (((size_t)branches * H * K * (Spad / 64) * sizeof(float) + 255) & ~(size_t)255) +
            part_elems * sizeof(float);   // V^T image | key norm bounds | split-form partial results
 }
 
-extern "C" int tf_ext_attn_fwd_strided(const void* q, const void* k, const void* v, void* out, int K, int Kq,
-                                       int q_frame0, int S, int H, int Dh, int64_t ld, const int64_t* strides,
-                                       float scale, int inject, int dtype, void* ws, size_t ws_bytes, void* stream) {
+extern "C" size_t tf_ext_attn_workspace_bytes(int K, int S, int H, int Dh, int dtype) {
+    return attn_ws_bytes(K, S, H, Dh, dtype, 3);
+}
+
+namespace {
+
+// One part of a multi-edit batch (tf_ext_attn_fwd_edits) as seen by the single-edit call that computes it: the caller has
+// moved the base pointers of q / k / v / out to the edit's slabs; the workspace holds the image of all `branches` branches
+// and the launches read it `shift` branches in (2 per edit in front of this one).
+struct EditsPart {
+    int branches;   // 1 + 2E
+    int shift;      // branches in front of this edit's uncond branch, minus 1: 2 * edit
+    int no_pack;    // the V^T pre-pass has been issued for all branches
+    int mv4;        // this call computes TWO edits' bank branches in the four-bank form
+    int force_dual; // the DUAL launch at any S
+    int probe;      // do not launch: return 1 if the call takes the fused small-problem kernel, else 0
+
+    // the parts of a batch of `branches` branches whose V^T image is packed: edit e's bank branches through the launches of
+    // its own bank-only call / the pair (e, e + 1) in the four-bank form / edit e in the DUAL launch at any S / the source
+    // branch / the probe of a part's fused-kernel decision
+    static EditsPart bank(int branches, int e) { return make(branches, 2 * e, 0, 0, 0); }
+    static EditsPart pair_mv4(int branches, int e) { return make(branches, 2 * e, 1, 0, 0); }
+    static EditsPart bank_dual(int branches, int e) { return make(branches, 2 * e, 0, 1, 0); }
+    static EditsPart source(int branches) { return make(branches, 0, 0, 0, 0); }
+    static EditsPart probe_of(int branches) { return make(branches, 0, 0, 0, 1); }
+
+private:
+    static EditsPart make(int branches, int shift, int mv4, int force_dual, int probe) {
+        EditsPart p{};
+        p.branches = branches, p.shift = shift, p.no_pack = 1, p.mv4 = mv4, p.force_dual = force_dual, p.probe = probe;
+        return p;
+    }
+};
+
+int attn_fwd_core(const void* q, const void* k, const void* v, void* out, int K, int Kq, int q_frame0, int S, int H, int Dh,
+                  int64_t ld, const int64_t* strides, float scale, int inject, int dtype, void* ws, size_t ws_bytes,
+                  void* stream, const EditsPart* ed) {
     TF_ARG(q && k && v && out && ws && strides, TF_ERR_NULL, "tf_ext_attn_fwd: null pointer");
     TF_ARG(dtype == TF_BF16 || dtype == TF_F16, TF_ERR_DTYPE, "tf_ext_attn_fwd: dtype %d (bf16/f16 only)", dtype);
     TF_ARG(Dh == 40 || Dh == 64 || Dh == 80 || Dh == 160, TF_ERR_SHAPE,
@@ -2491,8 +2553,9 @@ extern "C" int tf_ext_attn_fwd_strided(const void* q, const void* k, const void*
                (long long)strides[i]);
     TF_ARG(tf_aligned16(q) && tf_aligned16(k) && tf_aligned16(v) && tf_aligned16(out) && tf_aligned16(ws),
            TF_ERR_ALIGN, "tf_ext_attn_fwd: tensors not 16-byte aligned");
-    TF_ARG(ws_bytes >= tf_ext_attn_workspace_bytes(K, S, H, Dh, dtype), TF_ERR_WORKSPACE,
-           "tf_ext_attn_fwd: workspace %zu < %zu bytes", ws_bytes, tf_ext_attn_workspace_bytes(K, S, H, Dh, dtype));
+    const int branches = ed ? ed->branches : 3;
+    TF_ARG(ws_bytes >= attn_ws_bytes(K, S, H, Dh, dtype, branches), TF_ERR_WORKSPACE,
+           "tf_ext_attn_fwd: workspace %zu < %zu bytes", ws_bytes, attn_ws_bytes(K, S, H, Dh, dtype, branches));
     const int part_bits = inject & (TF_ATTN_BANK_ONLY | TF_ATTN_SOURCE_ONLY);
     TF_ARG(part_bits != (TF_ATTN_BANK_ONLY | TF_ATTN_SOURCE_ONLY), TF_ERR_SHAPE,
            "tf_ext_attn_fwd: TF_ATTN_BANK_ONLY and TF_ATTN_SOURCE_ONLY exclude each other");
@@ -2506,24 +2569,30 @@ extern "C" int tf_ext_attn_fwd_strided(const void* q, const void* k, const void*
         a.b0 = part_bits == TF_ATTN_BANK_ONLY ? 1 : 0;
         a.nb = part_bits == TF_ATTN_BANK_ONLY ? 2 : part_bits == TF_ATTN_SOURCE_ONLY ? 1 : 3;
         const TfFusedPlan plan = tf_attn_fused_plan(&a, 1, S, Dh, dtype, inject);
+        if (ed && ed->probe) return plan.use ? 1 : 0;
         if (plan.use)
             return tf_attn_fused_launch(&a, 1, S, Dh, scale, inject, dtype, plan, reinterpret_cast<hipStream_t>(stream));
     }
+    const int Spad = ((S + 127) / 128) * 128;
+    const int shift = ed ? ed->shift : 0;
+    const size_t vt_all = (vt_bytes(K, Spad, H, Dh, branches) + 255) & ~(size_t)255;
+    const size_t kn_all = ((size_t)branches * H * K * (Spad / 64) * sizeof(float) + 255) & ~(size_t)255;
+    unsigned char* const w8 = static_cast<unsigned char*>(ws);
     AttnParams p{};
     p.q = q;
     p.k = k;
-    p.vt = ws;
-    p.knorm2 = reinterpret_cast<const float*>(static_cast<const unsigned char*>(ws) +
-                                              ((vt_bytes(K, ((S + 127) / 128) * 128, H, Dh) + 255) & ~(size_t)255));
+    p.inject = (inject & TF_ATTN_INJECT) ? 1 : 0;
+    // an edit's launches read the image `shift` branches in; its key norms too, unless the keys are the source's (injection)
+    p.vt = w8 + vt_bytes(K, Spad, H, Dh, shift);
+    p.knorm2 = reinterpret_cast<const float*>(w8 + vt_all) + (p.inject ? 0 : (size_t)shift * H * K * (Spad / 64));
     p.out = out;
     p.K = K;
     p.Kq = Kq;
     p.q_frame0 = q_frame0;
     p.S = S;
     p.H = H;
-    p.Spad = ((S + 127) / 128) * 128;
+    p.Spad = Spad;
     p.nQT = (S + 127) / 128;
-    p.inject = (inject & TF_ATTN_INJECT) ? 1 : 0;
     p.part = inject & (TF_ATTN_BANK_ONLY | TF_ATTN_SOURCE_ONLY);
     p.fold = (inject & TF_ATTN_FOLD_SCALE) ? 1 : 0;
     p.out_f32 = (inject & TF_ATTN_OUT_F32) ? 1 : 0;
@@ -2532,9 +2601,7 @@ extern "C" int tf_ext_attn_fwd_strided(const void* q, const void* k, const void*
     p.pslots = p.nseg > 1 ? p.nseg : 0;
     p.bit_stable = (inject & TF_ATTN_NO_SPLIT) ? 1 : 0;
     p.mix = (inject & TF_ATTN_HINT_MIX) ? 1 : 0;
-    p.partials = reinterpret_cast<float*>(
-        reinterpret_cast<unsigned char*>(const_cast<float*>(p.knorm2)) +
-        (((size_t)3 * H * K * (((S + 127) / 128) * 128 / 64) * sizeof(float) + 255) & ~(size_t)255));
+    p.partials = reinterpret_cast<float*>(w8 + vt_all + kn_all);
     p.ld = ld;
     p.ld_q = ld_q;
     p.q_bs = strides[0];
@@ -2546,8 +2613,118 @@ extern "C" int tf_ext_attn_fwd_strided(const void* q, const void* k, const void*
     p.o_bs = strides[6];
     p.o_fs = strides[7];
     p.c = (float)((double)scale * 1.4426950408889634);
+    if (ed) p.no_pack = ed->no_pack, p.mv4 = ed->mv4, p.force_dual = ed->force_dual;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     return dtype == TF_BF16 ? dispatch_dh<BF16>(Dh, p, v, st) : dispatch_dh<F16>(Dh, p, v, st);
+}
+
+}  // namespace
+
+extern "C" int tf_ext_attn_fwd_strided(const void* q, const void* k, const void* v, void* out, int K, int Kq,
+                                       int q_frame0, int S, int H, int Dh, int64_t ld, const int64_t* strides,
+                                       float scale, int inject, int dtype, void* ws, size_t ws_bytes, void* stream) {
+    return attn_fwd_core(q, k, v, out, K, Kq, q_frame0, S, H, Dh, ld, strides, scale, inject, dtype, ws, ws_bytes, stream,
+                         nullptr);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Multi-edit batches (include/tokenflow_hip.h): B = 1 + 2E branches [source | uncond_1 | cond_1 | ... ].  Composition of the
+// single-edit parts: ONE V^T pre-pass over every branch a streaming launch reads, the source branch through the launches of a
+// TF_ATTN_SOURCE_ONLY call, every edit's bank branches through those of a TF_ATTN_BANK_ONLY call on that edit's slabs -- the
+// same kernels on the same values, so bit for bit the `part=` calls' results.  Under injection at Dh = 40 PAIRS of edits may
+// take the four-bank shared-softmax launch instead (MODE_MV4; TF_ATTN_MULTI_V / TF_ATTN_NO_MULTI_V).
+extern "C" size_t tf_ext_attn_edits_workspace_bytes(int K, int S, int H, int Dh, int n_edits, int dtype) {
+    if (n_edits < 1 || n_edits > TF_MAX_EDITS) return 0;
+    return attn_ws_bytes(K, S, H, Dh, dtype, 1 + 2 * n_edits);
+}
+
+// Default of the four-bank form where neither hint is given: only the shape classes in which it measured faster than the
+// DUAL composition by more than the run-to-run spread (profiles/r08_attn_edits_ab.txt): every keyframe's queries (Kq = K),
+// 8 heads, banks of 4 to 8 keyframes, frames of 1024 to 4096 tokens (-6 % / -17 % at E = 2, -3.5 % / -13 % at E = 3).
+// Everything else -- query-frame subsets, other head counts, shorter or longer frames, larger banks -- was not measured and
+// stays behind TF_ATTN_MULTI_V.
+static bool mv4_default(int K, int Kq, int S, int H) {
+    return Kq == K && H == 8 && K >= 4 && K <= 8 && S >= 1024 && S <= 4096;
+}
+
+extern "C" int tf_ext_attn_fwd_edits(const void* q, const void* k, const void* v, void* out, int K, int Kq, int q_frame0,
+                                     int S, int H, int Dh, int64_t ld, const int64_t* strides, float scale, int flags,
+                                     int dtype, int n_edits, void* ws, size_t ws_bytes, void* stream) {
+    TF_ARG(n_edits >= 1 && n_edits <= TF_MAX_EDITS, TF_ERR_SHAPE, "tf_ext_attn_fwd_edits: n_edits=%d (1 .. %d)", n_edits,
+           TF_MAX_EDITS);
+    TF_ARG(q && k && v && out && ws && strides, TF_ERR_NULL, "tf_ext_attn_fwd_edits: null pointer");
+    TF_ARG(dtype == TF_BF16 || dtype == TF_F16, TF_ERR_DTYPE, "tf_ext_attn_fwd_edits: dtype %d (bf16/f16 only)", dtype);
+    TF_ARG(!(flags & (TF_ATTN_BANK_ONLY | TF_ATTN_SOURCE_ONLY)), TF_ERR_SHAPE,
+           "tf_ext_attn_fwd_edits: TF_ATTN_BANK_ONLY / TF_ATTN_SOURCE_ONLY have no multi-edit form");
+    TF_ARG((flags & (TF_ATTN_MULTI_V | TF_ATTN_NO_MULTI_V)) != (TF_ATTN_MULTI_V | TF_ATTN_NO_MULTI_V), TF_ERR_SHAPE,
+           "tf_ext_attn_fwd_edits: TF_ATTN_MULTI_V and TF_ATTN_NO_MULTI_V exclude each other");
+    if (n_edits == 1)   // today's layout: today's call (the hints of the four-bank form have nothing to select)
+        return attn_fwd_core(q, k, v, out, K, Kq, q_frame0, S, H, Dh, ld, strides, scale,
+                             flags & ~(TF_ATTN_MULTI_V | TF_ATTN_NO_MULTI_V), dtype, ws, ws_bytes, stream, nullptr);
+    const int B = 1 + 2 * n_edits;
+    const int base = flags & ~(TF_ATTN_MULTI_V | TF_ATTN_NO_MULTI_V);
+    const bool inj = (flags & TF_ATTN_INJECT) != 0;
+    const int64_t osz = (flags & TF_ATTN_OUT_F32) ? 4 : 2;
+    auto at = [](const void* ptr, int64_t elems, int64_t esz) {
+        return static_cast<const void*>(static_cast<const unsigned char*>(ptr) + elems * esz);
+    };
+    // the four-bank form: injection, Dh = 40, fp32 score scaling, at least one pair of edits
+    const bool mv_ok = inj && Dh == 40 && !(flags & TF_ATTN_FOLD_SCALE) && n_edits >= 2;
+    const bool mv = mv_ok && !(flags & TF_ATTN_NO_MULTI_V) && ((flags & TF_ATTN_MULTI_V) || mv4_default(K, Kq, S, H));
+    // the pair launches and the odd edit beside them are one-pass streaming launches
+    const int bank_flags = base | TF_ATTN_BANK_ONLY | (mv ? TF_ATTN_NO_SPLIT | TF_ATTN_NO_FUSED : 0);
+    const int src_flags = base | TF_ATTN_SOURCE_ONLY;
+    auto call = [&](int e, int fl, const EditsPart& ed) {   // the part `fl` of edit e (e = 0 for the source branch)
+        const int sh = 2 * e;
+        return attn_fwd_core(inj ? q : at(q, sh * strides[0], 2), inj ? k : at(k, sh * strides[2], 2), at(v, sh * strides[4], 2),
+                             const_cast<void*>(at(out, sh * strides[6], osz)), K, Kq, q_frame0, S, H, Dh, ld, strides, scale, fl,
+                             dtype, ws, ws_bytes, stream, &ed);
+    };
+    // which parts stream (and read the V^T image): the decision of the part's own call
+    const EditsPart probe = EditsPart::probe_of(B);
+    const int src_fused = call(0, src_flags, probe);
+    if (src_fused < 0) return src_fused;
+    const int bank_fused = call(0, bank_flags, probe);
+    if (bank_fused < 0) return bank_fused;
+    const int b_lo = src_fused ? 1 : 0, b_hi = bank_fused ? 1 : B;
+    if (b_lo < b_hi) {   // ONE pre-pass for all of them
+        const int Spad = ((S + 127) / 128) * 128;
+        AttnParams p{};
+        p.k = k, p.vt = ws;
+        p.knorm2 = reinterpret_cast<const float*>(static_cast<unsigned char*>(ws) + ((vt_bytes(K, Spad, H, Dh, B) + 255) & ~(size_t)255));
+        p.K = p.Kb = K, p.S = S, p.H = H, p.Spad = Spad, p.inject = inj ? 1 : 0, p.nseg = 1;
+        p.ld = ld, p.k_bs = strides[2], p.k_fs = strides[3], p.v_bs = strides[4], p.v_fs = strides[5];
+        hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+        const int rc = dtype == TF_BF16 ? launch_vt_pack<BF16>(p, v, Dh, b_lo, b_hi, st) : launch_vt_pack<F16>(p, v, Dh, b_lo, b_hi, st);
+        if (rc) return rc;
+    }
+    // bank branches first (the long problems), then the source branch, as the single-edit call orders them
+    int e = 0;
+    if (mv)
+        for (; e + 2 <= n_edits; e += 2)
+            if (const int rc = call(e, bank_flags, EditsPart::pair_mv4(B, e))) return rc;
+    for (; e < n_edits; ++e)
+        if (const int rc = call(e, bank_flags, mv ? EditsPart::bank_dual(B, e) : EditsPart::bank(B, e))) return rc;
+    return call(0, src_flags, EditsPart::source(B));
+}
+
+// Launch plan of tf_ext_attn_fwd_edits for dense tensors, recorded by the entry point itself as tf_ext_attn_plan does.
+extern "C" int tf_ext_attn_edits_plan(int K, int Kq, int S, int H, int Dh, int n_edits, int flags, int dtype, char* buf,
+                                      size_t len) {
+    TF_ARG(K > 0 && S > 0 && H > 0 && Kq > 0 && Kq <= K, TF_ERR_SHAPE, "tf_ext_attn_edits_plan: K=%d Kq=%d S=%d H=%d", K, Kq,
+           S, H);
+    void* const ph = reinterpret_cast<void*>((uintptr_t)1 << 12);
+    const int64_t ld = (int64_t)H * Dh, fs = (int64_t)S * ld;
+    const int64_t strides[9] = {Kq * fs, fs, K * fs, fs, K * fs, fs, Kq * fs, fs, ld};
+    TfPlanRec rec{buf, len, 0, 0};
+    if (buf && len) buf[0] = 0;
+    tf_plan_rec = &rec;
+    const int rc = tf_ext_attn_fwd_edits(ph, ph, ph, ph, K, Kq, 0, S, H, Dh, ld, strides, 1.0f, flags, dtype, n_edits, ph,
+                                         (size_t)-1, nullptr);
+    tf_plan_rec = nullptr;
+    if (rc) return rc;
+    TF_ARG(rec.used < len, TF_ERR_WORKSPACE, "tf_ext_attn_edits_plan: the plan needs %zu bytes", rec.used + 1);
+    return rec.n;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -115,13 +115,16 @@ struct GbChunks {
 // MERGE: the indices come as the search's per-split partial results (tf_nn_gather_blend: no finalize launch
 // in between); every thread of a token merges them itself -- `splits` 8-byte reads, broadcast from cache.
 // CH: multi-chunk call (P == 2, MERGE).
-template <typename TIn, typename TRes, typename TOut, int P, bool MERGE, bool CH = false>
+// DYN: the number of branches is the argument `nb` (multi-edit batches, [source | uncond_1 | cond_1 | ... ]: the *_edits
+// entry points) instead of the constant 3; the arithmetic of a branch is the same code, so branch b of a DYN launch is
+// bit-identical to branch b of the 3-branch launch on the same tensors.
+template <typename TIn, typename TRes, typename TOut, int P, bool MERGE, bool CH = false, bool DYN = false>
 __global__ __launch_bounds__(256) void gather_blend_kernel(const TIn* __restrict__ kf_out,
                                                            const int32_t* __restrict__ idx,
                                                            const NnPartial* __restrict__ part, int splits,
                                                            const float* __restrict__ w, const TRes* __restrict__ resid,
                                                            TOut* __restrict__ out, int K, int n, int S, int D, int kf0,
-                                                           int kf1, GbChunks ch) {
+                                                           int kf1, GbChunks ch, int nb) {
     const int ppr = D >> 3;  // pieces per row
     const int64_t nS = (int64_t)n * S;
     const int64_t total = nS * ppr;
@@ -150,8 +153,7 @@ __global__ __launch_bounds__(256) void gather_blend_kernel(const TIn* __restrict
             w1 = w[frame];
             w2 = __fsub_rn(1.0f, w1);
         }
-#pragma unroll
-        for (int b = 0; b < 3; ++b) {
+        auto branch = [&](int b) {
             float a1[8], o[8];
             load8(src1 + coff + b * branch_in + (int64_t)i1 * D + c, a1);
             if (P == 2 && !single) {
@@ -178,6 +180,12 @@ __global__ __launch_bounds__(256) void gather_blend_kernel(const TIn* __restrict
                 }
             }
             store8_stream(out + off, o);
+        };
+        if constexpr (DYN) {
+            for (int b = 0; b < nb; ++b) branch(b);
+        } else {
+#pragma unroll
+            for (int b = 0; b < 3; ++b) branch(b);
         }
     }
 }
@@ -194,7 +202,8 @@ template <typename T16, typename TOut, int LPR, int NP, int P, bool CH>
 __global__ __launch_bounds__(256) void gather_blend_norm_kernel(
     const T16* __restrict__ kf_out, const NnPartial* __restrict__ part, int splits, const float* __restrict__ w,
     const T16* __restrict__ resid, TOut* __restrict__ out, T16* __restrict__ norm_out, const void* __restrict__ gamma,
-    const void* __restrict__ beta, int w_dtype, float eps, int K, int n, int S, int D, int kf0, int kf1, GbChunks ch) {
+    const void* __restrict__ beta, int w_dtype, float eps, int K, int n, int S, int D, int kf0, int kf1, GbChunks ch,
+    int nb) {
     constexpr int RPW = 64 / LPR;
     __shared__ __attribute__((aligned(16))) float sw[2][LPR * 8 * NP];
     ln_stage_weights<256>(sw[0], sw[1], gamma, beta, w_dtype, D);
@@ -204,7 +213,8 @@ __global__ __launch_bounds__(256) void gather_blend_norm_kernel(
     const int pieces = D >> 3;
     const float inv_d = 1.0f / (float)D;
     const int64_t nS = (int64_t)n * S;
-    const int64_t rows = 3 * nS;                    // row = b * nS + t  (branch-major, as the output tensor)
+    const int64_t rows = nb * nS;                   // row = b * nS + t  (branch-major, as the output tensor); nb = 3 branches,
+                                                    // 1 + 2E in a multi-edit batch
     const int64_t branch_in = (int64_t)K * S * D;
     const int64_t frame_in = (int64_t)S * D;
     const T16* src1 = kf_out + (int64_t)kf0 * frame_in;
@@ -278,6 +288,15 @@ __global__ __launch_bounds__(256) void inject_copy_kernel(u32x4* __restrict__ x,
     }
 }
 
+// multi-edit batch: x[b] = x[0] for every branch b >= 1 of [source | uncond_1 | cond_1 | ... ]
+__global__ __launch_bounds__(256) void inject_copy_edits_kernel(u32x4* __restrict__ x, int64_t pieces_per_branch, int nb) {
+    for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < pieces_per_branch;
+         g += (int64_t)gridDim.x * 256) {
+        const u32x4 v = x[g];
+        for (int b = 1; b < nb; ++b) x[b * pieces_per_branch + g] = v;
+    }
+}
+
 struct GbArgs {
     const void* kf_out;
     const int32_t* idx;
@@ -295,20 +314,23 @@ struct GbArgs {
     const void* beta = nullptr;
     int w_dtype = 0;
     float eps = 0.f;
+    int nb = 3;         // branches; dyn: the *_edits entry points (branch count as a kernel argument)
+    bool dyn = false;
 };
 
 // fused-norm form: T16 in / residual / norm out, result float (P = 2) or T16 (P = 1)
 template <typename T16, typename TOut, int P, bool CH>
 void launch_gbn(const GbArgs& a) {
-    const int64_t rows = (int64_t)3 * a.n * a.S;
+    const int64_t rows = (int64_t)a.nb * a.n * a.S;
     auto go = [&](auto kern, int lpr) {
         const int rows_per_wg = 4 * (64 / lpr);
         int64_t blocks = (rows + rows_per_wg - 1) / rows_per_wg;
         if (blocks > 256 * 16) blocks = 256 * 16;
         hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, a.st, (const T16*)a.kf_out, a.part, a.splits, a.w,
                            (const T16*)a.resid, (TOut*)a.out, (T16*)a.norm_out, a.gamma, a.beta, a.w_dtype, a.eps, a.K,
-                           a.n, a.S, a.D, a.kf0, P == 2 ? a.kf1 : a.kf0, a.ch);
+                           a.n, a.S, a.D, a.kf0, P == 2 ? a.kf1 : a.kf0, a.ch, a.nb);
     };
+    if (tf_plan_note("gather_norm[branches=%d]", a.nb)) return;
     const int pieces = a.D >> 3;   // 3 pieces per lane: D <= 384 / 768 / 1536 at 16 / 32 / 64 lanes per row
     if (pieces <= 48) go(gather_blend_norm_kernel<T16, TOut, 16, 3, P, CH>, 16);
     else if (pieces <= 96) go(gather_blend_norm_kernel<T16, TOut, 32, 3, P, CH>, 32);
@@ -335,9 +357,13 @@ void launch_gb(const GbArgs& a) {
     if (blocks > 256 * 16) blocks = 256 * 16;
     auto go = [&](auto kern, int kf1) {
         hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, a.st, (const TIn*)a.kf_out, a.idx, a.part,
-                           a.splits, a.w, (const TRes*)a.resid, (TOut*)a.out, a.K, a.n, a.S, a.D, a.kf0, kf1, a.ch);
+                           a.splits, a.w, (const TRes*)a.resid, (TOut*)a.out, a.K, a.n, a.S, a.D, a.kf0, kf1, a.ch, a.nb);
     };
-    if (a.ch.nc > 0) {
+    if (tf_plan_note("gather[branches=%d]", a.nb)) return;
+    if (a.dyn) {   // multi-edit batch: the chunk form, or the one-keyframe chunk alone
+        if (a.ch.nc > 0) go(gather_blend_kernel<TIn, TRes, TOut, 2, true, true, true>, a.kf1);
+        else go(gather_blend_kernel<TIn, TRes, TOut, 1, true, false, true>, a.kf0);
+    } else if (a.ch.nc > 0) {
         go(gather_blend_kernel<TIn, TRes, TOut, 2, true, true>, a.kf1);
     } else if (a.part) {
         if (a.P == 2) go(gather_blend_kernel<TIn, TRes, TOut, 2, true>, a.kf1);
@@ -409,7 +435,8 @@ struct NormArgs {   // the block's next LayerNorm, fused behind the gather (all 
 static int nn_gather_blend_impl(const char* name, const void* tgt, const void* piv, const float* inv_norm,
                                 const void* kf_out, const float* w, const void* resid, void* out, int K, int n, int S,
                                 int D, int P, int kf0, int kf1, int search_dtype, int in_dtype, int res_dtype,
-                                int out_dtype, void* ws, size_t ws_bytes, void* stream, const NormArgs& nm) {
+                                int out_dtype, void* ws, size_t ws_bytes, void* stream, const NormArgs& nm,
+                                int n_edits = 0) {   // n_edits >= 1: a multi-edit batch of 1 + 2*n_edits branches
     TF_ARG(tgt && piv && inv_norm && kf_out && out && ws && (P == 1 || w), TF_ERR_NULL, "%s: null pointer", name);
     TF_ARG(search_dtype == TF_BF16 || search_dtype == TF_F16, TF_ERR_DTYPE, "%s: search dtype %d (bf16/f16 only)", name,
            search_dtype);
@@ -439,6 +466,7 @@ static int nn_gather_blend_impl(const char* name, const void* tgt, const void* p
     const int rc = tf_nn_search_partials(tgt, piv, inv_norm, part, n_tgt, S, D, P, kf0, kf1, search_dtype, st, &splits);
     if (rc) return rc;
     GbArgs a{kf_out, nullptr, part, splits, w, resid, out, K, n, S, D, P, kf0, kf1, st, GbChunks{0, 0, 0}};
+    if (n_edits > 0) a.nb = 1 + 2 * n_edits, a.dyn = true;
     if (nm.out) {
         a.norm_out = nm.out, a.gamma = nm.gamma, a.beta = nm.beta, a.w_dtype = nm.w_dtype, a.eps = nm.eps;
         if (in_dtype == TF_BF16) dispatch_gbn<__bf16>(a);
@@ -450,6 +478,7 @@ static int nn_gather_blend_impl(const char* name, const void* tgt, const void* p
             default: dispatch_res<float>(a, res_dtype, out_dtype); break;
         }
     }
+    if (tf_plan_rec) return 0;   // plan recording: nothing was launched
     TF_LAUNCH_CHECK(name);
     return 0;
 }
@@ -484,7 +513,7 @@ static int nn_gather_blend_chunks_impl(const char* name, const void* tgt, const 
                                        const void* kf_out, const float* w, const void* resid, void* out, int K, int n,
                                        int C, int S, int D, int slot0, int first_single, int search_dtype, int in_dtype,
                                        int res_dtype, int out_dtype, int single_dtype, void* ws, size_t ws_bytes,
-                                       void* stream, const NormArgs& nm) {
+                                       void* stream, const NormArgs& nm, int n_edits = 0) {
     TF_ARG(tgt && piv && inv_norm && kf_out && out && ws && w, TF_ERR_NULL, "%s: null pointer", name);
     TF_ARG(search_dtype == TF_BF16 || search_dtype == TF_F16, TF_ERR_DTYPE, "%s: search dtype %d (bf16/f16 only)", name,
            search_dtype);
@@ -518,6 +547,7 @@ static int nn_gather_blend_chunks_impl(const char* name, const void* tgt, const 
     if (rc) return rc;
     GbArgs a{kf_out, nullptr, part, splits, w, resid, out, K, n * C, S, D, 2, slot0, slot0 - 1, st,
              GbChunks{n, first_single ? 1 : 0, single_dtype}};
+    if (n_edits > 0) a.nb = 1 + 2 * n_edits, a.dyn = true;
     if (nm.out) {
         a.norm_out = nm.out, a.gamma = nm.gamma, a.beta = nm.beta, a.w_dtype = nm.w_dtype, a.eps = nm.eps;
         if (in_dtype == TF_BF16) dispatch_gbn<__bf16>(a);
@@ -529,6 +559,7 @@ static int nn_gather_blend_chunks_impl(const char* name, const void* tgt, const 
             default: dispatch_res<float>(a, res_dtype, out_dtype); break;
         }
     }
+    if (tf_plan_rec) return 0;   // plan recording: nothing was launched
     TF_LAUNCH_CHECK(name);
     return 0;
 }
@@ -557,6 +588,74 @@ extern "C" int tf_nn_gather_blend_chunks_norm(const void* tgt, const void* piv, 
                                        single_dtype, ws, ws_bytes, stream, nm);
 }
 
+// Multi-edit batches (include/tokenflow_hip.h): the chunk forms over B = 1 + 2*n_edits branches.  ONE search (the launches of the
+// 3-branch call: the search reads the source branch only), then the gather loops the B branches on the same candidates.
+// C == 1 is served by the one-chunk forms (the one-keyframe chunk 0 of the video: P = 1; any other chunk: P = 2).
+static int nn_gather_blend_edits(const char* name, const void* tgt, const void* piv, const float* inv_norm,
+                                 const void* kf_out, const float* w, const void* resid, void* out, int K, int n, int C, int S,
+                                 int D, int slot0, int first_single, int search_dtype, int in_dtype, int res_dtype,
+                                 int out_dtype, int single_dtype, void* ws, size_t ws_bytes, void* stream,
+                                 const NormArgs& nm, int n_edits) {
+    TF_ARG(n_edits >= 1 && n_edits <= TF_MAX_EDITS, TF_ERR_SHAPE, "%s: n_edits=%d (1 .. %d)", name, n_edits, TF_MAX_EDITS);
+    if (C == 1 && first_single) {
+        TF_ARG(slot0 >= 0 && slot0 < K, TF_ERR_SHAPE, "%s: slot0=%d outside the %d keyframes", name, slot0, K);
+        TF_ARG(out_dtype == single_dtype, TF_ERR_DTYPE,
+               "%s: the one-keyframe chunk alone is stored in the dtype its own pass produces (out=%d single=%d)", name,
+               out_dtype, single_dtype);
+        return nn_gather_blend_impl(name, tgt, piv, inv_norm, kf_out, nullptr, resid, out, K, n, S, D, 1, slot0, 0,
+                                    search_dtype, in_dtype, res_dtype, out_dtype, ws, ws_bytes, stream, nm, n_edits);
+    }
+    return nn_gather_blend_chunks_impl(name, tgt, piv, inv_norm, kf_out, w, resid, out, K, n, C, S, D, slot0, first_single,
+                                       search_dtype, in_dtype, res_dtype, out_dtype, single_dtype, ws, ws_bytes, stream, nm,
+                                       n_edits);
+}
+
+extern "C" int tf_nn_gather_blend_chunks_edits(const void* tgt, const void* piv, const float* inv_norm, const void* kf_out,
+                                               const float* w, const void* resid, void* out, int K, int n, int C, int S,
+                                               int D, int slot0, int first_single, int search_dtype, int in_dtype,
+                                               int res_dtype, int out_dtype, int single_dtype, int n_edits, void* ws,
+                                               size_t ws_bytes, void* stream) {
+    return nn_gather_blend_edits("tf_nn_gather_blend_chunks_edits", tgt, piv, inv_norm, kf_out, w, resid, out, K, n, C, S, D,
+                                 slot0, first_single, search_dtype, in_dtype, res_dtype, out_dtype, single_dtype, ws,
+                                 ws_bytes, stream, NormArgs{}, n_edits);
+}
+
+extern "C" int tf_nn_gather_blend_chunks_norm_edits(const void* tgt, const void* piv, const float* inv_norm,
+                                                    const void* kf_out, const float* w, const void* resid, void* out,
+                                                    int K, int n, int C, int S, int D, int slot0, int first_single,
+                                                    int search_dtype, int in_dtype, int res_dtype, int out_dtype,
+                                                    int single_dtype, int n_edits, const void* gamma, const void* beta,
+                                                    float eps, int w_dtype, void* norm_out, int norm_dtype, void* ws,
+                                                    size_t ws_bytes, void* stream) {
+    TF_ARG(norm_out, TF_ERR_NULL, "tf_nn_gather_blend_chunks_norm_edits: null norm_out");
+    NormArgs nm;
+    nm.out = norm_out, nm.gamma = gamma, nm.beta = beta, nm.eps = eps, nm.w_dtype = w_dtype, nm.dtype = norm_dtype;
+    return nn_gather_blend_edits("tf_nn_gather_blend_chunks_norm_edits", tgt, piv, inv_norm, kf_out, w, resid, out, K, n, C,
+                                 S, D, slot0, first_single, search_dtype, in_dtype, res_dtype, out_dtype, single_dtype, ws,
+                                 ws_bytes, stream, nm, n_edits);
+}
+
+// Launch plan of tf_nn_gather_blend_chunks_edits (host only): the entry point itself under the plan recorder.
+extern "C" int tf_nn_gather_blend_edits_plan(int n, int C, int S, int D, int first_single, int n_edits, char* buf,
+                                             size_t len) {
+    TF_ARG(n > 0 && C > 0 && S > 0 && D > 0 && D % 8 == 0, TF_ERR_SHAPE, "tf_nn_gather_blend_edits_plan: n=%d C=%d S=%d D=%d",
+           n, C, S, D);
+    void* const ph = reinterpret_cast<void*>((uintptr_t)1 << 12);
+    const float* const phf = reinterpret_cast<const float*>(ph);
+    TfPlanRec rec{buf, len, 0, 0};
+    if (buf && len) buf[0] = 0;
+    tf_plan_rec = &rec;
+    const int K = C + 1;
+    const int rc = tf_nn_gather_blend_chunks_edits(ph, ph, phf, ph, phf, ph, ph, K, n, C, S, D, first_single ? 0 : 1,
+                                                   first_single, TF_BF16, TF_BF16, TF_BF16,
+                                                   (C == 1 && first_single) ? TF_BF16 : TF_F32, TF_BF16, n_edits, ph,
+                                                   (size_t)-1, nullptr);
+    tf_plan_rec = nullptr;
+    if (rc) return rc;
+    TF_ARG(rec.used < len, TF_ERR_WORKSPACE, "tf_nn_gather_blend_edits_plan: the plan needs %zu bytes", rec.used + 1);
+    return rec.n;
+}
+
 extern "C" int tf_inject_copy(void* x, int64_t elems_per_branch, int elem_bytes, void* stream) {
     TF_ARG(x, TF_ERR_NULL, "tf_inject_copy: null pointer");
     TF_ARG(elems_per_branch > 0 && elem_bytes > 0 && (elems_per_branch * elem_bytes) % 16 == 0, TF_ERR_SHAPE,
@@ -569,5 +668,21 @@ extern "C" int tf_inject_copy(void* x, int64_t elems_per_branch, int elem_bytes,
     hipLaunchKernelGGL(inject_copy_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                        reinterpret_cast<u32x4*>(x), pieces);
     TF_LAUNCH_CHECK("tf_inject_copy");
+    return 0;
+}
+
+extern "C" int tf_inject_copy_edits(void* x, int64_t elems_per_branch, int n_branches, int elem_bytes, void* stream) {
+    TF_ARG(x, TF_ERR_NULL, "tf_inject_copy_edits: null pointer");
+    TF_ARG(elems_per_branch > 0 && elem_bytes > 0 && (elems_per_branch * elem_bytes) % 16 == 0 && n_branches >= 3 &&
+               n_branches <= 1 + 2 * TF_MAX_EDITS && (n_branches & 1),
+           TF_ERR_SHAPE, "tf_inject_copy_edits: elems_per_branch=%lld elem_bytes=%d n_branches=%d (bytes per branch %% 16 == 0; "
+           "1 + 2E branches, E <= %d)", (long long)elems_per_branch, elem_bytes, n_branches, TF_MAX_EDITS);
+    TF_ARG(tf_aligned16(x), TF_ERR_ALIGN, "tf_inject_copy_edits: x not 16-byte aligned");
+    const int64_t pieces = elems_per_branch * elem_bytes / 16;
+    int64_t blocks = (pieces + 255) / 256;
+    if (blocks > 256 * 8) blocks = 256 * 8;
+    hipLaunchKernelGGL(inject_copy_edits_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                       reinterpret_cast<u32x4*>(x), pieces, n_branches);
+    TF_LAUNCH_CHECK("tf_inject_copy_edits");
     return 0;
 }

@@ -39,7 +39,7 @@ __all__ = [
     "register_pivotal", "register_batch_idx", "register_time", "load_source_latents_t",
     "register_conv_injection", "register_extended_attention_pnp", "register_extended_attention",
     "make_tokenflow_attention_block", "set_tokenflow", "isinstance_str", "batch_cosine_sim",
-    "register_frame_shard", "join_frame_shard",
+    "register_frame_shard", "join_frame_shard", "register_edits",
 ]
 
 
@@ -145,6 +145,42 @@ def register_time(model, t):
     setattr(tb.attn2, "t", t)
 
 
+def register_edits(model, n_edits):
+    """Multi-edit extension (no counterpart in the reference, which runs one prompt per pass): the passes that follow carry
+    E = n_edits edits of ONE source video, B = 1 + 2E branches [source | uncond_1 | cond_1 | ... | uncond_E | cond_E]
+    instead of [source | uncond | cond].  Sets `n_edits` where `register_time` sets `t`: on the 16 blocks, their `attn1`
+    and the injected resnet.  For every op of the path the slices of edit e are what the single-edit pass computes on
+    [source | uncond_e | cond_e]; the NN search, the source branch and (under injection) the scores are computed once.
+    n_edits = 1 (the default without this call) is the reference's layout and issues exactly the single-edit ops.
+    Not generalised, ValueError with n_edits > 1: a registered frame shard, the AdaLayerNormZero gated path, replay
+    through `tokenflow_amd.graphs.GraphCache` (INTEGRATION.md section 4 shows the driver side)."""
+    n_edits = int(n_edits)
+    from . import _lib
+    if not 1 <= n_edits <= _lib.TF_MAX_EDITS:
+        raise ValueError(f"register_edits: n_edits={n_edits} (1 .. {_lib.TF_MAX_EDITS})")
+    unet = model.unet
+    setattr(unet.up_blocks[1].resnets[1], "n_edits", n_edits)
+    tbs = [unet.up_blocks[res].attentions[b].transformer_blocks[0] for res, blocks in _UP.items() for b in blocks]
+    tbs += [unet.down_blocks[res].attentions[b].transformer_blocks[0] for res, blocks in _DOWN.items() for b in blocks]
+    tbs.append(unet.mid_block.attentions[0].transformer_blocks[0])
+    _set_edits(tbs, n_edits)
+
+
+def _set_edits(blocks, n_edits):
+    """`n_edits` on transformer blocks and their `attn1` (register_edits; tools/hooks_bench.py on its bare block list)."""
+    for tb in blocks:
+        setattr(tb, "n_edits", n_edits)
+        setattr(tb.attn1, "n_edits", n_edits)
+
+
+def _n_edits(module) -> int:
+    """Edits of the batch a module sees (register_edits); 1 = the reference's [source | uncond | cond]."""
+    E = int(getattr(module, "n_edits", 1))
+    if E > 1 and torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+        raise ValueError("register_edits: a multi-edit batch (n_edits > 1) cannot be captured for graphs.py replay yet")
+    return E
+
+
 _latents_cache = collections.OrderedDict()
 _LATENTS_CACHE_ENTRIES = 2      # the current timestep's file (+ one): the driver loads the SAME file C+1 times per step
 
@@ -208,7 +244,11 @@ def register_conv_injection(model, injection_schedule):
         if _injecting(conv_module):
             if not hidden_states.is_contiguous():
                 hidden_states = hidden_states.contiguous()
-            ops.inject_copy_(hidden_states)
+            E = _n_edits(conv_module)
+            if E == 1:
+                ops.inject_copy_(hidden_states)
+            else:       # every edit's uncond and cond branch takes the source branch's activations
+                ops.inject_copy_edits_(hidden_states, E)
         return hidden_states
 
     prev = conv_module.__dict__.pop("_tf_conv_hook", None)
@@ -313,10 +353,15 @@ def _make_sa_forward(self, pnp: bool):
                 q, k, v = q.to(cdt), k.to(cdt), v.to(cdt)
         inject = pnp and _injecting(self)
         shard = None if is_cross else _active_shard(self)
+        E = 1 if is_cross else _n_edits(self)
         if shard is not None:     # q, k, v are this rank's keyframes; the bank is everybody's (register_frame_shard)
+            if E > 1:
+                raise ValueError("register_edits: a multi-edit batch (n_edits > 1) on a registered frame shard is not supported")
             out = shard.pivotal_attention(q, k, v, self.heads, self.scale, inject)
-        else:
+        elif E == 1:
             out = ops.ext_attn(q, k, v, self.heads, self.scale, inject)
+        else:                     # [source | uncond_1 | cond_1 | ...]: the source branch and (injecting) the scores once
+            out = ops.ext_attn_edits(q, k, v, self.heads, self.scale, inject, E)
         return to_out(out if out.dtype == proj_dtype else out.to(proj_dtype))
 
     return forward
@@ -501,8 +546,19 @@ def make_tokenflow_attention_block(block_class: Type[torch.nn.Module]) -> Type[t
                     encoder_attention_mask=None, timestep=None, cross_attention_kwargs=None,
                     class_labels=None) -> torch.Tensor:
             batch_size, sequence_length, dim = hidden_states.shape
-            n_frames = batch_size // 3
-            hidden_states = hidden_states.view(3, n_frames, sequence_length, dim)
+            E = _n_edits(self)
+            nbr = 1 + 2 * E         # branches: [source | uncond | cond], or the multi-edit batch of register_edits
+            if E > 1:
+                if self.__dict__.get("_tf_shard") is not None:
+                    raise ValueError("register_edits: a multi-edit batch (n_edits > 1) on a registered frame shard is not "
+                                     "supported")
+                if self.use_ada_layer_norm_zero:
+                    raise ValueError("register_edits: a multi-edit batch (n_edits > 1) through the AdaLayerNormZero gated path "
+                                     "is not supported")
+                if batch_size % nbr:
+                    raise ValueError(f"register_edits: batch of {batch_size} does not hold {nbr} branches ({E} edits)")
+            n_frames = batch_size // nbr
+            hidden_states = hidden_states.view(nbr, n_frames, sequence_length, dim)
 
             norm_inv = None
             gate_msa = None
@@ -549,7 +605,7 @@ def make_tokenflow_attention_block(block_class: Type[torch.nn.Module]) -> Type[t
                                          else norm_hidden_states.dtype)
                 src = norm_hidden_states[0]
                 self._tf_pivots = src.to(ops.compute_dtype(src)).contiguous()       # [K,S,D] 16-bit
-                self._tf_pivot_inv_norm = (norm_inv.view(3, n_frames, sequence_length)[0] if norm_inv is not None
+                self._tf_pivot_inv_norm = (norm_inv.view(nbr, n_frames, sequence_length)[0] if norm_inv is not None
                                            else ops.pivot_inv_norm(self._tf_pivots))   # [K,S] fp32
                 shard = _active_shard(self)
                 inplace = False
@@ -607,7 +663,7 @@ def make_tokenflow_attention_block(block_class: Type[torch.nn.Module]) -> Type[t
                         shard.halo_wait(reqs)
                         self.__dict__["_tf_halo"] = (piv, inv, kf, [])
                     s0 = c0 - shard.kf0 + 1
-                K = kf.shape[0] // 3
+                K = kf.shape[0] // nbr
                 if self.use_ada_layer_norm_zero:
                     # 362-366: the reference gates the SELECTED keyframe outputs before the gather:
                     # `attn_output = gate_msa.unsqueeze(1) * kf_attn_output.view(3,K,S,D)[:, batch_idxs]`.  Same
@@ -625,7 +681,7 @@ def make_tokenflow_attention_block(block_class: Type[torch.nn.Module]) -> Type[t
                     # keyframes in descending order); lazily -- the gather below reads the cache in place
                     slots = list(range(s0 + n_chunks - 1, (s0 - 1 if c0 > 0 else s0) - 1, -1))
                     self.attn_output = (lambda kf_=kf, K_=K, sl=slots:
-                                        kf_.view(3, K_, sequence_length, dim)[:, sl])
+                                        kf_.view(nbr, K_, sequence_length, dim)[:, sl])
                 # 329-348: nearest neighbours of the SOURCE branch among keyframe c (and c-1), per chunk
                 tgt = norm_hidden_states[0].reshape(n_frames * sequence_length, dim).to(self._tf_pivots.dtype)
                 # 361-397: gather (same indices for the 3 branches), blend, residual -- fused with the search.
@@ -651,7 +707,10 @@ def make_tokenflow_attention_block(block_class: Type[torch.nn.Module]) -> Type[t
                     ndt = _fused_norm_dtype(nxt[1], resid, out_dtype)
                     if ndt is not None and ops.norm_fusable(kf, resid, out_dtype, 2 if two else 1, ndt):
                         fuse = (nxt[1].weight, nxt[1].bias, nxt[1].eps, ndt)
-                if n_chunks == 1:
+                if E > 1:       # one search, one gather over all 1 + 2E branches
+                    res = ops.propagate_chunks_edits(tgt, piv, inv, kf, w, n, n_chunks, s0 - kf_base, c0 == 0, resid,
+                                                     out_dtype, E, norm=fuse)
+                elif n_chunks == 1:
                     ids = [s0 - kf_base] if c0 == 0 else [s0 - kf_base, s0 - 1 - kf_base]
                     res = ops.propagate(tgt, piv, inv, ids, kf, w, n, resid, out_dtype, norm=fuse)
                 else:

@@ -147,6 +147,28 @@ def attn_run_plan(K: int, Kq: int, run_n: int, n_runs: int, S: int, heads: int, 
                         _DT[dtype])
 
 
+def _multi_v_bits(multi_v: Optional[bool]) -> int:
+    return 0 if multi_v is None else _lib.TF_ATTN_MULTI_V if multi_v else _lib.TF_ATTN_NO_MULTI_V
+
+
+def attn_edits_plan(K: int, Kq: int, S: int, heads: int, dh: int, inject: bool, n_edits: int,
+                    dtype: torch.dtype = torch.bfloat16, out_dtype: Optional[torch.dtype] = None,
+                    fold_scale: Optional[bool] = None, no_split: Optional[bool] = None, fused: Optional[bool] = None,
+                    multi_v: Optional[bool] = None, hints: int = 0) -> list:
+    """The launches `ext_attn_edits` makes for dense [(1+2E)K,S,heads*dh] tensors, as tokens (tf_ext_attn_edits_plan: the
+    tokens of `attn_plan`; the four-bank launch of a pair of edits is 'one<40,1,4,MV4,2,fq0>').  Host only: needs no GPU."""
+    flags = _attn_flags(inject, "all", out_dtype == torch.float32, fold_scale, no_split, fused, hints) | _multi_v_bits(multi_v)
+    return _plan_tokens("tf_ext_attn_edits_plan", _lib.load().tf_ext_attn_edits_plan, K, Kq, S, heads, dh, int(n_edits), flags,
+                        _DT[dtype])
+
+
+def propagate_edits_plan(n: int, n_chunks: int, S: int, D: int, first_single: bool, n_edits: int) -> list:
+    """The launches of `propagate_chunks_edits`: the search tokens of `nn_plan` (no finalize: the gather merges the splits)
+    followed by ONE gather over all 1 + 2E branches, 'gather[branches=B]'.  Host only."""
+    return _plan_tokens("tf_nn_gather_blend_edits_plan", _lib.load().tf_nn_gather_blend_edits_plan, int(n), int(n_chunks), S, D,
+                        1 if first_single else 0, int(n_edits))
+
+
 def nn_plan(n_tgt: int, S: int, D: int, P: int, C: int = 1) -> list:
     """The search launches of `nn_search` (C = 1) or of `propagate_chunks` over C > 1 chunks of n_tgt targets (P = 2),
     as tokens (tf_nn_search_plan: e.g. ['glds[splits=2]', 'finalize']).  Host only: needs no GPU."""
@@ -206,6 +228,62 @@ def ext_attn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, scal
     ws = _workspace(nbytes, q.device)
     _launch(dev, "tf_ext_attn_fwd", lib.tf_ext_attn_fwd, q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(),
             K, Kq, int(q_frame0), S, heads, dh, ld, float(scale), flags, dt, ws.data_ptr(), ws.numel())
+    return out
+
+
+def ext_attn_edits(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, scale: float, inject: bool,
+                   n_edits: int, out: Optional[torch.Tensor] = None, q_frame0: int = 0,
+                   fold_scale: Optional[bool] = None, out_dtype: Optional[torch.dtype] = None,
+                   no_split: Optional[bool] = None, fused: Optional[bool] = None, multi_v: Optional[bool] = None,
+                   hints: int = 0) -> torch.Tensor:
+    """`ext_attn` for a multi-edit batch: E = n_edits edits of one source video, B = 1 + 2E branches
+    [source | uncond_1 | cond_1 | ... | uncond_E | cond_E].  k, v: [B*K,S,D], q: [B*Kq,S,D]; returns [B*Kq,S,D].
+    The slices of edit e (source, uncond_e, cond_e) are what `ext_attn` computes on [source | uncond_e | cond_e]: the
+    bank branches equal `ext_attn_views(part="bank")` on that edit's slabs and the source branch `part="source"` bit for
+    bit -- except where pairs of edits take the four-bank shared-softmax launch under injection (head dim 40), which is
+    held to the oracle within the attention bound.  multi_v: True / False force that form on / off (TF_ATTN_MULTI_V /
+    TF_ATTN_NO_MULTI_V), None = the library's measured default.  n_edits = 1 is `ext_attn`.  Other arguments as `ext_attn`."""
+    dev = _need_gpu(q, k, v, out)
+    lib = _lib.load()
+    E = int(n_edits)
+    if not 1 <= E <= _lib.TF_MAX_EDITS:
+        raise ValueError(f"ext_attn_edits: n_edits={n_edits} (1 .. {_lib.TF_MAX_EDITS})")
+    nbr = 1 + 2 * E
+    BK, S, D = k.shape
+    Bq = q.shape[0]
+    if BK % nbr or Bq % nbr or D % heads or q.shape[1:] != k.shape[1:] or v.shape != k.shape:
+        raise ValueError(f"ext_attn_edits: bad shapes q{tuple(q.shape)} k{tuple(k.shape)} v{tuple(v.shape)} heads {heads} "
+                         f"for {E} edits ({nbr} branches)")
+    K, Kq, dh = BK // nbr, Bq // nbr, D // heads
+    dt = _DT.get(q.dtype)
+    if dt is None or dt == _lib.TF_F32 or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise TypeError(f"ext_attn_edits: q/k/v must share dtype bf16 or f16, got {q.dtype},{k.dtype},{v.dtype}")
+
+    def rows(t):
+        if t.stride(-1) != 1 or t.stride(0) != S * t.stride(1):
+            t = t.contiguous()
+        return t
+    q, k, v = rows(q), rows(k), rows(v)
+    ld = q.stride(1)
+    if k.stride(1) != ld or v.stride(1) != ld:
+        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        ld = D
+    if out_dtype is None:
+        out_dtype = out.dtype if out is not None else q.dtype
+    if out_dtype not in (q.dtype, torch.float32):
+        raise TypeError(f"ext_attn_edits: out_dtype {out_dtype} (the input dtype or float32)")
+    if out is None:
+        out = torch.empty(Bq, S, D, dtype=out_dtype, device=q.device)
+    elif out.dtype != out_dtype or not out.is_contiguous() or out.shape != (Bq, S, D):
+        raise ValueError("ext_attn_edits: `out` must be a contiguous [B*Kq,S,D] tensor of out_dtype")
+    flags = _attn_flags(inject, "all", out_dtype == torch.float32, fold_scale, no_split, fused, hints) | _multi_v_bits(multi_v)
+    nbytes = lib.tf_ext_attn_edits_workspace_bytes(K, S, heads, dh, E, dt)
+    ws = _workspace(nbytes, q.device)
+    fs = S * ld
+    strides = (ctypes.c_int64 * 9)(Kq * fs, fs, K * fs, fs, K * fs, fs, Kq * S * D, S * D, ld)
+    _launch(dev, "tf_ext_attn_fwd_edits", lib.tf_ext_attn_fwd_edits, q.data_ptr(), k.data_ptr(), v.data_ptr(),
+            out.data_ptr(), K, Kq, int(q_frame0), S, heads, dh, ld, ctypes.cast(strides, ctypes.c_void_p), float(scale),
+            flags, dt, E, ws.data_ptr(), ws.numel())
     return out
 
 
@@ -628,6 +706,62 @@ def propagate_chunks(tgt: torch.Tensor, piv: torch.Tensor, inv_norm: torch.Tenso
             _DT[residual.dtype] if residual is not None else 0, _DT[out_dtype], _DT[single_dtype],
             ws.data_ptr(), ws.numel())
     return out
+
+
+def propagate_chunks_edits(tgt: torch.Tensor, piv: torch.Tensor, inv_norm: torch.Tensor, kf_out: torch.Tensor,
+                           w: Optional[torch.Tensor], n: int, n_chunks: int, slot0: int, first_single: bool,
+                           residual: Optional[torch.Tensor], out_dtype: torch.dtype, n_edits: int, norm=None):
+    """`propagate_chunks` (n_chunks = 1: `propagate`) for a multi-edit batch of B = 1 + 2*n_edits branches: kf_out [B*K,S,D],
+    residual / result [B*n_chunks*n, S, D]; tgt (the source branch's rows), piv, inv_norm, w as there.  ONE search -- it
+    reads the source branch only -- and one gather over all B branches on the same candidates; every branch of the result
+    is bit-identical to the same branch of the single-edit call on [source | uncond_e | cond_e].  norm= as `propagate`."""
+    dev = _need_gpu(tgt, piv, inv_norm, kf_out, w, residual)
+    lib = _lib.load()
+    E = int(n_edits)
+    if not 1 <= E <= _lib.TF_MAX_EDITS:
+        raise ValueError(f"propagate_chunks_edits: n_edits={n_edits} (1 .. {_lib.TF_MAX_EDITS})")
+    nbr = 1 + 2 * E
+    tgt, piv, kf_out = tgt.contiguous(), piv.contiguous(), kf_out.contiguous()
+    K, S, D = piv.shape
+    C = int(n_chunks)
+    single = C == 1 and first_single           # the one-keyframe chunk 0 of the video alone: P = 1
+    if (tgt.dtype != piv.dtype or tgt.shape != (C * n * S, D) or kf_out.shape != (nbr * K, S, D)
+            or (w is None and not single) or slot0 + C > K or slot0 < (0 if first_single else 1)):
+        raise ValueError("propagate_chunks_edits: bad arguments")
+    if residual is not None:
+        residual = residual.contiguous()
+        if residual.shape != (nbr * C * n, S, D):
+            raise ValueError("propagate_chunks_edits: residual must be [B*n_chunks*n, S, D]")
+    single_dtype = kf_out.dtype if residual is None else torch.promote_types(kf_out.dtype, residual.dtype)
+    out = torch.empty(nbr * C * n, S, D, dtype=out_dtype, device=kf_out.device)
+    ws = _workspace(max(lib.tf_nn_gather_blend_chunks_workspace_bytes(n * S, S, D, C),
+                        lib.tf_nn_gather_blend_workspace_bytes(n * S, S, D, 1) if single else 0), tgt.device, "nn")
+    head = (tgt.data_ptr(), piv.data_ptr(), inv_norm.data_ptr(), kf_out.data_ptr(), w.data_ptr() if w is not None else 0,
+            residual.data_ptr() if residual is not None else 0, out.data_ptr(), K, n, C, S, D, int(slot0),
+            1 if first_single else 0, _DT[tgt.dtype], _DT[kf_out.dtype],
+            _DT[residual.dtype] if residual is not None else 0, _DT[out_dtype], _DT[single_dtype], E)
+    if norm is not None:
+        if not norm_fusable(kf_out, residual, out_dtype, 1 if single else 2, norm[3]):
+            raise TypeError("propagate_chunks_edits: these dtypes have no fused-norm form (ops.norm_fusable)")
+        g, b, eps, wdt, nout, ndt, _keep = _norm_args(norm, kf_out, (nbr * C * n, S, D))
+        _launch(dev, "tf_nn_gather_blend_chunks_norm_edits", lib.tf_nn_gather_blend_chunks_norm_edits, *head, g, b, eps, wdt,
+                nout.data_ptr(), ndt, ws.data_ptr(), ws.numel())
+        return out, nout
+    _launch(dev, "tf_nn_gather_blend_chunks_edits", lib.tf_nn_gather_blend_chunks_edits, *head, ws.data_ptr(), ws.numel())
+    return out
+
+
+def inject_copy_edits_(x: torch.Tensor, n_edits: int) -> torch.Tensor:
+    """In place, multi-edit batch of B = 1 + 2*n_edits branches: x[b*n:(b+1)*n] = x[:n] for every b >= 1, n = len(x)//B
+    (tokenflow_utils.py:87-91 for every edit).  n_edits = 1 is `inject_copy_`."""
+    dev = _need_gpu(x)
+    lib = _lib.load()
+    nbr = 1 + 2 * int(n_edits)
+    if not 1 <= int(n_edits) <= _lib.TF_MAX_EDITS or x.shape[0] % nbr or not x.is_contiguous():
+        raise ValueError(f"inject_copy_edits_: need a contiguous tensor whose batch is a multiple of {nbr} "
+                         f"(n_edits 1 .. {_lib.TF_MAX_EDITS})")
+    _launch(dev, "tf_inject_copy_edits", lib.tf_inject_copy_edits, x.data_ptr(), x.numel() // nbr, nbr, x.element_size())
+    return x
 
 
 def inject_copy_(x: torch.Tensor) -> torch.Tensor:

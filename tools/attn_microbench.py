@@ -1,7 +1,10 @@
 #!/usr/bin/env python
 """Time tf_ext_attn_fwd (and optionally tf_nn_search) on BASELINE shapes, one process per library
 build so that kernel variants can be A/B-ed:  TOKENFLOW_HIP_LIB=<.so> python tools/attn_microbench.py
-Prints avg/min ms over `reps` launches (HIP events on the launch stream) and TFLOP/s (algorithmic)."""
+Prints avg/min ms over `reps` launches (HIP events on the launch stream) and TFLOP/s (algorithmic).
+--edits E: a multi-edit batch of E edits under q/k injection, alternating A/B of three arms per shape -- (a) E full
+single-edit `ext_attn` calls (one per prompt), (b) `ext_attn_edits`, the composition, (c) `ext_attn_edits` with the
+four-bank form on -- median / min over --rounds rounds, plus the spread of arm (b) against itself."""
 import os
 import sys
 
@@ -24,12 +27,72 @@ def time_it(fn, reps=8, warm=2):
     return sum(t) / len(t), min(t)
 
 
+def ab(arms, rounds=15, warm=3):
+    """Alternating A/B: every round times each arm once, in turn (device events).  {name: (median, min, max)} in ms."""
+    for _ in range(warm):
+        for fn in arms.values():
+            fn()
+    torch.cuda.synchronize()
+    t = {name: [] for name in arms}
+    for _ in range(rounds):
+        for name, fn in arms.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            torch.cuda.synchronize()
+            t[name].append(a.elapsed_time(b))
+    return {name: (sorted(x)[len(x) // 2], min(x), max(x)) for name, x in t.items()}
+
+
+def flag(name, default):
+    """--name VALUE out of sys.argv (removed from it)."""
+    if name in sys.argv:
+        i = sys.argv.index(name)
+        val = int(sys.argv[i + 1])
+        del sys.argv[i:i + 2]
+        return val
+    return default
+
+
+def edits_ab(shapes, E, dt, rounds):
+    g = torch.Generator(device="cuda").manual_seed(0)
+    B = 1 + 2 * E
+    for K, S, h, d in shapes:
+        D = h * d
+        q, k, v = (torch.randn(B * K, S, D, generator=g, device="cuda").to(dt) for _ in range(3))
+        out = torch.empty_like(q)
+        singles = []
+        for e in range(E):      # what a user does today: one full pass per prompt over [source | uncond_e | cond_e]
+            sel = [0, 1 + 2 * e, 2 + 2 * e]
+            singles.append(tuple(t.view(B, K, S, D)[sel].reshape(3 * K, S, D).contiguous() for t in (q, k, v)))
+        out1 = torch.empty_like(singles[0][0])
+
+        def a_single():
+            for q1, k1, v1 in singles:
+                ops.ext_attn(q1, k1, v1, h, d ** -0.5, True, out=out1)
+        arms = {"(a) E single-edit calls": a_single,
+                "(b) composition": lambda: ops.ext_attn_edits(q, k, v, h, d ** -0.5, True, E, out=out, multi_v=False),
+                "(b') composition again": lambda: ops.ext_attn_edits(q, k, v, h, d ** -0.5, True, E, out=out, multi_v=False)}
+        plan_c = ops.attn_edits_plan(K, K, S, h, d, True, E, dtype=dt, multi_v=True)
+        if any("MV4" in t for t in plan_c):
+            arms["(c) four-bank form"] = lambda: ops.ext_attn_edits(q, k, v, h, d ** -0.5, True, E, out=out, multi_v=True)
+        print(f"ext_attn_edits {str(dt)[6:]} K={K} S={S} h={h} d={d} inject=1 E={E}  ({rounds} alternating rounds)")
+        print(f"  plan (b): {ops.attn_edits_plan(K, K, S, h, d, True, E, dtype=dt, multi_v=False)}")
+        print(f"  plan (c): {plan_c}")
+        for name, (med, mn, mx) in ab(arms, rounds).items():
+            print(f"  {name:26s} median {med:.3f} ms  min {mn:.3f} ms  max {mx:.3f} ms", flush=True)
+
+
 def main():
     shapes = [(8, 4096, 8, 40), (8, 1024, 8, 80), (8, 256, 8, 160), (10, 9216, 5, 64)]
+    E, rounds = flag("--edits", 0), flag("--rounds", 15)
     args = [a for a in sys.argv[1:] if a not in ("f16", "bf16")]
     dt = torch.float16 if "f16" in sys.argv[1:] else torch.bfloat16
     if args:
         shapes = [tuple(int(x) for x in a.split(",")) for a in args]
+    if E:
+        return edits_ab(shapes, E, dt, rounds)
     g = torch.Generator(device="cuda").manual_seed(0)
     for K, S, h, d in shapes:
         D = h * d

@@ -9,6 +9,8 @@ calls the ops directly on pre-made tensors.
       --proj        keep attn1's q/k/v/out Linear layers (default: identities)
       --graph       replay every pass from a HIP graph (tokenflow_amd.graphs.GraphCache): one host call per pass
       --all-chunks  ONE propagation pass over all chunks (register_batch_idx(model, range(K))) instead of K passes
+      --edits E     a multi-edit batch: E edits of the source video in one step, 1 + 2E branches (what register_edits sets);
+                    compare with E times the step of the plain command (one step per prompt).  Eager only.
       --ranks W [--rank r] [--wire-less]
                     ONE rank of a W-GPU frame-sharded run through the hook API (register_frame_shard with a NativeShard on
                     the library's loopback transport: every exchange a same-size local copy; --wire-less: no copies at
@@ -144,6 +146,8 @@ def main():
     if "--breakdown" in sys.argv:
         return breakdown()
     ranks, rank = _opt("--ranks", 1), _opt("--rank", 1)
+    edits = _opt("--edits", 1)
+    nbr = 1 + 2 * edits
     wireless = "--wire-less" in sys.argv
     argv = [a for a in sys.argv[1:] if not a.startswith("--")]
     cfg = workload.CONFIGS[argv[0] if len(argv) > 0 else "cfg2"]
@@ -156,6 +160,7 @@ def main():
         hooks._set_schedule(blk.attn1, [5] if injected else [])
         blk.attn1.t = 5
     tfu.set_tokenflow(holder)
+    hooks._set_edits([blk for blk, _, _ in blocks], edits)    # register_edits' own setter (the holder here is no UNet)
     K, n = cfg.K, cfg.chunk
     shard, Kq, chunks = None, K, list(range(K))
     if ranks > 1:
@@ -170,13 +175,13 @@ def main():
         shard = sharded.FrameShard(K, attn_split="--split" in sys.argv)
         hooks.register_frame_shard(holder, shard)
     g = torch.Generator(device=dev).manual_seed(0)
-    xs_piv = [torch.randn(3 * Kq, cfg.levels[l][0], cfg.levels[l][1], generator=g, device=dev, dtype=dtype)
+    xs_piv = [torch.randn(nbr * Kq, cfg.levels[l][0], cfg.levels[l][1], generator=g, device=dev, dtype=dtype)
               for _, l, _ in blocks]
-    xs_chk = [torch.randn(3 * n, cfg.levels[l][0], cfg.levels[l][1], generator=g, device=dev, dtype=dtype)
+    xs_chk = [torch.randn(nbr * n, cfg.levels[l][0], cfg.levels[l][1], generator=g, device=dev, dtype=dtype)
               for _, l, _ in blocks]
 
     if ALL_CHUNKS:     # one pass carries every chunk: frames chunk-major inside each branch
-        xs_chk = [x.view(3, 1, n, *x.shape[1:]).expand(3, len(chunks), n, *x.shape[1:]).reshape(3 * len(chunks) * n, *x.shape[1:]).contiguous()
+        xs_chk = [x.view(nbr, 1, n, *x.shape[1:]).expand(nbr, len(chunks), n, *x.shape[1:]).reshape(nbr * len(chunks) * n, *x.shape[1:]).contiguous()
                   for x in xs_chk]
     cache = None
     if GRAPH:
@@ -226,7 +231,7 @@ def main():
     t_cpu = time.perf_counter() - t0
     torch.cuda.synchronize()
     t = time.perf_counter() - t0
-    mode = ("graph replay" if GRAPH else "eager") + (", one pass over all chunks" if ALL_CHUNKS else "") + (", real projections" if PROJ else "")
+    mode = ("graph replay" if GRAPH else "eager") + (f", {edits} edits in one pass" if edits > 1 else "") + (", one pass over all chunks" if ALL_CHUNKS else "") + (", real projections" if PROJ else "")
     if shard is not None and ranks > 1:
         mode += f", rank {rank} of {ranks} (native executor, loopback transport{' without copies' if wireless else ''})"
     elif shard is not None:
