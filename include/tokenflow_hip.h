@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define TF_ABI_VERSION 10
+#define TF_ABI_VERSION 11
 
 /* Every entry point below is exported with default visibility; the library itself is built with -fvisibility=hidden, so
  * its exported symbols are exactly the declarations of this header (checked by tests/test_hooks_cpu.py). */
@@ -208,6 +208,44 @@ TF_API int tf_ext_attn_fwd_edits(const void* q, const void* k, const void* v, vo
 
 TF_API int tf_ext_attn_edits_plan(int K, int Kq, int S, int H, int Dh, int n_edits, int flags, int dtype, char* buf,
                            size_t len);
+
+/* ------------------------------------------------------------------------
+ * Per-edit injection state (ABI 11): the edits of one batch may differ in their q/k injection schedule (PnP's pnp_attn_t), so
+ * at some steps only SOME of them inject.  tf_ext_attn_fwd_edits_masked takes the arguments of tf_ext_attn_fwd_edits plus
+ * inject_mask: bit e set = edit e (0-based) injects, i.e. its uncond and cond branches use the source's q and k; bit e clear =
+ * they use their own.  The mask IS the injection state: TF_ATTN_INJECT in `flags` gives TF_ERR_SHAPE, and so does a bit at or
+ * above n_edits.  Semantics as above: the slices of edit e are what tf_ext_attn_fwd_strided computes on
+ * [source | uncond_e | cond_e] with edit e's OWN flag.  Workspace: tf_ext_attn_edits_workspace_bytes, unchanged.
+ *
+ * Composition: ONE V^T pre-pass over the span of the branches that a streaming launch reads; it leaves the key norms of
+ * every branch whose own keys are read -- the source and the edits that do not inject.  Then the bank launches, the source
+ * branch last:
+ *   1. the injecting edits in ascending order, paired 1st with 2nd, 3rd with 4th, ...: a pair takes the four-bank form where
+ *      the pair rule selects it, otherwise each edit the launches of its TF_ATTN_BANK_ONLY | TF_ATTN_INJECT call;
+ *   2. an odd last injecting edit as the odd edit of tf_ext_attn_fwd_edits (the DUAL launch beside four-bank pairs);
+ *   3. the other edits in ascending order, each through the launches of its own TF_ATTN_BANK_ONLY call on its own q / k / v;
+ *   4. the source branch through the launches of the TF_ATTN_SOURCE_ONLY call.  That call is given TF_ATTN_INJECT iff EVERY
+ *      edit injects: the source branch reads its own q and k either way and its values do not depend on the flag, but the
+ *      launch decision of a source-only call may, and the two uniform masks must be tf_ext_attn_fwd_edits exactly.
+ * Pair rule of the four-bank form: as for tf_ext_attn_fwd_edits, with the number of INJECTING edits (>= 2) in the place of
+ * n_edits; Dh = 40, fp32 score scaling, TF_ATTN_MULTI_V / TF_ATTN_NO_MULTI_V and the measured default unchanged.  The two
+ * edits of a pair need not be neighbours (mask 0b101 pairs edits 0 and 2): the launch is given the branch distance between
+ * them and is the same grid and work as a pair of neighbours.
+ *
+ * Identity: edit e's bank branches equal that edit's tf_ext_attn_fwd_strided(..., TF_ATTN_BANK_ONLY [| TF_ATTN_INJECT]) call,
+ * and the source branch the TF_ATTN_SOURCE_ONLY call, BIT FOR BIT; the exception is a pair in the four-bank form, held to the
+ * oracle within the attention bound.  inject_mask == 0 and inject_mask == all ones record exactly the plans of
+ * tf_ext_attn_fwd_edits without / with TF_ATTN_INJECT and give the same bits (that entry point IS these two masks).
+ *
+ * tf_ext_attn_edits_masked_plan: the launches of the call for dense tensors (host only), the tokens of
+ * tf_ext_attn_edits_plan.
+ * ------------------------------------------------------------------------ */
+TF_API int tf_ext_attn_fwd_edits_masked(const void* q, const void* k, const void* v, void* out, int K, int Kq, int q_frame0,
+                                 int S, int H, int Dh, int64_t ld, const int64_t* strides, float scale, int flags, int dtype,
+                                 int n_edits, unsigned inject_mask, void* ws, size_t ws_bytes, void* stream);
+
+TF_API int tf_ext_attn_edits_masked_plan(int K, int Kq, int S, int H, int Dh, int n_edits, unsigned inject_mask, int flags,
+                                  int dtype, char* buf, size_t len);
 
 /* ------------------------------------------------------------------------
  * Extended attention over a bank that arrives in pieces: "run + merge" (ABI 9).
@@ -475,6 +513,12 @@ TF_API int tf_inject_copy(void* x, int64_t elems_per_branch, int elem_bytes, voi
 /* The same for a multi-edit batch: x viewed as [n_branches, elems_per_branch], x[b] = x[0] for every b >= 1 (in place);
  * n_branches = 1 + 2E, 3 .. 1 + 2*TF_MAX_EDITS.  Bit-exact copies. */
 TF_API int tf_inject_copy_edits(void* x, int64_t elems_per_branch, int n_branches, int elem_bytes, void* stream);
+
+/* Per-edit feature injection (ABI 11): the same for the edits in edit_mask only -- bit e set: x[1 + 2e] = x[2 + 2e] = x[0];
+ * every other branch is neither read nor written.  One launch (the kernel of tf_inject_copy_edits with a branch mask);
+ * all ones gives the result of tf_inject_copy_edits, 0 launches nothing.  A bit at or above E: TF_ERR_SHAPE. */
+TF_API int tf_inject_copy_edits_masked(void* x, int64_t elems_per_branch, int n_branches, unsigned edit_mask, int elem_bytes,
+                                void* stream);
 
 /* ------------------------------------------------------------------------
  * Multi-GPU exchange steps over RCCL (one process per GPU).  The reference is single-process (no

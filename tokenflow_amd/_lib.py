@@ -23,7 +23,7 @@ def attn_hint(qw: int = 0, kw: int = 0, qb: int = 1) -> int:
     return (code[qw] << 8) | (code[kw] << 11) | (TF_ATTN_HINT_QB2 if qb == 2 else 0)
 
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 TF_MAX_EDITS = 8
 TF_RANK_HEADS, TF_RANK_BANK, TF_RANK_SLOTS, TF_RANK_NO_HALO, TF_RANK_INV_NORM = 0, 1, 64, 16, 32
 TF_RANK_BANK_RUNS = 2
@@ -53,6 +53,12 @@ _SIGNATURES = {
                                                         _c.c_size_t, _c.c_void_p]),
     "tf_nn_gather_blend_edits_plan": (_c.c_int, [_c.c_int] * 6 + [_c.c_char_p, _c.c_size_t]),
     "tf_inject_copy_edits": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int, _c.c_int, _c.c_void_p]),
+    # per-edit injection state (ABI 11)
+    "tf_ext_attn_fwd_edits_masked": (_c.c_int, [_c.c_void_p] * 4 + [_c.c_int] * 6 + [_c.c_int64, _c.c_void_p, _c.c_float,
+                                                _c.c_int, _c.c_int, _c.c_int, _c.c_uint, _c.c_void_p, _c.c_size_t,
+                                                _c.c_void_p]),
+    "tf_ext_attn_edits_masked_plan": (_c.c_int, [_c.c_int] * 6 + [_c.c_uint, _c.c_int, _c.c_int, _c.c_char_p, _c.c_size_t]),
+    "tf_inject_copy_edits_masked": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int, _c.c_uint, _c.c_int, _c.c_void_p]),
     # attention over a bank that arrives in pieces: run + merge (ABI 9)
     "tf_ext_attn_runs_workspace_bytes": (_c.c_size_t, [_c.c_int] * 7),
     "tf_ext_attn_run": (_c.c_int, [_c.c_void_p] * 4 + [_c.c_int] * 10 + [_c.c_int64, _c.c_void_p, _c.c_float, _c.c_int,

@@ -114,6 +114,10 @@ struct AttnParams {
     // host only, multi-edit batches (tf_ext_attn_fwd_edits): the composing call has packed V^T for all branches already /
     // the bank launch is the four-bank shared-softmax form (MODE_MV4) / the DUAL form at any S (the odd edit beside it)
     int no_pack, mv4, force_dual;
+    // MODE_MV4: branches between the uncond branches of the launch's two edits (2 = adjacent edits); its banks 2 and 3 are the
+    // branches b + gap and b + gap + 1 of the V^T image and of the output (the masked multi-edit call pairs injecting edits
+    // that need not be neighbours)
+    int gap;
 };
 
 // max over the two lanes (l, l ^ 32) that share a query: v_permlane32_swap instead of an LDS round trip
@@ -157,7 +161,8 @@ template <typename T>
 __global__ __launch_bounds__(256) void vt_pack_kernel(const typename T::elem* __restrict__ v,
                                                       typename T::elem* __restrict__ vt,
                                                       const typename T::elem* __restrict__ k,
-                                                      float* __restrict__ knorm2, int inject, int b0, int nf, int K,
+                                                      float* __restrict__ knorm2, unsigned own, int b_src, int b0, int nf,
+                                                      int K,
                                                       int S, int H, int DH, int Spad, int64_t ld, int64_t v_bs,
                                                       int64_t v_fs, int64_t k_bs, int64_t k_fs, int* __restrict__ run_hdr,
                                                       int run_slots) {
@@ -174,10 +179,12 @@ __global__ __launch_bounds__(256) void vt_pack_kernel(const typename T::elem* __
     // run launches: the number of partial-result slots the run fills, for tf_ext_attn_runs_merge
     if (run_hdr != nullptr && (blockIdx.x | blockIdx.y | blockIdx.z | threadIdx.x) == 0) *run_hdr = run_slots;
     const E* src = v + b * v_bs + f * v_fs + h * DH;
-    // keys of branch b without injection; with injection every branch reads the SOURCE keys, whose norms the
-    // first packed branch computes
-    if (k != nullptr && (!inject || b == b0) && threadIdx.x < 64) {   // wave 0: one key per lane
-        const int kb = inject ? 0 : b;
+    // keys of branch b where the branch's own keys are read (bit b of `own`: no injection; in a multi-edit batch the source
+    // and the edits that do not inject); under injection a branch reads the SOURCE keys, whose norms the workgroups of
+    // branch b_src compute (the first packed branch; -1: the source is among the `own` branches)
+    const bool own_k = (own >> b) & 1u;
+    if (k != nullptr && (own_k || b == b_src) && threadIdx.x < 64) {   // wave 0: one key per lane
+        const int kb = own_k ? b : 0;
         const int kk = tt * 64 + (int)threadIdx.x;
         float acc = 0.f;
         if (kk < S) {
@@ -223,7 +230,8 @@ __global__ __launch_bounds__(256) void vt_pack_kernel(const typename T::elem* __
 //                     once, two P.V products against the two V banks (NB = 2).
 //        MODE_MV4:    multi-edit batch under injection (Dh = 40): the uncond and cond branches of TWO edits share the
 //                     source q and k, so one workgroup does QK^T and the softmax once and FOUR P.V products (NB = 4)
-//                     against the banks of branches b .. b + 3 of the V^T image.
+//                     against the banks of branches b, b + 1, b + gap, b + gap + 1 of the V^T image (p.gap = 2: neighbouring
+//                     edits; the masked multi-edit call pairs the INJECTING edits, whatever lies between them).
 // MINW = min waves per SIMD for the register allocator
 // FQ   = fold the softmax scale into Q (see FOLD below; opt-in, TF_ATTN_FOLD_SCALE); false = the default, fp32
 //        scaling of the scores as the reference does (tokenflow_utils.py:173-175 `* self.scale` on the bmm output)
@@ -337,10 +345,13 @@ __global__ __launch_bounds__(64 * NW, MINW) void ext_attn_kernel(AttnParams p) {
     const E* qg = reinterpret_cast<const E*>(p.q);
     const E* kg = reinterpret_cast<const E*>(p.k) + bq * p.k_bs + h * DH;
     const int64_t vt_row = vt_row_stride(p.Kb, p.Spad);
+    // branch of V bank vb relative to b: consecutive branches, except that the second edit of a four-bank launch starts
+    // p.gap branches behind the first (gap = 2: neighbours)
+    auto bank_off = [&](int vb) { return (MODE == MODE_MV4 && vb >= 2) ? vb + (p.gap - 2) : vb; };
     const E* vg[NB];
 #pragma unroll
     for (int vb = 0; vb < NB; ++vb)
-        vg[vb] = reinterpret_cast<const E*>(p.vt) + ((int64_t)((b + vb) * H + h) * DH) * vt_row;
+        vg[vb] = reinterpret_cast<const E*>(p.vt) + ((int64_t)((b + bank_off(vb)) * H + h) * DH) * vt_row;
 
     // ---- LDS pads, written once and never staged over: K columns DH..DKP-1 = 0,
     //      V^T rows DH..VROWS-1 = 0 except row DH = 1 (denominator row) when ONES.
@@ -736,7 +747,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void ext_attn_kernel(AttnParams p) {
                         f32x4 w;
 #pragma unroll
                         for (int i = 0; i < 4; ++i) w[i] = o[g >> 1][qi][g & 1][rg * 4 + i] * inv_l;
-                        store_out4<E, vec4>(p.out, op0 + vb * branch + (R - vb * DH), w, p.out_f32);
+                        store_out4<E, vec4>(p.out, op0 + bank_off(vb) * branch + (R - vb * DH), w, p.out_f32);
                     }
                 }
         } else if (q_ok[qi]) {
@@ -2196,7 +2207,7 @@ int launch_one(AttnParams p, hipStream_t st) {
 
 // The V^T pre-pass over branches [b_lo, b_hi) of v (a multi-edit batch: once for all 1 + 2E branches)
 template <typename T>
-int launch_vt_pack(const AttnParams& p, const void* v, int DH, int b_lo, int b_hi, hipStream_t st) {
+int launch_vt_pack(const AttnParams& p, const void* v, int DH, int b_lo, int b_hi, unsigned own, int b_src, hipStream_t st) {
     typedef typename T::elem E;
     dim3 grid((unsigned)(p.Spad / 64), (unsigned)p.H, (unsigned)((b_hi - b_lo) * p.K));
     const size_t lds = (size_t)64 * (DH + 2) * sizeof(E);
@@ -2206,7 +2217,7 @@ int launch_vt_pack(const AttnParams& p, const void* v, int DH, int b_lo, int b_h
         hipLaunchKernelGGL(vt_pack_kernel<T>, grid, dim3(256), lds, st, reinterpret_cast<const E*>(v),
                            reinterpret_cast<E*>(const_cast<void*>(p.vt)),
                            bound ? reinterpret_cast<const E*>(p.k) : nullptr, const_cast<float*>(p.knorm2),
-                           p.inject, b_lo, p.K, p.Kb, p.S, p.H, DH, p.Spad, p.ld, p.v_bs, p.v_fs, p.k_bs, p.k_fs,
+                           own, b_src, b_lo, p.K, p.Kb, p.S, p.H, DH, p.Spad, p.ld, p.v_bs, p.v_fs, p.k_bs, p.k_fs,
                            p.run_hdr, p.nseg);
         TF_LAUNCH_CHECK("tf_ext_attn_fwd(vt_pack)");
     }
@@ -2226,7 +2237,10 @@ int launch_attn(const AttnParams& p, const void* v, hipStream_t st) {
     if (!p.no_pack) {   // pre-pass: V -> transposed, key-permuted, per-frame padded bank (only the branches this call computes)
         // (a run launch: the run's p.K frames only, at their positions in the image of the whole bank -- p.vt, p.knorm2, p.k and v
         // point at the run's first frame, so the runs of one bank fill disjoint parts of one workspace)
-        if (const int rc = launch_vt_pack<T>(p, v, DH, bank_only ? 1 : 0, src_only ? 1 : 3, st)) return rc;
+        // key norms: of every branch's own keys; under injection of the source's, by the first packed branch
+        const int b_lo = bank_only ? 1 : 0;
+        if (const int rc = launch_vt_pack<T>(p, v, DH, b_lo, src_only ? 1 : 3, p.inject ? 0u : ~0u, p.inject ? b_lo : -1, st))
+            return rc;
     }
     // Every head dim has three forms: ALL (one launch, bank problems then source problems), DUAL (injection:
     // uncond + cond share QK^T and the softmax; pays from S = 256 on) and SOURCE (the source branch alone).
@@ -2512,14 +2526,19 @@ struct EditsPart {
     int shift;      // branches in front of this edit's uncond branch, minus 1: 2 * edit
     int no_pack;    // the V^T pre-pass has been issued for all branches
     int mv4;        // this call computes TWO edits' bank branches in the four-bank form
+    int gap;        // ... whose uncond branches lie `gap` branches apart (2 = neighbouring edits)
     int force_dual; // the DUAL launch at any S
     int probe;      // do not launch: return 1 if the call takes the fused small-problem kernel, else 0
 
     // the parts of a batch of `branches` branches whose V^T image is packed: edit e's bank branches through the launches of
-    // its own bank-only call / the pair (e, e + 1) in the four-bank form / edit e in the DUAL launch at any S / the source
-    // branch / the probe of a part's fused-kernel decision
+    // its own bank-only call / the pair (e0, e1), e0 < e1, in the four-bank form / edit e in the DUAL launch at any S / the
+    // source branch / the probe of a part's fused-kernel decision
     static EditsPart bank(int branches, int e) { return make(branches, 2 * e, 0, 0, 0); }
-    static EditsPart pair_mv4(int branches, int e) { return make(branches, 2 * e, 1, 0, 0); }
+    static EditsPart pair_mv4(int branches, int e0, int e1) {
+        EditsPart p = make(branches, 2 * e0, 1, 0, 0);
+        p.gap = 2 * (e1 - e0);
+        return p;
+    }
     static EditsPart bank_dual(int branches, int e) { return make(branches, 2 * e, 0, 1, 0); }
     static EditsPart source(int branches) { return make(branches, 0, 0, 0, 0); }
     static EditsPart probe_of(int branches) { return make(branches, 0, 0, 0, 1); }
@@ -2528,6 +2547,7 @@ private:
     static EditsPart make(int branches, int shift, int mv4, int force_dual, int probe) {
         EditsPart p{};
         p.branches = branches, p.shift = shift, p.no_pack = 1, p.mv4 = mv4, p.force_dual = force_dual, p.probe = probe;
+        p.gap = 2;
         return p;
     }
 };
@@ -2613,7 +2633,8 @@ int attn_fwd_core(const void* q, const void* k, const void* v, void* out, int K,
     p.o_bs = strides[6];
     p.o_fs = strides[7];
     p.c = (float)((double)scale * 1.4426950408889634);
-    if (ed) p.no_pack = ed->no_pack, p.mv4 = ed->mv4, p.force_dual = ed->force_dual;
+    p.gap = 2;
+    if (ed) p.no_pack = ed->no_pack, p.mv4 = ed->mv4, p.force_dual = ed->force_dual, p.gap = ed->gap;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     return dtype == TF_BF16 ? dispatch_dh<BF16>(Dh, p, v, st) : dispatch_dh<F16>(Dh, p, v, st);
 }
@@ -2647,35 +2668,45 @@ static bool mv4_default(int K, int Kq, int S, int H) {
     return Kq == K && H == 8 && K >= 4 && K <= 8 && S >= 1024 && S <= 4096;
 }
 
-extern "C" int tf_ext_attn_fwd_edits(const void* q, const void* k, const void* v, void* out, int K, int Kq, int q_frame0,
-                                     int S, int H, int Dh, int64_t ld, const int64_t* strides, float scale, int flags,
-                                     int dtype, int n_edits, void* ws, size_t ws_bytes, void* stream) {
-    TF_ARG(n_edits >= 1 && n_edits <= TF_MAX_EDITS, TF_ERR_SHAPE, "tf_ext_attn_fwd_edits: n_edits=%d (1 .. %d)", n_edits,
-           TF_MAX_EDITS);
-    TF_ARG(q && k && v && out && ws && strides, TF_ERR_NULL, "tf_ext_attn_fwd_edits: null pointer");
-    TF_ARG(dtype == TF_BF16 || dtype == TF_F16, TF_ERR_DTYPE, "tf_ext_attn_fwd_edits: dtype %d (bf16/f16 only)", dtype);
+// The masked composition: bit e of inject_mask = edit e injects (its uncond and cond branches use the source's q and k).
+// tf_ext_attn_fwd_edits is the two uniform masks of it.
+static int attn_fwd_edits_masked(const char* name, const void* q, const void* k, const void* v, void* out, int K, int Kq,
+                                 int q_frame0, int S, int H, int Dh, int64_t ld, const int64_t* strides, float scale, int flags,
+                                 int dtype, int n_edits, unsigned inject_mask, void* ws, size_t ws_bytes, void* stream) {
+    TF_ARG(n_edits >= 1 && n_edits <= TF_MAX_EDITS, TF_ERR_SHAPE, "%s: n_edits=%d (1 .. %d)", name, n_edits, TF_MAX_EDITS);
+    TF_ARG(q && k && v && out && ws && strides, TF_ERR_NULL, "%s: null pointer", name);
+    TF_ARG(dtype == TF_BF16 || dtype == TF_F16, TF_ERR_DTYPE, "%s: dtype %d (bf16/f16 only)", name, dtype);
     TF_ARG(!(flags & (TF_ATTN_BANK_ONLY | TF_ATTN_SOURCE_ONLY)), TF_ERR_SHAPE,
-           "tf_ext_attn_fwd_edits: TF_ATTN_BANK_ONLY / TF_ATTN_SOURCE_ONLY have no multi-edit form");
+           "%s: TF_ATTN_BANK_ONLY / TF_ATTN_SOURCE_ONLY have no multi-edit form", name);
     TF_ARG((flags & (TF_ATTN_MULTI_V | TF_ATTN_NO_MULTI_V)) != (TF_ATTN_MULTI_V | TF_ATTN_NO_MULTI_V), TF_ERR_SHAPE,
-           "tf_ext_attn_fwd_edits: TF_ATTN_MULTI_V and TF_ATTN_NO_MULTI_V exclude each other");
+           "%s: TF_ATTN_MULTI_V and TF_ATTN_NO_MULTI_V exclude each other", name);
+    TF_ARG(!(flags & TF_ATTN_INJECT), TF_ERR_SHAPE, "%s: TF_ATTN_INJECT beside a mask (the mask is the injection state)", name);
+    const unsigned all = (1u << n_edits) - 1u;
+    TF_ARG(!(inject_mask & ~all), TF_ERR_SHAPE, "%s: inject_mask=0x%x has bits at or above n_edits=%d", name, inject_mask,
+           n_edits);
+    const int base = flags & ~(TF_ATTN_MULTI_V | TF_ATTN_NO_MULTI_V);
     if (n_edits == 1)   // today's layout: today's call (the hints of the four-bank form have nothing to select)
         return attn_fwd_core(q, k, v, out, K, Kq, q_frame0, S, H, Dh, ld, strides, scale,
-                             flags & ~(TF_ATTN_MULTI_V | TF_ATTN_NO_MULTI_V), dtype, ws, ws_bytes, stream, nullptr);
+                             base | (inject_mask ? TF_ATTN_INJECT : 0), dtype, ws, ws_bytes, stream, nullptr);
     const int B = 1 + 2 * n_edits;
-    const int base = flags & ~(TF_ATTN_MULTI_V | TF_ATTN_NO_MULTI_V);
-    const bool inj = (flags & TF_ATTN_INJECT) != 0;
+    int inj_e[TF_MAX_EDITS], non_e[TF_MAX_EDITS], n_inj = 0, n_non = 0;   // the injecting / the other edits, ascending
+    for (int e = 0; e < n_edits; ++e) ((inject_mask >> e) & 1u) ? inj_e[n_inj++] = e : non_e[n_non++] = e;
     const int64_t osz = (flags & TF_ATTN_OUT_F32) ? 4 : 2;
     auto at = [](const void* ptr, int64_t elems, int64_t esz) {
         return static_cast<const void*>(static_cast<const unsigned char*>(ptr) + elems * esz);
     };
-    // the four-bank form: injection, Dh = 40, fp32 score scaling, at least one pair of edits
-    const bool mv_ok = inj && Dh == 40 && !(flags & TF_ATTN_FOLD_SCALE) && n_edits >= 2;
+    // the four-bank form: Dh = 40, fp32 score scaling, at least one pair of INJECTING edits
+    const bool mv_ok = n_inj >= 2 && Dh == 40 && !(flags & TF_ATTN_FOLD_SCALE);
     const bool mv = mv_ok && !(flags & TF_ATTN_NO_MULTI_V) && ((flags & TF_ATTN_MULTI_V) || mv4_default(K, Kq, S, H));
     // the pair launches and the odd edit beside them are one-pass streaming launches
-    const int bank_flags = base | TF_ATTN_BANK_ONLY | (mv ? TF_ATTN_NO_SPLIT | TF_ATTN_NO_FUSED : 0);
-    const int src_flags = base | TF_ATTN_SOURCE_ONLY;
+    const int inj_flags = base | TF_ATTN_INJECT | TF_ATTN_BANK_ONLY | (mv ? TF_ATTN_NO_SPLIT | TF_ATTN_NO_FUSED : 0);
+    const int non_flags = base | TF_ATTN_BANK_ONLY;
+    // the source-only call sees TF_ATTN_INJECT iff every edit injects (its result does not depend on the flag: the source
+    // branch reads its own q and k either way; its split decision may)
+    const int src_flags = base | TF_ATTN_SOURCE_ONLY | (n_non == 0 ? TF_ATTN_INJECT : 0);
     auto call = [&](int e, int fl, const EditsPart& ed) {   // the part `fl` of edit e (e = 0 for the source branch)
         const int sh = 2 * e;
+        const bool inj = (fl & TF_ATTN_INJECT) != 0;
         return attn_fwd_core(inj ? q : at(q, sh * strides[0], 2), inj ? k : at(k, sh * strides[2], 2), at(v, sh * strides[4], 2),
                              const_cast<void*>(at(out, sh * strides[6], osz)), K, Kq, q_frame0, S, H, Dh, ld, strides, scale, fl,
                              dtype, ws, ws_bytes, stream, &ed);
@@ -2684,28 +2715,63 @@ extern "C" int tf_ext_attn_fwd_edits(const void* q, const void* k, const void* v
     const EditsPart probe = EditsPart::probe_of(B);
     const int src_fused = call(0, src_flags, probe);
     if (src_fused < 0) return src_fused;
-    const int bank_fused = call(0, bank_flags, probe);
-    if (bank_fused < 0) return bank_fused;
-    const int b_lo = src_fused ? 1 : 0, b_hi = bank_fused ? 1 : B;
-    if (b_lo < b_hi) {   // ONE pre-pass for all of them
+    const int inj_fused = n_inj ? call(0, inj_flags, probe) : 1;
+    if (inj_fused < 0) return inj_fused;
+    const int non_fused = n_non ? call(0, non_flags, probe) : 1;
+    if (non_fused < 0) return non_fused;
+    // ONE pre-pass over the span of the streaming branches; key norms of every packed branch whose OWN keys a launch reads
+    // (the source, the edits that do not inject); where an injecting edit streams beside a fused source part, the workgroups
+    // of the first injecting branch compute the source's norms, as in the single-edit call under injection
+    int b_lo = B, b_hi = 0;
+    unsigned own = 0;
+    auto span = [&](int lo, int hi) { b_lo = lo < b_lo ? lo : b_lo, b_hi = hi > b_hi ? hi : b_hi; };
+    if (!src_fused) span(0, 1), own |= 1u;
+    if (!inj_fused)
+        for (int i = 0; i < n_inj; ++i) span(1 + 2 * inj_e[i], 3 + 2 * inj_e[i]);
+    if (!non_fused)
+        for (int i = 0; i < n_non; ++i) span(1 + 2 * non_e[i], 3 + 2 * non_e[i]), own |= 3u << (1 + 2 * non_e[i]);
+    if (b_lo < b_hi) {
         const int Spad = ((S + 127) / 128) * 128;
         AttnParams p{};
         p.k = k, p.vt = ws;
         p.knorm2 = reinterpret_cast<const float*>(static_cast<unsigned char*>(ws) + ((vt_bytes(K, Spad, H, Dh, B) + 255) & ~(size_t)255));
-        p.K = p.Kb = K, p.S = S, p.H = H, p.Spad = Spad, p.inject = inj ? 1 : 0, p.nseg = 1;
+        p.K = p.Kb = K, p.S = S, p.H = H, p.Spad = Spad, p.nseg = 1;
         p.ld = ld, p.k_bs = strides[2], p.k_fs = strides[3], p.v_bs = strides[4], p.v_fs = strides[5];
+        const int b_src = (!inj_fused && src_fused) ? 1 + 2 * inj_e[0] : -1;
         hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-        const int rc = dtype == TF_BF16 ? launch_vt_pack<BF16>(p, v, Dh, b_lo, b_hi, st) : launch_vt_pack<F16>(p, v, Dh, b_lo, b_hi, st);
+        const int rc = dtype == TF_BF16 ? launch_vt_pack<BF16>(p, v, Dh, b_lo, b_hi, own, b_src, st)
+                                        : launch_vt_pack<F16>(p, v, Dh, b_lo, b_hi, own, b_src, st);
         if (rc) return rc;
     }
-    // bank branches first (the long problems), then the source branch, as the single-edit call orders them
-    int e = 0;
+    // bank branches first (the long problems), then the source branch, as the single-edit call orders them: the injecting
+    // edits (pairs in the four-bank form, an odd last one in the DUAL launch beside them), then the others
+    int i = 0;
     if (mv)
-        for (; e + 2 <= n_edits; e += 2)
-            if (const int rc = call(e, bank_flags, EditsPart::pair_mv4(B, e))) return rc;
-    for (; e < n_edits; ++e)
-        if (const int rc = call(e, bank_flags, mv ? EditsPart::bank_dual(B, e) : EditsPart::bank(B, e))) return rc;
+        for (; i + 2 <= n_inj; i += 2)
+            if (const int rc = call(inj_e[i], inj_flags, EditsPart::pair_mv4(B, inj_e[i], inj_e[i + 1]))) return rc;
+    for (; i < n_inj; ++i)
+        if (const int rc = call(inj_e[i], inj_flags, mv ? EditsPart::bank_dual(B, inj_e[i]) : EditsPart::bank(B, inj_e[i])))
+            return rc;
+    for (i = 0; i < n_non; ++i)
+        if (const int rc = call(non_e[i], non_flags, EditsPart::bank(B, non_e[i]))) return rc;
     return call(0, src_flags, EditsPart::source(B));
+}
+
+extern "C" int tf_ext_attn_fwd_edits(const void* q, const void* k, const void* v, void* out, int K, int Kq, int q_frame0,
+                                     int S, int H, int Dh, int64_t ld, const int64_t* strides, float scale, int flags,
+                                     int dtype, int n_edits, void* ws, size_t ws_bytes, void* stream) {
+    const unsigned all = (n_edits >= 1 && n_edits <= TF_MAX_EDITS) ? (1u << n_edits) - 1u : 0u;
+    return attn_fwd_edits_masked("tf_ext_attn_fwd_edits", q, k, v, out, K, Kq, q_frame0, S, H, Dh, ld, strides, scale,
+                                 flags & ~TF_ATTN_INJECT, dtype, n_edits, (flags & TF_ATTN_INJECT) ? all : 0u, ws, ws_bytes,
+                                 stream);
+}
+
+extern "C" int tf_ext_attn_fwd_edits_masked(const void* q, const void* k, const void* v, void* out, int K, int Kq,
+                                            int q_frame0, int S, int H, int Dh, int64_t ld, const int64_t* strides,
+                                            float scale, int flags, int dtype, int n_edits, unsigned inject_mask, void* ws,
+                                            size_t ws_bytes, void* stream) {
+    return attn_fwd_edits_masked("tf_ext_attn_fwd_edits_masked", q, k, v, out, K, Kq, q_frame0, S, H, Dh, ld, strides, scale,
+                                 flags, dtype, n_edits, inject_mask, ws, ws_bytes, stream);
 }
 
 // Launch plan of tf_ext_attn_fwd_edits for dense tensors, recorded by the entry point itself as tf_ext_attn_plan does.
@@ -2724,6 +2790,25 @@ extern "C" int tf_ext_attn_edits_plan(int K, int Kq, int S, int H, int Dh, int n
     tf_plan_rec = nullptr;
     if (rc) return rc;
     TF_ARG(rec.used < len, TF_ERR_WORKSPACE, "tf_ext_attn_edits_plan: the plan needs %zu bytes", rec.used + 1);
+    return rec.n;
+}
+
+// The same for tf_ext_attn_fwd_edits_masked.
+extern "C" int tf_ext_attn_edits_masked_plan(int K, int Kq, int S, int H, int Dh, int n_edits, unsigned inject_mask, int flags,
+                                             int dtype, char* buf, size_t len) {
+    TF_ARG(K > 0 && S > 0 && H > 0 && Kq > 0 && Kq <= K, TF_ERR_SHAPE, "tf_ext_attn_edits_masked_plan: K=%d Kq=%d S=%d H=%d", K,
+           Kq, S, H);
+    void* const ph = reinterpret_cast<void*>((uintptr_t)1 << 12);
+    const int64_t ld = (int64_t)H * Dh, fs = (int64_t)S * ld;
+    const int64_t strides[9] = {Kq * fs, fs, K * fs, fs, K * fs, fs, Kq * fs, fs, ld};
+    TfPlanRec rec{buf, len, 0, 0};
+    if (buf && len) buf[0] = 0;
+    tf_plan_rec = &rec;
+    const int rc = tf_ext_attn_fwd_edits_masked(ph, ph, ph, ph, K, Kq, 0, S, H, Dh, ld, strides, 1.0f, flags, dtype, n_edits,
+                                                inject_mask, ph, (size_t)-1, nullptr);
+    tf_plan_rec = nullptr;
+    if (rc) return rc;
+    TF_ARG(rec.used < len, TF_ERR_WORKSPACE, "tf_ext_attn_edits_masked_plan: the plan needs %zu bytes", rec.used + 1);
     return rec.n;
 }
 

@@ -288,12 +288,16 @@ __global__ __launch_bounds__(256) void inject_copy_kernel(u32x4* __restrict__ x,
     }
 }
 
-// multi-edit batch: x[b] = x[0] for every branch b >= 1 of [source | uncond_1 | cond_1 | ... ]
-__global__ __launch_bounds__(256) void inject_copy_edits_kernel(u32x4* __restrict__ x, int64_t pieces_per_branch, int nb) {
+// multi-edit batch: x[b] = x[0] for every branch b >= 1 of [source | uncond_1 | cond_1 | ... ]; MASKED: only for the branches
+// whose bit is set in `branch_mask` (the edits that inject at this step), the others are neither read nor written
+template <bool MASKED>
+__global__ __launch_bounds__(256) void inject_copy_edits_kernel(u32x4* __restrict__ x, int64_t pieces_per_branch, int nb,
+                                                                unsigned branch_mask) {
     for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < pieces_per_branch;
          g += (int64_t)gridDim.x * 256) {
         const u32x4 v = x[g];
-        for (int b = 1; b < nb; ++b) x[b * pieces_per_branch + g] = v;
+        for (int b = 1; b < nb; ++b)
+            if (!MASKED || ((branch_mask >> b) & 1u)) x[b * pieces_per_branch + g] = v;
     }
 }
 
@@ -671,18 +675,38 @@ extern "C" int tf_inject_copy(void* x, int64_t elems_per_branch, int elem_bytes,
     return 0;
 }
 
-extern "C" int tf_inject_copy_edits(void* x, int64_t elems_per_branch, int n_branches, int elem_bytes, void* stream) {
-    TF_ARG(x, TF_ERR_NULL, "tf_inject_copy_edits: null pointer");
+// edit_mask: bit e = edit e's uncond and cond branches take the source; `masked` = false is the unmasked launch
+static int inject_copy_edits_impl(const char* name, void* x, int64_t elems_per_branch, int n_branches, bool masked,
+                                  unsigned edit_mask, int elem_bytes, void* stream) {
+    TF_ARG(x, TF_ERR_NULL, "%s: null pointer", name);
     TF_ARG(elems_per_branch > 0 && elem_bytes > 0 && (elems_per_branch * elem_bytes) % 16 == 0 && n_branches >= 3 &&
                n_branches <= 1 + 2 * TF_MAX_EDITS && (n_branches & 1),
-           TF_ERR_SHAPE, "tf_inject_copy_edits: elems_per_branch=%lld elem_bytes=%d n_branches=%d (bytes per branch %% 16 == 0; "
-           "1 + 2E branches, E <= %d)", (long long)elems_per_branch, elem_bytes, n_branches, TF_MAX_EDITS);
-    TF_ARG(tf_aligned16(x), TF_ERR_ALIGN, "tf_inject_copy_edits: x not 16-byte aligned");
+           TF_ERR_SHAPE, "%s: elems_per_branch=%lld elem_bytes=%d n_branches=%d (bytes per branch %% 16 == 0; "
+           "1 + 2E branches, E <= %d)", name, (long long)elems_per_branch, elem_bytes, n_branches, TF_MAX_EDITS);
+    TF_ARG(tf_aligned16(x), TF_ERR_ALIGN, "%s: x not 16-byte aligned", name);
+    const int n_edits = (n_branches - 1) / 2;
+    TF_ARG(!masked || !(edit_mask >> n_edits), TF_ERR_SHAPE, "%s: edit_mask=0x%x has bits at or above the %d edits", name,
+           edit_mask, n_edits);
+    if (masked && edit_mask == 0) return 0;   // nobody injects: nothing to launch
+    unsigned branch_mask = 0;
+    for (int e = 0; e < n_edits; ++e)
+        if ((edit_mask >> e) & 1u) branch_mask |= 3u << (1 + 2 * e);
     const int64_t pieces = elems_per_branch * elem_bytes / 16;
     int64_t blocks = (pieces + 255) / 256;
     if (blocks > 256 * 8) blocks = 256 * 8;
-    hipLaunchKernelGGL(inject_copy_edits_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                       reinterpret_cast<u32x4*>(x), pieces, n_branches);
-    TF_LAUNCH_CHECK("tf_inject_copy_edits");
+    hipLaunchKernelGGL(masked ? inject_copy_edits_kernel<true> : inject_copy_edits_kernel<false>, dim3((unsigned)blocks),
+                       dim3(256), 0, reinterpret_cast<hipStream_t>(stream), reinterpret_cast<u32x4*>(x), pieces, n_branches,
+                       branch_mask);
+    TF_LAUNCH_CHECK(name);
     return 0;
+}
+
+extern "C" int tf_inject_copy_edits(void* x, int64_t elems_per_branch, int n_branches, int elem_bytes, void* stream) {
+    return inject_copy_edits_impl("tf_inject_copy_edits", x, elems_per_branch, n_branches, false, 0u, elem_bytes, stream);
+}
+
+extern "C" int tf_inject_copy_edits_masked(void* x, int64_t elems_per_branch, int n_branches, unsigned edit_mask,
+                                           int elem_bytes, void* stream) {
+    return inject_copy_edits_impl("tf_inject_copy_edits_masked", x, elems_per_branch, n_branches, true, edit_mask, elem_bytes,
+                                  stream);
 }

@@ -227,6 +227,62 @@ def _injecting(module) -> bool:
 def _set_schedule(module, injection_schedule):
     setattr(module, "injection_schedule", injection_schedule)
     module.__dict__["_tf_schedule_set"] = _schedule_set(injection_schedule)
+    module.__dict__.pop("_tf_edit_schedule_sets", None)      # an installer starts from the one shared schedule
+
+
+def _inject_mask(module, n_edits: int) -> int:
+    """The edits that inject at the module's `t`, bit e = edit e: with per-edit schedules (register_edit_schedules) each edit's
+    own `t in schedule or t == 1000`; without them the one shared state `_injecting(module)` for every edit."""
+    sets = module.__dict__.get("_tf_edit_schedule_sets")
+    if sets is None:
+        return (1 << n_edits) - 1 if _injecting(module) else 0
+    if len(sets) != n_edits:
+        raise ValueError(f"register_edit_schedules: {len(sets)} schedules on a module that sees {n_edits} edits "
+                         "(call it after register_edits)")
+    t = module.t
+    if isinstance(t, torch.Tensor):
+        t = t.item()
+    return sum(1 << e for e, sched in enumerate(sets) if sched is not None and (t in sched or t == 1000))
+
+
+def register_edit_schedules(model, qk_schedules=None, conv_schedules=None):
+    """Multi-edit extension: the edits of one pass may differ in their injection thresholds (PnP's pnp_attn_t / pnp_f_t, the
+    driver's qk_injection_timesteps / conv_injection_timesteps).  Each argument is a list of n_edits injection schedules in
+    the form the installers take (tensor or sequence of timesteps); `[]` or None inside the list = that edit never injects.
+    Call it after register_extended_attention_pnp, register_conv_injection and register_edits.
+      qk_schedules   -> `attn1` of the 8 decoder blocks that inject (the other blocks keep their empty schedule);
+      conv_schedules -> up_blocks[1].resnets[1].
+    At a call the hook computes the mask of the edits that inject at `t` (per edit: `t in schedule or t == 1000`, sets
+    converted once, no host sync): no edit -> today's call without injection, every edit -> today's call with it, anything
+    else -> the same op with `inject_mask=` / `edit_mask=`.  For every op the slices of edit e are what the single-edit op
+    computes on [source | uncond_e | cond_e] with edit e's own schedule.  None for an argument removes that kind's per-edit
+    schedules (the installer's shared schedule holds again); re-running an installer removes them on the modules it touches;
+    the SDEdit installer (register_extended_attention) never injects and ignores them."""
+    unet = model.unet
+
+    def sets_for(what, schedules, module):
+        if schedules is None:
+            return None
+        schedules = list(schedules)
+        E = int(getattr(module, "n_edits", 1))
+        if len(schedules) != E:
+            raise ValueError(f"register_edit_schedules: {len(schedules)} {what} schedules for n_edits={E}")
+        sets = [_schedule_set(sch) for sch in schedules]
+        return [sch if sch else None for sch in sets]
+
+    def put(module, sets):
+        if sets is None:
+            module.__dict__.pop("_tf_edit_schedule_sets", None)
+        else:
+            module.__dict__["_tf_edit_schedule_sets"] = sets
+
+    attns = [unet.up_blocks[res].attentions[b].transformer_blocks[0].attn1 for res, blocks in _INJECTED_UP.items() for b in blocks]
+    conv_module = unet.up_blocks[1].resnets[1]
+    qk_sets = [sets_for("qk", qk_schedules, m) for m in attns]       # validate everything before anything is set
+    conv_sets = sets_for("conv", conv_schedules, conv_module)
+    for m, sets in zip(attns, qk_sets):
+        put(m, sets)
+    put(conv_module, conv_sets)
 
 
 # --------------------------------------------------------------------------- PnP feature injection
@@ -241,14 +297,18 @@ def register_conv_injection(model, injection_schedule):
     conv_module = model.unet.up_blocks[1].resnets[1]
 
     def after_conv2(_conv2, _inputs, hidden_states):
-        if _injecting(conv_module):
+        E = int(getattr(conv_module, "n_edits", 1))
+        mask = _inject_mask(conv_module, E)
+        if mask:
             if not hidden_states.is_contiguous():
                 hidden_states = hidden_states.contiguous()
             E = _n_edits(conv_module)
             if E == 1:
                 ops.inject_copy_(hidden_states)
-            else:       # every edit's uncond and cond branch takes the source branch's activations
+            elif mask == (1 << E) - 1:   # every edit's uncond and cond branch takes the source branch's activations
                 ops.inject_copy_edits_(hidden_states, E)
+            else:                        # per-edit schedules that disagree at this step: only the edits that inject
+                ops.inject_copy_edits_(hidden_states, E, edit_mask=mask)
         return hidden_states
 
     prev = conv_module.__dict__.pop("_tf_conv_hook", None)
@@ -351,17 +411,21 @@ def _make_sa_forward(self, pnp: bool):
             cdt = ops.compute_dtype(q)
             if proj_dtype != cdt:
                 q, k, v = q.to(cdt), k.to(cdt), v.to(cdt)
-        inject = pnp and _injecting(self)
         shard = None if is_cross else _active_shard(self)
         E = 1 if is_cross else _n_edits(self)
+        # the edits that inject (one shared schedule: all or none; register_edit_schedules: each edit's own)
+        mask = _inject_mask(self, E) if pnp else 0
+        inject = mask != 0
         if shard is not None:     # q, k, v are this rank's keyframes; the bank is everybody's (register_frame_shard)
             if E > 1:
                 raise ValueError("register_edits: a multi-edit batch (n_edits > 1) on a registered frame shard is not supported")
             out = shard.pivotal_attention(q, k, v, self.heads, self.scale, inject)
         elif E == 1:
             out = ops.ext_attn(q, k, v, self.heads, self.scale, inject)
-        else:                     # [source | uncond_1 | cond_1 | ...]: the source branch and (injecting) the scores once
+        elif mask in (0, (1 << E) - 1):   # [source | uncond_1 | cond_1 | ...]: the source branch and (injecting) the scores once
             out = ops.ext_attn_edits(q, k, v, self.heads, self.scale, inject, E)
+        else:                     # per-edit schedules that disagree at this step
+            out = ops.ext_attn_edits(q, k, v, self.heads, self.scale, False, E, inject_mask=mask)
         return to_out(out if out.dtype == proj_dtype else out.to(proj_dtype))
 
     return forward

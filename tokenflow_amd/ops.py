@@ -151,13 +151,30 @@ def _multi_v_bits(multi_v: Optional[bool]) -> int:
     return 0 if multi_v is None else _lib.TF_ATTN_MULTI_V if multi_v else _lib.TF_ATTN_NO_MULTI_V
 
 
+def _edit_mask(what: str, mask, n_edits: int, inject: bool = False) -> int:
+    """A per-edit mask (bit e = edit e, 0-based) checked against the number of edits; it excludes the shared `inject`."""
+    E, m = int(n_edits), int(mask)
+    if not 1 <= E <= _lib.TF_MAX_EDITS:
+        raise ValueError(f"{what}: n_edits={n_edits} (1 .. {_lib.TF_MAX_EDITS})")
+    if inject:
+        raise ValueError(f"{what}: inject=True beside a mask (the mask is the injection state)")
+    if m < 0 or m >> E:
+        raise ValueError(f"{what}: mask {m:#x} has bits outside the {E} edits")
+    return m
+
+
 def attn_edits_plan(K: int, Kq: int, S: int, heads: int, dh: int, inject: bool, n_edits: int,
                     dtype: torch.dtype = torch.bfloat16, out_dtype: Optional[torch.dtype] = None,
                     fold_scale: Optional[bool] = None, no_split: Optional[bool] = None, fused: Optional[bool] = None,
-                    multi_v: Optional[bool] = None, hints: int = 0) -> list:
+                    multi_v: Optional[bool] = None, hints: int = 0, inject_mask: Optional[int] = None) -> list:
     """The launches `ext_attn_edits` makes for dense [(1+2E)K,S,heads*dh] tensors, as tokens (tf_ext_attn_edits_plan: the
-    tokens of `attn_plan`; the four-bank launch of a pair of edits is 'one<40,1,4,MV4,2,fq0>').  Host only: needs no GPU."""
+    tokens of `attn_plan`; the four-bank launch of a pair of edits is 'one<40,1,4,MV4,2,fq0>').  Host only: needs no GPU.
+    inject_mask: the per-edit injection state of `ext_attn_edits` (tf_ext_attn_edits_masked_plan); `inject` must be False."""
     flags = _attn_flags(inject, "all", out_dtype == torch.float32, fold_scale, no_split, fused, hints) | _multi_v_bits(multi_v)
+    if inject_mask is not None:
+        mask = _edit_mask("attn_edits_plan", inject_mask, n_edits, inject)
+        return _plan_tokens("tf_ext_attn_edits_masked_plan", _lib.load().tf_ext_attn_edits_masked_plan, K, Kq, S, heads, dh,
+                            int(n_edits), mask, flags, _DT[dtype])
     return _plan_tokens("tf_ext_attn_edits_plan", _lib.load().tf_ext_attn_edits_plan, K, Kq, S, heads, dh, int(n_edits), flags,
                         _DT[dtype])
 
@@ -235,17 +252,21 @@ def ext_attn_edits(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int
                    n_edits: int, out: Optional[torch.Tensor] = None, q_frame0: int = 0,
                    fold_scale: Optional[bool] = None, out_dtype: Optional[torch.dtype] = None,
                    no_split: Optional[bool] = None, fused: Optional[bool] = None, multi_v: Optional[bool] = None,
-                   hints: int = 0) -> torch.Tensor:
+                   hints: int = 0, inject_mask: Optional[int] = None) -> torch.Tensor:
     """`ext_attn` for a multi-edit batch: E = n_edits edits of one source video, B = 1 + 2E branches
     [source | uncond_1 | cond_1 | ... | uncond_E | cond_E].  k, v: [B*K,S,D], q: [B*Kq,S,D]; returns [B*Kq,S,D].
     The slices of edit e (source, uncond_e, cond_e) are what `ext_attn` computes on [source | uncond_e | cond_e]: the
     bank branches equal `ext_attn_views(part="bank")` on that edit's slabs and the source branch `part="source"` bit for
     bit -- except where pairs of edits take the four-bank shared-softmax launch under injection (head dim 40), which is
     held to the oracle within the attention bound.  multi_v: True / False force that form on / off (TF_ATTN_MULTI_V /
-    TF_ATTN_NO_MULTI_V), None = the library's measured default.  n_edits = 1 is `ext_attn`.  Other arguments as `ext_attn`."""
+    TF_ATTN_NO_MULTI_V), None = the library's measured default.  n_edits = 1 is `ext_attn`.  Other arguments as `ext_attn`.
+    inject_mask: the injection state PER EDIT (tf_ext_attn_fwd_edits_masked): bit e set = edit e (0-based) uses the source's
+    q and k, clear = its own; `inject` must then be False.  Every edit keeps the identity above with its own flag; the
+    four-bank form pairs the injecting edits, neighbours or not.  None = the one shared state `inject`, today's call."""
     dev = _need_gpu(q, k, v, out)
     lib = _lib.load()
     E = int(n_edits)
+    mask = None if inject_mask is None else _edit_mask("ext_attn_edits", inject_mask, n_edits, inject)
     if not 1 <= E <= _lib.TF_MAX_EDITS:
         raise ValueError(f"ext_attn_edits: n_edits={n_edits} (1 .. {_lib.TF_MAX_EDITS})")
     nbr = 1 + 2 * E
@@ -281,6 +302,11 @@ def ext_attn_edits(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int
     ws = _workspace(nbytes, q.device)
     fs = S * ld
     strides = (ctypes.c_int64 * 9)(Kq * fs, fs, K * fs, fs, K * fs, fs, Kq * S * D, S * D, ld)
+    if mask is not None:
+        _launch(dev, "tf_ext_attn_fwd_edits_masked", lib.tf_ext_attn_fwd_edits_masked, q.data_ptr(), k.data_ptr(),
+                v.data_ptr(), out.data_ptr(), K, Kq, int(q_frame0), S, heads, dh, ld, ctypes.cast(strides, ctypes.c_void_p),
+                float(scale), flags, dt, E, mask, ws.data_ptr(), ws.numel())
+        return out
     _launch(dev, "tf_ext_attn_fwd_edits", lib.tf_ext_attn_fwd_edits, q.data_ptr(), k.data_ptr(), v.data_ptr(),
             out.data_ptr(), K, Kq, int(q_frame0), S, heads, dh, ld, ctypes.cast(strides, ctypes.c_void_p), float(scale),
             flags, dt, E, ws.data_ptr(), ws.numel())
@@ -751,15 +777,21 @@ def propagate_chunks_edits(tgt: torch.Tensor, piv: torch.Tensor, inv_norm: torch
     return out
 
 
-def inject_copy_edits_(x: torch.Tensor, n_edits: int) -> torch.Tensor:
+def inject_copy_edits_(x: torch.Tensor, n_edits: int, edit_mask: Optional[int] = None) -> torch.Tensor:
     """In place, multi-edit batch of B = 1 + 2*n_edits branches: x[b*n:(b+1)*n] = x[:n] for every b >= 1, n = len(x)//B
-    (tokenflow_utils.py:87-91 for every edit).  n_edits = 1 is `inject_copy_`."""
+    (tokenflow_utils.py:87-91 for every edit).  n_edits = 1 is `inject_copy_`.
+    edit_mask: only the uncond and cond branches of the edits whose bit is set take the source (tf_inject_copy_edits_masked:
+    one launch, the other branches untouched; 0 launches nothing); None = every edit, today's call."""
     dev = _need_gpu(x)
     lib = _lib.load()
     nbr = 1 + 2 * int(n_edits)
     if not 1 <= int(n_edits) <= _lib.TF_MAX_EDITS or x.shape[0] % nbr or not x.is_contiguous():
         raise ValueError(f"inject_copy_edits_: need a contiguous tensor whose batch is a multiple of {nbr} "
                          f"(n_edits 1 .. {_lib.TF_MAX_EDITS})")
+    if edit_mask is not None:
+        _launch(dev, "tf_inject_copy_edits_masked", lib.tf_inject_copy_edits_masked, x.data_ptr(), x.numel() // nbr, nbr,
+                _edit_mask("inject_copy_edits_", edit_mask, n_edits), x.element_size())
+        return x
     _launch(dev, "tf_inject_copy_edits", lib.tf_inject_copy_edits, x.data_ptr(), x.numel() // nbr, nbr, x.element_size())
     return x
 

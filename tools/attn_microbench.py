@@ -4,7 +4,12 @@ build so that kernel variants can be A/B-ed:  TOKENFLOW_HIP_LIB=<.so> python too
 Prints avg/min ms over `reps` launches (HIP events on the launch stream) and TFLOP/s (algorithmic).
 --edits E: a multi-edit batch of E edits under q/k injection, alternating A/B of three arms per shape -- (a) E full
 single-edit `ext_attn` calls (one per prompt), (b) `ext_attn_edits`, the composition, (c) `ext_attn_edits` with the
-four-bank form on -- median / min over --rounds rounds, plus the spread of arm (b) against itself."""
+four-bank form on -- median / min over --rounds rounds, plus the spread of arm (b) against itself.
+--edits E --inject-mask M: the edits differ in their injection state (bit e of M = edit e injects) -- (a) E single-edit
+`ext_attn` calls, each with its own flag, (b) ONE masked call `ext_attn_edits(..., inject_mask=M)` with the library's
+default rule, (b') the same again (the spread), (c) the masked call as a pure composition (multi_v=False).
+--single-lib PATH takes arm (a) from another build of the library (tf_ext_attn_fwd of that .so, e.g. the parent commit's)."""
+import ctypes
 import os
 import sys
 
@@ -49,10 +54,69 @@ def flag(name, default):
     """--name VALUE out of sys.argv (removed from it)."""
     if name in sys.argv:
         i = sys.argv.index(name)
-        val = int(sys.argv[i + 1])
+        val = int(sys.argv[i + 1], 0)      # 5, 0b101, 0x5
         del sys.argv[i:i + 2]
         return val
     return default
+
+
+def foreign_single_edit(path):
+    """`ext_attn` (dense tensors, fresh output) through tf_ext_attn_fwd of ANOTHER build of the library."""
+    from tokenflow_amd import _lib
+    lib = ctypes.CDLL(path)
+    for name in ("tf_ext_attn_fwd", "tf_ext_attn_workspace_bytes"):
+        getattr(lib, name).restype, getattr(lib, name).argtypes = _lib._SIGNATURES[name]
+    ws = {}
+
+    def ext_attn(q, k, v, h, scale, inject, out):
+        K, S, D = k.shape[0] // 3, k.shape[1], k.shape[2]
+        dtc = _lib.TF_BF16 if q.dtype == torch.bfloat16 else _lib.TF_F16
+        key = (K, S, h, D // h, dtc)
+        if key not in ws:
+            ws[key] = torch.empty(lib.tf_ext_attn_workspace_bytes(*key), dtype=torch.uint8, device=q.device)
+        rc = lib.tf_ext_attn_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), K, K, 0, S, h, D // h, D,
+                                 float(scale), 1 if inject else 0, dtc, ws[key].data_ptr(), ws[key].numel(),
+                                 torch.cuda.current_stream().cuda_stream)
+        assert rc == 0, rc
+        return out
+    return lib.tf_abi_version(), ext_attn
+
+
+def edits_masked_ab(shapes, E, mask, dt, rounds, single_lib):
+    g = torch.Generator(device="cuda").manual_seed(0)
+    B = 1 + 2 * E
+    single, where = (lambda q1, k1, v1, h, sc, inj, out: ops.ext_attn(q1, k1, v1, h, sc, inj, out=out)), "this build"
+    if single_lib:
+        abi, single = foreign_single_edit(single_lib)
+        where = f"{single_lib} (ABI {abi})"
+    for K, S, h, d in shapes:
+        D = h * d
+        q, k, v = (torch.randn(B * K, S, D, generator=g, device="cuda").to(dt) for _ in range(3))
+        out = torch.empty_like(q)
+        singles = []
+        for e in range(E):      # what a user with differing schedules does without the mask: one full pass per edit
+            sel = [0, 1 + 2 * e, 2 + 2 * e]
+            singles.append(tuple(t.view(B, K, S, D)[sel].reshape(3 * K, S, D).contiguous() for t in (q, k, v)))
+        out1 = torch.empty_like(singles[0][0])
+
+        def a_single():
+            for e, (q1, k1, v1) in enumerate(singles):
+                single(q1, k1, v1, h, d ** -0.5, bool((mask >> e) & 1), out1)
+        # the foreign build against this one on the same inputs, before anything is timed
+        for e, (q1, k1, v1) in enumerate(singles):
+            inj = bool((mask >> e) & 1)
+            assert torch.equal(single(q1, k1, v1, h, d ** -0.5, inj, torch.empty_like(q1)), ops.ext_attn(q1, k1, v1, h, d ** -0.5, inj))
+
+        def masked(mv):
+            return lambda: ops.ext_attn_edits(q, k, v, h, d ** -0.5, False, E, out=out, multi_v=mv, inject_mask=mask)
+        arms = {"(a) E single-edit calls": a_single, "(b) one masked call": masked(None), "(b') masked call again": masked(None),
+                "(c) masked, composition": masked(False)}
+        print(f"ext_attn_edits {str(dt)[6:]} K={K} S={S} h={h} d={d} E={E} inject_mask={mask:#b}  ({rounds} alternating rounds; "
+              f"arm (a): {where})")
+        print(f"  plan (b): {ops.attn_edits_plan(K, K, S, h, d, False, E, dtype=dt, inject_mask=mask)}")
+        print(f"  plan (c): {ops.attn_edits_plan(K, K, S, h, d, False, E, dtype=dt, multi_v=False, inject_mask=mask)}")
+        for name, (med, mn, mx) in ab(arms, rounds).items():
+            print(f"  {name:26s} median {med:.3f} ms  min {mn:.3f} ms  max {mx:.3f} ms", flush=True)
 
 
 def edits_ab(shapes, E, dt, rounds):
@@ -86,11 +150,18 @@ def edits_ab(shapes, E, dt, rounds):
 
 def main():
     shapes = [(8, 4096, 8, 40), (8, 1024, 8, 80), (8, 256, 8, 160), (10, 9216, 5, 64)]
-    E, rounds = flag("--edits", 0), flag("--rounds", 15)
+    E, rounds, mask = flag("--edits", 0), flag("--rounds", 15), flag("--inject-mask", None)
+    single_lib = None
+    if "--single-lib" in sys.argv:
+        i = sys.argv.index("--single-lib")
+        single_lib = sys.argv[i + 1]
+        del sys.argv[i:i + 2]
     args = [a for a in sys.argv[1:] if a not in ("f16", "bf16")]
     dt = torch.float16 if "f16" in sys.argv[1:] else torch.bfloat16
     if args:
         shapes = [tuple(int(x) for x in a.split(",")) for a in args]
+    if E and mask is not None:
+        return edits_masked_ab(shapes, E, mask, dt, rounds, single_lib)
     if E:
         return edits_ab(shapes, E, dt, rounds)
     g = torch.Generator(device="cuda").manual_seed(0)
