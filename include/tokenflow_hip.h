@@ -248,6 +248,48 @@ TF_API int tf_ext_attn_edits_masked_plan(int K, int Kq, int S, int H, int Dh, in
                                   int dtype, char* buf, size_t len);
 
 /* ------------------------------------------------------------------------
+ * The PARTS of a multi-edit attention call (additive to ABI 11): what a frame-sharded rank needs -- the bank branches of every
+ * edit on the buffer its exchange delivered, the source branch of its own frames on its local tensors.
+ * tf_ext_attn_fwd_edits_part takes the arguments of tf_ext_attn_fwd_edits_masked plus qk_compact; tf_ext_attn_fwd_edits and
+ * tf_ext_attn_fwd_edits_masked themselves keep refusing the part bits.
+ *   flags: as tf_ext_attn_fwd_edits_masked, and
+ *     TF_ATTN_BANK_ONLY    the bank branches of every edit: steps 1-3 of the masked composition behind its single V^T
+ *                          pre-pass over the branches that stream.  Slab 0 (the source) of v and of out is never touched.
+ *     TF_ATTN_SOURCE_ONLY  step 4 alone (behind a pre-pass over the source branch where it streams).
+ *     neither              all parts.      Both: TF_ERR_SHAPE.
+ *     The four-bank form stays available in the bank part under its rule and hints.
+ *   Kq / q_frame0 as everywhere: a rank passes its own query frames against the bank of K.
+ *   qk_compact = 0: q and k are addressed densely, [source | uncond_1 | cond_1 | ...], as in the calls above.
+ *   qk_compact = 1: q and k hold only the branches some launch reads.  Branch slot 0 is the source; then two slots (uncond,
+ *     cond) per NON-injecting edit in ascending edit order: non-injecting edit number i of the mask (0-based) reads q and k
+ *     at slots 1 + 2i and 2 + 2i, every injecting edit reads slot 0.  v and out are never compacted.  A slot that nothing reads
+ *     (slot 0 of a bank part in which no edit injects; every slot but 0 of a source part) need not exist: the caller moves
+ *     the base pointer so that the slots that are read fall where they lie.  Other values: TF_ERR_SHAPE.
+ *   Workspace: tf_ext_attn_edits_workspace_bytes, unchanged.
+ *
+ * One fused launch: where EVERY part the call computes would take the fused small-problem kernel (each part's own decision,
+ * as in the calls above), all of them run in ONE launch of up to 1 + TF_MAX_EDITS tensor sets -- one per edit's bank branches
+ * (the injecting edits first, as the composition orders them) and the source set -- with the injection state per set.  In
+ * the plan this is the fused token with ",sets=N" appended for N > 2: fused[qw=1,kw=4,qb=1,prec=1,sets=4]; one or two sets
+ * record the plain token.  The arithmetic of a (query, head) in that kernel depends on KW and PREC only: under
+ * TF_ATTN_NO_SPLIT (KW = 4, PREC by shape) the one launch equals the launches of the parts bit for bit.  In the default mode
+ * the plan sees the joint grid and may choose another KW than a part alone would (or leave the fused kernel: the parts then
+ * run as in the masked call); results are then held to the attention bound, like any two launch plans.
+ *
+ * Identity: edit e's bank branches equal that edit's tf_ext_attn_fwd_strided(..., TF_ATTN_BANK_ONLY [| TF_ATTN_INJECT]) call
+ * and the source branch the TF_ATTN_SOURCE_ONLY call BIT FOR BIT, dense or compact; the exceptions are a pair in the
+ * four-bank form and the joint fused launch in the default mode (both within the attention bound of the oracle).
+ *
+ * tf_ext_attn_edits_part_plan: the launches of the call for dense tensors (host only).
+ * ------------------------------------------------------------------------ */
+TF_API int tf_ext_attn_fwd_edits_part(const void* q, const void* k, const void* v, void* out, int K, int Kq, int q_frame0,
+                               int S, int H, int Dh, int64_t ld, const int64_t* strides, float scale, int flags, int dtype,
+                               int n_edits, unsigned inject_mask, int qk_compact, void* ws, size_t ws_bytes, void* stream);
+
+TF_API int tf_ext_attn_edits_part_plan(int K, int Kq, int S, int H, int Dh, int n_edits, unsigned inject_mask, int qk_compact,
+                                int flags, int dtype, char* buf, size_t len);
+
+/* ------------------------------------------------------------------------
  * Extended attention over a bank that arrives in pieces: "run + merge" (ABI 9).
  *
  * The bank branches (uncond, cond) of Kq query frames are computed one RUN of bank frames [run_f0, run_f0 + run_n) at a
@@ -306,9 +348,11 @@ TF_API int tf_ext_attn_run_plan(int K, int Kq, int run_n, int n_runs, int S, int
 /* ------------------------------------------------------------------------
  * Frames <-> heads re-sharding of the multi-GPU pivotal pass (no counterpart in the single-process reference;
  * tokenflow_amd/sharded.py).  Rank r sends head group w of its Kl keyframes' slabs to rank w:
- *   tf_head_pack:    send[w][f][i][s][0..hd)  = slab_i[f][s][w*hd .. (w+1)*hd)     i < ns <= 6 slabs, each a
+ *   tf_head_pack:    send[w][f][i][s][0..hd)  = slab_i[f][s][w*hd .. (w+1)*hd)     i < ns slabs, each a
  *                    [Kl, S, ld] tensor with its own frame stride (elements); one launch for all slabs.
- *   tf_head_unpack:  dst_b[f][s][w*hd ..)     = recv[w][f][b][s][0..hd)            b < nb <= 6 destinations.
+ *   tf_head_unpack:  dst_b[f][s][w*hd ..)     = recv[w][f][b][s][0..hd)            b < nb destinations.
+ * ns, nb <= 6 * TF_MAX_EDITS (48): a multi-edit batch packs up to 6 slabs per edit -- q, k and v of its two branches where
+ * no edit injects -- and unpacks 2 per edit; a single edit's 6 keep the launch they always had.
  * elem_bytes 2 or 4; hd*elem_bytes and ld*elem_bytes multiples of 16.
  * ------------------------------------------------------------------------ */
 TF_API int tf_head_pack(const void* const* slabs, const int64_t* frame_strides, int ns, void* send, int W, int Kl, int S,

@@ -58,6 +58,12 @@ _SIGNATURES = {
                                                 _c.c_int, _c.c_int, _c.c_int, _c.c_uint, _c.c_void_p, _c.c_size_t,
                                                 _c.c_void_p]),
     "tf_ext_attn_edits_masked_plan": (_c.c_int, [_c.c_int] * 6 + [_c.c_uint, _c.c_int, _c.c_int, _c.c_char_p, _c.c_size_t]),
+    # the parts of a multi-edit call (a frame-sharded rank's bank part on its receive buffer, source part on its own tensors)
+    "tf_ext_attn_fwd_edits_part": (_c.c_int, [_c.c_void_p] * 4 + [_c.c_int] * 6 + [_c.c_int64, _c.c_void_p, _c.c_float,
+                                              _c.c_int, _c.c_int, _c.c_int, _c.c_uint, _c.c_int, _c.c_void_p, _c.c_size_t,
+                                              _c.c_void_p]),
+    "tf_ext_attn_edits_part_plan": (_c.c_int, [_c.c_int] * 6 + [_c.c_uint, _c.c_int, _c.c_int, _c.c_int, _c.c_char_p,
+                                               _c.c_size_t]),
     "tf_inject_copy_edits_masked": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int, _c.c_uint, _c.c_int, _c.c_void_p]),
     # attention over a bank that arrives in pieces: run + merge (ABI 9)
     "tf_ext_attn_runs_workspace_bytes": (_c.c_size_t, [_c.c_int] * 7),

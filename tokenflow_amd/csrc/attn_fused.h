@@ -4,7 +4,8 @@
 #include "tf_common.h"
 
 // One tensor set of a fused launch.  A launch carries one or two sets (a sharded rank: the bank branches on the
-// buffer its all-to-all delivered AND the source branch of its own frames on its local projections).
+// buffer its all-to-all delivered AND the source branch of its own frames on its local projections), or up to
+// 1 + TF_MAX_EDITS (the parts of a multi-edit batch: one set per edit's bank branches plus the source set).
 // Branch b of q / k / v / out lives at base + b * branch stride (the convention of tf_ext_attn_fwd_strided);
 // branch 0 is the source branch (a frame attends to its own S keys), branches 1 and 2 attend to all Kb frames.
 struct TfAttnSet {
@@ -20,6 +21,8 @@ struct TfAttnSet {
     int q_frame0;   // bank index of query frame 0 (the source branch of frame f reads keys of bank frame q_frame0 + f)
     int Kb;         // bank frames
     int b0, nb;     // branches [b0, b0 + nb)
+    int inject;     // this set's bank branches read the set's branch-0 q and k, as all sets do under TF_ATTN_INJECT of the
+                    // launch's flags (a multi-edit batch with a mixed injection mask sets it per edit)
 };
 
 struct TfFusedPlan {

@@ -161,7 +161,8 @@ template <typename T>
 __global__ __launch_bounds__(256) void vt_pack_kernel(const typename T::elem* __restrict__ v,
                                                       typename T::elem* __restrict__ vt,
                                                       const typename T::elem* __restrict__ k,
-                                                      float* __restrict__ knorm2, unsigned own, int b_src, int b0, int nf,
+                                                      float* __restrict__ knorm2, unsigned own, unsigned kc_mask, int b_src,
+                                                      int b0, int nf,
                                                       int K,
                                                       int S, int H, int DH, int Spad, int64_t ld, int64_t v_bs,
                                                       int64_t v_fs, int64_t k_bs, int64_t k_fs, int* __restrict__ run_hdr,
@@ -185,10 +186,13 @@ __global__ __launch_bounds__(256) void vt_pack_kernel(const typename T::elem* __
     const bool own_k = (own >> b) & 1u;
     if (k != nullptr && (own_k || b == b_src) && threadIdx.x < 64) {   // wave 0: one key per lane
         const int kb = own_k ? b : 0;
+        // compact q / k of a multi-edit part call (kc_mask = its injection mask, else 0): the keys of branch kb lie two slots
+        // further in for every injecting edit in front of its edit; the norms keep the dense index
+        const int ks = kb - 2 * __popc(kc_mask & ((1u << ((kb > 0 ? kb - 1 : 0) >> 1)) - 1u));
         const int kk = tt * 64 + (int)threadIdx.x;
         float acc = 0.f;
         if (kk < S) {
-            const E* kp = k + kb * k_bs + f * k_fs + (int64_t)kk * ld + h * DH;
+            const E* kp = k + ks * k_bs + f * k_fs + (int64_t)kk * ld + h * DH;
             for (int c8 = 0; c8 < DH; c8 += 8) {
                 const vec8 x = __builtin_bit_cast(vec8, ld16(kp + c8));
 #pragma unroll
@@ -2207,7 +2211,8 @@ int launch_one(AttnParams p, hipStream_t st) {
 
 // The V^T pre-pass over branches [b_lo, b_hi) of v (a multi-edit batch: once for all 1 + 2E branches)
 template <typename T>
-int launch_vt_pack(const AttnParams& p, const void* v, int DH, int b_lo, int b_hi, unsigned own, int b_src, hipStream_t st) {
+int launch_vt_pack(const AttnParams& p, const void* v, int DH, int b_lo, int b_hi, unsigned own, int b_src, hipStream_t st,
+                   unsigned kc_mask = 0) {
     typedef typename T::elem E;
     dim3 grid((unsigned)(p.Spad / 64), (unsigned)p.H, (unsigned)((b_hi - b_lo) * p.K));
     const size_t lds = (size_t)64 * (DH + 2) * sizeof(E);
@@ -2217,7 +2222,7 @@ int launch_vt_pack(const AttnParams& p, const void* v, int DH, int b_lo, int b_h
         hipLaunchKernelGGL(vt_pack_kernel<T>, grid, dim3(256), lds, st, reinterpret_cast<const E*>(v),
                            reinterpret_cast<E*>(const_cast<void*>(p.vt)),
                            bound ? reinterpret_cast<const E*>(p.k) : nullptr, const_cast<float*>(p.knorm2),
-                           own, b_src, b_lo, p.K, p.Kb, p.S, p.H, DH, p.Spad, p.ld, p.v_bs, p.v_fs, p.k_bs, p.k_fs,
+                           own, kc_mask, b_src, b_lo, p.K, p.Kb, p.S, p.H, DH, p.Spad, p.ld, p.v_bs, p.v_fs, p.k_bs, p.k_fs,
                            p.run_hdr, p.nseg);
         TF_LAUNCH_CHECK("tf_ext_attn_fwd(vt_pack)");
     }
@@ -2672,25 +2677,39 @@ static bool mv4_default(int K, int Kq, int S, int H) {
 // tf_ext_attn_fwd_edits is the two uniform masks of it.
 static int attn_fwd_edits_masked(const char* name, const void* q, const void* k, const void* v, void* out, int K, int Kq,
                                  int q_frame0, int S, int H, int Dh, int64_t ld, const int64_t* strides, float scale, int flags,
-                                 int dtype, int n_edits, unsigned inject_mask, void* ws, size_t ws_bytes, void* stream) {
+                                 int dtype, int n_edits, unsigned inject_mask, void* ws, size_t ws_bytes, void* stream,
+                                 bool part_call = false, int qk_compact = 0) {
     TF_ARG(n_edits >= 1 && n_edits <= TF_MAX_EDITS, TF_ERR_SHAPE, "%s: n_edits=%d (1 .. %d)", name, n_edits, TF_MAX_EDITS);
     TF_ARG(q && k && v && out && ws && strides, TF_ERR_NULL, "%s: null pointer", name);
     TF_ARG(dtype == TF_BF16 || dtype == TF_F16, TF_ERR_DTYPE, "%s: dtype %d (bf16/f16 only)", name, dtype);
-    TF_ARG(!(flags & (TF_ATTN_BANK_ONLY | TF_ATTN_SOURCE_ONLY)), TF_ERR_SHAPE,
-           "%s: TF_ATTN_BANK_ONLY / TF_ATTN_SOURCE_ONLY have no multi-edit form", name);
+    // tf_ext_attn_fwd_edits_part (part_call): the parts of this composition; one-pass fused parts share ONE launch there
+    const int part = flags & (TF_ATTN_BANK_ONLY | TF_ATTN_SOURCE_ONLY);
+    if (part_call) {
+        TF_ARG(part != (TF_ATTN_BANK_ONLY | TF_ATTN_SOURCE_ONLY), TF_ERR_SHAPE,
+               "%s: TF_ATTN_BANK_ONLY and TF_ATTN_SOURCE_ONLY exclude each other", name);
+        TF_ARG(qk_compact == 0 || qk_compact == 1, TF_ERR_SHAPE, "%s: qk_compact=%d (0 or 1)", name, qk_compact);
+    } else {
+        TF_ARG(!part, TF_ERR_SHAPE, "%s: TF_ATTN_BANK_ONLY / TF_ATTN_SOURCE_ONLY have no multi-edit form", name);
+    }
+    const bool do_bank = part != TF_ATTN_SOURCE_ONLY, do_src = part != TF_ATTN_BANK_ONLY;
     TF_ARG((flags & (TF_ATTN_MULTI_V | TF_ATTN_NO_MULTI_V)) != (TF_ATTN_MULTI_V | TF_ATTN_NO_MULTI_V), TF_ERR_SHAPE,
            "%s: TF_ATTN_MULTI_V and TF_ATTN_NO_MULTI_V exclude each other", name);
     TF_ARG(!(flags & TF_ATTN_INJECT), TF_ERR_SHAPE, "%s: TF_ATTN_INJECT beside a mask (the mask is the injection state)", name);
     const unsigned all = (1u << n_edits) - 1u;
     TF_ARG(!(inject_mask & ~all), TF_ERR_SHAPE, "%s: inject_mask=0x%x has bits at or above n_edits=%d", name, inject_mask,
            n_edits);
-    const int base = flags & ~(TF_ATTN_MULTI_V | TF_ATTN_NO_MULTI_V);
-    if (n_edits == 1)   // today's layout: today's call (the hints of the four-bank form have nothing to select)
+    const int base = flags & ~(TF_ATTN_MULTI_V | TF_ATTN_NO_MULTI_V | TF_ATTN_BANK_ONLY | TF_ATTN_SOURCE_ONLY);
+    if (n_edits == 1)   // today's layout: today's call (the hints of the four-bank form have nothing to select); the compact
+                        // q / k of one edit is the dense one as far as its launches read it
         return attn_fwd_core(q, k, v, out, K, Kq, q_frame0, S, H, Dh, ld, strides, scale,
-                             base | (inject_mask ? TF_ATTN_INJECT : 0), dtype, ws, ws_bytes, stream, nullptr);
+                             base | part | (inject_mask ? TF_ATTN_INJECT : 0), dtype, ws, ws_bytes, stream, nullptr);
     const int B = 1 + 2 * n_edits;
     int inj_e[TF_MAX_EDITS], non_e[TF_MAX_EDITS], n_inj = 0, n_non = 0;   // the injecting / the other edits, ascending
-    for (int e = 0; e < n_edits; ++e) ((inject_mask >> e) & 1u) ? inj_e[n_inj++] = e : non_e[n_non++] = e;
+    int qk_sh[TF_MAX_EDITS];   // q / k branch slots in front of edit e's uncond slot, minus 1 (an injecting edit reads slot 0)
+    for (int e = 0; e < n_edits; ++e) {
+        qk_sh[e] = qk_compact ? 2 * n_non : 2 * e;
+        ((inject_mask >> e) & 1u) ? inj_e[n_inj++] = e : non_e[n_non++] = e;
+    }
     const int64_t osz = (flags & TF_ATTN_OUT_F32) ? 4 : 2;
     auto at = [](const void* ptr, int64_t elems, int64_t esz) {
         return static_cast<const void*>(static_cast<const unsigned char*>(ptr) + elems * esz);
@@ -2707,25 +2726,55 @@ static int attn_fwd_edits_masked(const char* name, const void* q, const void* k,
     auto call = [&](int e, int fl, const EditsPart& ed) {   // the part `fl` of edit e (e = 0 for the source branch)
         const int sh = 2 * e;
         const bool inj = (fl & TF_ATTN_INJECT) != 0;
-        return attn_fwd_core(inj ? q : at(q, sh * strides[0], 2), inj ? k : at(k, sh * strides[2], 2), at(v, sh * strides[4], 2),
+        const int qsh = (fl & TF_ATTN_SOURCE_ONLY) ? 0 : qk_sh[e];
+        return attn_fwd_core(inj ? q : at(q, qsh * strides[0], 2), inj ? k : at(k, qsh * strides[2], 2), at(v, sh * strides[4], 2),
                              const_cast<void*>(at(out, sh * strides[6], osz)), K, Kq, q_frame0, S, H, Dh, ld, strides, scale, fl,
                              dtype, ws, ws_bytes, stream, &ed);
     };
     // which parts stream (and read the V^T image): the decision of the part's own call
     const EditsPart probe = EditsPart::probe_of(B);
-    const int src_fused = call(0, src_flags, probe);
+    const int src_fused = call(0, src_flags, probe);   // (a bank part decides its pre-pass as the whole call does)
     if (src_fused < 0) return src_fused;
-    const int inj_fused = n_inj ? call(0, inj_flags, probe) : 1;
+    const int inj_fused = n_inj && do_bank ? call(0, inj_flags, probe) : 1;
     if (inj_fused < 0) return inj_fused;
-    const int non_fused = n_non ? call(0, non_flags, probe) : 1;
+    const int non_fused = n_non && do_bank ? call(0, non_flags, probe) : 1;
     if (non_fused < 0) return non_fused;
+    if (part_call && (src_fused || !do_src) && inj_fused && non_fused) {
+        // every part this call computes takes the fused small-problem kernel: ONE launch over all of them, a set per edit's
+        // bank branches (the order of the streaming composition) and the source set; the injection state is the set's
+        TfAttnSet sets[1 + TF_MAX_EDITS] = {};
+        int n_sets = 0;
+        auto add = [&](int e, int b0, int nb, bool inj) {
+            TfAttnSet& a = sets[n_sets++];
+            const int sh = b0 ? 2 * e : 0, qsh = b0 && !inj ? qk_sh[e] : 0;
+            a.q = at(q, qsh * strides[0], 2), a.k = at(k, qsh * strides[2], 2), a.v = at(v, sh * strides[4], 2);
+            a.out = const_cast<void*>(at(out, sh * strides[6], osz));
+            a.q_bs = strides[0], a.q_fs = strides[1], a.ld_q = strides[8];
+            a.k_bs = strides[2], a.k_fs = strides[3], a.v_bs = strides[4], a.v_fs = strides[5], a.ld = ld;
+            a.o_bs = strides[6], a.o_fs = strides[7];
+            a.H = H, a.Kq = Kq, a.q_frame0 = q_frame0, a.Kb = K, a.b0 = b0, a.nb = nb, a.inject = inj ? 1 : 0;
+        };
+        if (do_bank) {
+            for (int i = 0; i < n_inj; ++i) add(inj_e[i], 1, 2, true);
+            for (int i = 0; i < n_non; ++i) add(non_e[i], 1, 2, false);
+        }
+        if (do_src) add(0, 0, 1, false);
+        const int fl = base;   // no launch-wide TF_ATTN_INJECT: every set carries its own
+        const TfFusedPlan plan = tf_attn_fused_plan(sets, n_sets, S, Dh, dtype, fl);
+        // (the default mode decides per grid: where the joint grid leaves the fused kernel's range, the parts run as below)
+        if (plan.use) {
+            TF_ARG(Kq > 0 && q_frame0 >= 0 && q_frame0 + Kq <= K && K > 0 && S > 0 && H > 0, TF_ERR_SHAPE,
+                   "%s: query frames [%d, %d) outside the %d-frame bank", name, q_frame0, q_frame0 + Kq, K);
+            return tf_attn_fused_launch(sets, n_sets, S, Dh, scale, fl, dtype, plan, reinterpret_cast<hipStream_t>(stream));
+        }
+    }
     // ONE pre-pass over the span of the streaming branches; key norms of every packed branch whose OWN keys a launch reads
     // (the source, the edits that do not inject); where an injecting edit streams beside a fused source part, the workgroups
     // of the first injecting branch compute the source's norms, as in the single-edit call under injection
     int b_lo = B, b_hi = 0;
     unsigned own = 0;
     auto span = [&](int lo, int hi) { b_lo = lo < b_lo ? lo : b_lo, b_hi = hi > b_hi ? hi : b_hi; };
-    if (!src_fused) span(0, 1), own |= 1u;
+    if (!src_fused && do_src) span(0, 1), own |= 1u;
     if (!inj_fused)
         for (int i = 0; i < n_inj; ++i) span(1 + 2 * inj_e[i], 3 + 2 * inj_e[i]);
     if (!non_fused)
@@ -2737,15 +2786,17 @@ static int attn_fwd_edits_masked(const char* name, const void* q, const void* k,
         p.knorm2 = reinterpret_cast<const float*>(static_cast<unsigned char*>(ws) + ((vt_bytes(K, Spad, H, Dh, B) + 255) & ~(size_t)255));
         p.K = p.Kb = K, p.S = S, p.H = H, p.Spad = Spad, p.nseg = 1;
         p.ld = ld, p.k_bs = strides[2], p.k_fs = strides[3], p.v_bs = strides[4], p.v_fs = strides[5];
-        const int b_src = (!inj_fused && src_fused) ? 1 + 2 * inj_e[0] : -1;
+        const int b_src = (!inj_fused && (src_fused || !do_src)) ? 1 + 2 * inj_e[0] : -1;
+        const unsigned kc_mask = qk_compact ? inject_mask : 0u;
         hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-        const int rc = dtype == TF_BF16 ? launch_vt_pack<BF16>(p, v, Dh, b_lo, b_hi, own, b_src, st)
-                                        : launch_vt_pack<F16>(p, v, Dh, b_lo, b_hi, own, b_src, st);
+        const int rc = dtype == TF_BF16 ? launch_vt_pack<BF16>(p, v, Dh, b_lo, b_hi, own, b_src, st, kc_mask)
+                                        : launch_vt_pack<F16>(p, v, Dh, b_lo, b_hi, own, b_src, st, kc_mask);
         if (rc) return rc;
     }
     // bank branches first (the long problems), then the source branch, as the single-edit call orders them: the injecting
     // edits (pairs in the four-bank form, an odd last one in the DUAL launch beside them), then the others
     int i = 0;
+    if (!do_bank) return call(0, src_flags, EditsPart::source(B));
     if (mv)
         for (; i + 2 <= n_inj; i += 2)
             if (const int rc = call(inj_e[i], inj_flags, EditsPart::pair_mv4(B, inj_e[i], inj_e[i + 1]))) return rc;
@@ -2754,7 +2805,7 @@ static int attn_fwd_edits_masked(const char* name, const void* q, const void* k,
             return rc;
     for (i = 0; i < n_non; ++i)
         if (const int rc = call(non_e[i], non_flags, EditsPart::bank(B, non_e[i]))) return rc;
-    return call(0, src_flags, EditsPart::source(B));
+    return do_src ? call(0, src_flags, EditsPart::source(B)) : 0;
 }
 
 extern "C" int tf_ext_attn_fwd_edits(const void* q, const void* k, const void* v, void* out, int K, int Kq, int q_frame0,
@@ -2772,6 +2823,35 @@ extern "C" int tf_ext_attn_fwd_edits_masked(const void* q, const void* k, const 
                                             size_t ws_bytes, void* stream) {
     return attn_fwd_edits_masked("tf_ext_attn_fwd_edits_masked", q, k, v, out, K, Kq, q_frame0, S, H, Dh, ld, strides, scale,
                                  flags, dtype, n_edits, inject_mask, ws, ws_bytes, stream);
+}
+
+// The parts of the masked composition (include/tokenflow_hip.h): a frame-sharded rank computes the bank branches of every
+// edit on the buffer its exchange delivered and the source branch on its own tensors.
+extern "C" int tf_ext_attn_fwd_edits_part(const void* q, const void* k, const void* v, void* out, int K, int Kq, int q_frame0,
+                                          int S, int H, int Dh, int64_t ld, const int64_t* strides, float scale, int flags,
+                                          int dtype, int n_edits, unsigned inject_mask, int qk_compact, void* ws,
+                                          size_t ws_bytes, void* stream) {
+    return attn_fwd_edits_masked("tf_ext_attn_fwd_edits_part", q, k, v, out, K, Kq, q_frame0, S, H, Dh, ld, strides, scale,
+                                 flags, dtype, n_edits, inject_mask, ws, ws_bytes, stream, true, qk_compact);
+}
+
+// Launch plan of tf_ext_attn_fwd_edits_part for dense tensors (q / k dense or compact: the plan does not depend on it).
+extern "C" int tf_ext_attn_edits_part_plan(int K, int Kq, int S, int H, int Dh, int n_edits, unsigned inject_mask,
+                                           int qk_compact, int flags, int dtype, char* buf, size_t len) {
+    TF_ARG(K > 0 && S > 0 && H > 0 && Kq > 0 && Kq <= K, TF_ERR_SHAPE, "tf_ext_attn_edits_part_plan: K=%d Kq=%d S=%d H=%d", K,
+           Kq, S, H);
+    void* const ph = reinterpret_cast<void*>((uintptr_t)1 << 12);
+    const int64_t ld = (int64_t)H * Dh, fs = (int64_t)S * ld;
+    const int64_t strides[9] = {Kq * fs, fs, K * fs, fs, K * fs, fs, Kq * fs, fs, ld};
+    TfPlanRec rec{buf, len, 0, 0};
+    if (buf && len) buf[0] = 0;
+    tf_plan_rec = &rec;
+    const int rc = tf_ext_attn_fwd_edits_part(ph, ph, ph, ph, K, Kq, 0, S, H, Dh, ld, strides, 1.0f, flags, dtype, n_edits,
+                                              inject_mask, qk_compact, ph, (size_t)-1, nullptr);
+    tf_plan_rec = nullptr;
+    if (rc) return rc;
+    TF_ARG(rec.used < len, TF_ERR_WORKSPACE, "tf_ext_attn_edits_part_plan: the plan needs %zu bytes", rec.used + 1);
+    return rec.n;
 }
 
 // Launch plan of tf_ext_attn_fwd_edits for dense tensors, recorded by the entry point itself as tf_ext_attn_plan does.

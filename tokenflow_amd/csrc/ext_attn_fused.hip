@@ -71,7 +71,8 @@ struct FusedSet {   // device form of TfAttnSet
     const void* v;
     void* out;
     int64_t q_bs, q_fs, ld_q, k_bs, k_fs, v_bs, v_fs, ld, o_bs, o_fs;
-    int H, Kq, q_frame0, Kb, b0, nb, n_wg, pad_;
+    int H, Kq, q_frame0, Kb, b0, nb, n_wg;
+    int inject;   // multi-set launches (FusedParamsN): this set's bank branches use the set's branch-0 q and k
 };
 
 struct FusedParams {
@@ -81,6 +82,20 @@ struct FusedParams {
     int inject, out_f32;
     float c;                   // scale * log2(e)
     float lag;                 // TF_FUSED_LAG / c: raw score units the sub-tile maximum may exceed a query's reference by
+    static constexpr int MAX_SETS = 2;
+};
+
+// The same for launches of 3 .. 1 + TF_MAX_EDITS sets (the parts of a multi-edit batch: one set per edit's bank branches and
+// the source set).  A type of its own, so that the one- and two-set kernels keep their parameter block and their code; the
+// injection state is the SET's here (a mixed injection mask), `inject` of the launch is unused.
+struct FusedParamsN {
+    static constexpr int MAX_SETS = 1 + TF_MAX_EDITS;
+    FusedSet set[MAX_SETS];
+    int n_sets, S, nQT, tpf;
+    unsigned tpf_magic;
+    int inject, out_f32;
+    float c;
+    float lag;
 };
 
 __device__ __forceinline__ float max_xor32(float x) {
@@ -105,14 +120,20 @@ __device__ __forceinline__ void store_out4(void* out, int64_t elem_off, f32x4 x,
 struct Problem {   // one (set, branch, frame, head, query tile) problem, decoded from blockIdx.x
     int si, h, qt, f, b, bq, f_lo, n_fr;
 };
-__device__ __forceinline__ Problem decode_problem(const FusedParams& p) {
+template <typename P>
+__device__ __forceinline__ Problem decode_problem(const P& p) {
     // sets in order (the long bank problems of set 0 first), head fastest (H = 8: one head per XCD)
     Problem pr;
     int u = blockIdx.x;
     pr.si = 0;
-    if (p.n_sets > 1 && u >= p.set[0].n_wg) {
-        u -= p.set[0].n_wg;
-        pr.si = 1;
+    if constexpr (P::MAX_SETS == 2) {
+        if (p.n_sets > 1 && u >= p.set[0].n_wg) {
+            u -= p.set[0].n_wg;
+            pr.si = 1;
+        }
+    } else {
+        // workgroup-uniform walk over the sets (scalar loads from the kernel argument segment)
+        for (int n = p.set[0].n_wg; pr.si + 1 < p.n_sets && u >= n; n = p.set[pr.si].n_wg) u -= n, ++pr.si;
     }
     const FusedSet& st = p.set[pr.si];
     pr.h = u % st.H;
@@ -123,7 +144,8 @@ __device__ __forceinline__ Problem decode_problem(const FusedParams& p) {
     const int bi = u / st.Kq;
     // a full set (source + two bank branches) runs its bank branches first
     pr.b = (st.b0 == 0 && st.nb == 3) ? (bi == 2 ? 0 : bi + 1) : st.b0 + bi;
-    pr.bq = (p.inject && pr.b > 0) ? 0 : pr.b;   // branch whose q and k are used (tokenflow_utils.py:124-130)
+    const int inject = P::MAX_SETS == 2 ? p.inject : st.inject;
+    pr.bq = (inject && pr.b > 0) ? 0 : pr.b;   // branch whose q and k are used (tokenflow_utils.py:124-130)
     pr.f_lo = pr.b == 0 ? st.q_frame0 + pr.f : 0;
     pr.n_fr = pr.b == 0 ? 1 : st.Kb;
     return pr;
@@ -290,8 +312,8 @@ constexpr int merge_bytes() { return KW > 1 ? 2 * NW * 16 * 64 * 4 + NW * 64 * 4
 // KW   key groups: sub-tile j (32 keys) of the problem's key sequence is computed by the waves of group j % KW; the QW
 //      waves of group kw stage slot kw together (wave-uniform base pointer + per-thread constant offsets)
 // PREC P as hi + lo (bf16 only)
-template <typename T, int DH, int QW, int KW, bool PREC>
-__global__ __launch_bounds__(64 * QW * KW, 1) void ext_attn_fused_kernel(FusedParams p) {
+template <typename T, int DH, int QW, int KW, bool PREC, typename P = FusedParams>
+__global__ __launch_bounds__(64 * QW * KW, 1) void ext_attn_fused_kernel(P p) {
     typedef FusedCfg<DH> C;
     typedef typename T::elem E;
     typedef typename T::vec8 vec8;
@@ -435,8 +457,8 @@ __global__ __launch_bounds__(64 * QW * KW, 1) void ext_attn_fused_kernel(FusedPa
 //     level 1 it measured 70-72 against 72-75 us -- the launch is bound by its instruction mix, not by the re-reads
 //     (profiles/r04_pmc_fused.csv) -- at 250+ registers (one wave per SIMD at Dh = 80).
 // Same arithmetic per (query, head) as the shared-tile form with the same KW: bit-identical results.
-template <typename T, int DH, int KW, int QB, bool PREC>
-__global__ __launch_bounds__(64 * KW, 1) void ext_attn_fused_wp_kernel(FusedParams p) {
+template <typename T, int DH, int KW, int QB, bool PREC, typename P = FusedParams>
+__global__ __launch_bounds__(64 * KW, 1) void ext_attn_fused_wp_kernel(P p) {
     typedef FusedCfg<DH> C;
     typedef typename T::elem E;
     typedef typename T::vec8 vec8;
@@ -599,35 +621,42 @@ __global__ __launch_bounds__(64 * KW, 1) void ext_attn_fused_wp_kernel(FusedPara
     }
 }
 
-template <typename T, int DH, int QW, int KW, bool PREC>
-int launch_fused(const FusedParams& p, unsigned grid, hipStream_t st) {
+// plan token of a launch: today's for one or two sets, ",sets=N" appended beyond
+template <typename P>
+bool fused_note(const P& p, int qw, int kw, int qb, int prec) {
+    if (p.n_sets > 2) return tf_plan_note("fused[qw=%d,kw=%d,qb=%d,prec=%d,sets=%d]", qw, kw, qb, prec, p.n_sets);
+    return tf_plan_note("fused[qw=%d,kw=%d,qb=%d,prec=%d]", qw, kw, qb, prec);
+}
+
+template <typename T, int DH, int QW, int KW, bool PREC, typename P>
+int launch_fused(const P& p, unsigned grid, hipStream_t st) {
     typedef FusedCfg<DH> C;
     constexpr int NW = QW * KW;
     constexpr int STAGE_BYTES = KW * (C::K_ELEMS + 32 * C::VS) * 2;
     constexpr int lds = STAGE_BYTES > merge_bytes<NW, KW>() ? STAGE_BYTES : merge_bytes<NW, KW>();
-    if (tf_plan_note("fused[qw=%d,kw=%d,qb=1,prec=%d]", QW, KW, PREC ? 1 : 0)) return 0;
-    auto kern = ext_attn_fused_kernel<T, DH, QW, KW, PREC>;
+    if (fused_note(p, QW, KW, 1, PREC ? 1 : 0)) return 0;
+    auto kern = ext_attn_fused_kernel<T, DH, QW, KW, PREC, P>;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NW), lds, st, p);
     TF_LAUNCH_CHECK("tf_ext_attn_fwd(fused)");
     return 0;
 }
 
-template <typename T, int DH, int KW, int QB, bool PREC>
-int launch_fused_wp(const FusedParams& p, unsigned grid, hipStream_t st) {
+template <typename T, int DH, int KW, int QB, bool PREC, typename P>
+int launch_fused_wp(const P& p, unsigned grid, hipStream_t st) {
     typedef FusedCfg<DH> C;
     constexpr int STAGE_BYTES = (KW * 32 * C::VS + (DH == 160 ? C::K_ELEMS : 0)) * 2;
     constexpr int lds = STAGE_BYTES > merge_bytes<KW, KW>() ? STAGE_BYTES : merge_bytes<KW, KW>();
-    if (tf_plan_note("fused[qw=1,kw=%d,qb=%d,prec=%d]", KW, QB, PREC ? 1 : 0)) return 0;
-    auto kern = ext_attn_fused_wp_kernel<T, DH, KW, QB, PREC>;
+    if (fused_note(p, 1, KW, QB, PREC ? 1 : 0)) return 0;
+    auto kern = ext_attn_fused_wp_kernel<T, DH, KW, QB, PREC, P>;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * KW), lds, st, p);
     TF_LAUNCH_CHECK("tf_ext_attn_fwd(fused)");
     return 0;
 }
 
-template <typename T, int DH, bool PREC>
-int dispatch_geom(const FusedParams& p, unsigned grid, int qw, int kw, int qb, hipStream_t st) {
+template <typename T, int DH, bool PREC, typename P>
+int dispatch_geom(const P& p, unsigned grid, int qw, int kw, int qb, hipStream_t st) {
     if constexpr (DH <= 80) {
         if (qw == 1 && kw == 4 && qb == 2) return launch_fused_wp<T, DH, 4, 2, PREC>(p, grid, st);
     }
@@ -645,15 +674,15 @@ int dispatch_geom(const FusedParams& p, unsigned grid, int qw, int kw, int qb, h
     return TF_ERR_SHAPE;
 }
 
-template <typename T, int DH>
-int dispatch_prec(const FusedParams& p, unsigned grid, const TfFusedPlan& plan, hipStream_t st) {
+template <typename T, int DH, typename P>
+int dispatch_prec(const P& p, unsigned grid, const TfFusedPlan& plan, hipStream_t st) {
     constexpr bool bf = std::is_same<T, BF16>::value;
     if (bf && plan.prec) return dispatch_geom<T, DH, bf>(p, grid, plan.qw, plan.kw, plan.qb, st);
     return dispatch_geom<T, DH, false>(p, grid, plan.qw, plan.kw, plan.qb, st);
 }
 
-template <typename T>
-int dispatch_dh(int Dh, const FusedParams& p, unsigned grid, const TfFusedPlan& plan, hipStream_t st) {
+template <typename T, typename P>
+int dispatch_dh(int Dh, const P& p, unsigned grid, const TfFusedPlan& plan, hipStream_t st) {
     switch (Dh) {
         case 40: return dispatch_prec<T, 40>(p, grid, plan, st);
         case 64: return dispatch_prec<T, 64>(p, grid, plan, st);
@@ -726,16 +755,16 @@ TfFusedPlan tf_attn_fused_plan(const TfAttnSet* sets, int n_sets, int S, int Dh,
     return pl;
 }
 
-int tf_attn_fused_launch(const TfAttnSet* sets, int n_sets, int S, int Dh, float scale, int flags, int dtype,
-                         const TfFusedPlan& plan, hipStream_t st) {
-    TF_ARG(sets && n_sets >= 1 && n_sets <= 2, TF_ERR_SHAPE, "tf_ext_attn_fwd(fused): %d tensor sets", n_sets);
-    FusedParams p{};
+template <typename P>
+static int fused_launch_sets(const TfAttnSet* sets, int n_sets, int S, int Dh, float scale, int flags, int dtype,
+                             const TfFusedPlan& plan, int inject0, hipStream_t st) {
+    P p{};
     p.n_sets = n_sets;
     p.S = S;
     p.nQT = (S + 32 * plan.qw * plan.qb - 1) / (32 * plan.qw * plan.qb);
     p.tpf = (S + 31) / 32;
     p.tpf_magic = p.tpf > 1 ? (unsigned)(((uint64_t)1 << 32) / (unsigned)p.tpf + 1) : 0u;
-    p.inject = (flags & TF_ATTN_INJECT) ? 1 : 0;
+    p.inject = inject0;
     p.out_f32 = (flags & TF_ATTN_OUT_F32) ? 1 : 0;
     p.c = (float)((double)scale * 1.4426950408889634);
     p.lag = (float)TF_FUSED_LAG / p.c;
@@ -751,6 +780,7 @@ int tf_attn_fused_launch(const TfAttnSet* sets, int n_sets, int S, int Dh, float
         d.q_bs = a.q_bs, d.q_fs = a.q_fs, d.ld_q = a.ld_q, d.k_bs = a.k_bs, d.k_fs = a.k_fs, d.v_bs = a.v_bs, d.v_fs = a.v_fs;
         d.ld = a.ld, d.o_bs = a.o_bs, d.o_fs = a.o_fs;
         d.H = a.H, d.Kq = a.Kq, d.q_frame0 = a.q_frame0, d.Kb = a.Kb, d.b0 = a.b0, d.nb = a.nb;
+        d.inject = ((flags & TF_ATTN_INJECT) || a.inject) ? 1 : 0;
         d.n_wg = a.nb * a.Kq * a.H * p.nQT;
         grid += d.n_wg;
     }
@@ -759,4 +789,22 @@ int tf_attn_fused_launch(const TfAttnSet* sets, int n_sets, int S, int Dh, float
     // the magic division is exact for j * tpf < 2^32: the sub-tile index stays far below that
     return dtype == TF_BF16 ? dispatch_dh<BF16>(Dh, p, (unsigned)grid, plan, st)
                             : dispatch_dh<F16>(Dh, p, (unsigned)grid, plan, st);
+}
+
+int tf_attn_fused_launch(const TfAttnSet* sets, int n_sets, int S, int Dh, float scale, int flags, int dtype,
+                         const TfFusedPlan& plan, hipStream_t st) {
+    TF_ARG(sets && n_sets >= 1 && n_sets <= 1 + TF_MAX_EDITS, TF_ERR_SHAPE, "tf_ext_attn_fwd(fused): %d tensor sets", n_sets);
+    // a set injects under TF_ATTN_INJECT of `flags` or its own `inject`.  One or two sets whose bank branches agree take
+    // the kernels with the launch-wide flag (today's launches exactly); anything else the per-set form
+    int inj = -1;
+    bool uniform = n_sets <= 2;
+    for (int i = 0; i < n_sets && uniform; ++i) {
+        if (sets[i].b0 + sets[i].nb <= 1) continue;   // source branch only: the flag has nothing to select
+        const int e = ((flags & TF_ATTN_INJECT) || sets[i].inject) ? 1 : 0;
+        uniform = inj < 0 || inj == e;
+        inj = e;
+    }
+    if (uniform)
+        return fused_launch_sets<FusedParams>(sets, n_sets, S, Dh, scale, flags, dtype, plan, inj > 0 ? 1 : 0, st);
+    return fused_launch_sets<FusedParamsN>(sets, n_sets, S, Dh, scale, flags, dtype, plan, 0, st);
 }

@@ -7,15 +7,21 @@
 
 namespace {
 
-constexpr int MAX_SLABS = 6;
+// One edit: q, k, v of its three branches less what injection leaves at home -- at most 6 slabs.  A multi-edit batch packs up
+// to 6 per edit (no edit injects) and unpacks 2 per edit.  Two parameter-block sizes, so that a single edit's launches keep
+// their 96-byte block and their code.
+constexpr int MAX_SLABS_1 = 6;
+constexpr int MAX_SLABS = 6 * TF_MAX_EDITS;
 
+template <int N>
 struct SlabPtrs {
-    const unsigned char* src[MAX_SLABS];   // pack: slab i = a [Kl, S, ld] tensor (frame stride fs[i]); unpack: dst[i]
-    int64_t fs[MAX_SLABS];                  // frame strides in BYTES
+    const unsigned char* src[N];   // pack: slab i = a [Kl, S, ld] tensor (frame stride fs[i]); unpack: dst[i]
+    int64_t fs[N];                 // frame strides in BYTES
 };
 
 // send[w][f][i][s][hd] = slab_i[f][s][w*hd ...]
-__global__ __launch_bounds__(256) void head_pack_kernel(SlabPtrs sl, unsigned char* __restrict__ send, int ns, int W,
+template <int N>
+__global__ __launch_bounds__(256) void head_pack_kernel(SlabPtrs<N> sl, unsigned char* __restrict__ send, int ns, int W,
                                                         int Kl, int S, int hd_pieces, int64_t ld_bytes) {
     const int64_t total = (int64_t)W * Kl * ns * S * hd_pieces;
     for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < total; g += (int64_t)gridDim.x * 256) {
@@ -36,8 +42,8 @@ __global__ __launch_bounds__(256) void head_pack_kernel(SlabPtrs sl, unsigned ch
 // The same launch with extra workgroups behind the packing ones that compute inv_norm[r] = 1 / ||piv[r]|| of the rank's
 // pivot rows (tf_pivot_inv_norm's arithmetic, one wave per row): at the coarse levels of a sharded rank a launch costs
 // more than either piece of work.
-template <typename T>
-__global__ __launch_bounds__(256) void head_pack_norm_kernel(SlabPtrs sl, unsigned char* __restrict__ send, int ns, int W,
+template <typename T, int N>
+__global__ __launch_bounds__(256) void head_pack_norm_kernel(SlabPtrs<N> sl, unsigned char* __restrict__ send, int ns, int W,
                                                              int Kl, int S, int hd_pieces, int64_t ld_bytes, int nb_pack,
                                                              const typename T::elem* __restrict__ piv,
                                                              float* __restrict__ inv_norm, int64_t rows, int D) {
@@ -67,7 +73,8 @@ __global__ __launch_bounds__(256) void head_pack_norm_kernel(SlabPtrs sl, unsign
 }
 
 // dst_b[f][s][w*hd ...] = recv[w][f][b][s][hd]
-__global__ __launch_bounds__(256) void head_unpack_kernel(const unsigned char* __restrict__ recv, SlabPtrs sl, int nb,
+template <int N>
+__global__ __launch_bounds__(256) void head_unpack_kernel(const unsigned char* __restrict__ recv, SlabPtrs<N> sl, int nb,
                                                           int W, int Kl, int S, int hd_pieces, int64_t ld_bytes) {
     const int64_t total = (int64_t)W * Kl * nb * S * hd_pieces;
     for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < total; g += (int64_t)gridDim.x * 256) {
@@ -101,6 +108,25 @@ int check(const char* name, const void* const* slabs, const int64_t* fs, int n, 
     return 0;
 }
 
+template <int N>
+SlabPtrs<N> slab_ptrs(const void* const* slabs, const int64_t* frame_strides, int n, int elem_bytes) {
+    SlabPtrs<N> sl{};
+    for (int i = 0; i < n; ++i) {
+        sl.src[i] = static_cast<const unsigned char*>(slabs[i]);
+        sl.fs[i] = frame_strides[i] * elem_bytes;
+    }
+    return sl;
+}
+
+template <typename T, int N>
+void launch_pack_norm(const void* const* slabs, const int64_t* frame_strides, int ns, void* send, int W, int Kl, int S,
+                      int hd_pieces, int64_t ld, int elem_bytes, int64_t blocks, int64_t nblocks, const void* piv,
+                      float* inv_norm, int64_t rows, int D, hipStream_t st) {
+    hipLaunchKernelGGL((head_pack_norm_kernel<T, N>), dim3((unsigned)(blocks + nblocks)), dim3(256), 0, st,
+                       slab_ptrs<N>(slabs, frame_strides, ns, elem_bytes), static_cast<unsigned char*>(send), ns, W, Kl, S,
+                       hd_pieces, ld * elem_bytes, (int)blocks, static_cast<const typename T::elem*>(piv), inv_norm, rows, D);
+}
+
 }  // namespace
 
 int tf_head_pack_norm(const void* const* slabs, const int64_t* frame_strides, int ns, void* send, int W, int Kl, int S,
@@ -110,11 +136,6 @@ int tf_head_pack_norm(const void* const* slabs, const int64_t* frame_strides, in
     if (const int rc = check("tf_head_pack", slabs, frame_strides, ns, send, W, Kl, S, hd, ld, elem_bytes)) return rc;
     TF_ARG(inv_norm && rows > 0 && D > 0 && D % 8 == 0 && (dtype == TF_BF16 || dtype == TF_F16) && tf_aligned16(piv),
            TF_ERR_SHAPE, "tf_head_pack(+inverse norms): rows=%lld D=%d dtype=%d", (long long)rows, D, dtype);
-    SlabPtrs sl{};
-    for (int i = 0; i < ns; ++i) {
-        sl.src[i] = static_cast<const unsigned char*>(slabs[i]);
-        sl.fs[i] = frame_strides[i] * elem_bytes;
-    }
     const int hd_pieces = hd * elem_bytes / 16;
     const int64_t total = (int64_t)W * Kl * ns * S * hd_pieces;
     int64_t blocks = (total + 255) / 256;
@@ -122,14 +143,9 @@ int tf_head_pack_norm(const void* const* slabs, const int64_t* frame_strides, in
     int64_t nblocks = (rows + 3) / 4;
     if (nblocks > 4096) nblocks = 4096;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == TF_BF16)
-        hipLaunchKernelGGL(head_pack_norm_kernel<BF16>, dim3((unsigned)(blocks + nblocks)), dim3(256), 0, st, sl,
-                           static_cast<unsigned char*>(send), ns, W, Kl, S, hd_pieces, ld * elem_bytes, (int)blocks,
-                           static_cast<const __bf16*>(piv), inv_norm, rows, D);
-    else
-        hipLaunchKernelGGL(head_pack_norm_kernel<F16>, dim3((unsigned)(blocks + nblocks)), dim3(256), 0, st, sl,
-                           static_cast<unsigned char*>(send), ns, W, Kl, S, hd_pieces, ld * elem_bytes, (int)blocks,
-                           static_cast<const _Float16*>(piv), inv_norm, rows, D);
+    auto go = ns <= MAX_SLABS_1 ? (dtype == TF_BF16 ? launch_pack_norm<BF16, MAX_SLABS_1> : launch_pack_norm<F16, MAX_SLABS_1>)
+                                : (dtype == TF_BF16 ? launch_pack_norm<BF16, MAX_SLABS> : launch_pack_norm<F16, MAX_SLABS>);
+    go(slabs, frame_strides, ns, send, W, Kl, S, hd_pieces, ld, elem_bytes, blocks, nblocks, piv, inv_norm, rows, D, st);
     TF_LAUNCH_CHECK("tf_head_pack");
     return 0;
 }
@@ -137,17 +153,19 @@ int tf_head_pack_norm(const void* const* slabs, const int64_t* frame_strides, in
 extern "C" int tf_head_pack(const void* const* slabs, const int64_t* frame_strides, int ns, void* send, int W, int Kl,
                             int S, int hd, int64_t ld, int elem_bytes, void* stream) {
     if (const int rc = check("tf_head_pack", slabs, frame_strides, ns, send, W, Kl, S, hd, ld, elem_bytes)) return rc;
-    SlabPtrs sl{};
-    for (int i = 0; i < ns; ++i) {
-        sl.src[i] = static_cast<const unsigned char*>(slabs[i]);
-        sl.fs[i] = frame_strides[i] * elem_bytes;
-    }
     const int hd_pieces = hd * elem_bytes / 16;
     const int64_t total = (int64_t)W * Kl * ns * S * hd_pieces;
     int64_t blocks = (total + 255) / 256;
     if (blocks > 256 * 16) blocks = 256 * 16;
-    hipLaunchKernelGGL(head_pack_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), sl,
-                       static_cast<unsigned char*>(send), ns, W, Kl, S, hd_pieces, ld * elem_bytes);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (ns <= MAX_SLABS_1)
+        hipLaunchKernelGGL(head_pack_kernel<MAX_SLABS_1>, dim3((unsigned)blocks), dim3(256), 0, st,
+                           slab_ptrs<MAX_SLABS_1>(slabs, frame_strides, ns, elem_bytes), static_cast<unsigned char*>(send), ns,
+                           W, Kl, S, hd_pieces, ld * elem_bytes);
+    else
+        hipLaunchKernelGGL(head_pack_kernel<MAX_SLABS>, dim3((unsigned)blocks), dim3(256), 0, st,
+                           slab_ptrs<MAX_SLABS>(slabs, frame_strides, ns, elem_bytes), static_cast<unsigned char*>(send), ns, W,
+                           Kl, S, hd_pieces, ld * elem_bytes);
     TF_LAUNCH_CHECK("tf_head_pack");
     return 0;
 }
@@ -157,17 +175,20 @@ extern "C" int tf_head_unpack(const void* recv, void* const* dsts, const int64_t
     if (const int rc = check("tf_head_unpack", const_cast<const void* const*>(dsts), frame_strides, nb, recv, W, Kl, S, hd,
                              ld, elem_bytes))
         return rc;
-    SlabPtrs sl{};
-    for (int i = 0; i < nb; ++i) {
-        sl.src[i] = static_cast<const unsigned char*>(dsts[i]);
-        sl.fs[i] = frame_strides[i] * elem_bytes;
-    }
     const int hd_pieces = hd * elem_bytes / 16;
     const int64_t total = (int64_t)W * Kl * nb * S * hd_pieces;
     int64_t blocks = (total + 255) / 256;
     if (blocks > 256 * 16) blocks = 256 * 16;
-    hipLaunchKernelGGL(head_unpack_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                       static_cast<const unsigned char*>(recv), sl, nb, W, Kl, S, hd_pieces, ld * elem_bytes);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const void* const* dptrs = const_cast<const void* const*>(dsts);
+    if (nb <= MAX_SLABS_1)
+        hipLaunchKernelGGL(head_unpack_kernel<MAX_SLABS_1>, dim3((unsigned)blocks), dim3(256), 0, st,
+                           static_cast<const unsigned char*>(recv), slab_ptrs<MAX_SLABS_1>(dptrs, frame_strides, nb, elem_bytes),
+                           nb, W, Kl, S, hd_pieces, ld * elem_bytes);
+    else
+        hipLaunchKernelGGL(head_unpack_kernel<MAX_SLABS>, dim3((unsigned)blocks), dim3(256), 0, st,
+                           static_cast<const unsigned char*>(recv), slab_ptrs<MAX_SLABS>(dptrs, frame_strides, nb, elem_bytes),
+                           nb, W, Kl, S, hd_pieces, ld * elem_bytes);
     TF_LAUNCH_CHECK("tf_head_unpack");
     return 0;
 }

@@ -94,6 +94,9 @@ def register_frame_shard(diffusion_model, shard):
     Results equal the single-process hooks' in the bit-stable mode (TOKENFLOW_ATTN_NO_SPLIT=1) bit for bit (`FrameShard`'s
     default one-pass attention; against the default single-process mode: within the attention's parity bound); every rank must
     draw the same `pivotal_idx` (run_tokenflow_pnp.py:224).  INTEGRATION.md section 3 shows the driver side.
+    With `register_edits(model, E > 1)` the batches are the rank's keyframes / chunks of all 1 + 2E branches and a `FrameShard`
+    runs them as ONE multi-edit pass (`supports_edits`: one pack, the same collectives, one unpack, one search per block);
+    `NativeShard` runs one edit and raises.
     A world-1 shard (one GPU) runs the bit-stable attention mode too unless it was built with `attn_split=True`: slower
     than the plain single-process hooks by the per-grid kernel choice it gives up (`tools/hooks_bench.py --ranks 1`)."""
     for module in _tokenflow_blocks(diffusion_model):
@@ -152,8 +155,10 @@ def register_edits(model, n_edits):
     and the injected resnet.  For every op of the path the slices of edit e are what the single-edit pass computes on
     [source | uncond_e | cond_e]; the NN search, the source branch and (under injection) the scores are computed once.
     n_edits = 1 (the default without this call) is the reference's layout and issues exactly the single-edit ops.
-    Not generalised, ValueError with n_edits > 1: a registered frame shard, the AdaLayerNormZero gated path, replay
-    through `tokenflow_amd.graphs.GraphCache` (INTEGRATION.md section 4 shows the driver side)."""
+    Combines with `register_frame_shard` where the shard type runs multi-edit batches (`FrameShard.supports_edits`): every rank
+    then runs one multi-edit pass on its keyframes and chunks.
+    Not generalised, ValueError with n_edits > 1: a frame shard without that capability (NativeShard), the AdaLayerNormZero gated
+    path, replay through `tokenflow_amd.graphs.GraphCache` (INTEGRATION.md section 4 shows the driver side)."""
     n_edits = int(n_edits)
     from . import _lib
     if not 1 <= n_edits <= _lib.TF_MAX_EDITS:
@@ -257,7 +262,8 @@ def register_edit_schedules(model, qk_schedules=None, conv_schedules=None):
     else -> the same op with `inject_mask=` / `edit_mask=`.  For every op the slices of edit e are what the single-edit op
     computes on [source | uncond_e | cond_e] with edit e's own schedule.  None for an argument removes that kind's per-edit
     schedules (the installer's shared schedule holds again); re-running an installer removes them on the modules it touches;
-    the SDEdit installer (register_extended_attention) never injects and ignores them."""
+    the SDEdit installer (register_extended_attention) never injects and ignores them.  On a registered `FrameShard` the
+    mask of a call goes to `shard.pivotal_attention(..., n_edits=E, inject_mask=mask)`."""
     unet = model.unet
 
     def sets_for(what, schedules, module):
@@ -418,8 +424,10 @@ def _make_sa_forward(self, pnp: bool):
         inject = mask != 0
         if shard is not None:     # q, k, v are this rank's keyframes; the bank is everybody's (register_frame_shard)
             if E > 1:
-                raise ValueError("register_edits: a multi-edit batch (n_edits > 1) on a registered frame shard is not supported")
-            out = shard.pivotal_attention(q, k, v, self.heads, self.scale, inject)
+                _need_edit_shard(shard)
+                out = shard.pivotal_attention(q, k, v, self.heads, self.scale, False, n_edits=E, inject_mask=mask)
+            else:
+                out = shard.pivotal_attention(q, k, v, self.heads, self.scale, inject)
         elif E == 1:
             out = ops.ext_attn(q, k, v, self.heads, self.scale, inject)
         elif mask in (0, (1 << E) - 1):   # [source | uncond_1 | cond_1 | ...]: the source branch and (injecting) the scores once
@@ -521,15 +529,24 @@ def _block_norm(mod: torch.nn.Module, x: torch.Tensor, want_inv_norm: bool = Fal
     return ops.layer_norm(x, mod.weight, mod.bias, mod.eps, dt, want_inv_norm, out=out, inv_out=inv_out)
 
 
-def _shard_state(block, shard, S: int, D: int, dtype, device):
+def _need_edit_shard(shard):
+    """A multi-edit batch needs a shard type that runs one (`FrameShard.supports_edits`; the native rank executor's
+    tf_rank_pivotal is single-edit)."""
+    if not getattr(type(shard), "supports_edits", False):
+        raise ValueError(f"register_edits: a multi-edit batch (n_edits > 1) on a registered frame shard of type "
+                         f"{type(shard).__name__} is not supported (FrameShard runs one; the native executor does not)")
+
+
+def _shard_state(block, shard, S: int, D: int, dtype, device, nbr: int = 3):
     """The block's halo-extended propagation state on a sharded rank, allocated ONCE per block and shape and reused
     step after step (a step's chunk passes are done with it before the next pivotal pass writes it):
+      (nbr = 3 branches, or the 1 + 2E of a multi-edit batch)
       norm [1 + 3*Kl, S, D]   slot 0 = the left neighbour's last keyframe, then norm1's output of the pivotal pass,
                               branch-major -- so the first Kl + 1 slots ARE the halo-extended pivots, written by the
                               norm itself;
       inv  [1 + 3*Kl, S]      the same for the rows' inverse norms;
       kfo  [3, Kl + 1, S, D]  cached attention output (after to_out) with the neighbour's slot in front."""
-    key = (shard.Kl, S, D, dtype, device)
+    key = (shard.Kl, S, D, dtype, device) if nbr == 3 else (shard.Kl, S, D, dtype, device, nbr)
     st = block.__dict__.get("_tf_shard_state")
     if st is None or st[0] != key:
         if device.type == "cuda" and torch.cuda.is_current_stream_capturing():
@@ -538,9 +555,9 @@ def _shard_state(block, shard, S: int, D: int, dtype, device):
             raise RuntimeError("register_frame_shard: the per-block propagation state would be allocated inside a HIP-graph "
                                "capture; run one eager pivotal pass first (GraphCache(warmup >= 1) does)")
         Kl = shard.Kl
-        st = (key, torch.empty(1 + 3 * Kl, S, D, dtype=dtype, device=device),
-              torch.empty(1 + 3 * Kl, S, dtype=torch.float32, device=device),
-              torch.empty(3, Kl + 1, S, D, dtype=dtype, device=device))
+        st = (key, torch.empty(1 + nbr * Kl, S, D, dtype=dtype, device=device),
+              torch.empty(1 + nbr * Kl, S, dtype=torch.float32, device=device),
+              torch.empty(nbr, Kl + 1, S, D, dtype=dtype, device=device))
         block.__dict__["_tf_shard_state"] = st
     return st[1], st[2], st[3]
 
@@ -614,8 +631,7 @@ def make_tokenflow_attention_block(block_class: Type[torch.nn.Module]) -> Type[t
             nbr = 1 + 2 * E         # branches: [source | uncond | cond], or the multi-edit batch of register_edits
             if E > 1:
                 if self.__dict__.get("_tf_shard") is not None:
-                    raise ValueError("register_edits: a multi-edit batch (n_edits > 1) on a registered frame shard is not "
-                                     "supported")
+                    _need_edit_shard(self.__dict__["_tf_shard"])
                 if self.use_ada_layer_norm_zero:
                     raise ValueError("register_edits: a multi-edit batch (n_edits > 1) through the AdaLayerNormZero gated path "
                                      "is not supported")
@@ -646,8 +662,8 @@ def make_tokenflow_attention_block(block_class: Type[torch.nn.Module]) -> Type[t
                         self.__dict__["_tf_halo"] = (prev[0], prev[1], prev[2], [])
                     # sharded pivotal pass: norm1 writes straight into the block's halo-extended state
                     def dest(dt, _s=shard0):
-                        nb, ib, _ = _shard_state(self, _s, sequence_length, dim, dt, hidden_states.device)
-                        return nb[1:].view(3, n_frames, sequence_length, dim), ib[1:].view(3, n_frames, sequence_length)
+                        nb, ib, _ = _shard_state(self, _s, sequence_length, dim, dt, hidden_states.device, nbr)
+                        return nb[1:].view(nbr, n_frames, sequence_length, dim), ib[1:].view(nbr, n_frames, sequence_length)
                 if self.pivotal_pass or NORM1_ALL_BRANCHES:
                     norm_hidden_states, norm_inv = _block_norm(self.norm1, hidden_states, bool(self.pivotal_pass), dest=dest)
                 else:
@@ -696,14 +712,15 @@ def make_tokenflow_attention_block(block_class: Type[torch.nn.Module]) -> Type[t
                     # Linear: its output tensor is torch's); no allocation, no other copy
                     nb, ib, kfo = st[1], st[2], st[3]
                     Kl = shard.Kl
-                    kfo[:, 1:].copy_(self.kf_attn_output.reshape(3, Kl, sequence_length, dim))
+                    kfo[:, 1:].copy_(self.kf_attn_output.reshape(nbr, Kl, sequence_length, dim))
                     piv_e, inv_e = nb[:Kl + 1], ib[:Kl + 1]
-                    reqs = shard.halo_block(piv_e, inv_e, kfo)
-                    self.__dict__["_tf_halo"] = (piv_e, inv_e, kfo.view(3 * (Kl + 1), sequence_length, dim), reqs)
+                    reqs = shard.halo_block(piv_e, inv_e, kfo) if E == 1 else shard.halo_block(piv_e, inv_e, kfo, n_edits=E)
+                    self.__dict__["_tf_halo"] = (piv_e, inv_e, kfo.view(nbr * (Kl + 1), sequence_length, dim), reqs)
                 elif shard is not None:   # (pivots, inverse norms, attention output) with the neighbour's slot in
                     # front, and the pending requests of the exchange: the first chunk pass waits for them
-                    self.__dict__["_tf_halo"] = shard.halo_finish(
-                        halo, self.kf_attn_output.reshape(batch_size, sequence_length, dim).contiguous(), wait=False)
+                    kfl = self.kf_attn_output.reshape(batch_size, sequence_length, dim).contiguous()
+                    self.__dict__["_tf_halo"] = (shard.halo_finish(halo, kfl, wait=False) if E == 1 else
+                                                 shard.halo_finish(halo, kfl, wait=False, n_edits=E))
                 if self.use_ada_layer_norm_zero:
                     self.attn_output = gate_msa.unsqueeze(1) * self.attn_output
                 attn_output = self.attn_output

@@ -361,6 +361,73 @@ def ext_attn_views(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch
     return out
 
 
+def ext_attn_edits_views(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, heads: int, scale: float,
+                         n_edits: int, inject_mask: int, part: str = "all", qk_compact: bool = False,
+                         branch0=(0, 0, 0, 0), q_frame0: int = 0, fold_scale: Optional[bool] = None,
+                         no_split: Optional[bool] = None, fused: Optional[bool] = None, multi_v: Optional[bool] = None,
+                         hints: int = 0, stream: Optional[int] = None) -> torch.Tensor:
+    """The parts of `ext_attn_edits` on strided 4-D views [branches, frames, S, D] (tf_ext_attn_fwd_edits_part), in the manner
+    of `ext_attn_views`: E = n_edits edits, v and out addressed as [source | uncond_1 | cond_1 | ...] (1 + 2E branches),
+    inject_mask the injection state per edit.  part = "bank": the bank branches of EVERY edit (the source slabs of v and out
+    are never touched), "source": the source branch alone, "all": both.
+    qk_compact: q and k hold only the branches a launch reads -- slot 0 the source, then (uncond, cond) of every
+    NON-injecting edit in ascending order; an injecting edit reads slot 0.  Each view holds the slots / branches
+    `branch0[i] ..` of its tensor (a bank part in which no edit injects passes q and k from slot 1 with branch0 = 1).
+    Every part that takes the fused small-problem kernel shares ONE launch with the others (bit-identical to the per-edit
+    `ext_attn_views` calls under no_split=True; within the attention bound otherwise).  Other arguments as
+    `ext_attn_views` / `ext_attn_edits`."""
+    dev = _need_gpu(q, k, v, out)
+    lib = _lib.load()
+    mask = _edit_mask("ext_attn_edits_views", inject_mask, n_edits)
+    E = int(n_edits)
+    S, D = k.shape[2], k.shape[3]
+    K, Kq, dh = k.shape[1], q.shape[1], D // heads
+    dt = _DT.get(q.dtype)
+    if dt is None or dt == _lib.TF_F32 or k.dtype != q.dtype or v.dtype != q.dtype or D % heads:
+        raise TypeError("ext_attn_edits_views: q/k/v must share dtype bf16 or f16")
+    qp, q_bs, q_fs, ld_q = _view_base(q, branch0[0], S, "q")
+    kp, k_bs, k_fs, ld = _view_base(k, branch0[1], S, "k")
+    vp, v_bs, v_fs, ld_v = _view_base(v, branch0[2], S, "v")
+    op, o_bs, o_fs, ld_o = _view_base(out, branch0[3], S, "out")
+    if ld_v != ld or ld_o != D or out.shape[1] != Kq or v.shape[1] != K:
+        raise ValueError("ext_attn_edits_views: k and v need one token stride, out a dense one; frames of v = frames of k")
+    if out.dtype not in (q.dtype, torch.float32):
+        raise TypeError("ext_attn_edits_views: out dtype")
+    # the branches each view must hold for this part (a view of ONE branch has no branch stride to address others with)
+    nbr = 1 + 2 * E
+    n_non = E - bin(mask).count("1")
+    n_qk = (1 + 2 * n_non) if qk_compact else nbr
+    lo_vo, hi_vo = (1, nbr) if part == "bank" else (0, 1) if part == "source" else (0, nbr)
+    lo_qk = 0 if (part != "bank" or mask) else 1
+    hi_qk = 1 if part == "source" else (n_qk if n_non else 1)
+    for t, b0, lo, hi, what in ((q, branch0[0], lo_qk, hi_qk, "q"), (k, branch0[1], lo_qk, hi_qk, "k"),
+                                (v, branch0[2], lo_vo, hi_vo, "v"), (out, branch0[3], lo_vo, hi_vo, "out")):
+        if b0 > lo or b0 + t.shape[0] < hi:
+            raise ValueError(f"ext_attn_edits_views: {what} holds branches [{b0}, {b0 + t.shape[0]}), part '{part}' of "
+                             f"{E} edits with mask {mask:#x} reads [{lo}, {hi})")
+    flags = _attn_flags(False, part, out.dtype == torch.float32, fold_scale, no_split, fused, hints) | _multi_v_bits(multi_v)
+    ws = _workspace(lib.tf_ext_attn_edits_workspace_bytes(K, S, heads, dh, E, dt), q.device, stream=stream)
+    strides = (ctypes.c_int64 * 9)(q_bs, q_fs, k_bs, k_fs, v_bs, v_fs, o_bs, o_fs, ld_q)
+    _launch(dev, "tf_ext_attn_fwd_edits_part", lib.tf_ext_attn_fwd_edits_part, qp, kp, vp, op, K, Kq, int(q_frame0), S, heads,
+            dh, ld, ctypes.cast(strides, ctypes.c_void_p), float(scale), flags, dt, E, mask, 1 if qk_compact else 0,
+            ws.data_ptr(), ws.numel(), stream=stream)
+    return out
+
+
+def attn_edits_part_plan(K: int, Kq: int, S: int, heads: int, dh: int, n_edits: int, inject_mask: int, part: str = "all",
+                         qk_compact: bool = False, dtype: torch.dtype = torch.bfloat16,
+                         out_dtype: Optional[torch.dtype] = None, fold_scale: Optional[bool] = None,
+                         no_split: Optional[bool] = None, fused: Optional[bool] = None, multi_v: Optional[bool] = None,
+                         hints: int = 0) -> list:
+    """The launches of `ext_attn_edits_views` for dense tensors, as tokens (tf_ext_attn_edits_part_plan): those of
+    `attn_edits_plan(inject_mask=...)` for the part, or -- where every part takes the fused kernel -- ONE token such as
+    'fused[qw=1,kw=4,qb=1,prec=1,sets=4]' (',sets=N' for N > 2 tensor sets).  Host only: needs no GPU."""
+    flags = _attn_flags(False, part, out_dtype == torch.float32, fold_scale, no_split, fused, hints) | _multi_v_bits(multi_v)
+    mask = _edit_mask("attn_edits_part_plan", inject_mask, n_edits)
+    return _plan_tokens("tf_ext_attn_edits_part_plan", _lib.load().tf_ext_attn_edits_part_plan, K, Kq, S, heads, dh,
+                        int(n_edits), mask, 1 if qk_compact else 0, flags, _DT[dtype])
+
+
 def _run_flags(inject: bool, bank_only: bool, out_f32: bool, fold_scale: Optional[bool], no_split: bool, hints: int) -> int:
     """The TF_ATTN_* bit mask of a run / merge call (the module default TOKENFLOW_ATTN_NO_SPLIT does not apply: a run set is
     a split form by construction; no_split=True only keeps a run from splitting itself further)."""
@@ -472,7 +539,7 @@ def ext_attn_runs(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int,
 
 
 def head_pack(slabs: Sequence[torch.Tensor], W: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """slabs: ns <= 6 tensors [Kl, S, D] (frame stride free, rows dense-strided, same dtype) -> the all-to-all send
+    """slabs: ns <= 6 * TF_MAX_EDITS tensors [Kl, S, D] (frame stride free, rows dense-strided, same dtype) -> the all-to-all send
     buffer [W, Kl, ns, S, D // W]: head group w of every slab, frame-major (tf_head_pack, one launch)."""
     dev = _need_gpu(*slabs)
     lib = _lib.load()
@@ -494,7 +561,7 @@ def head_pack(slabs: Sequence[torch.Tensor], W: int, out: Optional[torch.Tensor]
 
 def head_unpack(recv: torch.Tensor, dsts: Sequence[torch.Tensor]) -> None:
     """recv [W, Kl, nb, S, hd] (what the second all-to-all delivers) -> dsts[b][f, s, w*hd:(w+1)*hd], nb tensors
-    [Kl, S, W*hd] (tf_head_unpack, one launch)."""
+    [Kl, S, W*hd], nb <= 6 * TF_MAX_EDITS (tf_head_unpack, one launch)."""
     dev = _need_gpu(recv, *dsts)
     lib = _lib.load()
     W, Kl, nb, S, hd = recv.shape

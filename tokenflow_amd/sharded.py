@@ -137,6 +137,11 @@ class FrameShard:
     # model (not measured without), level 3 a tie; a step with this threshold equals the forced "bank_runs" step within the spread.
     BANK_RUNS_MIN_S = 1024
 
+    # Multi-edit batches (`hooks.register_edits`): every method below takes n_edits (and inject_mask where injection is an
+    # argument); B = 1 + 2E branches [source | uncond_1 | cond_1 | ...].  Per block the collectives and the launches stay at
+    # the single-edit count -- only their payload grows with E; n_edits = 1 issues exactly the single-edit ops.
+    supports_edits = True
+
     def __init__(self, K: int, group: Optional[dist.ProcessGroup] = None, comm=None,
                  attn_split: Optional[bool] = None, halo_group: Optional[dist.ProcessGroup] = None, halo_comm=None,
                  bank_runs: Optional[bool] = None):
@@ -281,8 +286,18 @@ class FrameShard:
             slabs = [k3[0], v3[1], v3[2]] if inject else [k3[1], k3[2], v3[1], v3[2]]
         else:
             slabs = [k3[0], v3[0], v3[1], v3[2]] if inject else [k3[0], k3[1], k3[2], v3[0], v3[1], v3[2]]
+        rp = self._gather_slabs(slabs, "runs" if peers_only else "bank")
+        if peers_only:
+            return ((rp[0:1], rp[1:3]) if inject else (rp[0:2], rp[2:4])) + (k3, v3)
+        return (rp[0:1], rp[1:4]) if inject else (rp[0:3], rp[3:6])
+
+    def _gather_slabs(self, slabs, tag: str):
+        """ONE pack (W = 1) and ONE all-gather of `slabs` ([Kl,S,D] views sharing a token stride) of the local keyframes:
+        returns the [len(slabs), K, S, D] view of the receive buffer (global frame order).  The collective of `_bank_gather`."""
+        Kl, K, W = self.Kl, self.K, self.world
+        _, S, D = slabs[0].shape
+        dev, dt = slabs[0].device, slabs[0].dtype
         ns = len(slabs)
-        tag = "runs" if peers_only else "bank"
         send = ops.head_pack(slabs, 1, out=self._buf(tag + "_send", (1, Kl, ns, S, D), dt, dev)).view(Kl, ns * S * D)
         recv = self._buf(tag + "_recv", (K, ns * S * D), dt, dev)
         comm = getattr(self, "comm", None)
@@ -316,28 +331,32 @@ class FrameShard:
                 recv.copy_(dst)
         else:
             self._side([recv, send], lambda st: comm.allgather_rows(send, recv, self.counts, stream=st)).wait()
-        rp = recv.view(K, ns, S, D).permute(1, 0, 2, 3)        # [ns, K, S, D] views: frame stride ns*S*D
-        if peers_only:
-            return ((rp[0:1], rp[1:3]) if inject else (rp[0:2], rp[2:4])) + (k3, v3)
-        return (rp[0:1], rp[1:4]) if inject else (rp[0:3], rp[3:6])
+        return recv.view(K, ns, S, D).permute(1, 0, 2, 3)        # [ns, K, S, D] views: frame stride ns*S*D
 
-    def auto_mode(self, heads: int, S: int) -> str:
+    def auto_mode(self, heads: int, S: int, n_edits: int = 1) -> str:
         """Exchange pattern of the pivotal pass for one block.  "heads" moves the least data (under 8 local slabs
         per rank whatever W) and is the choice wherever the block has real work; it needs heads % W == 0.  "bank"
         is ONE collective and ONE attention call instead of two collectives, a pack, an unpack and two calls: the
         choice where a block is a few tens of microseconds of work (S <= 64: the mid block) and the exchange is
         latency-, not volume-bound -- and the only one when the heads do not divide over the ranks."""
         mode = "bank" if (heads % self.world or S <= 64) else "heads"
-        if mode == "bank" and getattr(self, "bank_runs", False) and S >= self.BANK_RUNS_MIN_S:
+        if mode == "bank" and getattr(self, "bank_runs", False) and S >= self.BANK_RUNS_MIN_S and n_edits == 1:
             return "bank_runs"     # opt-in (bank_runs=True / TOKENFLOW_SHARD_BANK_RUNS=1): the bank in runs, see the module text
         return mode
 
     def pivotal_attention(self, q_local, k_local, v_local, heads: int, scale: float, inject: bool,
-                          mode: Optional[str] = None, out4: Optional[torch.Tensor] = None):
+                          mode: Optional[str] = None, out4: Optional[torch.Tensor] = None, n_edits: int = 1,
+                          inject_mask: Optional[int] = None):
         """Extended attention for the local keyframes against all K keyframes -> [3*Kl,S,D].
         mode: "heads" | "bank" | "bank_runs" | None (= `auto_mode`, chosen per block).
         out4: a [3,Kl,S,D] view (dense frames, free branch stride) the result is written into in place -- the
-        keyframe slots 1.. of a halo-extended buffer (`ext_alloc`); returned as is."""
+        keyframe slots 1.. of a halo-extended buffer (`ext_alloc`); returned as is.
+        n_edits = E > 1: a multi-edit batch, tensors [B*Kl,S,D] / out4 [B,Kl,S,D] with B = 1 + 2E; inject_mask = the
+        injection state per edit (bit e = edit e uses the source's q and k; None = `inject` for every edit).  Modes "heads"
+        and "bank"; the slices of edit e equal the single-edit pass on [source | uncond_e | cond_e] bit for bit in the
+        one-pass form."""
+        if n_edits != 1:
+            return self._pivotal_edits(q_local, k_local, v_local, heads, scale, inject, mode, out4, int(n_edits), inject_mask)
         if self.world == 1:
             # the same mode as a rank of a larger world: a world-1 shard equals a world-W shard bit for bit by default.
             # COST: with attn_split unset this is the bit-stable mode (no_split), which gives up the single-GPU default's
@@ -354,6 +373,95 @@ class FrameShard:
         if mode == "bank_runs":
             return self._pivotal_bank_runs(q_local, k_local, v_local, heads, scale, inject, out4)
         return self._pivotal_bank(q_local, k_local, v_local, heads, scale, inject, out4)
+
+    # ------------------------------------------------------------------ pivotal pass of a multi-edit batch
+    def _pivotal_edits(self, q_local, k_local, v_local, heads, scale, inject, mode, out4, E, inject_mask):
+        B = 1 + 2 * E
+        if inject_mask is None:
+            mask = (1 << E) - 1 if inject else 0
+        else:
+            mask = int(inject_mask)
+            if inject or mask < 0 or mask >> E:
+                raise ValueError(f"FrameShard.pivotal_attention: inject_mask {mask:#x} for {E} edits (bits below n_edits; "
+                                 f"`inject` must be False beside a mask)")
+        if self.world == 1:
+            out = None if out4 is None else out4.view(q_local.shape)
+            return ops.ext_attn_edits(q_local, k_local, v_local, heads, scale, False, E, out=out,
+                                      no_split=not self.attn_split, inject_mask=mask)
+        if mode is None:
+            mode = self.auto_mode(heads, q_local.shape[1], E)
+        if mode == "bank_runs":
+            raise ValueError("FrameShard: the \"bank_runs\" pattern has no multi-edit form (use \"bank\" or \"heads\")")
+        _, S, D = q_local.shape
+        Kl = self.Kl
+
+        def frames(t):     # [B*Kl, S, D] (token stride free) -> [B, Kl, S, D] view
+            if t.stride(2) != 1 or t.stride(0) != S * t.stride(1):
+                t = t.contiguous()
+            return t.view(B, Kl, S, D) if t.is_contiguous() else t.unflatten(0, (B, Kl))
+        q4, k4, v4 = frames(q_local), frames(k_local), frames(v_local)
+        if not (q4.stride(2) == k4.stride(2) == v4.stride(2)):
+            q4, k4, v4 = (t.contiguous() for t in (q4, k4, v4))
+        out = torch.empty(B, Kl, S, D, dtype=q4.dtype, device=q4.device) if out4 is None else out4
+        # the compact q / k layout of tf_ext_attn_fwd_edits_part: the source slot where some edit injects, then the slots of
+        # the edits that do not; b0 = the first slot that exists
+        slots = ([0] if mask else []) + [b for e in range(E) if not (mask >> e) & 1 for b in (1 + 2 * e, 2 + 2 * e)]
+        b0 = 0 if mask else 1
+        if mode == "heads":
+            self._pivotal_heads_edits(q4, k4, v4, out, heads, scale, E, mask, slots, b0)
+        else:
+            self._pivotal_bank_edits(q4, k4, v4, out, heads, scale, E, mask, slots, b0)
+        return out.view(B * Kl, S, D) if out4 is None else out4
+
+    def _pivotal_heads_edits(self, q4, k4, v4, out, heads, scale, E, mask, slots, b0):
+        """`_pivotal_heads` for E edits: ONE pack of [q slots | k slots | v_1 .. v_2E] (2 * len(slots) + 2E slabs), ONE first
+        all-to-all, the bank part of every edit on the receive buffer in place (`ops.ext_attn_edits_views`, compact q / k),
+        ONE second all-to-all of [K][2E][S][hd], ONE unpack into the 2E bank slabs of `out`; the source branch of the
+        rank's own frames beside the first exchange."""
+        W, Kl, K = self.world, self.Kl, self.K
+        B, _, S, D = q4.shape
+        if heads % W:
+            raise ValueError(f"{heads} heads do not divide over {W} ranks")
+        hd, dev, dt = D // W, q4.device, q4.dtype
+        even, ns_ = self.even, not self.attn_split
+        nq = len(slots)
+        slabs = [q4[b] for b in slots] + [k4[b] for b in slots] + [v4[b] for b in range(1, B)]
+        ns = len(slabs)
+        send = ops.head_pack(slabs, W, out=self._buf("send", (W, Kl, ns, S, hd), dt, dev))
+        recv = self._buf("recv", (K, ns, S, hd), dt, dev)
+        work = self._a2a(recv.view(K, -1), send.view(W * Kl, -1),
+                         None if even else self.counts, None if even else [Kl] * W, async_op=True)
+        src_done = None
+        if q4.is_cuda and getattr(self, "src_aux", False):
+            src_done = self._on_aux(dev, [q4, k4, v4, out], lambda st: ops.ext_attn_edits_views(
+                q4[0:1], k4[0:1], v4[0:1], out[0:1], heads, scale, E, mask, "source", no_split=ns_, stream=st))
+        else:
+            ops.ext_attn_edits_views(q4[0:1], k4[0:1], v4[0:1], out[0:1], heads, scale, E, mask, "source", no_split=ns_)
+        work.wait()
+        rp = recv.permute(1, 0, 2, 3)                                   # [ns, K, S, hd] view
+        send2 = self._buf("send2", (K, B - 1, S, hd), dt, dev)        # [frame][uncond_1|cond_1|...]: rows of rank w's run -> w
+        o4 = send2.permute(1, 0, 2, 3)                                  # [2E, K, S, hd] view = branches 1 ..
+        ops.ext_attn_edits_views(rp[0:nq], rp[nq:2 * nq], rp[2 * nq:], o4, heads // W, scale, E, mask, "bank", True,
+                                 branch0=(b0, b0, 1, 1), no_split=ns_)
+        recv2 = self._buf("recv2", (W, Kl, B - 1, S, hd), dt, dev)
+        self._a2a(recv2.view(W * Kl, -1), send2.view(K, -1),
+                  None if even else [Kl] * W, None if even else self.counts)
+        ops.head_unpack(recv2, [out[b] for b in range(1, B)])
+        if src_done is not None:
+            src_done.wait()
+
+    def _pivotal_bank_edits(self, q4, k4, v4, out, heads, scale, E, mask, slots, b0):
+        """`_pivotal_bank` for E edits: ONE gather of exactly the compact k slots and the 2E value slabs (the source branch's
+        v and every q stay at home), the bank part on the gathered buffer in place, the source part on the local tensors."""
+        Kl, K = self.Kl, self.K
+        B, _, S, D = q4.shape
+        nq, ns_ = len(slots), not self.attn_split
+        rp = self._gather_slabs([k4[b] for b in slots] + [v4[b] for b in range(1, B)], "bank_e")
+        # q in the same compact layout: the dense tensor is that layout already unless the mask is mixed
+        qc = q4[b0:] if len(slots) in (1, B - 1) else q4[slots]
+        ops.ext_attn_edits_views(qc, rp[0:nq], rp[nq:], out[1:], heads, scale, E, mask, "bank", True,
+                                 branch0=(b0, b0, 1, 1), q_frame0=self.kf0, no_split=ns_)
+        ops.ext_attn_edits_views(q4[0:1], k4[0:1], v4[0:1], out[0:1], heads, scale, E, mask, "source", no_split=ns_)
 
     def bank_runs_of_rank(self):
         """The runs of the bank this rank computes in the "bank_runs" form, in SLOT order: its own keyframes, the frames
@@ -468,20 +576,24 @@ class FrameShard:
         return out.view(3 * Kl, S, D) if out4 is None else out4
 
     # ------------------------------------------------------------------ pivotal pass of one block, in place
-    def ext_alloc(self, S: int, D: int, dtype: torch.dtype, device):
+    def ext_alloc(self, S: int, D: int, dtype: torch.dtype, device, n_edits: int = 1):
         """Per-block state of the propagation, halo slot included: (pivots [Kl+o,S,D], inverse norms [Kl+o,S] fp32,
         cached attention output [3,Kl+o,S,D]) with o = 1 when there is a left neighbour to hear from (world > 1), else
         0.  The producers write the local keyframes straight into slots o.. (norm1 -> pivots and inverse norms, the
-        attention -> its output): no staging copy on either side of the halo exchange."""
+        attention -> its output): no staging copy on either side of the halo exchange.  n_edits = E: the cached attention
+        output holds all 1 + 2E branches, [1+2E,Kl+o,S,D]."""
         o = 1 if self.world > 1 else 0
         Kl = self.Kl
         return (torch.empty(Kl + o, S, D, dtype=dtype, device=device),
                 torch.empty(Kl + o, S, dtype=torch.float32, device=device),
-                torch.empty(3, Kl + o, S, D, dtype=dtype, device=device))
+                torch.empty(1 + 2 * int(n_edits), Kl + o, S, D, dtype=dtype, device=device))
 
     def pivotal_block(self, q_local, k_local, v_local, heads: int, scale: float, inject: bool, ext,
-                      mode: Optional[str] = None, inv_norm: bool = False):
-        """The pivotal pass of one block on this rank, for the reference's call order (one pivotal pass over all
+                      mode: Optional[str] = None, inv_norm: bool = False, n_edits: int = 1,
+                      inject_mask: Optional[int] = None):
+        """n_edits / inject_mask: as `pivotal_attention`; `ext` from `ext_alloc(..., n_edits=)`; the ONE grouped exchange
+        carries the last keyframe of all 1 + 2E branches of the attention output.
+        The pivotal pass of one block on this rank, for the reference's call order (one pivotal pass over all
         blocks, then the chunk passes): `ext` = `ext_alloc(...)` whose pivot / inverse-norm slots o.. the caller has
         filled.  The attention writes its output into ext's slots o.. in place, then ONE grouped neighbour exchange
         carries the last local keyframe's pivots, inverse norms and attention output to slot 0 of rank r+1 (it has the
@@ -496,32 +608,39 @@ class FrameShard:
         S, D = piv.shape[1:]
         if inv_norm:
             ops.pivot_inv_norm(piv[o:], out=inv[o:])
-        self.pivotal_attention(q_local, k_local, v_local, heads, scale, inject, mode=mode, out4=kfo[:, o:])
+        nbr = 1 + 2 * int(n_edits)
+        if n_edits == 1:
+            self.pivotal_attention(q_local, k_local, v_local, heads, scale, inject, mode=mode, out4=kfo[:, o:])
+        else:
+            self.pivotal_attention(q_local, k_local, v_local, heads, scale, inject, mode=mode, out4=kfo[:, o:],
+                                   n_edits=n_edits, inject_mask=inject_mask)
         reqs = []
         if self.world > 1:
-            reqs = self._p2p([piv[-1], inv[-1], kfo[0, -1], kfo[1, -1], kfo[2, -1]],
-                             [piv[0], inv[0], kfo[0, 0], kfo[1, 0], kfo[2, 0]])
-        return piv, inv, kfo.view(3 * (Kl + o), S, D), reqs
+            reqs = self._p2p([piv[-1], inv[-1]] + [kfo[b, -1] for b in range(nbr)],
+                             [piv[0], inv[0]] + [kfo[b, 0] for b in range(nbr)])
+        return piv, inv, kfo.view(nbr * (Kl + o), S, D), reqs
 
-    def halo_block(self, piv_ext: torch.Tensor, inv_ext: torch.Tensor, kfo_ext: torch.Tensor):
+    def halo_block(self, piv_ext: torch.Tensor, inv_ext: torch.Tensor, kfo_ext: torch.Tensor, n_edits: int = 1):
         """ONE grouped neighbour exchange on halo-extended per-block state the producers have written in place
         (`ext_alloc` layout: slot 0 = the left neighbour's last keyframe): the last local keyframe's pivots, inverse
         norms and attention output go to rank r+1, the neighbour's arrive in slot 0.  Returns the pending requests
         (`halo_wait`).  What `pivotal_block` issues behind its attention; the hook path calls it behind `to_out`."""
         if self.world == 1:
             return []
-        return self._p2p([piv_ext[-1], inv_ext[-1], kfo_ext[0, -1], kfo_ext[1, -1], kfo_ext[2, -1]],
-                         [piv_ext[0], inv_ext[0], kfo_ext[0, 0], kfo_ext[1, 0], kfo_ext[2, 0]])
+        nbr = 1 + 2 * int(n_edits)       # kfo_ext [1+2E, Kl+1, S, D]: the last keyframe of every branch in the same exchange
+        return self._p2p([piv_ext[-1], inv_ext[-1]] + [kfo_ext[b, -1] for b in range(nbr)],
+                         [piv_ext[0], inv_ext[0]] + [kfo_ext[b, 0] for b in range(nbr)])
 
     # ------------------------------------------------------------------ halo for propagation
-    def exchange_halo(self, pivots_local: torch.Tensor, inv_local: torch.Tensor, kf_out_local: torch.Tensor):
+    def exchange_halo(self, pivots_local: torch.Tensor, inv_local: torch.Tensor, kf_out_local: torch.Tensor,
+                      n_edits: int = 1):
         """pivots_local [Kl,S,D], inv_local [Kl,S], kf_out_local [3*Kl,S,D] (this rank's keyframes).
         Returns the same three with ONE extra leading keyframe slot = the previous rank's last
         keyframe (unset and unread on rank 0: global chunk 0 matches a single keyframe, 331-333)."""
         h = self.halo_start(pivots_local, inv_local)
-        return self.halo_finish(h, kf_out_local)
+        return self.halo_finish(h, kf_out_local, n_edits=n_edits)
 
-    def halo_start(self, pivots_local: torch.Tensor, inv_local: torch.Tensor):
+    def halo_start(self, pivots_local: torch.Tensor, inv_local: torch.Tensor, n_edits: int = 1):
         """First half of the halo exchange: the pivot features and inverse norms of the last local keyframe go to
         rank r+1.  They exist as soon as norm1 has run, BEFORE the attention, so this is issued first and travels
         under the attention; `halo_finish` then sends the attention output."""
@@ -537,7 +656,7 @@ class FrameShard:
         reqs = self._p2p([pivots_local[-1], inv_local[-1]], [piv[0], inv[0]])
         return (piv, inv, reqs)
 
-    def halo_finish(self, handle, kf_out_local: torch.Tensor, wait: bool = True):
+    def halo_finish(self, handle, kf_out_local: torch.Tensor, wait: bool = True, n_edits: int = 1):
         """Second half: the attention output of the last local keyframe to rank r+1.  wait=False returns the
         pending requests as a 4th element (call `halo_wait`): the propagation of the local chunks 1.. does not read
         the halo slot and can be issued before."""
@@ -546,12 +665,13 @@ class FrameShard:
             return (piv, inv, kf_out_local) if wait else (piv, inv, kf_out_local, [])
         Kl = self.Kl
         S, D = kf_out_local.shape[1:]
-        kf3 = kf_out_local.view(3, Kl, S, D)
-        kfo = torch.empty(3, Kl + 1, S, D, dtype=kf_out_local.dtype, device=kf_out_local.device)
+        nbr = 1 + 2 * int(n_edits)       # kf_out_local [(1+2E)*Kl, S, D]
+        kf3 = kf_out_local.view(nbr, Kl, S, D)
+        kfo = torch.empty(nbr, Kl + 1, S, D, dtype=kf_out_local.dtype, device=kf_out_local.device)
         kfo[:, 1:].copy_(kf3)
         # no staging copies: every message is a contiguous view (the attention output travels as one message per branch)
-        reqs = list(reqs) + self._p2p([kf3[0, -1], kf3[1, -1], kf3[2, -1]], [kfo[0, 0], kfo[1, 0], kfo[2, 0]])
-        res = (piv, inv, kfo.view(3 * (Kl + 1), S, D))
+        reqs = list(reqs) + self._p2p([kf3[b, -1] for b in range(nbr)], [kfo[b, 0] for b in range(nbr)])
+        res = (piv, inv, kfo.view(nbr * (Kl + 1), S, D))
         if not wait:
             return res + (reqs,)
         self.halo_wait(reqs)
@@ -592,25 +712,45 @@ class FrameShard:
 
     # ------------------------------------------------------------------ propagation pass
     def propagate(self, j: int, tgt: torch.Tensor, residual: torch.Tensor, piv_ext, inv_ext, kf_out_ext,
-                  w: torch.Tensor, n: int, out_dtype_two: torch.dtype = torch.float32):
+                  w: torch.Tensor, n: int, out_dtype_two: torch.dtype = torch.float32, n_edits: int = 1):
         """Local chunk j (global chunk kf0 + j): NN search + gather/blend/residual.
-        tgt [n*S, D] 16-bit source-branch features, residual [3n,S,D]."""
+        tgt [n*S, D] 16-bit source-branch features, residual [3n,S,D] ([(1+2E)n,S,D] with n_edits = E: one search, one
+        gather over all branches)."""
         c = self.kf0 + j
         o = 1 if self.world > 1 else 0                   # halo slot offset
         ids = [j + o] if c == 0 else [j + o, j + o - 1]  # slots of keyframes [c, c-1] (tokenflow_utils.py:331-333)
         blend_dtype = out_dtype_two if len(ids) == 2 else kf_out_ext.dtype
         out_dtype = torch.promote_types(blend_dtype, residual.dtype) if residual is not None else blend_dtype
+        if n_edits != 1:
+            return ops.propagate_chunks_edits(tgt, piv_ext, inv_ext, kf_out_ext, w if len(ids) == 2 else None, n, 1, j + o,
+                                              c == 0, residual, out_dtype, n_edits)
         return ops.propagate(tgt, piv_ext, inv_ext, ids, kf_out_ext, w if len(ids) == 2 else None, n, residual,
                              out_dtype)
 
     def propagate_all(self, tgt_all: torch.Tensor, residual_all: torch.Tensor, piv_ext, inv_ext, kf_out_ext,
-                      w: torch.Tensor, n: int, out_dtype: torch.dtype = torch.float32, halo_reqs=None):
+                      w: torch.Tensor, n: int, out_dtype: torch.dtype = torch.float32, halo_reqs=None, n_edits: int = 1):
         """ALL local chunks (tf_nn_gather_blend_chunks): tgt_all [Kl*n*S, D] chunk-major, residual_all
         [3*Kl*n, S, D] (frames chunk-major inside each branch).  Same results as Kl calls of `propagate`, bit for
         bit; the one-keyframe chunk 0 of the video (rank 0) is rounded to the dtype its own call would produce.
         halo_reqs (from `halo_finish(wait=False)`): the local chunks 1.. read no halo slot and are issued FIRST,
         the first local chunk after the halo has landed; returns (first chunk [3n,S,D], rest [3(Kl-1)n,S,D] or None)."""
         o = 1 if self.world > 1 else 0
+        if n_edits != 1:     # [(1+2E)*Kl*n, S, D] residual and result; one search and one gather over all branches per call
+            E, nbr = int(n_edits), 1 + 2 * int(n_edits)
+            if halo_reqs is None:
+                return ops.propagate_chunks_edits(tgt_all, piv_ext, inv_ext, kf_out_ext, w, n, self.Kl, o, self.kf0 == 0,
+                                                  residual_all, out_dtype, E)
+            Kl, S, D = self.Kl, piv_ext.shape[1], piv_ext.shape[2]
+            nS = n * S
+            res = residual_all.view(nbr, Kl, n, S, D)
+            rest = None
+            if Kl > 1:
+                rest = ops.propagate_chunks_edits(tgt_all[nS:], piv_ext, inv_ext, kf_out_ext, w, n, Kl - 1, o + 1, False,
+                                                  res[:, 1:].reshape(nbr * (Kl - 1) * n, S, D), out_dtype, E)
+            self.halo_wait(halo_reqs)
+            first = self.propagate(0, tgt_all[:nS], res[:, 0].reshape(nbr * n, S, D), piv_ext, inv_ext, kf_out_ext, w, n,
+                                   n_edits=E)
+            return first, rest
         if halo_reqs is None:
             return ops.propagate_chunks(tgt_all, piv_ext, inv_ext, kf_out_ext, w, n, self.Kl, o, self.kf0 == 0,
                                         residual_all, out_dtype)
@@ -648,7 +788,9 @@ class NativeShard(FrameShard):
     bit for bit (same kernels, same buffers' layouts).  `comm` / `halo_comm`: `tokenflow_amd.comm.HipComm` objects (RCCL
     through the C ABI; a second communicator lets the halo of one block travel beside the exchanges of the next).
     Only the in-place two-pass API (`ext_alloc`, `pivotal_block`, `propagate_all(..., halo_reqs=)`) goes native; the
-    other methods are `FrameShard`'s own on the same communicator."""
+    other methods are `FrameShard`'s own on the same communicator.  tf_rank_pivotal runs one edit: no multi-edit batches."""
+
+    supports_edits = False
 
     def __init__(self, K: int, comm, halo_comm=None, attn_split: Optional[bool] = None, bank_runs: Optional[bool] = None):
         super().__init__(K, comm=comm, attn_split=attn_split, halo_comm=halo_comm, bank_runs=bank_runs)

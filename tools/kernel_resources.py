@@ -23,6 +23,6 @@ for line in out.splitlines():
 for r in rows:
     name = subprocess.run(["c++filt", r["name"]], capture_output=True, text=True).stdout.strip()
     name = re.sub(r"\(anonymous namespace\)::", "", name)
-    name = re.sub(r"\(.*", "", name)[:60]
-    print(f"{name:60s} vgpr {r.get('VGPRs', 0):4d} agpr {r.get('AGPRs', 0):4d} sgpr {r.get('TotalSGPRs', 0):4d} "
+    name = re.sub(r"\(.*", "", name)[:84]
+    print(f"{name:84s} vgpr {r.get('VGPRs', 0):4d} agpr {r.get('AGPRs', 0):4d} sgpr {r.get('TotalSGPRs', 0):4d} "
           f"scratch {r.get('ScratchSize', 0):4d} vspill {r.get('VGPRs Spill', 0):3d} occ {r.get('Occupancy', 0)}")
