@@ -696,6 +696,61 @@ TF_API int tf_rank_pivotal(tf_rank* rk, const void* q, const void* k, const void
                     int slot, void* ws, size_t ws_bytes, void* stream);
 TF_API int tf_rank_halo_wait(tf_rank* rk, int slot, void* stream);
 
+/* ------------------------------------------------------------------------
+ * The rank executor for a MULTI-EDIT batch (additive to ABI 11): tf_rank_pivotal for B = 1 + 2*n_edits branches
+ * [source | uncond_1 | cond_1 | ...]  --  the native form of `FrameShard._pivotal_heads_edits` / `_pivotal_bank_edits`
+ * (tokenflow_amd/sharded.py), with the same buffer layouts: on the same transport both fill every buffer with the same bits.
+ *
+ *   q, k, v   : the rank's local [B, Kl, S, H*Dh] projections; the 8 strides of tf_rank_pivotal
+ *   kfo_ext   : [B, Kl+o, S, H*Dh] ([B, Kl, ...] under TF_RANK_NO_HALO); piv_ext, inv_ext, slot, TF_RANK_INV_NORM,
+ *               TF_RANK_NO_HALO and tf_rank_halo_wait as for tf_rank_pivotal
+ *   inject_mask: the injection state per edit, as tf_ext_attn_fwd_edits_masked (bit e = edit e uses the source's q and k).
+ *               TF_ATTN_INJECT or a part flag in `flags`, a mask bit at or above n_edits, n_edits outside 1 .. TF_MAX_EDITS,
+ *               TF_RANK_BANK_RUNS with n_edits > 1 (no multi-edit form exists), TF_RANK_HEADS with H % W != 0: TF_ERR_SHAPE;
+ *               a null pointer: TF_ERR_NULL.  All of that is checked before anything touches the device.
+ *   ws        : tf_rank_pivotal_edits_workspace_bytes -- ONE size for both modes: the exchange buffers at their largest slab
+ *               counts (6E slabs in the heads form, 4E in the bank form), the staging region of the compact q, and one
+ *               attention workspace (tf_ext_attn_edits_workspace_bytes) each for the bank and the source part, which may run
+ *               concurrently.
+ *
+ * n_edits = 1 IS tf_rank_pivotal with TF_ATTN_INJECT set iff the mask is 1: the same launches, the same bits.
+ * One rank (comm = NULL): the inverse norms if asked, then tf_ext_attn_fwd_edits_masked straight into kfo_ext.
+ * W > 1.  Compact slots: slot 0 is the source if any edit injects (any = 1), then (uncond, cond) of each of the n_non
+ * non-injecting edits in ascending order -- the qk_compact layout of tf_ext_attn_fwd_edits_part.
+ *   TF_RANK_HEADS  ONE pack of [q slots | k slots | v_1 .. v_2E] (2 (any + 2 n_non) + 2E slabs; the inverse norms ride in the
+ *                  same launch), ONE tf_all_to_all_rows, the bank part of every edit on the receive buffer in place
+ *                  (tf_ext_attn_fwd_edits_part: TF_ATTN_BANK_ONLY, qk_compact, H / W heads, all K frames) into the send
+ *                  buffer [K][2E][S][H*Dh/W] of ONE second all-to-all, ONE tf_head_unpack into the 2E bank slabs of kfo_ext.
+ *                  The source part of the rank's own frames (TF_ATTN_SOURCE_ONLY on the local tensors) runs on the auxiliary
+ *                  compute stream where it is a streaming launch -- forked behind the pack, in front of the first exchange,
+ *                  joined in front of the second; TOKENFLOW_RANK_SRC_AUX=0 keeps it in line -- and in line behind the bank
+ *                  part where it takes the fused small-problem kernel.  That decision uses ceil(K / W) for Kl: it is the same
+ *                  on every rank of the block.
+ *   TF_RANK_BANK   ONE pack (W = 1) of the compact k slots and the 2E value slabs ((any + 2 n_non) + 2E; the source's v and
+ *                  every q stay at home), ONE tf_allgather_rows, the bank part on the gathered buffer (q_frame0 = the rank's
+ *                  first keyframe, Kq = Kl, qk_compact), the source part on the local tensors.  A MIXED mask first copies
+ *                  the compact q slots into the staging region (the pack kernel with W = 1, one launch); a uniform mask
+ *                  reads q in place.
+ *   Halo           ONE grouped tf_sendrecv_pivot of 2 + B messages: the pivots, the B branches of kfo_ext and the inverse
+ *                  norms of the last local keyframe to slot 0 of rank r+1.
+ *
+ * tf_rank_pivotal_edits_plan (host only: no device, stream or communicator): the sequence ONE call issues on `rank` of
+ * `world` ranks over K keyframes, ';'-separated, recorded by the executing code itself:
+ *   pack[ns=N] (pack+inv[ns=N] under TF_RANK_INV_NORM); qcompact[ns=N] where it happens; a2a[slabs=N] or gather[slabs=N]; the
+ *   tokens of tf_ext_attn_edits_part_plan for the bank part, then for the source part (the source part is listed there also
+ *   where it runs on the auxiliary stream); a2a[slabs=2E]; unpack[nb=2E]; halo[n=2+B] (absent under TF_RANK_NO_HALO and for
+ *   one rank).  One rank: inv_norm under TF_RANK_INV_NORM, then the tokens of tf_ext_attn_edits_masked_plan.  n_edits = 1: the
+ *   sequence of tf_rank_pivotal in the same tokens (its attention tokens are those of tf_ext_attn_plan).
+ * Returns the number of tokens, or a negative TF_ERR_* code.
+ * ------------------------------------------------------------------------ */
+TF_API size_t tf_rank_pivotal_edits_workspace_bytes(const tf_rank* rk, int S, int H, int Dh, int n_edits, int dtype);
+TF_API int tf_rank_pivotal_edits(tf_rank* rk, const void* q, const void* k, const void* v, const int64_t* strides,
+                          void* piv_ext, float* inv_ext, void* kfo_ext, int S, int H, int Dh, float scale, int flags,
+                          int dtype, int mode, int slot, int n_edits, unsigned inject_mask,
+                          void* ws, size_t ws_bytes, void* stream);
+TF_API int tf_rank_pivotal_edits_plan(int world, int rank, int K, int S, int H, int Dh, int n_edits, unsigned inject_mask,
+                               int mode, int flags, int dtype, char* buf, size_t len);
+
 #ifdef __cplusplus
 }
 #endif

@@ -120,6 +120,11 @@ _SIGNATURES = {
     "tf_rank_pivotal": (_c.c_int, [_c.c_void_p] * 8 + [_c.c_int] * 3 + [_c.c_float] + [_c.c_int] * 4 +
                         [_c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "tf_rank_halo_wait": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p]),
+    # the rank executor for a multi-edit batch (additive to ABI 11)
+    "tf_rank_pivotal_edits_workspace_bytes": (_c.c_size_t, [_c.c_void_p] + [_c.c_int] * 5),
+    "tf_rank_pivotal_edits": (_c.c_int, [_c.c_void_p] * 8 + [_c.c_int] * 3 + [_c.c_float] + [_c.c_int] * 5 + [_c.c_uint] +
+                              [_c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "tf_rank_pivotal_edits_plan": (_c.c_int, [_c.c_int] * 7 + [_c.c_uint] + [_c.c_int] * 3 + [_c.c_char_p, _c.c_size_t]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -340,8 +340,10 @@ extern "C" int tf_sendrecv_pivot(tf_comm* comm, const void* const* send, const i
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const size_t eb = elem_bytes(dtype);
     if (comm->kind == COMM_HOOKS) {
-        int64_t sb[16], rbs[16];
-        TF_ARG(n_send <= 16 && n_recv <= 16, TF_ERR_SHAPE, "tf_sendrecv_pivot: more than 16 messages");
+        // the halo of a multi-edit block: pivots, inverse norms and the 1 + 2E branches of the attention output
+        constexpr int MAX_MSGS = 3 + 2 * TF_MAX_EDITS;
+        int64_t sb[MAX_MSGS], rbs[MAX_MSGS];
+        TF_ARG(n_send <= MAX_MSGS && n_recv <= MAX_MSGS, TF_ERR_SHAPE, "tf_sendrecv_pivot: more than %d messages", MAX_MSGS);
         for (int i = 0; i < n_send; ++i) sb[i] = send_elems[i] * (int64_t)eb;
         for (int i = 0; i < n_recv; ++i) rbs[i] = recv_elems[i] * (int64_t)eb;
         const int rc = comm->hooks.sendrecv(comm->hooks.user, send, sb, n_send, send_peer, recv, rbs, n_recv, recv_peer,

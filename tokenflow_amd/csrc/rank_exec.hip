@@ -69,6 +69,7 @@ namespace {
 // `to` continues after everything enqueued on `from` so far.  Events are reused: a wait captures the record that is
 // current when it is issued (HIP semantics), and 64 events outlast any hand-over of a block.
 int order(tf_rank* rk, hipStream_t from, hipStream_t to, const char* what) {
+    if (tf_plan_rec) return 0;   // plan recording: no streams to order
     hipEvent_t e = rk->next();
     TF_HIP(hipEventRecord(e, from), what);
     TF_HIP(hipStreamWaitEvent(to, e, 0), what);
@@ -130,6 +131,77 @@ Layout layout(const tf_rank* rk, int S, int H, int Dh, int dtype, int mode) {
     return L;
 }
 
+// ---- the steps of a pass behind the record switch of the plan query (tf_rank_pivotal_edits_plan): while a recorder is set
+//      on the calling thread every step appends its token and touches no device, stream or communicator -- the attention entry
+//      points do the same for their launches -- so the plan is recorded by the code that runs, not by a copy of it.
+int do_pack(const void* const* slabs, const int64_t* fss, int ns, void* send, int W, int Kl, int S, int hd, int64_t ld,
+            const void* piv, float* inv, int64_t rows, int D, int dtype, void* stream) {
+    if (piv ? tf_plan_note("pack+inv[ns=%d]", ns) : tf_plan_note("pack[ns=%d]", ns)) return 0;
+    return tf_head_pack_norm(slabs, fss, ns, send, W, Kl, S, hd, ld, 2, piv, inv, rows, D, dtype, stream);
+}
+int do_unpack(const void* recv, void* const* dsts, const int64_t* dfs, int nb, int W, int Kl, int S, int hd, int64_t ld,
+              void* stream) {
+    if (tf_plan_note("unpack[nb=%d]", nb)) return 0;
+    return tf_head_unpack(recv, dsts, dfs, nb, W, Kl, S, hd, ld, 2, stream);
+}
+int do_a2a(tf_comm* comm, const void* send, void* recv, const int64_t* send_rows, const int64_t* recv_rows, int slabs,
+           int64_t slab_elems, int dtype, void* stream) {
+    if (tf_plan_note("a2a[slabs=%d]", slabs)) return 0;
+    return tf_all_to_all_rows(comm, send, recv, send_rows, recv_rows, slabs * slab_elems, dtype, stream);
+}
+int do_gather(tf_comm* comm, const void* send, void* recv, const int64_t* rows, int slabs, int64_t slab_elems, int dtype,
+              void* stream) {
+    if (tf_plan_note("gather[slabs=%d]", slabs)) return 0;
+    return tf_allgather_rows(comm, send, recv, rows, slabs * slab_elems, dtype, stream);
+}
+int do_inv_norm(const void* piv, float* inv, int64_t rows, int D, int dtype, void* stream) {
+    if (tf_plan_note("inv_norm")) return 0;
+    return tf_pivot_inv_norm(piv, inv, rows, D, dtype, stream);
+}
+
+// TOKENFLOW_RANK_SRC_AUX=0: the source part in line on the caller's stream instead of the auxiliary compute stream
+bool src_aux_enabled() {
+    static const bool on = [] { const char* e = getenv("TOKENFLOW_RANK_SRC_AUX"); return !e || atoi(e) != 0; }();
+    return on;
+}
+
+// ---- neighbour halo: the last local keyframe's pivots, inverse norms and the `nbr` branches of the attention output -> slot 0
+//      of rank r+1, ONE grouped exchange of 2 + nbr messages on the halo stream (the entry point moves bytes: the 16-bit rows
+//      are counted as SD/2 four-byte elements next to the fp32 inverse norms; S*D is even, D being a multiple of 8)
+int halo_exchange(tf_rank* rk, unsigned short* piv, float* inv_ext, unsigned short* kfo, int nbr, int64_t o_bs, int64_t SD,
+                  int S, int slot, hipStream_t st, const char* fn) {
+    const int W = rk->world, Kl = rk->Kl;
+    const int to = rk->rank + 1 < W ? rk->rank + 1 : -1, from = rk->rank > 0 ? rk->rank - 1 : -1;
+    if (to < 0 && from < 0) return 0;
+    constexpr int MAXM = 3 + 2 * TF_MAX_EDITS;
+    const int n = 2 + nbr;
+    if (tf_plan_note("halo[n=%d]", n)) return 0;
+    if (const int rc = order(rk, st, rk->hs, fn)) return rc;
+    const void* snd[MAXM];
+    void* rcv[MAXM];
+    int64_t n32[MAXM];
+    snd[0] = piv + (int64_t)Kl * SD, rcv[0] = piv, n32[0] = SD / 2;
+    for (int b = 0; b < nbr; ++b)
+        snd[1 + b] = kfo + b * o_bs + (int64_t)Kl * SD, rcv[1 + b] = kfo + b * o_bs, n32[1 + b] = SD / 2;
+    snd[n - 1] = inv_ext + (int64_t)Kl * S, rcv[n - 1] = inv_ext, n32[n - 1] = S;
+    if (const int rc = tf_sendrecv_pivot(rk->halo_comm, snd, n32, n, to, rcv, n32, n, from, TF_F32, rk->hs)) return rc;
+    TF_HIP(hipEventRecord(rk->halo_done[slot], rk->hs), fn);
+    rk->halo_set[slot] = true;
+    return 0;
+}
+
+// contiguous runs of the K keyframes, the first K % W ranks hold one more (sharded.py)
+void partition(tf_rank* rk, int K, int world, int rank) {
+    rk->K = K, rk->world = world, rk->rank = rank;
+    int off = 0;
+    for (int r = 0; r < world; ++r) {
+        rk->counts[r] = K / world + (r < K % world ? 1 : 0);
+        if (r == rank) rk->kf0 = off;
+        off += rk->counts[r];
+    }
+    rk->Kl = rk->counts[rank];
+}
+
 }  // namespace
 
 extern "C" int tf_rank_create(tf_comm* comm, tf_comm* halo_comm, int K, tf_rank** out) {
@@ -144,14 +216,7 @@ extern "C" int tf_rank_create(tf_comm* comm, tf_comm* halo_comm, int K, tf_rank*
     TF_ARG(rk, TF_ERR_NULL, "tf_rank_create: out of memory");
     rk->comm = comm;
     rk->halo_comm = halo_comm ? halo_comm : comm;
-    rk->K = K, rk->world = world, rk->rank = rank;
-    int off = 0;
-    for (int r = 0; r < world; ++r) {   // contiguous runs, the first K % W ranks hold one more (sharded.py)
-        rk->counts[r] = K / world + (r < K % world ? 1 : 0);
-        if (r == rank) rk->kf0 = off;
-        off += rk->counts[r];
-    }
-    rk->Kl = rk->counts[rank];
+    partition(rk, K, world, rank);
     for (int i = 0; i < TF_RANK_SLOTS; ++i) rk->halo_set[i] = false, rk->halo_done[i] = nullptr;
     for (int i = 0; i < RING; ++i) rk->ring[i] = nullptr;
     hipError_t e = hipSuccess;
@@ -235,7 +300,7 @@ extern "C" int tf_rank_pivotal(tf_rank* rk, const void* q, const void* k, const 
     float* inv_loc = want_inv ? inv_ext + (int64_t)o * S : nullptr;
     if (W == 1) {
         if (want_inv)
-            if (const int rc = tf_pivot_inv_norm(piv_loc, inv_loc, (int64_t)Kl * S, (int)D, dtype, stream)) return rc;
+            if (const int rc = do_inv_norm(piv_loc, inv_loc, (int64_t)Kl * S, (int)D, dtype, stream)) return rc;
         const int64_t strides[9] = {q_bs, q_fs, k_bs, k_fs, v_bs, v_fs, o_bs, SD, ld_q};
         return tf_ext_attn_fwd_strided(q, k, v, out_loc, K, K, 0, S, H, Dh, ld, strides, scale, flags, dtype, ws, ws_bytes,
                                        stream);
@@ -267,8 +332,8 @@ extern "C" int tf_rank_pivotal(tf_rank* rk, const void* q, const void* k, const 
             slabs[4] = ve + v_bs, slabs[5] = ve + 2 * v_bs;
             fss[0] = fss[1] = q_fs, fss[2] = fss[3] = k_fs, fss[4] = fss[5] = v_fs;
         }
-        if (const int rc = tf_head_pack_norm(slabs, fss, ns, send, W, Kl, S, (int)hd, ld, 2, piv_loc, inv_loc,
-                                             (int64_t)Kl * S, (int)D, dtype, stream))
+        if (const int rc = do_pack(slabs, fss, ns, send, W, Kl, S, (int)hd, ld, piv_loc, inv_loc, (int64_t)Kl * S, (int)D,
+                                   dtype, stream))
             return rc;
         // ---- the two tensor sets of the attention: the bank branches on this rank's head group over all K frames, read
         //      from `recv` and written to `send2` in place (both laid out for the collectives), and the source branch of
@@ -314,18 +379,17 @@ extern "C" int tf_rank_pivotal(tf_rank* rk, const void* q, const void* k, const 
         // 128 workgroups, 61 us alone; 471 -> 440 us per level-0 block with the wire taken out,
         // profiles/r05_rank_step_srcaux_ab.txt).  Joined in front of the second exchange.  The collectives stay on the
         // caller's stream.  TOKENFLOW_RANK_SRC_AUX=0: in line on the caller's stream, behind the exchange.
-        static const bool src_aux = [] { const char* e = getenv("TOKENFLOW_RANK_SRC_AUX"); return !e || atoi(e) != 0; }();
         const int64_t src_strides[9] = {q_bs, q_fs, k_bs, k_fs, v_bs, v_fs, o_bs, SD, ld_q};
         auto source_branch = [&](hipStream_t on) {
             return tf_ext_attn_fwd_strided(q, k, v, out_loc, Kl, Kl, 0, S, H, Dh, ld, src_strides, scale,
                                            flags | TF_ATTN_SOURCE_ONLY, dtype, wsb + L.ws_src, L.ws_src_bytes, on);
         };
-        const bool fork = !plan.use && src_aux;
+        const bool fork = !plan.use && src_aux_enabled() && !tf_plan_rec;   // (a recorded plan lists the in-line order)
         if (fork) {
             if (const int rc = order(rk, st, rk->as, "tf_rank_pivotal")) return rc;
             if (const int rc = source_branch(rk->as)) return rc;
         }
-        if (const int rc = tf_all_to_all_rows(rk->comm, send, recv, own, cnt, ns * Shd, dtype, st)) return rc;
+        if (const int rc = do_a2a(rk->comm, send, recv, own, cnt, ns, Shd, dtype, st)) return rc;
         if (plan.use) {
             // small problems (the coarse levels, a rank's share of the middle ones): ONE launch for both sets behind
             // the exchange -- no V^T pre-passes, no split + merge pair, no separate source launch
@@ -343,10 +407,10 @@ extern "C" int tf_rank_pivotal(tf_rank* rk, const void* q, const void* k, const 
         }
         // ---- outputs back to the frame owners: on the caller's stream (nothing can run beside this exchange: the
         //      unpack and the next block need its result)
-        if (const int rc = tf_all_to_all_rows(rk->comm, send2, recv2, cnt, own, 2 * Shd, dtype, st)) return rc;
+        if (const int rc = do_a2a(rk->comm, send2, recv2, cnt, own, 2, Shd, dtype, st)) return rc;
         void* dsts[2] = {out_loc + o_bs, out_loc + 2 * o_bs};
         const int64_t dfs[2] = {SD, SD};
-        if (const int rc = tf_head_unpack(recv2, dsts, dfs, 2, W, Kl, S, (int)hd, D, 2, stream)) return rc;
+        if (const int rc = do_unpack(recv2, dsts, dfs, 2, W, Kl, S, (int)hd, D, stream)) return rc;
     } else if (mode == TF_RANK_BANK_RUNS) {
         // ---- the bank in runs: the local run starts before the gather lands (tf_ext_attn_run / tf_ext_attn_runs_merge)
         const Layout L = layout(rk, S, H, Dh, dtype, TF_RANK_BANK_RUNS);
@@ -368,8 +432,8 @@ extern "C" int tf_rank_pivotal(tf_rank* rk, const void* q, const void* k, const 
             slabs[0] = ke + k_bs, slabs[1] = ke + 2 * k_bs, slabs[2] = ve + v_bs, slabs[3] = ve + 2 * v_bs;
             fss[0] = fss[1] = k_fs, fss[2] = fss[3] = v_fs;
         }
-        if (const int rc = tf_head_pack_norm(slabs, fss, ns, send, 1, Kl, S, (int)D, ld, 2, piv_loc, inv_loc,
-                                             (int64_t)Kl * S, (int)D, dtype, stream))
+        if (const int rc = do_pack(slabs, fss, ns, send, 1, Kl, S, (int)D, ld, piv_loc, inv_loc, (int64_t)Kl * S, (int)D,
+                                   dtype, stream))
             return rc;
         // 2. the LOCAL run on the auxiliary compute stream, forked behind the pack and in FRONT of the gather: the source
         //    branch of the rank's frames and their bank branches against the rank's OWN keyframes, read from the caller's
@@ -388,7 +452,7 @@ extern "C" int tf_rank_pivotal(tf_rank* rk, const void* q, const void* k, const 
                 return rc;
         }
         // 3. the gather stays on the caller's stream: every collective of a communicator on ONE stream (see the heads form)
-        if (const int rc = tf_allgather_rows(rk->comm, send, recv, cnt, ns * SD, dtype, st)) return rc;
+        if (const int rc = do_gather(rk->comm, send, recv, cnt, ns, SD, dtype, st)) return rc;
         // 4. behind it the remote runs, read from the receive buffer [K][slabs][S][D] in place (bank branches only: the
         //    base of a tensor whose branch 0 does not exist lies one slab in front of its first slab)
         const int64_t fs_r = ns * SD;
@@ -423,11 +487,11 @@ extern "C" int tf_rank_pivotal(tf_rank* rk, const void* q, const void* k, const 
             slabs[3] = ve, slabs[4] = ve + v_bs, slabs[5] = ve + 2 * v_bs;
             fss[0] = fss[1] = fss[2] = k_fs, fss[3] = fss[4] = fss[5] = v_fs;
         }
-        if (const int rc = tf_head_pack_norm(slabs, fss, ns, send, 1, Kl, S, (int)D, ld, 2, piv_loc, inv_loc,
-                                             (int64_t)Kl * S, (int)D, dtype, stream))
+        if (const int rc = do_pack(slabs, fss, ns, send, 1, Kl, S, (int)D, ld, piv_loc, inv_loc, (int64_t)Kl * S, (int)D,
+                                   dtype, stream))
             return rc;
         // the gather on the caller's stream: the attention needs it at once (no stream hand-over, see above)
-        if (const int rc = tf_allgather_rows(rk->comm, send, recv, cnt, ns * SD, dtype, st)) return rc;
+        if (const int rc = do_gather(rk->comm, send, recv, cnt, ns, SD, dtype, st)) return rc;
         const int64_t fs_r = ns * SD;
         const E* kb = recv;
         const E* vb = recv + (inject ? 1 : 3) * SD;
@@ -438,19 +502,8 @@ extern "C" int tf_rank_pivotal(tf_rank* rk, const void* q, const void* k, const 
     }
 
     // ---- neighbour halo: the last local keyframe's pivots, inverse norms and attention output -> slot 0 of rank r+1
-    const int to = rk->rank + 1 < W ? rk->rank + 1 : -1, from = rk->rank > 0 ? rk->rank - 1 : -1;
-    if (!no_halo && (to >= 0 || from >= 0)) {
-        if (const int rc = order(rk, st, rk->hs, "tf_rank_pivotal")) return rc;
-        // ONE grouped exchange for the five messages (the entry point moves bytes: the 16-bit rows are counted as
-        // SD/2 four-byte elements next to the fp32 inverse norms; S*D is even, D being a multiple of 8)
-        const void* snd[5] = {piv + (int64_t)Kl * SD, kfo + (int64_t)Kl * SD, kfo + o_bs + (int64_t)Kl * SD,
-                              kfo + 2 * o_bs + (int64_t)Kl * SD, inv_ext + (int64_t)Kl * S};
-        void* rcv[5] = {piv, kfo, kfo + o_bs, kfo + 2 * o_bs, inv_ext};
-        const int64_t n32[5] = {SD / 2, SD / 2, SD / 2, SD / 2, S};
-        if (const int rc = tf_sendrecv_pivot(rk->halo_comm, snd, n32, 5, to, rcv, n32, 5, from, TF_F32, rk->hs)) return rc;
-        TF_HIP(hipEventRecord(rk->halo_done[slot], rk->hs), "tf_rank_pivotal");
-        rk->halo_set[slot] = true;
-    }
+    if (!no_halo)
+        if (const int rc = halo_exchange(rk, piv, inv_ext, kfo, 3, o_bs, SD, S, slot, st, "tf_rank_pivotal")) return rc;
     return 0;
 }
 
@@ -461,4 +514,260 @@ extern "C" int tf_rank_halo_wait(tf_rank* rk, int slot, void* stream) {
     if (rk->halo_set[slot])
         TF_HIP(hipStreamWaitEvent(reinterpret_cast<hipStream_t>(stream), rk->halo_done[slot], 0), "tf_rank_halo_wait");
     return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The same pass for a multi-edit batch (include/tokenflow_hip.h): B = 1 + 2E branches [source | uncond_1 | cond_1 | ...], the
+// C++ form of FrameShard._pivotal_heads_edits / _pivotal_bank_edits (tokenflow_amd/sharded.py) with their buffer layouts.  Per
+// block the collectives and the launches stay at the single-edit count; only their payload grows with E.
+namespace {
+
+struct EditsLayout {   // exchange buffers of one call inside the caller's workspace; slab counts at their largest
+    size_t send, recv, send2, recv2, stage, ws_bank, ws_src, total;
+    size_t ws_bank_bytes, ws_src_bytes;
+};
+
+EditsLayout edits_layout(const tf_rank* rk, int S, int H, int Dh, int E, int dtype, int mode) {
+    const size_t eb = 2;
+    const int W = rk->world, Kl = rk->Kl, K = rk->K;
+    const size_t D = (size_t)H * Dh;
+    EditsLayout L{};
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        const size_t at = off;
+        off += up256(bytes);
+        return at;
+    };
+    if (mode == TF_RANK_HEADS) {   // [q slots | k slots | v_1 .. v_2E]: 6E slabs where no edit injects
+        const size_t hd = D / W;
+        L.send = take((size_t)W * Kl * 6 * E * S * hd * eb);
+        L.recv = take((size_t)K * 6 * E * S * hd * eb);
+        L.send2 = take((size_t)K * 2 * E * S * hd * eb);
+        L.recv2 = take((size_t)W * Kl * 2 * E * S * hd * eb);
+        L.ws_bank_bytes = tf_ext_attn_edits_workspace_bytes(K, S, H / W, Dh, E, dtype);
+    } else {                       // [k slots | v_1 .. v_2E]: 4E slabs; the compact q of a mixed mask is staged (< 2E slots)
+        L.send = take((size_t)Kl * 4 * E * S * D * eb);
+        L.recv = take((size_t)K * 4 * E * S * D * eb);
+        L.stage = take((size_t)Kl * 2 * E * S * D * eb);
+        L.ws_bank_bytes = tf_ext_attn_edits_workspace_bytes(K, S, H, Dh, E, dtype);
+    }
+    // the bank part and the source part may run concurrently: a workspace each
+    L.ws_src_bytes = tf_ext_attn_edits_workspace_bytes(Kl, S, H, Dh, E, dtype);
+    L.ws_bank = take(L.ws_bank_bytes);
+    L.ws_src = take(L.ws_src_bytes);
+    L.total = off;
+    return L;
+}
+
+}  // namespace
+
+extern "C" size_t tf_rank_pivotal_edits_workspace_bytes(const tf_rank* rk, int S, int H, int Dh, int n_edits, int dtype) {
+    if (!rk || S <= 0 || H <= 0 || Dh <= 0 || dtype == TF_F32 || n_edits < 1 || n_edits > TF_MAX_EDITS) return 0;
+    if (n_edits == 1) return tf_rank_pivotal_workspace_bytes(rk, S, H, Dh, dtype);
+    if (rk->world == 1) return up256(tf_ext_attn_edits_workspace_bytes(rk->K, S, H, Dh, n_edits, dtype));
+    const size_t bank = edits_layout(rk, S, H, Dh, n_edits, dtype, TF_RANK_BANK).total;   // ONE workspace for both modes
+    const size_t heads = H % rk->world == 0 ? edits_layout(rk, S, H, Dh, n_edits, dtype, TF_RANK_HEADS).total : 0;
+    return bank > heads ? bank : heads;
+}
+
+extern "C" int tf_rank_pivotal_edits(tf_rank* rk, const void* q, const void* k, const void* v, const int64_t* st_in,
+                                     void* piv_ext, float* inv_ext, void* kfo_ext, int S, int H, int Dh, float scale,
+                                     int flags, int dtype, int mode_in, int slot, int n_edits, unsigned inject_mask, void* ws,
+                                     size_t ws_bytes, void* stream) {
+    const char* const fn = "tf_rank_pivotal_edits";
+    const bool no_halo = (mode_in & TF_RANK_NO_HALO) != 0, want_inv = (mode_in & TF_RANK_INV_NORM) != 0;
+    const int mode = mode_in & ~(TF_RANK_NO_HALO | TF_RANK_INV_NORM);
+    // ---- arguments first: nothing below this block's end has touched the device
+    TF_ARG(rk && q && k && v && st_in && kfo_ext && ws && (no_halo || (piv_ext && inv_ext)), TF_ERR_NULL, "%s: null pointer", fn);
+    TF_ARG(n_edits >= 1 && n_edits <= TF_MAX_EDITS, TF_ERR_SHAPE, "%s: n_edits=%d (1 .. %d)", fn, n_edits, TF_MAX_EDITS);
+    TF_ARG(!(flags & TF_ATTN_INJECT), TF_ERR_SHAPE, "%s: TF_ATTN_INJECT beside a mask (the mask is the injection state)", fn);
+    TF_ARG(!(inject_mask >> n_edits), TF_ERR_SHAPE, "%s: inject_mask=0x%x has bits at or above n_edits=%d", fn, inject_mask,
+           n_edits);
+    TF_ARG(!(flags & (TF_ATTN_BANK_ONLY | TF_ATTN_SOURCE_ONLY)), TF_ERR_SHAPE, "%s: the part flags are the executor's own", fn);
+    TF_ARG(dtype == TF_BF16 || dtype == TF_F16, TF_ERR_DTYPE, "%s: dtype %d (bf16/f16 only)", fn, dtype);
+    TF_ARG(mode == TF_RANK_HEADS || mode == TF_RANK_BANK || mode == TF_RANK_BANK_RUNS, TF_ERR_SHAPE, "%s: mode %d", fn, mode);
+    TF_ARG(!(mode == TF_RANK_BANK_RUNS && n_edits > 1), TF_ERR_SHAPE,
+           "%s: TF_RANK_BANK_RUNS has no multi-edit form (TF_RANK_BANK or TF_RANK_HEADS)", fn);
+    TF_ARG(!(mode == TF_RANK_HEADS && rk->world > 1 && H % rk->world), TF_ERR_SHAPE,
+           "%s: %d heads do not divide over %d ranks (use TF_RANK_BANK)", fn, H, rk->world);
+    TF_ARG(slot >= 0 && slot < TF_RANK_SLOTS, TF_ERR_SHAPE, "%s: slot %d outside [0, %d)", fn, slot, TF_RANK_SLOTS);
+    TF_ARG(!(want_inv && no_halo), TF_ERR_SHAPE, "%s: TF_RANK_INV_NORM needs the propagation state (no TF_RANK_NO_HALO)", fn);
+    if (n_edits == 1)   // one edit: the single-edit executor itself -- the same launches, the same bits
+        return tf_rank_pivotal(rk, q, k, v, st_in, piv_ext, inv_ext, kfo_ext, S, H, Dh, scale,
+                               flags | (inject_mask ? TF_ATTN_INJECT : 0), dtype, mode_in, slot, ws, ws_bytes, stream);
+    TF_ARG(ws_bytes >= tf_rank_pivotal_edits_workspace_bytes(rk, S, H, Dh, n_edits, dtype), TF_ERR_WORKSPACE,
+           "%s: workspace %zu < %zu bytes", fn, ws_bytes, tf_rank_pivotal_edits_workspace_bytes(rk, S, H, Dh, n_edits, dtype));
+
+    const int E = n_edits, B = 1 + 2 * E;
+    const int W = rk->world, Kl = rk->Kl, K = rk->K, o = (W > 1 && !no_halo) ? 1 : 0;
+    const int64_t D = (int64_t)H * Dh, SD = (int64_t)S * D;
+    const int64_t q_bs = st_in[0], q_fs = st_in[1], k_bs = st_in[2], k_fs = st_in[3], v_bs = st_in[4], v_fs = st_in[5],
+                  ld_q = st_in[6], ld = st_in[7];
+    typedef unsigned short El;   // any 16-bit element: only pointer arithmetic happens here
+    const El* qe = static_cast<const El*>(q);
+    const El* ke = static_cast<const El*>(k);
+    const El* ve = static_cast<const El*>(v);
+    El* kfo = static_cast<El*>(kfo_ext);
+    El* piv = static_cast<El*>(piv_ext);
+    unsigned char* wsb = static_cast<unsigned char*>(ws);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int64_t o_bs = (int64_t)(Kl + o) * SD;   // branch stride of the halo-extended attention output
+    El* out_loc = kfo + (int64_t)o * SD;           // its local slots
+    if (!no_halo) rk->halo_set[slot] = false;
+    const El* piv_loc = want_inv ? piv + (int64_t)o * SD : nullptr;
+    float* inv_loc = want_inv ? inv_ext + (int64_t)o * S : nullptr;
+    const int64_t loc_strides[9] = {q_bs, q_fs, k_bs, k_fs, v_bs, v_fs, o_bs, SD, ld_q};
+
+    if (W == 1) {
+        if (want_inv)
+            if (const int rc = do_inv_norm(piv_loc, inv_loc, (int64_t)Kl * S, (int)D, dtype, stream)) return rc;
+        return tf_ext_attn_fwd_edits_masked(q, k, v, out_loc, K, K, 0, S, H, Dh, ld, loc_strides, scale, flags, dtype, E,
+                                            inject_mask, ws, ws_bytes, stream);
+    }
+    int64_t cnt[TF_MAX_WORLD], own[TF_MAX_WORLD];
+    for (int p = 0; p < W; ++p) cnt[p] = rk->counts[p], own[p] = Kl;
+
+    // the compact q / k layout of tf_ext_attn_fwd_edits_part: slot 0 the source where some edit injects, then (uncond, cond)
+    // of every edit that does not, ascending; b0 = the first slot that exists
+    int slots[1 + 2 * TF_MAX_EDITS], nq = 0;
+    if (inject_mask) slots[nq++] = 0;
+    for (int e = 0; e < E; ++e)
+        if (!((inject_mask >> e) & 1u)) slots[nq++] = 1 + 2 * e, slots[nq++] = 2 + 2 * e;
+    const int b0 = inject_mask ? 0 : 1;
+    const bool mixed = inject_mask && nq > 1;   // some edits inject, some do not
+    // base such that slab `first_slab` of a buffer of `unit`-element slabs is branch `first_branch` (the strided entry points'
+    // convention): a slot that does not exist is never addressed, so the base may lie in front of the buffer -- an integer
+    auto slab = [](const El* buf, int64_t first_slab, int first_branch, int64_t unit) {
+        return reinterpret_cast<const El*>(reinterpret_cast<uintptr_t>(buf) +
+                                           (uintptr_t)((first_slab - first_branch) * unit * (int64_t)sizeof(El)));
+    };
+    const void* slabs[6 * TF_MAX_EDITS];
+    int64_t fss[6 * TF_MAX_EDITS];
+    // the source part of the rank's own frames on the local tensors
+    const EditsLayout L = edits_layout(rk, S, H, Dh, E, dtype, mode);
+    auto source_part = [&](hipStream_t on) {
+        return tf_ext_attn_fwd_edits_part(q, k, v, out_loc, Kl, Kl, 0, S, H, Dh, ld, loc_strides, scale,
+                                          flags | TF_ATTN_SOURCE_ONLY, dtype, E, inject_mask, 0, wsb + L.ws_src, L.ws_src_bytes,
+                                          on);
+    };
+    El* send = reinterpret_cast<El*>(wsb + L.send);
+    El* recv = reinterpret_cast<El*>(wsb + L.recv);
+
+    if (mode == TF_RANK_HEADS) {
+        TF_ARG(ld_q == ld, TF_ERR_SHAPE, "%s: the head re-sharding packs q, k, v with one token stride", fn);
+        const int Hl = H / W;
+        const int64_t hd = D / W, Shd = (int64_t)S * hd;
+        El* send2 = reinterpret_cast<El*>(wsb + L.send2);
+        El* recv2 = reinterpret_cast<El*>(wsb + L.recv2);
+        // ---- ONE pack: head group w of [q slots | k slots | v_1 .. v_2E], frame-major; the inverse norms in the same launch
+        const int ns = 2 * nq + 2 * E;
+        for (int i = 0; i < nq; ++i) {
+            slabs[i] = qe + slots[i] * q_bs, fss[i] = q_fs;
+            slabs[nq + i] = ke + slots[i] * k_bs, fss[nq + i] = k_fs;
+        }
+        for (int j = 0; j < 2 * E; ++j) slabs[2 * nq + j] = ve + (1 + j) * v_bs, fss[2 * nq + j] = v_fs;
+        if (const int rc = do_pack(slabs, fss, ns, send, W, Kl, S, (int)hd, ld, piv_loc, inv_loc, (int64_t)Kl * S, (int)D,
+                                   dtype, stream))
+            return rc;
+        // ---- the source part beside the first exchange where it is a streaming launch (the single-edit rule: forked HERE,
+        //      behind the pack and in front of the exchange, joined in front of the second exchange); where it takes the fused
+        //      small-problem kernel, in line behind the exchange.  Every rank of the block must decide alike: the decision of
+        //      the source-only call (ext_attn.hip) with the largest local run ceil(K / W) standing for Kl.
+        TfAttnSet probe{};
+        probe.q = q, probe.k = k, probe.v = v, probe.out = out_loc;
+        probe.q_bs = q_bs, probe.q_fs = q_fs, probe.ld_q = ld_q, probe.k_bs = k_bs, probe.k_fs = k_fs;
+        probe.v_bs = v_bs, probe.v_fs = v_fs, probe.ld = ld, probe.o_bs = o_bs, probe.o_fs = SD;
+        probe.H = H, probe.Kq = probe.Kb = (K + W - 1) / W, probe.q_frame0 = 0, probe.b0 = 0, probe.nb = 1;
+        const int src_flags = flags | TF_ATTN_SOURCE_ONLY | (nq == 1 ? TF_ATTN_INJECT : 0);   // (every edit injects)
+        const bool src_fused = tf_attn_fused_plan(&probe, 1, S, Dh, dtype, src_flags).use != 0;
+        const bool fork = !src_fused && src_aux_enabled() && !tf_plan_rec;   // (a recorded plan lists the in-line order)
+        if (fork) {
+            if (const int rc = order(rk, st, rk->as, fn)) return rc;
+            if (const int rc = source_part(rk->as)) return rc;
+        }
+        // ---- ONE first all-to-all; every collective of the communicator on the caller's stream
+        if (const int rc = do_a2a(rk->comm, send, recv, own, cnt, ns, Shd, dtype, st)) return rc;
+        // ---- the bank part of every edit on this rank's head group over all K frames: reads `recv` [K][ns][S][hd], writes
+        //      `send2` [K][2E][S][hd], both in place
+        const int64_t fs_r = ns * Shd;
+        const El* qb = slab(recv, 0, b0, Shd);
+        const El* kb = slab(recv, nq, b0, Shd);
+        const El* vb = slab(recv, 2 * nq, 1, Shd);
+        El* ob = const_cast<El*>(slab(send2, 0, 1, Shd));
+        const int64_t strides[9] = {Shd, fs_r, Shd, fs_r, Shd, fs_r, Shd, 2 * E * Shd, hd};
+        if (const int rc = tf_ext_attn_fwd_edits_part(qb, kb, vb, ob, K, K, 0, S, Hl, Dh, hd, strides, scale,
+                                                      flags | TF_ATTN_BANK_ONLY, dtype, E, inject_mask, 1, wsb + L.ws_bank,
+                                                      L.ws_bank_bytes, stream))
+            return rc;
+        if (fork) {
+            if (const int rc = order(rk, rk->as, st, fn)) return rc;
+        } else if (const int rc = source_part(st)) {
+            return rc;
+        }
+        // ---- ONE second all-to-all: the outputs back to the frame owners; ONE unpack into the 2E bank slabs of kfo_ext
+        if (const int rc = do_a2a(rk->comm, send2, recv2, cnt, own, 2 * E, Shd, dtype, st)) return rc;
+        void* dsts[2 * TF_MAX_EDITS];
+        int64_t dfs[2 * TF_MAX_EDITS];
+        for (int j = 0; j < 2 * E; ++j) dsts[j] = out_loc + (1 + j) * o_bs, dfs[j] = SD;
+        if (const int rc = do_unpack(recv2, dsts, dfs, 2 * E, W, Kl, S, (int)hd, D, stream)) return rc;
+    } else {
+        // ---- ONE pack (W = 1) of exactly the compact k slots and the 2E value slabs: the source's v and every q stay at home
+        const int ns = nq + 2 * E;
+        for (int i = 0; i < nq; ++i) slabs[i] = ke + slots[i] * k_bs, fss[i] = k_fs;
+        for (int j = 0; j < 2 * E; ++j) slabs[nq + j] = ve + (1 + j) * v_bs, fss[nq + j] = v_fs;
+        if (const int rc = do_pack(slabs, fss, ns, send, 1, Kl, S, (int)D, ld, piv_loc, inv_loc, (int64_t)Kl * S, (int)D,
+                                   dtype, stream))
+            return rc;
+        // ---- q in the same compact layout: the dense tensor IS that layout unless the mask is mixed; then the slots are
+        //      copied into the staging region [Kl][nq][S][D] (the pack kernel with W = 1, one launch)
+        const El* qp = qe;
+        int64_t cq_bs = q_bs, cq_fs = q_fs, cq_ld = ld_q;
+        if (mixed) {
+            El* stage = reinterpret_cast<El*>(wsb + L.stage);
+            const void* qs[1 + 2 * TF_MAX_EDITS];
+            int64_t qfs[1 + 2 * TF_MAX_EDITS];
+            for (int i = 0; i < nq; ++i) qs[i] = qe + slots[i] * q_bs, qfs[i] = q_fs;
+            if (!tf_plan_note("qcompact[ns=%d]", nq))
+                if (const int rc = tf_head_pack(qs, qfs, nq, stage, 1, Kl, S, (int)D, ld_q, 2, stream)) return rc;
+            qp = stage, cq_bs = SD, cq_fs = nq * SD, cq_ld = D;
+        }
+        // ---- ONE gather into [K][ns][S][D], on the caller's stream: the attention needs it at once
+        if (const int rc = do_gather(rk->comm, send, recv, cnt, ns, SD, dtype, st)) return rc;
+        // ---- the bank part of the local keyframes' queries on the gathered buffer in place, then the source part
+        const int64_t fs_r = ns * SD;
+        const El* kb = slab(recv, 0, b0, SD);
+        const El* vb = slab(recv, nq, 1, SD);
+        const int64_t strides[9] = {cq_bs, cq_fs, SD, fs_r, SD, fs_r, o_bs, SD, cq_ld};
+        if (const int rc = tf_ext_attn_fwd_edits_part(qp, kb, vb, out_loc, K, Kl, rk->kf0, S, H, Dh, D, strides, scale,
+                                                      flags | TF_ATTN_BANK_ONLY, dtype, E, inject_mask, 1, wsb + L.ws_bank,
+                                                      L.ws_bank_bytes, stream))
+            return rc;
+        if (const int rc = source_part(st)) return rc;
+    }
+
+    // ---- neighbour halo: 2 + B messages in ONE grouped exchange
+    if (!no_halo)
+        if (const int rc = halo_exchange(rk, piv, inv_ext, kfo, B, o_bs, SD, S, slot, st, fn)) return rc;
+    return 0;
+}
+
+// The sequence one call issues, recorded by the call itself on a rank that owns no device object (host only).
+extern "C" int tf_rank_pivotal_edits_plan(int world, int rank, int K, int S, int H, int Dh, int n_edits, unsigned inject_mask,
+                                          int mode, int flags, int dtype, char* buf, size_t len) {
+    TF_ARG(world >= 1 && world <= TF_MAX_WORLD && rank >= 0 && rank < world && K >= world && S > 0 && H > 0 && Dh > 0,
+           TF_ERR_SHAPE, "tf_rank_pivotal_edits_plan: rank %d of %d over %d keyframes, S=%d H=%d Dh=%d", rank, world, K, S, H, Dh);
+    tf_rank rk{};
+    partition(&rk, K, world, rank);
+    void* const ph = reinterpret_cast<void*>((uintptr_t)1 << 40);   // never dereferenced
+    const int64_t D = (int64_t)H * Dh, SD = (int64_t)S * D;
+    const int64_t strides[8] = {rk.Kl * SD, SD, rk.Kl * SD, SD, rk.Kl * SD, SD, D, D};
+    TfPlanRec rec{buf, len, 0, 0};
+    if (buf && len) buf[0] = 0;
+    tf_plan_rec = &rec;
+    const int rc = tf_rank_pivotal_edits(&rk, ph, ph, ph, strides, ph, static_cast<float*>(ph), ph, S, H, Dh, 1.0f, flags,
+                                         dtype, mode, 0, n_edits, inject_mask, ph, (size_t)-1, nullptr);
+    tf_plan_rec = nullptr;
+    if (rc) return rc;
+    TF_ARG(rec.used < len, TF_ERR_WORKSPACE, "tf_rank_pivotal_edits_plan: the plan needs %zu bytes", rec.used + 1);
+    return rec.n;
 }

@@ -96,7 +96,7 @@ def register_frame_shard(diffusion_model, shard):
     draw the same `pivotal_idx` (run_tokenflow_pnp.py:224).  INTEGRATION.md section 3 shows the driver side.
     With `register_edits(model, E > 1)` the batches are the rank's keyframes / chunks of all 1 + 2E branches and a `FrameShard`
     runs them as ONE multi-edit pass (`supports_edits`: one pack, the same collectives, one unpack, one search per block);
-    `NativeShard` runs one edit and raises.
+    `NativeShard` runs one edit and raises; `NativeEditShard` is its multi-edit form (one tf_rank_pivotal_edits call per block).
     A world-1 shard (one GPU) runs the bit-stable attention mode too unless it was built with `attn_split=True`: slower
     than the plain single-process hooks by the per-grid kernel choice it gives up (`tools/hooks_bench.py --ranks 1`)."""
     for module in _tokenflow_blocks(diffusion_model):
@@ -157,7 +157,7 @@ def register_edits(model, n_edits):
     n_edits = 1 (the default without this call) is the reference's layout and issues exactly the single-edit ops.
     Combines with `register_frame_shard` where the shard type runs multi-edit batches (`FrameShard.supports_edits`): every rank
     then runs one multi-edit pass on its keyframes and chunks.
-    Not generalised, ValueError with n_edits > 1: a frame shard without that capability (NativeShard), the AdaLayerNormZero gated
+    Not generalised, ValueError with n_edits > 1: a frame shard without that capability (NativeShard; NativeEditShard has it), the AdaLayerNormZero gated
     path, replay through `tokenflow_amd.graphs.GraphCache` (INTEGRATION.md section 4 shows the driver side)."""
     n_edits = int(n_edits)
     from . import _lib

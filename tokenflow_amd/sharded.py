@@ -49,7 +49,8 @@ side stream ordered against the compute stream with events):
 
 Three hosts run this sequence with identical results: `FrameShard` over torch.distributed, `FrameShard`
 over the library's exchange entry points (`comm=`), and `NativeShard` (bottom of this file), whose
-pivotal pass of a block is ONE library call (tf_rank_pivotal, csrc/rank_exec.hip).  The hook API
+pivotal pass of a block is ONE library call (tf_rank_pivotal, csrc/rank_exec.hip; `NativeEditShard`: the same for multi-edit
+batches, tf_rank_pivotal_edits).  The hook API
 reaches them through `tokenflow_amd.hooks.register_frame_shard`.
 
 Work is partitioned, not re-associated: every output element is produced by exactly the same
@@ -883,3 +884,120 @@ class NativeShard(FrameShard):
         if rc:
             _lib.check(rc, "tf_rank_pivotal")
         return slot
+
+
+class NativeEditShard(NativeShard):
+    """`NativeShard` for multi-edit batches (`hooks.register_edits`): with n_edits = E > 1 the pivotal pass of a block is
+    ONE call of tf_rank_pivotal_edits (csrc/rank_exec.hip) -- the native form of `FrameShard._pivotal_heads_edits` /
+    `_pivotal_bank_edits`, same buffer layouts, same bits on the same transport.  n_edits = 1 is `NativeShard` itself.
+    Modes "heads" and "bank" (`auto_mode` answers "bank" in place of "bank_runs" for E > 1; the explicit "bank_runs" raises as
+    on `FrameShard`).  `ext_alloc`, `halo_block`, `halo_finish`, `propagate_all` are `FrameShard`'s, with n_edits."""
+
+    supports_edits = True
+
+    def __init__(self, K: int, comm, halo_comm=None, attn_split: Optional[bool] = None, bank_runs: Optional[bool] = None):
+        super().__init__(K, comm, halo_comm=halo_comm, attn_split=attn_split, bank_runs=bank_runs)
+        self._news = {}
+
+    @staticmethod
+    def _mask(E: int, inject: bool, inject_mask: Optional[int]) -> int:
+        if inject_mask is None:
+            return (1 << E) - 1 if inject else 0
+        mask = int(inject_mask)
+        if inject or mask < 0 or mask >> E:
+            raise ValueError(f"FrameShard.pivotal_attention: inject_mask {mask:#x} for {E} edits (bits below n_edits; "
+                             f"`inject` must be False beside a mask)")
+        return mask
+
+    def pivotal_attention(self, q_local, k_local, v_local, heads: int, scale: float, inject: bool,
+                          mode: Optional[str] = None, out4: Optional[torch.Tensor] = None, n_edits: int = 1,
+                          inject_mask: Optional[int] = None):
+        """`FrameShard.pivotal_attention` with n_edits / inject_mask; E > 1 is one tf_rank_pivotal_edits call with
+        TF_RANK_NO_HALO (what the hook path calls from `attn1`)."""
+        E = int(n_edits)
+        if E == 1:
+            return super().pivotal_attention(q_local, k_local, v_local, heads, scale, inject, mode=mode, out4=out4)
+        if self.world == 1 or out4 is not None or not q_local.is_cuda or q_local.dtype not in (torch.bfloat16,
+                                                                                                torch.float16):
+            return FrameShard.pivotal_attention(self, q_local, k_local, v_local, heads, scale, inject, mode=mode, out4=out4,
+                                                n_edits=E, inject_mask=inject_mask)
+        mask = self._mask(E, inject, inject_mask)
+        B, S, D = q_local.shape
+        out = torch.empty(1 + 2 * E, self.Kl, S, D, dtype=q_local.dtype, device=q_local.device)
+        self._native_edits(q_local, k_local, v_local, heads, scale, E, mask, mode, None, None, out, no_halo=True)
+        return out.view(B, S, D)
+
+    def pivotal_block(self, q_local, k_local, v_local, heads: int, scale: float, inject: bool, ext,
+                      mode: Optional[str] = None, inv_norm: bool = False, n_edits: int = 1,
+                      inject_mask: Optional[int] = None):
+        E = int(n_edits)
+        if E == 1:
+            return super().pivotal_block(q_local, k_local, v_local, heads, scale, inject, ext, mode=mode, inv_norm=inv_norm)
+        mask = self._mask(E, inject, inject_mask)
+        piv, inv, kfo = ext
+        _, S, D = q_local.shape
+        o = 1 if self.world > 1 else 0
+        slot = self._native_edits(q_local, k_local, v_local, heads, scale, E, mask, mode, piv, inv, kfo, no_halo=False,
+                                  inv_norm=inv_norm)
+        reqs = [_SlotWait(self, slot, q_local.device)] if self.world > 1 else []
+        return piv, inv, kfo.view((1 + 2 * E) * (self.Kl + o), S, D), reqs
+
+    def _native_edits(self, q_local, k_local, v_local, heads, scale, E, mask, mode, piv, inv, kfo, no_halo, inv_norm=False):
+        from . import _lib
+        lib = _lib.load()
+        _, S, D = q_local.shape
+        Kl, B = self.Kl, 1 + 2 * E
+        if mode is None:
+            mode = self.auto_mode(heads, S, E)
+        if mode == "bank_runs":
+            raise ValueError("FrameShard: the \"bank_runs\" pattern has no multi-edit form (use \"bank\" or \"heads\")")
+        dt = ops._DT.get(q_local.dtype)
+        if dt is None or dt == _lib.TF_F32 or not (q_local.is_cuda and kfo.is_contiguous()
+                                                    and (no_halo or (piv.is_contiguous() and inv.is_contiguous()))):
+            raise TypeError("NativeEditShard: 16-bit GPU tensors, contiguous (halo-extended) buffers")
+
+        def frames(t):     # [B*Kl, S, D] (token stride free) -> [B, Kl, S, D] view
+            if t.stride(2) != 1 or t.stride(0) != S * t.stride(1):
+                t = t.contiguous()
+            return t.view(B, Kl, S, D) if t.is_contiguous() else t.unflatten(0, (B, Kl))
+        q4, k4, v4 = frames(q_local), frames(k_local), frames(v_local)
+        if k4.stride(2) != v4.stride(2) or (mode == "heads" and q4.stride(2) != k4.stride(2)):
+            q4, k4, v4 = (t.contiguous() for t in (q4, k4, v4))
+        strides = (ctypes.c_int64 * 8)(q4.stride(0), q4.stride(1), k4.stride(0), k4.stride(1), v4.stride(0), v4.stride(1),
+                                       q4.stride(2), k4.stride(2))
+        dh = D // heads
+        key = (S, heads, dh, dt, q_local.device, E)
+        ws = self._news.get(key)
+        if ws is None:
+            nbytes = lib.tf_rank_pivotal_edits_workspace_bytes(self._rk, S, heads, dh, E, dt)
+            ws = self._news[key] = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=q_local.device)
+        flags = 0 if self.attn_split else _lib.TF_ATTN_NO_SPLIT
+        if ops.FOLD_SCALE:
+            flags |= _lib.TF_ATTN_FOLD_SCALE
+        slot = self._slot
+        if not no_halo:
+            self._slot = (slot + 1) % _lib.TF_RANK_SLOTS
+        m = ((_lib.TF_RANK_HEADS if mode == "heads" else _lib.TF_RANK_BANK)
+             | (_lib.TF_RANK_NO_HALO if no_halo else 0)
+             | (_lib.TF_RANK_INV_NORM if inv_norm else 0))
+        rc = lib.tf_rank_pivotal_edits(self._rk, q4.data_ptr(), k4.data_ptr(), v4.data_ptr(), strides,
+                                       None if piv is None else piv.data_ptr(), None if inv is None else inv.data_ptr(),
+                                       kfo.data_ptr(), S, heads, dh, float(scale), flags, dt, m, slot, E, mask,
+                                       ws.data_ptr(), ws.numel(), torch.cuda.current_stream(q_local.device).cuda_stream)
+        if rc:
+            _lib.check(rc, "tf_rank_pivotal_edits")
+        return slot
+
+
+def rank_edits_plan(world: int, rank: int, K: int, S: int, heads: int, dh: int, n_edits: int, inject_mask: int,
+                    mode: str = "heads", dtype: torch.dtype = torch.bfloat16, no_split: bool = True, no_halo: bool = False,
+                    inv_norm: bool = False, flags: int = 0) -> list:
+    """The sequence ONE `NativeEditShard` block call issues on `rank` of `world` ranks, as tokens
+    (tf_rank_pivotal_edits_plan: e.g. ['pack+inv[ns=10]', 'a2a[slabs=10]', 'vt_pack', ..., 'a2a[slabs=4]', 'unpack[nb=4]',
+    'halo[n=7]']).  Recorded by the executing code itself; host only: needs no GPU and no communicator."""
+    from . import _lib
+    m = ({"heads": _lib.TF_RANK_HEADS, "bank": _lib.TF_RANK_BANK, "bank_runs": _lib.TF_RANK_BANK_RUNS}[mode]
+         | (_lib.TF_RANK_NO_HALO if no_halo else 0) | (_lib.TF_RANK_INV_NORM if inv_norm else 0))
+    fl = int(flags) | (_lib.TF_ATTN_NO_SPLIT if no_split else 0)
+    return ops._plan_tokens("tf_rank_pivotal_edits_plan", _lib.load().tf_rank_pivotal_edits_plan, int(world), int(rank),
+                            int(K), S, heads, dh, int(n_edits), int(inject_mask), m, fl, ops._DT[dtype])

@@ -12,7 +12,12 @@ Prints, per configuration (attention split on / off, exchange pattern):
     blocks of the coarse levels are host-bound (the GPU waits for the next launch), inside a step the host runs ahead
     during the level-0 blocks;
   * the bytes a rank would put on the wire per block, and the time they take at an assumed per-link rate.
-Target: step <= single-GPU step / 6."""
+Target: step <= single-GPU step / 6.
+
+--edits E [--inject-mask M]: the step is ONE multi-edit pass of E prompts (B = 1 + 2E branches; `NativeEditShard` with
+--native, `FrameShard` without, both on the library's loopback transport so that --no-copies and --wire-model apply to
+either); the injected blocks of an inject=1 step run with mask M (default: every edit injects).  The yardstick is E times the
+--edits 1 step."""
 import argparse
 import os
 import statistics
@@ -77,6 +82,41 @@ class LocalComm:
             self.bytes += sum(t.numel() * t.element_size() for t in send)
 
 
+class EditBlock:
+    """bench.Block for a multi-edit batch: q / k / v, residual and the block's state hold B = 1 + 2E branches."""
+
+    def __init__(self, cfg, lvl, injected, shard, gen, dev, E):
+        S, D, h = cfg.levels[lvl]
+        self.S, self.D, self.h, self.lvl, self.injected = S, D, h, lvl, injected
+        Kl, n, B, bf = shard.Kl, cfg.chunk, 1 + 2 * E, torch.bfloat16
+
+        def rnd(*shape):
+            return torch.randn(*shape, generator=gen, device=dev, dtype=torch.float32).to(bf)
+        self.q, self.k, self.v = rnd(B * Kl, S, D), rnd(B * Kl, S, D), rnd(B * Kl, S, D)
+        self.ext = shard.ext_alloc(S, D, bf, dev, n_edits=E)
+        self.pivots = self.ext[0][1 if shard.world > 1 else 0:]
+        self.pivots.copy_(torch.nn.functional.layer_norm(torch.randn(Kl, S, D, generator=gen, device=dev), (D,)).to(bf))
+        tgt = []
+        for j in range(Kl):     # video-like targets: permuted pivot rows + noise, as bench.Block
+            perm = torch.stack([torch.randperm(S, generator=gen, device=dev) for _ in range(n)]).reshape(-1)
+            tgt.append(self.pivots[j].float()[perm] + 0.1 * torch.randn(n * S, D, generator=gen, device=dev))
+        self.tgt = torch.cat(tgt).to(bf)
+        self.res = rnd(B * Kl * n, S, D)
+
+
+def run_edit_step(cfg, blocks, shard, inject_on, w, E, mask, exchange=None):
+    """bench.run_step's two-pass order for ONE multi-edit pass: the pivotal pass over the 16 blocks, then their propagation."""
+    pending = []
+    for blk in blocks:
+        m = mask if (inject_on and blk.injected and cfg.pnp) else 0
+        pending.append((blk, shard.pivotal_block(blk.q, blk.k, blk.v, blk.h, (blk.D // blk.h) ** -0.5, False, blk.ext,
+                                                 mode=exchange, inv_norm=True, n_edits=E, inject_mask=m)))
+    outs = None
+    for blk, (piv_e, inv_e, kfo_e, reqs) in pending:
+        outs, _rest = shard.propagate_all(blk.tgt, blk.res, piv_e, inv_e, kfo_e, w, cfg.chunk, halo_reqs=reqs, n_edits=E)
+    return outs
+
+
 def latest_driver_ms(default=26.0):
     """ms_per_step of the newest driver bench record (BENCH_rNN.json at the repository root)."""
     import glob
@@ -136,7 +176,16 @@ def main():
     ap.add_argument("--native", action="store_true",
                     help="sharded.NativeShard: the pivotal pass of a block as ONE library call (tf_rank_pivotal) on the "
                          "library's loopback transport (tf_comm_init_loopback: the same wire-less stand-in, in C)")
+    ap.add_argument("--edits", type=int, default=1, metavar="E",
+                    help="one multi-edit pass of E prompts per step (NativeEditShard with --native, FrameShard without; both "
+                         "on the loopback transport); 1 = today's single-edit step")
+    ap.add_argument("--inject-mask", type=lambda x: int(x, 0), default=None, metavar="M",
+                    help="--edits: the injection mask of the injected blocks in an inject=1 step (default: every edit)")
     args = ap.parse_args()
+    E = args.edits
+    mask = (1 << E) - 1 if args.inject_mask is None else args.inject_mask
+    if E > 1 and args.world < 2:
+        ap.error("--edits needs --world >= 2 (the two-pass rank step)")
     cfg = workload.CONFIGS[args.config]
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
@@ -145,58 +194,72 @@ def main():
         for mode_name in ("auto", "heads", "bank", "bank_runs", "auto+runs"):
             if args.only and args.only != f"{'split' if split else 'onepass'},{mode_name}":
                 continue
+            if E > 1 and mode_name in ("bank_runs", "auto+runs"):      # the runs form has no multi-edit form
+                continue
             opt_in = mode_name == "auto+runs"       # FrameShard(bank_runs=True): auto_mode may answer "bank_runs"
             mode = None if mode_name in ("auto", "auto+runs") else mode_name
             wire = tuple(float(x) for x in args.wire_model.split(",")) if args.wire_model else None
-            if args.native:
+            if args.native or E > 1:
                 from tokenflow_amd import _lib
                 from tokenflow_amd.comm import HipComm
                 comm = HipComm.loopback(args.rank, args.world, copies=not args.no_copies, wire=wire)
                 comm.bytes = 0
                 hcomm = HipComm.loopback(args.rank, args.world, copies=not args.no_copies, wire=wire)
-                shard = sharded.NativeShard(cfg.K, comm, hcomm, attn_split=split, bank_runs=opt_in)
+                if E > 1:
+                    shard = (sharded.NativeEditShard(cfg.K, comm, hcomm, attn_split=split) if args.native else
+                             sharded.FrameShard(cfg.K, comm=comm, halo_comm=hcomm, attn_split=split))
+                else:
+                    shard = sharded.NativeShard(cfg.K, comm, hcomm, attn_split=split, bank_runs=opt_in)
             else:
                 comm = LocalComm(args.rank, args.world)
                 shard = sharded.FrameShard(cfg.K, comm=comm, attn_split=split, bank_runs=opt_in)
             if mode == "heads" and any(l[2] % args.world for l in cfg.levels):
                 continue
             gen = torch.Generator(device=dev).manual_seed(1234 + args.rank)
-            blocks = [bench.Block(cfg, lvl, inj, shard, gen, dev) for lvl, inj in workload.BLOCKS]
-            modes = [mode or shard.auto_mode(l[2], l[0]) for l in cfg.levels]
+            if E > 1:
+                blocks = [EditBlock(cfg, lvl, inj, shard, gen, dev, E) for lvl, inj in workload.BLOCKS]
+                modes = [mode or shard.auto_mode(l[2], l[0], E) for l in cfg.levels]
+                step = lambda inj_: run_edit_step(cfg, blocks, shard, inj_, w, E, mask, exchange=mode)
+                print(f"=== ONE multi-edit pass per step: {E} edits, mask {mask:#x} on the injected blocks of an inject=1 step, "
+                      f"{'NativeEditShard' if args.native else 'FrameShard'} on the loopback transport", flush=True)
+            else:
+                blocks = [bench.Block(cfg, lvl, inj, shard, gen, dev) for lvl, inj in workload.BLOCKS]
+                modes = [mode or shard.auto_mode(l[2], l[0]) for l in cfg.levels]
+                step = lambda inj_: bench.run_step(cfg, blocks, shard, inj_, w, exchange=mode)
             print(f"=== {'NATIVE executor, ' if args.native else ''}{'stand-in copies EXCLUDED, ' if args.no_copies else ''}rank {args.rank} of {args.world}, {cfg.name}: Kl={shard.Kl}, attention "
                   f"{'split+merge' if split else 'one-pass (bit-exact)'}, exchange per level {modes}", flush=True)
             if args.profile:
                 import cProfile
                 import pstats
                 for _ in range(3):
-                    bench.run_step(cfg, blocks, shard, False, w, exchange=mode)
+                    step(False)
                 torch.cuda.synchronize()
                 pr = cProfile.Profile()
                 pr.enable()
                 for _ in range(5):
-                    bench.run_step(cfg, blocks, shard, False, w, exchange=mode)
+                    step(False)
                 pr.disable()
                 torch.cuda.synchronize()
                 pstats.Stats(pr).sort_stats("cumulative").print_stats(45)
                 args.profile = False
             for inj in (False, True):
-                gpu, host = measure(lambda: bench.run_step(cfg, blocks, shard, inj, w, exchange=mode), args.reps, 3)
+                gpu, host = measure(lambda: step(inj), args.reps, 3)
                 med = statistics.median(gpu)
                 tag = f"wire model {wire[0]:g} us + bytes / {wire[1]:g} GB/s per link" if wire else "wire-less"
                 print(f"  step inject={int(inj)}: GPU {fmt(gpu)} us   host issue {fmt(host)} us   -> "
                       f"{args.single_ms * 1e3 / med:4.2f}x of the {args.single_ms} ms single-GPU step ({tag})",
                       flush=True)
-                if wire and args.native:   # the same step, wire off: the difference is the exchange time left exposed
+                if wire and (args.native or E > 1):   # the same step, wire off: the difference is the exchange time left exposed
                     for c in (comm, hcomm):
                         _lib.check(_lib.load().tf_comm_loopback_wire(c._h, 0.0, 0.0), "tf_comm_loopback_wire")
-                    gpu0, _ = measure(lambda: bench.run_step(cfg, blocks, shard, inj, w, exchange=mode), args.reps, 3)
+                    gpu0, _ = measure(lambda: step(inj), args.reps, 3)
                     for c in (comm, hcomm):
                         _lib.check(_lib.load().tf_comm_loopback_wire(c._h, wire[0], wire[1]), "tf_comm_loopback_wire")
                     med0 = statistics.median(gpu0)
                     print(f"    wire off: GPU {fmt(gpu0)} us -> exposed exchange time {med - med0:7.1f} us per step "
                           f"({(med - med0) / 16:5.1f} us per block)", flush=True)
             comm.bytes = 0
-            bench.run_step(cfg, blocks, shard, False, w, exchange=mode)
+            step(False)
             torch.cuda.synchronize()
             wire_us = comm.bytes / (args.link_gbs * 1e3) / min(args.world - 1, 7)
             if comm.bytes:
@@ -210,11 +273,19 @@ def main():
 
                     def pivotal():
                         scale = (b1.D // b1.h) ** -0.5
-                        state["h"] = shard.pivotal_block(b1.q, b1.k, b1.v, b1.h, scale, inj, b1.ext, mode=mode, inv_norm=True)
+                        if E > 1:
+                            state["h"] = shard.pivotal_block(b1.q, b1.k, b1.v, b1.h, scale, False, b1.ext, mode=mode,
+                                                             inv_norm=True, n_edits=E, inject_mask=mask if inj else 0)
+                        else:
+                            state["h"] = shard.pivotal_block(b1.q, b1.k, b1.v, b1.h, scale, inj, b1.ext, mode=mode,
+                                                             inv_norm=True)
 
                     def prop():
                         pe, ie, ke, reqs = state["h"]
-                        shard.propagate_all(b1.tgt, b1.res, pe, ie, ke, w, cfg.chunk, halo_reqs=reqs)
+                        if E > 1:
+                            shard.propagate_all(b1.tgt, b1.res, pe, ie, ke, w, cfg.chunk, halo_reqs=reqs, n_edits=E)
+                        else:
+                            shard.propagate_all(b1.tgt, b1.res, pe, ie, ke, w, cfg.chunk, halo_reqs=reqs)
                     g1, h1 = measure(pivotal, args.reps, 3)
                     g2, h2 = measure(prop, args.reps, 3)
                     print(f"  level {lvl} (S={b1.S}, D={b1.D}) inject={int(inj)} isolated block: pivotal GPU "
