@@ -346,6 +346,56 @@ TF_API int tf_ext_attn_run_plan(int K, int Kq, int run_n, int n_runs, int S, int
                          int flags, int dtype, char* buf, size_t len);
 
 /* ------------------------------------------------------------------------
+ * "Run + merge" for a MULTI-EDIT batch (additive to ABI 11): B = 1 + 2*n_edits branches [source | uncond_1 | cond_1 | ...],
+ * bit e of inject_mask = edit e (0-based) reads the source's q and k.  The composition of tf_ext_attn_fwd_edits_masked
+ * applied to a run: a run call computes, for the run's bank frames only, the partial results (unnormalised O, denominator,
+ * log2-domain shift) of EVERY edit's two bank branches, each edit under its own injection state, and -- without
+ * TF_ATTN_BANK_ONLY -- the source branch of the query frames, once and final, as tf_ext_attn_run does.
+ * tf_ext_attn_runs_merge_edits folds all runs of all 2E bank branches in slot order in ONE launch.
+ *
+ *   Launches of a run call: ONE V^T pre-pass over the run's frames of every branch the call reads (at the positions the
+ *   frames have in the image of the whole bank; key norms of the source and of the edits that do not inject), then every
+ *   edit through the launches of its own tf_ext_attn_run call -- the injecting edits first, then the others, ascending --
+ *   then the source launch.  Injecting edits take the DUAL run form where the single-edit run does; the four-bank form has no
+ *   partial epilogue: TF_ATTN_MULTI_V is TF_ERR_SHAPE, TF_ATTN_NO_MULTI_V is accepted and ignored.
+ *   q, k, v, out, strides: as tf_ext_attn_run, v and out addressed over all B branches (a bank-only call never touches their
+ *   source slabs).  compact: bit 0 = q, bit 1 = k is in the compact layout of tf_ext_attn_fwd_edits_part (slot 0 the
+ *   source, then (uncond, cond) of every NON-injecting edit, ascending); the two are separate, so a rank's remote runs read
+ *   its dense local q against the compact k of a receive buffer without a staging copy.
+ *   Refusals (TF_ERR_SHAPE, before anything touches the device): everything tf_ext_attn_run refuses; TF_ATTN_INJECT beside
+ *   a mask; mask bits at or above n_edits; n_edits outside 1 .. TF_MAX_EDITS; TF_ATTN_MULTI_V; compact outside 0 .. 3.
+ *   ws: ONE workspace per run set, tf_ext_attn_runs_edits_workspace_bytes -- the image and norm table of all B branches, one
+ *   header entry per run that carries the slot count of BOTH injection states (how far a run splits itself depends on the
+ *   edit's state; the merge picks per edit by inject_mask, which must be the run calls'), and the partial results
+ *   [2E][Kq][H][S][n_runs * slots][Dh + 8]: every edit's launches see the layout of a single-edit run set.
+ *   n_edits = 1 IS tf_ext_attn_run / tf_ext_attn_runs_merge (TF_ATTN_INJECT iff the mask is 1): same launches, same plan
+ *   tokens, same bits, same workspace size.
+ *
+ *   Identity: for every edit e the merged bank branches equal, bit for bit, the single-edit run set on
+ *   [source | uncond_e | cond_e] -- tf_ext_attn_run per run + tf_ext_attn_runs_merge with the same runs, the same flags and
+ *   edit e's injection flag -- and the source branch equals that run set's source branch bit for bit.  The result is a
+ *   function of the runs alone, not of issue order or streams.  It equals the oracle within the attention bound; it does NOT
+ *   equal the one-call multi-edit forms (tf_ext_attn_fwd_edits*) bit for bit.
+ *
+ * tf_ext_attn_run_edits_plan: the tokens of one run call -- vt_pack, per edit the ",run>" tokens of its own run call, the
+ * source token unless TF_ATTN_BANK_ONLY -- followed by merge[runs=N,edits=E].  Host only.
+ * ------------------------------------------------------------------------ */
+TF_API size_t tf_ext_attn_runs_edits_workspace_bytes(int K, int Kq, int S, int H, int Dh, int n_runs, int n_edits, int dtype);
+
+TF_API int tf_ext_attn_run_edits(const void* q, const void* k, const void* v, void* out,
+                          int K, int Kq, int q_frame0, int run_f0, int run_n, int run, int n_runs,
+                          int S, int H, int Dh, int64_t ld, const int64_t* strides,
+                          float scale, int flags, int dtype, int n_edits, unsigned inject_mask, int compact,
+                          void* ws, size_t ws_bytes, void* stream);
+
+TF_API int tf_ext_attn_runs_merge_edits(void* out, int K, int Kq, int S, int H, int Dh, int n_runs, int n_edits,
+                                 unsigned inject_mask, int64_t out_branch_stride, int64_t out_frame_stride,
+                                 int flags, int dtype, void* ws, size_t ws_bytes, void* stream);
+
+TF_API int tf_ext_attn_run_edits_plan(int K, int Kq, int run_n, int n_runs, int S, int H, int Dh, int n_edits,
+                               unsigned inject_mask, int flags, int dtype, char* buf, size_t len);
+
+/* ------------------------------------------------------------------------
  * Frames <-> heads re-sharding of the multi-GPU pivotal pass (no counterpart in the single-process reference;
  * tokenflow_amd/sharded.py).  Rank r sends head group w of its Kl keyframes' slabs to rank w:
  *   tf_head_pack:    send[w][f][i][s][0..hd)  = slab_i[f][s][w*hd .. (w+1)*hd)     i < ns slabs, each a
@@ -678,6 +728,7 @@ TF_API int tf_sendrecv_pivot(tf_comm* comm, const void* const* send, const int64
                                 follow behind it, and tf_ext_attn_runs_merge folds them: runs local, left, right in that slot order,
                                 whatever the schedule.  Equal bit for bit to tf_ext_attn_run + merge on the full tensors with the
                                 same runs, and to the oracle within the attention bound -- NOT to the one-call forms above. */
+#define TF_RANK_BANK_EDIT_RUNS 3  /* tf_rank_pivotal_edits only: TF_RANK_BANK_RUNS' schedule for a multi-edit batch (below) */
 #define TF_RANK_NO_HALO 16   /* or-ed into `mode`: the attention alone -- kfo_ext is a plain [3, Kl, S, H*Dh] output, piv_ext /
                                 inv_ext are not read (NULL allowed), no neighbour exchange (hosts whose cached attention
                                 output is not this one: the hook path caches it after the to_out projection) */
@@ -706,14 +757,17 @@ TF_API int tf_rank_halo_wait(tf_rank* rk, int slot, void* stream);
  *               TF_RANK_NO_HALO and tf_rank_halo_wait as for tf_rank_pivotal
  *   inject_mask: the injection state per edit, as tf_ext_attn_fwd_edits_masked (bit e = edit e uses the source's q and k).
  *               TF_ATTN_INJECT or a part flag in `flags`, a mask bit at or above n_edits, n_edits outside 1 .. TF_MAX_EDITS,
- *               TF_RANK_BANK_RUNS with n_edits > 1 (no multi-edit form exists), TF_RANK_HEADS with H % W != 0: TF_ERR_SHAPE;
+ *               TF_RANK_BANK_RUNS with n_edits > 1 (its multi-edit form is a mode of its own, TF_RANK_BANK_EDIT_RUNS),
+ *               TF_RANK_HEADS with H % W != 0: TF_ERR_SHAPE;
  *               a null pointer: TF_ERR_NULL.  All of that is checked before anything touches the device.
  *   ws        : tf_rank_pivotal_edits_workspace_bytes -- ONE size for both modes: the exchange buffers at their largest slab
  *               counts (6E slabs in the heads form, 4E in the bank form), the staging region of the compact q, and one
  *               attention workspace (tf_ext_attn_edits_workspace_bytes) each for the bank and the source part, which may run
- *               concurrently.
+ *               concurrently.  TF_RANK_BANK_EDIT_RUNS has a size query of its own, tf_rank_pivotal_edit_runs_workspace_bytes
+ *               (the bank form's exchange buffers and ONE run-set workspace, tf_ext_attn_runs_edits_workspace_bytes).
  *
- * n_edits = 1 IS tf_rank_pivotal with TF_ATTN_INJECT set iff the mask is 1: the same launches, the same bits.
+ * n_edits = 1 IS tf_rank_pivotal with TF_ATTN_INJECT set iff the mask is 1: the same launches, the same bits
+ * (TF_RANK_BANK_EDIT_RUNS with one edit is TF_RANK_BANK_RUNS).
  * One rank (comm = NULL): the inverse norms if asked, then tf_ext_attn_fwd_edits_masked straight into kfo_ext.
  * W > 1.  Compact slots: slot 0 is the source if any edit injects (any = 1), then (uncond, cond) of each of the n_non
  * non-injecting edits in ascending order -- the qk_compact layout of tf_ext_attn_fwd_edits_part.
@@ -731,6 +785,14 @@ TF_API int tf_rank_halo_wait(tf_rank* rk, int slot, void* stream);
  *                  first keyframe, Kq = Kl, qk_compact), the source part on the local tensors.  A MIXED mask first copies
  *                  the compact q slots into the staging region (the pack kernel with W = 1, one launch); a uniform mask
  *                  reads q in place.
+ *   TF_RANK_BANK_EDIT_RUNS  the schedule of TF_RANK_BANK_RUNS over the multi-edit run calls (any head count): the pack and
+ *                  the gather of TF_RANK_BANK -- (any + 2 n_non) + 2E slabs -- but the LOCAL run (tf_ext_attn_run_edits: the
+ *                  source branch and every edit's bank partials against the rank's own keyframes, q / k / v in place, dense)
+ *                  is forked onto the auxiliary compute stream behind the pack and in FRONT of the gather; behind the gather
+ *                  the remote runs (TF_ATTN_BANK_ONLY, k compact from the receive buffer, q dense from the local tensors:
+ *                  no staging copy under a mixed mask); join; tf_ext_attn_runs_merge_edits into the local slots of kfo_ext.
+ *                  Runs local, left, right in that slot order.  Per edit the bits of TF_RANK_BANK_RUNS on
+ *                  [source | uncond_e | cond_e]: within the attention bound of the oracle, NOT bit-equal to TF_RANK_BANK.
  *   Halo           ONE grouped tf_sendrecv_pivot of 2 + B messages: the pivots, the B branches of kfo_ext and the inverse
  *                  norms of the last local keyframe to slot 0 of rank r+1.
  *
@@ -739,11 +801,14 @@ TF_API int tf_rank_halo_wait(tf_rank* rk, int slot, void* stream);
  *   pack[ns=N] (pack+inv[ns=N] under TF_RANK_INV_NORM); qcompact[ns=N] where it happens; a2a[slabs=N] or gather[slabs=N]; the
  *   tokens of tf_ext_attn_edits_part_plan for the bank part, then for the source part (the source part is listed there also
  *   where it runs on the auxiliary stream); a2a[slabs=2E]; unpack[nb=2E]; halo[n=2+B] (absent under TF_RANK_NO_HALO and for
- *   one rank).  One rank: inv_norm under TF_RANK_INV_NORM, then the tokens of tf_ext_attn_edits_masked_plan.  n_edits = 1: the
+ *   one rank).  TF_RANK_BANK_EDIT_RUNS: pack[ns=N]; gather[slabs=N]; the run tokens of tf_ext_attn_run_edits_plan for the local
+ *   run (listed behind the gather, though it is issued in front of it), then for each remote run; merge[runs=R,edits=E];
+ *   halo[n=2+B].  One rank: inv_norm under TF_RANK_INV_NORM, then the tokens of tf_ext_attn_edits_masked_plan.  n_edits = 1: the
  *   sequence of tf_rank_pivotal in the same tokens (its attention tokens are those of tf_ext_attn_plan).
  * Returns the number of tokens, or a negative TF_ERR_* code.
  * ------------------------------------------------------------------------ */
 TF_API size_t tf_rank_pivotal_edits_workspace_bytes(const tf_rank* rk, int S, int H, int Dh, int n_edits, int dtype);
+TF_API size_t tf_rank_pivotal_edit_runs_workspace_bytes(const tf_rank* rk, int S, int H, int Dh, int n_edits, int dtype);
 TF_API int tf_rank_pivotal_edits(tf_rank* rk, const void* q, const void* k, const void* v, const int64_t* strides,
                           void* piv_ext, float* inv_ext, void* kfo_ext, int S, int H, int Dh, float scale, int flags,
                           int dtype, int mode, int slot, int n_edits, unsigned inject_mask,

@@ -27,6 +27,7 @@ ABI_VERSION = 11
 TF_MAX_EDITS = 8
 TF_RANK_HEADS, TF_RANK_BANK, TF_RANK_SLOTS, TF_RANK_NO_HALO, TF_RANK_INV_NORM = 0, 1, 64, 16, 32
 TF_RANK_BANK_RUNS = 2
+TF_RANK_BANK_EDIT_RUNS = 3   # tf_rank_pivotal_edits: the bank in runs for a multi-edit batch
 TF_ERR_COMM = -6
 
 _c = ctypes
@@ -72,6 +73,13 @@ _SIGNATURES = {
     "tf_ext_attn_runs_merge": (_c.c_int, [_c.c_void_p] + [_c.c_int] * 6 + [_c.c_int64, _c.c_int64, _c.c_int, _c.c_int,
                                           _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "tf_ext_attn_run_plan": (_c.c_int, [_c.c_int] * 9 + [_c.c_char_p, _c.c_size_t]),
+    # run + merge for a multi-edit batch (additive to ABI 11)
+    "tf_ext_attn_runs_edits_workspace_bytes": (_c.c_size_t, [_c.c_int] * 8),
+    "tf_ext_attn_run_edits": (_c.c_int, [_c.c_void_p] * 4 + [_c.c_int] * 10 + [_c.c_int64, _c.c_void_p, _c.c_float, _c.c_int,
+                                         _c.c_int, _c.c_int, _c.c_uint, _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "tf_ext_attn_runs_merge_edits": (_c.c_int, [_c.c_void_p] + [_c.c_int] * 7 + [_c.c_uint, _c.c_int64, _c.c_int64, _c.c_int,
+                                                _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "tf_ext_attn_run_edits_plan": (_c.c_int, [_c.c_int] * 8 + [_c.c_uint, _c.c_int, _c.c_int, _c.c_char_p, _c.c_size_t]),
     "tf_head_pack": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p] + [_c.c_int] * 4 + [_c.c_int64, _c.c_int,
                                 _c.c_void_p]),
     "tf_head_unpack": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p] + [_c.c_int] * 5 + [_c.c_int64, _c.c_int,
@@ -122,6 +130,7 @@ _SIGNATURES = {
     "tf_rank_halo_wait": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p]),
     # the rank executor for a multi-edit batch (additive to ABI 11)
     "tf_rank_pivotal_edits_workspace_bytes": (_c.c_size_t, [_c.c_void_p] + [_c.c_int] * 5),
+    "tf_rank_pivotal_edit_runs_workspace_bytes": (_c.c_size_t, [_c.c_void_p] + [_c.c_int] * 5),
     "tf_rank_pivotal_edits": (_c.c_int, [_c.c_void_p] * 8 + [_c.c_int] * 3 + [_c.c_float] + [_c.c_int] * 5 + [_c.c_uint] +
                               [_c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "tf_rank_pivotal_edits_plan": (_c.c_int, [_c.c_int] * 7 + [_c.c_uint] + [_c.c_int] * 3 + [_c.c_char_p, _c.c_size_t]),

@@ -851,6 +851,52 @@ __global__ __launch_bounds__(256) void attn_runs_merge_kernel(const float* __res
     }
 }
 
+// Runs form of a multi-edit batch (tf_ext_attn_run_edits / tf_ext_attn_runs_merge_edits), merge: the 2E bank branches of ALL
+// edits in one launch.  partials [2E][Kq][H][S][n_runs * spr][DH + 8]: edit e's two banks are exactly the region a single-edit
+// run set has.  How many slots a run filled depends on the edit's injection state (split_plan's `dual`), so hdr[r] carries
+// BOTH counts -- bits 0-15 for an edit that does not inject, bits 16-31 for one that does -- and bit e of inject_mask picks
+// edit e's.  The same sums in the same slot order as attn_runs_merge_kernel.
+template <typename T>
+__global__ __launch_bounds__(256) void attn_runs_merge_edits_kernel(const float* __restrict__ partials,
+                                                                    const int* __restrict__ hdr, void* __restrict__ out, int Kq,
+                                                                    int S, int H, int DH, int n_runs, int spr, int n_banks,
+                                                                    unsigned inject_mask, int out_f32, int64_t o_bs,
+                                                                    int64_t o_fs) {
+    typedef typename T::elem E;
+    typedef typename T::vec4 vec4;
+    const int PS = DH + 8, dq = DH >> 2;
+    const int64_t total = (int64_t)n_banks * Kq * H * S * dq;
+    for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < total; g += (int64_t)gridDim.x * 256) {
+        const int64_t R = g / dq;                 // ((vbank*Kq + f)*H + h)*S + q, vbank = 2 * edit + (0 uncond, 1 cond)
+        const int d0 = (int)(g - R * dq) * 4;
+        const int q = (int)(R % S);
+        int64_t t = R / S;
+        const int h = (int)(t % H);
+        t /= H;
+        const int f = (int)(t % Kq), vbank = (int)(t / Kq);
+        const int hsh = ((inject_mask >> (vbank >> 1)) & 1u) ? 16 : 0;
+        const float* pr = partials + R * ((int64_t)n_runs * spr) * PS;
+        float M = -INFINITY;
+        for (int r = 0; r < n_runs; ++r) {
+            const int ns = min((hdr[r] >> hsh) & 0xffff, spr);
+            for (int sg = 0; sg < ns; ++sg) M = fmaxf(M, pr[(r * spr + sg) * PS + DH + 1]);
+        }
+        f32x4 num = {0.f, 0.f, 0.f, 0.f};
+        float den = 0.f;
+        for (int r = 0; r < n_runs; ++r) {
+            const int ns = min((hdr[r] >> hsh) & 0xffff, spr);
+            for (int sg = 0; sg < ns; ++sg) {
+                const float* ps = pr + (r * spr + sg) * PS;
+                const float w = __builtin_amdgcn_exp2f(ps[DH + 1] - M);
+                num += *reinterpret_cast<const f32x4*>(ps + d0) * w;
+                den = fmaf(ps[DH], w, den);
+            }
+        }
+        const float inv = 1.0f / den;
+        store_out4<E, vec4>(out, (1 + vbank) * o_bs + f * o_fs + (int64_t)q * (H * DH) + h * DH + d0, num * inv, out_f32);
+    }
+}
+
 // How many runs of bank frames a bank problem is split into.  The grid of a sharded rank or of a small level has
 // too few waves to fill the chip (8-GPU rank at cfg2 level 0: 2 waves per SIMD, level 1: 0.5; single GPU at the
 // 16x16 level: 1): split until it has `occ` waves per SIMD, while a run keeps at least 2 tiles.
@@ -2903,7 +2949,7 @@ namespace {
 
 struct RunsLayout {
     int Spad, spr;   // spr = slots per run
-    size_t knorm_off, hdr_off, part_off, bytes;
+    size_t knorm_off, hdr_off, part_off, part_edit, bytes;   // part_edit: floats of ONE edit's partial results
 };
 
 // Slots a run owns: the largest split any run of this bank can take (split_plan never grows when the frame count shrinks).
@@ -2912,14 +2958,19 @@ static int runs_slots_per_run(int K, int Kq, int S, int H, int Dh) {
     return a > b ? a : b;
 }
 
-static RunsLayout runs_layout(int K, int Kq, int S, int H, int Dh, int n_runs) {
+// n_edits > 1 (tf_ext_attn_run_edits): the image and the norm table of all 1 + 2E branches, ONE header of n_runs ints (both
+// injection states' slot counts in each, see attn_runs_merge_edits_kernel) and the partial results of every edit one behind the
+// other, [2E][Kq][H][S][n_runs * spr][Dh + 8]: an edit's launches see the layout of a single-edit run set.
+static RunsLayout runs_layout(int K, int Kq, int S, int H, int Dh, int n_runs, int n_edits = 1) {
     RunsLayout L;
+    const int branches = 1 + 2 * n_edits;
     L.Spad = ((S + 127) / 128) * 128;
     L.spr = runs_slots_per_run(K, Kq, S, H, Dh);
-    L.knorm_off = (vt_bytes(K, L.Spad, H, Dh) + 255) & ~(size_t)255;
-    L.hdr_off = L.knorm_off + (((size_t)3 * H * K * (L.Spad / 64) * sizeof(float) + 255) & ~(size_t)255);
+    L.knorm_off = (vt_bytes(K, L.Spad, H, Dh, branches) + 255) & ~(size_t)255;
+    L.hdr_off = L.knorm_off + (((size_t)branches * H * K * (L.Spad / 64) * sizeof(float) + 255) & ~(size_t)255);
     L.part_off = L.hdr_off + (((size_t)n_runs * sizeof(int) + 255) & ~(size_t)255);
-    L.bytes = L.part_off + (size_t)2 * Kq * H * S * n_runs * L.spr * (Dh + 8) * sizeof(float);
+    L.part_edit = (size_t)2 * Kq * H * S * n_runs * L.spr * (Dh + 8);
+    L.bytes = L.part_off + (size_t)n_edits * L.part_edit * sizeof(float);
     return L;
 }
 
@@ -2935,6 +2986,163 @@ static int runs_check_shape(const char* fn, int K, int Kq, int S, int H, int Dh,
 constexpr int RUN_REFUSED = TF_ATTN_SOURCE_ONLY | TF_ATTN_FUSED | TF_ATTN_HINT_QW(7) | TF_ATTN_HINT_KW(7) | TF_ATTN_HINT_QB2 |
                             TF_ATTN_PRECISE_P | TF_ATTN_NO_PRECISE_P;
 
+// One part of a multi-edit run call (tf_ext_attn_run_edits) as seen by the single-edit run call that computes it: the caller
+// has moved the base pointers of q / k / v / out to the edit's slabs and packed the run's frames of every branch; the launches
+// read the image (and, unless the edit injects, the norm table) `shift` branches in and leave the partial results in the
+// edit's own region.
+struct RunEditsPart {
+    int n_edits;    // edits of the workspace layout
+    int edit;       // whose partial region: shift = 2 * edit
+    int src_only;   // the source branch of the query frames alone (edit = 0)
+};
+
+// What a run call checks before anything touches the device.
+static int attn_run_check(const char* fn, const void* q, const void* k, const void* v, const void* out, int K, int Kq,
+                          int q_frame0, int run_f0, int run_n, int run, int n_runs, int S, int H, int Dh, int64_t ld,
+                          const int64_t* strides, int flags, int dtype, const void* ws, size_t ws_bytes, int n_edits) {
+    TF_ARG(q && k && v && out && ws && strides, TF_ERR_NULL, "%s: null pointer", fn);
+    if (const int rc = runs_check_shape(fn, K, Kq, S, H, Dh, n_runs, dtype)) return rc;
+    TF_ARG(ld >= (int64_t)H * Dh && ld % 8 == 0, TF_ERR_SHAPE, "%s: ld=%lld (a multiple of 8, >= H*Dh)", fn, (long long)ld);
+    TF_ARG(q_frame0 >= 0 && q_frame0 + Kq <= K, TF_ERR_SHAPE, "%s: query frames [%d, %d) outside the %d-frame bank", fn,
+           q_frame0, q_frame0 + Kq, K);
+    TF_ARG(run >= 0 && run < n_runs, TF_ERR_SHAPE, "%s: run %d of %d", fn, run, n_runs);
+    TF_ARG(run_n >= 1 && run_f0 >= 0 && run_f0 <= K - run_n, TF_ERR_SHAPE,
+           "%s: run of frames [%d, %d) empty or outside the %d-frame bank", fn, run_f0, run_f0 + run_n, K);
+    TF_ARG(!(flags & RUN_REFUSED), TF_ERR_SHAPE,
+           "%s: flags 0x%x -- TF_ATTN_SOURCE_ONLY, TF_ATTN_FUSED and the fused kernel's hints have no run form", fn,
+           flags & RUN_REFUSED);
+    const bool bank_only = (flags & TF_ATTN_BANK_ONLY) != 0;
+    TF_ARG(bank_only || (q_frame0 >= run_f0 && q_frame0 + Kq <= run_f0 + run_n), TF_ERR_SHAPE,
+           "%s: the source branch needs the query frames [%d, %d) inside the run [%d, %d) "
+           "(TF_ATTN_BANK_ONLY for the other runs)", fn, q_frame0, q_frame0 + Kq, run_f0, run_f0 + run_n);
+    const int64_t ld_q = strides[8];
+    TF_ARG(ld_q >= (int64_t)H * Dh && ld_q % 8 == 0, TF_ERR_SHAPE, "%s: q token stride %lld (a multiple of 8, >= H*Dh)", fn,
+           (long long)ld_q);
+    for (int i = 0; i < 8; ++i)
+        TF_ARG(strides[i] % 8 == 0 &&
+                   (i & 1 ? strides[i] >= (int64_t)(S - 1) * (i < 2 ? ld_q : i < 6 ? ld : (int64_t)H * Dh) : true),
+               TF_ERR_SHAPE, "%s: stride %d = %lld (multiples of 8 elements; a frame holds S token rows)", fn, i,
+               (long long)strides[i]);
+    TF_ARG(tf_aligned16(q) && tf_aligned16(k) && tf_aligned16(v) && tf_aligned16(out) && tf_aligned16(ws), TF_ERR_ALIGN,
+           "%s: tensors not 16-byte aligned", fn);
+    const size_t need = runs_layout(K, Kq, S, H, Dh, n_runs, n_edits).bytes;
+    TF_ARG(ws_bytes >= need, TF_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", fn, ws_bytes, need);
+    return 0;
+}
+
+int attn_run_core(const char* fn, const void* q, const void* k, const void* v, void* out, int K, int Kq, int q_frame0,
+                  int run_f0, int run_n, int run, int n_runs, int S, int H, int Dh, int64_t ld, const int64_t* strides,
+                  float scale, int flags, int dtype, void* ws, size_t ws_bytes, void* stream, const RunEditsPart* ed) {
+    const int n_edits = ed ? ed->n_edits : 1;
+    if (const int rc = attn_run_check(fn, q, k, v, out, K, Kq, q_frame0, run_f0, run_n, run, n_runs, S, H, Dh, ld, strides, flags,
+                                      dtype, ws, ws_bytes, n_edits))
+        return rc;
+    const bool bank_only = (flags & TF_ATTN_BANK_ONLY) != 0;
+    const int64_t ld_q = strides[8];
+    const RunsLayout L = runs_layout(K, Kq, S, H, Dh, n_runs, n_edits);
+    const int shift = ed ? 2 * ed->edit : 0;
+
+    unsigned char* const w8 = static_cast<unsigned char*>(ws);
+    const int ppf = L.Spad / 64;
+    AttnParams p{};
+    // the frame window is folded into K and the base pointers: the kernels see a bank of run_n frames that starts at run_f0
+    // (frame f of the caller's k / v lives at base + f * frame stride; the V^T image and the norm table keep the whole
+    // bank's row strides, p.Kb)
+    p.q = q;
+    p.k = static_cast<const unsigned char*>(k) + (int64_t)run_f0 * strides[3] * 2;
+    const void* v_run = static_cast<const unsigned char*>(v) + (int64_t)run_f0 * strides[5] * 2;
+    p.inject = (flags & TF_ATTN_INJECT) ? 1 : 0;
+    // an edit's launches read the image `shift` branches in; its key norms too, unless the keys are the source's (injection)
+    p.vt = w8 + vt_bytes(K, L.Spad, H, Dh, shift) + (size_t)run_f0 * L.Spad * 2;
+    p.knorm2 = reinterpret_cast<const float*>(w8 + L.knorm_off) + (p.inject ? 0 : (size_t)shift * H * K * ppf) +
+               (size_t)run_f0 * ppf;
+    p.out = out;
+    p.K = run_n;
+    p.Kb = K;
+    p.Kq = Kq;
+    p.q_frame0 = bank_only ? 0 : q_frame0 - run_f0;
+    p.S = S;
+    p.H = H;
+    p.Spad = L.Spad;
+    p.nQT = (S + 127) / 128;
+    p.part = (ed && ed->src_only) ? TF_ATTN_SOURCE_ONLY : bank_only ? TF_ATTN_BANK_ONLY : 0;
+    p.fold = (flags & TF_ATTN_FOLD_SCALE) ? 1 : 0;
+    p.out_f32 = (flags & TF_ATTN_OUT_F32) ? 1 : 0;
+    const int ns = split_plan(run_n, Kq, S, H, Dh, p.inject != 0, p.part, !(flags & TF_ATTN_NO_SPLIT));
+    p.nseg = ns < L.spr ? ns : L.spr;
+    p.pslots = n_runs * L.spr;
+    p.run = 1;
+    p.run_hdr = reinterpret_cast<int*>(w8 + L.hdr_off) + run;
+    p.bit_stable = 1;   // the kernel choice of a run is a function of its arguments: the mixed-shape form only on TF_ATTN_HINT_MIX
+    p.mix = (flags & TF_ATTN_HINT_MIX) ? 1 : 0;
+    p.partials = reinterpret_cast<float*>(w8 + L.part_off) + (ed ? (size_t)ed->edit * L.part_edit : 0) +
+                 (size_t)run * L.spr * (Dh + 8);
+    p.ld = ld;
+    p.ld_q = ld_q;
+    p.q_bs = strides[0];
+    p.q_fs = strides[1];
+    p.k_bs = strides[2];
+    p.k_fs = strides[3];
+    p.v_bs = strides[4];
+    p.v_fs = strides[5];
+    p.o_bs = strides[6];
+    p.o_fs = strides[7];
+    p.c = (float)((double)scale * 1.4426950408889634);
+    p.gap = 2;
+    p.no_pack = ed ? 1 : 0;   // the composing call has packed the run's frames of every branch
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    return dtype == TF_BF16 ? dispatch_dh<BF16>(Dh, p, v_run, st) : dispatch_dh<F16>(Dh, p, v_run, st);
+}
+
+int attn_runs_merge_core(const char* fn, void* out, int K, int Kq, int S, int H, int Dh, int n_runs, int n_edits,
+                         unsigned inject_mask, int64_t out_branch_stride, int64_t out_frame_stride, int flags, int dtype,
+                         void* ws, size_t ws_bytes, void* stream) {
+    TF_ARG(out && ws, TF_ERR_NULL, "%s: null pointer", fn);
+    if (const int rc = runs_check_shape(fn, K, Kq, S, H, Dh, n_runs, dtype)) return rc;
+    TF_ARG(out_branch_stride % 8 == 0 && out_frame_stride % 8 == 0 && out_frame_stride >= (int64_t)(S - 1) * H * Dh,
+           TF_ERR_SHAPE, "%s: out strides %lld, %lld (multiples of 8 elements; a frame holds S token rows)", fn,
+           (long long)out_branch_stride, (long long)out_frame_stride);
+    TF_ARG(tf_aligned16(out) && tf_aligned16(ws), TF_ERR_ALIGN, "%s: tensors not 16-byte aligned", fn);
+    const RunsLayout L = runs_layout(K, Kq, S, H, Dh, n_runs, n_edits);
+    TF_ARG(ws_bytes >= L.bytes, TF_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", fn, ws_bytes, L.bytes);
+    if (n_edits == 1 ? tf_plan_note("merge[runs=%d]", n_runs) : tf_plan_note("merge[runs=%d,edits=%d]", n_runs, n_edits))
+        return 0;
+    unsigned char* const w8 = static_cast<unsigned char*>(ws);
+    const int64_t total = (int64_t)2 * n_edits * Kq * H * S * (Dh / 4);
+    const int64_t blocks = (total + 255) / 256;
+    const dim3 grid((unsigned)(blocks < 8192 ? blocks : 8192));
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const float* part = reinterpret_cast<const float*>(w8 + L.part_off);
+    const int* hdr = reinterpret_cast<const int*>(w8 + L.hdr_off);
+    const int f32 = (flags & TF_ATTN_OUT_F32) ? 1 : 0;
+    if (n_edits > 1) {
+        if (dtype == TF_BF16)
+            hipLaunchKernelGGL(attn_runs_merge_edits_kernel<BF16>, grid, dim3(256), 0, st, part, hdr, out, Kq, S, H, Dh, n_runs,
+                               L.spr, 2 * n_edits, inject_mask, f32, out_branch_stride, out_frame_stride);
+        else
+            hipLaunchKernelGGL(attn_runs_merge_edits_kernel<F16>, grid, dim3(256), 0, st, part, hdr, out, Kq, S, H, Dh, n_runs,
+                               L.spr, 2 * n_edits, inject_mask, f32, out_branch_stride, out_frame_stride);
+    } else if (dtype == TF_BF16)
+        hipLaunchKernelGGL(attn_runs_merge_kernel<BF16>, grid, dim3(256), 0, st, part, hdr, out, Kq, S, H, Dh, n_runs, L.spr, f32,
+                           out_branch_stride, out_frame_stride);
+    else
+        hipLaunchKernelGGL(attn_runs_merge_kernel<F16>, grid, dim3(256), 0, st, part, hdr, out, Kq, S, H, Dh, n_runs, L.spr, f32,
+                           out_branch_stride, out_frame_stride);
+    TF_LAUNCH_CHECK(fn);
+    return 0;
+}
+
+// What the multi-edit run and merge calls check of their own arguments.
+static int run_edits_check(const char* fn, int n_edits, unsigned inject_mask, int flags) {
+    TF_ARG(n_edits >= 1 && n_edits <= TF_MAX_EDITS, TF_ERR_SHAPE, "%s: n_edits=%d (1 .. %d)", fn, n_edits, TF_MAX_EDITS);
+    TF_ARG(!(flags & TF_ATTN_INJECT), TF_ERR_SHAPE, "%s: TF_ATTN_INJECT beside a mask (the mask is the injection state)", fn);
+    TF_ARG(!(inject_mask & ~((1u << n_edits) - 1u)), TF_ERR_SHAPE, "%s: inject_mask=0x%x has bits at or above n_edits=%d", fn,
+           inject_mask, n_edits);
+    TF_ARG(!(flags & TF_ATTN_MULTI_V), TF_ERR_SHAPE,
+           "%s: TF_ATTN_MULTI_V -- the four-bank kernel has no partial epilogue, a run takes the DUAL composition", fn);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" size_t tf_ext_attn_runs_workspace_bytes(int K, int Kq, int S, int H, int Dh, int n_runs, int dtype) {
@@ -2947,110 +3155,110 @@ extern "C" int tf_ext_attn_run(const void* q, const void* k, const void* v, void
                                int run_f0, int run_n, int run, int n_runs, int S, int H, int Dh, int64_t ld,
                                const int64_t* strides, float scale, int flags, int dtype, void* ws, size_t ws_bytes,
                                void* stream) {
-    TF_ARG(q && k && v && out && ws && strides, TF_ERR_NULL, "tf_ext_attn_run: null pointer");
-    if (const int rc = runs_check_shape("tf_ext_attn_run", K, Kq, S, H, Dh, n_runs, dtype)) return rc;
-    TF_ARG(ld >= (int64_t)H * Dh && ld % 8 == 0, TF_ERR_SHAPE, "tf_ext_attn_run: ld=%lld (a multiple of 8, >= H*Dh)",
-           (long long)ld);
-    TF_ARG(q_frame0 >= 0 && q_frame0 + Kq <= K, TF_ERR_SHAPE,
-           "tf_ext_attn_run: query frames [%d, %d) outside the %d-frame bank", q_frame0, q_frame0 + Kq, K);
-    TF_ARG(run >= 0 && run < n_runs, TF_ERR_SHAPE, "tf_ext_attn_run: run %d of %d", run, n_runs);
-    TF_ARG(run_n >= 1 && run_f0 >= 0 && run_f0 <= K - run_n, TF_ERR_SHAPE,
-           "tf_ext_attn_run: run of frames [%d, %d) empty or outside the %d-frame bank", run_f0, run_f0 + run_n, K);
-    TF_ARG(!(flags & RUN_REFUSED), TF_ERR_SHAPE,
-           "tf_ext_attn_run: flags 0x%x -- TF_ATTN_SOURCE_ONLY, TF_ATTN_FUSED and the fused kernel's hints have no run form",
-           flags & RUN_REFUSED);
-    const bool bank_only = (flags & TF_ATTN_BANK_ONLY) != 0;
-    TF_ARG(bank_only || (q_frame0 >= run_f0 && q_frame0 + Kq <= run_f0 + run_n), TF_ERR_SHAPE,
-           "tf_ext_attn_run: the source branch needs the query frames [%d, %d) inside the run [%d, %d) "
-           "(TF_ATTN_BANK_ONLY for the other runs)", q_frame0, q_frame0 + Kq, run_f0, run_f0 + run_n);
-    const int64_t ld_q = strides[8];
-    TF_ARG(ld_q >= (int64_t)H * Dh && ld_q % 8 == 0, TF_ERR_SHAPE,
-           "tf_ext_attn_run: q token stride %lld (a multiple of 8, >= H*Dh)", (long long)ld_q);
-    for (int i = 0; i < 8; ++i)
-        TF_ARG(strides[i] % 8 == 0 &&
-                   (i & 1 ? strides[i] >= (int64_t)(S - 1) * (i < 2 ? ld_q : i < 6 ? ld : (int64_t)H * Dh) : true),
-               TF_ERR_SHAPE, "tf_ext_attn_run: stride %d = %lld (multiples of 8 elements; a frame holds S token rows)", i,
-               (long long)strides[i]);
-    TF_ARG(tf_aligned16(q) && tf_aligned16(k) && tf_aligned16(v) && tf_aligned16(out) && tf_aligned16(ws), TF_ERR_ALIGN,
-           "tf_ext_attn_run: tensors not 16-byte aligned");
-    const RunsLayout L = runs_layout(K, Kq, S, H, Dh, n_runs);
-    TF_ARG(ws_bytes >= L.bytes, TF_ERR_WORKSPACE, "tf_ext_attn_run: workspace %zu < %zu bytes", ws_bytes, L.bytes);
-
-    unsigned char* const w8 = static_cast<unsigned char*>(ws);
-    const int ppf = L.Spad / 64;
-    AttnParams p{};
-    // the frame window is folded into K and the base pointers: the kernels see a bank of run_n frames that starts at run_f0
-    // (frame f of the caller's k / v lives at base + f * frame stride; the V^T image and the norm table keep the whole
-    // bank's row strides, p.Kb)
-    p.q = q;
-    p.k = static_cast<const unsigned char*>(k) + (int64_t)run_f0 * strides[3] * 2;
-    const void* v_run = static_cast<const unsigned char*>(v) + (int64_t)run_f0 * strides[5] * 2;
-    p.vt = w8 + (size_t)run_f0 * L.Spad * 2;
-    p.knorm2 = reinterpret_cast<const float*>(w8 + L.knorm_off) + (size_t)run_f0 * ppf;
-    p.out = out;
-    p.K = run_n;
-    p.Kb = K;
-    p.Kq = Kq;
-    p.q_frame0 = bank_only ? 0 : q_frame0 - run_f0;
-    p.S = S;
-    p.H = H;
-    p.Spad = L.Spad;
-    p.nQT = (S + 127) / 128;
-    p.inject = (flags & TF_ATTN_INJECT) ? 1 : 0;
-    p.part = bank_only ? TF_ATTN_BANK_ONLY : 0;
-    p.fold = (flags & TF_ATTN_FOLD_SCALE) ? 1 : 0;
-    p.out_f32 = (flags & TF_ATTN_OUT_F32) ? 1 : 0;
-    const int ns = split_plan(run_n, Kq, S, H, Dh, p.inject != 0, p.part, !(flags & TF_ATTN_NO_SPLIT));
-    p.nseg = ns < L.spr ? ns : L.spr;
-    p.pslots = n_runs * L.spr;
-    p.run = 1;
-    p.run_hdr = reinterpret_cast<int*>(w8 + L.hdr_off) + run;
-    p.bit_stable = 1;   // the kernel choice of a run is a function of its arguments: the mixed-shape form only on TF_ATTN_HINT_MIX
-    p.mix = (flags & TF_ATTN_HINT_MIX) ? 1 : 0;
-    p.partials = reinterpret_cast<float*>(w8 + L.part_off) + (size_t)run * L.spr * (Dh + 8);
-    p.ld = ld;
-    p.ld_q = ld_q;
-    p.q_bs = strides[0];
-    p.q_fs = strides[1];
-    p.k_bs = strides[2];
-    p.k_fs = strides[3];
-    p.v_bs = strides[4];
-    p.v_fs = strides[5];
-    p.o_bs = strides[6];
-    p.o_fs = strides[7];
-    p.c = (float)((double)scale * 1.4426950408889634);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    return dtype == TF_BF16 ? dispatch_dh<BF16>(Dh, p, v_run, st) : dispatch_dh<F16>(Dh, p, v_run, st);
+    return attn_run_core("tf_ext_attn_run", q, k, v, out, K, Kq, q_frame0, run_f0, run_n, run, n_runs, S, H, Dh, ld, strides,
+                         scale, flags, dtype, ws, ws_bytes, stream, nullptr);
 }
 
 extern "C" int tf_ext_attn_runs_merge(void* out, int K, int Kq, int S, int H, int Dh, int n_runs, int64_t out_branch_stride,
                                       int64_t out_frame_stride, int flags, int dtype, void* ws, size_t ws_bytes,
                                       void* stream) {
-    TF_ARG(out && ws, TF_ERR_NULL, "tf_ext_attn_runs_merge: null pointer");
-    if (const int rc = runs_check_shape("tf_ext_attn_runs_merge", K, Kq, S, H, Dh, n_runs, dtype)) return rc;
-    TF_ARG(out_branch_stride % 8 == 0 && out_frame_stride % 8 == 0 && out_frame_stride >= (int64_t)(S - 1) * H * Dh,
-           TF_ERR_SHAPE, "tf_ext_attn_runs_merge: out strides %lld, %lld (multiples of 8 elements; a frame holds S token rows)",
-           (long long)out_branch_stride, (long long)out_frame_stride);
-    TF_ARG(tf_aligned16(out) && tf_aligned16(ws), TF_ERR_ALIGN, "tf_ext_attn_runs_merge: tensors not 16-byte aligned");
-    const RunsLayout L = runs_layout(K, Kq, S, H, Dh, n_runs);
-    TF_ARG(ws_bytes >= L.bytes, TF_ERR_WORKSPACE, "tf_ext_attn_runs_merge: workspace %zu < %zu bytes", ws_bytes, L.bytes);
-    if (tf_plan_note("merge[runs=%d]", n_runs)) return 0;
+    return attn_runs_merge_core("tf_ext_attn_runs_merge", out, K, Kq, S, H, Dh, n_runs, 1, 0u, out_branch_stride,
+                                out_frame_stride, flags, dtype, ws, ws_bytes, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Runs form of a multi-edit batch (include/tokenflow_hip.h): attn_fwd_edits_masked applied to a run.  ONE V^T pre-pass per run
+// call over the run's frames of every branch the call reads, at their positions in the image of the whole bank (key norms of
+// the source and of the edits that do not inject; in a bank-only call under injection the first injecting branch computes
+// the source's), then every edit's bank branches through the launches of its own tf_ext_attn_run call -- base pointers 2e
+// branches in: q / k unless injected, v, out, the image, the norm table, the edit's partial region -- then the source branch.
+// No fused kernel, no four-bank form: neither has a partial epilogue.
+extern "C" size_t tf_ext_attn_runs_edits_workspace_bytes(int K, int Kq, int S, int H, int Dh, int n_runs, int n_edits,
+                                                         int dtype) {
+    if (n_edits < 1 || n_edits > TF_MAX_EDITS) return 0;
+    if (K <= 0 || Kq <= 0 || Kq > K || S <= 0 || H <= 0 || n_runs <= 0 || n_runs > K || dtype == TF_F32) return 0;
+    if (!(Dh == 40 || Dh == 64 || Dh == 80 || Dh == 160)) return 0;
+    return runs_layout(K, Kq, S, H, Dh, n_runs, n_edits).bytes;
+}
+
+extern "C" int tf_ext_attn_run_edits(const void* q, const void* k, const void* v, void* out, int K, int Kq, int q_frame0,
+                                     int run_f0, int run_n, int run, int n_runs, int S, int H, int Dh, int64_t ld,
+                                     const int64_t* strides, float scale, int flags, int dtype, int n_edits,
+                                     unsigned inject_mask, int compact, void* ws, size_t ws_bytes, void* stream) {
+    const char* const fn = "tf_ext_attn_run_edits";
+    if (const int rc = run_edits_check(fn, n_edits, inject_mask, flags)) return rc;
+    TF_ARG(compact >= 0 && compact <= 3, TF_ERR_SHAPE, "%s: compact=%d (bit 0: q, bit 1: k)", fn, compact);
+    const int base = flags & ~(TF_ATTN_NO_MULTI_V | TF_ATTN_BANK_ONLY);
+    const int part = flags & TF_ATTN_BANK_ONLY;
+    if (n_edits == 1)   // today's layout, today's launches (the compact q / k of one edit is the dense one as far as it is read)
+        return attn_run_core(fn, q, k, v, out, K, Kq, q_frame0, run_f0, run_n, run, n_runs, S, H, Dh, ld, strides, scale,
+                             base | part | (inject_mask ? TF_ATTN_INJECT : 0), dtype, ws, ws_bytes, stream, nullptr);
+    if (const int rc = attn_run_check(fn, q, k, v, out, K, Kq, q_frame0, run_f0, run_n, run, n_runs, S, H, Dh, ld, strides,
+                                      base | part, dtype, ws, ws_bytes, n_edits))
+        return rc;
+    const int B = 1 + 2 * n_edits;
+    const bool do_src = !part;
+    int inj_e[TF_MAX_EDITS], non_e[TF_MAX_EDITS], n_inj = 0, n_non = 0;   // the injecting / the other edits, ascending
+    int c_sh[TF_MAX_EDITS];   // compact q / k: slots in front of edit e's uncond slot, minus 1 (an injecting edit reads slot 0)
+    for (int e = 0; e < n_edits; ++e) {
+        c_sh[e] = 2 * n_non;
+        ((inject_mask >> e) & 1u) ? inj_e[n_inj++] = e : non_e[n_non++] = e;
+    }
+    const RunsLayout L = runs_layout(K, Kq, S, H, Dh, n_runs, n_edits);
     unsigned char* const w8 = static_cast<unsigned char*>(ws);
-    const int64_t total = (int64_t)2 * Kq * H * S * (Dh / 4);
-    const int64_t blocks = (total + 255) / 256;
-    const dim3 grid((unsigned)(blocks < 8192 ? blocks : 8192));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const float* part = reinterpret_cast<const float*>(w8 + L.part_off);
-    const int* hdr = reinterpret_cast<const int*>(w8 + L.hdr_off);
-    const int f32 = (flags & TF_ATTN_OUT_F32) ? 1 : 0;
-    if (dtype == TF_BF16)
-        hipLaunchKernelGGL(attn_runs_merge_kernel<BF16>, grid, dim3(256), 0, st, part, hdr, out, Kq, S, H, Dh, n_runs, L.spr, f32,
-                           out_branch_stride, out_frame_stride);
-    else
-        hipLaunchKernelGGL(attn_runs_merge_kernel<F16>, grid, dim3(256), 0, st, part, hdr, out, Kq, S, H, Dh, n_runs, L.spr, f32,
-                           out_branch_stride, out_frame_stride);
-    TF_LAUNCH_CHECK("tf_ext_attn_runs_merge");
-    return 0;
+    {   // the pre-pass: the run's frames of branches [b_lo, B); it also leaves the slots this run fills per injection state
+        auto slots = [&](bool inj) {
+            const int ns = split_plan(run_n, Kq, S, H, Dh, inj, part, !(flags & TF_ATTN_NO_SPLIT));
+            return ns < L.spr ? ns : L.spr;
+        };
+        AttnParams p{};
+        p.k = static_cast<const unsigned char*>(k) + (int64_t)run_f0 * strides[3] * 2;
+        const void* v_run = static_cast<const unsigned char*>(v) + (int64_t)run_f0 * strides[5] * 2;
+        p.vt = w8 + (size_t)run_f0 * L.Spad * 2;
+        p.knorm2 = reinterpret_cast<const float*>(w8 + L.knorm_off) + (size_t)run_f0 * (L.Spad / 64);
+        p.K = run_n, p.Kb = K, p.S = S, p.H = H, p.Spad = L.Spad;
+        p.ld = ld, p.k_bs = strides[2], p.k_fs = strides[3], p.v_bs = strides[4], p.v_fs = strides[5];
+        p.run_hdr = reinterpret_cast<int*>(w8 + L.hdr_off) + run;
+        p.nseg = slots(false) | (slots(true) << 16);
+        unsigned own = do_src ? 1u : 0u;
+        for (int i = 0; i < n_non; ++i) own |= 3u << (1 + 2 * non_e[i]);
+        const int b_src = (!do_src && n_inj) ? 1 + 2 * inj_e[0] : -1;
+        const unsigned kc_mask = (compact & 2) ? inject_mask : 0u;
+        const int b_lo = do_src ? 0 : 1;
+        const int rc = dtype == TF_BF16 ? launch_vt_pack<BF16>(p, v_run, Dh, b_lo, B, own, b_src, st, kc_mask)
+                                        : launch_vt_pack<F16>(p, v_run, Dh, b_lo, B, own, b_src, st, kc_mask);
+        if (rc) return rc;
+    }
+    const int64_t osz = (flags & TF_ATTN_OUT_F32) ? 4 : 2;
+    auto at = [](const void* ptr, int64_t elems, int64_t esz) {
+        return static_cast<const void*>(static_cast<const unsigned char*>(ptr) + elems * esz);
+    };
+    auto call = [&](int e, int fl, bool src) {   // the bank branches of edit e / the source branch
+        const RunEditsPart ed{n_edits, src ? 0 : e, src ? 1 : 0};
+        const int sh = src ? 0 : 2 * e;
+        const bool own_qk = !src && !(fl & TF_ATTN_INJECT);
+        const int qsh = own_qk ? ((compact & 1) ? c_sh[e] : 2 * e) : 0, ksh = own_qk ? ((compact & 2) ? c_sh[e] : 2 * e) : 0;
+        return attn_run_core(fn, at(q, qsh * strides[0], 2), at(k, ksh * strides[2], 2), at(v, sh * strides[4], 2),
+                             const_cast<void*>(at(out, sh * strides[6], osz)), K, Kq, q_frame0, run_f0, run_n, run, n_runs, S, H,
+                             Dh, ld, strides, scale, fl, dtype, ws, ws_bytes, stream, &ed);
+    };
+    // bank branches first (the long problems): the injecting edits, then the others; then the source branch
+    for (int i = 0; i < n_inj; ++i)
+        if (const int rc = call(inj_e[i], base | TF_ATTN_INJECT | TF_ATTN_BANK_ONLY, false)) return rc;
+    for (int i = 0; i < n_non; ++i)
+        if (const int rc = call(non_e[i], base | TF_ATTN_BANK_ONLY, false)) return rc;
+    // (the source launch sees TF_ATTN_INJECT iff every edit injects, as in the one-call form: its result does not depend on it)
+    return do_src ? call(0, base | (n_non == 0 ? TF_ATTN_INJECT : 0), true) : 0;
+}
+
+extern "C" int tf_ext_attn_runs_merge_edits(void* out, int K, int Kq, int S, int H, int Dh, int n_runs, int n_edits,
+                                            unsigned inject_mask, int64_t out_branch_stride, int64_t out_frame_stride,
+                                            int flags, int dtype, void* ws, size_t ws_bytes, void* stream) {
+    const char* const fn = "tf_ext_attn_runs_merge_edits";
+    if (const int rc = run_edits_check(fn, n_edits, inject_mask, flags)) return rc;
+    return attn_runs_merge_core(fn, out, K, Kq, S, H, Dh, n_runs, n_edits, inject_mask, out_branch_stride, out_frame_stride,
+                                flags, dtype, ws, ws_bytes, stream);
 }
 
 // Launch plan of ONE run call over run_n of the bank's K frames (dense tensors, the run and the query frames at frame 0)
@@ -3071,6 +3279,29 @@ extern "C" int tf_ext_attn_run_plan(int K, int Kq, int run_n, int n_runs, int S,
     tf_plan_rec = nullptr;
     if (rc) return rc;
     TF_ARG(rec.used < len, TF_ERR_WORKSPACE, "tf_ext_attn_run_plan: the plan needs %zu bytes", rec.used + 1);
+    return rec.n;
+}
+
+// The same for ONE tf_ext_attn_run_edits call followed by tf_ext_attn_runs_merge_edits.
+extern "C" int tf_ext_attn_run_edits_plan(int K, int Kq, int run_n, int n_runs, int S, int H, int Dh, int n_edits,
+                                          unsigned inject_mask, int flags, int dtype, char* buf, size_t len) {
+    if (const int rc = run_edits_check("tf_ext_attn_run_edits_plan", n_edits, inject_mask, flags)) return rc;
+    if (const int rc = runs_check_shape("tf_ext_attn_run_edits_plan", K, Kq, S, H, Dh, n_runs, dtype)) return rc;
+    void* const ph = reinterpret_cast<void*>((uintptr_t)1 << 12);
+    const int64_t ld = (int64_t)H * Dh, fs = (int64_t)S * ld;
+    const int64_t strides[9] = {Kq * fs, fs, K * fs, fs, K * fs, fs, Kq * fs, fs, ld};
+    const size_t wsb = tf_ext_attn_runs_edits_workspace_bytes(K, Kq, S, H, Dh, n_runs, n_edits, dtype);
+    TfPlanRec rec{buf, len, 0, 0};
+    if (buf && len) buf[0] = 0;
+    tf_plan_rec = &rec;
+    int rc = tf_ext_attn_run_edits(ph, ph, ph, ph, K, Kq, 0, 0, run_n, 0, n_runs, S, H, Dh, ld, strides, 1.0f, flags, dtype,
+                                   n_edits, inject_mask, 0, ph, wsb, nullptr);
+    if (!rc)
+        rc = tf_ext_attn_runs_merge_edits(ph, K, Kq, S, H, Dh, n_runs, n_edits, inject_mask, Kq * fs, fs, flags, dtype, ph, wsb,
+                                          nullptr);
+    tf_plan_rec = nullptr;
+    if (rc) return rc;
+    TF_ARG(rec.used < len, TF_ERR_WORKSPACE, "tf_ext_attn_run_edits_plan: the plan needs %zu bytes", rec.used + 1);
     return rec.n;
 }
 

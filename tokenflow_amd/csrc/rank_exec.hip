@@ -559,7 +559,33 @@ EditsLayout edits_layout(const tf_rank* rk, int S, int H, int Dh, int E, int dty
     return L;
 }
 
+// TF_RANK_BANK_EDIT_RUNS: the exchange buffers of the bank form ([k slots | v_1 .. v_2E]: 4E slabs where no edit injects) and
+// ONE run-set workspace of the multi-edit run calls (tf_ext_attn_run_edits)
+struct EditRunsLayout {
+    size_t send, recv, ws_runs, total, ws_runs_bytes;
+};
+
+EditRunsLayout edit_runs_layout(const tf_rank* rk, int S, int H, int Dh, int E, int dtype) {
+    const size_t eb = 2, D = (size_t)H * Dh;
+    EditRunsLayout L{};
+    L.send = 0;
+    L.recv = up256((size_t)rk->Kl * 4 * E * S * D * eb);
+    L.ws_runs = L.recv + up256((size_t)rk->K * 4 * E * S * D * eb);
+    L.ws_runs_bytes = tf_ext_attn_runs_edits_workspace_bytes(rk->K, rk->Kl, S, H, Dh, rank_runs(rk).n, E, dtype);
+    L.total = L.ws_runs + up256(L.ws_runs_bytes);
+    return L;
+}
+
 }  // namespace
+
+// Workspace of tf_rank_pivotal_edits with TF_RANK_BANK_EDIT_RUNS (the other modes: tf_rank_pivotal_edits_workspace_bytes).
+extern "C" size_t tf_rank_pivotal_edit_runs_workspace_bytes(const tf_rank* rk, int S, int H, int Dh, int n_edits, int dtype) {
+    if (!rk || S <= 0 || H <= 0 || Dh <= 0 || dtype == TF_F32 || n_edits < 1 || n_edits > TF_MAX_EDITS) return 0;
+    if (n_edits == 1) return tf_rank_pivotal_workspace_bytes(rk, S, H, Dh, dtype);
+    if (rk->world == 1) return up256(tf_ext_attn_edits_workspace_bytes(rk->K, S, H, Dh, n_edits, dtype));
+    if (!(Dh == 40 || Dh == 64 || Dh == 80 || Dh == 160)) return 0;
+    return edit_runs_layout(rk, S, H, Dh, n_edits, dtype).total;
+}
 
 extern "C" size_t tf_rank_pivotal_edits_workspace_bytes(const tf_rank* rk, int S, int H, int Dh, int n_edits, int dtype) {
     if (!rk || S <= 0 || H <= 0 || Dh <= 0 || dtype == TF_F32 || n_edits < 1 || n_edits > TF_MAX_EDITS) return 0;
@@ -585,18 +611,27 @@ extern "C" int tf_rank_pivotal_edits(tf_rank* rk, const void* q, const void* k, 
            n_edits);
     TF_ARG(!(flags & (TF_ATTN_BANK_ONLY | TF_ATTN_SOURCE_ONLY)), TF_ERR_SHAPE, "%s: the part flags are the executor's own", fn);
     TF_ARG(dtype == TF_BF16 || dtype == TF_F16, TF_ERR_DTYPE, "%s: dtype %d (bf16/f16 only)", fn, dtype);
-    TF_ARG(mode == TF_RANK_HEADS || mode == TF_RANK_BANK || mode == TF_RANK_BANK_RUNS, TF_ERR_SHAPE, "%s: mode %d", fn, mode);
+    TF_ARG(mode == TF_RANK_HEADS || mode == TF_RANK_BANK || mode == TF_RANK_BANK_RUNS || mode == TF_RANK_BANK_EDIT_RUNS,
+           TF_ERR_SHAPE, "%s: mode %d", fn, mode);
     TF_ARG(!(mode == TF_RANK_BANK_RUNS && n_edits > 1), TF_ERR_SHAPE,
-           "%s: TF_RANK_BANK_RUNS has no multi-edit form (TF_RANK_BANK or TF_RANK_HEADS)", fn);
+           "%s: TF_RANK_BANK_RUNS has no multi-edit form (TF_RANK_BANK, TF_RANK_HEADS or TF_RANK_BANK_EDIT_RUNS)", fn);
+    const bool edit_runs = mode == TF_RANK_BANK_EDIT_RUNS;
     TF_ARG(!(mode == TF_RANK_HEADS && rk->world > 1 && H % rk->world), TF_ERR_SHAPE,
            "%s: %d heads do not divide over %d ranks (use TF_RANK_BANK)", fn, H, rk->world);
     TF_ARG(slot >= 0 && slot < TF_RANK_SLOTS, TF_ERR_SHAPE, "%s: slot %d outside [0, %d)", fn, slot, TF_RANK_SLOTS);
     TF_ARG(!(want_inv && no_halo), TF_ERR_SHAPE, "%s: TF_RANK_INV_NORM needs the propagation state (no TF_RANK_NO_HALO)", fn);
-    if (n_edits == 1)   // one edit: the single-edit executor itself -- the same launches, the same bits
+    if (n_edits == 1)   // one edit: the single-edit executor itself -- the same launches, the same bits (the multi-edit run
+                        // form of one edit is TF_RANK_BANK_RUNS)
         return tf_rank_pivotal(rk, q, k, v, st_in, piv_ext, inv_ext, kfo_ext, S, H, Dh, scale,
-                               flags | (inject_mask ? TF_ATTN_INJECT : 0), dtype, mode_in, slot, ws, ws_bytes, stream);
-    TF_ARG(ws_bytes >= tf_rank_pivotal_edits_workspace_bytes(rk, S, H, Dh, n_edits, dtype), TF_ERR_WORKSPACE,
-           "%s: workspace %zu < %zu bytes", fn, ws_bytes, tf_rank_pivotal_edits_workspace_bytes(rk, S, H, Dh, n_edits, dtype));
+                               flags | (inject_mask ? TF_ATTN_INJECT : 0), dtype,
+                               edit_runs ? (mode_in & (TF_RANK_NO_HALO | TF_RANK_INV_NORM)) | TF_RANK_BANK_RUNS : mode_in, slot, ws,
+                               ws_bytes, stream);
+    {
+        const size_t need = edit_runs ? tf_rank_pivotal_edit_runs_workspace_bytes(rk, S, H, Dh, n_edits, dtype)
+                                      : tf_rank_pivotal_edits_workspace_bytes(rk, S, H, Dh, n_edits, dtype);
+        TF_ARG(!edit_runs || need, TF_ERR_SHAPE, "%s: head dim %d not in {40,64,80,160}", fn, Dh);
+        TF_ARG(ws_bytes >= need, TF_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", fn, ws_bytes, need);
+    }
 
     const int E = n_edits, B = 1 + 2 * E;
     const int W = rk->world, Kl = rk->Kl, K = rk->K, o = (W > 1 && !no_halo) ? 1 : 0;
@@ -643,6 +678,63 @@ extern "C" int tf_rank_pivotal_edits(tf_rank* rk, const void* q, const void* k, 
     };
     const void* slabs[6 * TF_MAX_EDITS];
     int64_t fss[6 * TF_MAX_EDITS];
+    if (edit_runs) {
+        // ---- the bank in runs for E edits: the schedule of TF_RANK_BANK_RUNS over tf_ext_attn_run_edits / _runs_merge_edits
+        const EditRunsLayout L = edit_runs_layout(rk, S, H, Dh, E, dtype);
+        El* send = reinterpret_cast<El*>(wsb + L.send);
+        El* recv = reinterpret_cast<El*>(wsb + L.recv);
+        void* wsr = wsb + L.ws_runs;
+        const Runs R = rank_runs(rk);
+        // 1. ONE pack (W = 1) of exactly what TF_RANK_BANK packs: the compact k slots and the 2E value slabs
+        const int ns = nq + 2 * E;
+        for (int i = 0; i < nq; ++i) slabs[i] = ke + slots[i] * k_bs, fss[i] = k_fs;
+        for (int j = 0; j < 2 * E; ++j) slabs[nq + j] = ve + (1 + j) * v_bs, fss[nq + j] = v_fs;
+        if (const int rc = do_pack(slabs, fss, ns, send, 1, Kl, S, (int)D, ld, piv_loc, inv_loc, (int64_t)Kl * S, (int)D,
+                                   dtype, stream))
+            return rc;
+        // 2. the LOCAL run on the auxiliary compute stream, forked behind the pack and in FRONT of the gather: the source
+        //    branch and every edit's bank partials against the rank's own keyframes, from q / k / v in place, dense (bank
+        //    frame f of the caller's k / v at base + (f - kf0) * frame stride: the shifted base is formed as an integer)
+        auto shifted = [](const El* base, int64_t elems) {
+            return reinterpret_cast<const El*>(reinterpret_cast<uintptr_t>(base) + (uintptr_t)(elems * (int64_t)sizeof(El)));
+        };
+        const int run_flags = flags & (TF_ATTN_FOLD_SCALE | TF_ATTN_HINT_MIX | TF_ATTN_NO_SPLIT);
+        auto local_run = [&](hipStream_t on) {
+            return tf_ext_attn_run_edits(q, shifted(ke, -(int64_t)rk->kf0 * k_fs), shifted(ve, -(int64_t)rk->kf0 * v_fs), out_loc,
+                                         K, Kl, rk->kf0, R.f0[0], R.len[0], 0, R.n, S, H, Dh, ld, loc_strides, scale, run_flags,
+                                         dtype, E, inject_mask, 0, wsr, L.ws_runs_bytes, on);
+        };
+        const bool fork = !tf_plan_rec;   // (a recorded plan lists the in-line order: the local run behind the gather)
+        if (fork) {
+            if (const int rc = order(rk, st, rk->as, fn)) return rc;
+            if (const int rc = local_run(rk->as)) return rc;
+        }
+        // 3. the gather on the caller's stream: every collective of a communicator on ONE stream
+        if (const int rc = do_gather(rk->comm, send, recv, cnt, ns, SD, dtype, st)) return rc;
+        if (!fork)
+            if (const int rc = local_run(st)) return rc;
+        // 4. behind it the remote runs: bank branches only, k compact from the receive buffer [K][ns][S][D] in place, q from
+        //    the local tensors (dense: no staging copy under a mixed mask)
+        const int64_t fs_r = ns * SD;
+        const El* kb = slab(recv, 0, b0, SD);
+        const El* vb = slab(recv, nq, 1, SD);
+        const int64_t rstrides[9] = {q_bs, q_fs, SD, fs_r, SD, fs_r, o_bs, SD, ld_q};
+        for (int r = 1; r < R.n; ++r)
+            if (const int rc = tf_ext_attn_run_edits(q, kb, vb, out_loc, K, Kl, rk->kf0, R.f0[r], R.len[r], r, R.n, S, H, Dh, D,
+                                                     rstrides, scale, run_flags | TF_ATTN_BANK_ONLY, dtype, E, inject_mask, 2,
+                                                     wsr, L.ws_runs_bytes, stream))
+                return rc;
+        // 5. join the local run, ONE merge over all 2E bank branches into the local slots of kfo_ext
+        if (fork)
+            if (const int rc = order(rk, rk->as, st, fn)) return rc;
+        if (const int rc = tf_ext_attn_runs_merge_edits(out_loc, K, Kl, S, H, Dh, R.n, E, inject_mask, o_bs, SD, run_flags, dtype,
+                                                        wsr, L.ws_runs_bytes, stream))
+            return rc;
+        // 6. the halo of 2 + B messages
+        if (!no_halo)
+            if (const int rc = halo_exchange(rk, piv, inv_ext, kfo, B, o_bs, SD, S, slot, st, fn)) return rc;
+        return 0;
+    }
     // the source part of the rank's own frames on the local tensors
     const EditsLayout L = edits_layout(rk, S, H, Dh, E, dtype, mode);
     auto source_part = [&](hipStream_t on) {

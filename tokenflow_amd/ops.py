@@ -538,6 +538,132 @@ def ext_attn_runs(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int,
     return out
 
 
+def attn_run_edits_plan(K: int, Kq: int, run_n: int, n_runs: int, S: int, heads: int, dh: int, n_edits: int, inject_mask: int,
+                        dtype: torch.dtype = torch.bfloat16, bank_only: bool = False, out_dtype: Optional[torch.dtype] = None,
+                        fold_scale: Optional[bool] = None, no_split: bool = False, hints: int = 0) -> list:
+    """The launches of ONE run call of `ext_attn_runs_edits` over run_n of the bank's K frames, followed by the merge, as
+    tokens (tf_ext_attn_run_edits_plan): 'vt_pack', per edit -- the injecting ones first, then the others, ascending -- the
+    ',run>' tokens of its own bank-only `attn_run_plan`, the source token unless bank_only, 'merge[runs=N,edits=E]'.  Host
+    only."""
+    flags = _run_flags(False, bank_only, out_dtype == torch.float32, fold_scale, no_split, hints)
+    mask = _edit_mask("attn_run_edits_plan", inject_mask, n_edits)
+    return _plan_tokens("tf_ext_attn_run_edits_plan", _lib.load().tf_ext_attn_run_edits_plan, K, Kq, run_n, n_runs, S, heads,
+                        dh, int(n_edits), mask, flags, _DT[dtype])
+
+
+def ext_attn_runs_edits_views(q: torch.Tensor, kv_runs: Sequence, out: torch.Tensor, heads: int, scale: float, n_edits: int,
+                              inject_mask: int, runs: Sequence, K: int, branch0=(0, 0), q_frame0: int = 0,
+                              q_compact: bool = False, streams: Optional[Sequence] = None,
+                              fold_scale: Optional[bool] = None, no_split: bool = False, hints: int = 0,
+                              order: Optional[Sequence[int]] = None) -> torch.Tensor:
+    """`ext_attn_runs_views` for a multi-edit batch (tf_ext_attn_run_edits + tf_ext_attn_runs_merge_edits): E = n_edits
+    edits, v and out addressed as [source | uncond_1 | cond_1 | ...] (1 + 2E branches), inject_mask the injection state per
+    edit.  kv_runs[r] = (k_view, v_view, k_branch0, v_branch0, k_compact): as in `ext_attn_runs_views`, and k_compact says
+    that run's k holds only the slots a launch reads (slot 0 the source, then (uncond, cond) of every NON-injecting edit,
+    ascending: the layout of `ext_attn_edits_views(qk_compact=True)`) -- a rank's local run reads its own dense k, its remote
+    runs the compact k of a receive buffer, all against the same q (q_compact: q is compact too).  Run 0 computes the source
+    branch; the others never touch the source slabs of v and out.  For every edit the result equals, bit for bit,
+    `ext_attn_runs_views` on [source | uncond_e | cond_e] with the same runs and that edit's flag.  ONE workspace per set."""
+    dev = _need_gpu(q, out, *[t for kv in kv_runs for t in kv[:2]])
+    lib = _lib.load()
+    mask = _edit_mask("ext_attn_runs_edits_views", inject_mask, n_edits)
+    E = int(n_edits)
+    S, D = q.shape[2], q.shape[3]
+    Kq, dh, n_runs = q.shape[1], D // heads, len(runs)
+    dt = _DT.get(q.dtype)
+    if dt is None or dt == _lib.TF_F32 or D % heads or len(kv_runs) != n_runs:
+        raise TypeError("ext_attn_runs_edits_views: q/k/v must share dtype bf16 or f16; one (k, v, ...) entry per run")
+    if sorted(f for f0, n in runs for f in range(f0, f0 + n)) != list(range(K)) or any(n < 1 for _, n in runs):
+        raise ValueError(f"ext_attn_runs_edits_views: runs {list(runs)} do not partition the {K}-frame bank")
+    if out.dtype not in (q.dtype, torch.float32) or out.shape[1] != Kq:
+        raise TypeError("ext_attn_runs_edits_views: out dtype / frames")
+    qp, q_bs, q_fs, ld_q = _view_base(q, branch0[0], S, "q")
+    op, o_bs, o_fs, ld_o = _view_base(out, branch0[1], S, "out")
+    if ld_o != D:
+        raise ValueError("ext_attn_runs_edits_views: out needs a dense token stride")
+    out_f32 = out.dtype == torch.float32
+    nbytes = lib.tf_ext_attn_runs_edits_workspace_bytes(K, Kq, S, heads, dh, n_runs, E, dt)
+    ws = _workspace(nbytes, q.device, tag="attn_runs")     # one per run SET: keyed by the current stream, not by the runs' streams
+    cur = torch.cuda.current_stream(dev)
+    fork = None
+    used = []
+    for r in (range(n_runs) if order is None else order):
+        f0, n = runs[r]
+        kv, vv, kb0, vb0, k_compact = kv_runs[r]
+        if kv.dtype != q.dtype or vv.dtype != q.dtype or kv.shape[1] != n or vv.shape[1] != n:
+            raise TypeError("ext_attn_runs_edits_views: a run's k / v views hold that run's frames in the dtype of q")
+        kp, k_bs, k_fs, ld = _view_base(kv, kb0, S, "k")
+        vp, v_bs, v_fs, ld_v = _view_base(vv, vb0, S, "v")
+        if ld_v != ld:
+            raise ValueError("ext_attn_runs_edits_views: k and v of a run need one token stride")
+        es = kv.element_size()
+        strides = (ctypes.c_int64 * 9)(q_bs, q_fs, k_bs, k_fs, v_bs, v_fs, o_bs, o_fs, ld_q)
+        flags = _run_flags(False, r != 0, out_f32, fold_scale, no_split, hints)
+        st = streams[r] if streams is not None else None
+        if st is not None:
+            if fork is None:
+                fork = torch.cuda.Event()
+                fork.record(cur)
+            st.wait_event(fork)
+            used.append(st)
+        _launch(dev, "tf_ext_attn_run_edits", lib.tf_ext_attn_run_edits, qp, kp - f0 * k_fs * es, vp - f0 * v_fs * es, op, K, Kq,
+                int(q_frame0), f0, n, r, n_runs, S, heads, dh, ld, ctypes.cast(strides, ctypes.c_void_p), float(scale),
+                flags, dt, E, mask, (1 if q_compact else 0) | (2 if k_compact else 0), ws.data_ptr(), ws.numel(),
+                stream=None if st is None else st.cuda_stream)
+    for st in used:
+        ev = torch.cuda.Event()
+        ev.record(st)
+        cur.wait_event(ev)
+    _launch(dev, "tf_ext_attn_runs_merge_edits", lib.tf_ext_attn_runs_merge_edits, op, K, Kq, S, heads, dh, n_runs, E, mask,
+            o_bs, o_fs, _run_flags(False, False, out_f32, fold_scale, no_split, hints), dt, ws.data_ptr(), ws.numel())
+    return out
+
+
+def ext_attn_runs_edits(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, scale: float, n_edits: int,
+                        inject_mask: int, runs: Sequence, q_frame0: int = 0, out: Optional[torch.Tensor] = None,
+                        out_dtype: Optional[torch.dtype] = None, streams: Optional[Sequence] = None,
+                        fold_scale: Optional[bool] = None, no_split: bool = False, hints: int = 0,
+                        order: Optional[Sequence[int]] = None, k_compact: bool = False) -> torch.Tensor:
+    """`ext_attn_edits(inject_mask=...)` computed run by run over the bank: k, v [B*K,S,D], q [B*Kq,S,D], B = 1 + 2E, runs as
+    in `ext_attn_runs`.  Returns [B*Kq,S,D] (fp32 with out_dtype=torch.float32).  For every edit e the slices (source,
+    uncond_e, cond_e) equal `ext_attn_runs` on [source | uncond_e | cond_e] with the same runs and that edit's flag, bit for
+    bit; the result is a function of the runs alone and equals the oracle within the attention bound -- not
+    `ext_attn_edits` bit for bit.  n_edits = 1 is `ext_attn_runs`.
+    k_compact: every run but the first reads k from a compact copy -- the source slot (where an edit injects), then
+    (uncond, cond) of every non-injecting edit -- as a rank's remote runs read a receive buffer; the same bits."""
+    _need_gpu(q, k, v, out)
+    mask = _edit_mask("ext_attn_runs_edits", inject_mask, n_edits)
+    E = int(n_edits)
+    nbr = 1 + 2 * E
+    BK, S, D = k.shape
+    Bq = q.shape[0]
+    if BK % nbr or Bq % nbr or D % heads or q.shape[1:] != k.shape[1:] or v.shape != k.shape:
+        raise ValueError(f"ext_attn_runs_edits: bad shapes q{tuple(q.shape)} k{tuple(k.shape)} v{tuple(v.shape)} heads {heads} "
+                         f"for {E} edits ({nbr} branches)")
+    K, Kq = BK // nbr, Bq // nbr
+    if q.dtype not in (torch.bfloat16, torch.float16) or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise TypeError(f"ext_attn_runs_edits: q/k/v must share dtype bf16 or f16, got {q.dtype},{k.dtype},{v.dtype}")
+    q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+    if out_dtype is None:
+        out_dtype = out.dtype if out is not None else q.dtype
+    if out_dtype not in (q.dtype, torch.float32):
+        raise TypeError(f"ext_attn_runs_edits: out_dtype {out_dtype} (the input dtype or float32)")
+    if out is None:
+        out = torch.empty(Bq, S, D, dtype=out_dtype, device=q.device)
+    elif out.dtype != out_dtype or not out.is_contiguous() or out.shape != (Bq, S, D):
+        raise ValueError("ext_attn_runs_edits: `out` must be a contiguous [B*Kq,S,D] tensor of out_dtype")
+    k4, v4 = k.view(nbr, K, S, D), v.view(nbr, K, S, D)
+    kv_runs = [(k4[:, f0:f0 + n], v4[:, f0:f0 + n], 0, 0, False) for f0, n in runs]
+    if k_compact:
+        slots = ([0] if mask else []) + [b for e in range(E) if not (mask >> e) & 1 for b in (1 + 2 * e, 2 + 2 * e)]
+        kc = k4[slots].contiguous()   # (a compact k in which no edit injects starts at slot 1)
+        kv_runs[1:] = [(kc[:, f0:f0 + n], v4[:, f0:f0 + n], 0 if mask else 1, 0, True) for f0, n in runs[1:]]
+    ext_attn_runs_edits_views(q.view(nbr, Kq, S, D), kv_runs, out.view(nbr, Kq, S, D), heads, scale, E, mask, runs, K,
+                              q_frame0=q_frame0, streams=streams, fold_scale=fold_scale, no_split=no_split, hints=hints,
+                              order=order)
+    return out
+
+
 def head_pack(slabs: Sequence[torch.Tensor], W: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """slabs: ns <= 6 * TF_MAX_EDITS tensors [Kl, S, D] (frame stride free, rows dense-strided, same dtype) -> the all-to-all send
     buffer [W, Kl, ns, S, D // W]: head group w of every slab, frame-major (tf_head_pack, one launch)."""

@@ -37,7 +37,9 @@ side stream ordered against the compute stream with events):
         (frames left of the rank's own, then right) follow when the gather has landed, and one merge folds the runs'
         partial results in the fixed order local, left, right (`ops.ext_attn_runs_views`).  The merge re-associates
         fp32 sums: this mode equals a single-process `ops.ext_attn_runs` with the same runs bit for bit and the
-        oracle within the attention bound -- NOT the bit-stable single-GPU call.
+        oracle within the attention bound -- NOT the bit-stable single-GPU call.  For a multi-edit batch the mode
+        needs an opt-in of its own (`edit_runs=True` / TOKENFLOW_SHARD_EDIT_RUNS=1): the gather of the multi-edit "bank"
+        form, the same runs through `ops.ext_attn_runs_edits_views`, the same guarantee per edit.
 
  2. propagation passes -- chunk c needs keyframes c and c-1 (331-333): the first local chunk's
     left neighbour lives on rank r-1, so each rank sends its LAST keyframe's pivot features,
@@ -127,6 +129,11 @@ def _all_to_all(recv: torch.Tensor, send: torch.Tensor, group, out_rows=None, in
     return dist.all_to_all_single(recv, send, out_rows, in_rows, group=group, async_op=async_op)
 
 
+# (an explicit "bank_runs" for several edits on a shard built without the opt-in)
+_NO_EDIT_RUNS = ("FrameShard: the \"bank_runs\" pattern has no multi-edit form (use \"bank\" or \"heads\") unless the shard "
+                 "opts in: edit_runs=True / TOKENFLOW_SHARD_EDIT_RUNS=1")
+
+
 class FrameShard:
     """K keyframes (= chunks) over the ranks of `group` in contiguous runs; the first K % W ranks hold one more
     (cfg5's 25 chunks over 8 ranks -> 4,3,3,3,3,3,3,3)."""
@@ -145,12 +152,18 @@ class FrameShard:
 
     def __init__(self, K: int, group: Optional[dist.ProcessGroup] = None, comm=None,
                  attn_split: Optional[bool] = None, halo_group: Optional[dist.ProcessGroup] = None, halo_comm=None,
-                 bank_runs: Optional[bool] = None):
+                 bank_runs: Optional[bool] = None, edit_runs: Optional[bool] = None):
         # bank_runs: opt-in for `auto_mode` (mode=None callers, the hook path): "bank_runs" where it would answer "bank"
         # and S >= BANK_RUNS_MIN_S.  None reads TOKENFLOW_SHARD_BANK_RUNS.  Off: today's answers.
         if bank_runs is None:
             bank_runs = os.environ.get("TOKENFLOW_SHARD_BANK_RUNS", "0") not in ("", "0")
         self.bank_runs = bool(bank_runs)
+        # edit_runs: opt-in for the "bank_runs" form of a MULTI-EDIT batch (`_pivotal_bank_runs_edits`): mode="bank_runs" with
+        # n_edits > 1 runs instead of raising, and -- together with bank_runs -- `auto_mode` answers "bank_runs" for
+        # n_edits > 1 where it answers it for one edit.  None reads TOKENFLOW_SHARD_EDIT_RUNS.  Off: today's answers.
+        if edit_runs is None:
+            edit_runs = os.environ.get("TOKENFLOW_SHARD_EDIT_RUNS", "0") not in ("", "0")
+        self.edit_runs = bool(edit_runs)
         # attn_split: let the attention split a rank's small grid over extra workgroups and merge (faster: -15..40 %
         # on a rank's attention at 8 GPUs; results then agree with the single-GPU ones within the
         # output rounding).  Default False: one pass per bank problem, arithmetic independent of the grid, sharded
@@ -341,7 +354,8 @@ class FrameShard:
         choice where a block is a few tens of microseconds of work (S <= 64: the mid block) and the exchange is
         latency-, not volume-bound -- and the only one when the heads do not divide over the ranks."""
         mode = "bank" if (heads % self.world or S <= 64) else "heads"
-        if mode == "bank" and getattr(self, "bank_runs", False) and S >= self.BANK_RUNS_MIN_S and n_edits == 1:
+        if (mode == "bank" and getattr(self, "bank_runs", False) and S >= self.BANK_RUNS_MIN_S
+                and (n_edits == 1 or getattr(self, "edit_runs", False))):
             return "bank_runs"     # opt-in (bank_runs=True / TOKENFLOW_SHARD_BANK_RUNS=1): the bank in runs, see the module text
         return mode
 
@@ -391,8 +405,8 @@ class FrameShard:
                                       no_split=not self.attn_split, inject_mask=mask)
         if mode is None:
             mode = self.auto_mode(heads, q_local.shape[1], E)
-        if mode == "bank_runs":
-            raise ValueError("FrameShard: the \"bank_runs\" pattern has no multi-edit form (use \"bank\" or \"heads\")")
+        if mode == "bank_runs" and not getattr(self, "edit_runs", False):
+            raise ValueError(_NO_EDIT_RUNS)
         _, S, D = q_local.shape
         Kl = self.Kl
 
@@ -410,6 +424,8 @@ class FrameShard:
         b0 = 0 if mask else 1
         if mode == "heads":
             self._pivotal_heads_edits(q4, k4, v4, out, heads, scale, E, mask, slots, b0)
+        elif mode == "bank_runs":
+            self._pivotal_bank_runs_edits(q4, k4, v4, out, heads, scale, E, mask, slots, b0)
         else:
             self._pivotal_bank_edits(q4, k4, v4, out, heads, scale, E, mask, slots, b0)
         return out.view(B * Kl, S, D) if out4 is None else out4
@@ -463,6 +479,23 @@ class FrameShard:
         ops.ext_attn_edits_views(qc, rp[0:nq], rp[nq:], out[1:], heads, scale, E, mask, "bank", True,
                                  branch0=(b0, b0, 1, 1), q_frame0=self.kf0, no_split=ns_)
         ops.ext_attn_edits_views(q4[0:1], k4[0:1], v4[0:1], out[0:1], heads, scale, E, mask, "source", no_split=ns_)
+
+    def _pivotal_bank_runs_edits(self, q4, k4, v4, out, heads, scale, E, mask, slots, b0):
+        """`_pivotal_bank_runs` for E edits (the `edit_runs` opt-in): ONE gather of exactly what `_pivotal_bank_edits` gathers
+        -- the compact k slots and the 2E value slabs -- then the runs of `bank_runs_of_rank()` in slot order local, left,
+        right: the local run reads the caller's tensors in place (dense q, k, v; it also computes the source branch), the
+        remote runs the receive buffer in place (k compact) against the same dense q; then the ONE merge over all 2E bank
+        branches.  No overlap here, as in `_pivotal_bank_runs`.  Per edit the bits of that form on [source | uncond_e |
+        cond_e]; the same bits as the native executor's TF_RANK_BANK_EDIT_RUNS on the same transport."""
+        B = q4.shape[0]
+        nq = len(slots)
+        rp = self._gather_slabs([k4[b] for b in slots] + [v4[b] for b in range(1, B)], "bank_e")
+        runs = self.bank_runs_of_rank()
+        kv_runs = [(k4, v4, 0, 0, False)]
+        for f0, n in runs[1:]:
+            kv_runs.append((rp[0:nq, f0:f0 + n], rp[nq:, f0:f0 + n], b0, 1, True))
+        ops.ext_attn_runs_edits_views(q4, kv_runs, out, heads, scale, E, mask, runs, self.K, q_frame0=self.kf0,
+                                      no_split=not self.attn_split)
 
     def bank_runs_of_rank(self):
         """The runs of the bank this rank computes in the "bank_runs" form, in SLOT order: its own keyframes, the frames
@@ -793,8 +826,9 @@ class NativeShard(FrameShard):
 
     supports_edits = False
 
-    def __init__(self, K: int, comm, halo_comm=None, attn_split: Optional[bool] = None, bank_runs: Optional[bool] = None):
-        super().__init__(K, comm=comm, attn_split=attn_split, halo_comm=halo_comm, bank_runs=bank_runs)
+    def __init__(self, K: int, comm, halo_comm=None, attn_split: Optional[bool] = None, bank_runs: Optional[bool] = None,
+                 edit_runs: Optional[bool] = None):
+        super().__init__(K, comm=comm, attn_split=attn_split, halo_comm=halo_comm, bank_runs=bank_runs, edit_runs=edit_runs)
         from . import _lib
         lib = _lib.load()
         h = ctypes.c_void_p()
@@ -891,12 +925,14 @@ class NativeEditShard(NativeShard):
     ONE call of tf_rank_pivotal_edits (csrc/rank_exec.hip) -- the native form of `FrameShard._pivotal_heads_edits` /
     `_pivotal_bank_edits`, same buffer layouts, same bits on the same transport.  n_edits = 1 is `NativeShard` itself.
     Modes "heads" and "bank" (`auto_mode` answers "bank" in place of "bank_runs" for E > 1; the explicit "bank_runs" raises as
-    on `FrameShard`).  `ext_alloc`, `halo_block`, `halo_finish`, `propagate_all` are `FrameShard`'s, with n_edits."""
+    on `FrameShard`) -- unless the shard opts in with `edit_runs`: "bank_runs" is then the executor's TF_RANK_BANK_EDIT_RUNS,
+    the native form of `FrameShard._pivotal_bank_runs_edits` with the local run beside the gather.  `ext_alloc`, `halo_block`, `halo_finish`, `propagate_all` are `FrameShard`'s, with n_edits."""
 
     supports_edits = True
 
-    def __init__(self, K: int, comm, halo_comm=None, attn_split: Optional[bool] = None, bank_runs: Optional[bool] = None):
-        super().__init__(K, comm, halo_comm=halo_comm, attn_split=attn_split, bank_runs=bank_runs)
+    def __init__(self, K: int, comm, halo_comm=None, attn_split: Optional[bool] = None, bank_runs: Optional[bool] = None,
+                 edit_runs: Optional[bool] = None):
+        super().__init__(K, comm, halo_comm=halo_comm, attn_split=attn_split, bank_runs=bank_runs, edit_runs=edit_runs)
         self._news = {}
 
     @staticmethod
@@ -949,8 +985,9 @@ class NativeEditShard(NativeShard):
         Kl, B = self.Kl, 1 + 2 * E
         if mode is None:
             mode = self.auto_mode(heads, S, E)
-        if mode == "bank_runs":
-            raise ValueError("FrameShard: the \"bank_runs\" pattern has no multi-edit form (use \"bank\" or \"heads\")")
+        runs = mode == "bank_runs"
+        if runs and not self.edit_runs:
+            raise ValueError(_NO_EDIT_RUNS)
         dt = ops._DT.get(q_local.dtype)
         if dt is None or dt == _lib.TF_F32 or not (q_local.is_cuda and kfo.is_contiguous()
                                                     and (no_halo or (piv.is_contiguous() and inv.is_contiguous()))):
@@ -966,10 +1003,11 @@ class NativeEditShard(NativeShard):
         strides = (ctypes.c_int64 * 8)(q4.stride(0), q4.stride(1), k4.stride(0), k4.stride(1), v4.stride(0), v4.stride(1),
                                        q4.stride(2), k4.stride(2))
         dh = D // heads
-        key = (S, heads, dh, dt, q_local.device, E)
+        key = (S, heads, dh, dt, q_local.device, E, runs)
         ws = self._news.get(key)
         if ws is None:
-            nbytes = lib.tf_rank_pivotal_edits_workspace_bytes(self._rk, S, heads, dh, E, dt)
+            size = lib.tf_rank_pivotal_edit_runs_workspace_bytes if runs else lib.tf_rank_pivotal_edits_workspace_bytes
+            nbytes = size(self._rk, S, heads, dh, E, dt)
             ws = self._news[key] = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=q_local.device)
         flags = 0 if self.attn_split else _lib.TF_ATTN_NO_SPLIT
         if ops.FOLD_SCALE:
@@ -977,7 +1015,7 @@ class NativeEditShard(NativeShard):
         slot = self._slot
         if not no_halo:
             self._slot = (slot + 1) % _lib.TF_RANK_SLOTS
-        m = ((_lib.TF_RANK_HEADS if mode == "heads" else _lib.TF_RANK_BANK)
+        m = ((_lib.TF_RANK_HEADS if mode == "heads" else _lib.TF_RANK_BANK_EDIT_RUNS if runs else _lib.TF_RANK_BANK)
              | (_lib.TF_RANK_NO_HALO if no_halo else 0)
              | (_lib.TF_RANK_INV_NORM if inv_norm else 0))
         rc = lib.tf_rank_pivotal_edits(self._rk, q4.data_ptr(), k4.data_ptr(), v4.data_ptr(), strides,
@@ -994,9 +1032,12 @@ def rank_edits_plan(world: int, rank: int, K: int, S: int, heads: int, dh: int, 
                     inv_norm: bool = False, flags: int = 0) -> list:
     """The sequence ONE `NativeEditShard` block call issues on `rank` of `world` ranks, as tokens
     (tf_rank_pivotal_edits_plan: e.g. ['pack+inv[ns=10]', 'a2a[slabs=10]', 'vt_pack', ..., 'a2a[slabs=4]', 'unpack[nb=4]',
-    'halo[n=7]']).  Recorded by the executing code itself; host only: needs no GPU and no communicator."""
+    'halo[n=7]']).  Recorded by the executing code itself; host only: needs no GPU and no communicator.
+    mode: "heads" | "bank" | "bank_runs" (TF_RANK_BANK_RUNS: one edit only) | "bank_edit_runs" (TF_RANK_BANK_EDIT_RUNS: what a
+    `NativeEditShard(edit_runs=True)` issues for "bank_runs")."""
     from . import _lib
-    m = ({"heads": _lib.TF_RANK_HEADS, "bank": _lib.TF_RANK_BANK, "bank_runs": _lib.TF_RANK_BANK_RUNS}[mode]
+    m = ({"heads": _lib.TF_RANK_HEADS, "bank": _lib.TF_RANK_BANK, "bank_runs": _lib.TF_RANK_BANK_RUNS,
+          "bank_edit_runs": _lib.TF_RANK_BANK_EDIT_RUNS}[mode]
          | (_lib.TF_RANK_NO_HALO if no_halo else 0) | (_lib.TF_RANK_INV_NORM if inv_norm else 0))
     fl = int(flags) | (_lib.TF_ATTN_NO_SPLIT if no_split else 0)
     return ops._plan_tokens("tf_rank_pivotal_edits_plan", _lib.load().tf_rank_pivotal_edits_plan, int(world), int(rank),

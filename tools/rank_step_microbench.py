@@ -17,7 +17,8 @@ Target: step <= single-GPU step / 6.
 --edits E [--inject-mask M]: the step is ONE multi-edit pass of E prompts (B = 1 + 2E branches; `NativeEditShard` with
 --native, `FrameShard` without, both on the library's loopback transport so that --no-copies and --wire-model apply to
 either); the injected blocks of an inject=1 step run with mask M (default: every edit injects).  The yardstick is E times the
---edits 1 step."""
+--edits 1 step.  With --edits, the modes bank_runs and auto+runs build the shard with edit_runs=True (the run form of a multi-edit
+batch: TF_RANK_BANK_EDIT_RUNS with --native)."""
 import argparse
 import os
 import statistics
@@ -194,8 +195,7 @@ def main():
         for mode_name in ("auto", "heads", "bank", "bank_runs", "auto+runs"):
             if args.only and args.only != f"{'split' if split else 'onepass'},{mode_name}":
                 continue
-            if E > 1 and mode_name in ("bank_runs", "auto+runs"):      # the runs form has no multi-edit form
-                continue
+            runs_e = E > 1 and mode_name in ("bank_runs", "auto+runs")   # the shard's edit_runs opt-in (TF_RANK_BANK_EDIT_RUNS)
             opt_in = mode_name == "auto+runs"       # FrameShard(bank_runs=True): auto_mode may answer "bank_runs"
             mode = None if mode_name in ("auto", "auto+runs") else mode_name
             wire = tuple(float(x) for x in args.wire_model.split(",")) if args.wire_model else None
@@ -206,8 +206,10 @@ def main():
                 comm.bytes = 0
                 hcomm = HipComm.loopback(args.rank, args.world, copies=not args.no_copies, wire=wire)
                 if E > 1:
-                    shard = (sharded.NativeEditShard(cfg.K, comm, hcomm, attn_split=split) if args.native else
-                             sharded.FrameShard(cfg.K, comm=comm, halo_comm=hcomm, attn_split=split))
+                    shard = (sharded.NativeEditShard(cfg.K, comm, hcomm, attn_split=split, bank_runs=opt_in, edit_runs=runs_e)
+                             if args.native else
+                             sharded.FrameShard(cfg.K, comm=comm, halo_comm=hcomm, attn_split=split, bank_runs=opt_in,
+                                                edit_runs=runs_e))
                 else:
                     shard = sharded.NativeShard(cfg.K, comm, hcomm, attn_split=split, bank_runs=opt_in)
             else:
