@@ -67,6 +67,14 @@ extern "C" {
 /* tf_ext_attn_fwd_edits only: the four-bank shared-softmax form for pairs of edits (below) forced on / off */
 #define TF_ATTN_MULTI_V (1 << 19)
 #define TF_ATTN_NO_MULTI_V (1 << 20)
+/* the four-bank form at Dh = 64 forced on (plan token one<64,1,8,MV4,2,fq1>): a hint of its own, because TF_ATTN_MULTI_V keeps
+   its meaning -- at Dh = 64 it selects nothing.  A no-op where the form does not exist: Dh != 64, fewer than two injecting
+   edits, TF_ATTN_FOLD_SCALE, n_edits = 1.  TF_ATTN_NO_MULTI_V switches this form off too; the two together are TF_ERR_SHAPE.
+   Without a hint the library takes the form only in the shape classes where it was measured faster than the composition
+   by more than the run-to-run spread (profiles/r13_attn_edits_d64_ab.txt): Kq = K, H = 5 or 10, 10 <= K <= 25, S % 64 == 0,
+   1024 <= S <= 9216; the composition everywhere else.  The run entry points (tf_ext_attn_run_edits,
+   tf_ext_attn_runs_merge_edits) refuse it as they refuse TF_ATTN_MULTI_V. */
+#define TF_ATTN_MULTI_V64 (1 << 21)
 
 /* most edits of one multi-edit batch (the *_edits entry points) */
 #define TF_MAX_EDITS 8
@@ -196,6 +204,9 @@ TF_API int tf_ext_attn_plan(int K, int Kq, int S, int H, int Dh, int flags, int 
  * off; without a hint the library takes it only for the shape classes where it was measured faster than the composition
  * by more than the run-to-run spread (profiles/r08_attn_edits_ab.txt): Kq = K, H = 8, 4 <= K <= 8, 1024 <= S <= 4096; the
  * composition everywhere else (other grids were not measured).
+ * At Dh = 64 the form has a hint of its own, TF_ATTN_MULTI_V64, and a measured default of its own (see the flag): four unpacked
+ * 64-row banks in one LDS image (8 M-tiles), one row sum for all four, 8-wave workgroups (token one<64,1,8,MV4,2,fq1>); same
+ * pairing, same one-pass launches, same bound.  TF_ATTN_MULTI_V selects nothing there.
  *
  * tf_ext_attn_edits_plan: the launches of the call for dense tensors, as tf_ext_attn_plan (host only); the four-bank launch
  * is the token one<40,1,4,MV4,2,fq0>.
@@ -228,7 +239,8 @@ TF_API int tf_ext_attn_edits_plan(int K, int Kq, int S, int H, int Dh, int n_edi
  *      edit injects: the source branch reads its own q and k either way and its values do not depend on the flag, but the
  *      launch decision of a source-only call may, and the two uniform masks must be tf_ext_attn_fwd_edits exactly.
  * Pair rule of the four-bank form: as for tf_ext_attn_fwd_edits, with the number of INJECTING edits (>= 2) in the place of
- * n_edits; Dh = 40, fp32 score scaling, TF_ATTN_MULTI_V / TF_ATTN_NO_MULTI_V and the measured default unchanged.  The two
+ * n_edits; Dh = 40 (Dh = 64 behind TF_ATTN_MULTI_V64), fp32 score scaling, TF_ATTN_MULTI_V / TF_ATTN_NO_MULTI_V and the
+ * measured default unchanged.  The two
  * edits of a pair need not be neighbours (mask 0b101 pairs edits 0 and 2): the launch is given the branch distance between
  * them and is the same grid and work as a pair of neighbours.
  *
@@ -357,7 +369,7 @@ TF_API int tf_ext_attn_run_plan(int K, int Kq, int run_n, int n_runs, int S, int
  *   frames have in the image of the whole bank; key norms of the source and of the edits that do not inject), then every
  *   edit through the launches of its own tf_ext_attn_run call -- the injecting edits first, then the others, ascending --
  *   then the source launch.  Injecting edits take the DUAL run form where the single-edit run does; the four-bank form has no
- *   partial epilogue: TF_ATTN_MULTI_V is TF_ERR_SHAPE, TF_ATTN_NO_MULTI_V is accepted and ignored.
+ *   partial epilogue: TF_ATTN_MULTI_V and TF_ATTN_MULTI_V64 are TF_ERR_SHAPE, TF_ATTN_NO_MULTI_V is accepted and ignored.
  *   q, k, v, out, strides: as tf_ext_attn_run, v and out addressed over all B branches (a bank-only call never touches their
  *   source slabs).  compact: bit 0 = q, bit 1 = k is in the compact layout of tf_ext_attn_fwd_edits_part (slot 0 the
  *   source, then (uncond, cond) of every NON-injecting edit, ascending); the two are separate, so a rank's remote runs read

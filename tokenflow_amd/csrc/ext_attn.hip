@@ -232,10 +232,12 @@ __global__ __launch_bounds__(256) void vt_pack_kernel(const typename T::elem* __
 //        MODE_DUAL:   q/k injection active -- uncond and cond share q, k, the scores and P
 //                     (tokenflow_utils.py:124-130), so ONE workgroup computes both: QK^T and the softmax
 //                     once, two P.V products against the two V banks (NB = 2).
-//        MODE_MV4:    multi-edit batch under injection (Dh = 40): the uncond and cond branches of TWO edits share the
+//        MODE_MV4:    multi-edit batch under injection (Dh = 40, 64): the uncond and cond branches of TWO edits share the
 //                     source q and k, so one workgroup does QK^T and the softmax once and FOUR P.V products (NB = 4)
 //                     against the banks of branches b, b + 1, b + gap, b + gap + 1 of the V^T image (p.gap = 2: neighbouring
 //                     edits; the masked multi-edit call pairs the INJECTING edits, whatever lies between them).
+//                     Dh = 40: the packed image (PACK below).  Dh = 64: four 64-row banks side by side, 8 M-tiles, one row
+//                     sum for all four (no ones row), the scores taken per 32-key half (HALF below).
 // MINW = min waves per SIMD for the register allocator
 // FQ   = fold the softmax scale into Q (see FOLD below; opt-in, TF_ATTN_FOLD_SCALE); false = the default, fp32
 //        scaling of the scores as the reference does (tokenflow_utils.py:173-175 `* self.scale` on the bmm output)
@@ -250,7 +252,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void ext_attn_kernel(AttnParams p) {
     constexpr int NT = 64 * NW;
     constexpr int NB = MODE == MODE_DUAL ? 2 : MODE == MODE_MV4 ? 4 : 1;   // V banks handled by this workgroup
     constexpr bool SHARED = MODE == MODE_DUAL || MODE == MODE_MV4;          // one softmax feeds NB P.V products
-    static_assert(MODE != MODE_MV4 || DH == 40, "the four-bank form exists in the packed image only");
+    static_assert(MODE != MODE_MV4 || DH == 40 || DH == 64, "the four-bank form exists at head dims 40 and 64");
     constexpr int NPK = C::npk(NT), NPV = C::npv(NT);
     constexpr int NBUFS = SB ? 1 : 2;
     // PACK (dual-V at Dh = 40): the two banks' V^T rows share ONE LDS image of 3 M-tiles -- rows 0-39 uncond,
@@ -298,6 +300,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void ext_attn_kernel(AttnParams p) {
     // same P.  Saves the 16 v_max3 + permlane of most tiles and most O rescales.
     //   Measured (round 2, cfg2 level 0, fp32 scaling): 4.25 -> 4.03 ms with the bound; the folded form is 3.58 ms.
     constexpr bool BOUND = attn_has_bound(DH);
+    constexpr bool HALF = MODE == MODE_MV4 && DH == 64;   // scores per 32-key half (see the tile loop)
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     auto sK = [&](int buf) { return reinterpret_cast<E*>(smem) + buf * BUF_ELEMS; };
@@ -510,6 +513,74 @@ __global__ __launch_bounds__(64 * NW, MINW) void ext_attn_kernel(AttnParams p) {
         for (int sub = 0; sub < C::SUB; ++sub) {
             const int key0 = tt_cur * KT + sub * 64;  // first key (within the frame) of this 64-key sub-tile
             if (C::SUB > 1 && ragged && key0 >= S) break;   // nothing but padding left in this tile
+            if constexpr (HALF) {
+                // Four banks at Dh = 64: 128 accumulator registers.  The scores are taken per 32-key half -- QK^T, softmax and the
+                // two P.V k-steps of one half before the next -- so 16 score and 8 P registers are live instead of 32 and 16.
+                // Every half is a step of the online softmax of its own (reference point and row sum as below, BOUND form).
+#pragma unroll
+                for (int kt = 0; kt < 2; ++kt) {
+                    f32x16 sh;
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) sh[r] = 0.f;
+#pragma unroll
+                    for (int t = 0; t < C::KS; ++t) {
+                        const E* krow = sK(buf) + (sub * 64 + kt * 32 + l31) * C::KROW + 8 * hi;
+                        sh = T::mfma32(__builtin_bit_cast(vec8, ld16(krow + 16 * t)), qf[0][t], sh);
+                    }
+                    if (ragged && key0 + kt * 32 + 32 > S) {
+#pragma unroll
+                        for (int r = 0; r < 16; ++r)
+                            if (key0 + kt * 32 + cd_row(r, hi) >= S) sh[r] = -INFINITY;
+                    }
+                    static_assert(BOUND && !FOLD && !ONES && QT == 1, "the half-tile steps are written for the Dh = 64 bound form");
+                    // (a second half that lies wholly in the padding never looks: it has no maximum, and P = 0 whatever the reference.
+                    // The test is uniform and costs nothing -- and without it hipcc's register allocation of this kernel spills)
+                    if (__any(s_bound[0] - m_run[0] * c > FOLD_T) && !(ragged && key0 + kt * 32 >= S)) {
+                        float mx = sh[0];
+#pragma unroll
+                        for (int r = 1; r < 16; ++r) mx = fmaxf(mx, sh[r]);
+                        mx = max_with_lane_xor32(mx);
+                        const bool over = (mx - m_run[0]) * c > FOLD_T;
+                        if (__any(over)) {
+                            const float m_new = over ? mx : m_run[0];
+                            const float alpha = __builtin_amdgcn_exp2f((m_run[0] - m_new) * c);  // exp2(-inf) = 0 on the first half
+                            m_run[0] = m_new;
+                            l_run[0] *= alpha;
+#pragma unroll
+                            for (int vb = 0; vb < NB; ++vb)
+#pragma unroll
+                                for (int mt = 0; mt < C::MT; ++mt)
+#pragma unroll
+                                    for (int r = 0; r < 16; ++r) o[vb][0][mt][r] *= alpha;
+                        }
+                    }
+                    const float mc = m_run[0] * c;
+                    const f32x2 mc2 = {mc, mc};
+                    vec8 ph[2];
+                    float lsum = 0.f;
+#pragma unroll
+                    for (int r = 0; r < 16; r += 2) {
+                        const f32x2 x = f32x2{sh[r], sh[r + 1]} * c2 - mc2;
+                        const float p0 = __builtin_amdgcn_exp2f(x[0]);
+                        const float p1 = __builtin_amdgcn_exp2f(x[1]);
+                        lsum += p0 + p1;
+                        ph[r >> 3][r & 7] = (E)p0;
+                        ph[r >> 3][(r & 7) + 1] = (E)p1;
+                    }
+                    l_run[0] += lsum;
+#pragma unroll
+                    for (int ks = 0; ks < 2; ++ks)   // k-step outermost: round-robin over the 8 accumulators
+#pragma unroll
+                        for (int vb = 0; vb < NB; ++vb)
+#pragma unroll
+                            for (int mt = 0; mt < C::MT; ++mt) {
+                                const E* vrow = sV(buf, vb) + (mt * 32 + l31) * C::VROW + sub * 64 + 8 * hi;
+                                o[vb][0][mt] = T::mfma32(__builtin_bit_cast(vec8, ld16(vrow + 16 * (2 * kt + ks))), ph[ks],
+                                                         o[vb][0][mt]);
+                            }
+                }
+                continue;
+            }
             // Program order per tile: QK(q0) QK(q1) | softmax(q0) PV(q0) | softmax(q1) PV(q1).
             // MFMAs execute asynchronously behind the in-order issue, so the softmax VALU of one query
             // tile runs while the matrix pipe works on the other one's QK^T / P.V.
@@ -757,7 +828,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void ext_attn_kernel(AttnParams p) {
         } else if (q_ok[qi]) {
 #pragma unroll
             for (int vb = 0; vb < NB; ++vb) {
-                const int64_t op = (b + vb) * p.o_bs + f * p.o_fs + (int64_t)q_row[qi] * (H * DH) + h * DH;
+                const int64_t op = (b + bank_off(vb)) * p.o_bs + f * p.o_fs + (int64_t)q_row[qi] * (H * DH) + h * DH;
 #pragma unroll
                 for (int mt = 0; mt < C::MT; ++mt)
 #pragma unroll
@@ -2234,7 +2305,7 @@ int launch_one(AttnParams p, hipStream_t st) {
     typedef AttnCfg<DH, KT> C;
     constexpr size_t lds = ((MODE == MODE_DUAL && DH == 40)  ? 2 * (size_t)(C::K_ELEMS + 96 * C::VROW) * 2    // PACK
                             : (MODE == MODE_MV4 && DH == 40) ? 2 * (size_t)(C::K_ELEMS + 192 * C::VROW) * 2   // PACK, four banks
-                                                             : C::lds_bytes(MODE == MODE_DUAL ? 2 : 1)) / (SB ? 2 : 1);
+                                                             : C::lds_bytes(MODE == MODE_DUAL ? 2 : MODE == MODE_MV4 ? 4 : 1)) / (SB ? 2 : 1);
     if (tf_plan_note("one<%d,%d,%d,%s,%d,fq%d%s%s%s>", DH, QT, NW, mode_name(MODE), MINW, FQ ? 1 : 0, KT != 64 ? ",kt128" : "",
                      SB ? ",sb" : "", run_mark<MODE>(p)))
         return 0;
@@ -2442,6 +2513,9 @@ int launch_attn(const AttnParams& p, const void* v, hipStream_t st) {
 #ifndef TF_TUNE_IL64_DMA
 #define TF_TUNE_IL64_DMA 2
 #endif
+        // multi-edit batch under injection: two edits' bank branches in one launch (tf_ext_attn_fwd_edits, TF_ATTN_MULTI_V64).
+        // Four unpacked 64-row banks, 92 KB of double-buffered tiles: ONE workgroup per CU, so 8 waves for two per SIMD (246 VGPRs)
+        if (p.mv4) return launch_one<T, DH, 1, 8, MODE_MV4, 2>(p, st);
 #ifndef TF_TUNE_NO_IL64
         const bool il = p.S % 64 == 0 && p.S >= 512;
 #else
@@ -2704,7 +2778,8 @@ extern "C" int tf_ext_attn_fwd_strided(const void* q, const void* k, const void*
 // single-edit parts: ONE V^T pre-pass over every branch a streaming launch reads, the source branch through the launches of a
 // TF_ATTN_SOURCE_ONLY call, every edit's bank branches through those of a TF_ATTN_BANK_ONLY call on that edit's slabs -- the
 // same kernels on the same values, so bit for bit the `part=` calls' results.  Under injection at Dh = 40 PAIRS of edits may
-// take the four-bank shared-softmax launch instead (MODE_MV4; TF_ATTN_MULTI_V / TF_ATTN_NO_MULTI_V).
+// take the four-bank shared-softmax launch instead (MODE_MV4; TF_ATTN_MULTI_V / TF_ATTN_NO_MULTI_V), at Dh = 64 behind
+// TF_ATTN_MULTI_V64.
 extern "C" size_t tf_ext_attn_edits_workspace_bytes(int K, int S, int H, int Dh, int n_edits, int dtype) {
     if (n_edits < 1 || n_edits > TF_MAX_EDITS) return 0;
     return attn_ws_bytes(K, S, H, Dh, dtype, 1 + 2 * n_edits);
@@ -2717,6 +2792,16 @@ extern "C" size_t tf_ext_attn_edits_workspace_bytes(int K, int S, int H, int Dh,
 // stays behind TF_ATTN_MULTI_V.
 static bool mv4_default(int K, int Kq, int S, int H) {
     return Kq == K && H == 8 && K >= 4 && K <= 8 && S >= 1024 && S <= 4096;
+}
+
+// The same for the four-bank form at Dh = 64 (one<64,1,8,MV4,..>; profiles/r13_attn_edits_d64_ab.txt): ahead of the DUAL
+// composition by far more than the run-to-run spread at the level-0 and level-1 shapes of BASELINE configs 4 and 5, for E = 2
+// and E = 3 -- (K, S, H) = (10, 9216, 5): 28.9 against 36.7 ms, (25, 4096, 5): 31.5 / 42.4, (10, 2304, 10): 3.79 / 4.83,
+// (25, 1024, 10): 4.18 / 5.42 at E = 2.  The rule is the box those four span: every keyframe's queries, 5 or 10 heads, banks
+// of 10 to 25 keyframes, whole 64-key tiles, frames of 1024 to 9216 tokens.  Everything else -- smaller banks, other head
+// counts, ragged or shorter frames, query-frame subsets -- was not measured and stays behind TF_ATTN_MULTI_V64.
+static bool mv4_d64_default(int K, int Kq, int S, int H) {
+    return Kq == K && (H == 5 || H == 10) && K >= 10 && K <= 25 && S % 64 == 0 && S >= 1024 && S <= 9216;
 }
 
 // The masked composition: bit e of inject_mask = edit e injects (its uncond and cond branches use the source's q and k).
@@ -2740,11 +2825,13 @@ static int attn_fwd_edits_masked(const char* name, const void* q, const void* k,
     const bool do_bank = part != TF_ATTN_SOURCE_ONLY, do_src = part != TF_ATTN_BANK_ONLY;
     TF_ARG((flags & (TF_ATTN_MULTI_V | TF_ATTN_NO_MULTI_V)) != (TF_ATTN_MULTI_V | TF_ATTN_NO_MULTI_V), TF_ERR_SHAPE,
            "%s: TF_ATTN_MULTI_V and TF_ATTN_NO_MULTI_V exclude each other", name);
+    TF_ARG((flags & (TF_ATTN_MULTI_V64 | TF_ATTN_NO_MULTI_V)) != (TF_ATTN_MULTI_V64 | TF_ATTN_NO_MULTI_V), TF_ERR_SHAPE,
+           "%s: TF_ATTN_MULTI_V64 and TF_ATTN_NO_MULTI_V exclude each other", name);
     TF_ARG(!(flags & TF_ATTN_INJECT), TF_ERR_SHAPE, "%s: TF_ATTN_INJECT beside a mask (the mask is the injection state)", name);
     const unsigned all = (1u << n_edits) - 1u;
     TF_ARG(!(inject_mask & ~all), TF_ERR_SHAPE, "%s: inject_mask=0x%x has bits at or above n_edits=%d", name, inject_mask,
            n_edits);
-    const int base = flags & ~(TF_ATTN_MULTI_V | TF_ATTN_NO_MULTI_V | TF_ATTN_BANK_ONLY | TF_ATTN_SOURCE_ONLY);
+    const int base = flags & ~(TF_ATTN_MULTI_V | TF_ATTN_MULTI_V64 | TF_ATTN_NO_MULTI_V | TF_ATTN_BANK_ONLY | TF_ATTN_SOURCE_ONLY);
     if (n_edits == 1)   // today's layout: today's call (the hints of the four-bank form have nothing to select); the compact
                         // q / k of one edit is the dense one as far as its launches read it
         return attn_fwd_core(q, k, v, out, K, Kq, q_frame0, S, H, Dh, ld, strides, scale,
@@ -2760,9 +2847,12 @@ static int attn_fwd_edits_masked(const char* name, const void* q, const void* k,
     auto at = [](const void* ptr, int64_t elems, int64_t esz) {
         return static_cast<const void*>(static_cast<const unsigned char*>(ptr) + elems * esz);
     };
-    // the four-bank form: Dh = 40, fp32 score scaling, at least one pair of INJECTING edits
-    const bool mv_ok = n_inj >= 2 && Dh == 40 && !(flags & TF_ATTN_FOLD_SCALE);
-    const bool mv = mv_ok && !(flags & TF_ATTN_NO_MULTI_V) && ((flags & TF_ATTN_MULTI_V) || mv4_default(K, Kq, S, H));
+    // the four-bank form: Dh = 40 or 64 (each behind its own hint and its own measured default), fp32 score scaling, at least
+    // one pair of INJECTING edits
+    const bool mv_ok = n_inj >= 2 && (Dh == 40 || Dh == 64) && !(flags & TF_ATTN_FOLD_SCALE);
+    const bool mv_on = Dh == 40 ? ((flags & TF_ATTN_MULTI_V) || mv4_default(K, Kq, S, H))
+                                : ((flags & TF_ATTN_MULTI_V64) || mv4_d64_default(K, Kq, S, H));
+    const bool mv = mv_ok && !(flags & TF_ATTN_NO_MULTI_V) && mv_on;
     // the pair launches and the odd edit beside them are one-pass streaming launches
     const int inj_flags = base | TF_ATTN_INJECT | TF_ATTN_BANK_ONLY | (mv ? TF_ATTN_NO_SPLIT | TF_ATTN_NO_FUSED : 0);
     const int non_flags = base | TF_ATTN_BANK_ONLY;
@@ -3138,8 +3228,9 @@ static int run_edits_check(const char* fn, int n_edits, unsigned inject_mask, in
     TF_ARG(!(flags & TF_ATTN_INJECT), TF_ERR_SHAPE, "%s: TF_ATTN_INJECT beside a mask (the mask is the injection state)", fn);
     TF_ARG(!(inject_mask & ~((1u << n_edits) - 1u)), TF_ERR_SHAPE, "%s: inject_mask=0x%x has bits at or above n_edits=%d", fn,
            inject_mask, n_edits);
-    TF_ARG(!(flags & TF_ATTN_MULTI_V), TF_ERR_SHAPE,
-           "%s: TF_ATTN_MULTI_V -- the four-bank kernel has no partial epilogue, a run takes the DUAL composition", fn);
+    TF_ARG(!(flags & (TF_ATTN_MULTI_V | TF_ATTN_MULTI_V64)), TF_ERR_SHAPE,
+           "%s: TF_ATTN_MULTI_V / TF_ATTN_MULTI_V64 -- the four-bank kernel has no partial epilogue, a run takes the DUAL composition",
+           fn);
     return 0;
 }
 

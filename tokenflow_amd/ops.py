@@ -147,8 +147,13 @@ def attn_run_plan(K: int, Kq: int, run_n: int, n_runs: int, S: int, heads: int, 
                         _DT[dtype])
 
 
-def _multi_v_bits(multi_v: Optional[bool]) -> int:
-    return 0 if multi_v is None else _lib.TF_ATTN_MULTI_V if multi_v else _lib.TF_ATTN_NO_MULTI_V
+def _multi_v_bits(multi_v: Optional[bool], multi_v64: Optional[bool] = None) -> int:
+    """multi_v: the four-bank form at head dim 40 forced on / off; False switches the form off at EVERY head dim.
+    multi_v64: True forces the form on at head dim 64 (TF_ATTN_MULTI_V64); None / False leave it to the library's measured
+    rule.
+    multi_v=False with multi_v64=True is the library's TF_ERR_SHAPE."""
+    bits = 0 if multi_v is None else _lib.TF_ATTN_MULTI_V if multi_v else _lib.TF_ATTN_NO_MULTI_V
+    return bits | (_lib.TF_ATTN_MULTI_V64 if multi_v64 else 0)
 
 
 def _edit_mask(what: str, mask, n_edits: int, inject: bool = False) -> int:
@@ -166,11 +171,13 @@ def _edit_mask(what: str, mask, n_edits: int, inject: bool = False) -> int:
 def attn_edits_plan(K: int, Kq: int, S: int, heads: int, dh: int, inject: bool, n_edits: int,
                     dtype: torch.dtype = torch.bfloat16, out_dtype: Optional[torch.dtype] = None,
                     fold_scale: Optional[bool] = None, no_split: Optional[bool] = None, fused: Optional[bool] = None,
-                    multi_v: Optional[bool] = None, hints: int = 0, inject_mask: Optional[int] = None) -> list:
+                    multi_v: Optional[bool] = None, hints: int = 0, inject_mask: Optional[int] = None,
+                    multi_v64: Optional[bool] = None) -> list:
     """The launches `ext_attn_edits` makes for dense [(1+2E)K,S,heads*dh] tensors, as tokens (tf_ext_attn_edits_plan: the
-    tokens of `attn_plan`; the four-bank launch of a pair of edits is 'one<40,1,4,MV4,2,fq0>').  Host only: needs no GPU.
+    tokens of `attn_plan`; the four-bank launch of a pair of edits is 'one<40,1,4,MV4,2,fq0>', at head dim 64 with
+    multi_v64=True 'one<64,1,8,MV4,2,fq1>').  Host only: needs no GPU.
     inject_mask: the per-edit injection state of `ext_attn_edits` (tf_ext_attn_edits_masked_plan); `inject` must be False."""
-    flags = _attn_flags(inject, "all", out_dtype == torch.float32, fold_scale, no_split, fused, hints) | _multi_v_bits(multi_v)
+    flags = _attn_flags(inject, "all", out_dtype == torch.float32, fold_scale, no_split, fused, hints) | _multi_v_bits(multi_v, multi_v64)
     if inject_mask is not None:
         mask = _edit_mask("attn_edits_plan", inject_mask, n_edits, inject)
         return _plan_tokens("tf_ext_attn_edits_masked_plan", _lib.load().tf_ext_attn_edits_masked_plan, K, Kq, S, heads, dh,
@@ -252,14 +259,16 @@ def ext_attn_edits(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int
                    n_edits: int, out: Optional[torch.Tensor] = None, q_frame0: int = 0,
                    fold_scale: Optional[bool] = None, out_dtype: Optional[torch.dtype] = None,
                    no_split: Optional[bool] = None, fused: Optional[bool] = None, multi_v: Optional[bool] = None,
-                   hints: int = 0, inject_mask: Optional[int] = None) -> torch.Tensor:
+                   hints: int = 0, inject_mask: Optional[int] = None, multi_v64: Optional[bool] = None) -> torch.Tensor:
     """`ext_attn` for a multi-edit batch: E = n_edits edits of one source video, B = 1 + 2E branches
     [source | uncond_1 | cond_1 | ... | uncond_E | cond_E].  k, v: [B*K,S,D], q: [B*Kq,S,D]; returns [B*Kq,S,D].
     The slices of edit e (source, uncond_e, cond_e) are what `ext_attn` computes on [source | uncond_e | cond_e]: the
     bank branches equal `ext_attn_views(part="bank")` on that edit's slabs and the source branch `part="source"` bit for
     bit -- except where pairs of edits take the four-bank shared-softmax launch under injection (head dim 40), which is
     held to the oracle within the attention bound.  multi_v: True / False force that form on / off (TF_ATTN_MULTI_V /
-    TF_ATTN_NO_MULTI_V), None = the library's measured default.  n_edits = 1 is `ext_attn`.  Other arguments as `ext_attn`.
+    TF_ATTN_NO_MULTI_V), None = the library's measured default.  multi_v64=True forces the form on at head dim 64
+    (TF_ATTN_MULTI_V64; multi_v=True selects nothing there, multi_v=False switches it off at every head dim, and the two
+    together are an error).  n_edits = 1 is `ext_attn`.  Other arguments as `ext_attn`.
     inject_mask: the injection state PER EDIT (tf_ext_attn_fwd_edits_masked): bit e set = edit e (0-based) uses the source's
     q and k, clear = its own; `inject` must then be False.  Every edit keeps the identity above with its own flag; the
     four-bank form pairs the injecting edits, neighbours or not.  None = the one shared state `inject`, today's call."""
@@ -297,7 +306,7 @@ def ext_attn_edits(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int
         out = torch.empty(Bq, S, D, dtype=out_dtype, device=q.device)
     elif out.dtype != out_dtype or not out.is_contiguous() or out.shape != (Bq, S, D):
         raise ValueError("ext_attn_edits: `out` must be a contiguous [B*Kq,S,D] tensor of out_dtype")
-    flags = _attn_flags(inject, "all", out_dtype == torch.float32, fold_scale, no_split, fused, hints) | _multi_v_bits(multi_v)
+    flags = _attn_flags(inject, "all", out_dtype == torch.float32, fold_scale, no_split, fused, hints) | _multi_v_bits(multi_v, multi_v64)
     nbytes = lib.tf_ext_attn_edits_workspace_bytes(K, S, heads, dh, E, dt)
     ws = _workspace(nbytes, q.device)
     fs = S * ld
@@ -365,7 +374,7 @@ def ext_attn_edits_views(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out:
                          n_edits: int, inject_mask: int, part: str = "all", qk_compact: bool = False,
                          branch0=(0, 0, 0, 0), q_frame0: int = 0, fold_scale: Optional[bool] = None,
                          no_split: Optional[bool] = None, fused: Optional[bool] = None, multi_v: Optional[bool] = None,
-                         hints: int = 0, stream: Optional[int] = None) -> torch.Tensor:
+                         hints: int = 0, stream: Optional[int] = None, multi_v64: Optional[bool] = None) -> torch.Tensor:
     """The parts of `ext_attn_edits` on strided 4-D views [branches, frames, S, D] (tf_ext_attn_fwd_edits_part), in the manner
     of `ext_attn_views`: E = n_edits edits, v and out addressed as [source | uncond_1 | cond_1 | ...] (1 + 2E branches),
     inject_mask the injection state per edit.  part = "bank": the bank branches of EVERY edit (the source slabs of v and out
@@ -405,7 +414,7 @@ def ext_attn_edits_views(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out:
         if b0 > lo or b0 + t.shape[0] < hi:
             raise ValueError(f"ext_attn_edits_views: {what} holds branches [{b0}, {b0 + t.shape[0]}), part '{part}' of "
                              f"{E} edits with mask {mask:#x} reads [{lo}, {hi})")
-    flags = _attn_flags(False, part, out.dtype == torch.float32, fold_scale, no_split, fused, hints) | _multi_v_bits(multi_v)
+    flags = _attn_flags(False, part, out.dtype == torch.float32, fold_scale, no_split, fused, hints) | _multi_v_bits(multi_v, multi_v64)
     ws = _workspace(lib.tf_ext_attn_edits_workspace_bytes(K, S, heads, dh, E, dt), q.device, stream=stream)
     strides = (ctypes.c_int64 * 9)(q_bs, q_fs, k_bs, k_fs, v_bs, v_fs, o_bs, o_fs, ld_q)
     _launch(dev, "tf_ext_attn_fwd_edits_part", lib.tf_ext_attn_fwd_edits_part, qp, kp, vp, op, K, Kq, int(q_frame0), S, heads,
@@ -418,11 +427,11 @@ def attn_edits_part_plan(K: int, Kq: int, S: int, heads: int, dh: int, n_edits: 
                          qk_compact: bool = False, dtype: torch.dtype = torch.bfloat16,
                          out_dtype: Optional[torch.dtype] = None, fold_scale: Optional[bool] = None,
                          no_split: Optional[bool] = None, fused: Optional[bool] = None, multi_v: Optional[bool] = None,
-                         hints: int = 0) -> list:
+                         hints: int = 0, multi_v64: Optional[bool] = None) -> list:
     """The launches of `ext_attn_edits_views` for dense tensors, as tokens (tf_ext_attn_edits_part_plan): those of
     `attn_edits_plan(inject_mask=...)` for the part, or -- where every part takes the fused kernel -- ONE token such as
     'fused[qw=1,kw=4,qb=1,prec=1,sets=4]' (',sets=N' for N > 2 tensor sets).  Host only: needs no GPU."""
-    flags = _attn_flags(False, part, out_dtype == torch.float32, fold_scale, no_split, fused, hints) | _multi_v_bits(multi_v)
+    flags = _attn_flags(False, part, out_dtype == torch.float32, fold_scale, no_split, fused, hints) | _multi_v_bits(multi_v, multi_v64)
     mask = _edit_mask("attn_edits_part_plan", inject_mask, n_edits)
     return _plan_tokens("tf_ext_attn_edits_part_plan", _lib.load().tf_ext_attn_edits_part_plan, K, Kq, S, heads, dh,
                         int(n_edits), mask, 1 if qk_compact else 0, flags, _DT[dtype])

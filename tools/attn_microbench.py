@@ -4,7 +4,8 @@ build so that kernel variants can be A/B-ed:  TOKENFLOW_HIP_LIB=<.so> python too
 Prints avg/min ms over `reps` launches (HIP events on the launch stream) and TFLOP/s (algorithmic).
 --edits E: a multi-edit batch of E edits under q/k injection, alternating A/B of three arms per shape -- (a) E full
 single-edit `ext_attn` calls (one per prompt), (b) `ext_attn_edits`, the composition, (c) `ext_attn_edits` with the
-four-bank form on -- median / min over --rounds rounds, plus the spread of arm (b) against itself.
+four-bank form on (head dim 40: multi_v=True; head dim 64: multi_v64=True) -- median / min over --rounds rounds, plus the
+spread of arm (b) against itself; the largest absolute difference between the results of (c) and (b) is printed first.
 --edits E --inject-mask M: the edits differ in their injection state (bit e of M = edit e injects) -- (a) E single-edit
 `ext_attn` calls, each with its own flag, (b) ONE masked call `ext_attn_edits(..., inject_mask=M)` with the library's
 default rule, (b') the same again (the spread), (c) the masked call as a pure composition (multi_v=False).
@@ -119,9 +120,13 @@ def edits_masked_ab(shapes, E, mask, dt, rounds, single_lib):
             print(f"  {name:26s} median {med:.3f} ms  min {mn:.3f} ms  max {mx:.3f} ms", flush=True)
 
 
-def edits_ab(shapes, E, dt, rounds):
+def edits_ab(shapes, E, dt, rounds, single_lib=None):
     g = torch.Generator(device="cuda").manual_seed(0)
     B = 1 + 2 * E
+    single, where = (lambda q1, k1, v1, h, sc, inj, out: ops.ext_attn(q1, k1, v1, h, sc, inj, out=out)), "this build"
+    if single_lib:
+        abi, single = foreign_single_edit(single_lib)
+        where = f"{single_lib} (ABI {abi})"
     for K, S, h, d in shapes:
         D = h * d
         q, k, v = (torch.randn(B * K, S, D, generator=g, device="cuda").to(dt) for _ in range(3))
@@ -134,16 +139,23 @@ def edits_ab(shapes, E, dt, rounds):
 
         def a_single():
             for q1, k1, v1 in singles:
-                ops.ext_attn(q1, k1, v1, h, d ** -0.5, True, out=out1)
+                single(q1, k1, v1, h, d ** -0.5, True, out1)
+        on = dict(multi_v64=True) if d == 64 else dict(multi_v=True)   # the hint of the four-bank form at this head dim
         arms = {"(a) E single-edit calls": a_single,
                 "(b) composition": lambda: ops.ext_attn_edits(q, k, v, h, d ** -0.5, True, E, out=out, multi_v=False),
                 "(b') composition again": lambda: ops.ext_attn_edits(q, k, v, h, d ** -0.5, True, E, out=out, multi_v=False)}
-        plan_c = ops.attn_edits_plan(K, K, S, h, d, True, E, dtype=dt, multi_v=True)
+        plan_c = ops.attn_edits_plan(K, K, S, h, d, True, E, dtype=dt, **on)
         if any("MV4" in t for t in plan_c):
-            arms["(c) four-bank form"] = lambda: ops.ext_attn_edits(q, k, v, h, d ** -0.5, True, E, out=out, multi_v=True)
-        print(f"ext_attn_edits {str(dt)[6:]} K={K} S={S} h={h} d={d} inject=1 E={E}  ({rounds} alternating rounds)")
+            arms["(c) four-bank form"] = lambda: ops.ext_attn_edits(q, k, v, h, d ** -0.5, True, E, out=out, **on)
+        print(f"ext_attn_edits {str(dt)[6:]} K={K} S={S} h={h} d={d} inject=1 E={E}  ({rounds} alternating rounds; "
+              f"arm (a): {where})")
         print(f"  plan (b): {ops.attn_edits_plan(K, K, S, h, d, True, E, dtype=dt, multi_v=False)}")
         print(f"  plan (c): {plan_c}")
+        if "(c) four-bank form" in arms:   # the two forms on the same inputs, before anything is timed
+            res_b = ops.ext_attn_edits(q, k, v, h, d ** -0.5, True, E, multi_v=False).float()
+            res_c = ops.ext_attn_edits(q, k, v, h, d ** -0.5, True, E, **on).float()
+            print(f"  max |(c) - (b)| = {float((res_c - res_b).abs().max()):.3e}  (max |(b)| = {float(res_b.abs().max()):.3e})")
+            del res_b, res_c
         for name, (med, mn, mx) in ab(arms, rounds).items():
             print(f"  {name:26s} median {med:.3f} ms  min {mn:.3f} ms  max {mx:.3f} ms", flush=True)
 
@@ -163,7 +175,7 @@ def main():
     if E and mask is not None:
         return edits_masked_ab(shapes, E, mask, dt, rounds, single_lib)
     if E:
-        return edits_ab(shapes, E, dt, rounds)
+        return edits_ab(shapes, E, dt, rounds, single_lib)
     g = torch.Generator(device="cuda").manual_seed(0)
     for K, S, h, d in shapes:
         D = h * d
