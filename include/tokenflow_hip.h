@@ -75,6 +75,15 @@ extern "C" {
    1024 <= S <= 9216; the composition everywhere else.  The run entry points (tf_ext_attn_run_edits,
    tf_ext_attn_runs_merge_edits) refuse it as they refuse TF_ATTN_MULTI_V. */
 #define TF_ATTN_MULTI_V64 (1 << 21)
+/* tf_ext_attn_run_edits / tf_ext_attn_run_edits_plan only (additive to ABI 11): the four-bank form in a run call, Dh = 40 and
+   64 alike -- the injecting edits are paired ascending and each pair is ONE four-bank run launch that leaves the partial
+   results of both edits (plan tokens one<40,1,4,MV4,2,fq0,run> / one<64,1,8,MV4,2,fq1,run>); an odd last injecting edit, the
+   other edits and the source branch keep their launches.  Opt-in only: a run's kernel choice is a function of its arguments,
+   so there is no measured default.  A no-op (same plan, same bits) where the form does not exist: Dh not 40 or 64,
+   TF_ATTN_FOLD_SCALE, TF_ATTN_NO_MULTI_V, fewer than two injecting edits, n_edits = 1.  tf_ext_attn_runs_merge_edits accepts
+   and ignores it (one merge folds pair-written and DUAL-written partial results alike); every call of a run set is given the
+   same value.  The one-call hints TF_ATTN_MULTI_V and TF_ATTN_MULTI_V64 stay TF_ERR_SHAPE in the run entry points. */
+#define TF_ATTN_RUN_MULTI_V (1 << 22)
 
 /* most edits of one multi-edit batch (the *_edits entry points) */
 #define TF_MAX_EDITS 8
@@ -368,8 +377,14 @@ TF_API int tf_ext_attn_run_plan(int K, int Kq, int run_n, int n_runs, int S, int
  *   Launches of a run call: ONE V^T pre-pass over the run's frames of every branch the call reads (at the positions the
  *   frames have in the image of the whole bank; key norms of the source and of the edits that do not inject), then every
  *   edit through the launches of its own tf_ext_attn_run call -- the injecting edits first, then the others, ascending --
- *   then the source launch.  Injecting edits take the DUAL run form where the single-edit run does; the four-bank form has no
- *   partial epilogue: TF_ATTN_MULTI_V and TF_ATTN_MULTI_V64 are TF_ERR_SHAPE, TF_ATTN_NO_MULTI_V is accepted and ignored.
+ *   then the source launch.  Injecting edits take the DUAL run form where the single-edit run does.  The one-call hints of
+ *   the four-bank form select nothing in a run: TF_ATTN_MULTI_V and TF_ATTN_MULTI_V64 are TF_ERR_SHAPE, TF_ATTN_NO_MULTI_V is
+ *   accepted.  The run form has an opt-in of its own, TF_ATTN_RUN_MULTI_V (Dh = 40, 64): the injecting edits are paired
+ *   ascending (1st with 2nd, 3rd with 4th, whatever lies between them) and each pair is ONE four-bank run launch in the place
+ *   of its first edit's launches -- one QK^T and one softmax over the source's q / k for the four P.V products, the partial
+ *   rows of each edit in that edit's own region, split into exactly the slots the header records for the injecting state.  An
+ *   odd last injecting edit, the other edits and the source branch keep their launches and their bits; a paired edit is held
+ *   to the oracle bound, not to its single-edit run set bit for bit.  The merge call accepts and ignores the bit.
  *   q, k, v, out, strides: as tf_ext_attn_run, v and out addressed over all B branches (a bank-only call never touches their
  *   source slabs).  compact: bit 0 = q, bit 1 = k is in the compact layout of tf_ext_attn_fwd_edits_part (slot 0 the
  *   source, then (uncond, cond) of every NON-injecting edit, ascending); the two are separate, so a rank's remote runs read

@@ -14,6 +14,7 @@ TF_ATTN_NO_FUSED, TF_ATTN_FUSED = 128, 1 << 17
 TF_ATTN_HINT_QB2, TF_ATTN_PRECISE_P, TF_ATTN_NO_PRECISE_P = 1 << 14, 1 << 15, 1 << 16
 TF_ATTN_MULTI_V, TF_ATTN_NO_MULTI_V = 1 << 19, 1 << 20   # ext_attn_edits: the four-bank form for pairs of edits forced on / off
 TF_ATTN_MULTI_V64 = 1 << 21                               # ... the form at head dim 64 forced on (TF_ATTN_NO_MULTI_V switches it off too)
+TF_ATTN_RUN_MULTI_V = 1 << 22                             # ext_attn_runs_edits: pairs of injecting edits as ONE four-bank run launch (Dh 40, 64)
 TF_ATTN_HINT_MIX = 1 << 18   # Dh = 40 streaming kernel: the mixed-MFMA-shape form whatever the launch size (S % 64 == 0, S >= 256)
 
 

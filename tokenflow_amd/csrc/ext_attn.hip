@@ -767,8 +767,9 @@ __global__ __launch_bounds__(64 * NW, MINW) void ext_attn_kernel(AttnParams p) {
             if (q_ok[qi]) {
                 constexpr int PS = DH + 8;
                 const float lshift = FOLD ? m_run[qi] : m_run[qi] * c;
+                // (four banks: the second edit's rows lie p.gap branches behind the first's, in that edit's own partial region)
                 auto row_ptr = [&](int vb) {
-                    const int64_t R = (((int64_t)(b - 1 + vb) * Kq + f) * H + h) * S + q_row[qi];
+                    const int64_t R = (((int64_t)(b - 1 + bank_off(vb)) * Kq + f) * H + h) * S + q_row[qi];
                     return p.partials + (R * p.pslots + seg) * PS;
                 };
                 if constexpr (PACK) {
@@ -3084,6 +3085,11 @@ struct RunEditsPart {
     int n_edits;    // edits of the workspace layout
     int edit;       // whose partial region: shift = 2 * edit
     int src_only;   // the source branch of the query frames alone (edit = 0)
+    int mv4_gap;    // > 0: ONE four-bank launch for `edit` and the injecting edit mv4_gap branches behind it (2 = the next edit)
+
+    static RunEditsPart bank(int n_edits, int e) { return RunEditsPart{n_edits, e, 0, 0}; }
+    static RunEditsPart pair_mv4(int n_edits, int e0, int e1) { return RunEditsPart{n_edits, e0, 0, 2 * (e1 - e0)}; }
+    static RunEditsPart source(int n_edits) { return RunEditsPart{n_edits, 0, 1, 0}; }
 };
 
 // What a run call checks before anything touches the device.
@@ -3179,6 +3185,9 @@ int attn_run_core(const char* fn, const void* q, const void* k, const void* v, v
     p.o_fs = strides[7];
     p.c = (float)((double)scale * 1.4426950408889634);
     p.gap = 2;
+    // a pair of injecting edits in the four-bank form: banks 2 and 3 are the second edit's, in the image and in the partial
+    // results alike (the edits' partial regions are one array of 2E branches, p.partials points into the first edit's)
+    if (ed && ed->mv4_gap) p.mv4 = 1, p.gap = ed->mv4_gap;
     p.no_pack = ed ? 1 : 0;   // the composing call has packed the run's frames of every branch
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     return dtype == TF_BF16 ? dispatch_dh<BF16>(Dh, p, v_run, st) : dispatch_dh<F16>(Dh, p, v_run, st);
@@ -3229,7 +3238,8 @@ static int run_edits_check(const char* fn, int n_edits, unsigned inject_mask, in
     TF_ARG(!(inject_mask & ~((1u << n_edits) - 1u)), TF_ERR_SHAPE, "%s: inject_mask=0x%x has bits at or above n_edits=%d", fn,
            inject_mask, n_edits);
     TF_ARG(!(flags & (TF_ATTN_MULTI_V | TF_ATTN_MULTI_V64)), TF_ERR_SHAPE,
-           "%s: TF_ATTN_MULTI_V / TF_ATTN_MULTI_V64 -- the four-bank kernel has no partial epilogue, a run takes the DUAL composition",
+           "%s: TF_ATTN_MULTI_V / TF_ATTN_MULTI_V64 -- the one-call hints select nothing in a run, whose four-bank form is opted into "
+           "with TF_ATTN_RUN_MULTI_V",
            fn);
     return 0;
 }
@@ -3263,7 +3273,10 @@ extern "C" int tf_ext_attn_runs_merge(void* out, int K, int Kq, int S, int H, in
 // the source and of the edits that do not inject; in a bank-only call under injection the first injecting branch computes
 // the source's), then every edit's bank branches through the launches of its own tf_ext_attn_run call -- base pointers 2e
 // branches in: q / k unless injected, v, out, the image, the norm table, the edit's partial region -- then the source branch.
-// No fused kernel, no four-bank form: neither has a partial epilogue.
+// No fused kernel: it has no partial epilogue.  With TF_ATTN_RUN_MULTI_V (Dh = 40, 64, fp32 score scaling) the injecting edits
+// are paired ascending and each pair is ONE four-bank run launch (MODE_MV4) over the source's q / k: it splits into the slots
+// the pre-pass header records for the injecting state and leaves each edit's partial rows in that edit's region, so the
+// header, the layout and the merge are those of the DUAL composition.
 extern "C" size_t tf_ext_attn_runs_edits_workspace_bytes(int K, int Kq, int S, int H, int Dh, int n_runs, int n_edits,
                                                          int dtype) {
     if (n_edits < 1 || n_edits > TF_MAX_EDITS) return 0;
@@ -3279,7 +3292,7 @@ extern "C" int tf_ext_attn_run_edits(const void* q, const void* k, const void* v
     const char* const fn = "tf_ext_attn_run_edits";
     if (const int rc = run_edits_check(fn, n_edits, inject_mask, flags)) return rc;
     TF_ARG(compact >= 0 && compact <= 3, TF_ERR_SHAPE, "%s: compact=%d (bit 0: q, bit 1: k)", fn, compact);
-    const int base = flags & ~(TF_ATTN_NO_MULTI_V | TF_ATTN_BANK_ONLY);
+    const int base = flags & ~(TF_ATTN_NO_MULTI_V | TF_ATTN_RUN_MULTI_V | TF_ATTN_BANK_ONLY);
     const int part = flags & TF_ATTN_BANK_ONLY;
     if (n_edits == 1)   // today's layout, today's launches (the compact q / k of one edit is the dense one as far as it is read)
         return attn_run_core(fn, q, k, v, out, K, Kq, q_frame0, run_f0, run_n, run, n_runs, S, H, Dh, ld, strides, scale,
@@ -3325,8 +3338,8 @@ extern "C" int tf_ext_attn_run_edits(const void* q, const void* k, const void* v
     auto at = [](const void* ptr, int64_t elems, int64_t esz) {
         return static_cast<const void*>(static_cast<const unsigned char*>(ptr) + elems * esz);
     };
-    auto call = [&](int e, int fl, bool src) {   // the bank branches of edit e / the source branch
-        const RunEditsPart ed{n_edits, src ? 0 : e, src ? 1 : 0};
+    auto call = [&](int e, int fl, const RunEditsPart& ed) {   // the bank branches of edit e (of a pair from e on) / the source branch
+        const bool src = ed.src_only != 0;
         const int sh = src ? 0 : 2 * e;
         const bool own_qk = !src && !(fl & TF_ATTN_INJECT);
         const int qsh = own_qk ? ((compact & 1) ? c_sh[e] : 2 * e) : 0, ksh = own_qk ? ((compact & 2) ? c_sh[e] : 2 * e) : 0;
@@ -3334,13 +3347,24 @@ extern "C" int tf_ext_attn_run_edits(const void* q, const void* k, const void* v
                              const_cast<void*>(at(out, sh * strides[6], osz)), K, Kq, q_frame0, run_f0, run_n, run, n_runs, S, H,
                              Dh, ld, strides, scale, fl, dtype, ws, ws_bytes, stream, &ed);
     };
-    // bank branches first (the long problems): the injecting edits, then the others; then the source branch
-    for (int i = 0; i < n_inj; ++i)
-        if (const int rc = call(inj_e[i], base | TF_ATTN_INJECT | TF_ATTN_BANK_ONLY, false)) return rc;
-    for (int i = 0; i < n_non; ++i)
-        if (const int rc = call(non_e[i], base | TF_ATTN_BANK_ONLY, false)) return rc;
+    // the four-bank form of a run (TF_ATTN_RUN_MULTI_V): Dh = 40 or 64, fp32 score scaling, at least one pair of INJECTING edits
+    const bool mv = (flags & TF_ATTN_RUN_MULTI_V) && !(flags & (TF_ATTN_NO_MULTI_V | TF_ATTN_FOLD_SCALE)) && (Dh == 40 || Dh == 64) &&
+                    n_inj >= 2;
+    // bank branches first (the long problems): the injecting edits (pairs in the four-bank form, an odd last one in its own
+    // launches), then the others; then the source branch
+    int i = 0;
+    if (mv)
+        for (; i + 2 <= n_inj; i += 2)
+            if (const int rc = call(inj_e[i], base | TF_ATTN_INJECT | TF_ATTN_BANK_ONLY,
+                                    RunEditsPart::pair_mv4(n_edits, inj_e[i], inj_e[i + 1])))
+                return rc;
+    for (; i < n_inj; ++i)
+        if (const int rc = call(inj_e[i], base | TF_ATTN_INJECT | TF_ATTN_BANK_ONLY, RunEditsPart::bank(n_edits, inj_e[i])))
+            return rc;
+    for (i = 0; i < n_non; ++i)
+        if (const int rc = call(non_e[i], base | TF_ATTN_BANK_ONLY, RunEditsPart::bank(n_edits, non_e[i]))) return rc;
     // (the source launch sees TF_ATTN_INJECT iff every edit injects, as in the one-call form: its result does not depend on it)
-    return do_src ? call(0, base | (n_non == 0 ? TF_ATTN_INJECT : 0), true) : 0;
+    return do_src ? call(0, base | (n_non == 0 ? TF_ATTN_INJECT : 0), RunEditsPart::source(n_edits)) : 0;
 }
 
 extern "C" int tf_ext_attn_runs_merge_edits(void* out, int K, int Kq, int S, int H, int Dh, int n_runs, int n_edits,

@@ -698,7 +698,8 @@ extern "C" int tf_rank_pivotal_edits(tf_rank* rk, const void* q, const void* k, 
         auto shifted = [](const El* base, int64_t elems) {
             return reinterpret_cast<const El*>(reinterpret_cast<uintptr_t>(base) + (uintptr_t)(elems * (int64_t)sizeof(El)));
         };
-        const int run_flags = flags & (TF_ATTN_FOLD_SCALE | TF_ATTN_HINT_MIX | TF_ATTN_NO_SPLIT);
+        // (TF_ATTN_RUN_MULTI_V: the four-bank run launches for pairs of injecting edits, the same in every call of the set)
+        const int run_flags = flags & (TF_ATTN_FOLD_SCALE | TF_ATTN_HINT_MIX | TF_ATTN_NO_SPLIT | TF_ATTN_RUN_MULTI_V);
         auto local_run = [&](hipStream_t on) {
             return tf_ext_attn_run_edits(q, shifted(ke, -(int64_t)rk->kf0 * k_fs), shifted(ve, -(int64_t)rk->kf0 * v_fs), out_loc,
                                          K, Kl, rk->kf0, R.f0[0], R.len[0], 0, R.n, S, H, Dh, ld, loc_strides, scale, run_flags,

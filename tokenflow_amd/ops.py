@@ -547,14 +547,21 @@ def ext_attn_runs(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int,
     return out
 
 
+def _run_multi_v_bit(multi_v: bool) -> int:
+    """TF_ATTN_RUN_MULTI_V of the multi-edit run calls (the same in every call of a run set, the merge included)."""
+    return _lib.TF_ATTN_RUN_MULTI_V if multi_v else 0
+
+
 def attn_run_edits_plan(K: int, Kq: int, run_n: int, n_runs: int, S: int, heads: int, dh: int, n_edits: int, inject_mask: int,
                         dtype: torch.dtype = torch.bfloat16, bank_only: bool = False, out_dtype: Optional[torch.dtype] = None,
-                        fold_scale: Optional[bool] = None, no_split: bool = False, hints: int = 0) -> list:
+                        fold_scale: Optional[bool] = None, no_split: bool = False, hints: int = 0,
+                        multi_v: bool = False) -> list:
     """The launches of ONE run call of `ext_attn_runs_edits` over run_n of the bank's K frames, followed by the merge, as
     tokens (tf_ext_attn_run_edits_plan): 'vt_pack', per edit -- the injecting ones first, then the others, ascending -- the
-    ',run>' tokens of its own bank-only `attn_run_plan`, the source token unless bank_only, 'merge[runs=N,edits=E]'.  Host
-    only."""
-    flags = _run_flags(False, bank_only, out_dtype == torch.float32, fold_scale, no_split, hints)
+    ',run>' tokens of its own bank-only `attn_run_plan`, the source token unless bank_only, 'merge[runs=N,edits=E]'.
+    multi_v (TF_ATTN_RUN_MULTI_V, head dims 40 and 64): each pair of injecting edits is ONE ',MV4,...,run>' token in the place
+    of its first edit's tokens.  Host only."""
+    flags = _run_flags(False, bank_only, out_dtype == torch.float32, fold_scale, no_split, hints) | _run_multi_v_bit(multi_v)
     mask = _edit_mask("attn_run_edits_plan", inject_mask, n_edits)
     return _plan_tokens("tf_ext_attn_run_edits_plan", _lib.load().tf_ext_attn_run_edits_plan, K, Kq, run_n, n_runs, S, heads,
                         dh, int(n_edits), mask, flags, _DT[dtype])
@@ -564,7 +571,7 @@ def ext_attn_runs_edits_views(q: torch.Tensor, kv_runs: Sequence, out: torch.Ten
                               inject_mask: int, runs: Sequence, K: int, branch0=(0, 0), q_frame0: int = 0,
                               q_compact: bool = False, streams: Optional[Sequence] = None,
                               fold_scale: Optional[bool] = None, no_split: bool = False, hints: int = 0,
-                              order: Optional[Sequence[int]] = None) -> torch.Tensor:
+                              order: Optional[Sequence[int]] = None, multi_v: bool = False) -> torch.Tensor:
     """`ext_attn_runs_views` for a multi-edit batch (tf_ext_attn_run_edits + tf_ext_attn_runs_merge_edits): E = n_edits
     edits, v and out addressed as [source | uncond_1 | cond_1 | ...] (1 + 2E branches), inject_mask the injection state per
     edit.  kv_runs[r] = (k_view, v_view, k_branch0, v_branch0, k_compact): as in `ext_attn_runs_views`, and k_compact says
@@ -572,7 +579,11 @@ def ext_attn_runs_edits_views(q: torch.Tensor, kv_runs: Sequence, out: torch.Ten
     ascending: the layout of `ext_attn_edits_views(qk_compact=True)`) -- a rank's local run reads its own dense k, its remote
     runs the compact k of a receive buffer, all against the same q (q_compact: q is compact too).  Run 0 computes the source
     branch; the others never touch the source slabs of v and out.  For every edit the result equals, bit for bit,
-    `ext_attn_runs_views` on [source | uncond_e | cond_e] with the same runs and that edit's flag.  ONE workspace per set."""
+    `ext_attn_runs_views` on [source | uncond_e | cond_e] with the same runs and that edit's flag.  ONE workspace per set.
+    multi_v (TF_ATTN_RUN_MULTI_V; head dims 40 and 64, fp32 score scaling, a no-op elsewhere): the injecting edits are paired
+    ascending and each pair is ONE four-bank launch per run -- one softmax for both edits.  A paired edit equals the oracle
+    within the attention bound instead of its single-edit run set bit for bit; every other edit and the source keep their
+    bits."""
     dev = _need_gpu(q, out, *[t for kv in kv_runs for t in kv[:2]])
     lib = _lib.load()
     mask = _edit_mask("ext_attn_runs_edits_views", inject_mask, n_edits)
@@ -607,7 +618,7 @@ def ext_attn_runs_edits_views(q: torch.Tensor, kv_runs: Sequence, out: torch.Ten
             raise ValueError("ext_attn_runs_edits_views: k and v of a run need one token stride")
         es = kv.element_size()
         strides = (ctypes.c_int64 * 9)(q_bs, q_fs, k_bs, k_fs, v_bs, v_fs, o_bs, o_fs, ld_q)
-        flags = _run_flags(False, r != 0, out_f32, fold_scale, no_split, hints)
+        flags = _run_flags(False, r != 0, out_f32, fold_scale, no_split, hints) | _run_multi_v_bit(multi_v)
         st = streams[r] if streams is not None else None
         if st is not None:
             if fork is None:
@@ -624,7 +635,8 @@ def ext_attn_runs_edits_views(q: torch.Tensor, kv_runs: Sequence, out: torch.Ten
         ev.record(st)
         cur.wait_event(ev)
     _launch(dev, "tf_ext_attn_runs_merge_edits", lib.tf_ext_attn_runs_merge_edits, op, K, Kq, S, heads, dh, n_runs, E, mask,
-            o_bs, o_fs, _run_flags(False, False, out_f32, fold_scale, no_split, hints), dt, ws.data_ptr(), ws.numel())
+            o_bs, o_fs, _run_flags(False, False, out_f32, fold_scale, no_split, hints) | _run_multi_v_bit(multi_v), dt,
+            ws.data_ptr(), ws.numel())
     return out
 
 
@@ -632,14 +644,17 @@ def ext_attn_runs_edits(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads
                         inject_mask: int, runs: Sequence, q_frame0: int = 0, out: Optional[torch.Tensor] = None,
                         out_dtype: Optional[torch.dtype] = None, streams: Optional[Sequence] = None,
                         fold_scale: Optional[bool] = None, no_split: bool = False, hints: int = 0,
-                        order: Optional[Sequence[int]] = None, k_compact: bool = False) -> torch.Tensor:
+                        order: Optional[Sequence[int]] = None, k_compact: bool = False,
+                        multi_v: bool = False) -> torch.Tensor:
     """`ext_attn_edits(inject_mask=...)` computed run by run over the bank: k, v [B*K,S,D], q [B*Kq,S,D], B = 1 + 2E, runs as
     in `ext_attn_runs`.  Returns [B*Kq,S,D] (fp32 with out_dtype=torch.float32).  For every edit e the slices (source,
     uncond_e, cond_e) equal `ext_attn_runs` on [source | uncond_e | cond_e] with the same runs and that edit's flag, bit for
     bit; the result is a function of the runs alone and equals the oracle within the attention bound -- not
     `ext_attn_edits` bit for bit.  n_edits = 1 is `ext_attn_runs`.
     k_compact: every run but the first reads k from a compact copy -- the source slot (where an edit injects), then
-    (uncond, cond) of every non-injecting edit -- as a rank's remote runs read a receive buffer; the same bits."""
+    (uncond, cond) of every non-injecting edit -- as a rank's remote runs read a receive buffer; the same bits.
+    multi_v: pairs of injecting edits share one four-bank launch per run (`ext_attn_runs_edits_views`); the paired edits are
+    then held to the oracle bound, not to `ext_attn_runs` bit for bit."""
     _need_gpu(q, k, v, out)
     mask = _edit_mask("ext_attn_runs_edits", inject_mask, n_edits)
     E = int(n_edits)
@@ -669,7 +684,7 @@ def ext_attn_runs_edits(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads
         kv_runs[1:] = [(kc[:, f0:f0 + n], v4[:, f0:f0 + n], 0 if mask else 1, 0, True) for f0, n in runs[1:]]
     ext_attn_runs_edits_views(q.view(nbr, Kq, S, D), kv_runs, out.view(nbr, Kq, S, D), heads, scale, E, mask, runs, K,
                               q_frame0=q_frame0, streams=streams, fold_scale=fold_scale, no_split=no_split, hints=hints,
-                              order=order)
+                              order=order, multi_v=multi_v)
     return out
 
 

@@ -39,7 +39,10 @@ side stream ordered against the compute stream with events):
         fp32 sums: this mode equals a single-process `ops.ext_attn_runs` with the same runs bit for bit and the
         oracle within the attention bound -- NOT the bit-stable single-GPU call.  For a multi-edit batch the mode
         needs an opt-in of its own (`edit_runs=True` / TOKENFLOW_SHARD_EDIT_RUNS=1): the gather of the multi-edit "bank"
-        form, the same runs through `ops.ext_attn_runs_edits_views`, the same guarantee per edit.
+        form, the same runs through `ops.ext_attn_runs_edits_views`, the same guarantee per edit.  With
+        `edit_runs_multi_v=True` / TOKENFLOW_SHARD_EDIT_RUNS_MULTI_V=1 on top of it, pairs of injecting edits share one
+        four-bank launch per run (head dims 40 and 64): those edits then equal `ops.ext_attn_runs_edits(multi_v=True)` bit
+        for bit and the oracle within the attention bound.
 
  2. propagation passes -- chunk c needs keyframes c and c-1 (331-333): the first local chunk's
     left neighbour lives on rank r-1, so each rank sends its LAST keyframe's pivot features,
@@ -152,7 +155,8 @@ class FrameShard:
 
     def __init__(self, K: int, group: Optional[dist.ProcessGroup] = None, comm=None,
                  attn_split: Optional[bool] = None, halo_group: Optional[dist.ProcessGroup] = None, halo_comm=None,
-                 bank_runs: Optional[bool] = None, edit_runs: Optional[bool] = None):
+                 bank_runs: Optional[bool] = None, edit_runs: Optional[bool] = None,
+                 edit_runs_multi_v: Optional[bool] = None):
         # bank_runs: opt-in for `auto_mode` (mode=None callers, the hook path): "bank_runs" where it would answer "bank"
         # and S >= BANK_RUNS_MIN_S.  None reads TOKENFLOW_SHARD_BANK_RUNS.  Off: today's answers.
         if bank_runs is None:
@@ -164,6 +168,12 @@ class FrameShard:
         if edit_runs is None:
             edit_runs = os.environ.get("TOKENFLOW_SHARD_EDIT_RUNS", "0") not in ("", "0")
         self.edit_runs = bool(edit_runs)
+        # edit_runs_multi_v: opt-in for the four-bank run launches of the multi-edit "bank_runs" form (ops.ext_attn_runs_edits_views
+        # multi_v= / TF_ATTN_RUN_MULTI_V: pairs of injecting edits share one softmax per run; head dims 40 and 64).  Effective
+        # only with edit_runs.  None reads TOKENFLOW_SHARD_EDIT_RUNS_MULTI_V.  Off: today's launches and bits.
+        if edit_runs_multi_v is None:
+            edit_runs_multi_v = os.environ.get("TOKENFLOW_SHARD_EDIT_RUNS_MULTI_V", "0") not in ("", "0")
+        self.edit_runs_multi_v = bool(edit_runs_multi_v)
         # attn_split: let the attention split a rank's small grid over extra workgroups and merge (faster: -15..40 %
         # on a rank's attention at 8 GPUs; results then agree with the single-GPU ones within the
         # output rounding).  Default False: one pass per bank problem, arithmetic independent of the grid, sharded
@@ -494,8 +504,10 @@ class FrameShard:
         kv_runs = [(k4, v4, 0, 0, False)]
         for f0, n in runs[1:]:
             kv_runs.append((rp[0:nq, f0:f0 + n], rp[nq:, f0:f0 + n], b0, 1, True))
+        # (the keyword only with the opt-in: without it the call is the one it was)
+        mv = dict(multi_v=True) if getattr(self, "edit_runs_multi_v", False) else {}
         ops.ext_attn_runs_edits_views(q4, kv_runs, out, heads, scale, E, mask, runs, self.K, q_frame0=self.kf0,
-                                      no_split=not self.attn_split)
+                                      no_split=not self.attn_split, **mv)
 
     def bank_runs_of_rank(self):
         """The runs of the bank this rank computes in the "bank_runs" form, in SLOT order: its own keyframes, the frames
@@ -827,8 +839,9 @@ class NativeShard(FrameShard):
     supports_edits = False
 
     def __init__(self, K: int, comm, halo_comm=None, attn_split: Optional[bool] = None, bank_runs: Optional[bool] = None,
-                 edit_runs: Optional[bool] = None):
-        super().__init__(K, comm=comm, attn_split=attn_split, halo_comm=halo_comm, bank_runs=bank_runs, edit_runs=edit_runs)
+                 edit_runs: Optional[bool] = None, edit_runs_multi_v: Optional[bool] = None):
+        super().__init__(K, comm=comm, attn_split=attn_split, halo_comm=halo_comm, bank_runs=bank_runs, edit_runs=edit_runs,
+                         edit_runs_multi_v=edit_runs_multi_v)
         from . import _lib
         lib = _lib.load()
         h = ctypes.c_void_p()
@@ -926,13 +939,15 @@ class NativeEditShard(NativeShard):
     `_pivotal_bank_edits`, same buffer layouts, same bits on the same transport.  n_edits = 1 is `NativeShard` itself.
     Modes "heads" and "bank" (`auto_mode` answers "bank" in place of "bank_runs" for E > 1; the explicit "bank_runs" raises as
     on `FrameShard`) -- unless the shard opts in with `edit_runs`: "bank_runs" is then the executor's TF_RANK_BANK_EDIT_RUNS,
-    the native form of `FrameShard._pivotal_bank_runs_edits` with the local run beside the gather.  `ext_alloc`, `halo_block`, `halo_finish`, `propagate_all` are `FrameShard`'s, with n_edits."""
+    the native form of `FrameShard._pivotal_bank_runs_edits` with the local run beside the gather (`edit_runs_multi_v`: with
+    TF_ATTN_RUN_MULTI_V).  `ext_alloc`, `halo_block`, `halo_finish`, `propagate_all` are `FrameShard`'s, with n_edits."""
 
     supports_edits = True
 
     def __init__(self, K: int, comm, halo_comm=None, attn_split: Optional[bool] = None, bank_runs: Optional[bool] = None,
-                 edit_runs: Optional[bool] = None):
-        super().__init__(K, comm, halo_comm=halo_comm, attn_split=attn_split, bank_runs=bank_runs, edit_runs=edit_runs)
+                 edit_runs: Optional[bool] = None, edit_runs_multi_v: Optional[bool] = None):
+        super().__init__(K, comm, halo_comm=halo_comm, attn_split=attn_split, bank_runs=bank_runs, edit_runs=edit_runs,
+                         edit_runs_multi_v=edit_runs_multi_v)
         self._news = {}
 
     @staticmethod
@@ -1012,6 +1027,8 @@ class NativeEditShard(NativeShard):
         flags = 0 if self.attn_split else _lib.TF_ATTN_NO_SPLIT
         if ops.FOLD_SCALE:
             flags |= _lib.TF_ATTN_FOLD_SCALE
+        if runs and self.edit_runs_multi_v:   # the executor hands the bit to the local run, the remote runs and the merge
+            flags |= _lib.TF_ATTN_RUN_MULTI_V
         slot = self._slot
         if not no_halo:
             self._slot = (slot + 1) % _lib.TF_RANK_SLOTS

@@ -9,7 +9,11 @@ spread of arm (b) against itself; the largest absolute difference between the re
 --edits E --inject-mask M: the edits differ in their injection state (bit e of M = edit e injects) -- (a) E single-edit
 `ext_attn` calls, each with its own flag, (b) ONE masked call `ext_attn_edits(..., inject_mask=M)` with the library's
 default rule, (b') the same again (the spread), (c) the masked call as a pure composition (multi_v=False).
---single-lib PATH takes arm (a) from another build of the library (tf_ext_attn_fwd of that .so, e.g. the parent commit's)."""
+--single-lib PATH takes arm (a) from another build of the library (tf_ext_attn_fwd of that .so, e.g. the parent commit's).
+--edits E --inject-mask M --runs W,R [--no-split]: ONE run set of a multi-edit batch as rank R of W frame-sharded ranks issues
+it (`ext_attn_runs_edits`: the rank's own keyframes hold the queries, then the frames left and right of them; remote runs read
+a compact k) -- (a) the DUAL composition, (a') the same again (the spread), (b) multi_v=True, the four-bank run launches for
+pairs of injecting edits.  --no-split: one-pass runs, the shards' default."""
 import ctypes
 import os
 import sys
@@ -120,6 +124,37 @@ def edits_masked_ab(shapes, E, mask, dt, rounds, single_lib):
             print(f"  {name:26s} median {med:.3f} ms  min {mn:.3f} ms  max {mx:.3f} ms", flush=True)
 
 
+def runs_ab(shapes, E, mask, W, R, dt, rounds, no_split):
+    g = torch.Generator(device="cuda").manual_seed(0)
+    B = 1 + 2 * E
+    for K, S, h, d in shapes:
+        D = h * d
+        counts = [K // W + (1 if r < K % W else 0) for r in range(W)]
+        f0, Kl = sum(counts[:R]), counts[R]
+        runs = [(f0, Kl)] + ([(0, f0)] if f0 else []) + ([(f0 + Kl, K - f0 - Kl)] if f0 + Kl < K else [])
+        q, k, v = (torch.randn(B * K, S, D, generator=g, device="cuda").to(dt) for _ in range(3))
+        ql = q.view(B, K, S, D)[:, f0:f0 + Kl].reshape(B * Kl, S, D).contiguous()
+        out = torch.empty_like(ql)
+
+        def run_set(mv):
+            return lambda: ops.ext_attn_runs_edits(ql, k, v, h, d ** -0.5, E, mask, runs, q_frame0=f0, out=out, no_split=no_split,
+                                                   k_compact=True, multi_v=mv)
+        print(f"ext_attn_runs_edits {str(dt)[6:]} K={K} S={S} h={h} d={d} E={E} inject_mask={mask:#b} rank {R} of {W}: runs {runs} "
+              f"no_split={int(no_split)}  ({rounds} alternating rounds)")
+        for mv in (False, True):
+            for r, (_, n) in enumerate(runs):
+                plan = ops.attn_run_edits_plan(K, Kl, n, len(runs), S, h, d, E, mask, dtype=dt, bank_only=r != 0, no_split=no_split,
+                                               multi_v=mv)
+                print(f"  plan multi_v={int(mv)} run {r} ({n} frames): {plan}")
+        res_a, res_b = run_set(False)().float(), run_set(True)().float()
+        print(f"  max |(b) - (a)| = {float((res_b - res_a).abs().max()):.3e}  (max |(a)| = {float(res_a.abs().max()):.3e})")
+        del res_a, res_b
+        arms = {"(a) DUAL composition": run_set(False), "(a') composition again": run_set(False),
+                "(b) four-bank run launches": run_set(True)}
+        for name, (med, mn, mx) in ab(arms, rounds).items():
+            print(f"  {name:26s} median {med:.3f} ms  min {mn:.3f} ms  max {mx:.3f} ms", flush=True)
+
+
 def edits_ab(shapes, E, dt, rounds, single_lib=None):
     g = torch.Generator(device="cuda").manual_seed(0)
     B = 1 + 2 * E
@@ -168,10 +203,20 @@ def main():
         i = sys.argv.index("--single-lib")
         single_lib = sys.argv[i + 1]
         del sys.argv[i:i + 2]
+    runs_of = None
+    if "--runs" in sys.argv:
+        i = sys.argv.index("--runs")
+        runs_of = tuple(int(x) for x in sys.argv[i + 1].split(","))
+        del sys.argv[i:i + 2]
+    no_split = "--no-split" in sys.argv
+    if no_split:
+        sys.argv.remove("--no-split")
     args = [a for a in sys.argv[1:] if a not in ("f16", "bf16")]
     dt = torch.float16 if "f16" in sys.argv[1:] else torch.bfloat16
     if args:
         shapes = [tuple(int(x) for x in a.split(",")) for a in args]
+    if E and runs_of:
+        return runs_ab(shapes, E, (1 << E) - 1 if mask is None else mask, runs_of[0], runs_of[1], dt, rounds, no_split)
     if E and mask is not None:
         return edits_masked_ab(shapes, E, mask, dt, rounds, single_lib)
     if E:
