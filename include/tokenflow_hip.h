@@ -450,7 +450,7 @@ TF_API int tf_head_unpack(const void* recv, void* const* dsts, const int64_t* fr
  *   tokenflow_utils.py:335) and every selected keyframe p < P (kf[p] indexes the
  *   K keyframes; the reference order is [i, i-1], lines 331-333):
  *       idx[p, t] = argmax_j  <tgt[t], piv[kf[p], j]> * inv_norm[kf[p]*S + j]
- *   first maximal j wins (torch.argmax).  The 1/||tgt[t]|| factor of util.py:66
+ *   first maximal j wins (torch.argmax).  n_tgt < 2^31 (per chunk in the chunk forms).  The 1/||tgt[t]|| factor of util.py:66
  *   is a positive per-row constant and cannot change the argmax, so targets are
  *   never normalised.  idx is int32 [P, n_tgt].  D multiple of 8; dtype bf16/f16.
  *   tgt, piv, ws AND inv_norm 16-byte aligned (TF_ERR_ALIGN otherwise; the same holds for the tf_nn_gather_blend*
@@ -585,6 +585,75 @@ TF_API int tf_nn_gather_blend_chunks_norm_edits(const void* tgt, const void* piv
                                          int norm_dtype, void* ws, size_t ws_bytes, void* stream);
 
 TF_API int tf_nn_gather_blend_edits_plan(int n, int C, int S, int D, int first_single, int n_edits, char* buf, size_t len);
+
+/* ------------------------------------------------------------------------
+ * Keyframe SEGMENTS (additive to ABI 11): several scenes or clips in one pass.  A pass carries n_seg segments,
+ * 1 <= n_seg <= TF_MAX_SEGMENTS; segment v owns seg_K[v] >= 1 CONSECUTIVE keyframes of the bank (sum = K) and the chunks that
+ * belong to them.  The batch layout is the usual [source | uncond | cond] x frames; a segment is a frame window of it.  For
+ * every op the slices of segment v are what the single-clip op computes on segment v's tensors alone: nothing crosses a cut.
+ *
+ * tf_ext_attn_fwd_segments: q, k, v dense [3, K, S, ld], out dense [3, K, S, H*Dh] (float with TF_ATTN_OUT_F32); seg_K a HOST
+ *   array of n_seg ints.  A bank branch of keyframe f attends to the seg_K[v] * S keys of its own segment, the source branch
+ *   to its own S keys.
+ *   flags: TF_ATTN_INJECT, TF_ATTN_OUT_F32, TF_ATTN_NO_SPLIT, TF_ATTN_NO_FUSED / TF_ATTN_FUSED, TF_ATTN_FOLD_SCALE and the hints
+ *     as tf_ext_attn_fwd, applied to every segment.  TF_ATTN_BANK_ONLY, TF_ATTN_SOURCE_ONLY and the multi-edit hints
+ *     (TF_ATTN_MULTI_V, TF_ATTN_NO_MULTI_V, TF_ATTN_MULTI_V64, TF_ATTN_RUN_MULTI_V): TF_ERR_SHAPE -- frame-sharded and
+ *     multi-edit passes have no segment form.  n_seg outside 1 .. TF_MAX_SEGMENTS, a segment without keyframes, a sum other
+ *     than K: TF_ERR_SHAPE.  Every refusal comes before anything touches the device.
+ *   n_seg = 1 IS tf_ext_attn_fwd(K, Kq = K): same launches, same bits.
+ *   Composition for n_seg > 1.  Every segment is asked what its OWN call -- tf_ext_attn_fwd_strided on its frame window,
+ *   (K, Kq) = (seg_K[v], seg_K[v]) -- would take.
+ *     - The segments whose own call takes the fused small-problem kernel share ONE fused launch, a tensor set per segment
+ *       (branches 0..2, base pointers at the segment's first frame, Kq = Kb = seg_K[v], q_frame0 = 0); plan token
+ *       fused[..,sets=N], N such segments (N = 1 and 2 included).  The launch is planned on the JOINT grid: under
+ *       TF_ATTN_NO_SPLIT the plan is a function of the shape alone and the launch equals the segments' own calls bit for bit;
+ *       in the default mode it may choose another KW than a segment alone would (results within the attention bound), or
+ *       leave the fused range as a one-shot call of that size would -- those segments then stream with the others.
+ *     - The other segments stream: ONE V^T pre-pass over the whole bank (all three branches of all K frames; key norms as
+ *       the single-clip call leaves them), then, in segment order, the launches the segment's own call issues behind its
+ *       pre-pass, with the frame window folded into the base pointers and the image's row stride as the run calls fold
+ *       theirs.  Same kernels, same values: BIT-IDENTICAL to the segment's own call, in the default mode and under
+ *       TF_ATTN_NO_SPLIT alike.  The fused launch, where there is one, follows the streaming launches.
+ *   ws: tf_ext_attn_segments_workspace_bytes(K, ...) -- the image and norm table of the whole bank and the split form's
+ *     partial results once (the segments run one behind the other on the stream); it does not depend on the segmentation
+ *     and is never smaller than tf_ext_attn_workspace_bytes(K, ...).
+ * tf_ext_attn_segments_plan: the launches of the call (host only), the tokens of tf_ext_attn_plan.
+ *
+ * tf_nn_gather_blend_chunks_segments / tf_nn_gather_blend_chunks_norm_segments: the arguments of tf_nn_gather_blend_chunks
+ *   [_norm] with first_single replaced by single_mask: bit j set = chunk j of the call is the first chunk of a segment, a
+ *   ONE-keyframe chunk that matches slot0 + j alone (tokenflow_utils.py:331-333, 390) and whose rows are rounded to
+ *   single_dtype as chunk 0's are; every other chunk j matches slots slot0 + j and slot0 + j - 1.  w depends on n only: one
+ *   w[n] serves every chunk.  1 <= C <= 64; slot0 >= 1 unless bit 0 is set; a bit at or above C: TF_ERR_SHAPE.
+ *   ONE search -- the launches of tf_nn_search_plan(n*S, S, D, 2, C), no finalize; the p = 1 half of a one-keyframe chunk is
+ *   neither computed nor read -- and ONE gather.  Bit-identical to the per-segment calls (tf_nn_gather_blend_chunks with
+ *   first_single on each segment's chunks) wherever the C-chunk search and theirs take the same kernel form; mask 1 and mask 0
+ *   ARE tf_nn_gather_blend_chunks with and without first_single.  Workspace: tf_nn_gather_blend_chunks_workspace_bytes.
+ * tf_nn_gather_blend_segments_plan: the launches of the call (host only): the search tokens followed by gather[branches=3].
+ * ------------------------------------------------------------------------ */
+#define TF_MAX_SEGMENTS 8
+
+TF_API size_t tf_ext_attn_segments_workspace_bytes(int K, int S, int H, int Dh, int dtype);
+
+TF_API int tf_ext_attn_fwd_segments(const void* q, const void* k, const void* v, void* out, int K, int n_seg, const int* seg_K,
+                             int S, int H, int Dh, int64_t ld, float scale, int flags, int dtype, void* ws, size_t ws_bytes,
+                             void* stream);
+
+TF_API int tf_ext_attn_segments_plan(int K, int n_seg, const int* seg_K, int S, int H, int Dh, int flags, int dtype, char* buf,
+                              size_t len);
+
+TF_API int tf_nn_gather_blend_chunks_segments(const void* tgt, const void* piv, const float* inv_norm, const void* kf_out,
+                                       const float* w, const void* resid, void* out, int K, int n, int C, int S, int D,
+                                       int slot0, uint64_t single_mask, int search_dtype, int in_dtype, int res_dtype,
+                                       int out_dtype, int single_dtype, void* ws, size_t ws_bytes, void* stream);
+
+TF_API int tf_nn_gather_blend_chunks_norm_segments(const void* tgt, const void* piv, const float* inv_norm,
+                                            const void* kf_out, const float* w, const void* resid, void* out, int K, int n,
+                                            int C, int S, int D, int slot0, uint64_t single_mask, int search_dtype,
+                                            int in_dtype, int res_dtype, int out_dtype, int single_dtype, const void* gamma,
+                                            const void* beta, float eps, int w_dtype, void* norm_out, int norm_dtype, void* ws,
+                                            size_t ws_bytes, void* stream);
+
+TF_API int tf_nn_gather_blend_segments_plan(int n, int C, int S, int D, uint64_t single_mask, char* buf, size_t len);
 
 /* ------------------------------------------------------------------------
  * Row LayerNorm producer  --  the `norm1` call of TokenFlowBlock.forward

@@ -33,6 +33,10 @@ struct TfFusedPlan {
     int prec;   // P carried as hi + lo bf16 (two P.V MFMAs): removes the rounding of P from the result
 };
 
+// Plan recording only (host, per thread): while non-zero a fused launch records ",sets=N" in its plan token whatever N -- the
+// joint launch of a segmented pass (tf_ext_attn_fwd_segments) names its sets even when there are two.
+extern thread_local int tf_plan_sets_note;
+
 // Shape- and grid-based decision; `flags` = the `inject` bit mask of tf_ext_attn_fwd (hints included).
 TfFusedPlan tf_attn_fused_plan(const TfAttnSet* sets, int n_sets, int S, int Dh, int dtype, int flags);
 

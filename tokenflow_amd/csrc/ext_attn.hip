@@ -2623,9 +2623,7 @@ int dispatch_dh(int Dh, const AttnParams& p, const void* v, hipStream_t st) {
 
 // Workspace of a call over `branches` branches: V^T image | key norm bounds | split-form partial results (of one edit: the
 // edits of a multi-edit batch run one behind the other on the stream and reuse them)
-static size_t attn_ws_bytes(int K, int S, int H, int Dh, int dtype, int branches) {
-    if (K <= 0 || S <= 0 || H <= 0 || Dh <= 0 || dtype == TF_F32) return 0;
-    const size_t Spad = (size_t)((S + 127) / 128) * 128;   // frames padded to the largest staged tile
+static size_t attn_part_elems(int K, int S, int H, int Dh) {
     size_t part_elems = 0;   // split form: worst case over the number of query frames a caller may pass
     for (int Kq = 1; Kq <= K; ++Kq)
         for (int inj = 0; inj < 2; ++inj) {
@@ -2633,9 +2631,30 @@ static size_t attn_ws_bytes(int K, int S, int H, int Dh, int dtype, int branches
             const size_t e = ns > 1 ? (size_t)2 * Kq * H * S * ns * (Dh + 8) : 0;
             part_elems = e > part_elems ? e : part_elems;
         }
+    return part_elems;
+}
+
+static size_t attn_ws_bytes(int K, int S, int H, int Dh, int dtype, int branches) {
+    if (K <= 0 || S <= 0 || H <= 0 || Dh <= 0 || dtype == TF_F32) return 0;
+    const size_t Spad = (size_t)((S + 127) / 128) * 128;   // frames padded to the largest staged tile
     return ((vt_bytes(K, (int)Spad, H, Dh, branches) + 255) & ~(size_t)255) +
            (((size_t)branches * H * K * (Spad / 64) * sizeof(float) + 255) & ~(size_t)255) +
-           part_elems * sizeof(float);   // V^T image | key norm bounds | split-form partial results
+           attn_part_elems(K, S, H, Dh) * sizeof(float);   // V^T image | key norm bounds | split-form partial results
+}
+
+// Workspace of a pass of keyframe segments (tf_ext_attn_fwd_segments): the image and the norm table of the whole bank of K
+// frames; the split-form partial results of the largest segment's own call (the segments run one behind the other on the stream
+// and reuse them), whatever the segmentation: the worst case over every bank size up to K
+static size_t attn_seg_ws_bytes(int K, int S, int H, int Dh, int dtype) {
+    if (K <= 0 || S <= 0 || H <= 0 || Dh <= 0 || dtype == TF_F32) return 0;
+    const size_t Spad = (size_t)((S + 127) / 128) * 128;
+    size_t part_elems = 0;
+    for (int Kv = 1; Kv <= K; ++Kv) {
+        const size_t e = attn_part_elems(Kv, S, H, Dh);
+        part_elems = e > part_elems ? e : part_elems;
+    }
+    return ((vt_bytes(K, (int)Spad, H, Dh, 3) + 255) & ~(size_t)255) +
+           (((size_t)3 * H * K * (Spad / 64) * sizeof(float) + 255) & ~(size_t)255) + part_elems * sizeof(float);
 }
 
 extern "C" size_t tf_ext_attn_workspace_bytes(int K, int S, int H, int Dh, int dtype) {
@@ -2678,9 +2697,19 @@ private:
     }
 };
 
+// One keyframe segment of a pass (tf_ext_attn_fwd_segments) as seen by the single-clip call that computes it: the caller has
+// moved the base pointers of q / k / v / out to the segment's first frame and packed the V^T image of the WHOLE bank of
+// `K_all` frames; K = Kq = the segment's frames, and the launches read the image and the norm table from frame `f0` on with
+// the whole bank's row strides (p.Kb), the way a run call folds its frame window.
+struct SegPart {
+    int K_all;
+    int f0;
+    int probe;   // do not launch: return 1 if the segment's own call takes the fused small-problem kernel, else 0
+};
+
 int attn_fwd_core(const void* q, const void* k, const void* v, void* out, int K, int Kq, int q_frame0, int S, int H, int Dh,
                   int64_t ld, const int64_t* strides, float scale, int inject, int dtype, void* ws, size_t ws_bytes,
-                  void* stream, const EditsPart* ed) {
+                  void* stream, const EditsPart* ed, const SegPart* sg = nullptr) {
     TF_ARG(q && k && v && out && ws && strides, TF_ERR_NULL, "tf_ext_attn_fwd: null pointer");
     TF_ARG(dtype == TF_BF16 || dtype == TF_F16, TF_ERR_DTYPE, "tf_ext_attn_fwd: dtype %d (bf16/f16 only)", dtype);
     TF_ARG(Dh == 40 || Dh == 64 || Dh == 80 || Dh == 160, TF_ERR_SHAPE,
@@ -2700,8 +2729,8 @@ int attn_fwd_core(const void* q, const void* k, const void* v, void* out, int K,
     TF_ARG(tf_aligned16(q) && tf_aligned16(k) && tf_aligned16(v) && tf_aligned16(out) && tf_aligned16(ws),
            TF_ERR_ALIGN, "tf_ext_attn_fwd: tensors not 16-byte aligned");
     const int branches = ed ? ed->branches : 3;
-    TF_ARG(ws_bytes >= attn_ws_bytes(K, S, H, Dh, dtype, branches), TF_ERR_WORKSPACE,
-           "tf_ext_attn_fwd: workspace %zu < %zu bytes", ws_bytes, attn_ws_bytes(K, S, H, Dh, dtype, branches));
+    const size_t ws_need = sg ? attn_seg_ws_bytes(sg->K_all, S, H, Dh, dtype) : attn_ws_bytes(K, S, H, Dh, dtype, branches);
+    TF_ARG(ws_bytes >= ws_need, TF_ERR_WORKSPACE, "tf_ext_attn_fwd: workspace %zu < %zu bytes", ws_bytes, ws_need);
     const int part_bits = inject & (TF_ATTN_BANK_ONLY | TF_ATTN_SOURCE_ONLY);
     TF_ARG(part_bits != (TF_ATTN_BANK_ONLY | TF_ATTN_SOURCE_ONLY), TF_ERR_SHAPE,
            "tf_ext_attn_fwd: TF_ATTN_BANK_ONLY and TF_ATTN_SOURCE_ONLY exclude each other");
@@ -2715,14 +2744,15 @@ int attn_fwd_core(const void* q, const void* k, const void* v, void* out, int K,
         a.b0 = part_bits == TF_ATTN_BANK_ONLY ? 1 : 0;
         a.nb = part_bits == TF_ATTN_BANK_ONLY ? 2 : part_bits == TF_ATTN_SOURCE_ONLY ? 1 : 3;
         const TfFusedPlan plan = tf_attn_fused_plan(&a, 1, S, Dh, dtype, inject);
-        if (ed && ed->probe) return plan.use ? 1 : 0;
+        if ((ed && ed->probe) || (sg && sg->probe)) return plan.use ? 1 : 0;
         if (plan.use)
             return tf_attn_fused_launch(&a, 1, S, Dh, scale, inject, dtype, plan, reinterpret_cast<hipStream_t>(stream));
     }
     const int Spad = ((S + 127) / 128) * 128;
     const int shift = ed ? ed->shift : 0;
-    const size_t vt_all = (vt_bytes(K, Spad, H, Dh, branches) + 255) & ~(size_t)255;
-    const size_t kn_all = ((size_t)branches * H * K * (Spad / 64) * sizeof(float) + 255) & ~(size_t)255;
+    const int Kb = sg ? sg->K_all : K;   // frames of the image and of the norm table
+    const size_t vt_all = (vt_bytes(Kb, Spad, H, Dh, branches) + 255) & ~(size_t)255;
+    const size_t kn_all = ((size_t)branches * H * Kb * (Spad / 64) * sizeof(float) + 255) & ~(size_t)255;
     unsigned char* const w8 = static_cast<unsigned char*>(ws);
     AttnParams p{};
     p.q = q;
@@ -2743,7 +2773,11 @@ int attn_fwd_core(const void* q, const void* k, const void* v, void* out, int K,
     p.fold = (inject & TF_ATTN_FOLD_SCALE) ? 1 : 0;
     p.out_f32 = (inject & TF_ATTN_OUT_F32) ? 1 : 0;
     p.nseg = split_plan(K, Kq, S, H, Dh, p.inject != 0, p.part, !(inject & TF_ATTN_NO_SPLIT));
-    p.Kb = K;
+    p.Kb = Kb;
+    if (sg) {   // a keyframe segment: its window of the whole bank's image and norm table
+        p.vt = w8 + (size_t)sg->f0 * Spad * 2;
+        p.knorm2 = reinterpret_cast<const float*>(w8 + vt_all) + (size_t)sg->f0 * (Spad / 64);
+    }
     p.pslots = p.nseg > 1 ? p.nseg : 0;
     p.bit_stable = (inject & TF_ATTN_NO_SPLIT) ? 1 : 0;
     p.mix = (inject & TF_ATTN_HINT_MIX) ? 1 : 0;
@@ -2761,6 +2795,7 @@ int attn_fwd_core(const void* q, const void* k, const void* v, void* out, int K,
     p.c = (float)((double)scale * 1.4426950408889634);
     p.gap = 2;
     if (ed) p.no_pack = ed->no_pack, p.mv4 = ed->mv4, p.force_dual = ed->force_dual, p.gap = ed->gap;
+    if (sg) p.no_pack = 1;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     return dtype == TF_BF16 ? dispatch_dh<BF16>(Dh, p, v, st) : dispatch_dh<F16>(Dh, p, v, st);
 }
@@ -3448,4 +3483,118 @@ extern "C" int tf_ext_attn_fwd(const void* q, const void* k, const void* v, void
     const int64_t strides[9] = {Kq * fs, fs, K * fs, fs, K * fs, fs, Kq * ofs, ofs, ld};
     return tf_ext_attn_fwd_strided(q, k, v, out, K, Kq, q_frame0, S, H, Dh, ld, strides, scale, inject, dtype, ws,
                                    ws_bytes, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Keyframe segments (include/tokenflow_hip.h): a pass of V scenes or clips, segment v = K_v consecutive keyframes of the bank.
+// Every segment is the single-clip call on its own frame window; the composition shares the launches that can be shared -- ONE
+// fused multi-set launch for the segments whose own call is fused, ONE V^T pre-pass for the ones that stream.
+extern "C" size_t tf_ext_attn_segments_workspace_bytes(int K, int S, int H, int Dh, int dtype) {
+    return attn_seg_ws_bytes(K, S, H, Dh, dtype);
+}
+
+extern "C" int tf_ext_attn_fwd_segments(const void* q, const void* k, const void* v, void* out, int K, int n_seg,
+                                        const int* seg_K, int S, int H, int Dh, int64_t ld, float scale, int flags, int dtype,
+                                        void* ws, size_t ws_bytes, void* stream) {
+    const char* const name = "tf_ext_attn_fwd_segments";
+    TF_ARG(seg_K, TF_ERR_NULL, "%s: null seg_K", name);
+    TF_ARG(n_seg >= 1 && n_seg <= TF_MAX_SEGMENTS, TF_ERR_SHAPE, "%s: n_seg=%d (1 .. %d)", name, n_seg, TF_MAX_SEGMENTS);
+    int sum = 0;
+    for (int i = 0; i < n_seg; ++i) {
+        TF_ARG(seg_K[i] >= 1 && seg_K[i] <= K, TF_ERR_SHAPE, "%s: segment %d has %d keyframes (1 .. K = %d)", name, i, seg_K[i], K);
+        sum += seg_K[i];
+    }
+    TF_ARG(sum == K, TF_ERR_SHAPE, "%s: the segments hold %d keyframes, the pass %d", name, sum, K);
+    constexpr int REFUSED = TF_ATTN_BANK_ONLY | TF_ATTN_SOURCE_ONLY | TF_ATTN_MULTI_V | TF_ATTN_NO_MULTI_V | TF_ATTN_MULTI_V64 |
+                            TF_ATTN_RUN_MULTI_V;
+    TF_ARG(!(flags & REFUSED), TF_ERR_SHAPE,
+           "%s: flags 0x%x -- TF_ATTN_BANK_ONLY / TF_ATTN_SOURCE_ONLY and the multi-edit hints have no segment form", name,
+           flags & REFUSED);
+    if (n_seg == 1)   // one shot: today's call
+        return tf_ext_attn_fwd(q, k, v, out, K, K, 0, S, H, Dh, ld, scale, flags, dtype, ws, ws_bytes, stream);
+    TF_ARG(q && k && v && out && ws, TF_ERR_NULL, "%s: null pointer", name);
+    TF_ARG(dtype == TF_BF16 || dtype == TF_F16, TF_ERR_DTYPE, "%s: dtype %d (bf16/f16 only)", name, dtype);
+    TF_ARG(S > 0 && H > 0 && (Dh == 40 || Dh == 64 || Dh == 80 || Dh == 160) && ld >= (int64_t)H * Dh && ld % 8 == 0, TF_ERR_SHAPE,
+           "%s: S=%d H=%d Dh=%d ld=%lld", name, S, H, Dh, (long long)ld);
+    TF_ARG(ws_bytes >= attn_seg_ws_bytes(K, S, H, Dh, dtype), TF_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", name, ws_bytes,
+           attn_seg_ws_bytes(K, S, H, Dh, dtype));
+    // dense [3, K, S, ld] tensors, out [3, K, S, H*Dh]: a segment keeps the pass's branch strides
+    const int64_t fs = (int64_t)S * ld, ofs = (int64_t)S * H * Dh;
+    const int64_t strides[9] = {K * fs, fs, K * fs, fs, K * fs, fs, K * ofs, ofs, ld};
+    const int64_t osz = (flags & TF_ATTN_OUT_F32) ? 4 : 2;
+    auto at = [](const void* ptr, int64_t elems, int64_t esz) {
+        return static_cast<const void*>(static_cast<const unsigned char*>(ptr) + elems * esz);
+    };
+    int f0[TF_MAX_SEGMENTS], fused[TF_MAX_SEGMENTS], n_fused = 0;
+    auto call = [&](int i, int fl, int probe) {   // segment i's own call on its frame window
+        const SegPart sg{K, f0[i], probe};
+        return attn_fwd_core(at(q, f0[i] * fs, 2), at(k, f0[i] * fs, 2), at(v, f0[i] * fs, 2),
+                             const_cast<void*>(at(out, f0[i] * ofs, osz)), seg_K[i], seg_K[i], 0, S, H, Dh, ld, strides, scale, fl,
+                             dtype, ws, ws_bytes, stream, nullptr, &sg);
+    };
+    for (int i = 0, f = 0; i < n_seg; f += seg_K[i++]) {
+        f0[i] = f;
+        fused[i] = call(i, flags, 1);   // the decision of the segment's own call
+        if (fused[i] < 0) return fused[i];
+        n_fused += fused[i];
+    }
+    bool joint = false;
+    TfAttnSet sets[TF_MAX_SEGMENTS] = {};
+    TfFusedPlan plan{};
+    if (n_fused) {   // ONE launch, a tensor set per fused segment -- where the plan of the joint grid stays in the fused range
+        int n = 0;
+        for (int i = 0; i < n_seg; ++i) {
+            if (!fused[i]) continue;
+            TfAttnSet& a = sets[n++];
+            a.q = at(q, f0[i] * fs, 2), a.k = at(k, f0[i] * fs, 2), a.v = at(v, f0[i] * fs, 2);
+            a.out = const_cast<void*>(at(out, f0[i] * ofs, osz));
+            a.q_bs = strides[0], a.q_fs = strides[1], a.ld_q = ld;
+            a.k_bs = strides[2], a.k_fs = strides[3], a.v_bs = strides[4], a.v_fs = strides[5], a.ld = ld;
+            a.o_bs = strides[6], a.o_fs = strides[7];
+            a.H = H, a.Kq = a.Kb = seg_K[i], a.q_frame0 = 0, a.b0 = 0, a.nb = 3;
+        }
+        plan = tf_attn_fused_plan(sets, n_fused, S, Dh, dtype, flags);
+        joint = plan.use != 0;
+    }
+    // where the joint grid leaves the fused range (the default mode decides per grid, as a one-shot call of that size would),
+    // those segments stream beside the others
+    const int stream_flags = flags | (n_fused && !joint ? TF_ATTN_NO_FUSED : 0);
+    if (!joint || n_fused < n_seg) {
+        // ONE pre-pass over the whole bank: every branch, the key norms as the single-clip call leaves them
+        const int Spad = ((S + 127) / 128) * 128;
+        const bool inj = (flags & TF_ATTN_INJECT) != 0;
+        AttnParams p{};
+        p.k = k, p.vt = ws;
+        p.knorm2 = reinterpret_cast<const float*>(static_cast<unsigned char*>(ws) + ((vt_bytes(K, Spad, H, Dh, 3) + 255) & ~(size_t)255));
+        p.K = p.Kb = K, p.S = S, p.H = H, p.Spad = Spad, p.nseg = 1;
+        p.ld = ld, p.k_bs = strides[2], p.k_fs = strides[3], p.v_bs = strides[4], p.v_fs = strides[5];
+        hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+        const int rc = dtype == TF_BF16 ? launch_vt_pack<BF16>(p, v, Dh, 0, 3, inj ? 0u : ~0u, inj ? 0 : -1, st)
+                                        : launch_vt_pack<F16>(p, v, Dh, 0, 3, inj ? 0u : ~0u, inj ? 0 : -1, st);
+        if (rc) return rc;
+        for (int i = 0; i < n_seg; ++i)
+            if (!joint || !fused[i])
+                if (const int rc2 = call(i, stream_flags, 0)) return rc2;
+    }
+    if (!joint) return 0;
+    tf_plan_sets_note = 1;   // the plan token of this launch names its sets whatever their number
+    const int rc = tf_attn_fused_launch(sets, n_fused, S, Dh, scale, flags, dtype, plan, reinterpret_cast<hipStream_t>(stream));
+    tf_plan_sets_note = 0;
+    return rc;
+}
+
+// Launch plan of tf_ext_attn_fwd_segments (host only): the entry point itself under the plan recorder.
+extern "C" int tf_ext_attn_segments_plan(int K, int n_seg, const int* seg_K, int S, int H, int Dh, int flags, int dtype,
+                                         char* buf, size_t len) {
+    TF_ARG(K > 0 && S > 0 && H > 0, TF_ERR_SHAPE, "tf_ext_attn_segments_plan: K=%d S=%d H=%d", K, S, H);
+    void* const ph = reinterpret_cast<void*>((uintptr_t)1 << 12);
+    TfPlanRec rec{buf, len, 0, 0};
+    if (buf && len) buf[0] = 0;
+    tf_plan_rec = &rec;
+    const int rc = tf_ext_attn_fwd_segments(ph, ph, ph, ph, K, n_seg, seg_K, S, H, Dh, (int64_t)H * Dh, 1.0f, flags, dtype, ph,
+                                            (size_t)-1, nullptr);
+    tf_plan_rec = nullptr;
+    if (rc) return rc;
+    TF_ARG(rec.used < len, TF_ERR_WORKSPACE, "tf_ext_attn_segments_plan: the plan needs %zu bytes", rec.used + 1);
+    return rec.n;
 }

@@ -27,6 +27,8 @@
 
 #include "attn_fused.h"
 
+thread_local int tf_plan_sets_note = 0;
+
 namespace {
 
 typedef __bf16 bf16x4_vs __attribute__((__vector_size__(8)));
@@ -621,10 +623,11 @@ __global__ __launch_bounds__(64 * KW, 1) void ext_attn_fused_wp_kernel(P p) {
     }
 }
 
-// plan token of a launch: today's for one or two sets, ",sets=N" appended beyond
+// plan token of a launch: today's for one or two sets, ",sets=N" appended beyond (and for the sets of a segmented pass,
+// tf_plan_sets_note, whatever their number)
 template <typename P>
 bool fused_note(const P& p, int qw, int kw, int qb, int prec) {
-    if (p.n_sets > 2) return tf_plan_note("fused[qw=%d,kw=%d,qb=%d,prec=%d,sets=%d]", qw, kw, qb, prec, p.n_sets);
+    if (p.n_sets > 2 || tf_plan_sets_note) return tf_plan_note("fused[qw=%d,kw=%d,qb=%d,prec=%d,sets=%d]", qw, kw, qb, prec, p.n_sets);
     return tf_plan_note("fused[qw=%d,kw=%d,qb=%d,prec=%d]", qw, kw, qb, prec);
 }
 

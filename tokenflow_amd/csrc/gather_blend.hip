@@ -108,9 +108,10 @@ struct NoRes {};
 // before they are widened to the call's output type -- so the call reproduces C separate calls bit for bit.
 struct GbChunks {
     int nc;             // frames per chunk (0: not a multi-chunk call)
-    int first_single;
     int single_dtype;   // TF_BF16 / TF_F16 / TF_F32
+    uint64_t single_mask;   // bit j: chunk j of the call has one keyframe (chunks at or above 64: never)
 };
+__device__ __forceinline__ bool gb_chunk_single(const GbChunks& ch, int j) { return j < 64 && ((ch.single_mask >> j) & 1); }
 
 // MERGE: the indices come as the search's per-split partial results (tf_nn_gather_blend: no finalize launch
 // in between); every thread of a token merges them itself -- `splits` 8-byte reads, broadcast from cache.
@@ -146,7 +147,7 @@ __global__ __launch_bounds__(256) void gather_blend_kernel(const TIn* __restrict
             const int j = frame / ch.nc;
             frame -= j * ch.nc;
             coff = j * frame_in;
-            single = ch.first_single && j == 0;
+            single = gb_chunk_single(ch, j);
         }
         if constexpr (P == 2) {
             if (!single) i2 = MERGE ? nn_merge_partials(part + nS + t, P * nS, splits) : idx[nS + t];
@@ -233,7 +234,7 @@ __global__ __launch_bounds__(256) void gather_blend_norm_kernel(
             const int j = frame / ch.nc;
             frame -= j * ch.nc;
             coff = j * frame_in;
-            single = ch.first_single && j == 0;
+            single = gb_chunk_single(ch, j);
         }
         if constexpr (P == 2) {
             if (!single) i2 = nn_merge_partials(part + nS + t, P * nS, splits);
@@ -515,9 +516,10 @@ extern "C" size_t tf_nn_gather_blend_chunks_workspace_bytes(int64_t n_tgt_chunk,
 
 static int nn_gather_blend_chunks_impl(const char* name, const void* tgt, const void* piv, const float* inv_norm,
                                        const void* kf_out, const float* w, const void* resid, void* out, int K, int n,
-                                       int C, int S, int D, int slot0, int first_single, int search_dtype, int in_dtype,
-                                       int res_dtype, int out_dtype, int single_dtype, void* ws, size_t ws_bytes,
-                                       void* stream, const NormArgs& nm, int n_edits = 0) {
+                                       int C, int S, int D, int slot0, uint64_t single_mask, int search_dtype,
+                                       int in_dtype, int res_dtype, int out_dtype, int single_dtype, void* ws,
+                                       size_t ws_bytes, void* stream, const NormArgs& nm, int n_edits = 0,
+                                       bool segments = false) {   // segments: the mask of the *_segments entry points
     TF_ARG(tgt && piv && inv_norm && kf_out && out && ws && w, TF_ERR_NULL, "%s: null pointer", name);
     TF_ARG(search_dtype == TF_BF16 || search_dtype == TF_F16, TF_ERR_DTYPE, "%s: search dtype %d (bf16/f16 only)", name,
            search_dtype);
@@ -525,10 +527,14 @@ static int nn_gather_blend_chunks_impl(const char* name, const void* tgt, const 
     TF_ARG(okdt(in_dtype) && okdt(out_dtype) && okdt(single_dtype) && (!resid || okdt(res_dtype)), TF_ERR_DTYPE,
            "%s: dtypes in=%d res=%d out=%d single=%d", name, in_dtype, res_dtype, out_dtype, single_dtype);
     // chunk j reads keyframe slots slot0 + j and slot0 + j - 1 (the one-keyframe chunk only slot0)
+    const bool first_single = single_mask & 1;
     TF_ARG(K > 0 && n > 0 && C > 0 && S > 0 && D > 0 && D % 8 == 0 && slot0 + C <= K &&
-               slot0 >= (first_single ? 0 : 1) && (C > 1 || !first_single),
+               slot0 >= (first_single ? 0 : 1) && (segments || C > 1 || !first_single),
            TF_ERR_SHAPE, "%s: K=%d n=%d C=%d S=%d D=%d slot0=%d first_single=%d", name, K, n, C, S, D, slot0,
-           first_single);
+           (int)first_single);
+    // a chunk that starts a keyframe segment matches slot0 + j alone: one bit per chunk of the call
+    TF_ARG(!segments || (C <= 64 && (C == 64 || !(single_mask >> C))), TF_ERR_SHAPE,
+           "%s: C=%d single_mask=0x%llx (C <= 64, no bit at or above C)", name, C, (unsigned long long)single_mask);
     TF_ARG(tf_aligned16(tgt) && tf_aligned16(piv) && tf_aligned16(kf_out) && tf_aligned16(out) &&
                tf_aligned16(resid) && tf_aligned16(ws) && tf_aligned16(inv_norm),
            TF_ERR_ALIGN, "%s: tensors not 16-byte aligned (inv_norm included)", name);
@@ -547,10 +553,10 @@ static int nn_gather_blend_chunks_impl(const char* name, const void* tgt, const 
     NnPartial* part = reinterpret_cast<NnPartial*>(ws);
     int splits = 1;
     const int rc = tf_nn_search_partials(tgt, piv, inv_norm, part, n_tgt, S, D, 2, slot0, slot0 - 1, search_dtype, st,
-                                         &splits, C, first_single ? 1 : 0);
+                                         &splits, C, single_mask);
     if (rc) return rc;
     GbArgs a{kf_out, nullptr, part, splits, w, resid, out, K, n * C, S, D, 2, slot0, slot0 - 1, st,
-             GbChunks{n, first_single ? 1 : 0, single_dtype}};
+             GbChunks{n, single_dtype, single_mask}};
     if (n_edits > 0) a.nb = 1 + 2 * n_edits, a.dyn = true;
     if (nm.out) {
         a.norm_out = nm.out, a.gamma = nm.gamma, a.beta = nm.beta, a.w_dtype = nm.w_dtype, a.eps = nm.eps;
@@ -574,8 +580,8 @@ extern "C" int tf_nn_gather_blend_chunks(const void* tgt, const void* piv, const
                                          int res_dtype, int out_dtype, int single_dtype, void* ws, size_t ws_bytes,
                                          void* stream) {
     return nn_gather_blend_chunks_impl("tf_nn_gather_blend_chunks", tgt, piv, inv_norm, kf_out, w, resid, out, K, n, C, S,
-                                       D, slot0, first_single, search_dtype, in_dtype, res_dtype, out_dtype, single_dtype,
-                                       ws, ws_bytes, stream, NormArgs{});
+                                       D, slot0, first_single ? 1 : 0, search_dtype, in_dtype, res_dtype, out_dtype,
+                                       single_dtype, ws, ws_bytes, stream, NormArgs{});
 }
 
 extern "C" int tf_nn_gather_blend_chunks_norm(const void* tgt, const void* piv, const float* inv_norm,
@@ -588,8 +594,53 @@ extern "C" int tf_nn_gather_blend_chunks_norm(const void* tgt, const void* piv, 
     NormArgs nm;
     nm.out = norm_out, nm.gamma = gamma, nm.beta = beta, nm.eps = eps, nm.w_dtype = w_dtype, nm.dtype = norm_dtype;
     return nn_gather_blend_chunks_impl("tf_nn_gather_blend_chunks_norm", tgt, piv, inv_norm, kf_out, w, resid, out, K, n,
-                                       C, S, D, slot0, first_single, search_dtype, in_dtype, res_dtype, out_dtype,
+                                       C, S, D, slot0, first_single ? 1 : 0, search_dtype, in_dtype, res_dtype, out_dtype,
                                        single_dtype, ws, ws_bytes, stream, nm);
+}
+
+// Keyframe segments (include/tokenflow_hip.h): the chunk forms with one bit per chunk in the place of first_single -- every
+// chunk that starts a segment is a one-keyframe chunk.  Same search launch, same gather launch; mask 0 / 1 are the chunk forms.
+extern "C" int tf_nn_gather_blend_chunks_segments(const void* tgt, const void* piv, const float* inv_norm,
+                                                  const void* kf_out, const float* w, const void* resid, void* out, int K,
+                                                  int n, int C, int S, int D, int slot0, uint64_t single_mask,
+                                                  int search_dtype, int in_dtype, int res_dtype, int out_dtype,
+                                                  int single_dtype, void* ws, size_t ws_bytes, void* stream) {
+    return nn_gather_blend_chunks_impl("tf_nn_gather_blend_chunks_segments", tgt, piv, inv_norm, kf_out, w, resid, out, K, n,
+                                       C, S, D, slot0, single_mask, search_dtype, in_dtype, res_dtype, out_dtype,
+                                       single_dtype, ws, ws_bytes, stream, NormArgs{}, 0, true);
+}
+
+extern "C" int tf_nn_gather_blend_chunks_norm_segments(const void* tgt, const void* piv, const float* inv_norm,
+                                                       const void* kf_out, const float* w, const void* resid, void* out,
+                                                       int K, int n, int C, int S, int D, int slot0, uint64_t single_mask,
+                                                       int search_dtype, int in_dtype, int res_dtype, int out_dtype,
+                                                       int single_dtype, const void* gamma, const void* beta, float eps,
+                                                       int w_dtype, void* norm_out, int norm_dtype, void* ws,
+                                                       size_t ws_bytes, void* stream) {
+    TF_ARG(norm_out, TF_ERR_NULL, "tf_nn_gather_blend_chunks_norm_segments: null norm_out");
+    NormArgs nm;
+    nm.out = norm_out, nm.gamma = gamma, nm.beta = beta, nm.eps = eps, nm.w_dtype = w_dtype, nm.dtype = norm_dtype;
+    return nn_gather_blend_chunks_impl("tf_nn_gather_blend_chunks_norm_segments", tgt, piv, inv_norm, kf_out, w, resid, out,
+                                       K, n, C, S, D, slot0, single_mask, search_dtype, in_dtype, res_dtype, out_dtype,
+                                       single_dtype, ws, ws_bytes, stream, nm, 0, true);
+}
+
+// Launch plan of tf_nn_gather_blend_chunks_segments (host only): the entry point itself under the plan recorder.
+extern "C" int tf_nn_gather_blend_segments_plan(int n, int C, int S, int D, uint64_t single_mask, char* buf, size_t len) {
+    TF_ARG(n > 0 && C > 0 && S > 0 && D > 0 && D % 8 == 0, TF_ERR_SHAPE,
+           "tf_nn_gather_blend_segments_plan: n=%d C=%d S=%d D=%d", n, C, S, D);
+    void* const ph = reinterpret_cast<void*>((uintptr_t)1 << 12);
+    const float* const phf = reinterpret_cast<const float*>(ph);
+    TfPlanRec rec{buf, len, 0, 0};
+    if (buf && len) buf[0] = 0;
+    tf_plan_rec = &rec;
+    const int rc = tf_nn_gather_blend_chunks_segments(ph, ph, phf, ph, phf, ph, ph, C + 1, n, C, S, D, (single_mask & 1) ? 0 : 1,
+                                                      single_mask, TF_BF16, TF_BF16, TF_BF16, TF_F32, TF_BF16, ph,
+                                                      (size_t)-1, nullptr);
+    tf_plan_rec = nullptr;
+    if (rc) return rc;
+    TF_ARG(rec.used < len, TF_ERR_WORKSPACE, "tf_nn_gather_blend_segments_plan: the plan needs %zu bytes", rec.used + 1);
+    return rec.n;
 }
 
 // Multi-edit batches (include/tokenflow_hip.h): the chunk forms over B = 1 + 2*n_edits branches.  ONE search (the launches of the
@@ -609,9 +660,9 @@ static int nn_gather_blend_edits(const char* name, const void* tgt, const void* 
         return nn_gather_blend_impl(name, tgt, piv, inv_norm, kf_out, nullptr, resid, out, K, n, S, D, 1, slot0, 0,
                                     search_dtype, in_dtype, res_dtype, out_dtype, ws, ws_bytes, stream, nm, n_edits);
     }
-    return nn_gather_blend_chunks_impl(name, tgt, piv, inv_norm, kf_out, w, resid, out, K, n, C, S, D, slot0, first_single,
-                                       search_dtype, in_dtype, res_dtype, out_dtype, single_dtype, ws, ws_bytes, stream, nm,
-                                       n_edits);
+    return nn_gather_blend_chunks_impl(name, tgt, piv, inv_norm, kf_out, w, resid, out, K, n, C, S, D, slot0,
+                                       first_single ? 1 : 0, search_dtype, in_dtype, res_dtype, out_dtype, single_dtype, ws,
+                                       ws_bytes, stream, nm, n_edits);
 }
 
 extern "C" int tf_nn_gather_blend_chunks_edits(const void* tgt, const void* piv, const float* inv_norm, const void* kf_out,

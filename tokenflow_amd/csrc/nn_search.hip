@@ -95,12 +95,12 @@ __global__ __launch_bounds__(256) void nn_search_kernel(const typename T::elem* 
     // chunk of the video this target panel belongs to (0 in the single-chunk call): chunk j matches keyframe
     // slots kf0 + j and kf1 + j; the first chunk of the video has ONE keyframe (tokenflow_utils.py:331-333)
     const int chunk = blockIdx.x / ch.ppc;
-    if (p == 1 && chunk == 0 && ch.first_single) return;
+    if (p == 1 && nn_chunk_single(ch, chunk)) return;
     const int kf = (p == 0 ? kf0 : kf1) + chunk;
     const typename T::elem* pv = piv + (int64_t)kf * S * D;
     const float* inv = inv_norm + (int64_t)kf * S;
-    const int64_t t0 = chunk * ch.nS + (int64_t)(blockIdx.x - chunk * ch.ppc) * TN;
-    const int64_t t_end = (chunk + 1) * ch.nS;   // targets of this chunk: [chunk * nS, t_end)
+    const int64_t t0 = chunk * (int64_t)ch.nS + (int64_t)(blockIdx.x - chunk * ch.ppc) * TN;
+    const int64_t t_end = (chunk + 1) * (int64_t)ch.nS;   // targets of this chunk: [chunk * nS, t_end)
 
     const int n_mt_all = (S + TM - 1) / TM;
     const int mt0 = blockIdx.z * tiles_per_split;           // this workgroup's slice of the pivot tiles
@@ -323,12 +323,12 @@ __global__ __launch_bounds__(512, 2) void nn_search_glds_kernel(const typename T
 
     const int p = blockIdx.y;
     const int chunk = blockIdx.x / ch.ppc;
-    if (p == 1 && chunk == 0 && ch.first_single) return;
+    if (p == 1 && nn_chunk_single(ch, chunk)) return;
     const int kf = (p == 0 ? kf0 : kf1) + chunk;
     const E* pv = piv + (int64_t)kf * S * D;
     const float* inv = inv_norm + (int64_t)kf * S;
-    const int64_t t0 = chunk * ch.nS + (int64_t)(blockIdx.x - chunk * ch.ppc) * TN;
-    const int64_t t_end = (chunk + 1) * ch.nS;
+    const int64_t t0 = chunk * (int64_t)ch.nS + (int64_t)(blockIdx.x - chunk * ch.ppc) * TN;
+    const int64_t t_end = (chunk + 1) * (int64_t)ch.nS;
 
     const int n_mt_all = (S + TM - 1) / TM;
     const int mt0 = blockIdx.z * tiles_per_split;
@@ -581,12 +581,12 @@ __global__ __launch_bounds__(256, 3) void nn_search_rb_kernel(const typename T::
     const int l31 = lane & 31;
     const int p = blockIdx.y;
     const int chunk = blockIdx.x / ch.ppc;       // see nn_search_kernel
-    if (p == 1 && chunk == 0 && ch.first_single) return;
+    if (p == 1 && nn_chunk_single(ch, chunk)) return;
     const int kf = (p == 0 ? kf0 : kf1) + chunk;
     const E* pv = piv + (int64_t)kf * S * D;
     const float* inv = inv_norm + (int64_t)kf * S;
-    const int64_t t_end = (chunk + 1) * ch.nS;
-    const int64_t t_row = chunk * ch.nS + (int64_t)(blockIdx.x - chunk * ch.ppc) * 128 + wave * 32 + l31;
+    const int64_t t_end = (chunk + 1) * (int64_t)ch.nS;
+    const int64_t t_row = chunk * (int64_t)ch.nS + (int64_t)(blockIdx.x - chunk * ch.ppc) * 128 + wave * 32 + l31;
 
     const int n_mt_all = (S + TMR - 1) / TMR;
     const int mt0 = blockIdx.z * tiles_per_split;
@@ -710,15 +710,15 @@ __global__ __launch_bounds__(256, TT == 1 ? 3 : 2) void nn_search_rbg_kernel(con
     const int l31 = lane & 31;
     const int p = blockIdx.y;
     const int chunk = blockIdx.x / ch.ppc;       // see nn_search_kernel
-    if (p == 1 && chunk == 0 && ch.first_single) return;
+    if (p == 1 && nn_chunk_single(ch, chunk)) return;
     const int kf = (p == 0 ? kf0 : kf1) + chunk;
     const E* pv = piv + (int64_t)kf * S * D;
     const float* inv = inv_norm + (int64_t)kf * S;
-    const int64_t t_end = (chunk + 1) * ch.nS;
+    const int64_t t_end = (chunk + 1) * (int64_t)ch.nS;
     int64_t t_row[TT];
 #pragma unroll
     for (int tt = 0; tt < TT; ++tt)
-        t_row[tt] = chunk * ch.nS + (int64_t)(blockIdx.x - chunk * ch.ppc) * (128 * TT) + (wave * TT + tt) * 32 + l31;
+        t_row[tt] = chunk * (int64_t)ch.nS + (int64_t)(blockIdx.x - chunk * ch.ppc) * (128 * TT) + (wave * TT + tt) * 32 + l31;
 
     const int n_mt_all = (S + TMR - 1) / TMR;
     const int mt0 = blockIdx.z * tiles_per_split;
@@ -862,15 +862,15 @@ __global__ __launch_bounds__(256, TJ == 4 ? 2 : 3) void nn_search_rbs_kernel(con
     const int n16 = lane & 15;    // A: pivot row of the 16-row sub-tile; B / C: target of the 16-target sub-tile
     const int p = blockIdx.y;
     const int chunk = blockIdx.x / ch.ppc;       // see nn_search_kernel
-    if (p == 1 && chunk == 0 && ch.first_single) return;
+    if (p == 1 && nn_chunk_single(ch, chunk)) return;
     const int kf = (p == 0 ? kf0 : kf1) + chunk;
     const E* pv = piv + (int64_t)kf * S * D;
     const float* inv = inv_norm + (int64_t)kf * S;
-    const int64_t t_end = (chunk + 1) * ch.nS;
+    const int64_t t_end = (chunk + 1) * (int64_t)ch.nS;
     int64_t t_row[TJ];
 #pragma unroll
     for (int j = 0; j < TJ; ++j)
-        t_row[j] = chunk * ch.nS + (int64_t)(blockIdx.x - chunk * ch.ppc) * (64 * TJ) + wave * (16 * TJ) + 16 * j + n16;
+        t_row[j] = chunk * (int64_t)ch.nS + (int64_t)(blockIdx.x - chunk * ch.ppc) * (64 * TJ) + wave * (16 * TJ) + 16 * j + n16;
 
     const int n_mt_all = (S + TMR - 1) / TMR;
     const int mt0 = blockIdx.z * tiles_per_split;
@@ -1106,11 +1106,11 @@ static int finalize(const NnPartial* part, int32_t* idx, int64_t total, int spli
     return 0;
 }
 
-// n_tgt = targets per chunk; C chunks per launch (C = 1, first_single = 0: the plain single-chunk search).
+// n_tgt = targets per chunk; C chunks per launch (C = 1, single_mask = 0: the plain single-chunk search).
 // Partial results / indices are laid out over all C * n_tgt targets.
 template <typename T, int WN, int BK, int TM>
 int launch_nn(const void* tgt, const void* piv, const float* inv_norm, int32_t* idx, NnPartial* ws, int64_t n_tgt,
-              int S, int D, int P, int kf0, int kf1, hipStream_t st, bool fin, int C, int first_single) {
+              int S, int D, int P, int kf0, int kf1, hipStream_t st, bool fin, int C, uint64_t single_mask) {
     constexpr int TN = 64 * WN;
     constexpr size_t lds = 2 * (TM + TN) * BK * 2 + 2 * TM * 4 + 2 * TN * 8;
     static_assert(lds <= 160 * 1024, "LDS");
@@ -1122,7 +1122,7 @@ int launch_nn(const void* tgt, const void* piv, const float* inv_norm, int32_t* 
         return (fin && splits > 1) ? finalize(ws, idx, n_tgt * C * P, splits, st) : 0;
     auto kern = nn_search_kernel<T, WN, BK, TM>;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    const NnChunks ch{n_tgt, (int)pl.panels, first_single};
+    const NnChunks ch = nn_chunks(n_tgt, (int)pl.panels, single_mask);
     hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, reinterpret_cast<const typename T::elem*>(tgt),
                        reinterpret_cast<const typename T::elem*>(piv), inv_norm, idx,
                        (splits > 1 || !fin) ? ws : nullptr, n_tgt * C, S, D, kf0, kf1, tps, ch);
@@ -1132,7 +1132,7 @@ int launch_nn(const void* tgt, const void* piv, const float* inv_norm, int32_t* 
 
 template <typename T>
 int launch_nn_glds(const void* tgt, const void* piv, const float* inv_norm, int32_t* idx, NnPartial* ws, int64_t n_tgt,
-                   int S, int D, int P, int kf0, int kf1, hipStream_t st, bool fin, int C, int first_single) {
+                   int S, int D, int P, int kf0, int kf1, hipStream_t st, bool fin, int C, uint64_t single_mask) {
     constexpr size_t lds = 2 * (256 + 256) * 64 * 2 + 2 * 256 * 4 + 4 * 256 * 8;
     static_assert(lds <= 160 * 1024, "LDS");
     const NnPlan pl = nn_plan(n_tgt, S, D, P, C);
@@ -1145,7 +1145,7 @@ int launch_nn_glds(const void* tgt, const void* piv, const float* inv_norm, int3
     auto kern = nn_search_glds_kernel<T, false>;
 #endif
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    const NnChunks ch{n_tgt, (int)pl.panels, first_single};
+    const NnChunks ch = nn_chunks(n_tgt, (int)pl.panels, single_mask);
     hipLaunchKernelGGL(kern, grid, dim3(512), lds, st, reinterpret_cast<const typename T::elem*>(tgt),
                        reinterpret_cast<const typename T::elem*>(piv), inv_norm, idx,
                        (splits > 1 || !fin) ? ws : nullptr, n_tgt * C, S, D, kf0, kf1, tps, ch);
@@ -1155,13 +1155,13 @@ int launch_nn_glds(const void* tgt, const void* piv, const float* inv_norm, int3
 
 template <typename T, int DK>
 int launch_nn_rb(const void* tgt, const void* piv, const float* inv_norm, int32_t* idx, NnPartial* ws, int64_t n_tgt,
-                 int S, int P, int kf0, int kf1, hipStream_t st, bool fin, int C, int first_single) {
+                 int S, int P, int kf0, int kf1, hipStream_t st, bool fin, int C, uint64_t single_mask) {
     constexpr int D = 16 * DK;
     const size_t lds = 2 * 32 * (D + 8) * 2 + 2 * 32 * 4;
     const NnPlan pl = nn_plan(n_tgt, S, D, P, C);
     const int splits = pl.splits, tps = pl.tiles_per_split;
     dim3 grid((unsigned)(pl.panels * C), (unsigned)P, (unsigned)splits);
-    const NnChunks ch{n_tgt, (int)pl.panels, first_single};
+    const NnChunks ch = nn_chunks(n_tgt, (int)pl.panels, single_mask);
     if (pl.kern == NN_RB2) {   // 256-target panels, two target tiles per wave (the plan has checked S % 32 == 0)
         const size_t lds_g = 2 * 32 * D * 2 + 2 * 32 * 4;
 #ifndef TF_TUNE_NN_NO_RBS
@@ -1210,21 +1210,23 @@ int launch_nn_rb(const void* tgt, const void* piv, const float* inv_norm, int32_
 
 template <typename T>
 int dispatch_nn(const void* tgt, const void* piv, const float* inv_norm, int32_t* idx, NnPartial* ws, int64_t n_tgt,
-                int S, int D, int P, int kf0, int kf1, hipStream_t st, bool fin, int C = 1, int first_single = 0) {
+                int S, int D, int P, int kf0, int kf1, hipStream_t st, bool fin, int C = 1, uint64_t single_mask = 0) {
+    // the chunk descriptor of a launch carries the targets per chunk in 32 bits (NnChunks)
+    TF_ARG(n_tgt <= (int64_t)INT32_MAX, TF_ERR_SHAPE, "tf_nn_search: %lld targets per chunk (< 2^31)", (long long)n_tgt);
     switch (nn_plan(n_tgt, S, D, P, C).kern) {
         case NN_RB:
         case NN_RB2:
-            return launch_nn_rb<T, 20>(tgt, piv, inv_norm, idx, ws, n_tgt, S, P, kf0, kf1, st, fin, C, first_single);
+            return launch_nn_rb<T, 20>(tgt, piv, inv_norm, idx, ws, n_tgt, S, P, kf0, kf1, st, fin, C, single_mask);
         case NN_GLDS:
-            return launch_nn_glds<T>(tgt, piv, inv_norm, idx, ws, n_tgt, S, D, P, kf0, kf1, st, fin, C, first_single);
+            return launch_nn_glds<T>(tgt, piv, inv_norm, idx, ws, n_tgt, S, D, P, kf0, kf1, st, fin, C, single_mask);
         case NN_WIDE:
-            return launch_nn<T, 2, 64, 128>(tgt, piv, inv_norm, idx, ws, n_tgt, S, D, P, kf0, kf1, st, fin, C, first_single);
+            return launch_nn<T, 2, 64, 128>(tgt, piv, inv_norm, idx, ws, n_tgt, S, D, P, kf0, kf1, st, fin, C, single_mask);
         case NN_DEEP:
-            return launch_nn<T, 1, 256, 64>(tgt, piv, inv_norm, idx, ws, n_tgt, S, D, P, kf0, kf1, st, fin, C, first_single);
+            return launch_nn<T, 1, 256, 64>(tgt, piv, inv_norm, idx, ws, n_tgt, S, D, P, kf0, kf1, st, fin, C, single_mask);
         case NN_BK128:
-            return launch_nn<T, 1, 128, 128>(tgt, piv, inv_norm, idx, ws, n_tgt, S, D, P, kf0, kf1, st, fin, C, first_single);
+            return launch_nn<T, 1, 128, 128>(tgt, piv, inv_norm, idx, ws, n_tgt, S, D, P, kf0, kf1, st, fin, C, single_mask);
         default:
-            return launch_nn<T, 1, 64, 128>(tgt, piv, inv_norm, idx, ws, n_tgt, S, D, P, kf0, kf1, st, fin, C, first_single);
+            return launch_nn<T, 1, 64, 128>(tgt, piv, inv_norm, idx, ws, n_tgt, S, D, P, kf0, kf1, st, fin, C, single_mask);
     }
 }
 
@@ -1289,11 +1291,11 @@ extern "C" int tf_nn_search(const void* tgt, const void* piv, const float* inv_n
 
 int tf_nn_search_partials(const void* tgt, const void* piv, const float* inv_norm, NnPartial* part, int64_t n_tgt,
                           int S, int D, int P, int kf0, int kf1, int dtype, hipStream_t st, int* splits, int C,
-                          int first_single) {
+                          uint64_t single_mask) {
     *splits = nn_plan(n_tgt, S, D, P, C).splits;
     return dtype == TF_BF16
-               ? dispatch_nn<BF16>(tgt, piv, inv_norm, nullptr, part, n_tgt, S, D, P, kf0, kf1, st, false, C, first_single)
-               : dispatch_nn<F16>(tgt, piv, inv_norm, nullptr, part, n_tgt, S, D, P, kf0, kf1, st, false, C, first_single);
+               ? dispatch_nn<BF16>(tgt, piv, inv_norm, nullptr, part, n_tgt, S, D, P, kf0, kf1, st, false, C, single_mask)
+               : dispatch_nn<F16>(tgt, piv, inv_norm, nullptr, part, n_tgt, S, D, P, kf0, kf1, st, false, C, single_mask);
 }
 
 size_t tf_nn_partials_bytes(int64_t n_tgt, int S, int D, int P, int C) {

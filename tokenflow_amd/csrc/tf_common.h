@@ -105,15 +105,24 @@ __device__ __forceinline__ int nn_merge_partials(const NnPartial* part, int64_t 
 // A launch over C consecutive chunks of the video (C = 1: the reference's one chunk per call): target panel ->
 // chunk j = panel / ppc, whose nS targets are matched against keyframe slots kf0 + j and kf1 + j.
 struct NnChunks {
-    int64_t nS;        // targets per chunk (n frames * S tokens)
+    int nS;            // targets per chunk (n frames * S tokens; < 2^31, checked by the launchers)
     int ppc;           // target panels per chunk
-    int first_single;  // chunk 0 of the launch is chunk 0 of the video: ONE keyframe (tokenflow_utils.py:331-333)
+    unsigned single_lo, single_hi;   // the 64-bit single mask, bit j: chunk j of the launch is the first chunk of a video / of a
+                                     // keyframe segment and has ONE keyframe (tokenflow_utils.py:331-333); its p = 1 half is
+                                     // never computed nor read.  Chunks at or above 64 are never single.  (Two 32-bit halves:
+                                     // the struct keeps 4-byte members behind nS, as it had with the first_single int.)
 };
+static inline NnChunks nn_chunks(int64_t nS, int ppc, uint64_t single_mask) {
+    return NnChunks{(int)nS, ppc, (unsigned)single_mask, (unsigned)(single_mask >> 32)};
+}
+__device__ __forceinline__ bool nn_chunk_single(const NnChunks& ch, int chunk) {
+    return chunk < 64 && (((chunk < 32 ? ch.single_lo : ch.single_hi) >> (chunk & 31)) & 1u);
+}
 // Search only (no finalize launch): partial results [splits][P][C * n_tgt] into `part`; arguments already validated.
 // n_tgt = targets per chunk.
 int tf_nn_search_partials(const void* tgt, const void* piv, const float* inv_norm, NnPartial* part, int64_t n_tgt,
                           int S, int D, int P, int kf0, int kf1, int dtype, hipStream_t st, int* splits, int C = 1,
-                          int first_single = 0);
+                          uint64_t single_mask = 0);
 size_t tf_nn_partials_bytes(int64_t n_tgt, int S, int D, int P, int C = 1);
 
 // ---- host-side error plumbing ------------------------------------------------

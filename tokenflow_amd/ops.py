@@ -193,6 +193,42 @@ def propagate_edits_plan(n: int, n_chunks: int, S: int, D: int, first_single: bo
                         1 if first_single else 0, int(n_edits))
 
 
+def _segments(what: str, segments, K: int):
+    """The keyframes per segment of a pass as a ctypes int array: 1 .. TF_MAX_SEGMENTS segments of >= 1 keyframes, sum K."""
+    seg = [int(x) for x in segments]
+    if not 1 <= len(seg) <= _lib.TF_MAX_SEGMENTS or any(x < 1 for x in seg):
+        raise ValueError(f"{what}: segments {seg} (1 .. {_lib.TF_MAX_SEGMENTS} segments of >= 1 keyframes)")
+    if sum(seg) != K:
+        raise ValueError(f"{what}: the segments {seg} hold {sum(seg)} keyframes, the pass {K}")
+    return (ctypes.c_int * len(seg))(*seg)
+
+
+def attn_segments_plan(K: int, segments: Sequence[int], S: int, heads: int, dh: int, inject: bool,
+                       dtype: torch.dtype = torch.bfloat16, out_dtype: Optional[torch.dtype] = None,
+                       fold_scale: Optional[bool] = None, no_split: Optional[bool] = None, fused: Optional[bool] = None,
+                       hints: int = 0) -> list:
+    """The launches `ext_attn_segments` makes for dense [3K,S,heads*dh] tensors, as tokens (tf_ext_attn_segments_plan: the
+    tokens of `attn_plan`; the joint launch of the fused segments is 'fused[..,sets=N]').  Host only: needs no GPU."""
+    seg = _segments("attn_segments_plan", segments, K)
+    flags = _attn_flags(inject, "all", out_dtype == torch.float32, fold_scale, no_split, fused, hints)
+    return _plan_tokens("tf_ext_attn_segments_plan", _lib.load().tf_ext_attn_segments_plan, K, len(seg), seg, S, heads, dh,
+                        flags, _DT[dtype])
+
+
+def _single_mask(what: str, mask, C: int) -> int:
+    m = int(mask)
+    if not 1 <= C <= 64 or m < 0 or m >> C:
+        raise ValueError(f"{what}: single_mask {m:#x} over {C} chunks (1 .. 64 chunks, no bit at or above them)")
+    return m
+
+
+def propagate_segments_plan(n: int, n_chunks: int, S: int, D: int, single_mask: int) -> list:
+    """The launches of `propagate_chunks_segments` for n_chunks > 1: the search tokens of `nn_plan(n*S, S, D, 2, n_chunks)`
+    (no finalize: the gather merges the splits) followed by 'gather[branches=3]'.  Host only."""
+    return _plan_tokens("tf_nn_gather_blend_segments_plan", _lib.load().tf_nn_gather_blend_segments_plan, int(n),
+                        int(n_chunks), S, D, _single_mask("propagate_segments_plan", single_mask, int(n_chunks)))
+
+
 def nn_plan(n_tgt: int, S: int, D: int, P: int, C: int = 1) -> list:
     """The search launches of `nn_search` (C = 1) or of `propagate_chunks` over C > 1 chunks of n_tgt targets (P = 2),
     as tokens (tf_nn_search_plan: e.g. ['glds[splits=2]', 'finalize']).  Host only: needs no GPU."""
@@ -252,6 +288,50 @@ def ext_attn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, scal
     ws = _workspace(nbytes, q.device)
     _launch(dev, "tf_ext_attn_fwd", lib.tf_ext_attn_fwd, q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(),
             K, Kq, int(q_frame0), S, heads, dh, ld, float(scale), flags, dt, ws.data_ptr(), ws.numel())
+    return out
+
+
+def ext_attn_segments(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, scale: float, inject: bool,
+                      segments: Sequence[int], out: Optional[torch.Tensor] = None, fold_scale: Optional[bool] = None,
+                      out_dtype: Optional[torch.dtype] = None, no_split: Optional[bool] = None,
+                      fused: Optional[bool] = None, hints: int = 0) -> torch.Tensor:
+    """`ext_attn` for a pass of several scenes or clips (tf_ext_attn_fwd_segments): q, k, v [3K,S,D] as there, `segments` the
+    keyframes per segment (consecutive frame windows, sum K).  The slices of a segment are what `ext_attn` computes on that
+    segment's tensors alone: a bank branch attends to the keys of its own segment only.  Segments whose own call is a fused
+    small-problem launch share ONE fused launch; the others share one V^T pre-pass and are bit-identical to their own
+    calls.  A single segment is `ext_attn`.  Arguments as `ext_attn` (no `part`, no q_frame0: every keyframe's queries)."""
+    dev = _need_gpu(q, k, v, out)
+    lib = _lib.load()
+    B, S, D = k.shape
+    if B % 3 or D % heads or q.shape != k.shape or v.shape != k.shape:
+        raise ValueError(f"ext_attn_segments: bad shapes q{tuple(q.shape)} k{tuple(k.shape)} v{tuple(v.shape)} heads {heads}")
+    K, dh = B // 3, D // heads
+    seg = _segments("ext_attn_segments", segments, K)
+    dt = _DT.get(q.dtype)
+    if dt is None or dt == _lib.TF_F32 or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise TypeError(f"ext_attn_segments: q/k/v must share dtype bf16 or f16, got {q.dtype},{k.dtype},{v.dtype}")
+
+    def rows(t):
+        if t.stride(-1) != 1 or t.stride(0) != S * t.stride(1):
+            t = t.contiguous()
+        return t
+    q, k, v = rows(q), rows(k), rows(v)
+    ld = q.stride(1)
+    if k.stride(1) != ld or v.stride(1) != ld:
+        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        ld = D
+    if out_dtype is None:
+        out_dtype = out.dtype if out is not None else q.dtype
+    if out_dtype not in (q.dtype, torch.float32):
+        raise TypeError(f"ext_attn_segments: out_dtype {out_dtype} (the input dtype or float32)")
+    if out is None:
+        out = torch.empty(B, S, D, dtype=out_dtype, device=q.device)
+    elif out.dtype != out_dtype or not out.is_contiguous() or out.shape != (B, S, D):
+        raise ValueError("ext_attn_segments: `out` must be a contiguous [3K,S,D] tensor of out_dtype")
+    flags = _attn_flags(inject, "all", out_dtype == torch.float32, fold_scale, no_split, fused, hints)
+    ws = _workspace(lib.tf_ext_attn_segments_workspace_bytes(K, S, heads, dh, dt), q.device)
+    _launch(dev, "tf_ext_attn_fwd_segments", lib.tf_ext_attn_fwd_segments, q.data_ptr(), k.data_ptr(), v.data_ptr(),
+            out.data_ptr(), K, len(seg), seg, S, heads, dh, ld, float(scale), flags, dt, ws.data_ptr(), ws.numel())
     return out
 
 
@@ -948,6 +1028,45 @@ def propagate_chunks(tgt: torch.Tensor, piv: torch.Tensor, inv_norm: torch.Tenso
             out.data_ptr(), K, n, C, S, D, int(slot0), 1 if first_single else 0, _DT[tgt.dtype], _DT[kf_out.dtype],
             _DT[residual.dtype] if residual is not None else 0, _DT[out_dtype], _DT[single_dtype],
             ws.data_ptr(), ws.numel())
+    return out
+
+
+def propagate_chunks_segments(tgt: torch.Tensor, piv: torch.Tensor, inv_norm: torch.Tensor, kf_out: torch.Tensor,
+                              w: torch.Tensor, n: int, n_chunks: int, slot0: int, single_mask: int,
+                              residual: Optional[torch.Tensor], out_dtype: torch.dtype, norm=None):
+    """`propagate_chunks` for a run of chunks that crosses scene cuts (tf_nn_gather_blend_chunks_segments): bit j of
+    `single_mask` = chunk j of the run is the first chunk of a keyframe segment, a one-keyframe chunk matching slot0 + j
+    alone (its rows rounded as chunk 0's of a video are); every other chunk j matches slots slot0 + j and slot0 + j - 1.
+    One search and one gather for the whole run.  Masks 1 and 0 are `propagate_chunks` with and without first_single; one
+    chunk is `propagate`."""
+    C = int(n_chunks)
+    m = _single_mask("propagate_chunks_segments", single_mask, C)
+    if C == 1:
+        return propagate_chunks(tgt, piv, inv_norm, kf_out, w, n, C, slot0, bool(m & 1), residual, out_dtype, norm=norm)
+    dev = _need_gpu(tgt, piv, inv_norm, kf_out, w, residual)
+    lib = _lib.load()
+    tgt, piv, kf_out = tgt.contiguous(), piv.contiguous(), kf_out.contiguous()
+    K, S, D = piv.shape
+    if (tgt.dtype != piv.dtype or tgt.shape != (C * n * S, D) or kf_out.shape != (3 * K, S, D) or w is None
+            or slot0 + C > K or slot0 < (0 if m & 1 else 1)):
+        raise ValueError("propagate_chunks_segments: bad arguments")
+    if residual is not None:
+        residual = residual.contiguous()
+    single_dtype = kf_out.dtype if residual is None else torch.promote_types(kf_out.dtype, residual.dtype)
+    out = torch.empty(3 * C * n, S, D, dtype=out_dtype, device=kf_out.device)
+    ws = _workspace(lib.tf_nn_gather_blend_chunks_workspace_bytes(n * S, S, D, C), tgt.device, "nn")
+    head = (tgt.data_ptr(), piv.data_ptr(), inv_norm.data_ptr(), kf_out.data_ptr(), w.data_ptr(),
+            residual.data_ptr() if residual is not None else 0, out.data_ptr(), K, n, C, S, D, int(slot0), m, _DT[tgt.dtype],
+            _DT[kf_out.dtype], _DT[residual.dtype] if residual is not None else 0, _DT[out_dtype], _DT[single_dtype])
+    if norm is not None:
+        if not norm_fusable(kf_out, residual, out_dtype, 2, norm[3]):
+            raise TypeError("propagate_chunks_segments: these dtypes have no fused-norm form (ops.norm_fusable)")
+        g, b, eps, wdt, nout, ndt, _keep = _norm_args(norm, kf_out, (3 * C * n, S, D))
+        _launch(dev, "tf_nn_gather_blend_chunks_norm_segments", lib.tf_nn_gather_blend_chunks_norm_segments, *head, g, b, eps,
+                wdt, nout.data_ptr(), ndt, ws.data_ptr(), ws.numel())
+        return out, nout
+    _launch(dev, "tf_nn_gather_blend_chunks_segments", lib.tf_nn_gather_blend_chunks_segments, *head, ws.data_ptr(),
+            ws.numel())
     return out
 
 
