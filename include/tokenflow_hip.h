@@ -656,6 +656,49 @@ TF_API int tf_nn_gather_blend_chunks_norm_segments(const void* tgt, const void* 
 TF_API int tf_nn_gather_blend_segments_plan(int n, int C, int S, int D, uint64_t single_mask, char* buf, size_t len);
 
 /* ------------------------------------------------------------------------
+ * Sliding-window keyframe BANK (additive to ABI 11): the extended attention of long videos.  A keyframe's uncond / cond
+ * branches attend to the keys of its NEIGHBOURING keyframes only -- overlapping windows, where keyframe segments are disjoint
+ * ones -- so the pivotal pass costs sum_i win_n[i] frame-banks instead of K * Kq.  This CHANGES THE RESULT relative to
+ * TokenFlow (there every keyframe attends to the whole bank); it is opt-in, and with every window = [0, K) it IS the
+ * reference computation.
+ *
+ * tf_ext_attn_fwd_windows: the arguments of tf_ext_attn_fwd_strided plus two HOST arrays of Kq ints.
+ *   The uncond / cond branches of query frame i (bank frame q_frame0 + i) attend to the keys of bank frames
+ *   [win_lo[i], win_lo[i] + win_n[i]); under TF_ATTN_INJECT with the source's q and k, over the same windows.  The source
+ *   branch attends to its own frame, as always.
+ *   Refused with TF_ERR_SHAPE, before anything touches the device: Kq > TF_MAX_WINDOW_FRAMES; win_n[i] < 1; a window outside
+ *     [0, K); a window that does not hold its own frame q_frame0 + i (a keyframe always sees itself); TF_ATTN_BANK_ONLY,
+ *     TF_ATTN_SOURCE_ONLY, TF_ATTN_FOLD_SCALE and the multi-edit hints (TF_ATTN_MULTI_V, TF_ATTN_NO_MULTI_V, TF_ATTN_MULTI_V64,
+ *     TF_ATTN_RUN_MULTI_V).  The other flags and hints act as in tf_ext_attn_fwd.
+ *   Every window = [0, K) IS tf_ext_attn_fwd_strided: same launches, same bits, same plan tokens.
+ *   Otherwise the call issues the launches tf_ext_attn_fwd_strided would issue for a bank of K' = max_i win_n[i] frames at the
+ *   same Kq, S, H, Dh and flags (the fused-kernel decision, the split plan and the kernel forms are those of K'; under
+ *   TF_ATTN_NO_SPLIT a function of the shape alone):
+ *     - ONE V^T pre-pass over the whole bank of K frames;
+ *     - ONE bank launch (or ONE fused launch, which needs no pre-pass) whose window table rides in the kernel arguments --
+ *       no device table, no copy, no sync: the call can be captured.  A bank problem of query frame i streams the frames of
+ *       window i; the split form splits the WINDOW into its nseg runs (a window shorter than nseg leaves empty runs, which the
+ *       merge weighs with 0).  Plan token: the plain launch's with ",win" appended -- il<..>,win, one<..>,win, pp<..>,win,
+ *       fused[..,win];
+ *     - the merge and the source launches as in the plain call.
+ *   Workgroups keep frame order.
+ *   Identity.  Frame i's OWN CALL is tf_ext_attn_fwd_strided on the window's tensors with (K, Kq, q_frame0) =
+ *   (win_n[i], 1, q_frame0 + i - win_lo[i]).  Frame i's result is within the attention bound of its own call always, and
+ *   BIT-IDENTICAL to it under TF_ATTN_NO_SPLIT wherever the two plans name the same kernel form: a one-pass launch's
+ *   arithmetic for a (query, head) depends only on the sequence of key tiles, the fused kernel's on KW and PREC only.
+ *   ws: tf_ext_attn_workspace_bytes(K, ...), unchanged.
+ * tf_ext_attn_windows_plan: the launches of the call for dense tensors (host only), the tokens of tf_ext_attn_plan.
+ * ------------------------------------------------------------------------ */
+#define TF_MAX_WINDOW_FRAMES 64
+
+TF_API int tf_ext_attn_fwd_windows(const void* q, const void* k, const void* v, void* out, int K, int Kq, int q_frame0, int S,
+                            int H, int Dh, int64_t ld, const int64_t* strides, float scale, int flags, int dtype,
+                            const int* win_lo, const int* win_n, void* ws, size_t ws_bytes, void* stream);
+
+TF_API int tf_ext_attn_windows_plan(int K, int Kq, int q_frame0, int S, int H, int Dh, int flags, int dtype, const int* win_lo,
+                             const int* win_n, char* buf, size_t len);
+
+/* ------------------------------------------------------------------------
  * Row LayerNorm producer  --  the `norm1` call of TokenFlowBlock.forward
  * (tokenflow_utils.py:313-323; also norm2 / norm3 of the same forward, 399-417)
  * when the block runs in 16 bit:  out[r] = (x[r] - mean) / sqrt(var + eps) * gamma + beta

@@ -28,6 +28,7 @@ def attn_hint(qw: int = 0, kw: int = 0, qb: int = 1) -> int:
 ABI_VERSION = 11
 TF_MAX_EDITS = 8
 TF_MAX_SEGMENTS = 8
+TF_MAX_WINDOW_FRAMES = 64
 TF_RANK_HEADS, TF_RANK_BANK, TF_RANK_SLOTS, TF_RANK_NO_HALO, TF_RANK_INV_NORM = 0, 1, 64, 16, 32
 TF_RANK_BANK_RUNS = 2
 TF_RANK_BANK_EDIT_RUNS = 3   # tf_rank_pivotal_edits: the bank in runs for a multi-edit batch
@@ -149,6 +150,10 @@ _SIGNATURES = {
                                                                   _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_size_t,
                                                                   _c.c_void_p]),
     "tf_nn_gather_blend_segments_plan": (_c.c_int, [_c.c_int] * 4 + [_c.c_uint64, _c.c_char_p, _c.c_size_t]),
+    # sliding-window keyframe bank: a keyframe attends to its neighbouring keyframes only (additive to ABI 11)
+    "tf_ext_attn_fwd_windows": (_c.c_int, [_c.c_void_p] * 4 + [_c.c_int] * 6 + [_c.c_int64, _c.c_void_p, _c.c_float, _c.c_int,
+                                           _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "tf_ext_attn_windows_plan": (_c.c_int, [_c.c_int] * 8 + [_c.c_void_p, _c.c_void_p, _c.c_char_p, _c.c_size_t]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -120,6 +120,37 @@ struct AttnParams {
     int gap;
 };
 
+// Sliding-window keyframe bank (tf_ext_attn_fwd_windows): the launch's parameter block with the window table behind it.  A type
+// of its own, so that every other launch keeps its parameter block and its code; the table rides in the kernel arguments (a
+// workgroup reads its query frame's entry with one scalar load), there is no device table, no copy and no sync.
+struct AttnParamsWin : AttnParams {
+    unsigned win[TF_MAX_WINDOW_FRAMES];   // query frame i: first bank frame of its window | frames of the window << 16
+};
+template <typename P>
+constexpr bool is_win = std::is_same<P, AttnParamsWin>::value;
+
+// Windowed launches, key range of a bank problem: run `seg` of the nseg runs of query frame f's WINDOW.  A window shorter than
+// nseg frames leaves some runs empty (n_fr = 0).
+__device__ __forceinline__ void window_range(const AttnParamsWin& p, int f, int seg, int nseg, int& f_lo, int& n_fr) {
+    const unsigned w = p.win[f];
+    const int lo = (int)(w & 0xffffu), n = (int)(w >> 16);
+    f_lo = lo + (seg * n) / nseg;
+    n_fr = lo + ((seg + 1) * n) / nseg - f_lo;
+}
+
+// Windowed split form, an empty run: the neutral partial result (O = 0, l = 0, shift = -inf: weight 0 in attn_merge_kernel)
+// for the `rows` queries from q0 on, in each of the nb banks from `bank` on.
+__device__ __forceinline__ void write_empty_run(const AttnParams& p, int bank, int nb, int f, int h, int seg, int q0, int rows,
+                                                int DH, int nthreads) {
+    const int PS = DH + 8;
+    for (int id = threadIdx.x; id < nb * rows * PS; id += nthreads) {
+        const int vb = id / (rows * PS), r = (id / PS) % rows, c = id % PS;
+        if (q0 + r >= p.S) continue;
+        const int64_t R = (((int64_t)(bank + vb) * p.Kq + f) * p.H + h) * p.S + q0 + r;
+        p.partials[(R * p.pslots + seg) * PS + c] = c == DH + 1 ? -INFINITY : 0.f;
+    }
+}
+
 // max over the two lanes (l, l ^ 32) that share a query: v_permlane32_swap instead of an LDS round trip
 __device__ __forceinline__ float max_with_lane_xor32(float x) {
     const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
@@ -243,8 +274,8 @@ __global__ __launch_bounds__(256) void vt_pack_kernel(const typename T::elem* __
 //        scaling of the scores as the reference does (tokenflow_utils.py:173-175 `* self.scale` on the bmm output)
 // SB   = single LDS buffer (two barriers per tile) instead of two: half the LDS per workgroup.  For head dim 160, where
 //        the double-buffered tiles (89 KB) allow ONE workgroup per CU and a wave waits alone for every 1 KB fragment
-template <typename T, int DH, int QT, int NW, int MODE, int MINW, int KT, bool FQ, bool SB = false>
-__global__ __launch_bounds__(64 * NW, MINW) void ext_attn_kernel(AttnParams p) {
+template <typename T, int DH, int QT, int NW, int MODE, int MINW, int KT, bool FQ, bool SB = false, typename P = AttnParams>
+__global__ __launch_bounds__(64 * NW, MINW) void ext_attn_kernel(P p) {
     typedef AttnCfg<DH, KT> C;
     typedef typename T::elem E;
     typedef typename T::vec8 vec8;
@@ -343,8 +374,15 @@ __global__ __launch_bounds__(64 * NW, MINW) void ext_attn_kernel(AttnParams p) {
     qt = u - f * p.nQT;
     const int bq = (p.inject && b > 0) ? 0 : b;  // branch whose q and k are used (tokenflow_utils.py:124-130)
     const bool split = p.pslots > 0 && b > 0;
-    const int f_lo = b == 0 ? p.q_frame0 + f : (seg * K) / nseg;
-    const int n_fr = b == 0 ? 1 : ((seg + 1) * K) / nseg - f_lo;
+    int f_lo = b == 0 ? p.q_frame0 + f : (seg * K) / nseg;
+    int n_fr = b == 0 ? 1 : ((seg + 1) * K) / nseg - f_lo;
+    if constexpr (is_win<P>) {   // a bank problem reads its query frame's window of the bank
+        if (b > 0) window_range(p, f, seg, nseg, f_lo, n_fr);
+        if (n_fr == 0) {   // a window shorter than the split: this run holds no frame
+            write_empty_run(p, b - 1, NB, f, h, seg, qt * (32 * QT * NW), 32 * QT * NW, DH, NT);
+            return;
+        }
+    }
     const int tpf = (S + KT - 1) / KT;  // staged tiles per frame
     const int ntiles = n_fr * tpf;
     const bool ragged = (S % KT) != 0;
@@ -1048,8 +1086,8 @@ struct PpSchedule {
 // RUN (tf_ext_attn_run): bank problems only; the epilogue leaves the unnormalised O, the denominator and the shift in the
 // run's partial-result slot (one slot: this kernel has no split form) instead of the output.  A template parameter, not a
 // run-time one: the kernel sits at 250 VGPRs and the one-call instantiation must not change.
-template <typename T, int DH, int MODE, int MINW, bool FQ = false, bool RUN = false>
-__global__ __launch_bounds__(256, MINW) void ext_attn_pp_kernel(AttnParams p) {
+template <typename T, int DH, int MODE, int MINW, bool FQ = false, bool RUN = false, typename P = AttnParams>
+__global__ __launch_bounds__(256, MINW) void ext_attn_pp_kernel(P p) {
     typedef AttnCfg<DH, 64> C;
     typedef typename T::elem E;
     typedef typename T::vec8 vec8;
@@ -1098,8 +1136,11 @@ __global__ __launch_bounds__(256, MINW) void ext_attn_pp_kernel(AttnParams p) {
     f = u / p.nQT;
     qt = u - f * p.nQT;
     const int bq = (p.inject && b > 0) ? 0 : b;
-    const int f_lo = b == 0 ? p.q_frame0 + f : 0;
-    const int n_fr = b == 0 ? 1 : K;
+    int f_lo = b == 0 ? p.q_frame0 + f : 0;
+    int n_fr = b == 0 ? 1 : K;
+    if constexpr (is_win<P>) {   // a bank problem reads its query frame's window of the bank (this kernel has no split form)
+        if (b > 0) window_range(p, f, 0, 1, f_lo, n_fr);
+    }
     const int tpf = (S + 63) >> 6;
     const int ntiles = n_fr * tpf;
     const bool ragged = (S & 63) != 0;
@@ -1560,8 +1601,8 @@ struct IlScheduleMix {   // NT = 16-row M-tiles of P.V (3 at Dh = 40: 48 rows; 4
 //           partial piece past the end of the image are masked off (the constant rows behind it must survive).
 // A tile is issued right behind the barrier that frees its buffer and drained (vmcnt(0)) in front of the next one: the same
 // distance the register staging had.
-template <typename T, int DH, int NW, int MODE, int MINW, int DMA = 0>
-__global__ __launch_bounds__(64 * NW, MINW) void ext_attn_il_kernel(AttnParams p) {
+template <typename T, int DH, int NW, int MODE, int MINW, int DMA = 0, typename P = AttnParams>
+__global__ __launch_bounds__(64 * NW, MINW) void ext_attn_il_kernel(P p) {
     typedef AttnCfg<DH, 64> C;
     typedef typename T::elem E;
     typedef typename T::vec8 vec8;
@@ -1636,8 +1677,15 @@ __global__ __launch_bounds__(64 * NW, MINW) void ext_attn_il_kernel(AttnParams p
     qt = u - f * p.nQT;
     const int bq = (p.inject && b > 0) ? 0 : b;
     const bool split = p.pslots > 0 && b > 0;
-    const int f_lo = b == 0 ? p.q_frame0 + f : (seg * K) / nseg;
-    const int n_fr = b == 0 ? 1 : ((seg + 1) * K) / nseg - f_lo;
+    int f_lo = b == 0 ? p.q_frame0 + f : (seg * K) / nseg;
+    int n_fr = b == 0 ? 1 : ((seg + 1) * K) / nseg - f_lo;
+    if constexpr (is_win<P>) {   // a bank problem reads its query frame's window of the bank
+        if (b > 0) window_range(p, f, seg, nseg, f_lo, n_fr);
+        if (n_fr == 0) {   // a window shorter than the split: this run holds no frame
+            write_empty_run(p, b - 1, PACK ? 2 : 1, f, h, seg, qt * (32 * NW), 32 * NW, DH, NT);
+            return;
+        }
+    }
     const int tpf = S >> 6;
     const int ntiles = n_fr * tpf;
 
@@ -2257,14 +2305,22 @@ __global__ __launch_bounds__(64 * NW, MINW) void ext_attn_il_kernel(AttnParams p
 template <int MODE>
 static inline const char* run_mark(const AttnParams& p) { return (p.run && MODE != MODE_SOURCE) ? ",run" : ""; }
 
-template <typename T, int DH, int NW, int MODE, int MINW, int DMA = 0>
-int launch_il(AttnParams p, hipStream_t st) {
+// A windowed launch (AttnParamsWin) exists for the launches that hold bank problems and that tf_ext_attn_fwd_windows can
+// reach: the ALL and DUAL forms.  Its source-only launches are the plain ones (a source problem reads its own frame whatever
+// the windows); the four-bank and run forms take no windows.  Plan token: the plain launch's with ",win" appended.
+template <typename P, int MODE, bool RUN = false>
+constexpr bool win_launch = is_win<P> && (MODE == MODE_ALL || MODE == MODE_DUAL) && !RUN;
+
+template <typename T, int DH, int NW, int MODE, int MINW, int DMA = 0, typename P>
+int launch_il(const P& p_in, hipStream_t st) {
+    std::conditional_t<win_launch<P, MODE>, P, AttnParams> p = p_in;   // the kernel's parameter block
     typedef AttnCfg<DH, 64> C;
     constexpr size_t lds = DMA == 1            ? 2 * (size_t)(64 * DH + C::MT * 32 * 64) * 2 + 16   // dense images (+ the K over-read)
                            : MODE == MODE_DUAL ? 2 * (size_t)(C::K_ELEMS + ((2 * DH + 31) / 32) * 32 * C::VROW) * 2   // packed dual-V image
                                                : C::lds_bytes(1);
-    if (tf_plan_note("il<%d,%d,%s,%d,%d%s>", DH, NW, mode_name(MODE), MINW, DMA, run_mark<MODE>(p))) return 0;
-    auto kern = ext_attn_il_kernel<T, DH, NW, MODE, MINW, DMA>;
+    if (tf_plan_note("il<%d,%d,%s,%d,%d%s>%s", DH, NW, mode_name(MODE), MINW, DMA, run_mark<MODE>(p), is_win<decltype(p)> ? ",win" : ""))
+        return 0;
+    auto kern = ext_attn_il_kernel<T, DH, NW, MODE, MINW, DMA, decltype(p)>;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)lds);
     p.nQT = (p.S + 32 * NW - 1) / (32 * NW);
@@ -2281,12 +2337,13 @@ int launch_il(AttnParams p, hipStream_t st) {
     return 0;
 }
 
-template <typename T, int DH, int MODE, int MINW, bool RUN = false>
-int launch_pp(AttnParams p, hipStream_t st) {
+template <typename T, int DH, int MODE, int MINW, bool RUN = false, typename P>
+int launch_pp(const P& p_in, hipStream_t st) {
+    std::conditional_t<win_launch<P, MODE, RUN>, P, AttnParams> p = p_in;   // the kernel's parameter block
     typedef AttnCfg<DH, 64> C;
     constexpr size_t lds = C::lds_bytes(1);
-    if (tf_plan_note("pp<%d,%s%s>", DH, mode_name(MODE), RUN ? ",run" : "")) return 0;
-    auto kern = ext_attn_pp_kernel<T, DH, MODE, MINW, false, RUN>;
+    if (tf_plan_note("pp<%d,%s%s>%s", DH, mode_name(MODE), RUN ? ",run" : "", is_win<decltype(p)> ? ",win" : "")) return 0;
+    auto kern = ext_attn_pp_kernel<T, DH, MODE, MINW, false, RUN, decltype(p)>;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)lds);
     p.nQT = (p.S + 255) / 256;
@@ -2301,16 +2358,17 @@ int launch_pp(AttnParams p, hipStream_t st) {
     return 0;
 }
 
-template <typename T, int DH, int QT, int NW, int MODE, int MINW, bool FQ = true, int KT = 64, bool SB = false>
-int launch_one(AttnParams p, hipStream_t st) {
+template <typename T, int DH, int QT, int NW, int MODE, int MINW, bool FQ = true, int KT = 64, bool SB = false, typename P>
+int launch_one(const P& p_in, hipStream_t st) {
+    std::conditional_t<win_launch<P, MODE>, P, AttnParams> p = p_in;   // the kernel's parameter block
     typedef AttnCfg<DH, KT> C;
     constexpr size_t lds = ((MODE == MODE_DUAL && DH == 40)  ? 2 * (size_t)(C::K_ELEMS + 96 * C::VROW) * 2    // PACK
                             : (MODE == MODE_MV4 && DH == 40) ? 2 * (size_t)(C::K_ELEMS + 192 * C::VROW) * 2   // PACK, four banks
                                                              : C::lds_bytes(MODE == MODE_DUAL ? 2 : MODE == MODE_MV4 ? 4 : 1)) / (SB ? 2 : 1);
-    if (tf_plan_note("one<%d,%d,%d,%s,%d,fq%d%s%s%s>", DH, QT, NW, mode_name(MODE), MINW, FQ ? 1 : 0, KT != 64 ? ",kt128" : "",
-                     SB ? ",sb" : "", run_mark<MODE>(p)))
+    if (tf_plan_note("one<%d,%d,%d,%s,%d,fq%d%s%s%s>%s", DH, QT, NW, mode_name(MODE), MINW, FQ ? 1 : 0, KT != 64 ? ",kt128" : "",
+                     SB ? ",sb" : "", run_mark<MODE>(p), is_win<decltype(p)> ? ",win" : ""))
         return 0;
-    auto kern = ext_attn_kernel<T, DH, QT, NW, MODE, MINW, KT, FQ, SB>;
+    auto kern = ext_attn_kernel<T, DH, QT, NW, MODE, MINW, KT, FQ, SB, decltype(p)>;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)lds);
     p.nQT = (p.S + 32 * QT * NW - 1) / (32 * QT * NW);
@@ -2351,8 +2409,9 @@ int launch_vt_pack(const AttnParams& p, const void* v, int DH, int b_lo, int b_h
 // INDEPENDENT waves per SIMD (softmax VALU of one wave overlaps MFMAs of another) and how many waves share
 // one staged tile.  Dh=40: 1 query tile/wave, 8 waves/workgroup, 111 VGPRs -> 4 waves/SIMD.
 // Dh=64: 2 query tiles/wave (each LDS fragment feeds 2 MFMAs).  Dh=80/160: register-bound, 1 tile/wave.
-template <typename T, int DH>
-int launch_attn(const AttnParams& p, const void* v, hipStream_t st) {
+template <typename T, int DH, typename P>
+int launch_attn(const P& p, const void* v, hipStream_t st) {
+    constexpr bool WIN = is_win<P>;   // windowed call: no four-bank, run or folded-scale form (refused by the entry point)
     const bool src_only = p.part == TF_ATTN_SOURCE_ONLY, bank_only = p.part == TF_ATTN_BANK_ONLY;
     // The kernel FAMILY of a run launch is the one the unsplit call of the same (Kq, S, H) takes, however the run splits
     // itself: the source branch out of a run call is then bit for bit the source-only call's (same kernel, same keys).
@@ -2397,7 +2456,7 @@ int launch_attn(const AttnParams& p, const void* v, hipStream_t st) {
         // multi-edit batch under injection: two edits' bank branches in one launch (tf_ext_attn_fwd_edits), 4-wave workgroups,
         // two per CU (70 KB of tiles each)
         if (p.mv4) return launch_one<T, DH, 1, 4, MODE_MV4, 2, false>(p, st);
-        if (!p.fold) {   // fp32 score scaling: the default
+        if (!p.fold || WIN) {   // fp32 score scaling: the default (a windowed call has no other: TF_ATTN_FOLD_SCALE is refused)
 #ifndef TF_TUNE_IL40_MIN_WGS
 #define TF_TUNE_IL40_MIN_WGS 256   // one 8-wave workgroup per CU: a W = 8 rank's one-pass level 0 (384 workgroups) runs
 #endif                             // 586 us interleaved against 672 us in the plain 4-wave form (profiles/r03_rank_shard.txt)
@@ -2495,11 +2554,15 @@ int launch_attn(const AttnParams& p, const void* v, hipStream_t st) {
                                             : launch_one<T, DH, 1, 4, MODE_SOURCE, 2, false>(p, st);
                            });
         }
-        return compose([&] { return big ? launch_one<T, DH, 1, 8, MODE_ALL, 2>(p, st)
-                                        : launch_one<T, DH, 1, 4, MODE_ALL, 2>(p, st); },
-                       [&] { return launch_one<T, DH, 1, 4, MODE_DUAL, 3>(p, st); },   // 151 VGPRs: 3 workgroups per CU
-                       [&] { return big ? launch_one<T, DH, 1, 8, MODE_SOURCE, 2>(p, st)
-                                        : launch_one<T, DH, 1, 4, MODE_SOURCE, 2>(p, st); });
+        if constexpr (WIN)
+            return TF_ERR_SHAPE;   // never reached (tf_ext_attn_fwd_windows refuses the folded scale): keeps the folded-scale
+                                   // kernels from being instantiated on the windowed parameter block
+        else
+            return compose([&] { return big ? launch_one<T, DH, 1, 8, MODE_ALL, 2>(p, st)
+                                            : launch_one<T, DH, 1, 4, MODE_ALL, 2>(p, st); },
+                           [&] { return launch_one<T, DH, 1, 4, MODE_DUAL, 3>(p, st); },   // 151 VGPRs: 3 workgroups per CU
+                           [&] { return big ? launch_one<T, DH, 1, 8, MODE_SOURCE, 2>(p, st)
+                                            : launch_one<T, DH, 1, 4, MODE_SOURCE, 2>(p, st); });
     } else if constexpr (DH == 64) {
         // Round 6: the half-tile interleaved kernel with its K / V^T tiles staged by LDS-DMA into the padded images (no staging
         // registers: 124 VGPRs, FOUR waves per SIMD) and the score bound -- 1067 / 1082 TF/s at cfg4 / cfg5 level 0 against
@@ -2525,7 +2588,7 @@ int launch_attn(const AttnParams& p, const void* v, hipStream_t st) {
         // A run through the ping-pong kernel: its bank problems in the partial form, then the source branch through the kernel
         // the source-only call takes (the ping-pong kernel's own source problems are a different arithmetic)
         auto run_pp = [&]() -> int {
-            AttnParams pb = p;
+            AttnParams pb = p;   // (never a windowed call: those are no runs)
             pb.part = TF_ATTN_BANK_ONLY;
             const int rc = launch_pp<T, DH, MODE_ALL, 2, true>(pb, st);
             return (rc || bank_only) ? rc : launch_one<T, DH, 1, 4, MODE_SOURCE, 2>(p, st);
@@ -2608,8 +2671,8 @@ int launch_attn(const AttnParams& p, const void* v, hipStream_t st) {
     }
 }
 
-template <typename T>
-int dispatch_dh(int Dh, const AttnParams& p, const void* v, hipStream_t st) {
+template <typename T, typename P>
+int dispatch_dh(int Dh, const P& p, const void* v, hipStream_t st) {
     switch (Dh) {
         case 40: return launch_attn<T, 40>(p, v, st);
         case 64: return launch_attn<T, 64>(p, v, st);
@@ -2707,9 +2770,16 @@ struct SegPart {
     int probe;   // do not launch: return 1 if the segment's own call takes the fused small-problem kernel, else 0
 };
 
+// A call over a sliding-window bank (tf_ext_attn_fwd_windows): the validated table, packed as the kernels read it, and the
+// longest window -- the bank size at which the call picks its kernel forms.
+struct WinPart {
+    const unsigned* win;   // [Kq]: first bank frame | frames << 16
+    int K_max;
+};
+
 int attn_fwd_core(const void* q, const void* k, const void* v, void* out, int K, int Kq, int q_frame0, int S, int H, int Dh,
                   int64_t ld, const int64_t* strides, float scale, int inject, int dtype, void* ws, size_t ws_bytes,
-                  void* stream, const EditsPart* ed, const SegPart* sg = nullptr) {
+                  void* stream, const EditsPart* ed, const SegPart* sg = nullptr, const WinPart* wn = nullptr) {
     TF_ARG(q && k && v && out && ws && strides, TF_ERR_NULL, "tf_ext_attn_fwd: null pointer");
     TF_ARG(dtype == TF_BF16 || dtype == TF_F16, TF_ERR_DTYPE, "tf_ext_attn_fwd: dtype %d (bf16/f16 only)", dtype);
     TF_ARG(Dh == 40 || Dh == 64 || Dh == 80 || Dh == 160, TF_ERR_SHAPE,
@@ -2740,13 +2810,15 @@ int attn_fwd_core(const void* q, const void* k, const void* v, void* out, int K,
         a.q_bs = strides[0], a.q_fs = strides[1], a.ld_q = ld_q;
         a.k_bs = strides[2], a.k_fs = strides[3], a.v_bs = strides[4], a.v_fs = strides[5], a.ld = ld;
         a.o_bs = strides[6], a.o_fs = strides[7];
-        a.H = H, a.Kq = Kq, a.q_frame0 = q_frame0, a.Kb = K;
+        a.H = H, a.Kq = Kq, a.q_frame0 = q_frame0, a.Kb = wn ? wn->K_max : K;   // (windows: planned for the longest window)
         a.b0 = part_bits == TF_ATTN_BANK_ONLY ? 1 : 0;
         a.nb = part_bits == TF_ATTN_BANK_ONLY ? 2 : part_bits == TF_ATTN_SOURCE_ONLY ? 1 : 3;
         const TfFusedPlan plan = tf_attn_fused_plan(&a, 1, S, Dh, dtype, inject);
         if ((ed && ed->probe) || (sg && sg->probe)) return plan.use ? 1 : 0;
+        a.Kb = K;
         if (plan.use)
-            return tf_attn_fused_launch(&a, 1, S, Dh, scale, inject, dtype, plan, reinterpret_cast<hipStream_t>(stream));
+            return tf_attn_fused_launch(&a, 1, S, Dh, scale, inject, dtype, plan, reinterpret_cast<hipStream_t>(stream),
+                                        wn ? wn->win : nullptr);
     }
     const int Spad = ((S + 127) / 128) * 128;
     const int shift = ed ? ed->shift : 0;
@@ -2772,7 +2844,7 @@ int attn_fwd_core(const void* q, const void* k, const void* v, void* out, int K,
     p.part = inject & (TF_ATTN_BANK_ONLY | TF_ATTN_SOURCE_ONLY);
     p.fold = (inject & TF_ATTN_FOLD_SCALE) ? 1 : 0;
     p.out_f32 = (inject & TF_ATTN_OUT_F32) ? 1 : 0;
-    p.nseg = split_plan(K, Kq, S, H, Dh, p.inject != 0, p.part, !(inject & TF_ATTN_NO_SPLIT));
+    p.nseg = split_plan(wn ? wn->K_max : K, Kq, S, H, Dh, p.inject != 0, p.part, !(inject & TF_ATTN_NO_SPLIT));
     p.Kb = Kb;
     if (sg) {   // a keyframe segment: its window of the whole bank's image and norm table
         p.vt = w8 + (size_t)sg->f0 * Spad * 2;
@@ -2797,6 +2869,17 @@ int attn_fwd_core(const void* q, const void* k, const void* v, void* out, int K,
     if (ed) p.no_pack = ed->no_pack, p.mv4 = ed->mv4, p.force_dual = ed->force_dual, p.gap = ed->gap;
     if (sg) p.no_pack = 1;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (wn) {   // the same launches with the window table behind the parameter block
+        // the split form's partial results: the workspace holds the worst case of the K-frame bank and the split is planned for
+        // the longest window, a shorter bank -- checked here rather than assumed (no bank of up to 64 keyframes and no window
+        // length is refused at the shapes swept in tests/test_windows_plan_cpu.py)
+        TF_ARG((size_t)2 * Kq * H * S * p.pslots * (Dh + 8) <= attn_part_elems(K, S, H, Dh), TF_ERR_WORKSPACE,
+               "tf_ext_attn_fwd_windows: %d partial-result slots do not fit the workspace of a %d-frame bank", p.pslots, K);
+        AttnParamsWin pw{};
+        static_cast<AttnParams&>(pw) = p;
+        for (int i = 0; i < Kq; ++i) pw.win[i] = wn->win[i];
+        return dtype == TF_BF16 ? dispatch_dh<BF16>(Dh, pw, v, st) : dispatch_dh<F16>(Dh, pw, v, st);
+    }
     return dtype == TF_BF16 ? dispatch_dh<BF16>(Dh, p, v, st) : dispatch_dh<F16>(Dh, p, v, st);
 }
 
@@ -3596,5 +3679,66 @@ extern "C" int tf_ext_attn_segments_plan(int K, int n_seg, const int* seg_K, int
     tf_plan_rec = nullptr;
     if (rc) return rc;
     TF_ARG(rec.used < len, TF_ERR_WORKSPACE, "tf_ext_attn_segments_plan: the plan needs %zu bytes", rec.used + 1);
+    return rec.n;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Sliding-window keyframe bank (include/tokenflow_hip.h): the uncond / cond branches of query frame i attend to the keys of
+// bank frames [win_lo[i], win_lo[i] + win_n[i]) only.  The launches of tf_ext_attn_fwd_strided for a bank of max_i win_n[i]
+// frames -- ONE pre-pass over the whole bank, ONE bank launch whose problems decode their frame's window from the table in the
+// kernel arguments -- so frame i's result is what its own call (the strided call on its window alone) computes.
+extern "C" int tf_ext_attn_fwd_windows(const void* q, const void* k, const void* v, void* out, int K, int Kq, int q_frame0,
+                                       int S, int H, int Dh, int64_t ld, const int64_t* strides, float scale, int flags,
+                                       int dtype, const int* win_lo, const int* win_n, void* ws, size_t ws_bytes,
+                                       void* stream) {
+    const char* const name = "tf_ext_attn_fwd_windows";
+    TF_ARG(win_lo && win_n, TF_ERR_NULL, "%s: null window table", name);
+    TF_ARG(K > 0 && Kq > 0 && q_frame0 >= 0 && q_frame0 + Kq <= K, TF_ERR_SHAPE,
+           "%s: query frames [%d, %d) outside the %d-frame bank", name, q_frame0, q_frame0 + Kq, K);
+    TF_ARG(Kq <= TF_MAX_WINDOW_FRAMES, TF_ERR_SHAPE, "%s: Kq=%d (at most %d query frames carry a window)", name, Kq,
+           TF_MAX_WINDOW_FRAMES);
+    unsigned win[TF_MAX_WINDOW_FRAMES];
+    int K_max = 0;
+    bool full = true;
+    for (int i = 0; i < Kq; ++i) {
+        const int lo = win_lo[i], n = win_n[i], own = q_frame0 + i;
+        TF_ARG(n >= 1, TF_ERR_SHAPE, "%s: window %d holds %d frames", name, i, n);
+        TF_ARG(lo >= 0 && lo <= K - n && K < (1 << 16), TF_ERR_SHAPE, "%s: window %d = [%d, %d) outside the %d-frame bank", name, i,
+               lo, lo + n, K);
+        TF_ARG(lo <= own && own < lo + n, TF_ERR_SHAPE, "%s: window %d = [%d, %d) does not hold its own frame %d", name, i, lo,
+               lo + n, own);
+        win[i] = (unsigned)lo | ((unsigned)n << 16);
+        K_max = n > K_max ? n : K_max;
+        full = full && lo == 0 && n == K;
+    }
+    constexpr int REFUSED = TF_ATTN_BANK_ONLY | TF_ATTN_SOURCE_ONLY | TF_ATTN_FOLD_SCALE | TF_ATTN_MULTI_V | TF_ATTN_NO_MULTI_V |
+                            TF_ATTN_MULTI_V64 | TF_ATTN_RUN_MULTI_V;
+    TF_ARG(!(flags & REFUSED), TF_ERR_SHAPE,
+           "%s: flags 0x%x -- TF_ATTN_BANK_ONLY / TF_ATTN_SOURCE_ONLY / TF_ATTN_FOLD_SCALE and the multi-edit hints have no "
+           "windowed form", name, flags & REFUSED);
+    if (full)   // every keyframe sees the whole bank: today's call
+        return tf_ext_attn_fwd_strided(q, k, v, out, K, Kq, q_frame0, S, H, Dh, ld, strides, scale, flags, dtype, ws, ws_bytes,
+                                       stream);
+    const WinPart wn{win, K_max};
+    return attn_fwd_core(q, k, v, out, K, Kq, q_frame0, S, H, Dh, ld, strides, scale, flags, dtype, ws, ws_bytes, stream, nullptr,
+                         nullptr, &wn);
+}
+
+// Launch plan of tf_ext_attn_fwd_windows for dense tensors (host only): the entry point itself under the plan recorder.
+extern "C" int tf_ext_attn_windows_plan(int K, int Kq, int q_frame0, int S, int H, int Dh, int flags, int dtype,
+                                        const int* win_lo, const int* win_n, char* buf, size_t len) {
+    TF_ARG(K > 0 && S > 0 && H > 0 && Kq > 0 && Kq <= K, TF_ERR_SHAPE, "tf_ext_attn_windows_plan: K=%d Kq=%d S=%d H=%d", K, Kq, S,
+           H);
+    void* const ph = reinterpret_cast<void*>((uintptr_t)1 << 12);
+    const int64_t ld = (int64_t)H * Dh, fs = (int64_t)S * ld;
+    const int64_t strides[9] = {Kq * fs, fs, K * fs, fs, K * fs, fs, Kq * fs, fs, ld};
+    TfPlanRec rec{buf, len, 0, 0};
+    if (buf && len) buf[0] = 0;
+    tf_plan_rec = &rec;
+    const int rc = tf_ext_attn_fwd_windows(ph, ph, ph, ph, K, Kq, q_frame0, S, H, Dh, ld, strides, 1.0f, flags, dtype, win_lo,
+                                           win_n, ph, tf_ext_attn_workspace_bytes(K, S, H, Dh, dtype), nullptr);
+    tf_plan_rec = nullptr;
+    if (rc) return rc;
+    TF_ARG(rec.used < len, TF_ERR_WORKSPACE, "tf_ext_attn_windows_plan: the plan needs %zu bytes", rec.used + 1);
     return rec.n;
 }

@@ -100,6 +100,19 @@ struct FusedParamsN {
     float lag;
 };
 
+// A one-set launch over a sliding-window bank (tf_ext_attn_fwd_windows): the window table rides behind the parameters.  A
+// type of its own again: every other launch keeps its parameter block and its code.
+struct FusedParamsWin {
+    static constexpr int MAX_SETS = 1;
+    FusedSet set[MAX_SETS];
+    int n_sets, S, nQT, tpf;
+    unsigned tpf_magic;
+    int inject, out_f32;
+    float c;
+    float lag;
+    unsigned win[TF_MAX_WINDOW_FRAMES];   // query frame i: first bank frame of its window | frames << 16
+};
+
 __device__ __forceinline__ float max_xor32(float x) {
     const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
     return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
@@ -133,7 +146,7 @@ __device__ __forceinline__ Problem decode_problem(const P& p) {
             u -= p.set[0].n_wg;
             pr.si = 1;
         }
-    } else {
+    } else if constexpr (P::MAX_SETS > 2) {
         // workgroup-uniform walk over the sets (scalar loads from the kernel argument segment)
         for (int n = p.set[0].n_wg; pr.si + 1 < p.n_sets && u >= n; n = p.set[pr.si].n_wg) u -= n, ++pr.si;
     }
@@ -150,6 +163,12 @@ __device__ __forceinline__ Problem decode_problem(const P& p) {
     pr.bq = (inject && pr.b > 0) ? 0 : pr.b;   // branch whose q and k are used (tokenflow_utils.py:124-130)
     pr.f_lo = pr.b == 0 ? st.q_frame0 + pr.f : 0;
     pr.n_fr = pr.b == 0 ? 1 : st.Kb;
+    if constexpr (std::is_same<P, FusedParamsWin>::value) {   // a bank problem reads its query frame's window
+        if (pr.b > 0) {
+            const unsigned w = p.win[pr.f];
+            pr.f_lo = (int)(w & 0xffffu), pr.n_fr = (int)(w >> 16);
+        }
+    }
     return pr;
 }
 
@@ -628,6 +647,7 @@ __global__ __launch_bounds__(64 * KW, 1) void ext_attn_fused_wp_kernel(P p) {
 template <typename P>
 bool fused_note(const P& p, int qw, int kw, int qb, int prec) {
     if (p.n_sets > 2 || tf_plan_sets_note) return tf_plan_note("fused[qw=%d,kw=%d,qb=%d,prec=%d,sets=%d]", qw, kw, qb, prec, p.n_sets);
+    if (std::is_same<P, FusedParamsWin>::value) return tf_plan_note("fused[qw=%d,kw=%d,qb=%d,prec=%d,win]", qw, kw, qb, prec);
     return tf_plan_note("fused[qw=%d,kw=%d,qb=%d,prec=%d]", qw, kw, qb, prec);
 }
 
@@ -760,8 +780,10 @@ TfFusedPlan tf_attn_fused_plan(const TfAttnSet* sets, int n_sets, int S, int Dh,
 
 template <typename P>
 static int fused_launch_sets(const TfAttnSet* sets, int n_sets, int S, int Dh, float scale, int flags, int dtype,
-                             const TfFusedPlan& plan, int inject0, hipStream_t st) {
+                             const TfFusedPlan& plan, int inject0, hipStream_t st, const unsigned* win = nullptr) {
     P p{};
+    if constexpr (std::is_same<P, FusedParamsWin>::value)
+        for (int i = 0; i < sets[0].Kq; ++i) p.win[i] = win[i];
     p.n_sets = n_sets;
     p.S = S;
     p.nQT = (S + 32 * plan.qw * plan.qb - 1) / (32 * plan.qw * plan.qb);
@@ -795,8 +817,14 @@ static int fused_launch_sets(const TfAttnSet* sets, int n_sets, int S, int Dh, f
 }
 
 int tf_attn_fused_launch(const TfAttnSet* sets, int n_sets, int S, int Dh, float scale, int flags, int dtype,
-                         const TfFusedPlan& plan, hipStream_t st) {
+                         const TfFusedPlan& plan, hipStream_t st, const unsigned* win) {
     TF_ARG(sets && n_sets >= 1 && n_sets <= 1 + TF_MAX_EDITS, TF_ERR_SHAPE, "tf_ext_attn_fwd(fused): %d tensor sets", n_sets);
+    if (win) {
+        TF_ARG(n_sets == 1 && sets[0].Kq <= TF_MAX_WINDOW_FRAMES, TF_ERR_SHAPE,
+               "tf_ext_attn_fwd(fused): a window table serves one set of at most %d query frames", TF_MAX_WINDOW_FRAMES);
+        const int inj = ((flags & TF_ATTN_INJECT) || sets[0].inject) ? 1 : 0;
+        return fused_launch_sets<FusedParamsWin>(sets, 1, S, Dh, scale, flags, dtype, plan, inj, st, win);
+    }
     // a set injects under TF_ATTN_INJECT of `flags` or its own `inject`.  One or two sets whose bank branches agree take
     // the kernels with the launch-wide flag (today's launches exactly); anything else the per-set form
     int inj = -1;

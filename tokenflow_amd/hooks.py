@@ -40,6 +40,7 @@ __all__ = [
     "register_conv_injection", "register_extended_attention_pnp", "register_extended_attention",
     "make_tokenflow_attention_block", "set_tokenflow", "isinstance_str", "batch_cosine_sim",
     "register_frame_shard", "join_frame_shard", "register_edits", "register_segments",
+    "register_bank_window",
 ]
 
 
@@ -246,6 +247,56 @@ def _segments(module, K=None):
     if K is not None and sum(segs) != K:
         raise ValueError(f"register_segments: the segments {list(segs)} hold {sum(segs)} keyframes, the pivotal pass {K}")
     return segs
+
+
+def register_bank_window(model, radius):
+    """Sliding-window keyframe bank (no counterpart in the reference, where every keyframe attends to the whole bank): in the
+    pivotal passes that follow, the uncond / cond branches of keyframe i attend to the keyframes i - radius .. i + radius only
+    (clamped to the bank; `ops.bank_windows`), the source branch to its own frame as always.  Consistency stays chained along
+    the clip through the overlapping windows, and the pass costs O(K * radius) frame-banks instead of K * K.  This CHANGES
+    THE RESULT relative to TokenFlow and is opt-in.  Sets `bank_window` where `register_segments` sets its state: on the 16
+    blocks and their `attn1`; both attention installers then call `ops.ext_attn_windows` whenever radius < K - 1.
+    `None`, or a radius >= K - 1 (every window is the whole bank), issues exactly today's ops: the reference computation.
+    Propagation is untouched: chunk c still blends keyframes c and c - 1.
+    Not generalised, ValueError at the call: `register_edits(model, E > 1)`, `register_segments` with several segments, a
+    registered frame shard -- there the radius is held against the shard's WHOLE bank (`shard.K`), not the rank's local
+    keyframes, and only a radius that covers it passes (INTEGRATION.md section 6 shows the driver side)."""
+    if radius is not None:
+        radius = int(radius)
+        if radius < 0:
+            raise ValueError(f"register_bank_window: radius={radius} (>= 0, or None for the whole bank)")
+    _set_bank_window(_hook_blocks(model.unet), radius)
+
+
+def _set_bank_window(blocks, radius):
+    """`bank_window` on transformer blocks and their `attn1` (register_bank_window; tools on a bare block list)."""
+    for tb in blocks:
+        setattr(tb, "bank_window", radius)
+        setattr(tb.attn1, "bank_window", radius)
+
+
+def _bank_window(module, K: int):
+    """The window radius of the pivotal pass of K keyframes a module sees (register_bank_window), or None = the whole bank;
+    the combinations that are not generalised raise.  On a registered frame shard the pass carries the rank's LOCAL keyframes:
+    the radius is held against the shard's whole bank (`shard.K`), and refused where that is not known."""
+    radius = getattr(module, "bank_window", None)
+    if radius is None:
+        return None
+    shard = _active_shard(module)   # the predicate of the attention path: a world-1 shard is the unsharded pass
+    if shard is not None:
+        K_all = getattr(shard, "K", None)
+        if K_all is None or radius < int(K_all) - 1:
+            raise ValueError("register_bank_window: a sliding-window bank on a registered frame shard is not supported")
+        return None
+    if radius >= K - 1:
+        return None
+    if int(getattr(module, "n_edits", 1)) > 1:
+        raise ValueError("register_bank_window: a sliding-window bank in a multi-edit batch (register_edits, n_edits > 1) is "
+                         "not supported")
+    if getattr(module, "keyframe_segments", None) is not None:
+        raise ValueError("register_bank_window: a sliding-window bank in a pass of several keyframe segments "
+                         "(register_segments) is not supported")
+    return radius
 
 
 _latents_cache = collections.OrderedDict()
@@ -481,6 +532,8 @@ def _make_sa_forward(self, pnp: bool):
                 q, k, v = q.to(cdt), k.to(cdt), v.to(cdt)
         shard = None if is_cross else _active_shard(self)
         E = 1 if is_cross else _n_edits(self)
+        # (a window excludes edits, segments and shards; the pass carries q.shape[0] / (1 + 2E) keyframes)
+        radius = None if is_cross else _bank_window(self, q.shape[0] // (1 + 2 * E))
         segs = None if is_cross else _segments(self, q.shape[0] // 3)
         # the edits that inject (one shared schedule: all or none; register_edit_schedules: each edit's own)
         mask = _inject_mask(self, E) if pnp else 0
@@ -491,6 +544,8 @@ def _make_sa_forward(self, pnp: bool):
                 out = shard.pivotal_attention(q, k, v, self.heads, self.scale, False, n_edits=E, inject_mask=mask)
             else:
                 out = shard.pivotal_attention(q, k, v, self.heads, self.scale, inject)
+        elif radius is not None:  # long videos: a bank branch attends to the neighbouring keyframes only
+            out = ops.ext_attn_windows(q, k, v, self.heads, self.scale, inject, ops.bank_windows(q.shape[0] // 3, radius))
         elif segs is not None:    # several scenes or clips: a bank branch attends to the keyframes of its own segment
             out = ops.ext_attn_segments(q, k, v, self.heads, self.scale, inject, segs)
         elif E == 1:
@@ -704,6 +759,8 @@ def make_tokenflow_attention_block(block_class: Type[torch.nn.Module]) -> Type[t
                 if batch_size % nbr:
                     raise ValueError(f"register_edits: batch of {batch_size} does not hold {nbr} branches ({E} edits)")
             n_frames = batch_size // nbr
+            if self.pivotal_pass:
+                _bank_window(self, n_frames)   # register_bank_window: the combinations that are not generalised raise here
             hidden_states = hidden_states.view(nbr, n_frames, sequence_length, dim)
 
             norm_inv = None

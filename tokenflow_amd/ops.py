@@ -215,6 +215,41 @@ def attn_segments_plan(K: int, segments: Sequence[int], S: int, heads: int, dh: 
                         flags, _DT[dtype])
 
 
+def bank_windows(K: int, radius: int) -> list:
+    """The clamped symmetric windows of a sliding-window bank: keyframe i attends to the keyframes max(0, i - radius) ..
+    min(K - 1, i + radius), as [(first frame, frames)] per keyframe.  radius >= K - 1 gives K full windows."""
+    K, R = int(K), int(radius)
+    if K < 1 or R < 0:
+        raise ValueError(f"bank_windows: K={K} radius={R} (K >= 1, radius >= 0)")
+    return [(max(0, i - R), min(K - 1, i + R) - max(0, i - R) + 1) for i in range(K)]
+
+
+def _windows(what: str, windows, K: int, Kq: int, q_frame0: int = 0):
+    """The window table of a call as two ctypes int arrays (first frames, frame counts): one window per query frame, inside
+    the bank, holding its own frame."""
+    win = [(int(lo), int(n)) for lo, n in windows]
+    if len(win) != Kq or not 1 <= Kq <= _lib.TF_MAX_WINDOW_FRAMES:
+        raise ValueError(f"{what}: {len(win)} windows for {Kq} query frames (one each, at most {_lib.TF_MAX_WINDOW_FRAMES})")
+    for i, (lo, n) in enumerate(win):
+        if n < 1 or lo < 0 or lo + n > K:
+            raise ValueError(f"{what}: window {i} = [{lo}, {lo + n}) (>= 1 frames inside the {K}-frame bank)")
+        if not lo <= q_frame0 + i < lo + n:
+            raise ValueError(f"{what}: window {i} = [{lo}, {lo + n}) does not hold its own frame {q_frame0 + i}")
+    return (ctypes.c_int * Kq)(*[w[0] for w in win]), (ctypes.c_int * Kq)(*[w[1] for w in win])
+
+
+def attn_windows_plan(K: int, windows, S: int, heads: int, dh: int, inject: bool, dtype: torch.dtype = torch.bfloat16,
+                      out_dtype: Optional[torch.dtype] = None, no_split: Optional[bool] = None,
+                      fused: Optional[bool] = None, hints: int = 0) -> list:
+    """The launches `ext_attn_windows` makes for dense [3K,S,heads*dh] tensors, as tokens (tf_ext_attn_windows_plan: the
+    tokens of `attn_plan` with ',win' appended to the windowed launch, e.g. ['vt_pack', 'il<40,8,ALL,4,2>,win'] or
+    ['fused[qw=1,kw=4,qb=1,prec=1,win]']; K full windows give `attn_plan(K, K, ...)`).  Host only: needs no GPU."""
+    lo, n = _windows("attn_windows_plan", windows, K, K)
+    flags = _attn_flags(inject, "all", out_dtype == torch.float32, False, no_split, fused, hints)
+    return _plan_tokens("tf_ext_attn_windows_plan", _lib.load().tf_ext_attn_windows_plan, K, K, 0, S, heads, dh, flags,
+                        _DT[dtype], ctypes.cast(lo, ctypes.c_void_p), ctypes.cast(n, ctypes.c_void_p))
+
+
 def _single_mask(what: str, mask, C: int) -> int:
     m = int(mask)
     if not 1 <= C <= 64 or m < 0 or m >> C:
@@ -332,6 +367,58 @@ def ext_attn_segments(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: 
     ws = _workspace(lib.tf_ext_attn_segments_workspace_bytes(K, S, heads, dh, dt), q.device)
     _launch(dev, "tf_ext_attn_fwd_segments", lib.tf_ext_attn_fwd_segments, q.data_ptr(), k.data_ptr(), v.data_ptr(),
             out.data_ptr(), K, len(seg), seg, S, heads, dh, ld, float(scale), flags, dt, ws.data_ptr(), ws.numel())
+    return out
+
+
+def ext_attn_windows(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, scale: float, inject: bool, windows, *,
+                     no_split: Optional[bool] = None, fused: Optional[bool] = None, hints: int = 0,
+                     out_dtype: Optional[torch.dtype] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`ext_attn` over a sliding-window keyframe bank (tf_ext_attn_fwd_windows): q, k, v [3K,S,D] as there, `windows` one
+    (first frame, frames) pair per keyframe (`bank_windows(K, radius)`).  The uncond / cond branches of keyframe i attend to
+    the keys of the keyframes of window i only -- under `inject` with the source's q and k -- and the source branch to its own
+    frame.  NOT TokenFlow's computation unless every window is the whole bank (then the call is `ext_attn`, bit for bit):
+    an opt-in whose cost grows with the window, not with the bank.  One launch for all keyframes; keyframe i's slices are
+    what `ext_attn` computes on window i's tensors alone (Kq = 1), bit for bit under no_split wherever both take the same
+    kernel form.  Arguments as `ext_attn` (no `part`, no q_frame0, no folded scale)."""
+    dev = _need_gpu(q, k, v, out)
+    lib = _lib.load()
+    B, S, D = k.shape
+    if B % 3 or D % heads or q.shape != k.shape or v.shape != k.shape:
+        raise ValueError(f"ext_attn_windows: bad shapes q{tuple(q.shape)} k{tuple(k.shape)} v{tuple(v.shape)} heads {heads}")
+    K, dh = B // 3, D // heads
+    lo, n = _windows("ext_attn_windows", windows, K, K)
+    dt = _DT.get(q.dtype)
+    if dt is None or dt == _lib.TF_F32 or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise TypeError(f"ext_attn_windows: q/k/v must share dtype bf16 or f16, got {q.dtype},{k.dtype},{v.dtype}")
+
+    def rows(t):
+        if t.stride(-1) != 1 or t.stride(0) != S * t.stride(1):
+            t = t.contiguous()
+        return t
+    q, k, v = rows(q), rows(k), rows(v)
+    ld = q.stride(1)
+    if k.stride(1) != ld or v.stride(1) != ld:
+        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        ld = D
+    if out_dtype is None:
+        out_dtype = out.dtype if out is not None else q.dtype
+    if out_dtype not in (q.dtype, torch.float32):
+        raise TypeError(f"ext_attn_windows: out_dtype {out_dtype} (the input dtype or float32)")
+    if out is None:
+        out = torch.empty(B, S, D, dtype=out_dtype, device=q.device)
+    elif out.dtype != out_dtype or not out.is_contiguous() or out.shape != (B, S, D):
+        raise ValueError("ext_attn_windows: `out` must be a contiguous [3K,S,D] tensor of out_dtype")
+    flags = _attn_flags(inject, "all", out_dtype == torch.float32, False, no_split, fused, hints)
+    key = (K, S, heads, dh, dt)
+    nbytes = _attn_ws_bytes.get(key)
+    if nbytes is None:
+        nbytes = _attn_ws_bytes[key] = lib.tf_ext_attn_workspace_bytes(K, S, heads, dh, dt)
+    ws = _workspace(nbytes, q.device)
+    fs, ofs = S * ld, S * D   # dense [3, K, S, ld] tensors, out [3, K, S, D]
+    strides = (ctypes.c_int64 * 9)(K * fs, fs, K * fs, fs, K * fs, fs, K * ofs, ofs, ld)
+    _launch(dev, "tf_ext_attn_fwd_windows", lib.tf_ext_attn_fwd_windows, q.data_ptr(), k.data_ptr(), v.data_ptr(),
+            out.data_ptr(), K, K, 0, S, heads, dh, ld, ctypes.cast(strides, ctypes.c_void_p), float(scale), flags, dt,
+            ctypes.cast(lo, ctypes.c_void_p), ctypes.cast(n, ctypes.c_void_p), ws.data_ptr(), ws.numel())
     return out
 
 
