@@ -11,6 +11,7 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+from tests.nn_families import spread_pivots
 from tests.test_sharded_gpu import _attn_oracle_bound, _free_port
 
 pytestmark = pytest.mark.gpu
@@ -38,7 +39,7 @@ def _worker(rank, world, port, K, h, inject, ret):
         scale = d ** -0.5
         g = torch.Generator().manual_seed(0)
         q, k, v = (torch.randn(3 * K, S, D, generator=g).bfloat16().cuda() for _ in range(3))
-        piv = torch.nn.functional.layer_norm(torch.randn(K, S, D, generator=g), (D,)).bfloat16().cuda()
+        piv = spread_pivots(K, S, D, torch.bfloat16, g)[0].cuda()      # row norms differ: a misplaced inv_norm shows
         inv = ops.pivot_inv_norm(piv)
         comm, halo_comm = gloo_comm(rank, world), gloo_comm(rank, world)
         sh = sharded.NativeShard(K, comm, halo_comm)

@@ -16,6 +16,7 @@ import torch
 
 from oracle import tokenflow_oracle as orc
 from tests import edit_forms as ef
+from tests import nn_families as nf
 from tests.test_kernels_gpu import assert_attn_close, attn_bound, attn_ref
 
 pytestmark = pytest.mark.gpu
@@ -37,7 +38,7 @@ def _prop_inputs(K, n, S, D, C, E, res_dtype, seed):
     B = 1 + 2 * E
     g = torch.Generator(device="cuda").manual_seed(seed)
     ln = torch.nn.LayerNorm(D, elementwise_affine=False)
-    piv = ln(torch.randn(K, S, D, generator=g, device="cuda")).bfloat16()
+    piv = nf.spread_pivots(K, S, D, torch.bfloat16, g)[0]      # row norms differ: a misplaced inv_norm changes the indices
     tgt = ln(torch.randn(C * n * S, D, generator=g, device="cuda")).bfloat16()
     kf = torch.randn(B * K, S, D, generator=g, device="cuda").bfloat16()
     res = torch.randn(B * C * n, S, D, generator=g, device="cuda").to(res_dtype)

@@ -212,7 +212,8 @@ def _nn_inputs(K, n_all, S, D, dtype, seed, same_slot):
 
 
 def _check_nn(idx, tgt, piv, slot, rows, planted):
-    """idx [rows] for targets `rows` against keyframe `slot`: tie-aware against the fp32 oracle; planted rows exact."""
+    """idx [rows] for targets `rows` against keyframe `slot`: tie-aware against the fp32 oracle; planted rows exact.
+    Returns the oracle's similarity matrix of the checked rows."""
     t = tgt[rows].float().cpu()
     sim = orc.batch_cosine_sim(t, piv[slot].float().cpu())
     got = idx.cpu().long()
@@ -221,6 +222,28 @@ def _check_nn(idx, tgt, piv, slot, rows, planted):
     assert bad == 0, f"slot {slot}: {bad} of {len(rows)} rows differ beyond a near-tie ({diff} differ at all)"
     for r, want in planted.items():
         assert int(got[r]) == want, f"slot {slot}: planted target {r} -> {int(got[r])}, the first index is {want}"
+    return sim
+
+
+def _sampled(c):
+    """The largest launches are checked on sampled targets (the oracle's similarity matrix is on the CPU)."""
+    return c["n_tgt"] * c["C"] * c["S"] * c["D"] * c["P"] > 4e10
+
+
+def _rows_single(n_tgt, sampled):
+    """The checked targets of a C = 1 case: all of them, or 2048 random ones and the last 512 (ragged panel, planted rows)."""
+    if not sampled:
+        return torch.arange(n_tgt)
+    return torch.cat([torch.randint(0, n_tgt - 512, (2048,), generator=torch.Generator().manual_seed(1)),
+                      torch.arange(n_tgt - 512, n_tgt)])
+
+
+def _rows_chunk(j, n_tgt, sampled):
+    """The checked targets of chunk j of a C > 1 case: all of them, or 512 random ones and the last 512."""
+    if not sampled:
+        return torch.arange(j * n_tgt, (j + 1) * n_tgt)
+    return torch.cat([torch.randint(j * n_tgt, (j + 1) * n_tgt - 512, (512,), generator=torch.Generator().manual_seed(j)),
+                      torch.arange((j + 1) * n_tgt - 512, (j + 1) * n_tgt)])
 
 
 def _plant(tgt, piv, slot, rows_base, S):
@@ -239,7 +262,7 @@ def test_nn_form_vs_oracle(form, i, dtype):
     c = kf.CASES[form][i]
     assert form in [kf.form(t) for t in kf.plan(ops, c)]
     n_tgt, S, D, P, C = c["n_tgt"], c["S"], c["D"], c["P"], c["C"]
-    sampled = n_tgt * C * S * D * P > 4e10
+    sampled = _sampled(c)
     npl = len(_tie_pairs(S))
     if C == 1:
         K = 2
@@ -247,10 +270,7 @@ def test_nn_form_vs_oracle(form, i, dtype):
         ids = [1, 0] if P == 2 else [1]
         planted = _plant(tgt, piv, 1, n_tgt - npl, S)          # the ragged last target panel, where there is one
         idx = ops.nn_search(tgt, piv, ops.pivot_inv_norm(piv), ids)
-        rows = torch.arange(n_tgt)
-        if sampled:
-            rows = torch.cat([torch.randint(0, n_tgt - 512, (2048,), generator=torch.Generator().manual_seed(1)),
-                              torch.arange(n_tgt - 512, n_tgt)])
+        rows = _rows_single(n_tgt, sampled)
         base = len(rows) - npl
         _check_nn(idx[0][rows.cuda()], tgt, piv, 1, rows.cuda(), {base + j: a for j, a in planted.items()})
         if P == 2:
@@ -273,11 +293,7 @@ def test_nn_form_vs_oracle(form, i, dtype):
         out = ops.propagate_chunks(tgt, piv, inv, kf_out, w, n, C, 0, True, None, torch.float32)
         res[wv] = out.view(3, C, n_tgt, D)[0, :, :, 0].round().long()
     for j in range(C):
-        rows = torch.arange(j * n_tgt, (j + 1) * n_tgt)
-        if sampled:
-            rows = torch.cat([torch.randint(j * n_tgt, (j + 1) * n_tgt - 512, (512,),
-                                            generator=torch.Generator().manual_seed(j)),
-                              torch.arange((j + 1) * n_tgt - 512, (j + 1) * n_tgt)])
+        rows = _rows_chunk(j, n_tgt, sampled)
         loc = (rows - j * n_tgt).cuda()
         base = len(rows) - npl
         for wv, slot in ((1.0, j), (0.0, j - 1)):

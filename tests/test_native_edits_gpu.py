@@ -14,6 +14,7 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+from tests.nn_families import spread_pivots
 from tests.test_sharded_gpu import _free_port
 
 pytestmark = pytest.mark.gpu
@@ -39,7 +40,7 @@ def _data(K, E, mask, S, h, d, n):
     B, D = 1 + 2 * E, h * d
     g = torch.Generator().manual_seed(E * 16 + mask)
     q, k, v = (torch.randn(B * K, S, D, generator=g).bfloat16().cuda() for _ in range(3))
-    piv = torch.nn.functional.layer_norm(torch.randn(K, S, D, generator=g), (D,)).bfloat16().cuda()
+    piv = spread_pivots(K, S, D, torch.bfloat16, g)[0].cuda()      # row norms differ: a misplaced inv_norm shows
     tgt = [(piv[c].float()[torch.randperm(S, generator=g).cuda()].repeat(n, 1)
             + 0.1 * torch.randn(n * S, D, generator=g).cuda()).bfloat16() for c in range(K)]
     res = [torch.randn(B * n, S, D, generator=g).bfloat16().cuda() for _ in range(K)]

@@ -20,6 +20,7 @@ import tokenflow_utils as tfu
 from oracle import golden_cases as gc
 from oracle import tokenflow_oracle as orc
 from tests import fake_diffusers as fd
+from tests import nn_families as nf
 from tests.test_kernels_gpu import NN_TAU, assert_attn_close, attn_ref
 from tokenflow_amd import _lib, hooks
 
@@ -145,7 +146,7 @@ def _groups(mask, C):
 def _prop_inputs(K, S, D, C, dtype, seed):
     g = torch.Generator(device="cuda").manual_seed(seed)
     ln = torch.nn.LayerNorm(D, elementwise_affine=False)
-    piv = ln(torch.randn(K, S, D, generator=g, device="cuda")).to(dtype)
+    piv = nf.spread_pivots(K, S, D, dtype, g)[0]               # row norms differ: a misplaced inv_norm changes the indices
     tgt = ln(torch.randn(C * N_PROP * S, D, generator=g, device="cuda")).to(dtype)
     kf = torch.randn(3 * K, S, D, generator=g, device="cuda").to(dtype)
     res = torch.randn(3 * C * N_PROP, S, D, generator=g, device="cuda").to(dtype)

@@ -14,6 +14,7 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+from tests.nn_families import spread_pivots
 from tests.test_bank_runs_gpu import _runs_of
 from tests.test_shard_edit_runs_gpu import TIMEOUT, _nan_fill
 from tests.test_sharded_gpu import _free_port
@@ -34,7 +35,7 @@ def _worker(rank, world, port, K, h, S, d, E, masks, ret):
         scale = d ** -0.5
         g = torch.Generator().manual_seed(11 + K + S)
         q, k, v = (torch.randn(B * K, S, D, generator=g).bfloat16().cuda() for _ in range(3))
-        piv = torch.nn.functional.layer_norm(torch.randn(K, S, D, generator=g), (D,)).bfloat16().cuda()
+        piv = spread_pivots(K, S, D, torch.bfloat16, g)[0].cuda()      # row norms differ: a misplaced inv_norm shows
         comm, halo_comm = gloo_comm(rank, world), gloo_comm(rank, world)
         shards = {
             ("native", True): sharded.NativeEditShard(K, comm, halo_comm, edit_runs=True, edit_runs_multi_v=True),

@@ -13,6 +13,8 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+from tests.nn_families import spread_pivots
+
 pytestmark = pytest.mark.gpu
 
 
@@ -58,7 +60,7 @@ def _worker(rank, world, port, K, inject, mode, no_split, ret, backend="gloo"):
         h_ = h
         g = torch.Generator().manual_seed(0)
         q, k, v = (torch.randn(3 * K, S, D, generator=g).bfloat16().cuda() for _ in range(3))
-        piv = torch.nn.functional.layer_norm(torch.randn(K, S, D, generator=g), (D,)).bfloat16().cuda()
+        piv = spread_pivots(K, S, D, torch.bfloat16, g)[0].cuda()      # row norms differ: a misplaced inv_norm shows
         tgt = [(piv[c].float()[torch.randperm(S, generator=g).cuda()].repeat(n, 1)
                 + 0.1 * torch.randn(n * S, D, generator=g).cuda()).bfloat16() for c in range(K)]
         res = [torch.randn(3 * n, S, D, generator=g).bfloat16().cuda() for _ in range(K)]
@@ -311,7 +313,7 @@ def _native_worker(rank, world, port, K, h, inject, mode, split, ret):
         D = h * d
         g = torch.Generator().manual_seed(0)
         q, k, v = (torch.randn(3 * K, S, D, generator=g).bfloat16().cuda() for _ in range(3))
-        piv = torch.nn.functional.layer_norm(torch.randn(K, S, D, generator=g), (D,)).bfloat16().cuda()
+        piv = spread_pivots(K, S, D, torch.bfloat16, g)[0].cuda()      # row norms differ: a misplaced inv_norm shows
         tgt = [(piv[c].float()[torch.randperm(S, generator=g).cuda()].repeat(n, 1)
                 + 0.1 * torch.randn(n * S, D, generator=g).cuda()).bfloat16() for c in range(K)]
         res = [torch.randn(3 * n, S, D, generator=g).bfloat16().cuda() for _ in range(K)]
