@@ -1,6 +1,8 @@
 #!/bin/bash
 # Build A/B variants of libtokenflow_hip.so into build/variants/ (travels to the GPU box; not tracked).
 # usage: tools/build_variants.sh name "-DTF_TUNE_X=1 ..." [name2 "flags2" ...]
+# (compile-time switches live in nn_search.hip, ext_attn_fused.hip and layer_norm.hip; ext_attn.hip and its attn_*.h headers
+# have none -- their A/B history is in profiles/README.md.  An empty flag string builds the working tree as it is.)
 # The variant-independent objects come from the regular in-tree build (made up to date first).  RELINK=1: keep a variant's
 # existing objects and only link again (after a change to one of the variant-independent files).
 set -e

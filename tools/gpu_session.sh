@@ -10,9 +10,6 @@ for stage in "$@"; do
   echo "=== stage $stage $(date +%T)"
   case $stage in
     seam)       timeout 900 python -m pytest tests/test_driver_seam.py tests/test_fullsize_gpu.py -m gpu -q --tb=short -p no:cacheprovider -s -k "driver or iid" 2>&1 | grep -v "^$" | tail -40 > $O/seam_tests.txt; grep -i "driver seam\|iid:\|passed\|failed\|Error\|assert" $O/seam_tests.txt | cut -c1-260 ;;
-    il64ab)     for lib in "" il64_4_3 il64_8_4 il64_8_3; do echo "== lib=${lib:-default}" | tee -a $O/attn_il64_ab.txt
-                  TOKENFLOW_HIP_LIB=${lib:+build/variants/lib_$lib.so} timeout 300 python tools/attn_microbench.py 10,9216,5,64 25,4096,5,64 10,2304,10,64 25,1024,10,64 2>/dev/null | tee -a $O/attn_il64_ab.txt; done
-                TOKENFLOW_HIP_LIB=build/variants/lib_il64_4_3.so timeout 600 python -m pytest tests/test_kernels_gpu.py tests/test_baseline_configs_gpu.py -q --tb=line -p no:cacheprovider -k "64 or cfg4 or cfg5" 2>&1 | tail -5 | tee -a $O/attn_il64_ab.txt ;;
     nosplitab)  for ns in 0 1; do echo "== TOKENFLOW_ATTN_NO_SPLIT=$ns" | tee -a $O/attn_nosplit_ab.txt
                   TOKENFLOW_ATTN_NO_SPLIT=$ns timeout 300 python tools/attn_microbench.py 8,256,8,160 8,64,8,160 4,256,8,80 4,64,8,160 10,144,20,64 2>/dev/null | tee -a $O/attn_nosplit_ab.txt; done ;;
     pmc40)      # instruction-level accounting of the level-0 kernel (no ATT decoder in this image: SQ counters, separate passes)
@@ -20,19 +17,10 @@ for stage in "$@"; do
                   rm -rf /tmp/p40; ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --pmc $grp -d /tmp/p40 -- python $GRAFT_REPO_ROOT/tools/attn_microbench.py 8,4096,8,40 > /dev/null 2>>$GRAFT_REPO_ROOT/$O/pmc40.err )
                   DB=$(find /tmp/p40 -name "*_results.db" | head -1); [ -n "$DB" ] && python tools/rocpd_pmc.py $DB | grep "il_kernel<BF16; 40; 8; 0\|^kernel" >> $O/pmc_l0_accounting.csv; done
                 cut -c1-60,100-220 $O/pmc_l0_accounting.csv ;;
-    r6ab)       # round 6: d = 64 / 40 / 80 streaming attention variants (tools/build_variants.sh), one process per library
-                for lib in base "" il64a il64b il64c il64e base "" il64a; do echo "== lib=${lib:-default}" | tee -a $O/attn_d64_ab.txt
-                  TOKENFLOW_HIP_LIB=${lib:+build/variants/lib_$lib.so} timeout 300 python tools/attn_microbench.py 10,9216,5,64 25,4096,5,64 10,2304,10,64 25,1024,10,64 2>/dev/null | grep "inject=0" | tee -a $O/attn_d64_ab.txt; done
-                for lib in "" il40p "" il40p; do echo "== lib=${lib:-default}" | tee -a $O/attn_d40_dma2_ab.txt
-                  TOKENFLOW_HIP_LIB=${lib:+build/variants/lib_$lib.so} timeout 300 python tools/attn_microbench.py 8,4096,8,40 4,1024,8,40 2>/dev/null | grep "inject=0" | tee -a $O/attn_d40_dma2_ab.txt; done
-                for lib in "" il80a il80b "" il80a il80b; do echo "== lib=${lib:-default}" | tee -a $O/attn_d80_dma2_ab.txt
-                  TOKENFLOW_HIP_LIB=${lib:+build/variants/lib_$lib.so} timeout 300 python tools/attn_microbench.py 8,1024,8,80 4,256,8,80 2>/dev/null | grep "inject=0" | tee -a $O/attn_d80_dma2_ab.txt; done ;;
-    r6abtests)  for lib in ${R6_TEST_LIBS:-"" il64a}; do echo "== lib=${lib:-default}" | tee -a $O/attn_variant_tests.txt
-                  TOKENFLOW_HIP_LIB=${lib:+build/variants/lib_$lib.so} timeout 900 python -m pytest tests/test_kernels_gpu.py tests/test_baseline_configs_gpu.py tests/test_fullsize_gpu.py -q --tb=line -p no:cacheprovider -k "attn or cfg4 or cfg5 or cfg2" 2>&1 | tail -6 | tee -a $O/attn_variant_tests.txt; done ;;
     pmc64)      # instruction-level accounting of the d = 64 level-0 kernel at cfg4; PMC64_LIB selects the build
                 for grp in "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_SCA" "SQ_WAIT_INST_LDS SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_WAVE_CYCLES" "SQ_INST_CYCLES_VMEM_RD SQ_INST_LEVEL_LDS SQ_INST_LEVEL_VMEM SQ_ACTIVE_INST_ANY" "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_COEXEC_CYCLES SQ_THREAD_CYCLES_VALU" "SQ_INSTS_VALU_TRANS_F32 SQ_INSTS_VALU_CVT SQ_INSTS_VALU_FMA_F32 SQ_INSTS_VALU_MUL_F32" "SQ_INSTS_VALU_ADD_F32 SQ_INSTS_SALU SQ_INSTS_SMEM SQ_IFETCH" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_LDS_DATA_FIFO_FULL SQ_LDS_CMD_FIFO_FULL" "SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_VALU_INT32" "SQ_ACTIVE_INST_MISC SQ_ACTIVE_INST_VALU2 SQ_BUSY_CU_CYCLES SQ_WAVES"; do
                   rm -rf /tmp/p64; ( cd /tmp && TOKENFLOW_HIP_LIB=${PMC64_LIB:+$GRAFT_REPO_ROOT/build/variants/lib_$PMC64_LIB.so} timeout 300 rocprofv3 --kernel-trace --pmc $grp -d /tmp/p64 -- python $GRAFT_REPO_ROOT/tools/attn_microbench.py 10,9216,5,64 > /dev/null 2>>$GRAFT_REPO_ROOT/$O/pmc64.err )
-                  DB=$(find /tmp/p64 -name "*_results.db" | head -1); [ -n "$DB" ] && python tools/rocpd_pmc.py $DB | grep "pp_kernel<BF16; 64; 0\|il_kernel<BF16; 64; [48]; 0\|^kernel" >> $O/pmc_d64_${PMC64_LIB:-default}.csv; done
+                  DB=$(find /tmp/p64 -name "*_results.db" | head -1); [ -n "$DB" ] && python tools/rocpd_pmc.py $DB | grep "pp_kernel<BF16;\|il_kernel<BF16; 64; [48]; 0\|^kernel" >> $O/pmc_d64_${PMC64_LIB:-default}.csv; done
                 cut -c1-60,100-220 $O/pmc_d64_${PMC64_LIB:-default}.csv ;;
     tailsplit)  # round 6: bank problems of large grids split into runs of frames where the last round of workgroups would run
                 # nearly empty (split_plan's round model) against the unsplit launch
@@ -42,47 +30,22 @@ for stage in "$@"; do
                 timeout 300 python tools/rank_step_microbench.py --native --only split,auto --no-levels --no-copies --reps 12 2>/dev/null | tee -a $O/rank_step_wire.txt ;;
     hooksbd)    for a in "cfg2 6 --graph" "cfg2 10 --ranks 8 --wire-less --graph" "cfg2 6 --ranks 1 --graph" "cfg2 6 --ranks 1 --split --graph"; do timeout 900 python tools/hooks_bench.py $a --breakdown 2>&1 | grep -v amdgpu.ids | tee -a $O/hooks_breakdown.txt; done
                 timeout 300 python tools/rank_step_microbench.py --native --only split,auto --no-copies --no-levels --reps 12 2>/dev/null | grep "step inject" | tee -a $O/hooks_breakdown.txt ;;
-    r6ab2)      # round 6, second A/B: cross-phase prefetch, prefetch distance, static priority, denominator on the matrix pipe
-                timeout 120 tools/ubench/mfma4_probe > $O/mfma4_probe.txt 2>&1; cat $O/mfma4_probe.txt
-                for lib in noxpfvalu "" lsumvalu noxpf pf3 prio noxpfvalu ""; do echo "== lib=${lib:-default}" | tee -a $O/attn_il_ab2.txt
-                  TOKENFLOW_HIP_LIB=${lib:+build/variants/lib_$lib.so} timeout 300 python tools/attn_microbench.py 10,9216,5,64 25,4096,5,64 10,2304,10,64 8,4096,8,40 8,1024,8,80 2>/dev/null | grep "inject=0" | tee -a $O/attn_il_ab2.txt; done ;;
     d64tests)   timeout 900 python -m pytest tests/test_kernels_gpu.py tests/test_baseline_configs_gpu.py tests/test_fullsize_gpu.py -q --tb=short -p no:cacheprovider -k "attn or cfg4 or cfg5 or cfg2" 2>&1 | tail -8 | tee -a $O/d64_tests.txt ;;
-    dualab)     for lib in "" dualdma dualdma4 dualdma8 "" dualdma; do echo "== lib=${lib:-default}" | tee -a $O/attn_d40_dual_ab.txt
-                  TOKENFLOW_HIP_LIB=${lib:+build/variants/lib_$lib.so} timeout 300 python tools/attn_microbench.py 8,4096,8,40 4,1024,8,40 2>/dev/null | grep "inject=1" | tee -a $O/attn_d40_dual_ab.txt; done ;;
     rb2ab)      for e in "TF_NN_RB2_MIN_WGS=100000000" "X=0" "TF_NN_RB2_MIN_WGS=100000000" "X=0"; do echo "== $e (X=0: two target tiles per wave where the plan takes them)" | tee -a $O/nn_rb2_ab.txt
                   env $e timeout 300 python tools/prop_microbench.py 8,5,4096,320 10,8,9216,320 25,8,4096,320 2>/dev/null | grep "one call" | tee -a $O/nn_rb2_ab.txt
                   env $e timeout 300 python tools/nn_microbench.py 8,5,4096,320 10,8,9216,320 2>/dev/null | tee -a $O/nn_rb2_ab.txt; done
                 timeout 900 python -m pytest tests/test_fullsize_gpu.py tests/test_kernels_gpu.py tests/test_baseline_configs_gpu.py -q --tb=short -p no:cacheprovider -k "nn_search or propagat or cfg2 or cfg4" 2>&1 | tail -4 | tee -a $O/nn_rb2_ab.txt ;;
-    dual64ab)   for lib in "" il64dual8 il64dual4 "" il64dual8 il64dual4; do echo "== lib=${lib:-default}" | tee -a $O/attn_d64_dual_ab.txt
-                  TOKENFLOW_HIP_LIB=${lib:+build/variants/lib_$lib.so} timeout 300 python tools/attn_microbench.py 10,9216,5,64 10,2304,10,64 10,576,20,64 2>/dev/null | grep "inject=1" | tee -a $O/attn_d64_dual_ab.txt; done
-                for lib in il64dual8 il64dual4; do TOKENFLOW_HIP_LIB=build/variants/lib_$lib.so timeout 900 python -m pytest tests/test_kernels_gpu.py tests/test_baseline_configs_gpu.py tests/test_fullsize_gpu.py -q --tb=short -p no:cacheprovider -k "attn or cfg4" 2>&1 | tail -4 | tee -a $O/attn_d64_dual_ab.txt; done ;;
-    benchab)    # whole-step A/B on ONE box: round 5's kernel choices rebuilt from this tree (build/variants/lib_r05eq.so) against the default
-                for lib in r05eq "" r05eq ""; do for cfg in cfg2 cfg4 cfg5; do
-                  TOKENFLOW_HIP_LIB=${lib:+build/variants/lib_$lib.so} timeout 600 python bench.py --config $cfg --steps $([ $cfg = cfg2 ] && echo 10 || echo 2) --warmup 2 --no-cpu-baseline --no-yardstick --no-parity --no-other-configs > $O/benchab_tmp.json 2>> $O/benchab.err
-                  python -c "import json;d=json.load(open('$O/benchab_tmp.json'));print('lib=${lib:-default}', '$cfg', 'ms/step', d['ms_per_step'], 'inject on/off', d['ms_per_step_inject_on'], d['ms_per_step_inject_off'], 'L0 attn ms', d['roofline']['avg_launch_ms'])" | tee -a $O/bench_step_ab.txt; done; done ;;
-    bound80ab)  for lib in "" bound80 "" bound80; do echo "== lib=${lib:-default}" | tee -a $O/attn_d80_bound_ab.txt
-                  TOKENFLOW_HIP_LIB=${lib:+build/variants/lib_$lib.so} timeout 300 python tools/attn_microbench.py 8,1024,8,80 2>/dev/null | tee -a $O/attn_d80_bound_ab.txt; done ;;
-    barrierexp) # timing experiments (WRONG results): the interleaved kernels without the per-tile barrier / without the DMA drain in front of it
-                for lib in "" nobar nowait "" nobar nowait; do echo "== lib=${lib:-default}" | tee -a $O/attn_barrier_experiment.txt
-                  TOKENFLOW_HIP_LIB=${lib:+build/variants/lib_$lib.so} timeout 300 python tools/attn_microbench.py 10,9216,5,64 8,4096,8,40 8,1024,8,80 8,4096,8,80 2>/dev/null | grep "inject=0" | tee -a $O/attn_barrier_experiment.txt; done ;;
     rb2thr)     # threshold of the two-tile register-B search: the per-chunk searches of the hook path (one chunk per UNet pass) are small launches
                 for e in "TF_NN_RB2_MIN_WGS=100000000" "TF_NN_RB2_MIN_WGS=2048" "TF_NN_RB2_MIN_WGS=1024" "TF_NN_RB2_MIN_WGS=512" "TF_NN_RB2_MIN_WGS=100000000" "TF_NN_RB2_MIN_WGS=1024"; do echo "== $e" | tee -a $O/nn_rb2_threshold.txt
                   env $e timeout 300 python tools/nn_microbench.py 8,5,4096,320 10,8,9216,320 25,8,4096,320 2>/dev/null | tee -a $O/nn_rb2_threshold.txt
                   env $e timeout 300 python tools/prop_microbench.py 8,5,4096,320 2>/dev/null | grep "per-chunk" | tee -a $O/nn_rb2_threshold.txt; done ;;
-    dual80ab)   for lib in "" il80dual "" il80dual; do echo "== lib=${lib:-default}" | tee -a $O/attn_d80_dual_ab.txt
-                  TOKENFLOW_HIP_LIB=${lib:+build/variants/lib_$lib.so} timeout 300 python tools/attn_microbench.py 8,1024,8,80 10,576,20,64 2>/dev/null | grep "inject=1" | tee -a $O/attn_d80_dual_ab.txt; done
-                TOKENFLOW_HIP_LIB=build/variants/lib_il80dual.so timeout 900 python -m pytest tests/test_kernels_gpu.py tests/test_baseline_configs_gpu.py tests/test_fullsize_gpu.py -q --tb=short -p no:cacheprovider -k "attn or cfg2" 2>&1 | tail -4 | tee -a $O/attn_d80_dual_ab.txt ;;
     seam2)      timeout 900 python -m pytest tests/test_driver_seam.py tests/test_sharded_gpu.py -m gpu -q --tb=short -p no:cacheprovider -s -k "driver or shard_vs_default" 2>&1 | grep -v "^$" | tail -60 > $O/seam2_tests.txt; grep -ai "driver seam\|passed\|failed\|Error\|assert" $O/seam2_tests.txt | cut -c1-300 ;;
     inputsab)   for n in 1 0 1 0; do timeout 600 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-yardstick --no-parity --input-sets $n > $O/bench_sets_$n.json 2>> $O/inputsab.err; python -c "import json;d=json.load(open('$O/bench_sets_$n.json'));print('input sets',d['input_sets']['n'],d['ms_per_step'],d['ms_per_step_inject_on'],d['ms_per_step_inject_off'],d['roofline']['avg_launch_ms'])" | tee -a $O/input_sets_ab.txt; done ;;
-    src4ab)     for lib in "" nosrc4 "" nosrc4; do echo "== lib=${lib:-current}" | tee -a $O/rank_step_src4_ab.txt
-                  TOKENFLOW_HIP_LIB=${lib:+build/variants/lib_$lib.so} timeout 300 python tools/rank_step_microbench.py --native --only split,auto --no-copies --reps 12 2>/dev/null | grep "step inject\|level 0" | tee -a $O/rank_step_src4_ab.txt; done ;;
     bmmprobe)   timeout 300 python tools/bmm_out_probe.py > $O/bmm_out_probe.txt 2>&1; grep -v amdgpu.ids $O/bmm_out_probe.txt | cut -c1-330 ;;
     srcaux)     for e in "X=0" "TOKENFLOW_RANK_SRC_AUX=1" "TOKENFLOW_RANK_SRC_AUX=1 TOKENFLOW_SPLIT_OVER=1" "TOKENFLOW_SPLIT_OVER=1" "X=0" "TOKENFLOW_RANK_SRC_AUX=1 TOKENFLOW_SPLIT_OVER=1"; do echo "== env $e" | tee -a $O/rank_step_srcaux_ab.txt
                   env $e timeout 300 python tools/rank_step_microbench.py --native --only split,auto --no-copies --reps 12 2>/dev/null | grep "step inject\|level 0" | tee -a $O/rank_step_srcaux_ab.txt; done ;;
     hooks2)     for a in "6" "6 --graph" "10 --ranks 8 --wire-less --graph" "10 --ranks 8 --wire-less"; do timeout 600 python tools/hooks_bench.py cfg2 $a >> $O/hooks_bench2.txt 2>/dev/null; done; cat $O/hooks_bench2.txt ;;
     hooksab)    for e in "TOKENFLOW_NORM1_ALL_BRANCHES=1" "TOKENFLOW_NORM1_ALL_BRANCHES=0" "TOKENFLOW_NORM1_ALL_BRANCHES=1" "TOKENFLOW_NORM1_ALL_BRANCHES=0"; do for a in "6 --graph" "10 --ranks 8 --wire-less --graph"; do echo -n "$e: " >> $O/hooks_norm1_ab.txt; env $e timeout 600 python tools/hooks_bench.py cfg2 $a >> $O/hooks_norm1_ab.txt 2>/dev/null; done; done; cat $O/hooks_norm1_ab.txt ;;
-    onepassab)  for lib in "" il40nw4 "" il40nw4; do echo "== lib=${lib:-current}" | tee -a $O/rank_step_onepass_ab.txt
-                  TOKENFLOW_HIP_LIB=${lib:+build/variants/lib_$lib.so} timeout 300 python tools/rank_step_microbench.py --native --only onepass,auto --no-copies --reps 12 2>/dev/null | grep "step inject\|level 0" | tee -a $O/rank_step_onepass_ab.txt; done ;;
     gldstests)  timeout 900 python -m pytest tests/test_fullsize_gpu.py tests/test_kernels_gpu.py tests/test_baseline_configs_gpu.py -q --tb=short -p no:cacheprovider -s -k "lds_dma or nn_search or propagat" 2>&1 | grep -v "^$" | tail -30 ;;
     gldsab)     for e in "TF_NN_GLDS_MIN_WGS=100000000" "TF_NN_GLDS_MIN_WGS=256" "TF_NN_GLDS_MIN_WGS=100000000" "TF_NN_GLDS_MIN_WGS=256" "TF_NN_GLDS_MIN_WGS=64"; do echo "== $e" | tee -a $O/nn_glds_ab.txt
                   env $e timeout 300 python tools/prop_microbench.py 8,5,1024,640 8,5,256,1280 10,8,2304,640 10,8,576,1280 25,8,1024,640 2>/dev/null | tee -a $O/nn_glds_ab.txt
@@ -104,9 +67,6 @@ for stage in "$@"; do
                   TOKENFLOW_HIP_LIB=${lib:+build/variants/lib_$lib.so} timeout 300 python tools/prop_microbench.py 8,5,1024,640 10,8,2304,640 25,8,1024,640 10,8,576,1280 4,2,1024,320 2>/dev/null | grep "one call" | tee -a $O/nn_glds_spread_ab.txt
                   TOKENFLOW_HIP_LIB=${lib:+build/variants/lib_$lib.so} timeout 300 python tools/nn_microbench.py 8,5,1024,640 2>/dev/null | tee -a $O/nn_glds_spread_ab.txt; done
                 timeout 600 python -m pytest tests/test_fullsize_gpu.py tests/test_kernels_gpu.py -q --tb=short -p no:cacheprovider -k "lds_dma or nn_search or propagat" 2>&1 | tail -3 | tee -a $O/nn_glds_spread_ab.txt ;;
-    il40dma)    for lib in "" il40dma "" il40dma; do echo "== lib=${lib:-current}" | tee -a $O/attn_il40_dma_ab.txt
-                  TOKENFLOW_HIP_LIB=${lib:+build/variants/lib_$lib.so} timeout 300 python tools/attn_microbench.py 8,4096,8,40 4,1024,8,40 2>/dev/null | tee -a $O/attn_il40_dma_ab.txt; done
-                TOKENFLOW_HIP_LIB=build/variants/lib_il40dma.so timeout 900 python -m pytest tests/test_kernels_gpu.py tests/test_fullsize_gpu.py tests/test_baseline_configs_gpu.py -q --tb=short -p no:cacheprovider -k "attn" 2>&1 | tail -6 | tee -a $O/attn_il40_dma_ab.txt ;;
     trprobe)    timeout 60 tools/ubench/tr_probe > $O/tr_probe.txt 2>&1; cat $O/tr_probe.txt ;;
     fusedtests) timeout 900 python -m pytest tests/test_fused_attn_gpu.py -q --tb=line -p no:cacheprovider 2>&1 | tail -40 > $O/fused_tests.txt; tail -25 $O/fused_tests.txt ;;
     kerneltests) timeout 1500 python -m pytest tests/test_kernels_gpu.py -q --tb=line -p no:cacheprovider -k "attn" 2>&1 | tail -30 > $O/kernel_attn_tests.txt; tail -15 $O/kernel_attn_tests.txt ;;
@@ -120,48 +80,17 @@ for stage in "$@"; do
     l1streamab) # round 6: a rank's level-1 pivotal pass in the streaming form (round-6 d = 80 kernels) against the fused launch
                 for e in "X=0" "TOKENFLOW_FUSED_MAX_S=256" "X=0" "TOKENFLOW_FUSED_MAX_S=256"; do echo "== $e (X=0: fused launch at level 1)" | tee -a $O/rank_l1_stream_ab.txt
                   env $e timeout 600 python tools/rank_step_microbench.py --native --only split,auto --no-copies --reps 12 2>/dev/null | grep "step inject\|level 1" | tee -a $O/rank_l1_stream_ab.txt; done ;;
-    il80w8ab)   # round 6: d = 80 plain kernel as 8-wave workgroups forced to 128 VGPRs (4 waves per SIMD, 19 spilled registers) against 4-wave / 145
-                for lib in "" il80w8 "" il80w8; do echo "== lib=${lib:-default}" | tee -a $O/attn_d80_w8_ab.txt
-                  TOKENFLOW_HIP_LIB=${lib:+build/variants/lib_$lib.so} timeout 300 python tools/attn_microbench.py 8,1024,8,80 8,4096,8,80 4,256,8,80 2>/dev/null | grep "inject=0" | tee -a $O/attn_d80_w8_ab.txt; done ;;
     pmc80)      # instruction-level accounting of the d = 80 interleaved kernel: cfg2 level 1 and the same kernel on a level-0-sized grid
                 for shape in 8,1024,8,80 8,4096,8,80; do
                 for grp in "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_SCA" "SQ_WAIT_INST_LDS SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_WAVE_CYCLES" "SQ_INST_CYCLES_VMEM_RD SQ_INST_LEVEL_LDS SQ_INST_LEVEL_VMEM SQ_ACTIVE_INST_ANY" "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_COEXEC_CYCLES SQ_THREAD_CYCLES_VALU" "SQ_INSTS_VALU_TRANS_F32 SQ_INSTS_VALU_CVT SQ_INSTS_VALU_FMA_F32 SQ_INSTS_VALU_MUL_F32" "SQ_INSTS_VALU_ADD_F32 SQ_INSTS_SALU SQ_INSTS_SMEM SQ_IFETCH" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_LDS_DATA_FIFO_FULL SQ_LDS_CMD_FIFO_FULL" "SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_VALU_INT32" "SQ_ACTIVE_INST_MISC SQ_ACTIVE_INST_VALU2 SQ_BUSY_CU_CYCLES SQ_WAVES"; do
                   rm -rf /tmp/p80; ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --pmc $grp -d /tmp/p80 -- python $GRAFT_REPO_ROOT/tools/attn_microbench.py $shape > /dev/null 2>>$GRAFT_REPO_ROOT/$O/pmc80.err )
                   DB=$(find /tmp/p80 -name "*_results.db" | head -1); [ -n "$DB" ] && python tools/rocpd_pmc.py $DB | grep "il_kernel<BF16; 80; 4; 0\|^kernel" >> $O/pmc_d80_S$(echo $shape | cut -d, -f2).csv; done
                 python tools/l0_accounting.py $O/pmc_d80_S$(echo $shape | cut -d, -f2).csv | tee $O/d80_accounting_S$(echo $shape | cut -d, -f2).txt; done ;;
-    mixab)      # round 6: mixed MFMA shapes in the d = 40 interleaved kernel (TF_TUNE_IL40_MIX: QK^T 32x32x16, P.V 16x16x32 behind v_permlane16_swap)
-                TOKENFLOW_HIP_LIB=build/variants/lib_il40mix.so timeout 900 python -m pytest tests/test_kernels_gpu.py -q --tb=short -p no:cacheprovider -x -k "attn" 2>&1 | tail -12 | tee -a $O/attn_d40_mix_ab.txt
-                for lib in "" il40mix "" il40mix "" il40mix; do echo "== lib=${lib:-default}" | tee -a $O/attn_d40_mix_ab.txt
-                  TOKENFLOW_HIP_LIB=${lib:+build/variants/lib_$lib.so} timeout 300 python tools/attn_microbench.py 8,4096,8,40 4,1024,8,40 2>/dev/null | tee -a $O/attn_d40_mix_ab.txt; done ;;
-    mixab2)     for lib in "" il40mix il40mix2 il40mix3 "" il40mix il40mix2 il40mix3; do echo "== lib=${lib:-default}" | tee -a $O/attn_d40_mix_ab2.txt
-                  TOKENFLOW_HIP_LIB=${lib:+build/variants/lib_$lib.so} timeout 300 python tools/attn_microbench.py 8,4096,8,40 2>/dev/null | grep "inject=0" | tee -a $O/attn_d40_mix_ab2.txt; done ;;
-    nosbab)     for lib in "" il40mix2 nosb40 nosb64 nosb80 "" il40mix2 nosb40 nosb64 nosb80; do echo "== lib=${lib:-default}" | tee -a $O/attn_il_nosb_ab.txt
-                  TOKENFLOW_HIP_LIB=${lib:+build/variants/lib_$lib.so} timeout 300 python tools/attn_microbench.py 8,4096,8,40 10,9216,5,64 8,1024,8,80 2>/dev/null | tee -a $O/attn_il_nosb_ab.txt; done ;;
-    mixab3)     for lib in "" il40mix2 il40mix4 il40mix1o il40mix4o il40mix2o "" il40mix2 il40mix4 il40mix1o il40mix4o il40mix2o; do echo "== lib=${lib:-default}" | tee -a $O/attn_d40_mix_ab3.txt
-                  TOKENFLOW_HIP_LIB=${lib:+build/variants/lib_$lib.so} timeout 300 python tools/attn_microbench.py 8,4096,8,40 4,1024,8,40 2>/dev/null | grep "inject=0" | tee -a $O/attn_d40_mix_ab3.txt; done ;;
-    mixstep)    # whole-step A/B on ONE box: the d = 40 kernel without the mixed MFMA shapes (build/variants/lib_nomix.so) against the default
-                for lib in nomix "" nomix ""; do TOKENFLOW_HIP_LIB=${lib:+build/variants/lib_$lib.so} timeout 600 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-yardstick --no-parity --no-other-configs > $O/bench_mix_${lib:-default}.json 2>> $O/mixstep.err
-                  python -c "import json;d=json.load(open('$O/bench_mix_${lib:-default}.json'));print('lib=${lib:-default}', 'step', d['ms_per_step'], 'inject on/off', d['ms_per_step_inject_on'], d['ms_per_step_inject_off'], 'level-0 plain launch', d['roofline']['avg_launch_ms'], 'frac', d['roofline']['frac'])" | tee -a $O/bench_mix_step_ab.txt; done ;;
-    mixab4)     for lib in "" mixpf3 mixnoxpf mixpf1 "" mixpf3 mixnoxpf mixpf1; do echo "== lib=${lib:-default}" | tee -a $O/attn_d40_mix_ab4.txt
-                  TOKENFLOW_HIP_LIB=${lib:+build/variants/lib_$lib.so} timeout 300 python tools/attn_microbench.py 8,4096,8,40 2>/dev/null | grep "inject=0" | tee -a $O/attn_d40_mix_ab4.txt; done ;;
-    mixab5)     for lib in "" mixw4m5 mixw4m4 "" mixw4m5 mixw4m4; do echo "== lib=${lib:-default}" | tee -a $O/attn_d40_mix_ab5.txt
-                  TOKENFLOW_HIP_LIB=${lib:+build/variants/lib_$lib.so} timeout 300 python tools/attn_microbench.py 8,4096,8,40 2>/dev/null | grep "inject=0" | tee -a $O/attn_d40_mix_ab5.txt; done ;;
-    mixab6)     TOKENFLOW_HIP_LIB= timeout 900 python -m pytest tests/test_kernels_gpu.py -q --tb=short -p no:cacheprovider -x -k "attn" 2>&1 | tail -3 | tee -a $O/attn_d40_mix_ab6.txt
-                for lib in mixnoswz "" mixnoswz "" mixnoswz ""; do echo "== lib=${lib:-default}" | tee -a $O/attn_d40_mix_ab6.txt
-                  TOKENFLOW_HIP_LIB=${lib:+build/variants/lib_$lib.so} timeout 300 python tools/attn_microbench.py 8,4096,8,40 4,1024,8,40 2>/dev/null | grep "inject=0" | tee -a $O/attn_d40_mix_ab6.txt; done
-                rm -rf /tmp/sq; ( cd /tmp && timeout 600 rocprofv3 --kernel-trace --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_ANY SQ_WAVE_CYCLES -d /tmp/sq -- python $GRAFT_REPO_ROOT/tools/attn_microbench.py 8,4096,8,40 > /dev/null 2>&1 )
-                python tools/rocpd_pmc.py $(find /tmp/sq -name "*_results.db" | head -1) | grep "il_kernel<BF16; 40; 8; 0" | tee -a $O/attn_d40_mix_ab6.txt ;;
-    mixrank)    for lib in nomix "" nomix ""; do echo "== lib=${lib:-default}" | tee -a $O/rank_step_mix_ab.txt
-                  TOKENFLOW_HIP_LIB=${lib:+build/variants/lib_$lib.so} timeout 600 python tools/rank_step_microbench.py --native --only split,auto --no-copies --reps 12 2>/dev/null | grep "step inject\|level 0" | tee -a $O/rank_step_mix_ab.txt; done ;;
     rbsab)      # round 6: the two-target-tile search with short MFMAs (nn_search_rbs_kernel, 16x16x32) against the 32x32x16 form (lib_norbs.so)
                 timeout 900 python -m pytest tests/test_kernels_gpu.py tests/test_fullsize_gpu.py tests/test_baseline_configs_gpu.py -q --tb=short -p no:cacheprovider -k "nn_search or propagat or iid or two_tile or cfg2 or cfg4" 2>&1 | tail -8 | tee -a $O/nn_rbs_ab.txt
                 for lib in norbs "" norbs "" norbs ""; do echo "== lib=${lib:-default}" | tee -a $O/nn_rbs_ab.txt
                   TOKENFLOW_HIP_LIB=${lib:+build/variants/lib_$lib.so} timeout 300 python tools/prop_microbench.py 8,5,4096,320 10,8,9216,320 25,8,4096,320 2>/dev/null | grep "one call" | tee -a $O/nn_rbs_ab.txt
                   TOKENFLOW_HIP_LIB=${lib:+build/variants/lib_$lib.so} timeout 300 python tools/nn_microbench.py 8,5,4096,320 2>/dev/null | tee -a $O/nn_rbs_ab.txt; done ;;
-    mix64ab)    # round 6: the mixed MFMA shapes at d = 64 (TF_TUNE_IL64_MIX): cfg4 / cfg5 level 0 and level 1; parity tests of the variant
-                TOKENFLOW_HIP_LIB=build/variants/lib_mix64.so timeout 1200 python -m pytest tests/test_kernels_gpu.py tests/test_baseline_configs_gpu.py -q --tb=short -p no:cacheprovider -k "64 or cfg4 or cfg5 or mixed" 2>&1 | tail -6 | tee -a $O/attn_d64_mix_ab.txt
-                for lib in "" mix64 "" mix64; do echo "== lib=${lib:-default}" | tee -a $O/attn_d64_mix_ab.txt
-                  TOKENFLOW_HIP_LIB=${lib:+build/variants/lib_$lib.so} timeout 300 python tools/attn_microbench.py 10,9216,5,64 25,4096,5,64 10,2304,10,64 2>/dev/null | grep "inject=0" | tee -a $O/attn_d64_mix_ab.txt; done ;;
     gldsshab)   # round 6: the LDS-DMA search kernel (D >= 512; D = 320 with <= 1024 pivots) with short MFMAs against the 32x32x16 form (lib_nogldssh.so)
                 timeout 900 python -m pytest tests/test_kernels_gpu.py tests/test_fullsize_gpu.py tests/test_baseline_configs_gpu.py -q --tb=short -p no:cacheprovider -k "nn_search or propagat or iid or lds_dma or cfg1 or cfg2 or cfg4 or cfg5" 2>&1 | tail -6 | tee -a $O/nn_glds_sh_ab.txt
                 for lib in nogldssh "" nogldssh "" nogldssh ""; do echo "== lib=${lib:-default}" | tee -a $O/nn_glds_sh_ab.txt
