@@ -834,6 +834,8 @@ __global__ __launch_bounds__(256, TT == 1 ? 3 : 2) void nn_search_rbg_kernel(con
 // Arithmetic: a (target, pivot) dot product is summed 32 features per MFMA in ascending order -- NOT bit-identical to the
 // 16-wide steps of the other search kernels (fp32 rounding of the partial sums); exact duplicates still tie exactly (the same
 // instruction sequence on the same data) and the first index wins as everywhere (ascending rows, strict '>').
+// The tile loop is software-pipelined: fragment addresses as base + immediate, a ring of fragments read ahead
+// of their MFMAs with counted waits, and half-tile phases whose argmax fold runs beside the MFMAs of the next half.
 template <typename T, int DK, int TJ = 4>
 __global__ __launch_bounds__(256, TJ == 4 ? 2 : 3) void nn_search_rbs_kernel(const typename T::elem* __restrict__ tgt,
                                                                const typename T::elem* __restrict__ piv,
@@ -852,7 +854,6 @@ __global__ __launch_bounds__(256, TJ == 4 ? 2 : 3) void nn_search_rbs_kernel(con
     constexpr int A_ELEMS = TMR * D;
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    auto sA = [&](int b) { return reinterpret_cast<E*>(smem) + b * A_ELEMS; };
     float* sInv = reinterpret_cast<float*>(smem + 2 * A_ELEMS * sizeof(E));  // [2][TMR]
 
     const int tid = threadIdx.x;
@@ -895,12 +896,23 @@ __global__ __launch_bounds__(256, TJ == 4 ? 2 : 3) void nn_search_rbs_kernel(con
         a_off[i] = r * D + ((pos ^ ((r >> 1) & 7)) << 3);
     }
     float rinv = 0.f;
+    // The DMA is issued from an asm statement (M0 = the piece's LDS address, saved and restored), not through
+    // __builtin_amdgcn_global_load_lds: the compiler books the builtin as a flat access that may touch LDS, and while one
+    // is pending -- here: the whole tile -- it turns every wait for a fragment read into lgkmcnt(0), the ring's read-ahead
+    // included.  Nothing changes in what is copied where; the data is ordered as before by the vmcnt(0) and the barrier
+    // at the end of the tile.
+    const unsigned lds0 = (unsigned)(size_t)(lds_ptr)smem;
     auto stage_load = [&](int mt) {
-        unsigned char* a = reinterpret_cast<unsigned char*>(sA(mt & 1));
         const E* tile = pv + (int64_t)(mt0 + mt) * TMR * D;
 #pragma unroll
-        for (int i = 0; i < NPIECE / 4; ++i)
-            __builtin_amdgcn_global_load_lds((glb_ptr)(tile + a_off[i]), (lds_ptr)(a + (wave_u + 4 * i) * 1024), 16, 0, 0);
+        for (int i = 0; i < NPIECE / 4; ++i) {
+            const unsigned dst = __builtin_amdgcn_readfirstlane(lds0 + (mt & 1) * (A_ELEMS * (int)sizeof(E)) + (wave_u + 4 * i) * 1024);
+            unsigned keep;
+            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                         : "=&s"(keep)
+                         : "v"((glb_ptr)(tile + a_off[i])), "s"(dst)
+                         : "memory");
+        }
         if (tid < TMR) {
             int row = (mt0 + mt) * TMR + tid;
             rinv = inv[row < S ? row : S - 1];
@@ -909,6 +921,34 @@ __global__ __launch_bounds__(256, TJ == 4 ? 2 : 3) void nn_search_rbs_kernel(con
     auto stage_write = [&](int mt) {
         if (tid < TMR) sInv[(mt & 1) * TMR + tid] = rinv;
     };
+    // end of a tile: the next tile's DMA has landed, every wave is done with this tile's buffers.  rinv is made opaque so
+    // that the compiler settles its own load of it here and not in front of the next stage_load's DMA
+    auto tile_done = [&]() {
+        asm volatile("" : "+v"(rinv));
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+    };
+
+    // A-fragment addresses (bytes into a tile image) as base + immediate.  Fragment k of a tile is half i = k / KS32 (pivot
+    // rows 16 i + n16) at k-step t = k % KS32: the 16-B piece 4 t + g of row r = 16 i + n16, stored at piece
+    // (4 t + g) ^ ((r >> 1) & 7).  (r >> 1) & 7 == (n16 >> 1) & 7 for both halves, and 4 t + g = 8 (t >> 1) + (4 (t & 1) + g)
+    // whose second term is below 8, so the XOR stays in the low three bits: two per-lane bases (t even / odd) and the
+    // immediates (t >> 1) * 128 B, i * HALF_BYTES and, added once per tile, the buffer's A_BYTES.
+    constexpr int ROW_BYTES = D * (int)sizeof(E);
+    constexpr int HALF_BYTES = 16 * ROW_BYTES;
+    constexpr int A_BYTES = A_ELEMS * (int)sizeof(E);
+    // fragments in flight: the read of group k + RING - 1 is issued before the MFMAs of group k.  A group is TJ MFMAs of
+    // 16 matrix-pipe clocks, so both forms read 128 clocks ahead, about the LDS round trip
+    constexpr int RING = TJ == 4 ? 3 : 5;
+    static_assert(TMR == 32 && sizeof(E) == 2, "two 16-row halves whose rows 16 i + n16 share (r >> 1) & 7; 8 elements per 16-B piece");
+    static_assert(KS32 % 2 == 0, "k-steps pair up into groups of 8 pieces");
+    static_assert((KS32 / 2 - 1) * 128 + HALF_BYTES + A_BYTES < 65536, "every fragment offset fits ds_read's 16-bit immediate");
+    static_assert(RING - 1 <= KS32, "the ring's prologue stays inside phase A");
+    const int fa_base[2] = {n16 * ROW_BYTES + ((g ^ ((n16 >> 1) & 7)) << 4), n16 * ROW_BYTES + (((4 + g) ^ ((n16 >> 1) & 7)) << 4)};
+    auto frag = [&](const int (&cur)[2], int k) {
+        const int t = k % KS32, i = k / KS32;
+        return __builtin_bit_cast(vec8, ld16(smem + cur[t & 1] + (t >> 1) * 128 + i * HALF_BYTES));
+    };
 
     float best_v[TJ];
     int best_i[TJ];
@@ -916,47 +956,89 @@ __global__ __launch_bounds__(256, TJ == 4 ? 2 : 3) void nn_search_rbs_kernel(con
     for (int j = 0; j < TJ; ++j) best_v[j] = -INFINITY, best_i[j] = 0;
     stage_load(0);
     stage_write(0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
+    // the B fragments are complete here, not at their first use inside the loop: a vmcnt placed there by the compiler would
+    // also wait for the DMA of the tile in flight
+#pragma unroll
+    for (int j = 0; j < TJ; ++j)
+#pragma unroll
+        for (int t = 0; t < KS32; ++t) asm volatile("" : "+v"(fb[j][t]));
+    // likewise the output pointers: a scalar load pending beside the fragment reads makes the first wait of every tile
+    // lgkmcnt(0)
+    asm volatile("" ::"s"(idx_out), "s"(part_out));
+    tile_done();
+    // Half-tile phases.  A tile is 2 KS32 groups of TJ MFMAs on one A fragment each.  Phase A: the KS32 groups of pivot rows
+    // 0-15 into acc0, beside them the fold of the PREVIOUS tile's rows 16-31 (acc1, w1 and row1 are carried over the barrier;
+    // sInv's buffer of tile mt is overwritten by stage_write(mt + 2), so w1 is in registers before the barrier of tile mt,
+    // and row1 names the tile the half belongs to, not the one its fold runs in).  Phase B: rows 16-31 into acc1, beside
+    // them the fold of acc0.  Per accumulator the MFMA sequence is t ascending as before: every score keeps its bits.
+    // Within a lane the folds stay in ascending pivot order (tile m rows 0-15, tile m rows 16-31, tile m + 1 rows 0-15, ..):
+    // with the strict '>' the first index wins.  The fragment reads run as a ring RING - 1 groups ahead of the MFMAs and
+    // drain at the end of the tile: the next tile's first reads stand behind the barrier, before which its DMA is not
+    // known to have landed.
+    constexpr int EPG = TJ / 2;              // scores folded beside one group: 4 TJ per half-tile over the groups 1 .. 8
+    static_assert(TJ % 2 == 0 && EPG * (KS32 - 2) >= 4 * TJ, "a half-tile's fold fits beside the inner groups of a phase");
+    // element e of a half-tile's fold: row e / TJ of this lane's four, sub-tile e % TJ -- ascending rows per sub-tile
+    auto fold1 = [&](const f32x4 (&a)[TJ], const f32x4 w, const int row0, int e) {
+        const int r = e / TJ, j = e % TJ;
+        // register-only arithmetic is held in its group by making the running best opaque before and after it
+        asm volatile("" : "+v"(best_v[j]), "+v"(best_i[j]));
+        const float sc = a[j][r] * w[r];
+        if (sc > best_v[j]) {
+            best_v[j] = sc;
+            best_i[j] = row0 + r;
+        }
+        asm volatile("" : "+v"(best_v[j]), "+v"(best_i[j]));
+    };
+    f32x4 acc0[TJ], acc1[TJ];
+#pragma unroll
+    for (int j = 0; j < TJ; ++j) acc1[j] = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};   // folds to nothing (strict '>')
+    f32x4 w0, w1 = f32x4{1.f, 1.f, 1.f, 1.f};
+    int row0, row1 = 0;
+    vec8 fa[RING];
+    int cur[2];
+    // group k of a tile: its read-ahead, its TJ MFMAs into acc (C = 0 at the first k-step), EPG scores of accf folded beside
+    // them -- {read, TJ x {MFMA, 2 VALU}}, pinned
+    auto group = [&](int k, f32x4 (&acc)[TJ], const f32x4 (&accf)[TJ], const f32x4 wf, const int rowf) {
+        const int t = k % KS32;
+        const bool read = k + RING - 1 < 2 * KS32;
+        if (read) fa[(k + RING - 1) % RING] = frag(cur, k + RING - 1);
+#pragma unroll
+        for (int j = 0; j < TJ; ++j)
+            acc[j] = T::mfma16(fa[k % RING], fb[j][t], t == 0 ? f32x4{0.f, 0.f, 0.f, 0.f} : acc[j]);
+        if (t >= 1 && t <= (4 * TJ) / EPG) {
+#pragma unroll
+            for (int e = (t - 1) * EPG; e < t * EPG; ++e) fold1(accf, wf, rowf, e);
+        }
+        if (read) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+#pragma unroll
+        for (int j = 0; j < TJ; ++j) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    };
     for (int mt = 0; mt < n_mt; ++mt) {
         const bool has_next = mt + 1 < n_mt;
+        const int buf = (mt & 1) * A_BYTES;
+        cur[0] = fa_base[0] + buf, cur[1] = fa_base[1] + buf;
+        const float* si = sInv + (mt & 1) * TMR + 4 * g;
+#pragma unroll
+        for (int k = 0; k < RING - 1; ++k) fa[k] = frag(cur, k);
+        w0 = *reinterpret_cast<const f32x4*>(si);
         if (has_next) stage_load(mt + 1);
-        f32x4 acc[2][TJ];
+        row0 = (mt0 + mt) * TMR + 4 * g;
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int i = 0; i < 2; ++i)
+        for (int k = 0; k < KS32; ++k) group(k, acc0, acc1, w1, row1);
+        w1 = *reinterpret_cast<const f32x4*>(si + 16);
 #pragma unroll
-            for (int j = 0; j < TJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-        const E* a0 = sA(mt & 1);
-#pragma unroll
-        for (int t = 0; t < KS32; ++t) {
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const int r = 16 * i + n16;   // pivot row of the tile; its 16-B piece 4 t + g, swizzled as stored
-                const vec8 fa = __builtin_bit_cast(vec8, ld16(a0 + r * D + (((4 * t + g) ^ ((r >> 1) & 7)) << 3)));
-#pragma unroll
-                for (int j = 0; j < TJ; ++j) acc[i][j] = T::mfma16(fa, fb[j][t], acc[i][j]);
-            }
-        }
-        const float* si = sInv + (mt & 1) * TMR;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int rl = 16 * i + 4 * g + r;   // ascending within the lane: first index wins with the strict '>'
-                const float w = si[rl];
-#pragma unroll
-                for (int j = 0; j < TJ; ++j) {
-                    const float sc = acc[i][j][r] * w;
-                    if (sc > best_v[j]) {
-                        best_v[j] = sc;
-                        best_i[j] = (mt0 + mt) * TMR + rl;
-                    }
-                }
-            }
+        for (int k = KS32; k < 2 * KS32; ++k) group(k, acc1, acc0, w0, row0);
+        row1 = row0 + 16;
         if (has_next) stage_write(mt + 1);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
+        tile_done();
     }
+#pragma unroll
+    for (int e = 0; e < 4 * TJ; ++e) fold1(acc1, w1, row1, e);   // rows 16-31 of the last tile
     // the four 16-lane rows hold disjoint pivot rows of the same target: merge, lower index on equal scores
 #pragma unroll
     for (int j = 0; j < TJ; ++j) {
