@@ -699,6 +699,53 @@ TF_API int tf_ext_attn_windows_plan(int K, int Kq, int q_frame0, int S, int H, i
                              const int* win_n, char* buf, size_t len);
 
 /* ------------------------------------------------------------------------
+ * Sliding-window bank for a MULTI-EDIT batch (additive to ABI 11): several prompts on one long video in one pass.
+ *
+ * tf_ext_attn_fwd_windows_edits: q, k, v, out, strides, n_edits and inject_mask as tf_ext_attn_fwd_edits_masked -- B = 1 + 2E
+ *   branches [source | uncond_1 | cond_1 | ...], bit e of the mask = edit e uses the source's q and k -- and win_lo, win_n as
+ *   tf_ext_attn_fwd_windows (HOST arrays of Kq ints, validated the same way).  The uncond / cond branches of EVERY edit attend,
+ *   for query frame i, to bank frames [win_lo[i], win_lo[i] + win_n[i]); the source branch to its own frame, once; nothing
+ *   mixes edits.
+ *   Refused with TF_ERR_SHAPE, before anything touches the device: what tf_ext_attn_fwd_windows refuses of its table (a bad
+ *     window, Kq > TF_MAX_WINDOW_FRAMES) and of its flags (TF_ATTN_BANK_ONLY, TF_ATTN_SOURCE_ONLY, TF_ATTN_FOLD_SCALE,
+ *     TF_ATTN_RUN_MULTI_V), and what the masked call refuses (TF_ATTN_INJECT beside the mask, mask bits at or above n_edits,
+ *     n_edits outside 1 .. TF_MAX_EDITS, TF_ATTN_NO_MULTI_V beside TF_ATTN_MULTI_V or TF_ATTN_MULTI_V64).  TF_ATTN_MULTI_V,
+ *     TF_ATTN_NO_MULTI_V and TF_ATTN_MULTI_V64 are ACCEPTED here (tf_ext_attn_fwd_windows keeps refusing them).
+ *   n_edits = 1 IS tf_ext_attn_fwd_windows, and every window = [0, K) IS tf_ext_attn_fwd_edits_masked: same launches, same
+ *   bits, same plan tokens.
+ *   Otherwise the call is the masked composition with the window table handed to every bank part; as in the windowed call the
+ *   fused-kernel decision, the split and the kernel forms are planned for K' = max_i win_n[i], windowed launches carry ",win"
+ *   in the plan, and the table rides in the kernel arguments (no device table, no copy, no sync):
+ *     - ONE V^T pre-pass over the span of the streaming branches;
+ *     - the injecting edits first: pairs in the windowed four-bank form where it is selected (below), an odd one in the DUAL
+ *       launch beside them; without the form each through the launches of its own windowed bank-only call;
+ *     - the edits that do not inject, each through its windowed bank-only launches;
+ *     - the source branch last, through the plain, unwindowed source-only launches.
+ *   Identity.  Edit e's bank branches are BIT-IDENTICAL to those of tf_ext_attn_fwd_windows on [source | uncond_e | cond_e]
+ *   with edit e's own injection flag, and its source branch to that call's source slice, under TF_ATTN_NO_SPLIT wherever both
+ *   plans name the same kernel form; always within the attention bound of the oracle on the window's slices.
+ *   The windowed four-bank form: one<40,1,4,MV4,2,fq0>,win (Dh = 40, the packed image) and one<64,1,8,MV4,2,fq1>,win (Dh = 64,
+ *   four 64-row banks).  One workgroup computes QK^T and the softmax of query frame f once, over the window of f, and the four
+ *   P.V products of branches b, b + 1, b + gap, b + gap + 1: all four banks read the SAME window.  Pair launches are one-pass
+ *   (TF_ATTN_NO_SPLIT | TF_ATTN_NO_FUSED), as in the masked call.  Frame i's OWN CALL is tf_ext_attn_fwd_edits_masked with the
+ *   four-bank hint on the window's tensors, (K, Kq, q_frame0) = (win_n[i], 1, q_frame0 + i - win_lo[i]): the windowed pair
+ *   launch is bit-identical to it (same kernel form; a one-pass launch's arithmetic depends only on the sequence of key tiles).
+ *   TF_ATTN_MULTI_V (Dh = 40) / TF_ATTN_MULTI_V64 (Dh = 64) force the form on, TF_ATTN_NO_MULTI_V forces it off.  The measured
+ *   defaults of the whole-bank call say nothing about windows: without a hint a windowed call takes the form only in the
+ *   shape classes where profiles/r19_window_edits_ab.txt shows it ahead of the DUAL composition by more than the run-to-run
+ *   spread (the rule and its figures stand in csrc/ext_attn.hip beside the other two).
+ *   ws: tf_ext_attn_edits_workspace_bytes(K, ...), unchanged.
+ * tf_ext_attn_windows_edits_plan: the launches of the call for dense tensors (host only), the tokens of tf_ext_attn_plan.
+ * ------------------------------------------------------------------------ */
+TF_API int tf_ext_attn_fwd_windows_edits(const void* q, const void* k, const void* v, void* out, int K, int Kq, int q_frame0,
+                                  int S, int H, int Dh, int64_t ld, const int64_t* strides, float scale, int flags, int dtype,
+                                  int n_edits, unsigned inject_mask, const int* win_lo, const int* win_n, void* ws,
+                                  size_t ws_bytes, void* stream);
+
+TF_API int tf_ext_attn_windows_edits_plan(int K, int Kq, int q_frame0, int S, int H, int Dh, int n_edits, unsigned inject_mask,
+                                   int flags, int dtype, const int* win_lo, const int* win_n, char* buf, size_t len);
+
+/* ------------------------------------------------------------------------
  * Row LayerNorm producer  --  the `norm1` call of TokenFlowBlock.forward
  * (tokenflow_utils.py:313-323; also norm2 / norm3 of the same forward, 399-417)
  * when the block runs in 16 bit:  out[r] = (x[r] - mean) / sqrt(var + eps) * gamma + beta

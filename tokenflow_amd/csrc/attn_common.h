@@ -147,10 +147,12 @@ __device__ __forceinline__ void store_out4(void* out, int64_t elem_off, f32x4 x,
 template <int MODE>
 static inline const char* run_mark(const AttnParams& p) { return (p.run && MODE != MODE_SOURCE) ? ",run" : ""; }
 
-// A windowed launch (AttnParamsWin) exists for the launches that hold bank problems and that tf_ext_attn_fwd_windows can
-// reach: the ALL and DUAL forms.  Its source-only launches are the plain ones (a source problem reads its own frame whatever
-// the windows); the four-bank and run forms take no windows.  Plan token: the plain launch's with ",win" appended.
+// A windowed launch (AttnParamsWin) exists for the launches that hold bank problems and that a windowed call can reach: the
+// ALL and DUAL forms (tf_ext_attn_fwd_windows) and the four-bank form of a pair of injecting edits
+// (tf_ext_attn_fwd_windows_edits: the four banks of a workgroup read the SAME window, their query frame's).  Its source-only
+// launches are the plain ones (a source problem reads its own frame whatever the windows); the run forms take no windows.
+// Plan token: the plain launch's with ",win" appended.
 template <typename P, int MODE, bool RUN = false>
-constexpr bool win_launch = is_win<P> && (MODE == MODE_ALL || MODE == MODE_DUAL) && !RUN;
+constexpr bool win_launch = is_win<P> && (MODE == MODE_ALL || MODE == MODE_DUAL || MODE == MODE_MV4) && !RUN;
 
 }  // namespace

@@ -132,7 +132,8 @@ __global__ __launch_bounds__(64 * NW, MINW) void ext_attn_kernel(P p) {
     int n_fr = b == 0 ? 1 : ((seg + 1) * K) / nseg - f_lo;
     if constexpr (is_win<P>) {   // a bank problem reads its query frame's window of the bank
         if (b > 0) window_range(p, f, seg, nseg, f_lo, n_fr);
-        if (n_fr == 0) {   // a window shorter than the split: this run holds no frame
+        if (n_fr == 0) {   // a window shorter than the split: this run holds no frame (never in the four-bank form, whose
+                           // launches are one-pass: nseg = 1 and a window holds at least its own frame)
             write_empty_run(p, b - 1, NB, f, h, seg, qt * (32 * QT * NW), 32 * QT * NW, DH, NT);
             return;
         }

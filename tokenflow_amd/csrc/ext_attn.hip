@@ -86,7 +86,7 @@ static int split_plan(int K, int Kq, int S, int H, int Dh, bool inject, int part
 // Dh=64: 2 query tiles/wave (each LDS fragment feeds 2 MFMAs).  Dh=80/160: register-bound, 1 tile/wave.
 template <typename T, int DH, typename P>
 int launch_attn(const P& p, const void* v, hipStream_t st) {
-    constexpr bool WIN = is_win<P>;   // windowed call: no four-bank, run or folded-scale form (refused by the entry point)
+    constexpr bool WIN = is_win<P>;   // windowed call: no run or folded-scale form (refused by the entry points)
     const bool src_only = p.part == TF_ATTN_SOURCE_ONLY, bank_only = p.part == TF_ATTN_BANK_ONLY;
     // The kernel FAMILY of a run launch is the one the unsplit call of the same (Kq, S, H) takes, however the run splits
     // itself: the source branch out of a run call is then bit for bit the source-only call's (same kernel, same keys).
@@ -502,12 +502,31 @@ static bool mv4_d64_default(int K, int Kq, int S, int H) {
     return Kq == K && (H == 5 || H == 10) && K >= 10 && K <= 25 && S % 64 == 0 && S >= 1024 && S <= 9216;
 }
 
+// The four-bank form in a WINDOWED multi-edit call (tf_ext_attn_fwd_windows_edits; K_max = the longest window).  The two rules
+// above were measured on whole banks and say nothing about windows: this one comes from the three-arm A/B of
+// profiles/r19_window_edits_ab.txt alone (E windowed single-edit calls / the DUAL composition / the four-bank form forced; radius
+// 2 at the level-0 shapes of BASELINE configs 2, 4 and 5, E = 2 and 3), and holds only the shape classes in which the forced
+// form is ahead of the DUAL composition by more than the run-to-run spread of both arms.  It is in all three, at E = 2 / E = 3
+// (medians, spreads of 0.3 to 0.9 % per arm):
+//   Dh = 64, (K, S, H) = (25, 4096, 5):  6.87 against  8.74 ms (-21 %) / 10.77 against 12.77 ms (-16 %)
+//   Dh = 64, (K, S, H) = (10, 9216, 5): 13.33 against 16.79 ms (-21 %) / 21.21 against 24.56 ms (-14 %)
+//   Dh = 40, (K, S, H) = (8, 4096, 8):   2.35 against  2.56 ms (-8 %)  /  3.49 against  3.67 ms (-5 %)
+// The rule is what those cells span and no more: every keyframe's queries, a longest window of 5 frames (radius 2); at Dh = 64
+// the box of the two shapes (5 heads, banks of 10 to 25 keyframes, whole 64-key tiles, frames of 4096 to 9216 tokens), at
+// Dh = 40 the one shape.  Other radii, head counts, frame sizes, query-frame subsets and irregular tables with longer windows
+// were not measured and stay behind TF_ATTN_MULTI_V / TF_ATTN_MULTI_V64.
+static bool mv4_win_default(int K, int K_max, int Kq, int S, int H, int Dh) {
+    if (Kq != K || K_max != 5) return false;
+    if (Dh == 64) return H == 5 && K >= 10 && K <= 25 && S % 64 == 0 && S >= 4096 && S <= 9216;
+    return Dh == 40 && H == 8 && K == 8 && S == 4096;
+}
+
 // The masked composition: bit e of inject_mask = edit e injects (its uncond and cond branches use the source's q and k).
 // tf_ext_attn_fwd_edits is the two uniform masks of it.
 static int attn_fwd_edits_masked(const char* name, const void* q, const void* k, const void* v, void* out, int K, int Kq,
                                  int q_frame0, int S, int H, int Dh, int64_t ld, const int64_t* strides, float scale, int flags,
                                  int dtype, int n_edits, unsigned inject_mask, void* ws, size_t ws_bytes, void* stream,
-                                 bool part_call = false, int qk_compact = 0) {
+                                 bool part_call = false, int qk_compact = 0, const WinPart* wn = nullptr) {
     TF_ARG(n_edits >= 1 && n_edits <= TF_MAX_EDITS, TF_ERR_SHAPE, "%s: n_edits=%d (1 .. %d)", name, n_edits, TF_MAX_EDITS);
     TF_ARG(q && k && v && out && ws && strides, TF_ERR_NULL, "%s: null pointer", name);
     TF_ARG(dtype == TF_BF16 || dtype == TF_F16, TF_ERR_DTYPE, "%s: dtype %d (bf16/f16 only)", name, dtype);
@@ -533,7 +552,7 @@ static int attn_fwd_edits_masked(const char* name, const void* q, const void* k,
     if (n_edits == 1)   // today's layout: today's call (the hints of the four-bank form have nothing to select); the compact
                         // q / k of one edit is the dense one as far as its launches read it
         return attn_fwd_core(q, k, v, out, K, Kq, q_frame0, S, H, Dh, ld, strides, scale,
-                             base | part | (inject_mask ? TF_ATTN_INJECT : 0), dtype, ws, ws_bytes, stream, nullptr);
+                             base | part | (inject_mask ? TF_ATTN_INJECT : 0), dtype, ws, ws_bytes, stream, nullptr, nullptr, wn);
     const int B = 1 + 2 * n_edits;
     int inj_e[TF_MAX_EDITS], non_e[TF_MAX_EDITS], n_inj = 0, n_non = 0;   // the injecting / the other edits, ascending
     int qk_sh[TF_MAX_EDITS];   // q / k branch slots in front of edit e's uncond slot, minus 1 (an injecting edit reads slot 0)
@@ -548,8 +567,10 @@ static int attn_fwd_edits_masked(const char* name, const void* q, const void* k,
     // the four-bank form: Dh = 40 or 64 (each behind its own hint and its own measured default), fp32 score scaling, at least
     // one pair of INJECTING edits
     const bool mv_ok = n_inj >= 2 && (Dh == 40 || Dh == 64) && !(flags & TF_ATTN_FOLD_SCALE);
-    const bool mv_on = Dh == 40 ? ((flags & TF_ATTN_MULTI_V) || mv4_default(K, Kq, S, H))
-                                : ((flags & TF_ATTN_MULTI_V64) || mv4_d64_default(K, Kq, S, H));
+    // (the two measured defaults speak of whole banks: a windowed call has its own rule)
+    const bool mv_on = Dh == 40 ? ((flags & TF_ATTN_MULTI_V) || (wn ? mv4_win_default(K, wn->K_max, Kq, S, H, Dh) : mv4_default(K, Kq, S, H)))
+                                : ((flags & TF_ATTN_MULTI_V64) ||
+                                   (wn ? mv4_win_default(K, wn->K_max, Kq, S, H, Dh) : mv4_d64_default(K, Kq, S, H)));
     const bool mv = mv_ok && !(flags & TF_ATTN_NO_MULTI_V) && mv_on;
     // the pair launches and the odd edit beside them are one-pass streaming launches
     const int inj_flags = base | TF_ATTN_INJECT | TF_ATTN_BANK_ONLY | (mv ? TF_ATTN_NO_SPLIT | TF_ATTN_NO_FUSED : 0);
@@ -561,9 +582,11 @@ static int attn_fwd_edits_masked(const char* name, const void* q, const void* k,
         const int sh = 2 * e;
         const bool inj = (fl & TF_ATTN_INJECT) != 0;
         const int qsh = (fl & TF_ATTN_SOURCE_ONLY) ? 0 : qk_sh[e];
+        // a sliding-window bank (tf_ext_attn_fwd_windows_edits): every bank part reads the windows; the source part is the plain
+        // source-only call (a source problem reads its own frame whatever the windows)
         return attn_fwd_core(inj ? q : at(q, qsh * strides[0], 2), inj ? k : at(k, qsh * strides[2], 2), at(v, sh * strides[4], 2),
                              const_cast<void*>(at(out, sh * strides[6], osz)), K, Kq, q_frame0, S, H, Dh, ld, strides, scale, fl,
-                             dtype, ws, ws_bytes, stream, &ed);
+                             dtype, ws, ws_bytes, stream, &ed, nullptr, (fl & TF_ATTN_SOURCE_ONLY) ? nullptr : wn);
     };
     // which parts stream (and read the V^T image): the decision of the part's own call
     const EditsPart probe = EditsPart::probe_of(B);
@@ -1266,19 +1289,15 @@ extern "C" int tf_ext_attn_segments_plan(int K, int n_seg, const int* seg_K, int
 // bank frames [win_lo[i], win_lo[i] + win_n[i]) only.  The launches of tf_ext_attn_fwd_strided for a bank of max_i win_n[i]
 // frames -- ONE pre-pass over the whole bank, ONE bank launch whose problems decode their frame's window from the table in the
 // kernel arguments -- so frame i's result is what its own call (the strided call on its window alone) computes.
-extern "C" int tf_ext_attn_fwd_windows(const void* q, const void* k, const void* v, void* out, int K, int Kq, int q_frame0,
-                                       int S, int H, int Dh, int64_t ld, const int64_t* strides, float scale, int flags,
-                                       int dtype, const int* win_lo, const int* win_n, void* ws, size_t ws_bytes,
-                                       void* stream) {
-    const char* const name = "tf_ext_attn_fwd_windows";
+// The window table of a call, validated and packed as the kernels read it.
+static int windows_pack(const char* name, int K, int Kq, int q_frame0, const int* win_lo, const int* win_n, unsigned* win,
+                        int* K_max, bool* full) {
     TF_ARG(win_lo && win_n, TF_ERR_NULL, "%s: null window table", name);
     TF_ARG(K > 0 && Kq > 0 && q_frame0 >= 0 && q_frame0 + Kq <= K, TF_ERR_SHAPE,
            "%s: query frames [%d, %d) outside the %d-frame bank", name, q_frame0, q_frame0 + Kq, K);
     TF_ARG(Kq <= TF_MAX_WINDOW_FRAMES, TF_ERR_SHAPE, "%s: Kq=%d (at most %d query frames carry a window)", name, Kq,
            TF_MAX_WINDOW_FRAMES);
-    unsigned win[TF_MAX_WINDOW_FRAMES];
-    int K_max = 0;
-    bool full = true;
+    *K_max = 0, *full = true;
     for (int i = 0; i < Kq; ++i) {
         const int lo = win_lo[i], n = win_n[i], own = q_frame0 + i;
         TF_ARG(n >= 1, TF_ERR_SHAPE, "%s: window %d holds %d frames", name, i, n);
@@ -1287,9 +1306,21 @@ extern "C" int tf_ext_attn_fwd_windows(const void* q, const void* k, const void*
         TF_ARG(lo <= own && own < lo + n, TF_ERR_SHAPE, "%s: window %d = [%d, %d) does not hold its own frame %d", name, i, lo,
                lo + n, own);
         win[i] = (unsigned)lo | ((unsigned)n << 16);
-        K_max = n > K_max ? n : K_max;
-        full = full && lo == 0 && n == K;
+        *K_max = n > *K_max ? n : *K_max;
+        *full = *full && lo == 0 && n == K;
     }
+    return 0;
+}
+
+extern "C" int tf_ext_attn_fwd_windows(const void* q, const void* k, const void* v, void* out, int K, int Kq, int q_frame0,
+                                       int S, int H, int Dh, int64_t ld, const int64_t* strides, float scale, int flags,
+                                       int dtype, const int* win_lo, const int* win_n, void* ws, size_t ws_bytes,
+                                       void* stream) {
+    const char* const name = "tf_ext_attn_fwd_windows";
+    unsigned win[TF_MAX_WINDOW_FRAMES];
+    int K_max = 0;
+    bool full = true;
+    if (const int rc = windows_pack(name, K, Kq, q_frame0, win_lo, win_n, win, &K_max, &full)) return rc;
     constexpr int REFUSED = TF_ATTN_BANK_ONLY | TF_ATTN_SOURCE_ONLY | TF_ATTN_FOLD_SCALE | TF_ATTN_MULTI_V | TF_ATTN_NO_MULTI_V |
                             TF_ATTN_MULTI_V64 | TF_ATTN_RUN_MULTI_V;
     TF_ARG(!(flags & REFUSED), TF_ERR_SHAPE,
@@ -1319,5 +1350,49 @@ extern "C" int tf_ext_attn_windows_plan(int K, int Kq, int q_frame0, int S, int 
     tf_plan_rec = nullptr;
     if (rc) return rc;
     TF_ARG(rec.used < len, TF_ERR_WORKSPACE, "tf_ext_attn_windows_plan: the plan needs %zu bytes", rec.used + 1);
+    return rec.n;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Sliding-window bank for a multi-edit batch (include/tokenflow_hip.h): the masked composition with the window table handed to
+// every bank part -- ONE pre-pass, the injecting edits (pairs in the windowed four-bank form where it is selected), the others,
+// then the plain source-only launches.
+extern "C" int tf_ext_attn_fwd_windows_edits(const void* q, const void* k, const void* v, void* out, int K, int Kq, int q_frame0,
+                                             int S, int H, int Dh, int64_t ld, const int64_t* strides, float scale, int flags,
+                                             int dtype, int n_edits, unsigned inject_mask, const int* win_lo, const int* win_n,
+                                             void* ws, size_t ws_bytes, void* stream) {
+    const char* const name = "tf_ext_attn_fwd_windows_edits";
+    unsigned win[TF_MAX_WINDOW_FRAMES];
+    int K_max = 0;
+    bool full = true;
+    if (const int rc = windows_pack(name, K, Kq, q_frame0, win_lo, win_n, win, &K_max, &full)) return rc;
+    // (the multi-edit hints TF_ATTN_MULTI_V / TF_ATTN_NO_MULTI_V / TF_ATTN_MULTI_V64 select the pair form here)
+    constexpr int REFUSED = TF_ATTN_BANK_ONLY | TF_ATTN_SOURCE_ONLY | TF_ATTN_FOLD_SCALE | TF_ATTN_RUN_MULTI_V;
+    TF_ARG(!(flags & REFUSED), TF_ERR_SHAPE,
+           "%s: flags 0x%x -- TF_ATTN_BANK_ONLY / TF_ATTN_SOURCE_ONLY / TF_ATTN_FOLD_SCALE / TF_ATTN_RUN_MULTI_V have no windowed "
+           "form", name, flags & REFUSED);
+    // (n_edits = 1: the masked composition is attn_fwd_core on today's layout, here with the window table: tf_ext_attn_fwd_windows)
+    const WinPart wn{win, K_max};
+    // every window = [0, K): the masked call itself
+    return attn_fwd_edits_masked(name, q, k, v, out, K, Kq, q_frame0, S, H, Dh, ld, strides, scale, flags, dtype, n_edits,
+                                 inject_mask, ws, ws_bytes, stream, false, 0, full ? nullptr : &wn);
+}
+
+// Launch plan of tf_ext_attn_fwd_windows_edits for dense tensors (host only): the entry point itself under the plan recorder.
+extern "C" int tf_ext_attn_windows_edits_plan(int K, int Kq, int q_frame0, int S, int H, int Dh, int n_edits, unsigned inject_mask,
+                                              int flags, int dtype, const int* win_lo, const int* win_n, char* buf, size_t len) {
+    TF_ARG(K > 0 && S > 0 && H > 0 && Kq > 0 && Kq <= K, TF_ERR_SHAPE, "tf_ext_attn_windows_edits_plan: K=%d Kq=%d S=%d H=%d", K,
+           Kq, S, H);
+    void* const ph = reinterpret_cast<void*>((uintptr_t)1 << 12);
+    const int64_t ld = (int64_t)H * Dh, fs = (int64_t)S * ld;
+    const int64_t strides[9] = {Kq * fs, fs, K * fs, fs, K * fs, fs, Kq * fs, fs, ld};
+    TfPlanRec rec{buf, len, 0, 0};
+    if (buf && len) buf[0] = 0;
+    tf_plan_rec = &rec;
+    const int rc = tf_ext_attn_fwd_windows_edits(ph, ph, ph, ph, K, Kq, q_frame0, S, H, Dh, ld, strides, 1.0f, flags, dtype, n_edits,
+                                                 inject_mask, win_lo, win_n, ph, (size_t)-1, nullptr);
+    tf_plan_rec = nullptr;
+    if (rc) return rc;
+    TF_ARG(rec.used < len, TF_ERR_WORKSPACE, "tf_ext_attn_windows_edits_plan: the plan needs %zu bytes", rec.used + 1);
     return rec.n;
 }

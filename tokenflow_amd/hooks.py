@@ -249,7 +249,7 @@ def _segments(module, K=None):
     return segs
 
 
-def register_bank_window(model, radius):
+def register_bank_window(model, radius, edits=False):
     """Sliding-window keyframe bank (no counterpart in the reference, where every keyframe attends to the whole bank): in the
     pivotal passes that follow, the uncond / cond branches of keyframe i attend to the keyframes i - radius .. i + radius only
     (clamped to the bank; `ops.bank_windows`), the source branch to its own frame as always.  Consistency stays chained along
@@ -258,21 +258,28 @@ def register_bank_window(model, radius):
     blocks and their `attn1`; both attention installers then call `ops.ext_attn_windows` whenever radius < K - 1.
     `None`, or a radius >= K - 1 (every window is the whole bank), issues exactly today's ops: the reference computation.
     Propagation is untouched: chunk c still blends keyframes c and c - 1.
-    Not generalised, ValueError at the call: `register_edits(model, E > 1)`, `register_segments` with several segments, a
-    registered frame shard -- there the radius is held against the shard's WHOLE bank (`shard.K`), not the rank's local
-    keyframes, and only a radius that covers it passes (INTEGRATION.md section 6 shows the driver side)."""
+    edits=True opens the window for a multi-edit batch (`register_edits(model, E > 1)`, with one shared schedule or
+    `register_edit_schedules`): the pivotal pass is then ONE `ops.ext_attn_windows_edits` over all 1 + 2E branches -- every
+    edit's bank branches attend to the windows, with the per-edit injection mask of the step.  Without the keyword a window
+    in a multi-edit batch stays an error, as before.
+    Not generalised, ValueError at the call: `register_edits(model, E > 1)` unless edits=True, `register_segments` with several
+    segments, a registered frame shard -- there the radius is held against the shard's WHOLE bank (`shard.K`), not the rank's
+    local keyframes, and only a radius that covers it passes -- and, as for every multi-edit pass, graph capture
+    (INTEGRATION.md section 6 shows the driver side)."""
     if radius is not None:
         radius = int(radius)
         if radius < 0:
             raise ValueError(f"register_bank_window: radius={radius} (>= 0, or None for the whole bank)")
-    _set_bank_window(_hook_blocks(model.unet), radius)
+    _set_bank_window(_hook_blocks(model.unet), radius, bool(edits) and radius is not None)
 
 
-def _set_bank_window(blocks, radius):
-    """`bank_window` on transformer blocks and their `attn1` (register_bank_window; tools on a bare block list)."""
+def _set_bank_window(blocks, radius, edits=False):
+    """`bank_window` (and `bank_window_edits`, the multi-edit opt-in) on transformer blocks and their `attn1`
+    (register_bank_window; tools on a bare block list)."""
     for tb in blocks:
-        setattr(tb, "bank_window", radius)
-        setattr(tb.attn1, "bank_window", radius)
+        for m in (tb, tb.attn1):
+            setattr(m, "bank_window", radius)
+            setattr(m, "bank_window_edits", edits)
 
 
 def _bank_window(module, K: int):
@@ -290,9 +297,9 @@ def _bank_window(module, K: int):
         return None
     if radius >= K - 1:
         return None
-    if int(getattr(module, "n_edits", 1)) > 1:
+    if int(getattr(module, "n_edits", 1)) > 1 and not getattr(module, "bank_window_edits", False):
         raise ValueError("register_bank_window: a sliding-window bank in a multi-edit batch (register_edits, n_edits > 1) is "
-                         "not supported")
+                         "opt-in: register_bank_window(model, radius, edits=True)")
     if getattr(module, "keyframe_segments", None) is not None:
         raise ValueError("register_bank_window: a sliding-window bank in a pass of several keyframe segments "
                          "(register_segments) is not supported")
@@ -532,7 +539,7 @@ def _make_sa_forward(self, pnp: bool):
                 q, k, v = q.to(cdt), k.to(cdt), v.to(cdt)
         shard = None if is_cross else _active_shard(self)
         E = 1 if is_cross else _n_edits(self)
-        # (a window excludes edits, segments and shards; the pass carries q.shape[0] / (1 + 2E) keyframes)
+        # (a window excludes segments and shards, and edits unless opted in; the pass carries q.shape[0] / (1 + 2E) keyframes)
         radius = None if is_cross else _bank_window(self, q.shape[0] // (1 + 2 * E))
         segs = None if is_cross else _segments(self, q.shape[0] // 3)
         # the edits that inject (one shared schedule: all or none; register_edit_schedules: each edit's own)
@@ -544,6 +551,9 @@ def _make_sa_forward(self, pnp: bool):
                 out = shard.pivotal_attention(q, k, v, self.heads, self.scale, False, n_edits=E, inject_mask=mask)
             else:
                 out = shard.pivotal_attention(q, k, v, self.heads, self.scale, inject)
+        elif radius is not None and E > 1:   # ... several prompts on a long video: every edit's bank branches read the windows
+            out = ops.ext_attn_windows_edits(q, k, v, self.heads, self.scale, False, E,
+                                             ops.bank_windows(q.shape[0] // (1 + 2 * E), radius), inject_mask=mask)
         elif radius is not None:  # long videos: a bank branch attends to the neighbouring keyframes only
             out = ops.ext_attn_windows(q, k, v, self.heads, self.scale, inject, ops.bank_windows(q.shape[0] // 3, radius))
         elif segs is not None:    # several scenes or clips: a bank branch attends to the keyframes of its own segment
