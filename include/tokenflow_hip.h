@@ -746,6 +746,50 @@ TF_API int tf_ext_attn_windows_edits_plan(int K, int Kq, int q_frame0, int S, in
                                    int flags, int dtype, const int* win_lo, const int* win_n, char* buf, size_t len);
 
 /* ------------------------------------------------------------------------
+ * FRAME-SET keyframe bank (additive to ABI 11): a local window plus a few global ANCHOR keyframes, or any other keyframe
+ * sparsity.  A purely local window has no global reference: consistency is only chained along the clip through the overlapping
+ * windows.  The usual remedy is a window plus anchors that every keyframe sees (the first keyframe, every m-th one); the cost
+ * stays linear in K: 2 radius + 1 + A frame-banks per keyframe.  The per-keyframe table is a SET of bank frames instead of a
+ * range; dilated windows or windows clipped at scene cuts are expressed the same way.  Like the windowed call this CHANGES
+ * THE RESULT relative to TokenFlow; it is opt-in, and with every set = [0, K) it IS the reference computation.
+ *
+ * tf_ext_attn_fwd_frame_sets: the arguments of tf_ext_attn_fwd_strided plus one HOST array of Kq 64-bit masks.
+ *   Bit j of sets[i]: the uncond / cond branches of query frame i (bank frame q_frame0 + i) attend to the keys of bank frame j;
+ *   under TF_ATTN_INJECT with the source's q and k, over the same sets.  The source branch attends to its own frame, as
+ *   always.  Members are visited in ASCENDING frame order.
+ *   Refused before anything touches the device: a null table (TF_ERR_NULL); with TF_ERR_SHAPE K > 64; Kq >
+ *     TF_MAX_WINDOW_FRAMES; an empty set; a bit at or above K; a set without its own frame q_frame0 + i; and the flags
+ *     tf_ext_attn_fwd_windows refuses (TF_ATTN_BANK_ONLY, TF_ATTN_SOURCE_ONLY, TF_ATTN_FOLD_SCALE and the multi-edit hints).
+ *   Canonical forms.  If every set is a contiguous range the call IS tf_ext_attn_fwd_windows on the equivalent (lo, n) table:
+ *   same launches, same bits, same plan tokens (",win" included); so every set = [0, K) IS tf_ext_attn_fwd_strided.
+ *   Otherwise the call issues the launches tf_ext_attn_fwd_strided would issue for a bank of K' = max_i popcount(sets[i])
+ *   frames at the same Kq, S, H, Dh and flags (the fused-kernel decision, the split plan and the kernel forms are those of K'):
+ *     - ONE V^T pre-pass over the whole bank of K frames;
+ *     - ONE bank launch (or ONE fused launch, which needs no pre-pass) whose set table rides in the kernel arguments (64 x 8
+ *       bytes behind the parameter block) -- no device table, no copy, no sync.  A bank problem of query frame i streams the
+ *       member frames of set i; at every frame boundary its tile cursors jump to the next member.  The split form: run seg of
+ *       nseg takes members [seg n / nseg, (seg + 1) n / nseg) of the ascending member list, n = popcount(sets[i]); an empty
+ *       run leaves the neutral partial result, which the merge weighs with 0.  Plan token: the plain launch's with ",set"
+ *       appended -- il<..>,set, one<..>,set, pp<..>,set, fused[..,set];
+ *     - the merge and the source launches as in the plain call.
+ *   Identity.  Frame i's OWN CALL is tf_ext_attn_fwd_strided on the GATHERED tensors -- the member frames of set i copied next
+ *   to each other in ascending order -- with (K, Kq, q_frame0) = (popcount(sets[i]), 1, rank of the own frame among the
+ *   members).  Frame i's result is within the attention bound of its own call always, and BIT-IDENTICAL to it under
+ *   TF_ATTN_NO_SPLIT wherever the two plans name the same kernel form: the key tiles arrive in the same order, and the
+ *   Cauchy-Schwarz score bound (head dims 40 and 64) is the maximum key norm over the MEMBER frames only, not over the span
+ *   from the first to the last member (a superset would give another shift).
+ *   Not built: the four-bank form, multi-edit batches, keyframe segments and frame shards over frame sets.
+ *   ws: tf_ext_attn_workspace_bytes(K, ...), unchanged.
+ * tf_ext_attn_frame_sets_plan: the launches of the call for dense tensors (host only), the tokens of tf_ext_attn_plan.
+ * ------------------------------------------------------------------------ */
+TF_API int tf_ext_attn_fwd_frame_sets(const void* q, const void* k, const void* v, void* out, int K, int Kq, int q_frame0,
+                               int S, int H, int Dh, int64_t ld, const int64_t* strides, float scale, int flags, int dtype,
+                               const uint64_t* sets, void* ws, size_t ws_bytes, void* stream);
+
+TF_API int tf_ext_attn_frame_sets_plan(int K, int Kq, int q_frame0, int S, int H, int Dh, int flags, int dtype,
+                                const uint64_t* sets, char* buf, size_t len);
+
+/* ------------------------------------------------------------------------
  * Row LayerNorm producer  --  the `norm1` call of TokenFlowBlock.forward
  * (tokenflow_utils.py:313-323; also norm2 / norm3 of the same forward, 399-417)
  * when the block runs in 16 bit:  out[r] = (x[r] - mean) / sqrt(var + eps) * gamma + beta

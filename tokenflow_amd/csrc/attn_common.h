@@ -113,6 +113,64 @@ __device__ __forceinline__ void write_empty_run(const AttnParams& p, int bank, i
     }
 }
 
+// Frame-set keyframe bank (tf_ext_attn_fwd_frame_sets): the launch's parameter block with one 64-bit member mask per query
+// frame behind it -- bit j of set[i]: the bank branches of query frame i read the keys of bank frame j.  A type of its own
+// again (every plain and windowed launch keeps its parameter block and its code); the table rides in the kernel arguments,
+// a workgroup reads its query frame's mask with one scalar load.
+struct AttnParamsSet : AttnParams {
+    uint64_t set[TF_MAX_WINDOW_FRAMES];
+};
+template <typename P>
+constexpr bool is_set = std::is_same<P, AttnParamsSet>::value;
+
+// Frame-set launches, key frames of a bank problem: run `seg` of nseg takes members [seg n / nseg, (seg + 1) n / nseg) of the
+// ascending member list of query frame f's set (n = its popcount); returned as a mask, n_fr = its members.  A set shorter than
+// nseg leaves some runs empty.  Everything here depends on kernel arguments and the workgroup index only: scalar code.
+__device__ __forceinline__ uint64_t set_run(const AttnParamsSet& p, int f, int seg, int nseg, int& n_fr) {
+    uint64_t m = p.set[f];
+    const int n = __builtin_popcountll(m);
+    const int lo = (seg * n) / nseg, hi = ((seg + 1) * n) / nseg;
+    for (int i = 0; i < lo; ++i) m &= m - 1;   // drop the members in front of the run
+    uint64_t rest = m;
+    for (int i = lo; i < hi; ++i) rest &= rest - 1;   // ... and those behind it
+    n_fr = hi - lo;
+    return m & ~rest;
+}
+
+// Frame-set launches: the frame side of a tile cursor.  A streaming kernel moves its K and its V^T tile pointer by a constant
+// at every frame boundary; over a frame set the boundary step is "jump to the next member": hop() returns the bank frames
+// skipped on the way there, the caller adds that many frame strides on top of its wrap offset.  The K and the V^T cursor
+// advance at different pipeline stages, so each carries a walk of its own; wave-uniform (scalar registers: the remaining
+// mask and the frame the cursor stands in).
+struct SetWalk {
+    uint64_t rest;   // members behind the current one
+    int cur;         // bank frame of the current member
+    __device__ __forceinline__ void init(uint64_t run) {
+        cur = __builtin_ctzll(run);
+        rest = run & (run - 1);
+    }
+    __device__ __forceinline__ int hop() {
+        // behind the last member there is nothing to jump to: the pointer moves on by one frame and is never read again
+        const int next = rest ? __builtin_ctzll(rest) : cur + 1;
+        const int skip = next - cur - 1;
+        rest &= rest - 1;
+        cur = next;
+        return skip;
+    }
+};
+
+// Score bound of a frame-set problem: max |k|^2 over the 64-key blocks of the MEMBER frames only (not of the span from the
+// first to the last member: a superset would give another shift than the frame's own call on the gathered members takes; the
+// maximum over the same values in another order is the same number).  `base` = the norm row of the problem's (branch, head).
+__device__ __forceinline__ float set_knorm2(const float* base, uint64_t run, int ppf, int lane) {
+    float kn2 = 0.f;
+    for (uint64_t m = run; m; m &= m - 1) {
+        const float* part = base + (int64_t)__builtin_ctzll(m) * ppf;
+        for (int i = lane; i < ppf; i += 64) kn2 = fmaxf(kn2, part[i]);
+    }
+    return kn2;
+}
+
 // max over the two lanes (l, l ^ 32) that share a query: v_permlane32_swap instead of an LDS round trip
 __device__ __forceinline__ float max_with_lane_xor32(float x) {
     const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
@@ -154,5 +212,17 @@ static inline const char* run_mark(const AttnParams& p) { return (p.run && MODE 
 // Plan token: the plain launch's with ",win" appended.
 template <typename P, int MODE, bool RUN = false>
 constexpr bool win_launch = is_win<P> && (MODE == MODE_ALL || MODE == MODE_DUAL || MODE == MODE_MV4) && !RUN;
+
+// A frame-set launch (AttnParamsSet) likewise, for the ALL and DUAL forms (tf_ext_attn_fwd_frame_sets; the four-bank form has
+// no frame-set instantiation).  Plan token: the plain launch's with ",set" appended.
+template <typename P, int MODE, bool RUN = false>
+constexpr bool set_launch = is_set<P> && (MODE == MODE_ALL || MODE == MODE_DUAL) && !RUN;
+
+// The parameter block a launch hands its kernel: the caller's where the launch has a windowed / frame-set instantiation, the
+// plain one otherwise; and the mark its plan token carries
+template <typename P, int MODE, bool RUN = false>
+using launch_params_t = std::conditional_t<win_launch<P, MODE, RUN> || set_launch<P, MODE, RUN>, P, AttnParams>;
+template <typename P>
+static inline const char* table_mark() { return is_win<P> ? ",win" : is_set<P> ? ",set" : ""; }
 
 }  // namespace

@@ -43,5 +43,8 @@ TfFusedPlan tf_attn_fused_plan(const TfAttnSet* sets, int n_sets, int S, int Dh,
 // One launch over every (set, branch, frame, head, query tile) problem.  No workspace, no pre-pass, no merge launch.
 // `win` (one set only; tf_ext_attn_fwd_windows): the bank branches of query frame i read the bank frames of window i,
 // win[i] = first frame | frames << 16, sets[0].Kq entries that ride in the kernel arguments; plan token fused[..,win].
+// `frame_set` (one set only, instead of `win`; tf_ext_attn_fwd_frame_sets): the bank branches of query frame i read the bank
+// frames whose bits are set in frame_set[i], in ascending order; plan token fused[..,set].
 int tf_attn_fused_launch(const TfAttnSet* sets, int n_sets, int S, int Dh, float scale, int flags, int dtype,
-                         const TfFusedPlan& plan, hipStream_t st, const unsigned* win = nullptr);
+                         const TfFusedPlan& plan, hipStream_t st, const unsigned* win = nullptr,
+                         const uint64_t* frame_set = nullptr);

@@ -174,6 +174,18 @@ __global__ __launch_bounds__(64 * NW, MINW) void ext_attn_il_kernel(P p) {
             return;
         }
     }
+    [[maybe_unused]] uint64_t run = 0;   // frame-set launches: the member frames of this problem (see set_run, SetWalk)
+    if constexpr (is_set<P>) {   // a bank problem reads the member frames of its query frame's set, in ascending order
+        run = (uint64_t)1 << f_lo;   // (a source problem: its own frame)
+        if (b > 0) {
+            run = set_run(p, f, seg, nseg, n_fr);
+            if (n_fr == 0) {   // a set shorter than the split: this run holds no member
+                write_empty_run(p, b - 1, PACK ? 2 : 1, f, h, seg, qt * (32 * NW), 32 * NW, DH, NT);
+                return;
+            }
+            f_lo = __builtin_ctzll(run);
+        }
+    }
     const int tpf = S >> 6;
     const int ntiles = n_fr * tpf;
 
@@ -207,7 +219,9 @@ __global__ __launch_bounds__(64 * NW, MINW) void ext_attn_il_kernel(P p) {
         const int ppf = p.Spad / 64;
         const float* part = p.knorm2 + ((int64_t)(bq * H + h) * p.Kb + f_lo) * ppf;
         float kn2 = 0.f;
-        for (int i = lane; i < n_fr * ppf; i += 64) kn2 = fmaxf(kn2, part[i]);
+        if constexpr (is_set<P>) kn2 = set_knorm2(part - (int64_t)f_lo * ppf, run, ppf, lane);   // the member frames' blocks only
+        else
+            for (int i = lane; i < n_fr * ppf; i += 64) kn2 = fmaxf(kn2, part[i]);
 #pragma unroll
         for (int o_ = 32; o_ > 0; o_ >>= 1) kn2 = fmaxf(kn2, __shfl_xor(kn2, o_));
         float q2 = 0.f;
@@ -240,11 +254,17 @@ __global__ __launch_bounds__(64 * NW, MINW) void ext_attn_il_kernel(P p) {
     const E* k_next = kg + f_lo * p.k_fs;
     const E* v_next = vg + (int64_t)f_lo * p.Spad;
     int k_tt = 0, v_tt = 0;
+    [[maybe_unused]] SetWalk k_walk{}, v_walk{};   // frame-set launches: the member frame each cursor stands in
+    if constexpr (is_set<P>) k_walk.init(run), v_walk.init(run);
+    // (a frame boundary of a frame-set launch, below: on to the next member frame, over the frames between it and this one)
     auto load_k = [&]() {
 #pragma unroll
         for (int i = 0; i < NPK; ++i) rk[i] = ld16(k_next + k_goff[i]);
         const bool wrap = k_tt == tpf - 1;
         k_next += wrap ? k_wrap_off : (int64_t)64 * p.ld;
+        if constexpr (is_set<P>) {
+            if (wrap) k_next += (int64_t)k_walk.hop() * p.k_fs;
+        }
         k_tt = wrap ? 0 : k_tt + 1;
     };
     auto load_v = [&]() {
@@ -252,6 +272,9 @@ __global__ __launch_bounds__(64 * NW, MINW) void ext_attn_il_kernel(P p) {
         for (int i = 0; i < NPV; ++i) rv[i] = ld16(v_next + v_goff[i]);
         const bool wrap = v_tt == tpf - 1;
         v_next += wrap ? v_wrap : 64;
+        if constexpr (is_set<P>) {
+            if (wrap) v_next += (int64_t)v_walk.hop() * p.Spad;
+        }
         v_tt = wrap ? 0 : v_tt + 1;
     };
     auto write_k = [&](int buf) {
@@ -311,6 +334,9 @@ __global__ __launch_bounds__(64 * NW, MINW) void ext_attn_il_kernel(P p) {
         }
         const bool wrap = k_tt == tpf - 1;
         k_next += wrap ? k_wrap_off : (int64_t)64 * p.ld;
+        if constexpr (is_set<P>) {
+            if (wrap) k_next += (int64_t)k_walk.hop() * p.k_fs;
+        }
         k_tt = wrap ? 0 : k_tt + 1;
     };
     auto dma_v = [&](int buf) {      // the next V^T tile -> Vbuf[buf]
@@ -327,6 +353,9 @@ __global__ __launch_bounds__(64 * NW, MINW) void ext_attn_il_kernel(P p) {
         }
         const bool wrap = v_tt == tpf - 1;
         v_next += wrap ? v_wrap : 64;
+        if constexpr (is_set<P>) {
+            if (wrap) v_next += (int64_t)v_walk.hop() * p.Spad;
+        }
         v_tt = wrap ? 0 : v_tt + 1;
     };
     auto dma_wait = [&]() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); };
@@ -734,11 +763,11 @@ __global__ __launch_bounds__(64 * NW, MINW) void ext_attn_il_kernel(P p) {
 
 template <typename T, int DH, int NW, int MODE, int MINW, int DMA = 0, typename P>
 int launch_il(const P& p_in, hipStream_t st) {
-    std::conditional_t<win_launch<P, MODE>, P, AttnParams> p = p_in;   // the kernel's parameter block
+    launch_params_t<P, MODE> p = p_in;   // the kernel's parameter block
     typedef AttnCfg<DH> C;
     constexpr size_t lds = MODE == MODE_DUAL ? 2 * (size_t)(C::K_ELEMS + ((2 * DH + 31) / 32) * 32 * C::VROW) * 2   // packed dual-V image
                                              : C::lds_bytes(1);
-    if (tf_plan_note("il<%d,%d,%s,%d,%d%s>%s", DH, NW, mode_name(MODE), MINW, DMA, run_mark<MODE>(p), is_win<decltype(p)> ? ",win" : ""))
+    if (tf_plan_note("il<%d,%d,%s,%d,%d%s>%s", DH, NW, mode_name(MODE), MINW, DMA, run_mark<MODE>(p), table_mark<decltype(p)>()))
         return 0;
     auto kern = ext_attn_il_kernel<T, DH, NW, MODE, MINW, DMA, decltype(p)>;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,

@@ -138,6 +138,18 @@ __global__ __launch_bounds__(64 * NW, MINW) void ext_attn_kernel(P p) {
             return;
         }
     }
+    [[maybe_unused]] uint64_t run = 0;   // frame-set launches: the member frames of this problem (see set_run, SetWalk)
+    if constexpr (is_set<P>) {   // a bank problem reads the member frames of its query frame's set, in ascending order
+        run = (uint64_t)1 << f_lo;   // (a source problem: its own frame)
+        if (b > 0) {
+            run = set_run(p, f, seg, nseg, n_fr);
+            if (n_fr == 0) {   // a set shorter than the split: this run holds no member
+                write_empty_run(p, b - 1, NB, f, h, seg, qt * (32 * QT * NW), 32 * QT * NW, DH, NT);
+                return;
+            }
+            f_lo = __builtin_ctzll(run);
+        }
+    }
     const int tpf = (S + KT - 1) / KT;  // staged tiles per frame
     const int ntiles = n_fr * tpf;
     const bool ragged = (S % KT) != 0;
@@ -200,7 +212,9 @@ __global__ __launch_bounds__(64 * NW, MINW) void ext_attn_kernel(P p) {
         const int ppf = p.Spad / 64;   // 64-key blocks per frame; this problem sees frames f_lo .. f_lo + n_fr - 1
         const float* part = p.knorm2 + ((int64_t)(bq * H + h) * p.Kb + f_lo) * ppf;
         float kn2 = 0.f;
-        for (int i = lane; i < n_fr * ppf; i += 64) kn2 = fmaxf(kn2, part[i]);
+        if constexpr (is_set<P>) kn2 = set_knorm2(part - (int64_t)f_lo * ppf, run, ppf, lane);   // the member frames' blocks only
+        else
+            for (int i = lane; i < n_fr * ppf; i += 64) kn2 = fmaxf(kn2, part[i]);
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) kn2 = fmaxf(kn2, __shfl_xor(kn2, o));
         const float kn = __builtin_sqrtf(kn2) * 1.001f;
@@ -246,6 +260,8 @@ __global__ __launch_bounds__(64 * NW, MINW) void ext_attn_kernel(P p) {
 #pragma unroll
     for (int vb = 0; vb < NB; ++vb) v_next[vb] = vg[vb] + (int64_t)f_lo * p.Spad;
     int ld_tt = 0;
+    [[maybe_unused]] SetWalk walk{};   // frame-set launches: K and V^T move together here, one walk serves both
+    if constexpr (is_set<P>) walk.init(run);
     auto stage_load = [&]() {
         const bool wrap = ld_tt == tpf - 1;
         const int rlim = wrap ? k_wrap - 1 : KT - 1;   // last valid key row of this tile (rows past S are masked later)
@@ -259,6 +275,14 @@ __global__ __launch_bounds__(64 * NW, MINW) void ext_attn_kernel(P p) {
             v_next[vb] += wrap ? v_wrap : KT;
         }
         k_next += wrap ? k_wrap_off : (int64_t)KT * p.ld;
+        if constexpr (is_set<P>) {
+            if (wrap) {   // the next member frame: the frames between it and this one are skipped
+                const int skip = walk.hop();
+                k_next += (int64_t)skip * p.k_fs;
+#pragma unroll
+                for (int vb = 0; vb < NB; ++vb) v_next[vb] += (int64_t)skip * p.Spad;
+            }
+        }
         ld_tt = wrap ? 0 : ld_tt + 1;
     };
     auto stage_write = [&](int buf) {
@@ -644,13 +668,13 @@ __global__ __launch_bounds__(64 * NW, MINW) void ext_attn_kernel(P p) {
 // tests/golden/kernel_plans.json.
 template <typename T, int DH, int NW, int MODE, int MINW, bool FQ = true, bool SB = false, typename P>
 int launch_one(const P& p_in, hipStream_t st) {
-    std::conditional_t<win_launch<P, MODE>, P, AttnParams> p = p_in;   // the kernel's parameter block
+    launch_params_t<P, MODE> p = p_in;   // the kernel's parameter block
     typedef AttnCfg<DH> C;
     constexpr size_t lds = ((MODE == MODE_DUAL && DH == 40)  ? 2 * (size_t)(C::K_ELEMS + 96 * C::VROW) * 2    // PACK
                             : (MODE == MODE_MV4 && DH == 40) ? 2 * (size_t)(C::K_ELEMS + 192 * C::VROW) * 2   // PACK, four banks
                                                              : C::lds_bytes(MODE == MODE_DUAL ? 2 : MODE == MODE_MV4 ? 4 : 1)) / (SB ? 2 : 1);
     if (tf_plan_note("one<%d,1,%d,%s,%d,fq%d%s%s>%s", DH, NW, mode_name(MODE), MINW, FQ ? 1 : 0, SB ? ",sb" : "", run_mark<MODE>(p),
-                     is_win<decltype(p)> ? ",win" : ""))
+                     table_mark<decltype(p)>()))
         return 0;
     auto kern = ext_attn_kernel<T, DH, 1, NW, MODE, MINW, 64, FQ, SB, decltype(p)>;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,

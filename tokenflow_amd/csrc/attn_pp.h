@@ -99,6 +99,14 @@ __global__ __launch_bounds__(256, 2) void ext_attn_pp_kernel(P p) {
     if constexpr (is_win<P>) {   // a bank problem reads its query frame's window of the bank (this kernel has no split form)
         if (b > 0) window_range(p, f, 0, 1, f_lo, n_fr);
     }
+    [[maybe_unused]] uint64_t run = 0;   // frame-set launches: the member frames of this problem (see set_run, SetWalk)
+    if constexpr (is_set<P>) {   // a bank problem reads the member frames of its query frame's set, in ascending order
+        run = (uint64_t)1 << f_lo;   // (a source problem: its own frame)
+        if (b > 0) {
+            run = set_run(p, f, 0, 1, n_fr);   // (no split form: a set holds at least its own frame)
+            f_lo = __builtin_ctzll(run);
+        }
+    }
     const int tpf = (S + 63) >> 6;
     const int ntiles = n_fr * tpf;
     const bool ragged = (S & 63) != 0;
@@ -155,6 +163,8 @@ __global__ __launch_bounds__(256, 2) void ext_attn_pp_kernel(P p) {
     const E* k_next = kg + f_lo * p.k_fs;   // first row of the next K tile to load
     const E* v_next = vg + (int64_t)f_lo * p.Spad;
     int k_tt = 0, v_tt = 0;                            // its tile index within the frame
+    [[maybe_unused]] SetWalk k_walk{}, v_walk{};       // frame-set launches: the member frame each cursor stands in
+    if constexpr (is_set<P>) k_walk.init(run), v_walk.init(run);
     auto load_k = [&]() {
         const bool wrap = k_tt == tpf - 1;
         const int rlim = wrap ? k_wrap - 1 : 63;
@@ -162,6 +172,9 @@ __global__ __launch_bounds__(256, 2) void ext_attn_pp_kernel(P p) {
 #pragma unroll
         for (int i = 0; i < NPK; ++i) rk[i] = ld16(k_next + (k_row[i] <= rlim ? k_goff[i] : clamp_off + k_col[i]));
         k_next += wrap ? k_wrap_off : (int64_t)64 * p.ld;
+        if constexpr (is_set<P>) {
+            if (wrap) k_next += (int64_t)k_walk.hop() * p.k_fs;   // on to the next member frame
+        }
         k_tt = wrap ? 0 : k_tt + 1;
     };
     auto load_v = [&]() {
@@ -169,6 +182,9 @@ __global__ __launch_bounds__(256, 2) void ext_attn_pp_kernel(P p) {
         for (int i = 0; i < NPV; ++i) rv[i] = ld16(v_next + v_goff[i]);
         const bool wrap = v_tt == tpf - 1;
         v_next += wrap ? v_wrap : 64;
+        if constexpr (is_set<P>) {
+            if (wrap) v_next += (int64_t)v_walk.hop() * p.Spad;
+        }
         v_tt = wrap ? 0 : v_tt + 1;
     };
     auto write_k = [&](int buf) {
@@ -387,9 +403,9 @@ __global__ __launch_bounds__(256, 2) void ext_attn_pp_kernel(P p) {
 // Plan token `pp<64,ALL..>`: the head dim and the problem set the kernel is written for.
 template <typename T, bool RUN = false, typename P>
 int launch_pp(const P& p_in, hipStream_t st) {
-    std::conditional_t<win_launch<P, MODE_ALL, RUN>, P, AttnParams> p = p_in;   // the kernel's parameter block
+    launch_params_t<P, MODE_ALL, RUN> p = p_in;   // the kernel's parameter block
     constexpr size_t lds = AttnCfg<64>::lds_bytes(1);
-    if (tf_plan_note("pp<64,ALL%s>%s", RUN ? ",run" : "", is_win<decltype(p)> ? ",win" : "")) return 0;
+    if (tf_plan_note("pp<64,ALL%s>%s", RUN ? ",run" : "", table_mark<decltype(p)>())) return 0;
     auto kern = ext_attn_pp_kernel<T, RUN, decltype(p)>;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)lds);

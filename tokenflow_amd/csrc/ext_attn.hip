@@ -86,7 +86,7 @@ static int split_plan(int K, int Kq, int S, int H, int Dh, bool inject, int part
 // Dh=64: 2 query tiles/wave (each LDS fragment feeds 2 MFMAs).  Dh=80/160: register-bound, 1 tile/wave.
 template <typename T, int DH, typename P>
 int launch_attn(const P& p, const void* v, hipStream_t st) {
-    constexpr bool WIN = is_win<P>;   // windowed call: no run or folded-scale form (refused by the entry points)
+    constexpr bool WIN = is_win<P> || is_set<P>;   // windowed / frame-set call: no run or folded-scale form (refused by the entry points)
     const bool src_only = p.part == TF_ATTN_SOURCE_ONLY, bank_only = p.part == TF_ATTN_BANK_ONLY;
     // The kernel FAMILY of a run launch is the one the unsplit call of the same (Kq, S, H) takes, however the run splits
     // itself: the source branch out of a run call is then bit for bit the source-only call's (same kernel, same keys).
@@ -356,9 +356,18 @@ struct WinPart {
     int K_max;
 };
 
+// A call over a frame-set bank (tf_ext_attn_fwd_frame_sets): the validated member masks and the largest set -- the bank size at
+// which the call picks its kernel forms.
+struct SetPart {
+    const uint64_t* set;   // [Kq]: bit j = bank frame j is a member
+    int K_max;
+};
+
 int attn_fwd_core(const void* q, const void* k, const void* v, void* out, int K, int Kq, int q_frame0, int S, int H, int Dh,
                   int64_t ld, const int64_t* strides, float scale, int inject, int dtype, void* ws, size_t ws_bytes,
-                  void* stream, const EditsPart* ed, const SegPart* sg = nullptr, const WinPart* wn = nullptr) {
+                  void* stream, const EditsPart* ed, const SegPart* sg = nullptr, const WinPart* wn = nullptr,
+                  const SetPart* fs = nullptr) {
+    const int K_plan = wn ? wn->K_max : fs ? fs->K_max : K;   // windows / frame sets: planned for the longest window / largest set
     TF_ARG(q && k && v && out && ws && strides, TF_ERR_NULL, "tf_ext_attn_fwd: null pointer");
     TF_ARG(dtype == TF_BF16 || dtype == TF_F16, TF_ERR_DTYPE, "tf_ext_attn_fwd: dtype %d (bf16/f16 only)", dtype);
     TF_ARG(Dh == 40 || Dh == 64 || Dh == 80 || Dh == 160, TF_ERR_SHAPE,
@@ -389,7 +398,7 @@ int attn_fwd_core(const void* q, const void* k, const void* v, void* out, int K,
         a.q_bs = strides[0], a.q_fs = strides[1], a.ld_q = ld_q;
         a.k_bs = strides[2], a.k_fs = strides[3], a.v_bs = strides[4], a.v_fs = strides[5], a.ld = ld;
         a.o_bs = strides[6], a.o_fs = strides[7];
-        a.H = H, a.Kq = Kq, a.q_frame0 = q_frame0, a.Kb = wn ? wn->K_max : K;   // (windows: planned for the longest window)
+        a.H = H, a.Kq = Kq, a.q_frame0 = q_frame0, a.Kb = K_plan;
         a.b0 = part_bits == TF_ATTN_BANK_ONLY ? 1 : 0;
         a.nb = part_bits == TF_ATTN_BANK_ONLY ? 2 : part_bits == TF_ATTN_SOURCE_ONLY ? 1 : 3;
         const TfFusedPlan plan = tf_attn_fused_plan(&a, 1, S, Dh, dtype, inject);
@@ -397,7 +406,7 @@ int attn_fwd_core(const void* q, const void* k, const void* v, void* out, int K,
         a.Kb = K;
         if (plan.use)
             return tf_attn_fused_launch(&a, 1, S, Dh, scale, inject, dtype, plan, reinterpret_cast<hipStream_t>(stream),
-                                        wn ? wn->win : nullptr);
+                                        wn ? wn->win : nullptr, fs ? fs->set : nullptr);
     }
     const int Spad = ((S + 127) / 128) * 128;
     const int shift = ed ? ed->shift : 0;
@@ -423,7 +432,7 @@ int attn_fwd_core(const void* q, const void* k, const void* v, void* out, int K,
     p.part = inject & (TF_ATTN_BANK_ONLY | TF_ATTN_SOURCE_ONLY);
     p.fold = (inject & TF_ATTN_FOLD_SCALE) ? 1 : 0;
     p.out_f32 = (inject & TF_ATTN_OUT_F32) ? 1 : 0;
-    p.nseg = split_plan(wn ? wn->K_max : K, Kq, S, H, Dh, p.inject != 0, p.part, !(inject & TF_ATTN_NO_SPLIT));
+    p.nseg = split_plan(K_plan, Kq, S, H, Dh, p.inject != 0, p.part, !(inject & TF_ATTN_NO_SPLIT));
     p.Kb = Kb;
     if (sg) {   // a keyframe segment: its window of the whole bank's image and norm table
         p.vt = w8 + (size_t)sg->f0 * Spad * 2;
@@ -458,6 +467,14 @@ int attn_fwd_core(const void* q, const void* k, const void* v, void* out, int K,
         static_cast<AttnParams&>(pw) = p;
         for (int i = 0; i < Kq; ++i) pw.win[i] = wn->win[i];
         return dtype == TF_BF16 ? dispatch_dh<BF16>(Dh, pw, v, st) : dispatch_dh<F16>(Dh, pw, v, st);
+    }
+    if (fs) {   // the same launches with the member masks behind the parameter block; the same check of the partial results
+        TF_ARG((size_t)2 * Kq * H * S * p.pslots * (Dh + 8) <= attn_part_elems(K, S, H, Dh), TF_ERR_WORKSPACE,
+               "tf_ext_attn_fwd_frame_sets: %d partial-result slots do not fit the workspace of a %d-frame bank", p.pslots, K);
+        AttnParamsSet ps{};
+        static_cast<AttnParams&>(ps) = p;
+        for (int i = 0; i < Kq; ++i) ps.set[i] = fs->set[i];
+        return dtype == TF_BF16 ? dispatch_dh<BF16>(Dh, ps, v, st) : dispatch_dh<F16>(Dh, ps, v, st);
     }
     return dtype == TF_BF16 ? dispatch_dh<BF16>(Dh, p, v, st) : dispatch_dh<F16>(Dh, p, v, st);
 }
@@ -1394,5 +1411,69 @@ extern "C" int tf_ext_attn_windows_edits_plan(int K, int Kq, int q_frame0, int S
     tf_plan_rec = nullptr;
     if (rc) return rc;
     TF_ARG(rec.used < len, TF_ERR_WORKSPACE, "tf_ext_attn_windows_edits_plan: the plan needs %zu bytes", rec.used + 1);
+    return rec.n;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Frame-set keyframe bank (include/tokenflow_hip.h): the uncond / cond branches of query frame i attend to the keys of the bank
+// frames whose bits are set in sets[i], in ascending frame order.  A table of contiguous ranges IS tf_ext_attn_fwd_windows on
+// the equivalent (lo, n) table (and so tf_ext_attn_fwd_strided when every set is the whole bank): delegated here, so those paths
+// are reached unchanged.  Everything else: the launches of tf_ext_attn_fwd_strided for a bank of max_i popcount(sets[i]) frames
+// -- ONE pre-pass over the whole bank, ONE bank launch whose problems walk their frame's member mask from the table in the
+// kernel arguments -- so frame i's result is what its own call (the strided call on its member frames, gathered) computes.
+extern "C" int tf_ext_attn_fwd_frame_sets(const void* q, const void* k, const void* v, void* out, int K, int Kq, int q_frame0,
+                                          int S, int H, int Dh, int64_t ld, const int64_t* strides, float scale, int flags,
+                                          int dtype, const uint64_t* sets, void* ws, size_t ws_bytes, void* stream) {
+    const char* const name = "tf_ext_attn_fwd_frame_sets";
+    TF_ARG(sets, TF_ERR_NULL, "%s: null set table", name);
+    TF_ARG(K > 0 && Kq > 0 && q_frame0 >= 0 && q_frame0 + Kq <= K, TF_ERR_SHAPE,
+           "%s: query frames [%d, %d) outside the %d-frame bank", name, q_frame0, q_frame0 + Kq, K);
+    TF_ARG(K <= 64, TF_ERR_SHAPE, "%s: K=%d (a set is a 64-bit mask: at most 64 bank frames)", name, K);
+    TF_ARG(Kq <= TF_MAX_WINDOW_FRAMES, TF_ERR_SHAPE, "%s: Kq=%d (at most %d query frames carry a set)", name, Kq,
+           TF_MAX_WINDOW_FRAMES);
+    int win_lo[TF_MAX_WINDOW_FRAMES], win_n[TF_MAX_WINDOW_FRAMES], K_max = 0;
+    bool ranges = true;
+    for (int i = 0; i < Kq; ++i) {
+        const uint64_t m = sets[i];
+        const int own = q_frame0 + i;
+        TF_ARG(m != 0, TF_ERR_SHAPE, "%s: set %d is empty", name, i);
+        TF_ARG(K == 64 || !(m >> K), TF_ERR_SHAPE, "%s: set %d = 0x%llx has bits at or above the %d-frame bank", name, i,
+               (unsigned long long)m, K);
+        TF_ARG((m >> own) & 1u, TF_ERR_SHAPE, "%s: set %d = 0x%llx does not hold its own frame %d", name, i, (unsigned long long)m,
+               own);
+        const int lo = __builtin_ctzll(m), n = __builtin_popcountll(m);
+        win_lo[i] = lo, win_n[i] = n;
+        ranges = ranges && (m >> lo) == (n == 64 ? ~(uint64_t)0 : ((uint64_t)1 << n) - 1);
+        K_max = n > K_max ? n : K_max;
+    }
+    constexpr int REFUSED = TF_ATTN_BANK_ONLY | TF_ATTN_SOURCE_ONLY | TF_ATTN_FOLD_SCALE | TF_ATTN_MULTI_V | TF_ATTN_NO_MULTI_V |
+                            TF_ATTN_MULTI_V64 | TF_ATTN_RUN_MULTI_V;
+    TF_ARG(!(flags & REFUSED), TF_ERR_SHAPE,
+           "%s: flags 0x%x -- TF_ATTN_BANK_ONLY / TF_ATTN_SOURCE_ONLY / TF_ATTN_FOLD_SCALE and the multi-edit hints have no "
+           "frame-set form", name, flags & REFUSED);
+    if (ranges)   // every set a contiguous range: the windowed call (which is the plain call where every range is the bank)
+        return tf_ext_attn_fwd_windows(q, k, v, out, K, Kq, q_frame0, S, H, Dh, ld, strides, scale, flags, dtype, win_lo, win_n, ws,
+                                       ws_bytes, stream);
+    const SetPart fs{sets, K_max};
+    return attn_fwd_core(q, k, v, out, K, Kq, q_frame0, S, H, Dh, ld, strides, scale, flags, dtype, ws, ws_bytes, stream, nullptr,
+                         nullptr, nullptr, &fs);
+}
+
+// Launch plan of tf_ext_attn_fwd_frame_sets for dense tensors (host only): the entry point itself under the plan recorder.
+extern "C" int tf_ext_attn_frame_sets_plan(int K, int Kq, int q_frame0, int S, int H, int Dh, int flags, int dtype,
+                                           const uint64_t* sets, char* buf, size_t len) {
+    TF_ARG(K > 0 && S > 0 && H > 0 && Kq > 0 && Kq <= K, TF_ERR_SHAPE, "tf_ext_attn_frame_sets_plan: K=%d Kq=%d S=%d H=%d", K, Kq,
+           S, H);
+    void* const ph = reinterpret_cast<void*>((uintptr_t)1 << 12);
+    const int64_t ld = (int64_t)H * Dh, fs = (int64_t)S * ld;
+    const int64_t strides[9] = {Kq * fs, fs, K * fs, fs, K * fs, fs, Kq * fs, fs, ld};
+    TfPlanRec rec{buf, len, 0, 0};
+    if (buf && len) buf[0] = 0;
+    tf_plan_rec = &rec;
+    const int rc = tf_ext_attn_fwd_frame_sets(ph, ph, ph, ph, K, Kq, q_frame0, S, H, Dh, ld, strides, 1.0f, flags, dtype, sets, ph,
+                                              tf_ext_attn_workspace_bytes(K, S, H, Dh, dtype), nullptr);
+    tf_plan_rec = nullptr;
+    if (rc) return rc;
+    TF_ARG(rec.used < len, TF_ERR_WORKSPACE, "tf_ext_attn_frame_sets_plan: the plan needs %zu bytes", rec.used + 1);
     return rec.n;
 }

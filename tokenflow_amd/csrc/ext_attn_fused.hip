@@ -113,6 +113,21 @@ struct FusedParamsWin {
     unsigned win[TF_MAX_WINDOW_FRAMES];   // query frame i: first bank frame of its window | frames << 16
 };
 
+// A one-set launch over a frame-set bank (tf_ext_attn_fwd_frame_sets): one 64-bit member mask per query frame behind the
+// parameters.  A type of its own once more: every other launch keeps its parameter block and its code.
+struct FusedParamsSet {
+    static constexpr int MAX_SETS = 1;
+    FusedSet set[MAX_SETS];
+    int n_sets, S, nQT, tpf;
+    unsigned tpf_magic;
+    int inject, out_f32;
+    float c;
+    float lag;
+    uint64_t fset[TF_MAX_WINDOW_FRAMES];   // query frame i: bit j = its bank branches read bank frame j
+};
+template <typename P>
+constexpr bool is_fset = std::is_same<P, FusedParamsSet>::value;
+
 __device__ __forceinline__ float max_xor32(float x) {
     const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
     return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
@@ -169,8 +184,31 @@ __device__ __forceinline__ Problem decode_problem(const P& p) {
             pr.f_lo = (int)(w & 0xffffu), pr.n_fr = (int)(w >> 16);
         }
     }
+    if constexpr (is_fset<P>) {   // a bank problem reads the members of its query frame's set: n_fr of them, mapped by FrameMap
+        if (pr.b > 0) pr.n_fr = __builtin_popcountll(p.fset[pr.f]);
+    }
     return pr;
 }
+
+// Frame-set launches: member index (what Cursor.fr counts) -> bank frame, the fr-th set bit of the problem's mask.  A load
+// cursor's fr only grows, so the map keeps the mask of the members from its last answer on and pops the difference.
+// Wave-uniform (the mask comes from the kernel arguments, fr from the wave's index).  A source problem (its own frame, already
+// in f_lo) and every other launch type: the identity on a mask of one.
+struct FrameMap {
+    uint64_t rest;
+    int idx;
+    template <typename P>
+    __device__ __forceinline__ void init(const P& p, const Problem& pr) {
+        idx = 0, rest = 1;
+        if constexpr (is_fset<P>) {
+            if (pr.b > 0) rest = p.fset[pr.f];
+        }
+    }
+    __device__ __forceinline__ int frame(int fr) {
+        while (idx < fr) rest &= rest - 1, ++idx;
+        return __builtin_ctzll(rest);
+    }
+};
 
 // Wave-uniform cursor over the sub-tiles j0, j0 + step, ... of a problem's key sequence (frames of tpf sub-tiles);
 // past the end it stays on the last sub-tile, so that the branch-free staging loads always have a valid address.
@@ -396,10 +434,14 @@ __global__ __launch_bounds__(64 * QW * KW, 1) void ext_attn_fused_kernel(P p) {
     Cursor ldc, cc;   // sub-tile being loaded / computed
     ldc.init(kw, tpf, nst);
     cc.init(kw, tpf, nst);
+    [[maybe_unused]] FrameMap ldm;   // frame-set launches: the load cursor's member index -> bank frame (the compute side needs none)
+    if constexpr (is_fset<P>) ldm.init(p, pr);
     auto stage_load = [&]() {
         const int nvalid = min(32, S - ldc.tt * 32);
-        const E* kb = kg + ldc.fr * k_fs + (int64_t)(ldc.tt * 32) * ld;
-        const E* vb = vg + ldc.fr * v_fs + (int64_t)(ldc.tt * 32) * ld;
+        int fr = ldc.fr;
+        if constexpr (is_fset<P>) fr = ldm.frame(fr);
+        const E* kb = kg + fr * k_fs + (int64_t)(ldc.tt * 32) * ld;
+        const E* vb = vg + fr * v_fs + (int64_t)(ldc.tt * 32) * ld;
 #pragma unroll
         for (int i = 0; i < NP; ++i) {
             const int off = min(s_row[i], nvalid - 1) * ld + s_col[i];
@@ -549,18 +591,24 @@ __global__ __launch_bounds__(64 * KW, 1) void ext_attn_fused_wp_kernel(P p) {
     Cursor ldk, ldv;
     ldk.init(kw, tpf, nst);
     ldv.init(kw, tpf, nst);
+    [[maybe_unused]] FrameMap mk, mv;   // frame-set launches: each load cursor's member index -> bank frame
+    if constexpr (is_fset<P>) mk.init(p, pr), mv.init(p, pr);
     int key0_k = 0;   // first key (inside its frame) of the sub-tile whose K fragments sit in rk
     auto load_k = [&]() {
         const int nvalid = min(32, S - ldk.tt * 32);
         key0_k = ldk.tt * 32;
-        const E* kb = kg + ldk.fr * k_fs + (int64_t)(ldk.tt * 32) * ld + min(l31, nvalid - 1) * ld + 8 * hi;
+        int fr = ldk.fr;
+        if constexpr (is_fset<P>) fr = mk.frame(fr);
+        const E* kb = kg + fr * k_fs + (int64_t)(ldk.tt * 32) * ld + min(l31, nvalid - 1) * ld + 8 * hi;
 #pragma unroll
         for (int t = 0; t < C::KS; ++t) rk[t] = (16 * t + 8 * hi < DH) ? ld16(kb + 16 * t) : u32x4{0, 0, 0, 0};
         ldk.advance(KW, tpf, nst);
     };
     auto load_v = [&]() {
         const int nvalid = min(32, S - ldv.tt * 32);
-        const E* vb = vg + ldv.fr * v_fs + (int64_t)(ldv.tt * 32) * ld + min(v_row, nvalid - 1) * ld;
+        int fr = ldv.fr;
+        if constexpr (is_fset<P>) fr = mv.frame(fr);
+        const E* vb = vg + fr * v_fs + (int64_t)(ldv.tt * 32) * ld + min(v_row, nvalid - 1) * ld;
 #pragma unroll
         for (int i = 0; i < NPH; ++i) rv[i] = ld16(vb + min(v_pc0 + i, C::PPR - 1) * 8);
         ldv.advance(KW, tpf, nst);
@@ -648,6 +696,7 @@ template <typename P>
 bool fused_note(const P& p, int qw, int kw, int qb, int prec) {
     if (p.n_sets > 2 || tf_plan_sets_note) return tf_plan_note("fused[qw=%d,kw=%d,qb=%d,prec=%d,sets=%d]", qw, kw, qb, prec, p.n_sets);
     if (std::is_same<P, FusedParamsWin>::value) return tf_plan_note("fused[qw=%d,kw=%d,qb=%d,prec=%d,win]", qw, kw, qb, prec);
+    if (is_fset<P>) return tf_plan_note("fused[qw=%d,kw=%d,qb=%d,prec=%d,set]", qw, kw, qb, prec);
     return tf_plan_note("fused[qw=%d,kw=%d,qb=%d,prec=%d]", qw, kw, qb, prec);
 }
 
@@ -780,10 +829,13 @@ TfFusedPlan tf_attn_fused_plan(const TfAttnSet* sets, int n_sets, int S, int Dh,
 
 template <typename P>
 static int fused_launch_sets(const TfAttnSet* sets, int n_sets, int S, int Dh, float scale, int flags, int dtype,
-                             const TfFusedPlan& plan, int inject0, hipStream_t st, const unsigned* win = nullptr) {
+                             const TfFusedPlan& plan, int inject0, hipStream_t st, const unsigned* win = nullptr,
+                             const uint64_t* frame_set = nullptr) {
     P p{};
     if constexpr (std::is_same<P, FusedParamsWin>::value)
         for (int i = 0; i < sets[0].Kq; ++i) p.win[i] = win[i];
+    if constexpr (is_fset<P>)
+        for (int i = 0; i < sets[0].Kq; ++i) p.fset[i] = frame_set[i];
     p.n_sets = n_sets;
     p.S = S;
     p.nQT = (S + 32 * plan.qw * plan.qb - 1) / (32 * plan.qw * plan.qb);
@@ -817,8 +869,14 @@ static int fused_launch_sets(const TfAttnSet* sets, int n_sets, int S, int Dh, f
 }
 
 int tf_attn_fused_launch(const TfAttnSet* sets, int n_sets, int S, int Dh, float scale, int flags, int dtype,
-                         const TfFusedPlan& plan, hipStream_t st, const unsigned* win) {
+                         const TfFusedPlan& plan, hipStream_t st, const unsigned* win, const uint64_t* frame_set) {
     TF_ARG(sets && n_sets >= 1 && n_sets <= 1 + TF_MAX_EDITS, TF_ERR_SHAPE, "tf_ext_attn_fwd(fused): %d tensor sets", n_sets);
+    if (frame_set) {
+        TF_ARG(!win && n_sets == 1 && sets[0].Kq <= TF_MAX_WINDOW_FRAMES, TF_ERR_SHAPE,
+               "tf_ext_attn_fwd(fused): a frame-set table serves one set of at most %d query frames", TF_MAX_WINDOW_FRAMES);
+        const int inj = ((flags & TF_ATTN_INJECT) || sets[0].inject) ? 1 : 0;
+        return fused_launch_sets<FusedParamsSet>(sets, 1, S, Dh, scale, flags, dtype, plan, inj, st, nullptr, frame_set);
+    }
     if (win) {
         TF_ARG(n_sets == 1 && sets[0].Kq <= TF_MAX_WINDOW_FRAMES, TF_ERR_SHAPE,
                "tf_ext_attn_fwd(fused): a window table serves one set of at most %d query frames", TF_MAX_WINDOW_FRAMES);

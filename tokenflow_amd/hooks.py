@@ -249,7 +249,7 @@ def _segments(module, K=None):
     return segs
 
 
-def register_bank_window(model, radius, edits=False):
+def register_bank_window(model, radius, edits=False, anchors=None):
     """Sliding-window keyframe bank (no counterpart in the reference, where every keyframe attends to the whole bank): in the
     pivotal passes that follow, the uncond / cond branches of keyframe i attend to the keyframes i - radius .. i + radius only
     (clamped to the bank; `ops.bank_windows`), the source branch to its own frame as always.  Consistency stays chained along
@@ -262,6 +262,14 @@ def register_bank_window(model, radius, edits=False):
     `register_edit_schedules`): the pivotal pass is then ONE `ops.ext_attn_windows_edits` over all 1 + 2E branches -- every
     edit's bank branches attend to the windows, with the per-edit injection mask of the step.  Without the keyword a window
     in a multi-edit batch stays an error, as before.
+    anchors adds global ANCHOR keyframes that every keyframe sees beside its window -- a sequence of keyframe indices, or an
+    int m >= 1 for every m-th keyframe (0, m, 2m, ...); None or an empty sequence: none.  A purely local window has no global
+    reference; with A anchors a keyframe attends to at most 2 radius + 1 + A keyframes, still linear in K.  Stored as
+    `bank_window_anchors` beside `bank_window` and resolved against K at the pivotal pass (an index >= K is a ValueError
+    there); the installers then call `ops.ext_attn_frame_sets(.., ops.bank_frame_sets(K, radius, anchors))` whenever
+    radius < K - 1.  Without anchors the call is `ops.ext_attn_windows` exactly as before; with a covering radius today's
+    full-bank ops are issued whatever the anchors.  This, too, is NOT TokenFlow's result.  Anchors in a multi-edit batch
+    (edits=True, E > 1) are not generalised: ValueError at the pass.
     Not generalised, ValueError at the call: `register_edits(model, E > 1)` unless edits=True, `register_segments` with several
     segments, a registered frame shard -- there the radius is held against the shard's WHOLE bank (`shard.K`), not the rank's
     local keyframes, and only a radius that covers it passes -- and, as for every multi-edit pass, graph capture
@@ -270,16 +278,31 @@ def register_bank_window(model, radius, edits=False):
         radius = int(radius)
         if radius < 0:
             raise ValueError(f"register_bank_window: radius={radius} (>= 0, or None for the whole bank)")
-    _set_bank_window(_hook_blocks(model.unet), radius, bool(edits) and radius is not None)
+    if anchors is not None and not isinstance(anchors, bool) and isinstance(anchors, int):
+        if anchors < 1:
+            raise ValueError(f"register_bank_window: anchors={anchors} (every m-th keyframe: m >= 1)")
+    elif anchors is not None:
+        try:
+            anchors = tuple(anchors)
+            bad = [a for a in anchors if isinstance(a, bool) or int(a) != a or int(a) < 0]
+        except (TypeError, ValueError):
+            bad = [anchors]
+        if bad:
+            raise ValueError(f"register_bank_window: anchors={anchors!r} (keyframe indices >= 0, an int m >= 1 for every m-th "
+                             "keyframe, or None)")
+        anchors = tuple(int(a) for a in anchors) or None
+    _set_bank_window(_hook_blocks(model.unet), radius, bool(edits) and radius is not None,
+                     anchors if radius is not None else None)
 
 
-def _set_bank_window(blocks, radius, edits=False):
-    """`bank_window` (and `bank_window_edits`, the multi-edit opt-in) on transformer blocks and their `attn1`
-    (register_bank_window; tools on a bare block list)."""
+def _set_bank_window(blocks, radius, edits=False, anchors=None):
+    """`bank_window` (`bank_window_edits`, the multi-edit opt-in, and `bank_window_anchors`: a tuple of keyframe indices, an
+    int stride or None) on transformer blocks and their `attn1` (register_bank_window; tools on a bare block list)."""
     for tb in blocks:
         for m in (tb, tb.attn1):
             setattr(m, "bank_window", radius)
             setattr(m, "bank_window_edits", edits)
+            setattr(m, "bank_window_anchors", anchors)
 
 
 def _bank_window(module, K: int):
@@ -304,6 +327,23 @@ def _bank_window(module, K: int):
         raise ValueError("register_bank_window: a sliding-window bank in a pass of several keyframe segments "
                          "(register_segments) is not supported")
     return radius
+
+
+def _bank_anchors(module, K: int):
+    """The anchor keyframes of a windowed pivotal pass of K keyframes (register_bank_window(anchors=...)) as a tuple of
+    indices, or None: call where `_bank_window(module, K)` has returned a radius.  The combination that is not generalised and
+    an index outside the pass raise."""
+    anchors = getattr(module, "bank_window_anchors", None)
+    if anchors is None:
+        return None
+    if int(getattr(module, "n_edits", 1)) > 1:
+        raise ValueError("register_bank_window: anchor keyframes in a multi-edit batch (register_edits, n_edits > 1) are not "
+                         "supported")
+    if isinstance(anchors, int):
+        return tuple(range(0, K, anchors))
+    if max(anchors) >= K:
+        raise ValueError(f"register_bank_window: anchors={list(anchors)} in a pivotal pass of {K} keyframes (indices < {K})")
+    return anchors
 
 
 _latents_cache = collections.OrderedDict()
@@ -541,6 +581,7 @@ def _make_sa_forward(self, pnp: bool):
         E = 1 if is_cross else _n_edits(self)
         # (a window excludes segments and shards, and edits unless opted in; the pass carries q.shape[0] / (1 + 2E) keyframes)
         radius = None if is_cross else _bank_window(self, q.shape[0] // (1 + 2 * E))
+        anchors = None if radius is None else _bank_anchors(self, q.shape[0] // (1 + 2 * E))
         segs = None if is_cross else _segments(self, q.shape[0] // 3)
         # the edits that inject (one shared schedule: all or none; register_edit_schedules: each edit's own)
         mask = _inject_mask(self, E) if pnp else 0
@@ -554,6 +595,9 @@ def _make_sa_forward(self, pnp: bool):
         elif radius is not None and E > 1:   # ... several prompts on a long video: every edit's bank branches read the windows
             out = ops.ext_attn_windows_edits(q, k, v, self.heads, self.scale, False, E,
                                              ops.bank_windows(q.shape[0] // (1 + 2 * E), radius), inject_mask=mask)
+        elif anchors is not None:   # ... and to the global anchor keyframes (E = 1: anchors in a multi-edit batch raise)
+            out = ops.ext_attn_frame_sets(q, k, v, self.heads, self.scale, inject,
+                                          ops.bank_frame_sets(q.shape[0] // 3, radius, anchors))
         elif radius is not None:  # long videos: a bank branch attends to the neighbouring keyframes only
             out = ops.ext_attn_windows(q, k, v, self.heads, self.scale, inject, ops.bank_windows(q.shape[0] // 3, radius))
         elif segs is not None:    # several scenes or clips: a bank branch attends to the keyframes of its own segment
@@ -770,7 +814,9 @@ def make_tokenflow_attention_block(block_class: Type[torch.nn.Module]) -> Type[t
                     raise ValueError(f"register_edits: batch of {batch_size} does not hold {nbr} branches ({E} edits)")
             n_frames = batch_size // nbr
             if self.pivotal_pass:
-                _bank_window(self, n_frames)   # register_bank_window: the combinations that are not generalised raise here
+                # register_bank_window: the combinations that are not generalised raise here
+                if _bank_window(self, n_frames) is not None:
+                    _bank_anchors(self, n_frames)
             hidden_states = hidden_states.view(nbr, n_frames, sequence_length, dim)
 
             norm_inv = None

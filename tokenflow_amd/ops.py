@@ -265,6 +265,48 @@ def attn_windows_edits_plan(K: int, windows, S: int, heads: int, dh: int, n_edit
                         int(n_edits), mask, flags, _DT[dtype], ctypes.cast(lo, ctypes.c_void_p), ctypes.cast(n, ctypes.c_void_p))
 
 
+def bank_frame_sets(K: int, radius: int, anchors=()) -> list:
+    """The frame sets of an anchored sliding-window bank, one int mask per keyframe: bit j of mask i = keyframe i attends to
+    keyframe j.  Mask i is window i of `bank_windows(K, radius)` plus every anchor (global keyframes that all keyframes see;
+    0 <= a < K, duplicates are fine).  No anchors give the windows as masks; radius >= K - 1 gives K full sets."""
+    K = int(K)
+    anc = 0
+    for a in anchors:
+        if isinstance(a, bool) or int(a) != a or not 0 <= int(a) < K:
+            raise ValueError(f"bank_frame_sets: anchor {a!r} (keyframe indices 0 <= a < {K})")
+        anc |= 1 << int(a)
+    return [(((1 << n) - 1) << lo) | anc for lo, n in bank_windows(K, radius)]
+
+
+def _frame_sets(what: str, sets, K: int, Kq: int, q_frame0: int = 0):
+    """The set table of a call as a ctypes uint64 array: one non-empty mask per query frame, inside the bank, holding its own
+    frame."""
+    masks = [int(m) for m in sets]
+    if K > 64:
+        raise ValueError(f"{what}: K={K} (a set is a 64-bit mask: at most 64 bank frames)")
+    if len(masks) != Kq or not 1 <= Kq <= _lib.TF_MAX_WINDOW_FRAMES:
+        raise ValueError(f"{what}: {len(masks)} sets for {Kq} query frames (one each, at most {_lib.TF_MAX_WINDOW_FRAMES})")
+    for i, m in enumerate(masks):
+        if m <= 0 or m >> K:
+            raise ValueError(f"{what}: set {i} = {m:#x} (>= 1 frames inside the {K}-frame bank)")
+        if not (m >> (q_frame0 + i)) & 1:
+            raise ValueError(f"{what}: set {i} = {m:#x} does not hold its own frame {q_frame0 + i}")
+    return (ctypes.c_uint64 * Kq)(*masks)
+
+
+def attn_frame_sets_plan(K: int, sets, S: int, heads: int, dh: int, inject: bool, dtype: torch.dtype = torch.bfloat16,
+                         out_dtype: Optional[torch.dtype] = None, no_split: Optional[bool] = None,
+                         fused: Optional[bool] = None, hints: int = 0) -> list:
+    """The launches `ext_attn_frame_sets` makes for dense [3K,S,heads*dh] tensors, as tokens (tf_ext_attn_frame_sets_plan: the
+    tokens of `attn_plan` with ',set' appended to the launch that walks the sets, e.g. ['vt_pack', 'il<40,8,ALL,4,2>,set'] or
+    ['fused[qw=1,kw=4,qb=1,prec=1,set]']; sets that are all contiguous ranges give `attn_windows_plan`, K full sets
+    `attn_plan(K, K, ...)`).  Host only: needs no GPU."""
+    tab = _frame_sets("attn_frame_sets_plan", sets, K, K)
+    flags = _attn_flags(inject, "all", out_dtype == torch.float32, False, no_split, fused, hints)
+    return _plan_tokens("tf_ext_attn_frame_sets_plan", _lib.load().tf_ext_attn_frame_sets_plan, K, K, 0, S, heads, dh, flags,
+                        _DT[dtype], ctypes.cast(tab, ctypes.c_void_p))
+
+
 def _single_mask(what: str, mask, C: int) -> int:
     m = int(mask)
     if not 1 <= C <= 64 or m < 0 or m >> C:
@@ -434,6 +476,59 @@ def ext_attn_windows(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: i
     _launch(dev, "tf_ext_attn_fwd_windows", lib.tf_ext_attn_fwd_windows, q.data_ptr(), k.data_ptr(), v.data_ptr(),
             out.data_ptr(), K, K, 0, S, heads, dh, ld, ctypes.cast(strides, ctypes.c_void_p), float(scale), flags, dt,
             ctypes.cast(lo, ctypes.c_void_p), ctypes.cast(n, ctypes.c_void_p), ws.data_ptr(), ws.numel())
+    return out
+
+
+def ext_attn_frame_sets(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, scale: float, inject: bool, sets, *,
+                        no_split: Optional[bool] = None, fused: Optional[bool] = None, hints: int = 0,
+                        out_dtype: Optional[torch.dtype] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`ext_attn` over a frame-set keyframe bank (tf_ext_attn_fwd_frame_sets): q, k, v [3K,S,D] as there, `sets` one int mask
+    per keyframe (`bank_frame_sets(K, radius, anchors)`: a sliding window plus global anchor keyframes; any other sparsity is
+    a table of masks too).  The uncond / cond branches of keyframe i attend to the keys of the keyframes whose bits are set
+    in mask i, in ascending order -- under `inject` with the source's q and k -- and the source branch to its own frame.  NOT
+    TokenFlow's computation unless every set is the whole bank (then the call is `ext_attn`, bit for bit; sets that are all
+    contiguous ranges are `ext_attn_windows`).  One launch for all keyframes; keyframe i's slices are what `ext_attn`
+    computes on the member frames of set i gathered next to each other (Kq = 1), bit for bit under no_split wherever both
+    take the same kernel form.  Arguments as `ext_attn_windows`, with masks instead of pairs."""
+    dev = _need_gpu(q, k, v, out)
+    lib = _lib.load()
+    B, S, D = k.shape
+    if B % 3 or D % heads or q.shape != k.shape or v.shape != k.shape:
+        raise ValueError(f"ext_attn_frame_sets: bad shapes q{tuple(q.shape)} k{tuple(k.shape)} v{tuple(v.shape)} heads {heads}")
+    K, dh = B // 3, D // heads
+    tab = _frame_sets("ext_attn_frame_sets", sets, K, K)
+    dt = _DT.get(q.dtype)
+    if dt is None or dt == _lib.TF_F32 or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise TypeError(f"ext_attn_frame_sets: q/k/v must share dtype bf16 or f16, got {q.dtype},{k.dtype},{v.dtype}")
+
+    def rows(t):
+        if t.stride(-1) != 1 or t.stride(0) != S * t.stride(1):
+            t = t.contiguous()
+        return t
+    q, k, v = rows(q), rows(k), rows(v)
+    ld = q.stride(1)
+    if k.stride(1) != ld or v.stride(1) != ld:
+        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        ld = D
+    if out_dtype is None:
+        out_dtype = out.dtype if out is not None else q.dtype
+    if out_dtype not in (q.dtype, torch.float32):
+        raise TypeError(f"ext_attn_frame_sets: out_dtype {out_dtype} (the input dtype or float32)")
+    if out is None:
+        out = torch.empty(B, S, D, dtype=out_dtype, device=q.device)
+    elif out.dtype != out_dtype or not out.is_contiguous() or out.shape != (B, S, D):
+        raise ValueError("ext_attn_frame_sets: `out` must be a contiguous [3K,S,D] tensor of out_dtype")
+    flags = _attn_flags(inject, "all", out_dtype == torch.float32, False, no_split, fused, hints)
+    key = (K, S, heads, dh, dt)
+    nbytes = _attn_ws_bytes.get(key)
+    if nbytes is None:
+        nbytes = _attn_ws_bytes[key] = lib.tf_ext_attn_workspace_bytes(K, S, heads, dh, dt)
+    ws = _workspace(nbytes, q.device)
+    fs, ofs = S * ld, S * D   # dense [3, K, S, ld] tensors, out [3, K, S, D]
+    strides = (ctypes.c_int64 * 9)(K * fs, fs, K * fs, fs, K * fs, fs, K * ofs, ofs, ld)
+    _launch(dev, "tf_ext_attn_fwd_frame_sets", lib.tf_ext_attn_fwd_frame_sets, q.data_ptr(), k.data_ptr(), v.data_ptr(),
+            out.data_ptr(), K, K, 0, S, heads, dh, ld, ctypes.cast(strides, ctypes.c_void_p), float(scale), flags, dt,
+            ctypes.cast(tab, ctypes.c_void_p), ws.data_ptr(), ws.numel())
     return out
 
 

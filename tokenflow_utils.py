@@ -13,7 +13,8 @@ from tokenflow_amd.hooks import (  # noqa: F401
 # register_edits: multi-edit extension (several prompts on one source video in one pass), not part of it either;
 # register_edit_schedules: the edits' own injection schedules
 # register_segments: keyframe-segment extension (several scenes or clips in one pass)
-# register_bank_window: sliding-window bank extension (a keyframe attends to its neighbouring keyframes only: long videos)
+# register_bank_window: sliding-window bank extension (a keyframe attends to its neighbouring keyframes only: long videos;
+# anchors=... adds global anchor keyframes that every keyframe sees)
 
 # `from tokenflow_utils import *` in the reference also leaks these two names (its module does
 # `import torch, os` at top level, tokenflow_utils.py:2-3); keep that surface identical.
