@@ -778,7 +778,8 @@ TF_API int tf_ext_attn_windows_edits_plan(int K, int Kq, int q_frame0, int S, in
  *   TF_ATTN_NO_SPLIT wherever the two plans name the same kernel form: the key tiles arrive in the same order, and the
  *   Cauchy-Schwarz score bound (head dims 40 and 64) is the maximum key norm over the MEMBER frames only, not over the span
  *   from the first to the last member (a superset would give another shift).
- *   Not built: the four-bank form, multi-edit batches, keyframe segments and frame shards over frame sets.
+ *   Multi-edit batches and the four-bank form over frame sets: tf_ext_attn_fwd_frame_sets_edits, below.
+ *   Not built: keyframe segments, frame shards and the run forms over frame sets.
  *   ws: tf_ext_attn_workspace_bytes(K, ...), unchanged.
  * tf_ext_attn_frame_sets_plan: the launches of the call for dense tensors (host only), the tokens of tf_ext_attn_plan.
  * ------------------------------------------------------------------------ */
@@ -788,6 +789,58 @@ TF_API int tf_ext_attn_fwd_frame_sets(const void* q, const void* k, const void* 
 
 TF_API int tf_ext_attn_frame_sets_plan(int K, int Kq, int q_frame0, int S, int H, int Dh, int flags, int dtype,
                                 const uint64_t* sets, char* buf, size_t len);
+
+/* ------------------------------------------------------------------------
+ * Frame-set bank for a MULTI-EDIT batch (additive to ABI 11): several prompts on one long video in one pass, with anchor
+ * keyframes beside the window.  Like the windowed and the frame-set call this CHANGES THE RESULT relative to TokenFlow unless
+ * every set is the whole bank.
+ *
+ * tf_ext_attn_fwd_frame_sets_edits: q, k, v, out, strides, n_edits and inject_mask as tf_ext_attn_fwd_edits_masked -- B = 1 + 2E
+ *   branches [source | uncond_1 | cond_1 | ...], bit e of the mask = edit e uses the source's q and k -- and sets as
+ *   tf_ext_attn_fwd_frame_sets (a HOST array of Kq 64-bit masks, validated the same way).  The uncond / cond branches of EVERY
+ *   edit attend, for query frame i, to the member frames of sets[i] in ascending order; the source branch to its own frame,
+ *   once; nothing mixes edits.
+ *   Refused before anything touches the device: what tf_ext_attn_fwd_frame_sets refuses of its table (a null table:
+ *     TF_ERR_NULL; with TF_ERR_SHAPE K > 64, Kq > TF_MAX_WINDOW_FRAMES, an empty set, a bit at or above K, a set without its own
+ *     frame), the flags tf_ext_attn_fwd_windows_edits refuses (TF_ATTN_BANK_ONLY, TF_ATTN_SOURCE_ONLY, TF_ATTN_FOLD_SCALE,
+ *     TF_ATTN_RUN_MULTI_V), and what the masked call refuses (TF_ATTN_INJECT beside the mask, mask bits at or above n_edits,
+ *     n_edits outside 1 .. TF_MAX_EDITS, TF_ATTN_NO_MULTI_V beside TF_ATTN_MULTI_V or TF_ATTN_MULTI_V64).  TF_ATTN_MULTI_V,
+ *     TF_ATTN_NO_MULTI_V and TF_ATTN_MULTI_V64 are ACCEPTED here (tf_ext_attn_fwd_frame_sets keeps refusing them).
+ *   Canonical forms: same launches, same bits, same plan tokens.  n_edits = 1 IS tf_ext_attn_fwd_frame_sets.  If every set is a
+ *   contiguous range the call IS tf_ext_attn_fwd_windows_edits on the equivalent (lo, n) table; so every set = [0, K) IS
+ *   tf_ext_attn_fwd_edits_masked.
+ *   Otherwise the call is the masked composition with the set table handed to every bank part; as in the frame-set call the
+ *   fused-kernel decision, the split and the kernel forms are planned for K' = max_i popcount(sets[i]), frame-set launches
+ *   carry ",set" in the plan, and the table rides in the kernel arguments (no device table, no copy, no sync):
+ *     - ONE V^T pre-pass over the span of the streaming branches;
+ *     - the injecting edits first: pairs in the frame-set four-bank form where it is selected (below), an odd one in the DUAL
+ *       set launch beside them; without the form each through the launches of its own frame-set bank-only call;
+ *     - the edits that do not inject, each through its frame-set bank-only launches (il<..>,set, one<..>,set, pp<..>,set,
+ *       fused[..,set]);
+ *     - the source branch last, through the plain source-only launches.
+ *   Identity.  Edit e's bank branches are BIT-IDENTICAL to those of tf_ext_attn_fwd_frame_sets on [source | uncond_e | cond_e]
+ *   with edit e's own injection flag, and its source branch to that call's source slice, under TF_ATTN_NO_SPLIT wherever both
+ *   plans name the same kernel form; always within the attention bound of the oracle on the gathered member frames.
+ *   The frame-set four-bank form: one<40,1,4,MV4,2,fq0>,set (Dh = 40, the packed six-M-tile image) and one<64,1,8,MV4,2,fq1>,set
+ *   (Dh = 64, four 64-row banks, scores per 32-key half).  One workgroup computes QK^T and the softmax of query frame f once,
+ *   over the member frames of set f, and the four P.V products of branches b, b + 1, b + gap, b + gap + 1: all four banks take
+ *   the SAME hops.  The score bound is the maximum key norm over the member frames of the source's norm row.  Pair launches are
+ *   one-pass (TF_ATTN_NO_SPLIT | TF_ATTN_NO_FUSED), as in the masked call.  Frame i's OWN CALL is tf_ext_attn_fwd_edits_masked
+ *   with the four-bank hint on the GATHERED member frames of set i (ascending), (K, Kq, q_frame0) = (popcount(sets[i]), 1, rank
+ *   of the own frame among the members): the frame-set pair launch is bit-identical to it.
+ *   TF_ATTN_MULTI_V (Dh = 40) / TF_ATTN_MULTI_V64 (Dh = 64) force the form on, TF_ATTN_NO_MULTI_V forces it off.  The measured
+ *   defaults of the whole-bank and of the windowed call say nothing about sets: the rule of this call (mv4_set_default in
+ *   csrc/ext_attn.hip) is written from profiles/r21_frame_sets_edits_ab.txt alone.
+ *   ws: tf_ext_attn_edits_workspace_bytes(K, ...), unchanged.
+ * tf_ext_attn_frame_sets_edits_plan: the launches of the call for dense tensors (host only), the tokens of tf_ext_attn_plan.
+ * ------------------------------------------------------------------------ */
+TF_API int tf_ext_attn_fwd_frame_sets_edits(const void* q, const void* k, const void* v, void* out, int K, int Kq, int q_frame0,
+                                     int S, int H, int Dh, int64_t ld, const int64_t* strides, float scale, int flags,
+                                     int dtype, int n_edits, unsigned inject_mask, const uint64_t* sets, void* ws,
+                                     size_t ws_bytes, void* stream);
+
+TF_API int tf_ext_attn_frame_sets_edits_plan(int K, int Kq, int q_frame0, int S, int H, int Dh, int n_edits, unsigned inject_mask,
+                                      int flags, int dtype, const uint64_t* sets, char* buf, size_t len);
 
 /* ------------------------------------------------------------------------
  * Row LayerNorm producer  --  the `norm1` call of TokenFlowBlock.forward

@@ -164,6 +164,12 @@ _SIGNATURES = {
     "tf_ext_attn_fwd_frame_sets": (_c.c_int, [_c.c_void_p] * 4 + [_c.c_int] * 6 + [_c.c_int64, _c.c_void_p, _c.c_float, _c.c_int,
                                               _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "tf_ext_attn_frame_sets_plan": (_c.c_int, [_c.c_int] * 8 + [_c.c_void_p, _c.c_char_p, _c.c_size_t]),
+    # ... for a multi-edit batch: several prompts with anchor keyframes in one pass (additive to ABI 11)
+    "tf_ext_attn_fwd_frame_sets_edits": (_c.c_int, [_c.c_void_p] * 4 + [_c.c_int] * 6 + [_c.c_int64, _c.c_void_p, _c.c_float,
+                                                    _c.c_int, _c.c_int, _c.c_int, _c.c_uint, _c.c_void_p, _c.c_void_p,
+                                                    _c.c_size_t, _c.c_void_p]),
+    "tf_ext_attn_frame_sets_edits_plan": (_c.c_int, [_c.c_int] * 7 + [_c.c_uint, _c.c_int, _c.c_int, _c.c_void_p, _c.c_char_p,
+                                                     _c.c_size_t]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -213,10 +213,11 @@ static inline const char* run_mark(const AttnParams& p) { return (p.run && MODE 
 template <typename P, int MODE, bool RUN = false>
 constexpr bool win_launch = is_win<P> && (MODE == MODE_ALL || MODE == MODE_DUAL || MODE == MODE_MV4) && !RUN;
 
-// A frame-set launch (AttnParamsSet) likewise, for the ALL and DUAL forms (tf_ext_attn_fwd_frame_sets; the four-bank form has
-// no frame-set instantiation).  Plan token: the plain launch's with ",set" appended.
+// A frame-set launch (AttnParamsSet) likewise: the ALL and DUAL forms (tf_ext_attn_fwd_frame_sets) and the four-bank form of a
+// pair of injecting edits (tf_ext_attn_fwd_frame_sets_edits: the four banks of a workgroup walk the SAME member frames, their
+// query frame's set, and take every hop together).  Plan token: the plain launch's with ",set" appended.
 template <typename P, int MODE, bool RUN = false>
-constexpr bool set_launch = is_set<P> && (MODE == MODE_ALL || MODE == MODE_DUAL) && !RUN;
+constexpr bool set_launch = is_set<P> && (MODE == MODE_ALL || MODE == MODE_DUAL || MODE == MODE_MV4) && !RUN;
 
 // The parameter block a launch hands its kernel: the caller's where the launch has a windowed / frame-set instantiation, the
 // plain one otherwise; and the mark its plan token carries

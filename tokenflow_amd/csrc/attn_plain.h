@@ -22,6 +22,9 @@ namespace {
 //                     edits; the masked multi-edit call pairs the INJECTING edits, whatever lies between them).
 //                     Dh = 40: the packed image (PACK below).  Dh = 64: four 64-row banks side by side, 8 M-tiles, one row
 //                     sum for all four (no ones row), the scores taken per 32-key half (HALF below).
+//                     Over a frame set (P = AttnParamsSet) the K cursor and all four V^T cursors hop together in stage_load;
+//                     everything else that looks at a tile's position -- the ragged masking, the HALF steps, the PACK image
+//                     -- works on the tile index INSIDE its frame (tt_cur, ld_tt), which a hop does not touch.
 // MINW = min waves per SIMD for the register allocator
 // FQ   = fold the softmax scale into Q (see FOLD below; opt-in, TF_ATTN_FOLD_SCALE); false = the default, fp32
 //        scaling of the scores as the reference does (tokenflow_utils.py:173-175 `* self.scale` on the bmm output)
@@ -143,7 +146,8 @@ __global__ __launch_bounds__(64 * NW, MINW) void ext_attn_kernel(P p) {
         run = (uint64_t)1 << f_lo;   // (a source problem: its own frame)
         if (b > 0) {
             run = set_run(p, f, seg, nseg, n_fr);
-            if (n_fr == 0) {   // a set shorter than the split: this run holds no member
+            if (n_fr == 0) {   // a set shorter than the split: this run holds no member (never in the four-bank form, whose
+                               // launches are one-pass: nseg = 1 and a set holds at least its own frame)
                 write_empty_run(p, b - 1, NB, f, h, seg, qt * (32 * QT * NW), 32 * QT * NW, DH, NT);
                 return;
             }

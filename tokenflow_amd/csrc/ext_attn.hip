@@ -538,12 +538,32 @@ static bool mv4_win_default(int K, int K_max, int Kq, int S, int H, int Dh) {
     return Dh == 40 && H == 8 && K == 8 && S == 4096;
 }
 
+// The four-bank form in a FRAME-SET multi-edit call (tf_ext_attn_fwd_frame_sets_edits; K_max = the largest set).  The three rules
+// above speak of whole banks or of radius-2 windows and say nothing about sets: this one is written from the three-arm A/B of
+// profiles/r21_frame_sets_edits_ab.txt alone and covers only the shape classes in which the forced form is ahead of the DUAL
+// composition by more than the run-to-run spread of both arms (E single-edit frame-set calls of the parent build / the DUAL
+// composition / the four-bank form forced; radius 2 with anchor keyframe 0 -- a largest set of 6 frames -- at the level-0 shapes
+// of BASELINE configs 2, 4 and 5, E = 2 and 3).  It is in all three, at E = 2 / E = 3 (medians, spreads of 0.1 to 1.5 % per arm):
+//   Dh = 64, (K, S, H) = (25, 4096, 5):  7.96 against 10.40 ms (-23 %) / 12.65 against 15.21 ms (-17 %)
+//   Dh = 64, (K, S, H) = (10, 9216, 5): 15.21 against 19.80 ms (-23 %) / 24.72 against 29.33 ms (-16 %)
+//   Dh = 40, (K, S, H) = (8, 4096, 8):   2.72 against  2.94 ms (-8 %)  /  4.08 against  4.28 ms (-5 %)
+// The rule is what those cells span and no more: every keyframe's queries, a largest set of 6 frames; at Dh = 64 the box of the
+// two shapes (5 heads, banks of 10 to 25 keyframes, whole 64-key tiles, frames of 4096 to 9216 tokens), at Dh = 40 the one shape.
+// Other radii and anchor counts, head counts, frame sizes and query-frame subsets were not measured and stay behind
+// TF_ATTN_MULTI_V / TF_ATTN_MULTI_V64.
+static bool mv4_set_default(int K, int K_max, int Kq, int S, int H, int Dh) {
+    if (Kq != K || K_max != 6) return false;
+    if (Dh == 64) return H == 5 && K >= 10 && K <= 25 && S % 64 == 0 && S >= 4096 && S <= 9216;
+    return Dh == 40 && H == 8 && K == 8 && S == 4096;
+}
+
 // The masked composition: bit e of inject_mask = edit e injects (its uncond and cond branches use the source's q and k).
 // tf_ext_attn_fwd_edits is the two uniform masks of it.
 static int attn_fwd_edits_masked(const char* name, const void* q, const void* k, const void* v, void* out, int K, int Kq,
                                  int q_frame0, int S, int H, int Dh, int64_t ld, const int64_t* strides, float scale, int flags,
                                  int dtype, int n_edits, unsigned inject_mask, void* ws, size_t ws_bytes, void* stream,
-                                 bool part_call = false, int qk_compact = 0, const WinPart* wn = nullptr) {
+                                 bool part_call = false, int qk_compact = 0, const WinPart* wn = nullptr,
+                                 const SetPart* fs = nullptr) {
     TF_ARG(n_edits >= 1 && n_edits <= TF_MAX_EDITS, TF_ERR_SHAPE, "%s: n_edits=%d (1 .. %d)", name, n_edits, TF_MAX_EDITS);
     TF_ARG(q && k && v && out && ws && strides, TF_ERR_NULL, "%s: null pointer", name);
     TF_ARG(dtype == TF_BF16 || dtype == TF_F16, TF_ERR_DTYPE, "%s: dtype %d (bf16/f16 only)", name, dtype);
@@ -569,7 +589,7 @@ static int attn_fwd_edits_masked(const char* name, const void* q, const void* k,
     if (n_edits == 1)   // today's layout: today's call (the hints of the four-bank form have nothing to select); the compact
                         // q / k of one edit is the dense one as far as its launches read it
         return attn_fwd_core(q, k, v, out, K, Kq, q_frame0, S, H, Dh, ld, strides, scale,
-                             base | part | (inject_mask ? TF_ATTN_INJECT : 0), dtype, ws, ws_bytes, stream, nullptr, nullptr, wn);
+                             base | part | (inject_mask ? TF_ATTN_INJECT : 0), dtype, ws, ws_bytes, stream, nullptr, nullptr, wn, fs);
     const int B = 1 + 2 * n_edits;
     int inj_e[TF_MAX_EDITS], non_e[TF_MAX_EDITS], n_inj = 0, n_non = 0;   // the injecting / the other edits, ascending
     int qk_sh[TF_MAX_EDITS];   // q / k branch slots in front of edit e's uncond slot, minus 1 (an injecting edit reads slot 0)
@@ -584,10 +604,11 @@ static int attn_fwd_edits_masked(const char* name, const void* q, const void* k,
     // the four-bank form: Dh = 40 or 64 (each behind its own hint and its own measured default), fp32 score scaling, at least
     // one pair of INJECTING edits
     const bool mv_ok = n_inj >= 2 && (Dh == 40 || Dh == 64) && !(flags & TF_ATTN_FOLD_SCALE);
-    // (the two measured defaults speak of whole banks: a windowed call has its own rule)
-    const bool mv_on = Dh == 40 ? ((flags & TF_ATTN_MULTI_V) || (wn ? mv4_win_default(K, wn->K_max, Kq, S, H, Dh) : mv4_default(K, Kq, S, H)))
-                                : ((flags & TF_ATTN_MULTI_V64) ||
-                                   (wn ? mv4_win_default(K, wn->K_max, Kq, S, H, Dh) : mv4_d64_default(K, Kq, S, H)));
+    // (the two measured defaults speak of whole banks: a windowed and a frame-set call have a rule of their own each)
+    const bool mv_dflt = wn ? mv4_win_default(K, wn->K_max, Kq, S, H, Dh)
+                       : fs ? mv4_set_default(K, fs->K_max, Kq, S, H, Dh)
+                            : (Dh == 40 ? mv4_default(K, Kq, S, H) : mv4_d64_default(K, Kq, S, H));
+    const bool mv_on = (flags & (Dh == 40 ? TF_ATTN_MULTI_V : TF_ATTN_MULTI_V64)) || mv_dflt;
     const bool mv = mv_ok && !(flags & TF_ATTN_NO_MULTI_V) && mv_on;
     // the pair launches and the odd edit beside them are one-pass streaming launches
     const int inj_flags = base | TF_ATTN_INJECT | TF_ATTN_BANK_ONLY | (mv ? TF_ATTN_NO_SPLIT | TF_ATTN_NO_FUSED : 0);
@@ -599,11 +620,13 @@ static int attn_fwd_edits_masked(const char* name, const void* q, const void* k,
         const int sh = 2 * e;
         const bool inj = (fl & TF_ATTN_INJECT) != 0;
         const int qsh = (fl & TF_ATTN_SOURCE_ONLY) ? 0 : qk_sh[e];
-        // a sliding-window bank (tf_ext_attn_fwd_windows_edits): every bank part reads the windows; the source part is the plain
-        // source-only call (a source problem reads its own frame whatever the windows)
+        // a sliding-window bank (tf_ext_attn_fwd_windows_edits) or a frame-set bank (tf_ext_attn_fwd_frame_sets_edits): every bank
+        // part reads the table; the source part is the plain source-only call (a source problem reads its own frame whatever
+        // the table)
         return attn_fwd_core(inj ? q : at(q, qsh * strides[0], 2), inj ? k : at(k, qsh * strides[2], 2), at(v, sh * strides[4], 2),
                              const_cast<void*>(at(out, sh * strides[6], osz)), K, Kq, q_frame0, S, H, Dh, ld, strides, scale, fl,
-                             dtype, ws, ws_bytes, stream, &ed, nullptr, (fl & TF_ATTN_SOURCE_ONLY) ? nullptr : wn);
+                             dtype, ws, ws_bytes, stream, &ed, nullptr, (fl & TF_ATTN_SOURCE_ONLY) ? nullptr : wn,
+                             (fl & TF_ATTN_SOURCE_ONLY) ? nullptr : fs);
     };
     // which parts stream (and read the V^T image): the decision of the part's own call
     const EditsPart probe = EditsPart::probe_of(B);
@@ -1421,18 +1444,17 @@ extern "C" int tf_ext_attn_windows_edits_plan(int K, int Kq, int q_frame0, int S
 // are reached unchanged.  Everything else: the launches of tf_ext_attn_fwd_strided for a bank of max_i popcount(sets[i]) frames
 // -- ONE pre-pass over the whole bank, ONE bank launch whose problems walk their frame's member mask from the table in the
 // kernel arguments -- so frame i's result is what its own call (the strided call on its member frames, gathered) computes.
-extern "C" int tf_ext_attn_fwd_frame_sets(const void* q, const void* k, const void* v, void* out, int K, int Kq, int q_frame0,
-                                          int S, int H, int Dh, int64_t ld, const int64_t* strides, float scale, int flags,
-                                          int dtype, const uint64_t* sets, void* ws, size_t ws_bytes, void* stream) {
-    const char* const name = "tf_ext_attn_fwd_frame_sets";
+//
+// The set table of a call (this one's and tf_ext_attn_fwd_frame_sets_edits'), validated: the equivalent (lo, n) table, the largest set, and whether every set is a contiguous range.
+static int frame_sets_check(const char* name, int K, int Kq, int q_frame0, const uint64_t* sets, int* win_lo, int* win_n,
+                            int* K_max, bool* ranges) {
     TF_ARG(sets, TF_ERR_NULL, "%s: null set table", name);
     TF_ARG(K > 0 && Kq > 0 && q_frame0 >= 0 && q_frame0 + Kq <= K, TF_ERR_SHAPE,
            "%s: query frames [%d, %d) outside the %d-frame bank", name, q_frame0, q_frame0 + Kq, K);
     TF_ARG(K <= 64, TF_ERR_SHAPE, "%s: K=%d (a set is a 64-bit mask: at most 64 bank frames)", name, K);
     TF_ARG(Kq <= TF_MAX_WINDOW_FRAMES, TF_ERR_SHAPE, "%s: Kq=%d (at most %d query frames carry a set)", name, Kq,
            TF_MAX_WINDOW_FRAMES);
-    int win_lo[TF_MAX_WINDOW_FRAMES], win_n[TF_MAX_WINDOW_FRAMES], K_max = 0;
-    bool ranges = true;
+    *K_max = 0, *ranges = true;
     for (int i = 0; i < Kq; ++i) {
         const uint64_t m = sets[i];
         const int own = q_frame0 + i;
@@ -1443,9 +1465,19 @@ extern "C" int tf_ext_attn_fwd_frame_sets(const void* q, const void* k, const vo
                own);
         const int lo = __builtin_ctzll(m), n = __builtin_popcountll(m);
         win_lo[i] = lo, win_n[i] = n;
-        ranges = ranges && (m >> lo) == (n == 64 ? ~(uint64_t)0 : ((uint64_t)1 << n) - 1);
-        K_max = n > K_max ? n : K_max;
+        *ranges = *ranges && (m >> lo) == (n == 64 ? ~(uint64_t)0 : ((uint64_t)1 << n) - 1);
+        *K_max = n > *K_max ? n : *K_max;
     }
+    return 0;
+}
+
+extern "C" int tf_ext_attn_fwd_frame_sets(const void* q, const void* k, const void* v, void* out, int K, int Kq, int q_frame0,
+                                          int S, int H, int Dh, int64_t ld, const int64_t* strides, float scale, int flags,
+                                          int dtype, const uint64_t* sets, void* ws, size_t ws_bytes, void* stream) {
+    const char* const name = "tf_ext_attn_fwd_frame_sets";
+    int win_lo[TF_MAX_WINDOW_FRAMES], win_n[TF_MAX_WINDOW_FRAMES], K_max = 0;
+    bool ranges = true;
+    if (const int rc = frame_sets_check(name, K, Kq, q_frame0, sets, win_lo, win_n, &K_max, &ranges)) return rc;
     constexpr int REFUSED = TF_ATTN_BANK_ONLY | TF_ATTN_SOURCE_ONLY | TF_ATTN_FOLD_SCALE | TF_ATTN_MULTI_V | TF_ATTN_NO_MULTI_V |
                             TF_ATTN_MULTI_V64 | TF_ATTN_RUN_MULTI_V;
     TF_ARG(!(flags & REFUSED), TF_ERR_SHAPE,
@@ -1475,5 +1507,61 @@ extern "C" int tf_ext_attn_frame_sets_plan(int K, int Kq, int q_frame0, int S, i
     tf_plan_rec = nullptr;
     if (rc) return rc;
     TF_ARG(rec.used < len, TF_ERR_WORKSPACE, "tf_ext_attn_frame_sets_plan: the plan needs %zu bytes", rec.used + 1);
+    return rec.n;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Frame-set bank for a multi-edit batch (include/tokenflow_hip.h): the masked composition with the set table handed to every bank
+// part -- ONE pre-pass, the injecting edits (pairs in the frame-set four-bank form where it is selected, an odd one in the DUAL set
+// launch), the others through their bank-only set launches, then the plain source-only launches.  A table of contiguous ranges is
+// handed on as the equivalent window table: the launches of tf_ext_attn_fwd_windows_edits (of tf_ext_attn_fwd_edits_masked where
+// every range is the bank).
+extern "C" int tf_ext_attn_fwd_frame_sets_edits(const void* q, const void* k, const void* v, void* out, int K, int Kq, int q_frame0,
+                                                int S, int H, int Dh, int64_t ld, const int64_t* strides, float scale, int flags,
+                                                int dtype, int n_edits, unsigned inject_mask, const uint64_t* sets, void* ws,
+                                                size_t ws_bytes, void* stream) {
+    const char* const name = "tf_ext_attn_fwd_frame_sets_edits";
+    int win_lo[TF_MAX_WINDOW_FRAMES], win_n[TF_MAX_WINDOW_FRAMES], K_max = 0;
+    bool ranges = true;
+    if (const int rc = frame_sets_check(name, K, Kq, q_frame0, sets, win_lo, win_n, &K_max, &ranges)) return rc;
+    // (the multi-edit hints TF_ATTN_MULTI_V / TF_ATTN_NO_MULTI_V / TF_ATTN_MULTI_V64 select the pair form here)
+    constexpr int REFUSED = TF_ATTN_BANK_ONLY | TF_ATTN_SOURCE_ONLY | TF_ATTN_FOLD_SCALE | TF_ATTN_RUN_MULTI_V;
+    TF_ARG(!(flags & REFUSED), TF_ERR_SHAPE,
+           "%s: flags 0x%x -- TF_ATTN_BANK_ONLY / TF_ATTN_SOURCE_ONLY / TF_ATTN_FOLD_SCALE / TF_ATTN_RUN_MULTI_V have no frame-set "
+           "form", name, flags & REFUSED);
+    if (ranges) {   // the windowed multi-edit call's launches (a checked set table is a valid window table)
+        unsigned win[TF_MAX_WINDOW_FRAMES];
+        bool full = true;
+        for (int i = 0; i < Kq; ++i) {
+            win[i] = (unsigned)win_lo[i] | ((unsigned)win_n[i] << 16);
+            full = full && win_n[i] == K;
+        }
+        const WinPart wn{win, K_max};
+        return attn_fwd_edits_masked(name, q, k, v, out, K, Kq, q_frame0, S, H, Dh, ld, strides, scale, flags, dtype, n_edits,
+                                     inject_mask, ws, ws_bytes, stream, false, 0, full ? nullptr : &wn);
+    }
+    // (n_edits = 1: the masked composition is attn_fwd_core on today's layout, here with the set table: tf_ext_attn_fwd_frame_sets)
+    const SetPart fs{sets, K_max};
+    return attn_fwd_edits_masked(name, q, k, v, out, K, Kq, q_frame0, S, H, Dh, ld, strides, scale, flags, dtype, n_edits,
+                                 inject_mask, ws, ws_bytes, stream, false, 0, nullptr, &fs);
+}
+
+// Launch plan of tf_ext_attn_fwd_frame_sets_edits for dense tensors (host only): the entry point itself under the plan recorder.
+extern "C" int tf_ext_attn_frame_sets_edits_plan(int K, int Kq, int q_frame0, int S, int H, int Dh, int n_edits,
+                                                 unsigned inject_mask, int flags, int dtype, const uint64_t* sets, char* buf,
+                                                 size_t len) {
+    TF_ARG(K > 0 && S > 0 && H > 0 && Kq > 0 && Kq <= K, TF_ERR_SHAPE, "tf_ext_attn_frame_sets_edits_plan: K=%d Kq=%d S=%d H=%d", K,
+           Kq, S, H);
+    void* const ph = reinterpret_cast<void*>((uintptr_t)1 << 12);
+    const int64_t ld = (int64_t)H * Dh, fs = (int64_t)S * ld;
+    const int64_t strides[9] = {Kq * fs, fs, K * fs, fs, K * fs, fs, Kq * fs, fs, ld};
+    TfPlanRec rec{buf, len, 0, 0};
+    if (buf && len) buf[0] = 0;
+    tf_plan_rec = &rec;
+    const int rc = tf_ext_attn_fwd_frame_sets_edits(ph, ph, ph, ph, K, Kq, q_frame0, S, H, Dh, ld, strides, 1.0f, flags, dtype,
+                                                    n_edits, inject_mask, sets, ph, (size_t)-1, nullptr);
+    tf_plan_rec = nullptr;
+    if (rc) return rc;
+    TF_ARG(rec.used < len, TF_ERR_WORKSPACE, "tf_ext_attn_frame_sets_edits_plan: the plan needs %zu bytes", rec.used + 1);
     return rec.n;
 }

@@ -249,7 +249,7 @@ def _segments(module, K=None):
     return segs
 
 
-def register_bank_window(model, radius, edits=False, anchors=None):
+def register_bank_window(model, radius, edits=False, anchors=None, anchor_edits=False):
     """Sliding-window keyframe bank (no counterpart in the reference, where every keyframe attends to the whole bank): in the
     pivotal passes that follow, the uncond / cond branches of keyframe i attend to the keyframes i - radius .. i + radius only
     (clamped to the bank; `ops.bank_windows`), the source branch to its own frame as always.  Consistency stays chained along
@@ -268,8 +268,11 @@ def register_bank_window(model, radius, edits=False, anchors=None):
     `bank_window_anchors` beside `bank_window` and resolved against K at the pivotal pass (an index >= K is a ValueError
     there); the installers then call `ops.ext_attn_frame_sets(.., ops.bank_frame_sets(K, radius, anchors))` whenever
     radius < K - 1.  Without anchors the call is `ops.ext_attn_windows` exactly as before; with a covering radius today's
-    full-bank ops are issued whatever the anchors.  This, too, is NOT TokenFlow's result.  Anchors in a multi-edit batch
-    (edits=True, E > 1) are not generalised: ValueError at the pass.
+    full-bank ops are issued whatever the anchors.  This, too, is NOT TokenFlow's result.
+    anchor_edits=True opens the anchors for a multi-edit batch (beside edits=True): the pivotal pass is then ONE
+    `ops.ext_attn_frame_sets_edits` over all 1 + 2E branches -- every edit's bank branches attend to window plus anchors, with
+    the per-edit injection mask of the step -- whenever radius < K - 1.  Without the keyword anchors in a multi-edit batch
+    (edits=True, E > 1) stay an error: ValueError at the pass.
     Not generalised, ValueError at the call: `register_edits(model, E > 1)` unless edits=True, `register_segments` with several
     segments, a registered frame shard -- there the radius is held against the shard's WHOLE bank (`shard.K`), not the rank's
     local keyframes, and only a radius that covers it passes -- and, as for every multi-edit pass, graph capture
@@ -292,16 +295,18 @@ def register_bank_window(model, radius, edits=False, anchors=None):
                              "keyframe, or None)")
         anchors = tuple(int(a) for a in anchors) or None
     _set_bank_window(_hook_blocks(model.unet), radius, bool(edits) and radius is not None,
-                     anchors if radius is not None else None)
+                     anchors if radius is not None else None, bool(anchor_edits) and radius is not None)
 
 
-def _set_bank_window(blocks, radius, edits=False, anchors=None):
-    """`bank_window` (`bank_window_edits`, the multi-edit opt-in, and `bank_window_anchors`: a tuple of keyframe indices, an
-    int stride or None) on transformer blocks and their `attn1` (register_bank_window; tools on a bare block list)."""
+def _set_bank_window(blocks, radius, edits=False, anchors=None, anchor_edits=False):
+    """`bank_window` (`bank_window_edits`, the multi-edit opt-in, `bank_window_anchors`: a tuple of keyframe indices, an
+    int stride or None, and `bank_window_anchor_edits`, the opt-in of anchors in a multi-edit batch) on transformer blocks
+    and their `attn1` (register_bank_window; tools on a bare block list)."""
     for tb in blocks:
         for m in (tb, tb.attn1):
             setattr(m, "bank_window", radius)
             setattr(m, "bank_window_edits", edits)
+            setattr(m, "bank_window_anchor_edits", anchor_edits)
             setattr(m, "bank_window_anchors", anchors)
 
 
@@ -336,9 +341,9 @@ def _bank_anchors(module, K: int):
     anchors = getattr(module, "bank_window_anchors", None)
     if anchors is None:
         return None
-    if int(getattr(module, "n_edits", 1)) > 1:
-        raise ValueError("register_bank_window: anchor keyframes in a multi-edit batch (register_edits, n_edits > 1) are not "
-                         "supported")
+    if int(getattr(module, "n_edits", 1)) > 1 and not getattr(module, "bank_window_anchor_edits", False):
+        raise ValueError("register_bank_window: anchor keyframes in a multi-edit batch (register_edits, n_edits > 1) are "
+                         "opt-in: register_bank_window(model, radius, edits=True, anchors=..., anchor_edits=True)")
     if isinstance(anchors, int):
         return tuple(range(0, K, anchors))
     if max(anchors) >= K:
@@ -592,10 +597,14 @@ def _make_sa_forward(self, pnp: bool):
                 out = shard.pivotal_attention(q, k, v, self.heads, self.scale, False, n_edits=E, inject_mask=mask)
             else:
                 out = shard.pivotal_attention(q, k, v, self.heads, self.scale, inject)
+        elif anchors is not None and E > 1:   # ... several prompts with anchors: every edit's bank branches read the frame sets
+            out = ops.ext_attn_frame_sets_edits(q, k, v, self.heads, self.scale, False, E,
+                                                ops.bank_frame_sets(q.shape[0] // (1 + 2 * E), radius, anchors),
+                                                inject_mask=mask)
         elif radius is not None and E > 1:   # ... several prompts on a long video: every edit's bank branches read the windows
             out = ops.ext_attn_windows_edits(q, k, v, self.heads, self.scale, False, E,
                                              ops.bank_windows(q.shape[0] // (1 + 2 * E), radius), inject_mask=mask)
-        elif anchors is not None:   # ... and to the global anchor keyframes (E = 1: anchors in a multi-edit batch raise)
+        elif anchors is not None:   # ... and to the global anchor keyframes (E = 1)
             out = ops.ext_attn_frame_sets(q, k, v, self.heads, self.scale, inject,
                                           ops.bank_frame_sets(q.shape[0] // 3, radius, anchors))
         elif radius is not None:  # long videos: a bank branch attends to the neighbouring keyframes only

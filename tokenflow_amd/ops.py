@@ -307,6 +307,22 @@ def attn_frame_sets_plan(K: int, sets, S: int, heads: int, dh: int, inject: bool
                         _DT[dtype], ctypes.cast(tab, ctypes.c_void_p))
 
 
+def attn_frame_sets_edits_plan(K: int, sets, S: int, heads: int, dh: int, n_edits: int, inject_mask: int,
+                               dtype: torch.dtype = torch.bfloat16, out_dtype: Optional[torch.dtype] = None,
+                               no_split: Optional[bool] = None, fused: Optional[bool] = None, multi_v: Optional[bool] = None,
+                               multi_v64: Optional[bool] = None, hints: int = 0) -> list:
+    """The launches `ext_attn_frame_sets_edits` makes for dense [(1+2E)K,S,heads*dh] tensors, as tokens
+    (tf_ext_attn_frame_sets_edits_plan: the tokens of `attn_edits_plan` with ',set' appended to every bank launch that walks
+    the sets; the frame-set four-bank launch of a pair of injecting edits is 'one<40,1,4,MV4,2,fq0>,set' /
+    'one<64,1,8,MV4,2,fq1>,set').  n_edits = 1 gives `attn_frame_sets_plan`, sets that are all contiguous ranges
+    `attn_windows_edits_plan`, K full sets `attn_edits_plan(inject_mask=...)`.  Host only: needs no GPU."""
+    tab = _frame_sets("attn_frame_sets_edits_plan", sets, K, K)
+    mask = _edit_mask("attn_frame_sets_edits_plan", inject_mask, n_edits)
+    flags = _attn_flags(False, "all", out_dtype == torch.float32, False, no_split, fused, hints) | _multi_v_bits(multi_v, multi_v64)
+    return _plan_tokens("tf_ext_attn_frame_sets_edits_plan", _lib.load().tf_ext_attn_frame_sets_edits_plan, K, K, 0, S, heads,
+                        dh, int(n_edits), mask, flags, _DT[dtype], ctypes.cast(tab, ctypes.c_void_p))
+
+
 def _single_mask(what: str, mask, C: int) -> int:
     m = int(mask)
     if not 1 <= C <= 64 or m < 0 or m >> C:
@@ -659,6 +675,70 @@ def ext_attn_windows_edits(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, he
     _launch(dev, "tf_ext_attn_fwd_windows_edits", lib.tf_ext_attn_fwd_windows_edits, q.data_ptr(), k.data_ptr(), v.data_ptr(),
             out.data_ptr(), K, K, 0, S, heads, dh, ld, ctypes.cast(strides, ctypes.c_void_p), float(scale), flags, dt, E, mask,
             ctypes.cast(lo, ctypes.c_void_p), ctypes.cast(n, ctypes.c_void_p), ws.data_ptr(), ws.numel())
+    return out
+
+
+def ext_attn_frame_sets_edits(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, scale: float, inject: bool,
+                              n_edits: int, sets, *, inject_mask: Optional[int] = None, multi_v: Optional[bool] = None,
+                              multi_v64: Optional[bool] = None, no_split: Optional[bool] = None, fused: Optional[bool] = None,
+                              hints: int = 0, out_dtype: Optional[torch.dtype] = None,
+                              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`ext_attn_edits` over a frame-set keyframe bank (tf_ext_attn_fwd_frame_sets_edits): E = n_edits prompts on one long
+    video in one pass, with anchor keyframes beside the window.  q, k, v [(1+2E)K,S,D] in the layout [source | uncond_1 |
+    cond_1 | ...], `sets` one int mask per keyframe (`bank_frame_sets(K, radius, anchors)`).  The uncond / cond branches of
+    every edit attend, for keyframe i, to the keyframes whose bits are set in mask i, in ascending order -- an injecting edit
+    with the source's q and k -- and the source branch to its own frame, once.  NOT TokenFlow's computation unless every set is
+    the whole bank (then the call is `ext_attn_edits`, bit for bit); n_edits = 1 is `ext_attn_frame_sets`, sets that are all
+    contiguous ranges are `ext_attn_windows_edits`.  The slices of edit e are what `ext_attn_frame_sets` computes on [source |
+    uncond_e | cond_e] with edit e's injection flag, bit for bit under no_split wherever both take the same kernel form --
+    except where pairs of injecting edits take the frame-set four-bank launch (multi_v=True at head dim 40, multi_v64=True at
+    64; multi_v=False switches it off; None = the library's measured rule for frame-set calls), each frame of which is bit for
+    bit its own four-bank `ext_attn_edits` call on the gathered member frames.
+    inject_mask: the injection state per edit (bit e = edit e, `inject` must then be False); None = the shared state `inject`."""
+    dev = _need_gpu(q, k, v, out)
+    lib = _lib.load()
+    E = int(n_edits)
+    if inject_mask is None:
+        if not 1 <= E <= _lib.TF_MAX_EDITS:
+            raise ValueError(f"ext_attn_frame_sets_edits: n_edits={n_edits} (1 .. {_lib.TF_MAX_EDITS})")
+        mask = (1 << E) - 1 if inject else 0
+    else:
+        mask = _edit_mask("ext_attn_frame_sets_edits", inject_mask, n_edits, inject)
+    nbr = 1 + 2 * E
+    BK, S, D = k.shape
+    if BK % nbr or D % heads or q.shape != k.shape or v.shape != k.shape:
+        raise ValueError(f"ext_attn_frame_sets_edits: bad shapes q{tuple(q.shape)} k{tuple(k.shape)} v{tuple(v.shape)} heads {heads} "
+                         f"for {E} edits ({nbr} branches)")
+    K, dh = BK // nbr, D // heads
+    tab = _frame_sets("ext_attn_frame_sets_edits", sets, K, K)
+    dt = _DT.get(q.dtype)
+    if dt is None or dt == _lib.TF_F32 or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise TypeError(f"ext_attn_frame_sets_edits: q/k/v must share dtype bf16 or f16, got {q.dtype},{k.dtype},{v.dtype}")
+
+    def rows(t):
+        if t.stride(-1) != 1 or t.stride(0) != S * t.stride(1):
+            t = t.contiguous()
+        return t
+    q, k, v = rows(q), rows(k), rows(v)
+    ld = q.stride(1)
+    if k.stride(1) != ld or v.stride(1) != ld:
+        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        ld = D
+    if out_dtype is None:
+        out_dtype = out.dtype if out is not None else q.dtype
+    if out_dtype not in (q.dtype, torch.float32):
+        raise TypeError(f"ext_attn_frame_sets_edits: out_dtype {out_dtype} (the input dtype or float32)")
+    if out is None:
+        out = torch.empty(BK, S, D, dtype=out_dtype, device=q.device)
+    elif out.dtype != out_dtype or not out.is_contiguous() or out.shape != (BK, S, D):
+        raise ValueError("ext_attn_frame_sets_edits: `out` must be a contiguous [B*K,S,D] tensor of out_dtype")
+    flags = _attn_flags(False, "all", out_dtype == torch.float32, False, no_split, fused, hints) | _multi_v_bits(multi_v, multi_v64)
+    ws = _workspace(lib.tf_ext_attn_edits_workspace_bytes(K, S, heads, dh, E, dt), q.device)
+    fs = S * ld
+    strides = (ctypes.c_int64 * 9)(K * fs, fs, K * fs, fs, K * fs, fs, K * S * D, S * D, ld)
+    _launch(dev, "tf_ext_attn_fwd_frame_sets_edits", lib.tf_ext_attn_fwd_frame_sets_edits, q.data_ptr(), k.data_ptr(),
+            v.data_ptr(), out.data_ptr(), K, K, 0, S, heads, dh, ld, ctypes.cast(strides, ctypes.c_void_p), float(scale), flags,
+            dt, E, mask, ctypes.cast(tab, ctypes.c_void_p), ws.data_ptr(), ws.numel())
     return out
 
 

@@ -14,7 +14,7 @@ from tokenflow_amd.hooks import (  # noqa: F401
 # register_edit_schedules: the edits' own injection schedules
 # register_segments: keyframe-segment extension (several scenes or clips in one pass)
 # register_bank_window: sliding-window bank extension (a keyframe attends to its neighbouring keyframes only: long videos;
-# anchors=... adds global anchor keyframes that every keyframe sees)
+# anchors=... adds global anchor keyframes that every keyframe sees; edits=True / anchor_edits=True open both for several prompts)
 
 # `from tokenflow_utils import *` in the reference also leaks these two names (its module does
 # `import torch, os` at top level, tokenflow_utils.py:2-3); keep that surface identical.
