@@ -55,6 +55,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void ext_attn_kernel(P p) {
     // When the head dim is not a multiple of 32 the last PV M-tile has unused rows: row DH of the
     // V^T image is set to 1.0, so that accumulator row collects sum_k P[k] -- the softmax
     // denominator comes out of the MFMA for free, summed over the SAME rounded P as the numerator.
+    // At the other head dims (64) the VALU sums the rounded P too (l_run): see the tile loop.
     constexpr bool ONES = (DH % 32) != 0;
     constexpr int ONES_R = ((DH % 32) & 3) + 4 * ((DH % 32) >> 3);  // C/D register of row DH%32 (lane half 0)
     static_assert(!ONES || ((DH % 32) & 4) == 0, "row DH must live in lane half 0");
@@ -384,9 +385,13 @@ __global__ __launch_bounds__(64 * NW, MINW) void ext_attn_kernel(P p) {
                         const f32x2 x = f32x2{sh[r], sh[r + 1]} * c2 - mc2;
                         const float p0 = __builtin_amdgcn_exp2f(x[0]);
                         const float p1 = __builtin_amdgcn_exp2f(x[1]);
-                        lsum += p0 + p1;
-                        ph[r >> 3][r & 7] = (E)p0;
-                        ph[r >> 3][(r & 7) + 1] = (E)p1;
+                        // the denominator is summed from the ROUNDED P, the values the P.V MFMA multiplies: with a reference
+                        // point below the maximum (lag, deferred shift) the largest P is no power of two, and only a common
+                        // rounding of numerator and denominator cancels in a peaked softmax
+                        const E e0 = (E)p0, e1 = (E)p1;
+                        lsum += (float)e0 + (float)e1;
+                        ph[r >> 3][r & 7] = e0;
+                        ph[r >> 3][(r & 7) + 1] = e1;
                     }
                     l_run[0] += lsum;
 #pragma unroll
@@ -523,9 +528,10 @@ __global__ __launch_bounds__(64 * NW, MINW) void ext_attn_kernel(P p) {
                             const f32x2 x = f32x2{s[qi][kt][r], s[qi][kt][r + 1]} * c2 - mc2;
                             const float p0 = __builtin_amdgcn_exp2f(x[0]);
                             const float p1 = __builtin_amdgcn_exp2f(x[1]);
-                            if constexpr (!ONES) lsum += p0 + p1;
-                            pf[kt * 2 + (r >> 3)][r & 7] = (E)p0;
-                            pf[kt * 2 + (r >> 3)][(r & 7) + 1] = (E)p1;
+                            const E e0 = (E)p0, e1 = (E)p1;
+                            if constexpr (!ONES) lsum += (float)e0 + (float)e1;   // the rounded P, as the ones row sums it
+                            pf[kt * 2 + (r >> 3)][r & 7] = e0;
+                            pf[kt * 2 + (r >> 3)][(r & 7) + 1] = e1;
                         }
                     if constexpr (!ONES) l_run[qi] += lsum;
                 }

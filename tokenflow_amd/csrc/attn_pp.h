@@ -311,9 +311,10 @@ __global__ __launch_bounds__(256, 2) void ext_attn_pp_kernel(P p) {
                 // two scalar v_fma_f32, NOT one v_pk_fma_f32: packed f32 VALU beside MFMAs costs ~+22 cycles each
                 const float p0 = __builtin_amdgcn_exp2f(fmaf(s[X][kt][r], c, -mc));
                 const float p1 = __builtin_amdgcn_exp2f(fmaf(s[X][kt][r + 1], c, -mc));
-                lsum += p0 + p1;
-                pf[X][kt * 2 + (r >> 3)][r & 7] = (E)p0;
-                pf[X][kt * 2 + (r >> 3)][(r & 7) + 1] = (E)p1;
+                const E e0 = (E)p0, e1 = (E)p1;
+                lsum += (float)e0 + (float)e1;   // the rounded P: numerator and denominator see the same values
+                pf[X][kt * 2 + (r >> 3)][r & 7] = e0;
+                pf[X][kt * 2 + (r >> 3)][(r & 7) + 1] = e1;
             }
             __builtin_amdgcn_sched_barrier(0);
         }
