@@ -530,6 +530,11 @@ def test_inject_copy_exact():
 
 
 # --------------------------------------------------------------------------- layer norm (row f2)
+def layer_norm_bound(ref, out_dt):
+    """The bound on |out - ref| against torch's fp32 layer_norm `ref`: 2e-6 relative to max(1, |ref|) for an fp32 output, one
+    rounding of the fp32 result for a 16-bit one."""
+    eps = {torch.float32: 2e-6, torch.bfloat16: 2.0 ** -8, torch.float16: 2.0 ** -11}[out_dt]
+    return eps * ref.abs().clamp(min=1.0) + (4e-6 if out_dt != torch.float32 else 0.0)
 
 
 @pytest.mark.parametrize("rows,D", [(4096, 320), (515, 640), (37, 1280), (5, 72), (3, 2048)])
@@ -552,8 +557,7 @@ def test_layer_norm_vs_torch_fp32(rows, D, in_dt, w_dt, out_dt):
                               out_dt, want_inv_norm=True)
     assert out.dtype == out_dt and out.shape == x.shape and inv.shape == (rows,)
     got = out.float().cpu()
-    eps = {torch.float32: 2e-6, torch.bfloat16: 2.0 ** -8, torch.float16: 2.0 ** -11}[out_dt]
-    bound = eps * ref.abs().clamp(min=1.0) + (4e-6 if out_dt != torch.float32 else 0.0)
+    bound = layer_norm_bound(ref, out_dt)
     assert bool(((got - ref).abs() <= bound).all()), float(((got - ref).abs() - bound).max())
     inv_ref = 1.0 / got.norm(dim=-1)
     assert torch.allclose(inv.cpu(), inv_ref, rtol=2e-6, atol=0)

@@ -195,8 +195,9 @@ __global__ __launch_bounds__(256) void gather_blend_kernel(const TIn* __restrict
 // TokenFlowBlock.forward, tokenflow_utils.py:399-414, whose only consumer is a Linear): the propagation pass leaves
 // its residual stream in fp32 (the reference's promotion, 385-397), and a separate norm launch re-reads those 4 bytes
 // per element only to emit 2.  Here a row of the result never leaves the registers between the two: LPR lanes own one
-// (branch, token) row (the mapping and arithmetic of ln_row.h, so the normalised rows are bit-identical to
-// tf_layer_norm on the stored result), write it once and write its norm in the 16-bit type the Linear reads.
+// (branch, token) row (the mapping and arithmetic of ln_row.h, LPR from ln_lanes_per_row as in tf_layer_norm, so the
+// normalised rows are bit-identical to tf_layer_norm on the stored result at every D), write it once and write its norm
+// in the 16-bit type the Linear reads.
 // Always the MERGE form (indices from the search's partial results).  T16 = the 16-bit model type (cached attention
 // output, residual, norm output); TOut = result type: float (two keyframes) or T16 (the one-keyframe chunk alone).
 template <typename T16, typename TOut, int LPR, int NP, int P, bool CH>
@@ -336,10 +337,19 @@ void launch_gbn(const GbArgs& a) {
                            a.n, a.S, a.D, a.kf0, P == 2 ? a.kf1 : a.kf0, a.ch, a.nb);
     };
     if (tf_plan_note("gather_norm[branches=%d]", a.nb)) return;
-    const int pieces = a.D >> 3;   // 3 pieces per lane: D <= 384 / 768 / 1536 at 16 / 32 / 64 lanes per row
-    if (pieces <= 48) go(gather_blend_norm_kernel<T16, TOut, 16, 3, P, CH>, 16);
-    else if (pieces <= 96) go(gather_blend_norm_kernel<T16, TOut, 32, 3, P, CH>, 32);
-    else go(gather_blend_norm_kernel<T16, TOut, 64, 3, P, CH>, 64);
+    // lanes per row as tf_layer_norm has them (ln_row.h): the norm's bits depend on it.  3 pieces per lane cover the
+    // model's widths (D = 320 / 640 / 1280) and everything up to D = 384 / 768 / 1536 at 16 / 32 / 64 lanes; the widths
+    // between (D <= 512 at 16 lanes, <= 1024 at 32) take the 4-piece instantiation
+    const int pieces = a.D >> 3, lpr = ln_lanes_per_row(a.D);
+    if (lpr == 16) {
+        if (pieces <= 48) go(gather_blend_norm_kernel<T16, TOut, 16, 3, P, CH>, 16);
+        else go(gather_blend_norm_kernel<T16, TOut, 16, LN_MAXP, P, CH>, 16);
+    } else if (lpr == 32) {
+        if (pieces <= 96) go(gather_blend_norm_kernel<T16, TOut, 32, 3, P, CH>, 32);
+        else go(gather_blend_norm_kernel<T16, TOut, 32, LN_MAXP, P, CH>, 32);
+    } else {
+        go(gather_blend_norm_kernel<T16, TOut, 64, 3, P, CH>, 64);
+    }
 }
 
 // which calls the fused-norm form covers (the hook path's: 16-bit model, residual of the model type)

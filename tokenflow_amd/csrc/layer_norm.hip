@@ -59,8 +59,6 @@ __device__ __forceinline__ void ln_store_sum(void* p, int dtype, int64_t off, fl
     }
 }
 
-constexpr int LN_MAXP = 4;   // 16-B pieces per lane
-
 // 8 consecutive elements as they come from memory (16 B of a 16-bit type, 32 B of fp32): loads are issued as raw
 // words and converted when the row is processed, so that the NEXT row group's loads are in flight while the current
 // one is reduced and stored
@@ -229,8 +227,9 @@ void launch_ln_lpr(const void* x, const void* gamma, const void* beta, void* out
 template <typename TIn, typename TOut>
 void launch_ln(const void* x, const void* gamma, const void* beta, void* out, float* inv_norm, int64_t rows, int D,
                float eps, int w_dtype, hipStream_t st, const LnAdd& ad) {
-    if (D <= 16 * 8 * LN_MAXP) launch_ln_lpr<TIn, TOut, 16>(x, gamma, beta, out, inv_norm, rows, D, eps, w_dtype, st, ad);
-    else if (D <= 32 * 8 * LN_MAXP) launch_ln_lpr<TIn, TOut, 32>(x, gamma, beta, out, inv_norm, rows, D, eps, w_dtype, st, ad);
+    const int lpr = ln_lanes_per_row(D);
+    if (lpr == 16) launch_ln_lpr<TIn, TOut, 16>(x, gamma, beta, out, inv_norm, rows, D, eps, w_dtype, st, ad);
+    else if (lpr == 32) launch_ln_lpr<TIn, TOut, 32>(x, gamma, beta, out, inv_norm, rows, D, eps, w_dtype, st, ad);
     else launch_ln_lpr<TIn, TOut, 64>(x, gamma, beta, out, inv_norm, rows, D, eps, w_dtype, st, ad);
 }
 

@@ -8,6 +8,13 @@
 #pragma once
 #include "tf_common.h"
 
+constexpr int LN_MAXP = 4;   // 16-B pieces per lane
+
+// Lanes per row of a norm over D features (D <= LPR * 8 * LN_MAXP).  The order in which a row's statistics are reduced,
+// hence their bits, depends on it, so every launcher takes it from here: tf_layer_norm, tf_add_layer_norm and the
+// fused-norm gather, which must reproduce tf_layer_norm bit for bit at every D and not only at the model's widths.
+inline int ln_lanes_per_row(int D) { return D <= 16 * 8 * LN_MAXP ? 16 : D <= 32 * 8 * LN_MAXP ? 32 : 64; }
+
 // sum over the LPR lanes that share a row
 template <int LPR>
 __device__ __forceinline__ float ln_row_sum(float x) {
