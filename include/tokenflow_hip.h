@@ -439,6 +439,23 @@ TF_API int tf_head_unpack(const void* recv, void* const* dsts, const int64_t* fr
                    int hd, int64_t ld, int elem_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Halo pack of a sliding-window bank on a frame shard (additive to ABI 11; tf_rank_pivotal_window below).
+ * ONE launch packs the bank slabs of the local keyframes that peers read into the send buffer of ONE tf_all_to_all_rows:
+ *   send rows, peer after peer: for segment p the local frames [seg_f0[p], seg_f0[p] + seg_n[p]), each row
+ *   [slab 0 .. ns)[S][D] = slab_i[frame][s][0 .. D)   (slab_i a [Kl, S, ld] tensor with its own frame stride, in elements).
+ * A frame several peers read is written to each of their segments; a peer that reads nothing has seg_n = 0.  The segment
+ * table (n_seg <= TF_MAX_WORLD entries) rides in the kernel arguments: no device table, no synchronisation, capturable.
+ * With the rank's own frames as its self rows (seg = [0, Kl) for itself) the RECEIVE buffer of the exchange is the extended
+ * bank [F][ns][S][D] in ascending global frame order, which the attention reads in place (frame stride ns*S*D, branch stride
+ * S*D).  The self rows cost one extra device copy of Kl*ns*S*D elements (RCCL moves them device to device, the host hooks and
+ * the loopback transport through their own copies); removing it is left to a later change.
+ * 16-bit elements only (TF_ERR_DTYPE otherwise); D and ld multiples of 8 elements, ns <= 6, segments inside [0, Kl):
+ * TF_ERR_SHAPE; pointers and frame strides 16-byte aligned: TF_ERR_ALIGN.  All checked before anything touches the device.
+ * ------------------------------------------------------------------------ */
+TF_API int tf_window_halo_pack(const void* const* slabs, const int64_t* frame_strides, int ns, void* send, int n_seg,
+                        const int* seg_f0, const int* seg_n, int Kl, int S, int D, int64_t ld, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------
  * Nearest-neighbour token search  --  replaces batch_cosine_sim + chunk + argmax:
  * util.py:61-69 and tokenflow_utils.py:335-343.
  *
@@ -697,6 +714,30 @@ TF_API int tf_ext_attn_fwd_windows(const void* q, const void* k, const void* v, 
 
 TF_API int tf_ext_attn_windows_plan(int K, int Kq, int q_frame0, int S, int H, int Dh, int flags, int dtype, const int* win_lo,
                              const int* win_n, char* buf, size_t len);
+
+/* ------------------------------------------------------------------------
+ * The BANK PART of a windowed pass (additive to ABI 11): what a frame-sharded rank runs over its halo-extended receive buffer
+ * (tf_rank_pivotal_window, `FrameShard._pivotal_window`).
+ *
+ * tf_ext_attn_fwd_windows_part takes the arguments of tf_ext_attn_fwd_windows, but TF_ATTN_BANK_ONLY is accepted: k and v then
+ * hold only the slabs the bank branches read, with the branch offsets of tf_ext_attn_fwd_strided under that flag (branch b of a
+ * tensor at base + b * branch stride; under injection k holds the source slab, branch 0, alone).  Without the flag the call IS
+ * tf_ext_attn_fwd_windows.  TF_ATTN_SOURCE_ONLY is refused (TF_ERR_SHAPE): the source part of a windowed pass is window-free --
+ * it is tf_ext_attn_fwd_strided with TF_ATTN_SOURCE_ONLY.  tf_ext_attn_fwd_windows itself keeps refusing both part flags.
+ *   Identity.  The two parts together -- this call with TF_ATTN_BANK_ONLY, then the source-only strided call -- equal
+ *   tf_ext_attn_fwd_windows on the same tensors BIT FOR BIT under TF_ATTN_NO_SPLIT wherever the plans name the same kernel form
+ *   (the tokens apart from their part field; fused launches agree in KW and PREC), and lie within the attention bound of it
+ *   everywhere.  Every window = the whole bank is tf_ext_attn_fwd_strided with the same part flag.
+ *   ws: tf_ext_attn_workspace_bytes(K, ...).
+ * tf_ext_attn_windows_part_plan: the launches of the call for dense tensors (host only); the bank launch's token carries
+ *   ',win' as in tf_ext_attn_windows_plan.
+ * ------------------------------------------------------------------------ */
+TF_API int tf_ext_attn_fwd_windows_part(const void* q, const void* k, const void* v, void* out, int K, int Kq, int q_frame0,
+                                 int S, int H, int Dh, int64_t ld, const int64_t* strides, float scale, int flags, int dtype,
+                                 const int* win_lo, const int* win_n, void* ws, size_t ws_bytes, void* stream);
+
+TF_API int tf_ext_attn_windows_part_plan(int K, int Kq, int q_frame0, int S, int H, int Dh, int flags, int dtype,
+                                  const int* win_lo, const int* win_n, char* buf, size_t len);
 
 /* ------------------------------------------------------------------------
  * Sliding-window bank for a MULTI-EDIT batch (additive to ABI 11): several prompts on one long video in one pass.
@@ -1098,6 +1139,45 @@ TF_API int tf_rank_pivotal_edits(tf_rank* rk, const void* q, const void* k, cons
                           void* ws, size_t ws_bytes, void* stream);
 TF_API int tf_rank_pivotal_edits_plan(int world, int rank, int K, int S, int H, int Dh, int n_edits, unsigned inject_mask,
                                int mode, int flags, int dtype, char* buf, size_t len);
+
+/* ------------------------------------------------------------------------
+ * The rank executor over a SLIDING-WINDOW bank (additive to ABI 11): tf_rank_pivotal with a `radius` -- long videos across
+ * GPUs.  NOT TokenFlow's result unless the radius covers the bank; opt-in like tf_ext_attn_fwd_windows.
+ *
+ * Geometry (pure arithmetic of (world, rank, K, radius); `sharded.window_halo_plan` is the same in Python).  Rank r owns the
+ * keyframes [kf0, kf0 + Kl).  It reads the global frames [lo, hi) = [max(0, kf0 - R), min(K, kf0 + Kl + R)): hl = kf0 - lo halo
+ * frames on the left, hr = hi - kf0 - Kl on the right, F = hl + Kl + hr in all.  Peer p sends it own(p) & [lo, hi) -- for
+ * R > Kl that spans several ranks -- so a rank receives at most 2R remote frames instead of K - Kl, and computes at most
+ * (2R + 1) * Kl frame-banks of attention instead of K * Kl.  Local query i is global keyframe g = kf0 + i with the window of
+ * g, [max(0, g - R), min(K - 1, g + R)], shifted by -lo; q_frame0 = hl.
+ *
+ * Schedule of ONE call (W > 1, radius < K - 1):
+ *   1. tf_window_halo_pack: [k1, k2, v1, v2] of the frames peers read (under injection [k0, v1, v2]), own frames as self rows;
+ *      the inverse norms under TF_RANK_INV_NORM are a launch of their own in front of it (tf_pivot_inv_norm);
+ *   2. the source part of the local frames (tf_ext_attn_fwd_strided, TF_ATTN_SOURCE_ONLY, q / k / v in place) on the
+ *      auxiliary compute stream, forked behind the pack and in front of the exchange (TOKENFLOW_RANK_SRC_AUX=0: in line);
+ *   3. ONE tf_all_to_all_rows with the sparse row counts, on the caller's stream;
+ *   4. tf_ext_attn_fwd_windows_part(TF_ATTN_BANK_ONLY) over the receive buffer [F][ns][S][D] in place, Kq = Kl, q_frame0 = hl;
+ *   5. join;  6. the neighbour halo of the propagation, as in every mode (TF_RANK_NO_HALO, TF_RANK_INV_NORM, slot,
+ *      tf_rank_halo_wait as for tf_rank_pivotal).
+ * mode: TF_RANK_BANK (or 0) with the two modifier bits; the windowed pass has no heads form.
+ * radius >= K - 1 IS tf_rank_pivotal(TF_RANK_BANK): the same launches, the same bits.  One rank (comm = NULL) is
+ * tf_ext_attn_fwd_windows with the table of the radius.  Results: the bits of one process issuing
+ * tf_ext_attn_fwd_windows_part(TF_ATTN_BANK_ONLY) and the source-only call on the full tensors under TF_ATTN_NO_SPLIT.
+ * Refused with TF_ERR_SHAPE before anything touches the device: radius < 0, Kl > TF_MAX_WINDOW_FRAMES, F >= 2^16, a part flag
+ * or TF_ATTN_FOLD_SCALE in `flags`, any other mode.
+ *   ws: tf_rank_pivotal_window_workspace_bytes (never below tf_rank_pivotal_workspace_bytes: one workspace whatever the radius).
+ * tf_rank_pivotal_window_plan (host only): the sequence, ';'-separated, recorded by the executing code itself:
+ *   inv_norm under TF_RANK_INV_NORM; halo_pack[ns=N]; a2a[slabs=N,send=a/b/..,recv=a/b/..] (rows per peer, rank order); the
+ *   tokens of the source-only tf_ext_attn_plan (listed behind the exchange, though it is issued in front of it); the tokens of
+ *   tf_ext_attn_windows_part_plan for the bank part; halo[n=5].  A covering radius: the sequence of tf_rank_pivotal.
+ * ------------------------------------------------------------------------ */
+TF_API size_t tf_rank_pivotal_window_workspace_bytes(const tf_rank* rk, int S, int H, int Dh, int dtype, int radius);
+TF_API int tf_rank_pivotal_window(tf_rank* rk, const void* q, const void* k, const void* v, const int64_t* strides,
+                           void* piv_ext, float* inv_ext, void* kfo_ext, int S, int H, int Dh, float scale, int flags,
+                           int dtype, int mode, int slot, int radius, void* ws, size_t ws_bytes, void* stream);
+TF_API int tf_rank_pivotal_window_plan(int world, int rank, int K, int S, int H, int Dh, int radius, int mode, int flags,
+                                int dtype, char* buf, size_t len);
 
 #ifdef __cplusplus
 }

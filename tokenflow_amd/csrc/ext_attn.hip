@@ -1352,21 +1352,20 @@ static int windows_pack(const char* name, int K, int Kq, int q_frame0, const int
     return 0;
 }
 
-extern "C" int tf_ext_attn_fwd_windows(const void* q, const void* k, const void* v, void* out, int K, int Kq, int q_frame0,
-                                       int S, int H, int Dh, int64_t ld, const int64_t* strides, float scale, int flags,
-                                       int dtype, const int* win_lo, const int* win_n, void* ws, size_t ws_bytes,
-                                       void* stream) {
-    const char* const name = "tf_ext_attn_fwd_windows";
+// The flags no windowed call has; tf_ext_attn_fwd_windows refuses the part flags too.
+constexpr int WIN_REFUSED = TF_ATTN_FOLD_SCALE | TF_ATTN_MULTI_V | TF_ATTN_NO_MULTI_V | TF_ATTN_MULTI_V64 | TF_ATTN_RUN_MULTI_V;
+
+// tf_ext_attn_fwd_windows and tf_ext_attn_fwd_windows_part: the two differ in the flags they refuse (and in how they say so).
+static int windows_fwd(const char* name, int refused, const char* refused_what, const void* q, const void* k, const void* v,
+                       void* out, int K, int Kq, int q_frame0, int S, int H, int Dh, int64_t ld, const int64_t* strides,
+                       float scale, int flags, int dtype, const int* win_lo, const int* win_n, void* ws, size_t ws_bytes,
+                       void* stream) {
     unsigned win[TF_MAX_WINDOW_FRAMES];
     int K_max = 0;
     bool full = true;
     if (const int rc = windows_pack(name, K, Kq, q_frame0, win_lo, win_n, win, &K_max, &full)) return rc;
-    constexpr int REFUSED = TF_ATTN_BANK_ONLY | TF_ATTN_SOURCE_ONLY | TF_ATTN_FOLD_SCALE | TF_ATTN_MULTI_V | TF_ATTN_NO_MULTI_V |
-                            TF_ATTN_MULTI_V64 | TF_ATTN_RUN_MULTI_V;
-    TF_ARG(!(flags & REFUSED), TF_ERR_SHAPE,
-           "%s: flags 0x%x -- TF_ATTN_BANK_ONLY / TF_ATTN_SOURCE_ONLY / TF_ATTN_FOLD_SCALE and the multi-edit hints have no "
-           "windowed form", name, flags & REFUSED);
-    if (full)   // every keyframe sees the whole bank: today's call
+    TF_ARG(!(flags & refused), TF_ERR_SHAPE, "%s: flags 0x%x -- %s", name, flags & refused, refused_what);
+    if (full)   // every keyframe sees the whole bank: today's call (with the same part flag, if any)
         return tf_ext_attn_fwd_strided(q, k, v, out, K, Kq, q_frame0, S, H, Dh, ld, strides, scale, flags, dtype, ws, ws_bytes,
                                        stream);
     const WinPart wn{win, K_max};
@@ -1374,23 +1373,60 @@ extern "C" int tf_ext_attn_fwd_windows(const void* q, const void* k, const void*
                          nullptr, &wn);
 }
 
-// Launch plan of tf_ext_attn_fwd_windows for dense tensors (host only): the entry point itself under the plan recorder.
-extern "C" int tf_ext_attn_windows_plan(int K, int Kq, int q_frame0, int S, int H, int Dh, int flags, int dtype,
-                                        const int* win_lo, const int* win_n, char* buf, size_t len) {
-    TF_ARG(K > 0 && S > 0 && H > 0 && Kq > 0 && Kq <= K, TF_ERR_SHAPE, "tf_ext_attn_windows_plan: K=%d Kq=%d S=%d H=%d", K, Kq, S,
-           H);
+// The launch plan of either entry point for dense tensors (host only): the entry point itself under the plan recorder.
+template <typename Fn>
+static int windows_plan(const char* name, Fn fwd, int K, int Kq, int q_frame0, int S, int H, int Dh, int flags, int dtype,
+                        const int* win_lo, const int* win_n, char* buf, size_t len) {
+    TF_ARG(K > 0 && S > 0 && H > 0 && Kq > 0 && Kq <= K, TF_ERR_SHAPE, "%s: K=%d Kq=%d S=%d H=%d", name, K, Kq, S, H);
     void* const ph = reinterpret_cast<void*>((uintptr_t)1 << 12);
     const int64_t ld = (int64_t)H * Dh, fs = (int64_t)S * ld;
     const int64_t strides[9] = {Kq * fs, fs, K * fs, fs, K * fs, fs, Kq * fs, fs, ld};
     TfPlanRec rec{buf, len, 0, 0};
     if (buf && len) buf[0] = 0;
     tf_plan_rec = &rec;
-    const int rc = tf_ext_attn_fwd_windows(ph, ph, ph, ph, K, Kq, q_frame0, S, H, Dh, ld, strides, 1.0f, flags, dtype, win_lo,
-                                           win_n, ph, tf_ext_attn_workspace_bytes(K, S, H, Dh, dtype), nullptr);
+    const int rc = fwd(ph, ph, ph, ph, K, Kq, q_frame0, S, H, Dh, ld, strides, 1.0f, flags, dtype, win_lo, win_n, ph,
+                       tf_ext_attn_workspace_bytes(K, S, H, Dh, dtype), nullptr);
     tf_plan_rec = nullptr;
     if (rc) return rc;
-    TF_ARG(rec.used < len, TF_ERR_WORKSPACE, "tf_ext_attn_windows_plan: the plan needs %zu bytes", rec.used + 1);
+    TF_ARG(rec.used < len, TF_ERR_WORKSPACE, "%s: the plan needs %zu bytes", name, rec.used + 1);
     return rec.n;
+}
+
+extern "C" int tf_ext_attn_fwd_windows(const void* q, const void* k, const void* v, void* out, int K, int Kq, int q_frame0,
+                                       int S, int H, int Dh, int64_t ld, const int64_t* strides, float scale, int flags,
+                                       int dtype, const int* win_lo, const int* win_n, void* ws, size_t ws_bytes,
+                                       void* stream) {
+    return windows_fwd("tf_ext_attn_fwd_windows", WIN_REFUSED | TF_ATTN_BANK_ONLY | TF_ATTN_SOURCE_ONLY,
+                       "TF_ATTN_BANK_ONLY / TF_ATTN_SOURCE_ONLY / TF_ATTN_FOLD_SCALE and the multi-edit hints have no windowed form",
+                       q, k, v, out, K, Kq, q_frame0, S, H, Dh, ld, strides, scale, flags, dtype, win_lo, win_n, ws, ws_bytes,
+                       stream);
+}
+
+// The bank part of a windowed pass (include/tokenflow_hip.h): tf_ext_attn_fwd_windows with TF_ATTN_BANK_ONLY accepted -- k and v
+// hold only the slabs the bank branches read, addressed as in tf_ext_attn_fwd_strided with that flag.  What a frame-sharded rank
+// runs over its halo-extended receive buffer; the source part of a windowed pass is window-free (tf_ext_attn_fwd_strided with
+// TF_ATTN_SOURCE_ONLY).
+extern "C" int tf_ext_attn_fwd_windows_part(const void* q, const void* k, const void* v, void* out, int K, int Kq, int q_frame0,
+                                            int S, int H, int Dh, int64_t ld, const int64_t* strides, float scale, int flags,
+                                            int dtype, const int* win_lo, const int* win_n, void* ws, size_t ws_bytes,
+                                            void* stream) {
+    return windows_fwd("tf_ext_attn_fwd_windows_part", WIN_REFUSED | TF_ATTN_SOURCE_ONLY,
+                       "TF_ATTN_SOURCE_ONLY (the source part of a windowed pass is tf_ext_attn_fwd_strided) / TF_ATTN_FOLD_SCALE "
+                       "and the multi-edit hints have no windowed form",
+                       q, k, v, out, K, Kq, q_frame0, S, H, Dh, ld, strides, scale, flags, dtype, win_lo, win_n, ws, ws_bytes,
+                       stream);
+}
+
+extern "C" int tf_ext_attn_windows_part_plan(int K, int Kq, int q_frame0, int S, int H, int Dh, int flags, int dtype,
+                                             const int* win_lo, const int* win_n, char* buf, size_t len) {
+    return windows_plan("tf_ext_attn_windows_part_plan", tf_ext_attn_fwd_windows_part, K, Kq, q_frame0, S, H, Dh, flags, dtype,
+                        win_lo, win_n, buf, len);
+}
+
+extern "C" int tf_ext_attn_windows_plan(int K, int Kq, int q_frame0, int S, int H, int Dh, int flags, int dtype,
+                                        const int* win_lo, const int* win_n, char* buf, size_t len) {
+    return windows_plan("tf_ext_attn_windows_plan", tf_ext_attn_fwd_windows, K, Kq, q_frame0, S, H, Dh, flags, dtype, win_lo,
+                        win_n, buf, len);
 }
 
 // ---------------------------------------------------------------------------------------------

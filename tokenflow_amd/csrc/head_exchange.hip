@@ -93,6 +93,36 @@ __global__ __launch_bounds__(256) void head_unpack_kernel(const unsigned char* _
     }
 }
 
+// Halo pack of a windowed frame shard (tf_window_halo_pack): the send rows of ONE tf_all_to_all_rows.  Send row r belongs to
+// the segment s with row0[s] <= r < row0[s + 1] (peer order) and holds the slabs of local frame f0[s] + r - row0[s]; a frame
+// several peers read lies in several segments.  The table rides in the kernel arguments: no device table, no sync, capturable.
+struct HaloSegs {
+    int n;                         // segments = ranks
+    int row0[TF_MAX_WORLD + 1];    // first send row per segment; row0[n] = rows in all
+    int f0[TF_MAX_WORLD];          // first local frame per segment
+};
+
+// send[r][i][s][0..D) = slab_i[frame(r)][s][0..D): one thread = one 16-byte piece, grid-stride over the bytes of the send buffer
+template <int N>
+__global__ __launch_bounds__(256) void window_halo_pack_kernel(SlabPtrs<N> sl, unsigned char* __restrict__ send, HaloSegs sg,
+                                                               int ns, int S, int d_pieces, int64_t ld_bytes) {
+    const int64_t per_row = (int64_t)ns * S * d_pieces;
+    const int64_t total = (int64_t)sg.row0[sg.n] * per_row;
+    for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < total; g += (int64_t)gridDim.x * 256) {
+        const int r = (int)(g / per_row);
+        int64_t t = g - (int64_t)r * per_row;
+        const int pc = (int)(t % d_pieces);
+        t /= d_pieces;
+        const int s = (int)(t % S);
+        const int i = (int)(t / S);
+        int seg = 0;
+        while (seg + 1 < sg.n && r >= sg.row0[seg + 1]) ++seg;
+        const int f = sg.f0[seg] + (r - sg.row0[seg]);
+        const unsigned char* src = sl.src[i] + f * sl.fs[i] + (int64_t)s * ld_bytes + (int64_t)pc * 16;
+        st16(send + g * 16, ld16(src));
+    }
+}
+
 int check(const char* name, const void* const* slabs, const int64_t* fs, int n, const void* buf, int W, int Kl, int S,
           int hd, int64_t ld, int elem_bytes) {
     TF_ARG(slabs && fs && buf, TF_ERR_NULL, "%s: null pointer", name);
@@ -190,5 +220,48 @@ extern "C" int tf_head_unpack(const void* recv, void* const* dsts, const int64_t
                            static_cast<const unsigned char*>(recv), slab_ptrs<MAX_SLABS>(dptrs, frame_strides, nb, elem_bytes),
                            nb, W, Kl, S, hd_pieces, ld * elem_bytes);
     TF_LAUNCH_CHECK("tf_head_unpack");
+    return 0;
+}
+
+// One launch packs the bank slabs of the local keyframes that peers read into the send buffer of one tf_all_to_all_rows
+// (include/tokenflow_hip.h).  Pure data movement; every argument is checked before anything touches the device.
+extern "C" int tf_window_halo_pack(const void* const* slabs, const int64_t* frame_strides, int ns, void* send, int n_seg,
+                                   const int* seg_f0, const int* seg_n, int Kl, int S, int D, int64_t ld, int dtype,
+                                   void* stream) {
+    const char* const name = "tf_window_halo_pack";
+    TF_ARG(slabs && frame_strides && send && seg_f0 && seg_n, TF_ERR_NULL, "%s: null pointer", name);
+    TF_ARG(dtype == TF_BF16 || dtype == TF_F16, TF_ERR_DTYPE, "%s: dtype %d (bf16/f16 only)", name, dtype);
+    TF_ARG(ns >= 1 && ns <= MAX_SLABS_1 && n_seg >= 1 && n_seg <= TF_MAX_WORLD && Kl >= 1 && S >= 1 && D >= 8 && D % 8 == 0 &&
+               ld >= D && ld % 8 == 0,
+           TF_ERR_SHAPE, "%s: ns=%d segments=%d Kl=%d S=%d D=%d ld=%lld (D and ld multiples of 8 elements, ld >= D, at most %d "
+           "slabs and %d segments)", name, ns, n_seg, Kl, S, D, (long long)ld, MAX_SLABS_1, TF_MAX_WORLD);
+    HaloSegs sg{};
+    sg.n = n_seg;
+    int64_t rows = 0;
+    for (int p = 0; p < n_seg; ++p) {
+        TF_ARG(seg_n[p] >= 0 && seg_f0[p] >= 0 && (int64_t)seg_f0[p] + seg_n[p] <= Kl, TF_ERR_SHAPE,
+               "%s: segment %d = local frames [%d, %d) outside the %d local keyframes", name, p, seg_f0[p], seg_f0[p] + seg_n[p], Kl);
+        sg.row0[p] = (int)rows, sg.f0[p] = seg_f0[p];
+        rows += seg_n[p];
+    }
+    TF_ARG(rows < (1 << 16), TF_ERR_SHAPE, "%s: %lld send rows (below 65536)", name, (long long)rows);
+    sg.row0[n_seg] = (int)rows;
+    TF_ARG(tf_aligned16(send), TF_ERR_ALIGN, "%s: send buffer not 16-byte aligned", name);
+    for (int i = 0; i < ns; ++i) {
+        TF_ARG(slabs[i], TF_ERR_NULL, "%s: slab %d is null", name, i);
+        TF_ARG(tf_aligned16(slabs[i]) && (frame_strides[i] * 2) % 16 == 0, TF_ERR_ALIGN, "%s: slab %d not 16-byte aligned", name, i);
+        // (a frame holds S token rows: the last byte read is inside the slab's Kl frames)
+        TF_ARG(frame_strides[i] >= (int64_t)(S - 1) * ld + D || Kl == 1, TF_ERR_SHAPE, "%s: slab %d: frame stride %lld below a frame",
+               name, i, (long long)frame_strides[i]);
+    }
+    if (rows == 0) return 0;   // nobody reads this rank's frames and it sends none to itself: nothing to launch
+    const int d_pieces = D * 2 / 16;
+    const int64_t total = rows * ns * S * d_pieces;
+    int64_t blocks = (total + 255) / 256;
+    if (blocks > 2048) blocks = 2048;   // 256 CUs x 8 resident workgroups; the rest by the grid stride
+    hipLaunchKernelGGL(window_halo_pack_kernel<MAX_SLABS_1>, dim3((unsigned)blocks), dim3(256), 0,
+                       reinterpret_cast<hipStream_t>(stream), slab_ptrs<MAX_SLABS_1>(slabs, frame_strides, ns, 2),
+                       static_cast<unsigned char*>(send), sg, ns, S, d_pieces, ld * 2);
+    TF_LAUNCH_CHECK("tf_window_halo_pack");
     return 0;
 }

@@ -18,6 +18,7 @@
 // host synchronisation anywhere.
 // TF_RANK_BANK_RUNS uses the same auxiliary compute stream for the LOCAL run of the bank (the rank's own keyframes: source
 // branch + bank branches, forked behind the pack and in front of the gather, joined in front of the merge).
+#include <stdio.h>
 #include <stdlib.h>
 
 #include <new>
@@ -200,6 +201,101 @@ void partition(tf_rank* rk, int K, int world, int rank) {
         off += rk->counts[r];
     }
     rk->Kl = rk->counts[rank];
+}
+
+// ---- sliding-window bank on a frame shard (tf_rank_pivotal_window): what `sharded.window_halo_plan` computes in Python.
+//      With radius R rank r reads the global frames [lo, hi) = [max(0, kf0 - R), min(K, kf0 + Kl + R)): hl = kf0 - lo halo
+//      frames on the left, hr on the right, F in all.  Peer p sends it own(p) & [lo, hi) -- several ranks' worth for R > Kl --
+//      and it sends peer p own(r) & [lo_p, hi_p); its own frames travel as its self rows, so that the receive buffer IS the
+//      extended bank in ascending global frame order.  Local query i (global g = kf0 + i) gets the window of g shifted by -lo.
+struct WinGeom {
+    int lo, hi, hl, hr, F;
+    int seg_f0[TF_MAX_WORLD], seg_n[TF_MAX_WORLD];   // per peer: the local frames it reads (first, count)
+    int64_t send_rows[TF_MAX_WORLD], recv_rows[TF_MAX_WORLD];
+    int64_t send_total;
+    int win_lo[TF_MAX_WINDOW_FRAMES], win_n[TF_MAX_WINDOW_FRAMES];
+};
+
+inline int imax(int a, int b) { return a > b ? a : b; }
+inline int imin(int a, int b) { return a < b ? a : b; }
+
+// (Kl <= TF_MAX_WINDOW_FRAMES is the caller's check: the window table holds one entry per local keyframe)
+WinGeom window_geometry(const tf_rank* rk, int R) {
+    WinGeom g{};
+    const int K = rk->K, Kl = rk->Kl, kf0 = rk->kf0;
+    const int64_t Rl = R;   // (a radius near INT_MAX must not overflow the sums)
+    g.lo = (int)(kf0 - Rl > 0 ? kf0 - Rl : 0);
+    g.hi = (int)(kf0 + Kl + Rl < K ? kf0 + Kl + Rl : K);
+    g.hl = kf0 - g.lo, g.hr = g.hi - kf0 - Kl, g.F = g.hi - g.lo;
+    int off = 0;
+    for (int p = 0; p < rk->world; ++p) {
+        const int p0 = off, p1 = off + rk->counts[p];
+        off = p1;
+        // what arrives from p: own(p) & [lo, hi)
+        const int a = imax(p0, g.lo), b = imin(p1, g.hi);
+        g.recv_rows[p] = b > a ? b - a : 0;
+        // what goes to p: own(r) & [lo_p, hi_p)
+        const int lo_p = (int)(p0 - Rl > 0 ? p0 - Rl : 0), hi_p = (int)(p1 + Rl < K ? p1 + Rl : K);
+        const int c = imax(kf0, lo_p), d = imin(kf0 + Kl, hi_p);
+        g.seg_n[p] = d > c ? d - c : 0;
+        g.seg_f0[p] = d > c ? c - kf0 : 0;
+        g.send_rows[p] = g.seg_n[p];
+        g.send_total += g.seg_n[p];
+    }
+    for (int i = 0; i < Kl && i < TF_MAX_WINDOW_FRAMES; ++i) {
+        const int64_t gi = kf0 + i;
+        const int w0 = (int)(gi - Rl > 0 ? gi - Rl : 0), w1 = (int)(gi + Rl < K - 1 ? gi + Rl : K - 1);
+        g.win_lo[i] = w0 - g.lo, g.win_n[i] = w1 - w0 + 1;
+    }
+    return g;
+}
+
+struct WinLayout {   // exchange buffers of one windowed call inside the caller's workspace
+    size_t send, recv, ws_bank, ws_src, total;
+    size_t ws_bank_bytes, ws_src_bytes;
+};
+
+WinLayout window_layout(const tf_rank* rk, const WinGeom& g, int S, int H, int Dh, int dtype) {
+    const size_t eb = 2, D = (size_t)H * Dh;
+    WinLayout L{};
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        const size_t at = off;
+        off += up256(bytes);
+        return at;
+    };
+    // only what peers read travels: [k1, k2, v1, v2], under injection [k0, v1, v2] (sized for the former)
+    L.send = take((size_t)g.send_total * 4 * S * D * eb);
+    L.recv = take((size_t)g.F * 4 * S * D * eb);
+    // the bank part and the source part may run concurrently: a workspace each
+    L.ws_bank_bytes = tf_ext_attn_workspace_bytes(g.F, S, H, Dh, dtype);
+    L.ws_src_bytes = tf_ext_attn_workspace_bytes(rk->Kl, S, H, Dh, dtype);
+    L.ws_bank = take(L.ws_bank_bytes);
+    L.ws_src = take(L.ws_src_bytes);
+    L.total = off;
+    return L;
+}
+
+int do_halo_pack(const void* const* slabs, const int64_t* fss, int ns, void* send, const tf_rank* rk, const WinGeom& g, int S,
+                 int D, int64_t ld, int dtype, void* stream) {
+    if (tf_plan_note("halo_pack[ns=%d]", ns)) return 0;
+    return tf_window_halo_pack(slabs, fss, ns, send, rk->world, g.seg_f0, g.seg_n, rk->Kl, S, D, ld, dtype, stream);
+}
+
+// the sparse exchange: its plan token lists the rows per peer, out and in ("/"-separated, rank order)
+int do_a2a_rows(const tf_rank* rk, const void* send, void* recv, const WinGeom& g, int slabs, int64_t slab_elems, int dtype,
+                void* stream) {
+    if (tf_plan_rec) {
+        char out[4 * TF_MAX_WORLD + 8], in[4 * TF_MAX_WORLD + 8];
+        size_t no = 0, ni = 0;
+        for (int p = 0; p < rk->world; ++p) {
+            no += (size_t)snprintf(out + no, sizeof(out) - no, p ? "/%d" : "%d", (int)g.send_rows[p]);
+            ni += (size_t)snprintf(in + ni, sizeof(in) - ni, p ? "/%d" : "%d", (int)g.recv_rows[p]);
+        }
+        tf_plan_note("a2a[slabs=%d,send=%s,recv=%s]", slabs, out, in);
+        return 0;
+    }
+    return tf_all_to_all_rows(rk->comm, send, recv, g.send_rows, g.recv_rows, slabs * slab_elems, dtype, stream);
 }
 
 }  // namespace
@@ -505,6 +601,147 @@ extern "C" int tf_rank_pivotal(tf_rank* rk, const void* q, const void* k, const 
     if (!no_halo)
         if (const int rc = halo_exchange(rk, piv, inv_ext, kfo, 3, o_bs, SD, S, slot, st, "tf_rank_pivotal")) return rc;
     return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// One rank's pivotal pass over a SLIDING-WINDOW bank (include/tokenflow_hip.h): tf_rank_pivotal with a radius.  The rank needs
+// the keyframes within `radius` of its own run only: ONE halo pack, ONE sparse tf_all_to_all_rows (mostly neighbour ranks)
+// whose receive buffer is the halo-extended bank, the windowed bank part over it in place, the source part of the local frames
+// on the auxiliary compute stream beside the exchange.
+extern "C" size_t tf_rank_pivotal_window_workspace_bytes(const tf_rank* rk, int S, int H, int Dh, int dtype, int radius) {
+    if (!rk || S <= 0 || H <= 0 || Dh <= 0 || dtype == TF_F32 || radius < 0) return 0;
+    const size_t full = tf_rank_pivotal_workspace_bytes(rk, S, H, Dh, dtype);   // a covering radius IS tf_rank_pivotal
+    if (rk->world == 1 || radius >= rk->K - 1 || rk->Kl > TF_MAX_WINDOW_FRAMES) return full;
+    const size_t win = window_layout(rk, window_geometry(rk, radius), S, H, Dh, dtype).total;
+    return win > full ? win : full;   // ONE workspace whatever the radius
+}
+
+extern "C" int tf_rank_pivotal_window(tf_rank* rk, const void* q, const void* k, const void* v, const int64_t* st_in,
+                                      void* piv_ext, float* inv_ext, void* kfo_ext, int S, int H, int Dh, float scale,
+                                      int flags, int dtype, int mode, int slot, int radius, void* ws, size_t ws_bytes,
+                                      void* stream) {
+    const char* const fn = "tf_rank_pivotal_window";
+    const bool no_halo = (mode & TF_RANK_NO_HALO) != 0, want_inv = (mode & TF_RANK_INV_NORM) != 0;
+    const int mods = mode & (TF_RANK_NO_HALO | TF_RANK_INV_NORM), base = mode & ~(TF_RANK_NO_HALO | TF_RANK_INV_NORM);
+    // ---- arguments first: nothing below this block's end has touched the device
+    TF_ARG(rk && q && k && v && st_in && kfo_ext && ws && (no_halo || (piv_ext && inv_ext)), TF_ERR_NULL, "%s: null pointer", fn);
+    TF_ARG(dtype == TF_BF16 || dtype == TF_F16, TF_ERR_DTYPE, "%s: dtype %d (bf16/f16 only)", fn, dtype);
+    TF_ARG(radius >= 0, TF_ERR_SHAPE, "%s: radius %d (>= 0)", fn, radius);
+    TF_ARG(base == 0 || base == TF_RANK_BANK, TF_ERR_SHAPE,
+           "%s: mode %d (the windowed pass has the bank form only: TF_RANK_BANK with TF_RANK_NO_HALO / TF_RANK_INV_NORM)", fn, base);
+    TF_ARG(slot >= 0 && slot < TF_RANK_SLOTS, TF_ERR_SHAPE, "%s: slot %d outside [0, %d)", fn, slot, TF_RANK_SLOTS);
+    TF_ARG(!(want_inv && no_halo), TF_ERR_SHAPE, "%s: TF_RANK_INV_NORM needs the propagation state (no TF_RANK_NO_HALO)", fn);
+    TF_ARG(!(flags & (TF_ATTN_BANK_ONLY | TF_ATTN_SOURCE_ONLY)), TF_ERR_SHAPE, "%s: the part flags are the executor's own", fn);
+    if (radius >= rk->K - 1)   // every window is the whole bank: today's pass -- the same launches, the same bits
+        return tf_rank_pivotal(rk, q, k, v, st_in, piv_ext, inv_ext, kfo_ext, S, H, Dh, scale, flags, dtype, TF_RANK_BANK | mods,
+                               slot, ws, ws_bytes, stream);
+    TF_ARG(rk->Kl <= TF_MAX_WINDOW_FRAMES, TF_ERR_SHAPE, "%s: %d local keyframes (at most %d carry a window)", fn, rk->Kl,
+           TF_MAX_WINDOW_FRAMES);
+    TF_ARG(!(flags & TF_ATTN_FOLD_SCALE), TF_ERR_SHAPE, "%s: TF_ATTN_FOLD_SCALE has no windowed form", fn);
+    const WinGeom G = window_geometry(rk, radius);
+    TF_ARG(G.F < (1 << 16), TF_ERR_SHAPE, "%s: a halo-extended bank of %d frames (below 65536)", fn, G.F);
+    TF_ARG(ws_bytes >= tf_rank_pivotal_window_workspace_bytes(rk, S, H, Dh, dtype, radius), TF_ERR_WORKSPACE,
+           "%s: workspace %zu < %zu bytes", fn, ws_bytes, tf_rank_pivotal_window_workspace_bytes(rk, S, H, Dh, dtype, radius));
+
+    const int W = rk->world, Kl = rk->Kl, K = rk->K, o = (W > 1 && !no_halo) ? 1 : 0;
+    const int64_t D = (int64_t)H * Dh, SD = (int64_t)S * D;
+    const int64_t q_bs = st_in[0], q_fs = st_in[1], k_bs = st_in[2], k_fs = st_in[3], v_bs = st_in[4], v_fs = st_in[5],
+                  ld_q = st_in[6], ld = st_in[7];
+    typedef unsigned short E;   // any 16-bit element: only pointer arithmetic happens here
+    const E* ke = static_cast<const E*>(k);
+    const E* ve = static_cast<const E*>(v);
+    E* kfo = static_cast<E*>(kfo_ext);
+    E* piv = static_cast<E*>(piv_ext);
+    unsigned char* wsb = static_cast<unsigned char*>(ws);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int64_t o_bs = (int64_t)(Kl + o) * SD;   // branch stride of the halo-extended attention output
+    E* out_loc = kfo + (int64_t)o * SD;            // its local slots
+    const int inject = flags & TF_ATTN_INJECT;
+    if (!no_halo) rk->halo_set[slot] = false;
+    if (want_inv)   // (a launch of its own: the halo pack kernel carries no inverse norms)
+        if (const int rc = do_inv_norm(piv + (int64_t)o * SD, inv_ext + (int64_t)o * S, (int64_t)Kl * S, (int)D, dtype, stream))
+            return rc;
+    if (W == 1) {   // one rank: the windowed single-GPU call straight into kfo_ext
+        const int64_t strides[9] = {q_bs, q_fs, k_bs, k_fs, v_bs, v_fs, o_bs, SD, ld_q};
+        return tf_ext_attn_fwd_windows(q, k, v, out_loc, K, K, 0, S, H, Dh, ld, strides, scale, flags, dtype, G.win_lo, G.win_n, ws,
+                                       ws_bytes, stream);
+    }
+    const WinLayout L = window_layout(rk, G, S, H, Dh, dtype);
+    E* send = reinterpret_cast<E*>(wsb + L.send);
+    E* recv = reinterpret_cast<E*>(wsb + L.recv);
+    // 1. pack only what PEERS read (the choice of TF_RANK_BANK_RUNS): [k1, k2, v1, v2], under injection [k0, v1, v2]; a local
+    //    frame several peers need is written to each of their segments, the rank's own frames to its self rows
+    const void* slabs[4];
+    int64_t fss[4];
+    int ns;
+    if (inject) {
+        ns = 3;
+        slabs[0] = ke, slabs[1] = ve + v_bs, slabs[2] = ve + 2 * v_bs;
+        fss[0] = k_fs, fss[1] = fss[2] = v_fs;
+    } else {
+        ns = 4;
+        slabs[0] = ke + k_bs, slabs[1] = ke + 2 * k_bs, slabs[2] = ve + v_bs, slabs[3] = ve + 2 * v_bs;
+        fss[0] = fss[1] = k_fs, fss[2] = fss[3] = v_fs;
+    }
+    if (const int rc = do_halo_pack(slabs, fss, ns, send, rk, G, S, (int)D, ld, dtype, stream)) return rc;
+    // 2. the source part of the local frames (window-free: own-frame keys), read from q / k / v in place, on the auxiliary
+    //    compute stream: forked behind the pack, in FRONT of the exchange, joined behind the bank part.
+    //    TOKENFLOW_RANK_SRC_AUX=0: in line on the caller's stream, behind the exchange (a recorded plan lists that order)
+    const int64_t src_strides[9] = {q_bs, q_fs, k_bs, k_fs, v_bs, v_fs, o_bs, SD, ld_q};
+    auto source_part = [&](hipStream_t on) {
+        return tf_ext_attn_fwd_strided(q, k, v, out_loc, Kl, Kl, 0, S, H, Dh, ld, src_strides, scale, flags | TF_ATTN_SOURCE_ONLY,
+                                       dtype, wsb + L.ws_src, L.ws_src_bytes, on);
+    };
+    const bool fork = src_aux_enabled() && !tf_plan_rec;
+    if (fork) {
+        if (const int rc = order(rk, st, rk->as, fn)) return rc;
+        if (const int rc = source_part(rk->as)) return rc;
+    }
+    // 3. the sparse exchange on the caller's stream (every collective of a communicator on ONE stream)
+    if (const int rc = do_a2a_rows(rk, send, recv, G, ns, SD, dtype, st)) return rc;
+    if (!fork)
+        if (const int rc = source_part(st)) return rc;
+    // 4. the windowed bank part over the receive buffer [F][ns][S][D] in place (the base of a tensor whose branch 0 does not
+    //    exist lies one slab in front of its first slab: formed as an integer, never dereferenced there)
+    auto shifted = [](const E* b, int64_t elems) {
+        return reinterpret_cast<const E*>(reinterpret_cast<uintptr_t>(b) + (uintptr_t)(elems * (int64_t)sizeof(E)));
+    };
+    const int64_t fs_r = ns * SD;
+    const E* kb = inject ? recv : shifted(recv, -SD);   // [k0 | ...] or [k1, k2 | ...]
+    const E* vb = inject ? recv : shifted(recv, SD);    // [k0, v1, v2] or [k1, k2, v1, v2]
+    const int64_t strides[9] = {q_bs, q_fs, SD, fs_r, SD, fs_r, o_bs, SD, ld_q};
+    if (const int rc = tf_ext_attn_fwd_windows_part(q, kb, vb, out_loc, G.F, Kl, G.hl, S, H, Dh, D, strides, scale,
+                                                    flags | TF_ATTN_BANK_ONLY, dtype, G.win_lo, G.win_n, wsb + L.ws_bank,
+                                                    L.ws_bank_bytes, stream))
+        return rc;
+    // 5. join
+    if (fork)
+        if (const int rc = order(rk, rk->as, st, fn)) return rc;
+    // 6. the neighbour halo for the propagation, as in every mode
+    if (!no_halo)
+        if (const int rc = halo_exchange(rk, piv, inv_ext, kfo, 3, o_bs, SD, S, slot, st, fn)) return rc;
+    return 0;
+}
+
+// The sequence one windowed call issues, recorded by the call itself on a rank that owns no device object (host only).
+extern "C" int tf_rank_pivotal_window_plan(int world, int rank, int K, int S, int H, int Dh, int radius, int mode, int flags,
+                                           int dtype, char* buf, size_t len) {
+    TF_ARG(world >= 1 && world <= TF_MAX_WORLD && rank >= 0 && rank < world && K >= world && S > 0 && H > 0 && Dh > 0,
+           TF_ERR_SHAPE, "tf_rank_pivotal_window_plan: rank %d of %d over %d keyframes, S=%d H=%d Dh=%d", rank, world, K, S, H, Dh);
+    tf_rank rk{};
+    partition(&rk, K, world, rank);
+    void* const ph = reinterpret_cast<void*>((uintptr_t)1 << 40);   // never dereferenced
+    const int64_t D = (int64_t)H * Dh, SD = (int64_t)S * D;
+    const int64_t strides[8] = {rk.Kl * SD, SD, rk.Kl * SD, SD, rk.Kl * SD, SD, D, D};
+    TfPlanRec rec{buf, len, 0, 0};
+    if (buf && len) buf[0] = 0;
+    tf_plan_rec = &rec;
+    const int rc = tf_rank_pivotal_window(&rk, ph, ph, ph, strides, ph, static_cast<float*>(ph), ph, S, H, Dh, 1.0f, flags, dtype,
+                                          mode, 0, radius, ph, (size_t)-1, nullptr);
+    tf_plan_rec = nullptr;
+    if (rc) return rc;
+    TF_ARG(rec.used < len, TF_ERR_WORKSPACE, "tf_rank_pivotal_window_plan: the plan needs %zu bytes", rec.used + 1);
+    return rec.n;
 }
 
 extern "C" int tf_rank_halo_wait(tf_rank* rk, int slot, void* stream) {

@@ -249,7 +249,7 @@ def _segments(module, K=None):
     return segs
 
 
-def register_bank_window(model, radius, edits=False, anchors=None, anchor_edits=False):
+def register_bank_window(model, radius, edits=False, anchors=None, anchor_edits=False, shard=False):
     """Sliding-window keyframe bank (no counterpart in the reference, where every keyframe attends to the whole bank): in the
     pivotal passes that follow, the uncond / cond branches of keyframe i attend to the keyframes i - radius .. i + radius only
     (clamped to the bank; `ops.bank_windows`), the source branch to its own frame as always.  Consistency stays chained along
@@ -276,7 +276,14 @@ def register_bank_window(model, radius, edits=False, anchors=None, anchor_edits=
     Not generalised, ValueError at the call: `register_edits(model, E > 1)` unless edits=True, `register_segments` with several
     segments, a registered frame shard -- there the radius is held against the shard's WHOLE bank (`shard.K`), not the rank's
     local keyframes, and only a radius that covers it passes -- and, as for every multi-edit pass, graph capture
-    (INTEGRATION.md section 6 shows the driver side)."""
+    (INTEGRATION.md section 6 shows the driver side).
+    shard=True opens the window on a registered frame shard (`register_frame_shard`; long videos across GPUs): where the
+    shard's type reports `K` and takes `window=` (`FrameShard`, `NativeShard`), a radius below `shard.K - 1` passes and the
+    attention installers call `shard.pivotal_attention(..., window=radius)` -- every rank fetches only the keyframes within
+    `radius` of its own run and computes the windowed attention of its keyframes, the result of the unsharded windowed pass.
+    A radius that covers the shard's bank issues today's sharded pass.  On a windowed shard anchors, several segments and
+    n_edits > 1 are a ValueError at the pass; a shard type without `window=` raises the frame-shard error above.  Without
+    the keyword every refusal stays as it was."""
     if radius is not None:
         radius = int(radius)
         if radius < 0:
@@ -295,10 +302,11 @@ def register_bank_window(model, radius, edits=False, anchors=None, anchor_edits=
                              "keyframe, or None)")
         anchors = tuple(int(a) for a in anchors) or None
     _set_bank_window(_hook_blocks(model.unet), radius, bool(edits) and radius is not None,
-                     anchors if radius is not None else None, bool(anchor_edits) and radius is not None)
+                     anchors if radius is not None else None, bool(anchor_edits) and radius is not None,
+                     bool(shard) and radius is not None)
 
 
-def _set_bank_window(blocks, radius, edits=False, anchors=None, anchor_edits=False):
+def _set_bank_window(blocks, radius, edits=False, anchors=None, anchor_edits=False, shard=False):
     """`bank_window` (`bank_window_edits`, the multi-edit opt-in, `bank_window_anchors`: a tuple of keyframe indices, an
     int stride or None, and `bank_window_anchor_edits`, the opt-in of anchors in a multi-edit batch) on transformer blocks
     and their `attn1` (register_bank_window; tools on a bare block list)."""
@@ -308,6 +316,7 @@ def _set_bank_window(blocks, radius, edits=False, anchors=None, anchor_edits=Fal
             setattr(m, "bank_window_edits", edits)
             setattr(m, "bank_window_anchor_edits", anchor_edits)
             setattr(m, "bank_window_anchors", anchors)
+            setattr(m, "bank_window_shard", shard)      # the opt-in of a window on a registered frame shard
 
 
 def _bank_window(module, K: int):
@@ -320,9 +329,21 @@ def _bank_window(module, K: int):
     shard = _active_shard(module)   # the predicate of the attention path: a world-1 shard is the unsharded pass
     if shard is not None:
         K_all = getattr(shard, "K", None)
-        if K_all is None or radius < int(K_all) - 1:
+        if K_all is not None and radius >= int(K_all) - 1:
+            return None
+        if K_all is None or not getattr(module, "bank_window_shard", False) or not getattr(shard, "supports_window", False):
             raise ValueError("register_bank_window: a sliding-window bank on a registered frame shard is not supported")
-        return None
+        # the opt-in (register_bank_window(..., shard=True)): the shard runs the windowed pass; what it does not generalise
+        if int(getattr(module, "n_edits", 1)) > 1:
+            raise ValueError("register_bank_window: a sliding-window bank on a registered frame shard runs one edit "
+                             "(register_edits, n_edits > 1 is not supported there)")
+        if getattr(module, "bank_window_anchors", None) is not None:
+            raise ValueError("register_bank_window: anchor keyframes on a registered frame shard are not supported (every "
+                             "rank would have to hold the anchors)")
+        if getattr(module, "keyframe_segments", None) is not None:
+            raise ValueError("register_bank_window: a sliding-window bank in a pass of several keyframe segments "
+                             "(register_segments) is not supported")
+        return radius
     if radius >= K - 1:
         return None
     if int(getattr(module, "n_edits", 1)) > 1 and not getattr(module, "bank_window_edits", False):
@@ -584,7 +605,7 @@ def _make_sa_forward(self, pnp: bool):
                 q, k, v = q.to(cdt), k.to(cdt), v.to(cdt)
         shard = None if is_cross else _active_shard(self)
         E = 1 if is_cross else _n_edits(self)
-        # (a window excludes segments and shards, and edits unless opted in; the pass carries q.shape[0] / (1 + 2E) keyframes)
+        # (a window excludes segments, and edits and shards unless opted in; the pass carries q.shape[0] / (1 + 2E) keyframes)
         radius = None if is_cross else _bank_window(self, q.shape[0] // (1 + 2 * E))
         anchors = None if radius is None else _bank_anchors(self, q.shape[0] // (1 + 2 * E))
         segs = None if is_cross else _segments(self, q.shape[0] // 3)
@@ -595,6 +616,8 @@ def _make_sa_forward(self, pnp: bool):
             if E > 1:
                 _need_edit_shard(shard)
                 out = shard.pivotal_attention(q, k, v, self.heads, self.scale, False, n_edits=E, inject_mask=mask)
+            elif radius is not None:   # register_bank_window(..., shard=True): the rank's keyframes against their windows
+                out = shard.pivotal_attention(q, k, v, self.heads, self.scale, inject, window=radius)
             else:
                 out = shard.pivotal_attention(q, k, v, self.heads, self.scale, inject)
         elif anchors is not None and E > 1:   # ... several prompts with anchors: every edit's bank branches read the frame sets

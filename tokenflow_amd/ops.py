@@ -250,6 +250,21 @@ def attn_windows_plan(K: int, windows, S: int, heads: int, dh: int, inject: bool
                         _DT[dtype], ctypes.cast(lo, ctypes.c_void_p), ctypes.cast(n, ctypes.c_void_p))
 
 
+def attn_windows_part_plan(K: int, Kq: int, q_frame0: int, windows, S: int, heads: int, dh: int, inject: bool,
+                           dtype: torch.dtype = torch.bfloat16, part: str = "bank", out_dtype: Optional[torch.dtype] = None,
+                           no_split: Optional[bool] = None, fused: Optional[bool] = None, hints: int = 0) -> list:
+    """The launches `ext_attn_windows_views` makes for dense tensors, as tokens (tf_ext_attn_windows_part_plan): Kq query frames
+    from bank frame q_frame0 on, one window each, over a bank of K frames; part "bank" (TF_ATTN_BANK_ONLY: what a frame-sharded
+    rank runs over its halo-extended bank) or "all" (= `attn_windows_plan` for Kq = K).  The bank launch's token carries ',win'.
+    The source part of a windowed pass is window-free: `attn_plan(Kq, Kq, ..., part="source")`.  Host only: needs no GPU."""
+    if part not in ("bank", "all"):
+        raise ValueError(f"attn_windows_part_plan: part {part!r} (\"bank\" or \"all\": the source part is window-free)")
+    lo, n = _windows("attn_windows_part_plan", windows, K, Kq, int(q_frame0))
+    flags = _attn_flags(inject, part, out_dtype == torch.float32, False, no_split, fused, hints)
+    return _plan_tokens("tf_ext_attn_windows_part_plan", _lib.load().tf_ext_attn_windows_part_plan, K, Kq, int(q_frame0), S,
+                        heads, dh, flags, _DT[dtype], ctypes.cast(lo, ctypes.c_void_p), ctypes.cast(n, ctypes.c_void_p))
+
+
 def attn_windows_edits_plan(K: int, windows, S: int, heads: int, dh: int, n_edits: int, inject_mask: int,
                             dtype: torch.dtype = torch.bfloat16, out_dtype: Optional[torch.dtype] = None,
                             no_split: Optional[bool] = None, fused: Optional[bool] = None, multi_v: Optional[bool] = None,
@@ -790,6 +805,48 @@ def ext_attn_views(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch
     return out
 
 
+def ext_attn_windows_views(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, heads: int, scale: float,
+                           inject: bool, windows, part: str = "bank", branch0=(0, 0, 0, 0), q_frame0: int = 0,
+                           no_split: Optional[bool] = None, stream: Optional[int] = None, fused: Optional[bool] = None,
+                           hints: int = 0) -> torch.Tensor:
+    """`ext_attn_windows` on strided 4-D views [branches, frames, S, D] (tf_ext_attn_fwd_windows_part), shaped like
+    `ext_attn_views`: the Kq = q.shape[1] query frames are the bank frames q_frame0 .. of k / v, `windows` holds one
+    (first frame, frames) pair per QUERY frame in bank coordinates.  part "bank": only the uncond / cond branches, k and v hold
+    only the slabs those read (branch0 as in `ext_attn_views`: under injection k is the source slab with branch0 = 0) -- what a
+    frame-sharded rank runs over its halo-extended receive buffer; part "all": the whole windowed call.  The source part of a
+    windowed pass is window-free: `ext_attn_views(..., part="source")`.  Both parts together equal `ext_attn_windows` bit for
+    bit under no_split wherever the plans name the same kernel form."""
+    if part not in ("bank", "all"):
+        raise ValueError(f"ext_attn_windows_views: part {part!r} (\"bank\" or \"all\": the source part is window-free)")
+    dev = _need_gpu(q, k, v, out)
+    lib = _lib.load()
+    S, D = k.shape[2], k.shape[3]
+    K, Kq, dh = k.shape[1], q.shape[1], D // heads
+    dt = _DT.get(q.dtype)
+    if dt is None or dt == _lib.TF_F32 or k.dtype != q.dtype or v.dtype != q.dtype or D % heads:
+        raise TypeError("ext_attn_windows_views: q/k/v must share dtype bf16 or f16")
+    lo, n = _windows("ext_attn_windows_views", windows, K, Kq, int(q_frame0))
+    qp, q_bs, q_fs, ld_q = _view_base(q, branch0[0], S, "q")
+    kp, k_bs, k_fs, ld = _view_base(k, branch0[1], S, "k")
+    vp, v_bs, v_fs, ld_v = _view_base(v, branch0[2], S, "v")
+    op, o_bs, o_fs, ld_o = _view_base(out, branch0[3], S, "out")
+    if ld_v != ld or ld_o != D or out.shape[1] != Kq or v.shape[1] != K:
+        raise ValueError("ext_attn_windows_views: k and v need one token stride, out a dense one; frames of v = frames of k")
+    if out.dtype not in (q.dtype, torch.float32):
+        raise TypeError("ext_attn_windows_views: out dtype")
+    flags = _attn_flags(inject, part, out.dtype == torch.float32, False, no_split, fused, hints)
+    key = (K, S, heads, dh, dt)
+    nbytes = _attn_ws_bytes.get(key)
+    if nbytes is None:
+        nbytes = _attn_ws_bytes[key] = lib.tf_ext_attn_workspace_bytes(K, S, heads, dh, dt)
+    ws = _workspace(nbytes, q.device, stream=stream)
+    strides = (ctypes.c_int64 * 9)(q_bs, q_fs, k_bs, k_fs, v_bs, v_fs, o_bs, o_fs, ld_q)
+    _launch(dev, "tf_ext_attn_fwd_windows_part", lib.tf_ext_attn_fwd_windows_part, qp, kp, vp, op, K, Kq, int(q_frame0), S,
+            heads, dh, ld, ctypes.cast(strides, ctypes.c_void_p), float(scale), flags, dt, ctypes.cast(lo, ctypes.c_void_p),
+            ctypes.cast(n, ctypes.c_void_p), ws.data_ptr(), ws.numel(), stream=stream)
+    return out
+
+
 def ext_attn_edits_views(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, heads: int, scale: float,
                          n_edits: int, inject_mask: int, part: str = "all", qk_compact: bool = False,
                          branch0=(0, 0, 0, 0), q_frame0: int = 0, fold_scale: Optional[bool] = None,
@@ -1127,6 +1184,39 @@ def head_pack(slabs: Sequence[torch.Tensor], W: int, out: Optional[torch.Tensor]
     _launch(dev, "tf_head_pack", lib.tf_head_pack, ctypes.cast(ptrs, ctypes.c_void_p), ctypes.cast(fs, ctypes.c_void_p),
             ns, send.data_ptr(), W, Kl, S, hd, ld, slabs[0].element_size())
     return send
+
+
+def window_halo_pack(slabs: Sequence[torch.Tensor], segments, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """slabs: ns <= 6 tensors [Kl, S, D] (frame stride free, one token stride, one 16-bit dtype); segments: one (first local
+    frame, frames) pair per peer, in rank order -> the send buffer [rows, ns, S, D] of ONE row all-to-all, rows = the segments'
+    frames one after the other, frame-major [frame][slab][S][D] (tf_window_halo_pack, one launch).  A frame in several segments
+    is written to each; an empty segment contributes nothing.  The packing of a windowed frame shard
+    (`sharded.window_halo_plan(...).send`)."""
+    dev = _need_gpu(*slabs)
+    lib = _lib.load()
+    Kl, S, D = slabs[0].shape
+    ns = len(slabs)
+    ld = slabs[0].stride(1)
+    dt = _DT.get(slabs[0].dtype)
+    if any(t.shape != (Kl, S, D) or t.stride(2) != 1 or t.stride(1) != ld or t.dtype != slabs[0].dtype for t in slabs):
+        raise ValueError("window_halo_pack: slabs must be [Kl, S, D] views sharing dtype and token stride")
+    seg = [(int(f0), int(n)) for f0, n in segments]
+    if not seg or any(n < 0 or f0 < 0 or f0 + n > Kl for f0, n in seg):
+        raise ValueError(f"window_halo_pack: segments {seg} (runs of the {Kl} local frames, one per peer)")
+    rows = sum(n for _, n in seg)
+    if out is None:
+        out = torch.empty(rows, ns, S, D, dtype=slabs[0].dtype, device=slabs[0].device)
+    elif out.shape != (rows, ns, S, D) or not out.is_contiguous() or out.dtype != slabs[0].dtype:
+        raise ValueError(f"window_halo_pack: `out` must be a contiguous [{rows}, {ns}, {S}, {D}] tensor of the slabs' dtype")
+    if rows == 0:      # nobody reads this rank's frames: nothing to launch
+        return out
+    ptrs = (ctypes.c_void_p * ns)(*[t.data_ptr() for t in slabs])
+    fs = (ctypes.c_int64 * ns)(*[t.stride(0) for t in slabs])
+    f0s, cnt = (ctypes.c_int * len(seg))(*[f0 for f0, _ in seg]), (ctypes.c_int * len(seg))(*[n for _, n in seg])
+    _launch(dev, "tf_window_halo_pack", lib.tf_window_halo_pack, ctypes.cast(ptrs, ctypes.c_void_p),
+            ctypes.cast(fs, ctypes.c_void_p), ns, out.data_ptr(), len(seg), ctypes.cast(f0s, ctypes.c_void_p),
+            ctypes.cast(cnt, ctypes.c_void_p), Kl, S, D, ld, -1 if dt is None else dt)
+    return out
 
 
 def head_unpack(recv: torch.Tensor, dsts: Sequence[torch.Tensor]) -> None:

@@ -69,6 +69,7 @@ and agrees with the sharded results within the attention's parity bound, like an
 `FrameShard(..., attn_split=True)` (or TOKENFLOW_SHARD_ATTN_SPLIT=1) lets the small grid of a rank split
 the bank over extra workgroups and merge: faster, held to the ORACLE's bound.
 """
+import collections
 import ctypes
 import os
 from typing import Optional
@@ -130,6 +131,44 @@ def _all_to_all(recv: torch.Tensor, send: torch.Tensor, group, out_rows=None, in
         recv.copy_(host)
         return _Done() if async_op else None
     return dist.all_to_all_single(recv, send, out_rows, in_rows, group=group, async_op=async_op)
+
+
+WindowHaloPlan = collections.namedtuple(
+    "WindowHaloPlan", "K world rank radius counts offsets kf0 Kl lo hi hl hr F send recv send_rows recv_rows windows")
+
+
+def window_halo_plan(K: int, world: int, rank: int, radius: int) -> WindowHaloPlan:
+    """Exchange geometry of a sliding-window bank on a frame shard (pure arithmetic; csrc/rank_exec.hip computes the same from
+    the same four numbers).  Rank r owns the keyframes [kf0, kf0 + Kl) (`FrameShard.counts` / `offsets`); with radius R it reads
+    the global frames [lo, hi) = [max(0, kf0 - R), min(K, kf0 + Kl + R)): hl = kf0 - lo halo frames on the left, hr on the
+    right, F = hl + Kl + hr in all.
+      send[p] = (first LOCAL frame, frames) of own(r) & [lo_p, hi_p): what peer p reads of this rank's frames (for R > Kl a
+                frame goes to several peers); send[r] = (0, Kl), the rank's own frames as its self rows
+      recv[p] = (first GLOBAL frame, frames) of own(p) & [lo, hi): what arrives from peer p -- in rank order these are the
+                frames lo .. hi - 1 in ascending order, so the receive buffer of ONE row all-to-all IS the extended bank
+      send_rows / recv_rows: the frame counts of the two, the row counts of that exchange
+      windows[i] = (first frame, frames) of local query i (global keyframe kf0 + i) in the extended bank's coordinates:
+                `ops.bank_windows(K, R)[kf0 + i]` shifted by -lo; the queries are the bank frames hl .. hl + Kl - 1."""
+    K, W, r, R = int(K), int(world), int(rank), int(radius)
+    if W < 1 or not 0 <= r < W or K < W:
+        raise ValueError(f"window_halo_plan: rank {r} of {W} over {K} keyframes (every rank owns at least one)")
+    if R < 0:
+        raise ValueError(f"window_halo_plan: radius={R} (>= 0)")
+    counts = [K // W + (1 if p < K % W else 0) for p in range(W)]
+    offsets = [sum(counts[:p]) for p in range(W)]
+    reach = lambda p: (max(0, offsets[p] - R), min(K, offsets[p] + counts[p] + R))      # noqa: E731
+    kf0, Kl = offsets[r], counts[r]
+    lo, hi = reach(r)
+    send, recv = [], []
+    for p in range(W):
+        a, b = max(offsets[p], lo), min(offsets[p] + counts[p], hi)
+        recv.append((a, b - a) if b > a else (0, 0))
+        lo_p, hi_p = reach(p)
+        c, d = max(kf0, lo_p), min(kf0 + Kl, hi_p)
+        send.append((c - kf0, d - c) if d > c else (0, 0))
+    windows = [(w0 - lo, n) for w0, n in ops.bank_windows(K, R)[kf0:kf0 + Kl]]
+    return WindowHaloPlan(K, W, r, R, counts, offsets, kf0, Kl, lo, hi, kf0 - lo, hi - kf0 - Kl, hi - lo, send, recv,
+                          [n for _, n in send], [n for _, n in recv], windows)
 
 
 # (an explicit "bank_runs" for several edits on a shard built without the opt-in)
@@ -371,8 +410,11 @@ class FrameShard:
 
     def pivotal_attention(self, q_local, k_local, v_local, heads: int, scale: float, inject: bool,
                           mode: Optional[str] = None, out4: Optional[torch.Tensor] = None, n_edits: int = 1,
-                          inject_mask: Optional[int] = None):
+                          inject_mask: Optional[int] = None, window: Optional[int] = None):
         """Extended attention for the local keyframes against all K keyframes -> [3*Kl,S,D].
+        window = R: a sliding-window bank (`_pivotal_window`; NOT TokenFlow's result): the bank branches of keyframe g attend
+        to the keyframes g - R .. g + R only, of which the rank fetches just those within R of its own run.  None, or a radius
+        that covers the bank (R >= K - 1), is the pass without the keyword; one edit only.
         mode: "heads" | "bank" | "bank_runs" | None (= `auto_mode`, chosen per block).
         out4: a [3,Kl,S,D] view (dense frames, free branch stride) the result is written into in place -- the
         keyframe slots 1.. of a halo-extended buffer (`ext_alloc`); returned as is.
@@ -380,6 +422,8 @@ class FrameShard:
         injection state per edit (bit e = edit e uses the source's q and k; None = `inject` for every edit).  Modes "heads"
         and "bank"; the slices of edit e equal the single-edit pass on [source | uncond_e | cond_e] bit for bit in the
         one-pass form."""
+        if self._window(window, n_edits, mode) is not None:
+            return self._pivotal_window(q_local, k_local, v_local, heads, scale, inject, int(window), out4)
         if n_edits != 1:
             return self._pivotal_edits(q_local, k_local, v_local, heads, scale, inject, mode, out4, int(n_edits), inject_mask)
         if self.world == 1:
@@ -398,6 +442,74 @@ class FrameShard:
         if mode == "bank_runs":
             return self._pivotal_bank_runs(q_local, k_local, v_local, heads, scale, inject, out4)
         return self._pivotal_bank(q_local, k_local, v_local, heads, scale, inject, out4)
+
+    # ------------------------------------------------------------------ pivotal pass over a sliding-window bank
+    supports_window = True      # `pivotal_attention` / `pivotal_block` take window= (hooks.register_bank_window(shard=True))
+
+    def _window(self, window, n_edits: int = 1, mode=None):
+        """The radius of a windowed pass, or None where the pass is the one without the keyword (no window, or one that covers
+        the bank); the combinations that are out of scope raise.  The windowed pass has ONE exchange pattern: an explicit
+        `mode` beside a window that does not cover the bank is an error, not ignored."""
+        if window is None:
+            return None
+        R = int(window)
+        if R < 0:
+            raise ValueError(f"FrameShard: window={window} (a radius >= 0, or None for the whole bank)")
+        if R >= self.K - 1:
+            return None
+        if mode is not None:
+            raise ValueError(f"FrameShard: mode={mode!r} beside window={R}: the windowed pass has one exchange pattern of its "
+                             "own (pass mode=None)")
+        if int(n_edits) != 1:
+            raise ValueError("FrameShard: a sliding-window bank on a frame shard runs one edit (n_edits > 1 with window= is "
+                             "not supported)")
+        from . import _lib
+        if self.Kl > _lib.TF_MAX_WINDOW_FRAMES:
+            raise ValueError(f"FrameShard: {self.Kl} local keyframes (at most {_lib.TF_MAX_WINDOW_FRAMES} carry a window)")
+        return R
+
+    def _pivotal_window(self, q_local, k_local, v_local, heads: int, scale: float, inject: bool, R: int, out4=None):
+        """The windowed pass (module text of `window_halo_plan`): the same packing, exchange and two attention calls as the
+        native executor's tf_rank_pivotal_window -- the same bits on the same transport, and the bits of ONE process issuing
+        `ops.ext_attn_windows_views(part="bank")` with `ops.bank_windows(K, R)` plus the source-only call on the full tensors.
+          1. ONE `ops.window_halo_pack` of the slabs PEERS read ([k1,k2,v1,v2]; under injection [k0,v1,v2]: the choice of
+             `_bank_gather(peers_only=True)`) for the frames each peer's windows reach, own frames as self rows;
+          2. ONE row all-to-all with the sparse counts: the receive buffer is the extended bank [F, slabs, S, D];
+          3. the source part of the local frames, window-free, on the caller's own tensors;
+          4. the bank part over the receive buffer in place, Kq = Kl, q_frame0 = hl, the local window table.
+        No overlap here (through gloo the exchange is staged through the host anyway)."""
+        B, S, D = q_local.shape
+        Kl = self.Kl
+        ns_ = not self.attn_split
+        if self.world == 1:
+            out = None if out4 is None else out4.view(q_local.shape)
+            return ops.ext_attn_windows(q_local, k_local, v_local, heads, scale, inject, ops.bank_windows(self.K, R), out=out,
+                                        no_split=ns_)
+        plan = window_halo_plan(self.K, self.world, self.rank, R)
+        dev, dt = q_local.device, q_local.dtype
+
+        def frames(t):     # [3*Kl, S, D] (token stride free) -> [3, Kl, S, D] view
+            if t.stride(2) != 1 or t.stride(0) != S * t.stride(1):
+                t = t.contiguous()
+            return t.view(3, Kl, S, D) if t.is_contiguous() else t.unflatten(0, (3, Kl))
+        q3, k3, v3 = frames(q_local), frames(k_local), frames(v_local)
+        if k3.stride(2) != v3.stride(2):
+            k3, v3 = k3.contiguous(), v3.contiguous()
+        slabs = [k3[0], v3[1], v3[2]] if inject else [k3[1], k3[2], v3[1], v3[2]]
+        ns = len(slabs)
+        send = ops.window_halo_pack(slabs, plan.send, out=self._buf("win_send", (sum(plan.send_rows), ns, S, D), dt, dev))
+        recv = self._buf("win_recv", (plan.F, ns, S, D), dt, dev)
+        self._a2a(recv.view(plan.F, -1), send.view(send.shape[0], -1), plan.recv_rows, plan.send_rows)
+        out = torch.empty(3, Kl, S, D, dtype=dt, device=dev) if out4 is None else out4
+        ops.ext_attn_views(q3, k3, v3, out, heads, scale, inject, "source", no_split=ns_)
+        rp = recv.permute(1, 0, 2, 3)                                   # [ns, F, S, D] views: frame stride ns*S*D
+        if inject:     # k holds the source slab alone (branch 0), v the two value banks (branches 1, 2)
+            ops.ext_attn_windows_views(q3, rp[0:1], rp[1:3], out, heads, scale, True, plan.windows, "bank",
+                                       branch0=(0, 0, 1, 0), q_frame0=plan.hl, no_split=ns_)
+        else:
+            ops.ext_attn_windows_views(q3, rp[0:2], rp[2:4], out, heads, scale, False, plan.windows, "bank",
+                                       branch0=(0, 1, 1, 0), q_frame0=plan.hl, no_split=ns_)
+        return out.view(3 * Kl, S, D) if out4 is None else out4
 
     # ------------------------------------------------------------------ pivotal pass of a multi-edit batch
     def _pivotal_edits(self, q_local, k_local, v_local, heads, scale, inject, mode, out4, E, inject_mask):
@@ -636,8 +748,8 @@ class FrameShard:
 
     def pivotal_block(self, q_local, k_local, v_local, heads: int, scale: float, inject: bool, ext,
                       mode: Optional[str] = None, inv_norm: bool = False, n_edits: int = 1,
-                      inject_mask: Optional[int] = None):
-        """n_edits / inject_mask: as `pivotal_attention`; `ext` from `ext_alloc(..., n_edits=)`; the ONE grouped exchange
+                      inject_mask: Optional[int] = None, window: Optional[int] = None):
+        """n_edits / inject_mask / window: as `pivotal_attention`; `ext` from `ext_alloc(..., n_edits=)`; the ONE grouped exchange
         carries the last keyframe of all 1 + 2E branches of the attention output.
         The pivotal pass of one block on this rank, for the reference's call order (one pivotal pass over all
         blocks, then the chunk passes): `ext` = `ext_alloc(...)` whose pivot / inverse-norm slots o.. the caller has
@@ -655,7 +767,9 @@ class FrameShard:
         if inv_norm:
             ops.pivot_inv_norm(piv[o:], out=inv[o:])
         nbr = 1 + 2 * int(n_edits)
-        if n_edits == 1:
+        if self._window(window, n_edits, mode) is not None:
+            self.pivotal_attention(q_local, k_local, v_local, heads, scale, inject, out4=kfo[:, o:], window=window)
+        elif n_edits == 1:
             self.pivotal_attention(q_local, k_local, v_local, heads, scale, inject, mode=mode, out4=kfo[:, o:])
         else:
             self.pivotal_attention(q_local, k_local, v_local, heads, scale, inject, mode=mode, out4=kfo[:, o:],
@@ -866,29 +980,34 @@ class NativeShard(FrameShard):
             pass
 
     def pivotal_attention(self, q_local, k_local, v_local, heads: int, scale: float, inject: bool,
-                          mode: Optional[str] = None, out4: Optional[torch.Tensor] = None):
+                          mode: Optional[str] = None, out4: Optional[torch.Tensor] = None, window: Optional[int] = None):
         """`FrameShard.pivotal_attention` as one library call (tf_rank_pivotal with TF_RANK_NO_HALO): what the hook path
-        calls from `attn1` (its cached attention output is the to_out-projected one, so the halo stays the block's)."""
+        calls from `attn1` (its cached attention output is the to_out-projected one, so the halo stays the block's).
+        window = R: the windowed pass, ONE tf_rank_pivotal_window call."""
+        R = self._window(window, 1, mode)
         if self.world == 1 or out4 is not None or not q_local.is_cuda or q_local.dtype not in (torch.bfloat16,
                                                                                                 torch.float16):
+            if R is not None:
+                return FrameShard.pivotal_attention(self, q_local, k_local, v_local, heads, scale, inject, out4=out4, window=R)
             return super().pivotal_attention(q_local, k_local, v_local, heads, scale, inject, mode=mode, out4=out4)
         B, S, D = q_local.shape
         out = torch.empty(3, self.Kl, S, D, dtype=q_local.dtype, device=q_local.device)
-        self._native(q_local, k_local, v_local, heads, scale, inject, mode, None, None, out, no_halo=True)
+        self._native(q_local, k_local, v_local, heads, scale, inject, mode, None, None, out, no_halo=True, window=R)
         return out.view(B, S, D)
 
     def pivotal_block(self, q_local, k_local, v_local, heads: int, scale: float, inject: bool, ext,
-                      mode: Optional[str] = None, inv_norm: bool = False):
+                      mode: Optional[str] = None, inv_norm: bool = False, window: Optional[int] = None):
         piv, inv, kfo = ext
         B, S, D = q_local.shape
         Kl = self.Kl
         o = 1 if self.world > 1 else 0
         slot = self._native(q_local, k_local, v_local, heads, scale, inject, mode, piv, inv, kfo, no_halo=False,
-                            inv_norm=inv_norm)
+                            inv_norm=inv_norm, window=self._window(window, 1, mode))
         reqs = [_SlotWait(self, slot, q_local.device)] if self.world > 1 else []
         return piv, inv, kfo.view(3 * (Kl + o), S, D), reqs
 
-    def _native(self, q_local, k_local, v_local, heads, scale, inject, mode, piv, inv, kfo, no_halo, inv_norm=False):
+    def _native(self, q_local, k_local, v_local, heads, scale, inject, mode, piv, inv, kfo, no_halo, inv_norm=False,
+                window=None):
         from . import _lib
         lib = _lib.load()
         B, S, D = q_local.shape
@@ -910,17 +1029,29 @@ class NativeShard(FrameShard):
         strides = (ctypes.c_int64 * 8)(q3.stride(0), q3.stride(1), k3.stride(0), k3.stride(1), v3.stride(0), v3.stride(1),
                                        q3.stride(2), k3.stride(2))
         dh = D // heads
-        key = (S, heads, dh, dt, q_local.device)
+        key = (S, heads, dh, dt, q_local.device, window)
         ws = self._nws.get(key)
         if ws is None:
-            nbytes = lib.tf_rank_pivotal_workspace_bytes(self._rk, S, heads, dh, dt)
+            if window is None:
+                nbytes = lib.tf_rank_pivotal_workspace_bytes(self._rk, S, heads, dh, dt)
+            else:
+                nbytes = lib.tf_rank_pivotal_window_workspace_bytes(self._rk, S, heads, dh, dt, int(window))
             ws = self._nws[key] = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=q_local.device)
         flags = (_lib.TF_ATTN_INJECT if inject else 0) | (0 if self.attn_split else _lib.TF_ATTN_NO_SPLIT)
-        if ops.FOLD_SCALE:
+        if ops.FOLD_SCALE and window is None:      # (a windowed call has no folded-scale form: `ops.ext_attn_windows`)
             flags |= _lib.TF_ATTN_FOLD_SCALE
         slot = self._slot
         if not no_halo:
             self._slot = (slot + 1) % _lib.TF_RANK_SLOTS
+        if window is not None:      # the windowed pass: ONE tf_rank_pivotal_window call
+            m = _lib.TF_RANK_BANK | (_lib.TF_RANK_NO_HALO if no_halo else 0) | (_lib.TF_RANK_INV_NORM if inv_norm else 0)
+            rc = lib.tf_rank_pivotal_window(self._rk, q3.data_ptr(), k3.data_ptr(), v3.data_ptr(), strides,
+                                            None if piv is None else piv.data_ptr(), None if inv is None else inv.data_ptr(),
+                                            kfo.data_ptr(), S, heads, dh, float(scale), flags, dt, m, slot, int(window),
+                                            ws.data_ptr(), ws.numel(), torch.cuda.current_stream(q_local.device).cuda_stream)
+            if rc:
+                _lib.check(rc, "tf_rank_pivotal_window")
+            return slot
         m = ({"heads": _lib.TF_RANK_HEADS, "bank_runs": _lib.TF_RANK_BANK_RUNS}.get(mode, _lib.TF_RANK_BANK)
              | (_lib.TF_RANK_NO_HALO if no_halo else 0)
              | (_lib.TF_RANK_INV_NORM if inv_norm else 0))
@@ -962,12 +1093,14 @@ class NativeEditShard(NativeShard):
 
     def pivotal_attention(self, q_local, k_local, v_local, heads: int, scale: float, inject: bool,
                           mode: Optional[str] = None, out4: Optional[torch.Tensor] = None, n_edits: int = 1,
-                          inject_mask: Optional[int] = None):
+                          inject_mask: Optional[int] = None, window: Optional[int] = None):
         """`FrameShard.pivotal_attention` with n_edits / inject_mask; E > 1 is one tf_rank_pivotal_edits call with
-        TF_RANK_NO_HALO (what the hook path calls from `attn1`)."""
+        TF_RANK_NO_HALO (what the hook path calls from `attn1`).  window=: one edit only, `NativeShard`'s windowed pass."""
         E = int(n_edits)
+        self._window(window, E, mode)      # (a windowed multi-edit batch raises)
         if E == 1:
-            return super().pivotal_attention(q_local, k_local, v_local, heads, scale, inject, mode=mode, out4=out4)
+            return super().pivotal_attention(q_local, k_local, v_local, heads, scale, inject, mode=mode, out4=out4,
+                                             window=window)
         if self.world == 1 or out4 is not None or not q_local.is_cuda or q_local.dtype not in (torch.bfloat16,
                                                                                                 torch.float16):
             return FrameShard.pivotal_attention(self, q_local, k_local, v_local, heads, scale, inject, mode=mode, out4=out4,
@@ -980,10 +1113,12 @@ class NativeEditShard(NativeShard):
 
     def pivotal_block(self, q_local, k_local, v_local, heads: int, scale: float, inject: bool, ext,
                       mode: Optional[str] = None, inv_norm: bool = False, n_edits: int = 1,
-                      inject_mask: Optional[int] = None):
+                      inject_mask: Optional[int] = None, window: Optional[int] = None):
         E = int(n_edits)
+        self._window(window, E, mode)      # (a windowed multi-edit batch raises)
         if E == 1:
-            return super().pivotal_block(q_local, k_local, v_local, heads, scale, inject, ext, mode=mode, inv_norm=inv_norm)
+            return super().pivotal_block(q_local, k_local, v_local, heads, scale, inject, ext, mode=mode, inv_norm=inv_norm,
+                                         window=window)
         mask = self._mask(E, inject, inject_mask)
         piv, inv, kfo = ext
         _, S, D = q_local.shape
@@ -1059,3 +1194,16 @@ def rank_edits_plan(world: int, rank: int, K: int, S: int, heads: int, dh: int, 
     fl = int(flags) | (_lib.TF_ATTN_NO_SPLIT if no_split else 0)
     return ops._plan_tokens("tf_rank_pivotal_edits_plan", _lib.load().tf_rank_pivotal_edits_plan, int(world), int(rank),
                             int(K), S, heads, dh, int(n_edits), int(inject_mask), m, fl, ops._DT[dtype])
+
+
+def rank_window_plan(world: int, rank: int, K: int, S: int, heads: int, dh: int, radius: int, inject: bool = False,
+                     dtype: torch.dtype = torch.bfloat16, no_split: bool = True, no_halo: bool = False,
+                     inv_norm: bool = False, flags: int = 0) -> list:
+    """The sequence ONE windowed `NativeShard` block call issues on `rank` of `world` ranks, as tokens
+    (tf_rank_pivotal_window_plan: e.g. ['halo_pack[ns=4]', 'a2a[slabs=4,send=3/1,recv=3/1]', <source tokens>, <bank tokens with
+    ',win'>, 'halo[n=5]']).  Recorded by the executing code itself; host only: needs no GPU and no communicator."""
+    from . import _lib
+    m = _lib.TF_RANK_BANK | (_lib.TF_RANK_NO_HALO if no_halo else 0) | (_lib.TF_RANK_INV_NORM if inv_norm else 0)
+    fl = int(flags) | (_lib.TF_ATTN_NO_SPLIT if no_split else 0) | (_lib.TF_ATTN_INJECT if inject else 0)
+    return ops._plan_tokens("tf_rank_pivotal_window_plan", _lib.load().tf_rank_pivotal_window_plan, int(world), int(rank),
+                            int(K), S, heads, dh, int(radius), m, fl, ops._DT[dtype])

@@ -182,8 +182,14 @@ def main():
                          "on the loopback transport); 1 = today's single-edit step")
     ap.add_argument("--inject-mask", type=lambda x: int(x, 0), default=None, metavar="M",
                     help="--edits: the injection mask of the injected blocks in an inject=1 step (default: every edit)")
+    ap.add_argument("--window", type=int, default=None, metavar="R",
+                    help="the sliding-window bank of radius R on the shard (pivotal_block(..., window=R): FrameShard and --native; "
+                         "one edit).  The exchange of every level is then the sparse row all-to-all of the windowed pass: one arm "
+                         "per attention form (the mode labels do not apply); the loopback wire model sees its per-peer row counts")
     args = ap.parse_args()
     E = args.edits
+    if args.window is not None and E > 1:
+        ap.error("--window runs one edit (a windowed shard has no multi-edit form)")
     mask = (1 << E) - 1 if args.inject_mask is None else args.inject_mask
     if E > 1 and args.world < 2:
         ap.error("--edits needs --world >= 2 (the two-pass rank step)")
@@ -195,9 +201,11 @@ def main():
         for mode_name in ("auto", "heads", "bank", "bank_runs", "auto+runs"):
             if args.only and args.only != f"{'split' if split else 'onepass'},{mode_name}":
                 continue
+            if args.window is not None and mode_name != "auto" and not args.only:
+                continue      # the windowed pass has one exchange pattern: one arm per attention form, not one per mode label
             runs_e = E > 1 and mode_name in ("bank_runs", "auto+runs")   # the shard's edit_runs opt-in (TF_RANK_BANK_EDIT_RUNS)
             opt_in = mode_name == "auto+runs"       # FrameShard(bank_runs=True): auto_mode may answer "bank_runs"
-            mode = None if mode_name in ("auto", "auto+runs") else mode_name
+            mode = None if mode_name in ("auto", "auto+runs") or args.window is not None else mode_name
             wire = tuple(float(x) for x in args.wire_model.split(",")) if args.wire_model else None
             if args.native or E > 1:
                 from tokenflow_amd import _lib
@@ -217,6 +225,13 @@ def main():
                 shard = sharded.FrameShard(cfg.K, comm=comm, attn_split=split, bank_runs=opt_in)
             if mode == "heads" and any(l[2] % args.world for l in cfg.levels):
                 continue
+            if args.window is not None:      # every pivotal pass of the step and of the isolated blocks takes the window
+                plain = shard.pivotal_block
+                shard.pivotal_block = lambda *a, _plain=plain, **kw: _plain(*a, **dict(kw, window=args.window))
+                plan = sharded.window_halo_plan(cfg.K, args.world, args.rank, args.window)
+                print(f"=== sliding-window bank, radius {args.window}: rank {args.rank} reads frames [{plan.lo}, {plan.hi}) "
+                      f"({plan.F - plan.Kl} remote of {cfg.K - plan.Kl}); rows out {plan.send_rows}, rows in {plan.recv_rows}",
+                      flush=True)
             gen = torch.Generator(device=dev).manual_seed(1234 + args.rank)
             if E > 1:
                 blocks = [EditBlock(cfg, lvl, inj, shard, gen, dev, E) for lvl, inj in workload.BLOCKS]
@@ -227,6 +242,8 @@ def main():
             else:
                 blocks = [bench.Block(cfg, lvl, inj, shard, gen, dev) for lvl, inj in workload.BLOCKS]
                 modes = [mode or shard.auto_mode(l[2], l[0]) for l in cfg.levels]
+                if args.window is not None:
+                    modes = [f"window {args.window}"] * len(cfg.levels)
                 step = lambda inj_: bench.run_step(cfg, blocks, shard, inj_, w, exchange=mode)
             print(f"=== {'NATIVE executor, ' if args.native else ''}{'stand-in copies EXCLUDED, ' if args.no_copies else ''}rank {args.rank} of {args.world}, {cfg.name}: Kl={shard.Kl}, attention "
                   f"{'split+merge' if split else 'one-pass (bit-exact)'}, exchange per level {modes}", flush=True)
