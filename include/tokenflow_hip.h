@@ -456,6 +456,21 @@ TF_API int tf_window_halo_pack(const void* const* slabs, const int64_t* frame_st
                         const int* seg_f0, const int* seg_n, int Kl, int S, int D, int64_t ld, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Halo pack of an ANCHORED sliding-window bank on a frame shard (additive to ABI 11; tf_rank_pivotal_frame_sets below).
+ * tf_window_halo_pack where what peer p reads of this rank is a SET of local frames -- its window reach plus the anchor
+ * keyframes this rank owns -- instead of one range: masks is a HOST array of n_peer <= TF_MAX_WORLD 64-bit masks over the Kl
+ * local frames (Kl <= 64).  Peer p's send rows are the member frames of masks[p] in ASCENDING order, each row
+ * [slab 0 .. ns)[S][D] as there.  An empty mask contributes nothing; a frame in several masks is written to each.  The masks
+ * and the row prefix ride in the kernel arguments (64 x 8 + 65 x 4 bytes): no device table, no copy, no sync, capturable.
+ * ONE launch, a bandwidth-bound copy in 16-byte pieces; a workgroup works on ONE send row, so the peer and the n-th member of
+ * its mask are found once per workgroup, not once per piece.
+ * 16-bit elements only (TF_ERR_DTYPE otherwise); D and ld multiples of 8 elements, ns <= 6, Kl <= 64, a mask bit at or above
+ * Kl: TF_ERR_SHAPE; pointers and frame strides 16-byte aligned: TF_ERR_ALIGN.  All checked before anything touches the device.
+ * ------------------------------------------------------------------------ */
+TF_API int tf_frame_set_halo_pack(const void* const* slabs, const int64_t* frame_strides, int ns, void* send, int n_peer,
+                           const uint64_t* masks, int Kl, int S, int D, int64_t ld, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------
  * Nearest-neighbour token search  --  replaces batch_cosine_sim + chunk + argmax:
  * util.py:61-69 and tokenflow_utils.py:335-343.
  *
@@ -820,7 +835,8 @@ TF_API int tf_ext_attn_windows_edits_plan(int K, int Kq, int q_frame0, int S, in
  *   Cauchy-Schwarz score bound (head dims 40 and 64) is the maximum key norm over the MEMBER frames only, not over the span
  *   from the first to the last member (a superset would give another shift).
  *   Multi-edit batches and the four-bank form over frame sets: tf_ext_attn_fwd_frame_sets_edits, below.
- *   Not built: keyframe segments, frame shards and the run forms over frame sets.
+ *   Frame shards: tf_ext_attn_fwd_frame_sets_part and tf_rank_pivotal_frame_sets, below.
+ *   Not built: keyframe segments and the run forms over frame sets.
  *   ws: tf_ext_attn_workspace_bytes(K, ...), unchanged.
  * tf_ext_attn_frame_sets_plan: the launches of the call for dense tensors (host only), the tokens of tf_ext_attn_plan.
  * ------------------------------------------------------------------------ */
@@ -830,6 +846,32 @@ TF_API int tf_ext_attn_fwd_frame_sets(const void* q, const void* k, const void* 
 
 TF_API int tf_ext_attn_frame_sets_plan(int K, int Kq, int q_frame0, int S, int H, int Dh, int flags, int dtype,
                                 const uint64_t* sets, char* buf, size_t len);
+
+/* ------------------------------------------------------------------------
+ * The BANK PART of a frame-set pass (additive to ABI 11): what a frame-sharded rank runs over its anchor-extended receive
+ * buffer (tf_rank_pivotal_frame_sets, `FrameShard._pivotal_frame_sets`).  To tf_ext_attn_fwd_frame_sets what
+ * tf_ext_attn_fwd_windows_part is to tf_ext_attn_fwd_windows.
+ *
+ * tf_ext_attn_fwd_frame_sets_part takes the arguments of tf_ext_attn_fwd_frame_sets, but TF_ATTN_BANK_ONLY is accepted: k and v
+ * then hold only the slabs the bank branches read, with the branch offsets of tf_ext_attn_fwd_strided under that flag.  Without
+ * the flag the call IS tf_ext_attn_fwd_frame_sets.  TF_ATTN_SOURCE_ONLY is refused (TF_ERR_SHAPE): the source part of a
+ * frame-set pass is set-free -- it is tf_ext_attn_fwd_strided with TF_ATTN_SOURCE_ONLY.  tf_ext_attn_fwd_frame_sets itself
+ * keeps refusing both part flags.  K is the bank the masks index (on a shard the rank's extended bank), at most 64.
+ *   Canonical forms.  Every set a contiguous range IS tf_ext_attn_fwd_windows_part on the equivalent (lo, n) table: same
+ *   launches, same bits, same plan tokens; every set the whole bank IS tf_ext_attn_fwd_strided with the same part flag.
+ *   Identity.  The two parts together -- this call with TF_ATTN_BANK_ONLY, then the source-only strided call -- equal
+ *   tf_ext_attn_fwd_frame_sets on the same tensors BIT FOR BIT under TF_ATTN_NO_SPLIT wherever the plans name the same kernel
+ *   form, and lie within the attention bound of it everywhere.
+ *   ws: tf_ext_attn_workspace_bytes(K, ...).
+ * tf_ext_attn_frame_sets_part_plan: the launches of the call for dense tensors (host only); the bank launch's token carries
+ *   ',set' as in tf_ext_attn_frame_sets_plan (',win' where every set is a range).
+ * ------------------------------------------------------------------------ */
+TF_API int tf_ext_attn_fwd_frame_sets_part(const void* q, const void* k, const void* v, void* out, int K, int Kq, int q_frame0,
+                                    int S, int H, int Dh, int64_t ld, const int64_t* strides, float scale, int flags,
+                                    int dtype, const uint64_t* sets, void* ws, size_t ws_bytes, void* stream);
+
+TF_API int tf_ext_attn_frame_sets_part_plan(int K, int Kq, int q_frame0, int S, int H, int Dh, int flags, int dtype,
+                                     const uint64_t* sets, char* buf, size_t len);
 
 /* ------------------------------------------------------------------------
  * Frame-set bank for a MULTI-EDIT batch (additive to ABI 11): several prompts on one long video in one pass, with anchor
@@ -1178,6 +1220,47 @@ TF_API int tf_rank_pivotal_window(tf_rank* rk, const void* q, const void* k, con
                            int dtype, int mode, int slot, int radius, void* ws, size_t ws_bytes, void* stream);
 TF_API int tf_rank_pivotal_window_plan(int world, int rank, int K, int S, int H, int Dh, int radius, int mode, int flags,
                                 int dtype, char* buf, size_t len);
+
+/* ------------------------------------------------------------------------
+ * The rank executor over an ANCHORED sliding-window bank (additive to ABI 11): tf_rank_pivotal_window plus global anchor
+ * keyframes that every keyframe sees beside its window -- frame sets across GPUs.  NOT TokenFlow's result unless the radius
+ * covers the bank; opt-in.
+ *
+ * anchors: a HOST array of n_anchors GLOBAL keyframe indices, 0 <= a < K, duplicates fine (indices, not a mask: K is free).
+ * Geometry (pure arithmetic; `sharded.frame_set_halo_plan` is the same in Python).  With [lo, hi) as in the windowed call rank
+ * r reads the set U = [lo, hi) + anchors, F = |U| <= 64 frames: a set is a 64-bit mask over the rank's EXTENDED bank, so the
+ * cap K <= 64 of tf_ext_attn_fwd_frame_sets does not hold here.  Peer p sends it U & own(p), ascending: in rank order the
+ * receive buffer of ONE tf_all_to_all_rows is U in ascending order.  It sends peer p own(r) & U_p, a mask over its Kl local
+ * frames (an anchor it owns goes to every peer); its own frames travel as its self rows and are contiguous in U, from
+ * q_frame0 = the number of members of U below kf0.  Local query i gets (window of keyframe kf0 + i) + anchors as a mask over
+ * the positions in U.
+ *
+ * Schedule of ONE call (W > 1, radius < K - 1, n_anchors > 0): that of tf_rank_pivotal_window with two changes --
+ *   1. tf_frame_set_halo_pack replaces tf_window_halo_pack;
+ *   4. tf_ext_attn_fwd_frame_sets_part(TF_ATTN_BANK_ONLY) over the receive buffer [F][ns][S][D] in place, Kq = Kl, q_frame0 and
+ *      the set table above (a rank whose sets are all ranges in U's coordinates thereby issues the windowed part).
+ * The source part on the auxiliary stream (TOKENFLOW_RANK_SRC_AUX=0: in line), the join, the neighbour halo, TF_RANK_NO_HALO,
+ * TF_RANK_INV_NORM and the slots are unchanged.
+ * n_anchors = 0 IS tf_rank_pivotal_window; radius >= K - 1 IS tf_rank_pivotal(TF_RANK_BANK) whatever the anchors; one rank is
+ * tf_ext_attn_fwd_frame_sets with the table of radius and anchors (K <= 64 there).  Results: the bits of one process issuing
+ * tf_ext_attn_fwd_frame_sets_part(TF_ATTN_BANK_ONLY) and the source-only call on the full tensors under TF_ATTN_NO_SPLIT,
+ * wherever the plans name the same kernel form (the form follows the rank's largest set).
+ * Refused with TF_ERR_SHAPE before anything touches the device: what tf_rank_pivotal_window refuses, an anchor outside [0, K),
+ * more than 4096 anchors, F > 64.
+ *   ws: tf_rank_pivotal_frame_sets_workspace_bytes (never below tf_rank_pivotal_window_workspace_bytes for the same radius; 0
+ *   for arguments the call refuses).
+ * tf_rank_pivotal_frame_sets_plan (host only): the sequence, ';'-separated, recorded by the executing code itself:
+ *   inv_norm under TF_RANK_INV_NORM; set_pack[ns=N]; a2a[slabs=N,send=a/b/..,recv=a/b/..]; the tokens of the source-only
+ *   tf_ext_attn_plan; the tokens of tf_ext_attn_frame_sets_part_plan for the bank part; halo[n=5].
+ * ------------------------------------------------------------------------ */
+TF_API size_t tf_rank_pivotal_frame_sets_workspace_bytes(const tf_rank* rk, int S, int H, int Dh, int dtype, int radius,
+                                                  const int* anchors, int n_anchors);
+TF_API int tf_rank_pivotal_frame_sets(tf_rank* rk, const void* q, const void* k, const void* v, const int64_t* strides,
+                               void* piv_ext, float* inv_ext, void* kfo_ext, int S, int H, int Dh, float scale, int flags,
+                               int dtype, int mode, int slot, int radius, const int* anchors, int n_anchors, void* ws,
+                               size_t ws_bytes, void* stream);
+TF_API int tf_rank_pivotal_frame_sets_plan(int world, int rank, int K, int S, int H, int Dh, int radius, const int* anchors,
+                                    int n_anchors, int mode, int flags, int dtype, char* buf, size_t len);
 
 #ifdef __cplusplus
 }

@@ -181,6 +181,16 @@ _SIGNATURES = {
     "tf_rank_pivotal_window": (_c.c_int, [_c.c_void_p] * 8 + [_c.c_int] * 3 + [_c.c_float] + [_c.c_int] * 5 +
                                [_c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "tf_rank_pivotal_window_plan": (_c.c_int, [_c.c_int] * 10 + [_c.c_char_p, _c.c_size_t]),
+    # anchor keyframes on a windowed frame shard: frame sets across GPUs (additive to ABI 11)
+    "tf_ext_attn_fwd_frame_sets_part": (_c.c_int, [_c.c_void_p] * 4 + [_c.c_int] * 6 + [_c.c_int64, _c.c_void_p, _c.c_float,
+                                                   _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "tf_ext_attn_frame_sets_part_plan": (_c.c_int, [_c.c_int] * 8 + [_c.c_void_p, _c.c_char_p, _c.c_size_t]),
+    "tf_frame_set_halo_pack": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p] +
+                               [_c.c_int] * 3 + [_c.c_int64, _c.c_int, _c.c_void_p]),
+    "tf_rank_pivotal_frame_sets_workspace_bytes": (_c.c_size_t, [_c.c_void_p] + [_c.c_int] * 5 + [_c.c_void_p, _c.c_int]),
+    "tf_rank_pivotal_frame_sets": (_c.c_int, [_c.c_void_p] * 8 + [_c.c_int] * 3 + [_c.c_float] + [_c.c_int] * 5 +
+                                   [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "tf_rank_pivotal_frame_sets_plan": (_c.c_int, [_c.c_int] * 7 + [_c.c_void_p] + [_c.c_int] * 4 + [_c.c_char_p, _c.c_size_t]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

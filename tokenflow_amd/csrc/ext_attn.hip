@@ -1546,6 +1546,52 @@ extern "C" int tf_ext_attn_frame_sets_plan(int K, int Kq, int q_frame0, int S, i
     return rec.n;
 }
 
+// The bank part of a frame-set pass (include/tokenflow_hip.h): tf_ext_attn_fwd_frame_sets with TF_ATTN_BANK_ONLY accepted -- k and
+// v hold only the slabs the bank branches read, addressed as in tf_ext_attn_fwd_strided with that flag.  What a frame-sharded rank
+// runs over its anchor-extended receive buffer; the source part of a frame-set pass is set-free.  An entry point and its checks:
+// attn_fwd_core takes the set table beside the part flags (the multi-edit composition hands it the same pair).
+extern "C" int tf_ext_attn_fwd_frame_sets_part(const void* q, const void* k, const void* v, void* out, int K, int Kq, int q_frame0,
+                                               int S, int H, int Dh, int64_t ld, const int64_t* strides, float scale, int flags,
+                                               int dtype, const uint64_t* sets, void* ws, size_t ws_bytes, void* stream) {
+    const char* const name = "tf_ext_attn_fwd_frame_sets_part";
+    if (!(flags & TF_ATTN_BANK_ONLY))   // without the flag the call IS tf_ext_attn_fwd_frame_sets (which refuses the source flag)
+        return tf_ext_attn_fwd_frame_sets(q, k, v, out, K, Kq, q_frame0, S, H, Dh, ld, strides, scale, flags, dtype, sets, ws,
+                                          ws_bytes, stream);
+    int win_lo[TF_MAX_WINDOW_FRAMES], win_n[TF_MAX_WINDOW_FRAMES], K_max = 0;
+    bool ranges = true;
+    if (const int rc = frame_sets_check(name, K, Kq, q_frame0, sets, win_lo, win_n, &K_max, &ranges)) return rc;
+    constexpr int REFUSED = TF_ATTN_SOURCE_ONLY | TF_ATTN_FOLD_SCALE | TF_ATTN_MULTI_V | TF_ATTN_NO_MULTI_V | TF_ATTN_MULTI_V64 |
+                            TF_ATTN_RUN_MULTI_V;
+    TF_ARG(!(flags & REFUSED), TF_ERR_SHAPE,
+           "%s: flags 0x%x -- TF_ATTN_SOURCE_ONLY (the source part of a frame-set pass is tf_ext_attn_fwd_strided) / "
+           "TF_ATTN_FOLD_SCALE and the multi-edit hints have no frame-set form", name, flags & REFUSED);
+    if (ranges)   // every set a contiguous range: the windowed part (the strided call where every range is the bank)
+        return tf_ext_attn_fwd_windows_part(q, k, v, out, K, Kq, q_frame0, S, H, Dh, ld, strides, scale, flags, dtype, win_lo, win_n,
+                                            ws, ws_bytes, stream);
+    const SetPart fs{sets, K_max};
+    return attn_fwd_core(q, k, v, out, K, Kq, q_frame0, S, H, Dh, ld, strides, scale, flags, dtype, ws, ws_bytes, stream, nullptr,
+                         nullptr, nullptr, &fs);
+}
+
+// Launch plan of tf_ext_attn_fwd_frame_sets_part for dense tensors (host only): the entry point itself under the plan recorder.
+extern "C" int tf_ext_attn_frame_sets_part_plan(int K, int Kq, int q_frame0, int S, int H, int Dh, int flags, int dtype,
+                                                const uint64_t* sets, char* buf, size_t len) {
+    TF_ARG(K > 0 && S > 0 && H > 0 && Kq > 0 && Kq <= K, TF_ERR_SHAPE, "tf_ext_attn_frame_sets_part_plan: K=%d Kq=%d S=%d H=%d", K,
+           Kq, S, H);
+    void* const ph = reinterpret_cast<void*>((uintptr_t)1 << 12);
+    const int64_t ld = (int64_t)H * Dh, fs = (int64_t)S * ld;
+    const int64_t strides[9] = {Kq * fs, fs, K * fs, fs, K * fs, fs, Kq * fs, fs, ld};
+    TfPlanRec rec{buf, len, 0, 0};
+    if (buf && len) buf[0] = 0;
+    tf_plan_rec = &rec;
+    const int rc = tf_ext_attn_fwd_frame_sets_part(ph, ph, ph, ph, K, Kq, q_frame0, S, H, Dh, ld, strides, 1.0f, flags, dtype, sets,
+                                                   ph, tf_ext_attn_workspace_bytes(K, S, H, Dh, dtype), nullptr);
+    tf_plan_rec = nullptr;
+    if (rc) return rc;
+    TF_ARG(rec.used < len, TF_ERR_WORKSPACE, "tf_ext_attn_frame_sets_part_plan: the plan needs %zu bytes", rec.used + 1);
+    return rec.n;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Frame-set bank for a multi-edit batch (include/tokenflow_hip.h): the masked composition with the set table handed to every bank
 // part -- ONE pre-pass, the injecting edits (pairs in the frame-set four-bank form where it is selected, an odd one in the DUAL set

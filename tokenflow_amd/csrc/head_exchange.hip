@@ -123,6 +123,38 @@ __global__ __launch_bounds__(256) void window_halo_pack_kernel(SlabPtrs<N> sl, u
     }
 }
 
+// Halo pack of an ANCHORED windowed frame shard (tf_frame_set_halo_pack): as above, but what peer p reads of this rank is a SET
+// of local frames (its window reach plus the anchors this rank owns): a 64-bit mask per peer instead of one range.  Send row r
+// of segment s holds the (r - row0[s])-th member of mask[s] in ascending order.  Masks and prefix ride in the kernel arguments.
+struct HaloSets {
+    int n;                             // peers = ranks
+    int row0[TF_MAX_WORLD + 1];        // first send row per peer; row0[n] = rows in all
+    uint64_t mask[TF_MAX_WORLD];       // local frames per peer
+};
+
+// One workgroup column (blockIdx.x) = ONE send row: the peer scan and the n-th set bit are a function of blockIdx.x alone
+// (wave-uniform, scalar registers, done once); the workgroups blockIdx.y .. of the row stride over its 16-byte pieces.
+template <int N>
+__global__ __launch_bounds__(256) void frame_set_halo_pack_kernel(SlabPtrs<N> sl, unsigned char* __restrict__ send, HaloSets sg,
+                                                                  int ns, int S, int d_pieces, int64_t ld_bytes) {
+    const int r = (int)blockIdx.x;
+    int seg = 0;
+    while (seg + 1 < sg.n && r >= sg.row0[seg + 1]) ++seg;
+    uint64_t m = sg.mask[seg];
+    for (int j = r - sg.row0[seg]; j > 0; --j) m &= m - 1;   // drop the j lowest members
+    const int f = __builtin_ctzll(m);
+    const int per_slab = S * d_pieces;
+    const int64_t per_row = (int64_t)ns * per_slab;
+    unsigned char* dst = send + (int64_t)r * per_row * 16;
+    for (int64_t g = (int64_t)blockIdx.y * 256 + threadIdx.x; g < per_row; g += (int64_t)gridDim.y * 256) {
+        const int i = (int)(g / per_slab);
+        const int t = (int)(g - (int64_t)i * per_slab);
+        const int s = t / d_pieces, pc = t - s * d_pieces;
+        const unsigned char* src = sl.src[i] + f * sl.fs[i] + (int64_t)s * ld_bytes + (int64_t)pc * 16;
+        st16(dst + g * 16, ld16(src));
+    }
+}
+
 int check(const char* name, const void* const* slabs, const int64_t* fs, int n, const void* buf, int W, int Kl, int S,
           int hd, int64_t ld, int elem_bytes) {
     TF_ARG(slabs && fs && buf, TF_ERR_NULL, "%s: null pointer", name);
@@ -263,5 +295,46 @@ extern "C" int tf_window_halo_pack(const void* const* slabs, const int64_t* fram
                        reinterpret_cast<hipStream_t>(stream), slab_ptrs<MAX_SLABS_1>(slabs, frame_strides, ns, 2),
                        static_cast<unsigned char*>(send), sg, ns, S, d_pieces, ld * 2);
     TF_LAUNCH_CHECK("tf_window_halo_pack");
+    return 0;
+}
+
+// The same packing where what a peer reads is a SET of local frames (include/tokenflow_hip.h): an anchored windowed frame shard.
+extern "C" int tf_frame_set_halo_pack(const void* const* slabs, const int64_t* frame_strides, int ns, void* send, int n_peer,
+                                      const uint64_t* masks, int Kl, int S, int D, int64_t ld, int dtype, void* stream) {
+    const char* const name = "tf_frame_set_halo_pack";
+    TF_ARG(slabs && frame_strides && send && masks, TF_ERR_NULL, "%s: null pointer", name);
+    TF_ARG(dtype == TF_BF16 || dtype == TF_F16, TF_ERR_DTYPE, "%s: dtype %d (bf16/f16 only)", name, dtype);
+    TF_ARG(ns >= 1 && ns <= MAX_SLABS_1 && n_peer >= 1 && n_peer <= TF_MAX_WORLD && Kl >= 1 && Kl <= 64 && S >= 1 && D >= 8 &&
+               D % 8 == 0 && ld >= D && ld % 8 == 0 && (int64_t)S * (D / 8) < ((int64_t)1 << 30),
+           TF_ERR_SHAPE, "%s: ns=%d peers=%d Kl=%d S=%d D=%d ld=%lld (D and ld multiples of 8 elements, ld >= D, at most %d "
+           "slabs, %d peers and 64 local frames)", name, ns, n_peer, Kl, S, D, (long long)ld, MAX_SLABS_1, TF_MAX_WORLD);
+    HaloSets sg{};
+    sg.n = n_peer;
+    int rows = 0;
+    for (int p = 0; p < n_peer; ++p) {
+        TF_ARG(Kl == 64 || !(masks[p] >> Kl), TF_ERR_SHAPE, "%s: mask %d = 0x%llx has bits at or above the %d local keyframes", name,
+               p, (unsigned long long)masks[p], Kl);
+        sg.row0[p] = rows, sg.mask[p] = masks[p];
+        rows += __builtin_popcountll(masks[p]);
+    }
+    sg.row0[n_peer] = rows;
+    TF_ARG(tf_aligned16(send), TF_ERR_ALIGN, "%s: send buffer not 16-byte aligned", name);
+    for (int i = 0; i < ns; ++i) {
+        TF_ARG(slabs[i], TF_ERR_NULL, "%s: slab %d is null", name, i);
+        TF_ARG(tf_aligned16(slabs[i]) && (frame_strides[i] * 2) % 16 == 0, TF_ERR_ALIGN, "%s: slab %d not 16-byte aligned", name, i);
+        // (a frame holds S token rows: the last byte read is inside the slab's Kl frames)
+        TF_ARG(frame_strides[i] >= (int64_t)(S - 1) * ld + D || Kl == 1, TF_ERR_SHAPE, "%s: slab %d: frame stride %lld below a frame",
+               name, i, (long long)frame_strides[i]);
+    }
+    if (rows == 0) return 0;   // nobody reads this rank's frames and it sends none to itself: nothing to launch
+    const int d_pieces = D * 2 / 16;
+    const int64_t per_row = (int64_t)ns * S * d_pieces;
+    // about 2048 workgroups in all (256 CUs x 8 resident), at least one and at most a row's worth per send row (rows <= 4096)
+    int64_t ny = (2048 + rows - 1) / rows;
+    if (ny > (per_row + 255) / 256) ny = (per_row + 255) / 256;
+    hipLaunchKernelGGL(frame_set_halo_pack_kernel<MAX_SLABS_1>, dim3((unsigned)rows, (unsigned)ny), dim3(256), 0,
+                       reinterpret_cast<hipStream_t>(stream), slab_ptrs<MAX_SLABS_1>(slabs, frame_strides, ns, 2),
+                       static_cast<unsigned char*>(send), sg, ns, S, d_pieces, ld * 2);
+    TF_LAUNCH_CHECK("tf_frame_set_halo_pack");
     return 0;
 }

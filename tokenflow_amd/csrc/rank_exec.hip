@@ -744,6 +744,258 @@ extern "C" int tf_rank_pivotal_window_plan(int world, int rank, int K, int S, in
     return rec.n;
 }
 
+// ---------------------------------------------------------------------------------------------
+// One rank's pivotal pass over an ANCHORED sliding-window bank (include/tokenflow_hip.h): tf_rank_pivotal_window plus global
+// anchor keyframes that every keyframe sees.  What `sharded.frame_set_halo_plan` computes in Python: rank r reads the set
+// U = [lo, hi) + anchors (ascending, F frames, at most 64: a set is a mask over the EXTENDED bank, so K itself is free); peer p
+// sends it U & own(p), it sends peer p own(r) & U_p -- a mask of local frames; its own frames travel as its self rows and are
+// contiguous in U at q_frame0 = the members of U below kf0.  Local query i gets (window of kf0 + i) + anchors as a mask over
+// the positions in U.
+namespace {
+
+struct SetGeom {
+    WinGeom w;   // lo / hi / F, the row counts and send_total of the exchange (the window table is not used)
+    int q_frame0;
+    uint64_t send_mask[TF_MAX_WORLD];             // per peer: the LOCAL frames it reads
+    uint64_t sets[TF_MAX_WINDOW_FRAMES];          // per local query: its members, positions in U
+};
+
+// anchors: sorted, unique, inside [0, K); Kl <= 64 (the caller's checks).  Returns false where U holds more than 64 frames.
+bool frame_set_geometry(const tf_rank* rk, int R, const int* anc, int na, SetGeom* out) {
+    SetGeom& g = *out;
+    g = SetGeom{};
+    const int K = rk->K, Kl = rk->Kl, kf0 = rk->kf0;
+    const int64_t Rl = R;
+    auto reach_lo = [&](int f0) { return (int)(f0 - Rl > 0 ? f0 - Rl : 0); };
+    auto reach_hi = [&](int f1) { return (int)(f1 + Rl < K ? f1 + Rl : K); };
+    auto is_anchor = [&](int f) {
+        int a = 0, b = na;
+        while (a < b) {
+            const int m = (a + b) / 2;
+            if (anc[m] < f) a = m + 1; else b = m;
+        }
+        return a < na && anc[a] == f;
+    };
+    const int lo = reach_lo(kf0), hi = reach_hi(kf0 + Kl);
+    int nlow = 0, nhigh = 0;
+    for (int j = 0; j < na; ++j) nlow += anc[j] < lo, nhigh += anc[j] >= hi;
+    g.w.lo = lo, g.w.hi = hi, g.w.hl = kf0 - lo, g.w.hr = hi - kf0 - Kl;
+    const int64_t F = (int64_t)nlow + (hi - lo) + nhigh;
+    if (F > 64) return false;
+    g.w.F = (int)F;
+    g.q_frame0 = nlow + (kf0 - lo);
+    int off = 0;
+    for (int p = 0; p < rk->world; ++p) {
+        const int p0 = off, p1 = off + rk->counts[p];
+        off = p1;
+        // what arrives from p: own(p) & U
+        const int a = imax(p0, lo), b = imin(p1, hi);
+        int n = b > a ? b - a : 0;
+        for (int j = 0; j < na; ++j) n += anc[j] >= p0 && anc[j] < p1 && (anc[j] < lo || anc[j] >= hi);
+        g.w.recv_rows[p] = n;
+        // what goes to p: own(r) & U_p
+        const int lo_p = reach_lo(p0), hi_p = reach_hi(p1);
+        uint64_t m = 0;
+        for (int i = 0; i < Kl; ++i) {
+            const int f = kf0 + i;
+            if ((f >= lo_p && f < hi_p) || is_anchor(f)) m |= (uint64_t)1 << i;
+        }
+        g.send_mask[p] = m;
+        g.w.send_rows[p] = __builtin_popcountll(m);
+        g.w.send_total += g.w.send_rows[p];
+    }
+    // the anchors as positions in U: those outside [lo, hi) fill the two ends, those inside sit at their offset
+    uint64_t am = 0;
+    for (int j = 0, below = 0, above = 0; j < na; ++j) {
+        const int a = anc[j];
+        const int pos = a < lo ? below++ : a >= hi ? nlow + (hi - lo) + above++ : nlow + (a - lo);
+        am |= (uint64_t)1 << pos;
+    }
+    for (int i = 0; i < Kl; ++i) {
+        const int64_t gi = kf0 + i;
+        const int w0 = (int)(gi - Rl > 0 ? gi - Rl : 0), w1 = (int)(gi + Rl < K - 1 ? gi + Rl : K - 1);
+        const int n = w1 - w0 + 1;
+        g.sets[i] = ((n == 64 ? ~(uint64_t)0 : ((uint64_t)1 << n) - 1) << (nlow + (w0 - lo))) | am;
+    }
+    return true;
+}
+
+// the anchors of a call validated, sorted and without duplicates (n_out <= n): a bad index is TF_ERR_SHAPE
+int sorted_anchors(const char* fn, int K, const int* anchors, int n, int* out, int* n_out) {
+    for (int j = 0; j < n; ++j) {
+        TF_ARG(anchors[j] >= 0 && anchors[j] < K, TF_ERR_SHAPE, "%s: anchor %d outside the %d keyframes", fn, anchors[j], K);
+        int i = j;   // insertion sort: a handful of anchors
+        for (; i > 0 && out[i - 1] > anchors[j]; --i) out[i] = out[i - 1];
+        out[i] = anchors[j];
+    }
+    int m = 0;
+    for (int j = 0; j < n; ++j)
+        if (!m || out[m - 1] != out[j]) out[m++] = out[j];
+    *n_out = m;
+    return 0;
+}
+
+constexpr int MAX_ANCHORS = 4096;   // of one call (duplicates included); at most 64 distinct ones can lie in a rank's bank anyway
+
+int do_set_pack(const void* const* slabs, const int64_t* fss, int ns, void* send, const tf_rank* rk, const SetGeom& g, int S,
+                int D, int64_t ld, int dtype, void* stream) {
+    if (tf_plan_note("set_pack[ns=%d]", ns)) return 0;
+    return tf_frame_set_halo_pack(slabs, fss, ns, send, rk->world, g.send_mask, rk->Kl, S, D, ld, dtype, stream);
+}
+
+}  // namespace
+
+extern "C" size_t tf_rank_pivotal_frame_sets_workspace_bytes(const tf_rank* rk, int S, int H, int Dh, int dtype, int radius,
+                                                             const int* anchors, int n_anchors) {
+    const size_t win = tf_rank_pivotal_window_workspace_bytes(rk, S, H, Dh, dtype, radius);   // (0 for what that call refuses)
+    if (n_anchors == 0 || !win) return win;   // no anchors IS the windowed call
+    if (n_anchors < 0 || n_anchors > MAX_ANCHORS || !anchors) return 0;
+    if (rk->world == 1 || radius >= rk->K - 1 || rk->Kl > TF_MAX_WINDOW_FRAMES) return win;
+    int anc[MAX_ANCHORS], na = 0;
+    for (int j = 0; j < n_anchors; ++j)
+        if (anchors[j] < 0 || anchors[j] >= rk->K) return 0;
+    sorted_anchors("", rk->K, anchors, n_anchors, anc, &na);
+    SetGeom G;
+    if (!frame_set_geometry(rk, radius, anc, na, &G)) return 0;
+    const size_t set = window_layout(rk, G.w, S, H, Dh, dtype).total;
+    return set > win ? set : win;   // never below the windowed call's for the same radius
+}
+
+extern "C" int tf_rank_pivotal_frame_sets(tf_rank* rk, const void* q, const void* k, const void* v, const int64_t* st_in,
+                                          void* piv_ext, float* inv_ext, void* kfo_ext, int S, int H, int Dh, float scale,
+                                          int flags, int dtype, int mode, int slot, int radius, const int* anchors,
+                                          int n_anchors, void* ws, size_t ws_bytes, void* stream) {
+    const char* const fn = "tf_rank_pivotal_frame_sets";
+    const bool no_halo = (mode & TF_RANK_NO_HALO) != 0, want_inv = (mode & TF_RANK_INV_NORM) != 0;
+    const int mods = mode & (TF_RANK_NO_HALO | TF_RANK_INV_NORM), base = mode & ~(TF_RANK_NO_HALO | TF_RANK_INV_NORM);
+    // ---- arguments first: nothing below this block's end has touched the device
+    TF_ARG(rk && q && k && v && st_in && kfo_ext && ws && (no_halo || (piv_ext && inv_ext)) && (anchors || n_anchors == 0),
+           TF_ERR_NULL, "%s: null pointer", fn);
+    TF_ARG(n_anchors >= 0 && n_anchors <= MAX_ANCHORS, TF_ERR_SHAPE, "%s: %d anchors (0 .. %d)", fn, n_anchors, MAX_ANCHORS);
+    if (n_anchors == 0)   // no anchors: the windowed pass -- the same launches, the same bits, the same plan tokens
+        return tf_rank_pivotal_window(rk, q, k, v, st_in, piv_ext, inv_ext, kfo_ext, S, H, Dh, scale, flags, dtype, mode, slot,
+                                      radius, ws, ws_bytes, stream);
+    TF_ARG(dtype == TF_BF16 || dtype == TF_F16, TF_ERR_DTYPE, "%s: dtype %d (bf16/f16 only)", fn, dtype);
+    TF_ARG(radius >= 0, TF_ERR_SHAPE, "%s: radius %d (>= 0)", fn, radius);
+    TF_ARG(base == 0 || base == TF_RANK_BANK, TF_ERR_SHAPE,
+           "%s: mode %d (the anchored pass has the bank form only: TF_RANK_BANK with TF_RANK_NO_HALO / TF_RANK_INV_NORM)", fn, base);
+    TF_ARG(slot >= 0 && slot < TF_RANK_SLOTS, TF_ERR_SHAPE, "%s: slot %d outside [0, %d)", fn, slot, TF_RANK_SLOTS);
+    TF_ARG(!(want_inv && no_halo), TF_ERR_SHAPE, "%s: TF_RANK_INV_NORM needs the propagation state (no TF_RANK_NO_HALO)", fn);
+    TF_ARG(!(flags & (TF_ATTN_BANK_ONLY | TF_ATTN_SOURCE_ONLY)), TF_ERR_SHAPE, "%s: the part flags are the executor's own", fn);
+    int anc[MAX_ANCHORS], na = 0;
+    if (const int rc = sorted_anchors(fn, rk->K, anchors, n_anchors, anc, &na)) return rc;
+    if (radius >= rk->K - 1)   // every window is the whole bank: today's pass whatever the anchors
+        return tf_rank_pivotal(rk, q, k, v, st_in, piv_ext, inv_ext, kfo_ext, S, H, Dh, scale, flags, dtype, TF_RANK_BANK | mods,
+                               slot, ws, ws_bytes, stream);
+    TF_ARG(rk->Kl <= TF_MAX_WINDOW_FRAMES, TF_ERR_SHAPE, "%s: %d local keyframes (at most %d carry a set)", fn, rk->Kl,
+           TF_MAX_WINDOW_FRAMES);
+    TF_ARG(!(flags & TF_ATTN_FOLD_SCALE), TF_ERR_SHAPE, "%s: TF_ATTN_FOLD_SCALE has no frame-set form", fn);
+    SetGeom G;
+    TF_ARG(frame_set_geometry(rk, radius, anc, na, &G), TF_ERR_SHAPE,
+           "%s: window reach plus anchors exceed 64 frames on rank %d (a set is a 64-bit mask over the rank's extended bank)", fn,
+           rk->rank);
+    const size_t ws_need = tf_rank_pivotal_frame_sets_workspace_bytes(rk, S, H, Dh, dtype, radius, anchors, n_anchors);
+    TF_ARG(ws_bytes >= ws_need, TF_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", fn, ws_bytes, ws_need);
+
+    const int W = rk->world, Kl = rk->Kl, K = rk->K, o = (W > 1 && !no_halo) ? 1 : 0;
+    const int64_t D = (int64_t)H * Dh, SD = (int64_t)S * D;
+    const int64_t q_bs = st_in[0], q_fs = st_in[1], k_bs = st_in[2], k_fs = st_in[3], v_bs = st_in[4], v_fs = st_in[5],
+                  ld_q = st_in[6], ld = st_in[7];
+    typedef unsigned short E;   // any 16-bit element: only pointer arithmetic happens here
+    const E* ke = static_cast<const E*>(k);
+    const E* ve = static_cast<const E*>(v);
+    E* kfo = static_cast<E*>(kfo_ext);
+    E* piv = static_cast<E*>(piv_ext);
+    unsigned char* wsb = static_cast<unsigned char*>(ws);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int64_t o_bs = (int64_t)(Kl + o) * SD;   // branch stride of the halo-extended attention output
+    E* out_loc = kfo + (int64_t)o * SD;            // its local slots
+    const int inject = flags & TF_ATTN_INJECT;
+    if (!no_halo) rk->halo_set[slot] = false;
+    if (want_inv)   // (a launch of its own: the pack kernel carries no inverse norms)
+        if (const int rc = do_inv_norm(piv + (int64_t)o * SD, inv_ext + (int64_t)o * S, (int64_t)Kl * S, (int)D, dtype, stream))
+            return rc;
+    if (W == 1) {   // one rank: U is the whole bank, the single-GPU frame-set call straight into kfo_ext (K <= 64 there)
+        const int64_t strides[9] = {q_bs, q_fs, k_bs, k_fs, v_bs, v_fs, o_bs, SD, ld_q};
+        return tf_ext_attn_fwd_frame_sets(q, k, v, out_loc, K, K, 0, S, H, Dh, ld, strides, scale, flags, dtype, G.sets, ws, ws_bytes,
+                                          stream);
+    }
+    const WinLayout L = window_layout(rk, G.w, S, H, Dh, dtype);
+    E* send = reinterpret_cast<E*>(wsb + L.send);
+    E* recv = reinterpret_cast<E*>(wsb + L.recv);
+    // 1. pack only what PEERS read: [k1, k2, v1, v2], under injection [k0, v1, v2]; per peer the members of its mask in ascending
+    //    order (an anchor this rank owns goes to every peer), the rank's own frames to its self rows
+    const void* slabs[4];
+    int64_t fss[4];
+    int ns;
+    if (inject) {
+        ns = 3;
+        slabs[0] = ke, slabs[1] = ve + v_bs, slabs[2] = ve + 2 * v_bs;
+        fss[0] = k_fs, fss[1] = fss[2] = v_fs;
+    } else {
+        ns = 4;
+        slabs[0] = ke + k_bs, slabs[1] = ke + 2 * k_bs, slabs[2] = ve + v_bs, slabs[3] = ve + 2 * v_bs;
+        fss[0] = fss[1] = k_fs, fss[2] = fss[3] = v_fs;
+    }
+    if (const int rc = do_set_pack(slabs, fss, ns, send, rk, G, S, (int)D, ld, dtype, stream)) return rc;
+    // 2. the source part of the local frames (set-free), as in the windowed call
+    const int64_t src_strides[9] = {q_bs, q_fs, k_bs, k_fs, v_bs, v_fs, o_bs, SD, ld_q};
+    auto source_part = [&](hipStream_t on) {
+        return tf_ext_attn_fwd_strided(q, k, v, out_loc, Kl, Kl, 0, S, H, Dh, ld, src_strides, scale, flags | TF_ATTN_SOURCE_ONLY,
+                                       dtype, wsb + L.ws_src, L.ws_src_bytes, on);
+    };
+    const bool fork = src_aux_enabled() && !tf_plan_rec;
+    if (fork) {
+        if (const int rc = order(rk, st, rk->as, fn)) return rc;
+        if (const int rc = source_part(rk->as)) return rc;
+    }
+    // 3. the sparse exchange on the caller's stream: the receive buffer is U in ascending order
+    if (const int rc = do_a2a_rows(rk, send, recv, G.w, ns, SD, dtype, st)) return rc;
+    if (!fork)
+        if (const int rc = source_part(st)) return rc;
+    // 4. the frame-set bank part over the receive buffer [F][ns][S][D] in place (a table of ranges: the windowed part)
+    auto shifted = [](const E* b, int64_t elems) {
+        return reinterpret_cast<const E*>(reinterpret_cast<uintptr_t>(b) + (uintptr_t)(elems * (int64_t)sizeof(E)));
+    };
+    const int64_t fs_r = ns * SD;
+    const E* kb = inject ? recv : shifted(recv, -SD);   // [k0 | ...] or [k1, k2 | ...]
+    const E* vb = inject ? recv : shifted(recv, SD);    // [k0, v1, v2] or [k1, k2, v1, v2]
+    const int64_t strides[9] = {q_bs, q_fs, SD, fs_r, SD, fs_r, o_bs, SD, ld_q};
+    if (const int rc = tf_ext_attn_fwd_frame_sets_part(q, kb, vb, out_loc, G.w.F, Kl, G.q_frame0, S, H, Dh, D, strides, scale,
+                                                       flags | TF_ATTN_BANK_ONLY, dtype, G.sets, wsb + L.ws_bank, L.ws_bank_bytes,
+                                                       stream))
+        return rc;
+    // 5. join
+    if (fork)
+        if (const int rc = order(rk, rk->as, st, fn)) return rc;
+    // 6. the neighbour halo for the propagation, as in every mode
+    if (!no_halo)
+        if (const int rc = halo_exchange(rk, piv, inv_ext, kfo, 3, o_bs, SD, S, slot, st, fn)) return rc;
+    return 0;
+}
+
+// The sequence one anchored call issues, recorded by the call itself on a rank that owns no device object (host only).
+extern "C" int tf_rank_pivotal_frame_sets_plan(int world, int rank, int K, int S, int H, int Dh, int radius, const int* anchors,
+                                               int n_anchors, int mode, int flags, int dtype, char* buf, size_t len) {
+    TF_ARG(world >= 1 && world <= TF_MAX_WORLD && rank >= 0 && rank < world && K >= world && S > 0 && H > 0 && Dh > 0,
+           TF_ERR_SHAPE, "tf_rank_pivotal_frame_sets_plan: rank %d of %d over %d keyframes, S=%d H=%d Dh=%d", rank, world, K, S, H,
+           Dh);
+    tf_rank rk{};
+    partition(&rk, K, world, rank);
+    void* const ph = reinterpret_cast<void*>((uintptr_t)1 << 40);   // never dereferenced
+    const int64_t D = (int64_t)H * Dh, SD = (int64_t)S * D;
+    const int64_t strides[8] = {rk.Kl * SD, SD, rk.Kl * SD, SD, rk.Kl * SD, SD, D, D};
+    TfPlanRec rec{buf, len, 0, 0};
+    if (buf && len) buf[0] = 0;
+    tf_plan_rec = &rec;
+    const int rc = tf_rank_pivotal_frame_sets(&rk, ph, ph, ph, strides, ph, static_cast<float*>(ph), ph, S, H, Dh, 1.0f, flags,
+                                              dtype, mode, 0, radius, anchors, n_anchors, ph, (size_t)-1, nullptr);
+    tf_plan_rec = nullptr;
+    if (rc) return rc;
+    TF_ARG(rec.used < len, TF_ERR_WORKSPACE, "tf_rank_pivotal_frame_sets_plan: the plan needs %zu bytes", rec.used + 1);
+    return rec.n;
+}
+
 extern "C" int tf_rank_halo_wait(tf_rank* rk, int slot, void* stream) {
     TF_ARG(rk, TF_ERR_NULL, "tf_rank_halo_wait: null pointer");
     TF_ARG(slot >= 0 && slot < TF_RANK_SLOTS, TF_ERR_SHAPE, "tf_rank_halo_wait: slot %d outside [0, %d)", slot,

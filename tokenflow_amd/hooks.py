@@ -249,7 +249,7 @@ def _segments(module, K=None):
     return segs
 
 
-def register_bank_window(model, radius, edits=False, anchors=None, anchor_edits=False, shard=False):
+def register_bank_window(model, radius, edits=False, anchors=None, anchor_edits=False, shard=False, anchor_shard=False):
     """Sliding-window keyframe bank (no counterpart in the reference, where every keyframe attends to the whole bank): in the
     pivotal passes that follow, the uncond / cond branches of keyframe i attend to the keyframes i - radius .. i + radius only
     (clamped to the bank; `ops.bank_windows`), the source branch to its own frame as always.  Consistency stays chained along
@@ -283,7 +283,13 @@ def register_bank_window(model, radius, edits=False, anchors=None, anchor_edits=
     `radius` of its own run and computes the windowed attention of its keyframes, the result of the unsharded windowed pass.
     A radius that covers the shard's bank issues today's sharded pass.  On a windowed shard anchors, several segments and
     n_edits > 1 are a ValueError at the pass; a shard type without `window=` raises the frame-shard error above.  Without
-    the keyword every refusal stays as it was."""
+    the keyword every refusal stays as it was.
+    anchor_shard=True (beside shard=True and anchors=...) opens the anchors on a windowed frame shard: where the shard's type
+    reports `supports_window_anchors`, the installers call `shard.pivotal_attention(..., window=radius, anchors=resolved)` --
+    every rank fetches the keyframes within `radius` of its own run plus the anchors, at most 64 frames in all, so the cap
+    K <= 64 of the single-GPU frame-set call does not hold there.  The anchors resolve against the shard's WHOLE bank: an int
+    stride m gives range(0, shard.K, m), an index >= shard.K is a ValueError at the pass.  Without the keyword anchors on a
+    windowed shard stay the ValueError they were."""
     if radius is not None:
         radius = int(radius)
         if radius < 0:
@@ -303,10 +309,10 @@ def register_bank_window(model, radius, edits=False, anchors=None, anchor_edits=
         anchors = tuple(int(a) for a in anchors) or None
     _set_bank_window(_hook_blocks(model.unet), radius, bool(edits) and radius is not None,
                      anchors if radius is not None else None, bool(anchor_edits) and radius is not None,
-                     bool(shard) and radius is not None)
+                     bool(shard) and radius is not None, bool(anchor_shard) and radius is not None)
 
 
-def _set_bank_window(blocks, radius, edits=False, anchors=None, anchor_edits=False, shard=False):
+def _set_bank_window(blocks, radius, edits=False, anchors=None, anchor_edits=False, shard=False, anchor_shard=False):
     """`bank_window` (`bank_window_edits`, the multi-edit opt-in, `bank_window_anchors`: a tuple of keyframe indices, an
     int stride or None, and `bank_window_anchor_edits`, the opt-in of anchors in a multi-edit batch) on transformer blocks
     and their `attn1` (register_bank_window; tools on a bare block list)."""
@@ -317,6 +323,7 @@ def _set_bank_window(blocks, radius, edits=False, anchors=None, anchor_edits=Fal
             setattr(m, "bank_window_anchor_edits", anchor_edits)
             setattr(m, "bank_window_anchors", anchors)
             setattr(m, "bank_window_shard", shard)      # the opt-in of a window on a registered frame shard
+            setattr(m, "bank_window_anchor_shard", anchor_shard)      # ... and of anchors beside it
 
 
 def _bank_window(module, K: int):
@@ -337,7 +344,8 @@ def _bank_window(module, K: int):
         if int(getattr(module, "n_edits", 1)) > 1:
             raise ValueError("register_bank_window: a sliding-window bank on a registered frame shard runs one edit "
                              "(register_edits, n_edits > 1 is not supported there)")
-        if getattr(module, "bank_window_anchors", None) is not None:
+        if getattr(module, "bank_window_anchors", None) is not None and not (
+                getattr(module, "bank_window_anchor_shard", False) and getattr(shard, "supports_window_anchors", False)):
             raise ValueError("register_bank_window: anchor keyframes on a registered frame shard are not supported (every "
                              "rank would have to hold the anchors)")
         if getattr(module, "keyframe_segments", None) is not None:
@@ -365,6 +373,15 @@ def _bank_anchors(module, K: int):
     if int(getattr(module, "n_edits", 1)) > 1 and not getattr(module, "bank_window_anchor_edits", False):
         raise ValueError("register_bank_window: anchor keyframes in a multi-edit batch (register_edits, n_edits > 1) are "
                          "opt-in: register_bank_window(model, radius, edits=True, anchors=..., anchor_edits=True)")
+    shard = _active_shard(module)
+    if shard is not None:      # (register_bank_window(..., anchor_shard=True)): K is the rank's local count; the anchors are global
+        K_all = int(shard.K)
+        if isinstance(anchors, int):
+            return tuple(range(0, K_all, anchors))
+        if max(anchors) >= K_all:
+            raise ValueError(f"register_bank_window: anchors={list(anchors)} on a frame shard of {K_all} keyframes "
+                             f"(indices < {K_all})")
+        return anchors
     if isinstance(anchors, int):
         return tuple(range(0, K, anchors))
     if max(anchors) >= K:
@@ -617,7 +634,10 @@ def _make_sa_forward(self, pnp: bool):
                 _need_edit_shard(shard)
                 out = shard.pivotal_attention(q, k, v, self.heads, self.scale, False, n_edits=E, inject_mask=mask)
             elif radius is not None:   # register_bank_window(..., shard=True): the rank's keyframes against their windows
-                out = shard.pivotal_attention(q, k, v, self.heads, self.scale, inject, window=radius)
+                if anchors is not None:   # ... plus the global anchors (anchor_shard=True)
+                    out = shard.pivotal_attention(q, k, v, self.heads, self.scale, inject, window=radius, anchors=anchors)
+                else:
+                    out = shard.pivotal_attention(q, k, v, self.heads, self.scale, inject, window=radius)
             else:
                 out = shard.pivotal_attention(q, k, v, self.heads, self.scale, inject)
         elif anchors is not None and E > 1:   # ... several prompts with anchors: every edit's bank branches read the frame sets

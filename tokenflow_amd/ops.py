@@ -322,6 +322,22 @@ def attn_frame_sets_plan(K: int, sets, S: int, heads: int, dh: int, inject: bool
                         _DT[dtype], ctypes.cast(tab, ctypes.c_void_p))
 
 
+def attn_frame_sets_part_plan(K: int, Kq: int, q_frame0: int, sets, S: int, heads: int, dh: int, inject: bool,
+                              dtype: torch.dtype = torch.bfloat16, part: str = "bank", out_dtype: Optional[torch.dtype] = None,
+                              no_split: Optional[bool] = None, fused: Optional[bool] = None, hints: int = 0) -> list:
+    """The launches `ext_attn_frame_sets_views` makes for dense tensors, as tokens (tf_ext_attn_frame_sets_part_plan): Kq query
+    frames from bank frame q_frame0 on, one set each, over a bank of K <= 64 frames (on a shard the rank's extended bank); part
+    "bank" (TF_ATTN_BANK_ONLY: what a frame-sharded rank runs over its anchor-extended bank) or "all" (= `attn_frame_sets_plan`
+    for Kq = K).  The bank launch's token carries ',set' (',win' where every set is a range: `attn_windows_part_plan`).  The
+    source part of a frame-set pass is set-free: `attn_plan(Kq, Kq, ..., part="source")`.  Host only: needs no GPU."""
+    if part not in ("bank", "all"):
+        raise ValueError(f"attn_frame_sets_part_plan: part {part!r} (\"bank\" or \"all\": the source part is set-free)")
+    tab = _frame_sets("attn_frame_sets_part_plan", sets, K, Kq, int(q_frame0))
+    flags = _attn_flags(inject, part, out_dtype == torch.float32, False, no_split, fused, hints)
+    return _plan_tokens("tf_ext_attn_frame_sets_part_plan", _lib.load().tf_ext_attn_frame_sets_part_plan, K, Kq, int(q_frame0), S,
+                        heads, dh, flags, _DT[dtype], ctypes.cast(tab, ctypes.c_void_p))
+
+
 def attn_frame_sets_edits_plan(K: int, sets, S: int, heads: int, dh: int, n_edits: int, inject_mask: int,
                                dtype: torch.dtype = torch.bfloat16, out_dtype: Optional[torch.dtype] = None,
                                no_split: Optional[bool] = None, fused: Optional[bool] = None, multi_v: Optional[bool] = None,
@@ -847,6 +863,48 @@ def ext_attn_windows_views(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, ou
     return out
 
 
+def ext_attn_frame_sets_views(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, heads: int, scale: float,
+                              inject: bool, sets, part: str = "bank", branch0=(0, 0, 0, 0), q_frame0: int = 0,
+                              no_split: Optional[bool] = None, stream: Optional[int] = None, fused: Optional[bool] = None,
+                              hints: int = 0) -> torch.Tensor:
+    """`ext_attn_frame_sets` on strided 4-D views [branches, frames, S, D] (tf_ext_attn_fwd_frame_sets_part), shaped like
+    `ext_attn_windows_views`: the Kq = q.shape[1] query frames are the bank frames q_frame0 .. of k / v, `sets` holds one int
+    mask per QUERY frame over the K = k.shape[1] <= 64 bank frames.  part "bank": only the uncond / cond branches, k and v hold
+    only the slabs those read -- what a frame-sharded rank runs over its anchor-extended receive buffer; part "all": the whole
+    frame-set call.  The source part of a frame-set pass is set-free: `ext_attn_views(..., part="source")`.  Both parts together
+    equal `ext_attn_frame_sets` bit for bit under no_split wherever the plans name the same kernel form; sets that are all
+    ranges are `ext_attn_windows_views`."""
+    if part not in ("bank", "all"):
+        raise ValueError(f"ext_attn_frame_sets_views: part {part!r} (\"bank\" or \"all\": the source part is set-free)")
+    dev = _need_gpu(q, k, v, out)
+    lib = _lib.load()
+    S, D = k.shape[2], k.shape[3]
+    K, Kq, dh = k.shape[1], q.shape[1], D // heads
+    dt = _DT.get(q.dtype)
+    if dt is None or dt == _lib.TF_F32 or k.dtype != q.dtype or v.dtype != q.dtype or D % heads:
+        raise TypeError("ext_attn_frame_sets_views: q/k/v must share dtype bf16 or f16")
+    tab = _frame_sets("ext_attn_frame_sets_views", sets, K, Kq, int(q_frame0))
+    qp, q_bs, q_fs, ld_q = _view_base(q, branch0[0], S, "q")
+    kp, k_bs, k_fs, ld = _view_base(k, branch0[1], S, "k")
+    vp, v_bs, v_fs, ld_v = _view_base(v, branch0[2], S, "v")
+    op, o_bs, o_fs, ld_o = _view_base(out, branch0[3], S, "out")
+    if ld_v != ld or ld_o != D or out.shape[1] != Kq or v.shape[1] != K:
+        raise ValueError("ext_attn_frame_sets_views: k and v need one token stride, out a dense one; frames of v = frames of k")
+    if out.dtype not in (q.dtype, torch.float32):
+        raise TypeError("ext_attn_frame_sets_views: out dtype")
+    flags = _attn_flags(inject, part, out.dtype == torch.float32, False, no_split, fused, hints)
+    key = (K, S, heads, dh, dt)
+    nbytes = _attn_ws_bytes.get(key)
+    if nbytes is None:
+        nbytes = _attn_ws_bytes[key] = lib.tf_ext_attn_workspace_bytes(K, S, heads, dh, dt)
+    ws = _workspace(nbytes, q.device, stream=stream)
+    strides = (ctypes.c_int64 * 9)(q_bs, q_fs, k_bs, k_fs, v_bs, v_fs, o_bs, o_fs, ld_q)
+    _launch(dev, "tf_ext_attn_fwd_frame_sets_part", lib.tf_ext_attn_fwd_frame_sets_part, qp, kp, vp, op, K, Kq, int(q_frame0), S,
+            heads, dh, ld, ctypes.cast(strides, ctypes.c_void_p), float(scale), flags, dt, ctypes.cast(tab, ctypes.c_void_p),
+            ws.data_ptr(), ws.numel(), stream=stream)
+    return out
+
+
 def ext_attn_edits_views(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, heads: int, scale: float,
                          n_edits: int, inject_mask: int, part: str = "all", qk_compact: bool = False,
                          branch0=(0, 0, 0, 0), q_frame0: int = 0, fold_scale: Optional[bool] = None,
@@ -1216,6 +1274,39 @@ def window_halo_pack(slabs: Sequence[torch.Tensor], segments, out: Optional[torc
     _launch(dev, "tf_window_halo_pack", lib.tf_window_halo_pack, ctypes.cast(ptrs, ctypes.c_void_p),
             ctypes.cast(fs, ctypes.c_void_p), ns, out.data_ptr(), len(seg), ctypes.cast(f0s, ctypes.c_void_p),
             ctypes.cast(cnt, ctypes.c_void_p), Kl, S, D, ld, -1 if dt is None else dt)
+    return out
+
+
+def frame_set_halo_pack(slabs: Sequence[torch.Tensor], masks, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`window_halo_pack` where a peer reads a SET of the local frames: masks = one int mask over the Kl <= 64 local frames per
+    peer, in rank order -> the send buffer [rows, ns, S, D] of ONE row all-to-all, rows = the members of mask 0 in ascending
+    order, then those of mask 1, ... (tf_frame_set_halo_pack, one launch).  A frame in several masks is written to each; an empty
+    mask contributes nothing.  The packing of an anchored windowed frame shard (`sharded.frame_set_halo_plan(...).send`)."""
+    dev = _need_gpu(*slabs)
+    lib = _lib.load()
+    Kl, S, D = slabs[0].shape
+    ns = len(slabs)
+    ld = slabs[0].stride(1)
+    dt = _DT.get(slabs[0].dtype)
+    if any(t.shape != (Kl, S, D) or t.stride(2) != 1 or t.stride(1) != ld or t.dtype != slabs[0].dtype for t in slabs):
+        raise ValueError("frame_set_halo_pack: slabs must be [Kl, S, D] views sharing dtype and token stride")
+    ms = [int(m) for m in masks]
+    if not ms or Kl > 64 or any(m < 0 or m >> Kl for m in ms):
+        raise ValueError(f"frame_set_halo_pack: masks {[hex(m) for m in ms]} (bits below the {Kl} <= 64 local frames, one mask "
+                         "per peer)")
+    rows = sum(bin(m).count("1") for m in ms)
+    if out is None:
+        out = torch.empty(rows, ns, S, D, dtype=slabs[0].dtype, device=slabs[0].device)
+    elif out.shape != (rows, ns, S, D) or not out.is_contiguous() or out.dtype != slabs[0].dtype:
+        raise ValueError(f"frame_set_halo_pack: `out` must be a contiguous [{rows}, {ns}, {S}, {D}] tensor of the slabs' dtype")
+    if rows == 0:      # nobody reads this rank's frames: nothing to launch
+        return out
+    ptrs = (ctypes.c_void_p * ns)(*[t.data_ptr() for t in slabs])
+    fs = (ctypes.c_int64 * ns)(*[t.stride(0) for t in slabs])
+    tab = (ctypes.c_uint64 * len(ms))(*ms)
+    _launch(dev, "tf_frame_set_halo_pack", lib.tf_frame_set_halo_pack, ctypes.cast(ptrs, ctypes.c_void_p),
+            ctypes.cast(fs, ctypes.c_void_p), ns, out.data_ptr(), len(ms), ctypes.cast(tab, ctypes.c_void_p), Kl, S, D, ld,
+            -1 if dt is None else dt)
     return out
 
 

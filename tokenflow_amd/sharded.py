@@ -171,6 +171,69 @@ def window_halo_plan(K: int, world: int, rank: int, radius: int) -> WindowHaloPl
                           [n for _, n in send], [n for _, n in recv], windows)
 
 
+FrameSetHaloPlan = collections.namedtuple(
+    "FrameSetHaloPlan", "K world rank radius anchors counts offsets kf0 Kl lo hi U F q_frame0 send recv send_rows recv_rows sets")
+
+
+def _anchor_list(what: str, anchors, K: int) -> list:
+    """The anchors of a call as a sorted list of distinct ints inside [0, K) (None = none)."""
+    out = set()
+    for a in (anchors or ()):
+        if isinstance(a, bool) or int(a) != a or not 0 <= int(a) < K:
+            raise ValueError(f"{what}: anchor {a!r} (keyframe indices 0 <= a < {K})")
+        out.add(int(a))
+    return sorted(out)
+
+
+def frame_set_halo_plan(K: int, world: int, rank: int, radius: int, anchors=()):
+    """Exchange geometry of an ANCHORED sliding-window bank on a frame shard (pure arithmetic; csrc/rank_exec.hip computes the
+    same from the same inputs).  `anchors`: global keyframe indices 0 <= a < K that every keyframe sees beside its window
+    (duplicates are fine; K may exceed 64).  With [lo, hi) as in `window_halo_plan` rank r reads the set
+    U = [lo, hi) | anchors (ascending), F = |U| <= 64 frames: a set is a 64-bit mask over the rank's EXTENDED bank.
+      recv[p] = the members of U that peer p owns, ascending (GLOBAL indices) -- in rank order these are U ascending, so the
+                receive buffer of ONE row all-to-all IS the extended bank [F][ns][S][D]
+      send[p] = the LOCAL frames of this rank that lie in U_p, as an int mask over the Kl local frames; send[r] = all Kl
+      send_rows / recv_rows: the frame counts of the two, the row counts of that exchange
+      q_frame0 = the members of U below kf0: the own frames are contiguous in U, the queries are the bank frames
+                q_frame0 .. q_frame0 + Kl - 1
+      sets[i] = (window of global keyframe kf0 + i) | anchors, as an int mask over the POSITIONS in U
+    No anchors (None, empty): the plan IS `window_halo_plan(K, world, rank, radius)`, returned as that type."""
+    K, W, r, R = int(K), int(world), int(rank), int(radius)
+    if W < 1 or not 0 <= r < W or K < W:
+        raise ValueError(f"frame_set_halo_plan: rank {r} of {W} over {K} keyframes (every rank owns at least one)")
+    if R < 0:
+        raise ValueError(f"frame_set_halo_plan: radius={R} (>= 0)")
+    anc = _anchor_list("frame_set_halo_plan", anchors, K)
+    if not anc:
+        return window_halo_plan(K, W, r, R)
+    from . import _lib
+    counts = [K // W + (1 if p < K % W else 0) for p in range(W)]
+    offsets = [sum(counts[:p]) for p in range(W)]
+    if counts[r] > _lib.TF_MAX_WINDOW_FRAMES:
+        raise ValueError(f"frame_set_halo_plan: {counts[r]} local keyframes (at most {_lib.TF_MAX_WINDOW_FRAMES} carry a set)")
+
+    def reads(p):      # U_p, ascending
+        lo_p, hi_p = max(0, offsets[p] - R), min(K, offsets[p] + counts[p] + R)
+        return sorted(set(range(lo_p, hi_p)) | set(anc))
+    kf0, Kl = offsets[r], counts[r]
+    U = reads(r)
+    if len(U) > 64:
+        raise ValueError(f"frame_set_halo_plan: rank {r} reads {len(U)} frames (window reach plus anchors: at most 64, a set is "
+                         "a 64-bit mask over the rank's extended bank)")
+    pos = {g: j for j, g in enumerate(U)}
+    send, recv = [], []
+    for p in range(W):
+        recv.append([g for g in U if offsets[p] <= g < offsets[p] + counts[p]])
+        Up = set(reads(p))
+        send.append(sum(1 << i for i in range(Kl) if kf0 + i in Up))
+    sets = []
+    for g in range(kf0, kf0 + Kl):
+        members = set(range(max(0, g - R), min(K - 1, g + R) + 1)) | set(anc)
+        sets.append(sum(1 << pos[m] for m in members))
+    return FrameSetHaloPlan(K, W, r, R, tuple(anc), counts, offsets, kf0, Kl, max(0, kf0 - R), min(K, kf0 + Kl + R), U, len(U),
+                            pos[kf0], send, recv, [bin(m).count("1") for m in send], [len(x) for x in recv], sets)
+
+
 # (an explicit "bank_runs" for several edits on a shard built without the opt-in)
 _NO_EDIT_RUNS = ("FrameShard: the \"bank_runs\" pattern has no multi-edit form (use \"bank\" or \"heads\") unless the shard "
                  "opts in: edit_runs=True / TOKENFLOW_SHARD_EDIT_RUNS=1")
@@ -410,11 +473,13 @@ class FrameShard:
 
     def pivotal_attention(self, q_local, k_local, v_local, heads: int, scale: float, inject: bool,
                           mode: Optional[str] = None, out4: Optional[torch.Tensor] = None, n_edits: int = 1,
-                          inject_mask: Optional[int] = None, window: Optional[int] = None):
+                          inject_mask: Optional[int] = None, window: Optional[int] = None, anchors=None):
         """Extended attention for the local keyframes against all K keyframes -> [3*Kl,S,D].
         window = R: a sliding-window bank (`_pivotal_window`; NOT TokenFlow's result): the bank branches of keyframe g attend
         to the keyframes g - R .. g + R only, of which the rank fetches just those within R of its own run.  None, or a radius
         that covers the bank (R >= K - 1), is the pass without the keyword; one edit only.
+        anchors (beside window): GLOBAL keyframe indices every keyframe sees beside its window (`_pivotal_frame_sets`); none
+        is the windowed pass itself.
         mode: "heads" | "bank" | "bank_runs" | None (= `auto_mode`, chosen per block).
         out4: a [3,Kl,S,D] view (dense frames, free branch stride) the result is written into in place -- the
         keyframe slots 1.. of a halo-extended buffer (`ext_alloc`); returned as is.
@@ -422,7 +487,10 @@ class FrameShard:
         injection state per edit (bit e = edit e uses the source's q and k; None = `inject` for every edit).  Modes "heads"
         and "bank"; the slices of edit e equal the single-edit pass on [source | uncond_e | cond_e] bit for bit in the
         one-pass form."""
+        anc = self._anchors(window, anchors)
         if self._window(window, n_edits, mode) is not None:
+            if anc:
+                return self._pivotal_frame_sets(q_local, k_local, v_local, heads, scale, inject, int(window), anc, out4)
             return self._pivotal_window(q_local, k_local, v_local, heads, scale, inject, int(window), out4)
         if n_edits != 1:
             return self._pivotal_edits(q_local, k_local, v_local, heads, scale, inject, mode, out4, int(n_edits), inject_mask)
@@ -509,6 +577,59 @@ class FrameShard:
         else:
             ops.ext_attn_windows_views(q3, rp[0:2], rp[2:4], out, heads, scale, False, plan.windows, "bank",
                                        branch0=(0, 1, 1, 0), q_frame0=plan.hl, no_split=ns_)
+        return out.view(3 * Kl, S, D) if out4 is None else out4
+
+    # ------------------------------------------------------------------ ... plus global anchor keyframes
+    supports_window_anchors = True      # `pivotal_attention` / `pivotal_block` take anchors= beside window=
+
+    def _anchors(self, window, anchors) -> tuple:
+        """The anchors of a pass as sorted distinct global indices (() = none), checked against the shard's WHOLE bank;
+        `anchors` without `window` is an error."""
+        if anchors is None:
+            return ()
+        if window is None:
+            raise ValueError("FrameShard: anchors= without window= (anchor keyframes stand beside a sliding-window bank)")
+        return tuple(_anchor_list("FrameShard", anchors, self.K))
+
+    def _pivotal_frame_sets(self, q_local, k_local, v_local, heads: int, scale: float, inject: bool, R: int, anchors, out4=None):
+        """The anchored windowed pass (`frame_set_halo_plan`): `_pivotal_window` with a set instead of a range on both sides of
+        the exchange -- the same packing, exchange and two attention calls as the native executor's tf_rank_pivotal_frame_sets:
+          1. ONE `ops.frame_set_halo_pack` of the slabs peers read, per peer the members of its mask, own frames as self rows;
+          2. ONE row all-to-all with the sparse counts: the receive buffer is the extended bank U [F, slabs, S, D];
+          3. the source part of the local frames, set-free;
+          4. `ops.ext_attn_frame_sets_views(part="bank")` over the receive buffer in place, Kq = Kl, q_frame0 and the sets of
+             the plan (masks over U's positions: F <= 64 whatever K)."""
+        B, S, D = q_local.shape
+        Kl = self.Kl
+        ns_ = not self.attn_split
+        if self.world == 1:
+            out = None if out4 is None else out4.view(q_local.shape)
+            return ops.ext_attn_frame_sets(q_local, k_local, v_local, heads, scale, inject,
+                                           ops.bank_frame_sets(self.K, R, anchors), out=out, no_split=ns_)
+        plan = frame_set_halo_plan(self.K, self.world, self.rank, R, anchors)
+        dev, dt = q_local.device, q_local.dtype
+
+        def frames(t):     # [3*Kl, S, D] (token stride free) -> [3, Kl, S, D] view
+            if t.stride(2) != 1 or t.stride(0) != S * t.stride(1):
+                t = t.contiguous()
+            return t.view(3, Kl, S, D) if t.is_contiguous() else t.unflatten(0, (3, Kl))
+        q3, k3, v3 = frames(q_local), frames(k_local), frames(v_local)
+        if k3.stride(2) != v3.stride(2):
+            k3, v3 = k3.contiguous(), v3.contiguous()
+        slabs = [k3[0], v3[1], v3[2]] if inject else [k3[1], k3[2], v3[1], v3[2]]
+        ns = len(slabs)
+        send = ops.frame_set_halo_pack(slabs, plan.send, out=self._buf("set_send", (sum(plan.send_rows), ns, S, D), dt, dev))
+        recv = self._buf("set_recv", (plan.F, ns, S, D), dt, dev)
+        self._a2a(recv.view(plan.F, -1), send.view(send.shape[0], -1), plan.recv_rows, plan.send_rows)
+        out = torch.empty(3, Kl, S, D, dtype=dt, device=dev) if out4 is None else out4
+        ops.ext_attn_views(q3, k3, v3, out, heads, scale, inject, "source", no_split=ns_)
+        rp = recv.permute(1, 0, 2, 3)                                   # [ns, F, S, D] views: frame stride ns*S*D
+        if inject:     # k holds the source slab alone (branch 0), v the two value banks (branches 1, 2)
+            ops.ext_attn_frame_sets_views(q3, rp[0:1], rp[1:3], out, heads, scale, True, plan.sets, "bank",
+                                          branch0=(0, 0, 1, 0), q_frame0=plan.q_frame0, no_split=ns_)
+        else:
+            ops.ext_attn_frame_sets_views(q3, rp[0:2], rp[2:4], out, heads, scale, False, plan.sets, "bank",
+                                          branch0=(0, 1, 1, 0), q_frame0=plan.q_frame0, no_split=ns_)
         return out.view(3 * Kl, S, D) if out4 is None else out4
 
     # ------------------------------------------------------------------ pivotal pass of a multi-edit batch
@@ -748,8 +869,8 @@ class FrameShard:
 
     def pivotal_block(self, q_local, k_local, v_local, heads: int, scale: float, inject: bool, ext,
                       mode: Optional[str] = None, inv_norm: bool = False, n_edits: int = 1,
-                      inject_mask: Optional[int] = None, window: Optional[int] = None):
-        """n_edits / inject_mask / window: as `pivotal_attention`; `ext` from `ext_alloc(..., n_edits=)`; the ONE grouped exchange
+                      inject_mask: Optional[int] = None, window: Optional[int] = None, anchors=None):
+        """n_edits / inject_mask / window / anchors: as `pivotal_attention`; `ext` from `ext_alloc(..., n_edits=)`; the ONE grouped exchange
         carries the last keyframe of all 1 + 2E branches of the attention output.
         The pivotal pass of one block on this rank, for the reference's call order (one pivotal pass over all
         blocks, then the chunk passes): `ext` = `ext_alloc(...)` whose pivot / inverse-norm slots o.. the caller has
@@ -767,8 +888,10 @@ class FrameShard:
         if inv_norm:
             ops.pivot_inv_norm(piv[o:], out=inv[o:])
         nbr = 1 + 2 * int(n_edits)
+        anc = self._anchors(window, anchors)
         if self._window(window, n_edits, mode) is not None:
-            self.pivotal_attention(q_local, k_local, v_local, heads, scale, inject, out4=kfo[:, o:], window=window)
+            self.pivotal_attention(q_local, k_local, v_local, heads, scale, inject, out4=kfo[:, o:], window=window,
+                                   anchors=anc or None)
         elif n_edits == 1:
             self.pivotal_attention(q_local, k_local, v_local, heads, scale, inject, mode=mode, out4=kfo[:, o:])
         else:
@@ -980,34 +1103,40 @@ class NativeShard(FrameShard):
             pass
 
     def pivotal_attention(self, q_local, k_local, v_local, heads: int, scale: float, inject: bool,
-                          mode: Optional[str] = None, out4: Optional[torch.Tensor] = None, window: Optional[int] = None):
+                          mode: Optional[str] = None, out4: Optional[torch.Tensor] = None, window: Optional[int] = None,
+                          anchors=None):
         """`FrameShard.pivotal_attention` as one library call (tf_rank_pivotal with TF_RANK_NO_HALO): what the hook path
         calls from `attn1` (its cached attention output is the to_out-projected one, so the halo stays the block's).
-        window = R: the windowed pass, ONE tf_rank_pivotal_window call."""
+        window = R: the windowed pass, ONE tf_rank_pivotal_window call; with anchors ONE tf_rank_pivotal_frame_sets call."""
+        anc = self._anchors(window, anchors)
         R = self._window(window, 1, mode)
         if self.world == 1 or out4 is not None or not q_local.is_cuda or q_local.dtype not in (torch.bfloat16,
                                                                                                 torch.float16):
             if R is not None:
-                return FrameShard.pivotal_attention(self, q_local, k_local, v_local, heads, scale, inject, out4=out4, window=R)
+                return FrameShard.pivotal_attention(self, q_local, k_local, v_local, heads, scale, inject, out4=out4, window=R,
+                                                    anchors=anc or None)
             return super().pivotal_attention(q_local, k_local, v_local, heads, scale, inject, mode=mode, out4=out4)
         B, S, D = q_local.shape
         out = torch.empty(3, self.Kl, S, D, dtype=q_local.dtype, device=q_local.device)
-        self._native(q_local, k_local, v_local, heads, scale, inject, mode, None, None, out, no_halo=True, window=R)
+        self._native(q_local, k_local, v_local, heads, scale, inject, mode, None, None, out, no_halo=True, window=R,
+                     anchors=anc if R is not None else ())
         return out.view(B, S, D)
 
     def pivotal_block(self, q_local, k_local, v_local, heads: int, scale: float, inject: bool, ext,
-                      mode: Optional[str] = None, inv_norm: bool = False, window: Optional[int] = None):
+                      mode: Optional[str] = None, inv_norm: bool = False, window: Optional[int] = None, anchors=None):
         piv, inv, kfo = ext
         B, S, D = q_local.shape
         Kl = self.Kl
         o = 1 if self.world > 1 else 0
+        anc = self._anchors(window, anchors)
+        R = self._window(window, 1, mode)
         slot = self._native(q_local, k_local, v_local, heads, scale, inject, mode, piv, inv, kfo, no_halo=False,
-                            inv_norm=inv_norm, window=self._window(window, 1, mode))
+                            inv_norm=inv_norm, window=R, anchors=anc if R is not None else ())
         reqs = [_SlotWait(self, slot, q_local.device)] if self.world > 1 else []
         return piv, inv, kfo.view(3 * (Kl + o), S, D), reqs
 
     def _native(self, q_local, k_local, v_local, heads, scale, inject, mode, piv, inv, kfo, no_halo, inv_norm=False,
-                window=None):
+                window=None, anchors=()):
         from . import _lib
         lib = _lib.load()
         B, S, D = q_local.shape
@@ -1029,11 +1158,18 @@ class NativeShard(FrameShard):
         strides = (ctypes.c_int64 * 8)(q3.stride(0), q3.stride(1), k3.stride(0), k3.stride(1), v3.stride(0), v3.stride(1),
                                        q3.stride(2), k3.stride(2))
         dh = D // heads
-        key = (S, heads, dh, dt, q_local.device, window)
+        anchors = tuple(anchors)
+        anc = (ctypes.c_int * max(len(anchors), 1))(*anchors)
+        key = (S, heads, dh, dt, q_local.device, window) + ((anchors,) if anchors else ())
         ws = self._nws.get(key)
         if ws is None:
             if window is None:
                 nbytes = lib.tf_rank_pivotal_workspace_bytes(self._rk, S, heads, dh, dt)
+            elif anchors:
+                plan = frame_set_halo_plan(self.K, self.world, self.rank, int(window), anchors)      # (raises what is refused)
+                nbytes = lib.tf_rank_pivotal_frame_sets_workspace_bytes(self._rk, S, heads, dh, dt, int(window),
+                                                                        ctypes.cast(anc, ctypes.c_void_p), len(anchors))
+                assert nbytes > 0, plan
             else:
                 nbytes = lib.tf_rank_pivotal_window_workspace_bytes(self._rk, S, heads, dh, dt, int(window))
             ws = self._nws[key] = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=q_local.device)
@@ -1043,6 +1179,17 @@ class NativeShard(FrameShard):
         slot = self._slot
         if not no_halo:
             self._slot = (slot + 1) % _lib.TF_RANK_SLOTS
+        if window is not None and anchors:      # the anchored windowed pass: ONE tf_rank_pivotal_frame_sets call
+            m = _lib.TF_RANK_BANK | (_lib.TF_RANK_NO_HALO if no_halo else 0) | (_lib.TF_RANK_INV_NORM if inv_norm else 0)
+            rc = lib.tf_rank_pivotal_frame_sets(self._rk, q3.data_ptr(), k3.data_ptr(), v3.data_ptr(), strides,
+                                                None if piv is None else piv.data_ptr(),
+                                                None if inv is None else inv.data_ptr(), kfo.data_ptr(), S, heads, dh,
+                                                float(scale), flags, dt, m, slot, int(window),
+                                                ctypes.cast(anc, ctypes.c_void_p), len(anchors), ws.data_ptr(), ws.numel(),
+                                                torch.cuda.current_stream(q_local.device).cuda_stream)
+            if rc:
+                _lib.check(rc, "tf_rank_pivotal_frame_sets")
+            return slot
         if window is not None:      # the windowed pass: ONE tf_rank_pivotal_window call
             m = _lib.TF_RANK_BANK | (_lib.TF_RANK_NO_HALO if no_halo else 0) | (_lib.TF_RANK_INV_NORM if inv_norm else 0)
             rc = lib.tf_rank_pivotal_window(self._rk, q3.data_ptr(), k3.data_ptr(), v3.data_ptr(), strides,
@@ -1093,14 +1240,15 @@ class NativeEditShard(NativeShard):
 
     def pivotal_attention(self, q_local, k_local, v_local, heads: int, scale: float, inject: bool,
                           mode: Optional[str] = None, out4: Optional[torch.Tensor] = None, n_edits: int = 1,
-                          inject_mask: Optional[int] = None, window: Optional[int] = None):
+                          inject_mask: Optional[int] = None, window: Optional[int] = None, anchors=None):
         """`FrameShard.pivotal_attention` with n_edits / inject_mask; E > 1 is one tf_rank_pivotal_edits call with
-        TF_RANK_NO_HALO (what the hook path calls from `attn1`).  window=: one edit only, `NativeShard`'s windowed pass."""
+        TF_RANK_NO_HALO (what the hook path calls from `attn1`).  window= / anchors=: one edit only, `NativeShard`'s passes."""
         E = int(n_edits)
+        self._anchors(window, anchors)
         self._window(window, E, mode)      # (a windowed multi-edit batch raises)
         if E == 1:
             return super().pivotal_attention(q_local, k_local, v_local, heads, scale, inject, mode=mode, out4=out4,
-                                             window=window)
+                                             window=window, anchors=anchors)
         if self.world == 1 or out4 is not None or not q_local.is_cuda or q_local.dtype not in (torch.bfloat16,
                                                                                                 torch.float16):
             return FrameShard.pivotal_attention(self, q_local, k_local, v_local, heads, scale, inject, mode=mode, out4=out4,
@@ -1113,12 +1261,13 @@ class NativeEditShard(NativeShard):
 
     def pivotal_block(self, q_local, k_local, v_local, heads: int, scale: float, inject: bool, ext,
                       mode: Optional[str] = None, inv_norm: bool = False, n_edits: int = 1,
-                      inject_mask: Optional[int] = None, window: Optional[int] = None):
+                      inject_mask: Optional[int] = None, window: Optional[int] = None, anchors=None):
         E = int(n_edits)
+        self._anchors(window, anchors)
         self._window(window, E, mode)      # (a windowed multi-edit batch raises)
         if E == 1:
             return super().pivotal_block(q_local, k_local, v_local, heads, scale, inject, ext, mode=mode, inv_norm=inv_norm,
-                                         window=window)
+                                         window=window, anchors=anchors)
         mask = self._mask(E, inject, inject_mask)
         piv, inv, kfo = ext
         _, S, D = q_local.shape
@@ -1207,3 +1356,20 @@ def rank_window_plan(world: int, rank: int, K: int, S: int, heads: int, dh: int,
     fl = int(flags) | (_lib.TF_ATTN_NO_SPLIT if no_split else 0) | (_lib.TF_ATTN_INJECT if inject else 0)
     return ops._plan_tokens("tf_rank_pivotal_window_plan", _lib.load().tf_rank_pivotal_window_plan, int(world), int(rank),
                             int(K), S, heads, dh, int(radius), m, fl, ops._DT[dtype])
+
+
+def rank_frame_sets_plan(world: int, rank: int, K: int, S: int, heads: int, dh: int, radius: int, anchors=(),
+                         inject: bool = False, dtype: torch.dtype = torch.bfloat16, no_split: bool = True,
+                         no_halo: bool = False, inv_norm: bool = False, flags: int = 0) -> list:
+    """The sequence ONE anchored windowed `NativeShard` block call issues on `rank` of `world` ranks, as tokens
+    (tf_rank_pivotal_frame_sets_plan: e.g. ['set_pack[ns=4]', 'a2a[slabs=4,send=3/2/1,recv=3/1/0]', <source tokens>, <bank tokens
+    with ',set' -- ',win' on a rank whose sets are all ranges in its extended bank>, 'halo[n=5]']).  No anchors give
+    `rank_window_plan`, a covering radius the bank pass.  Recorded by the executing code itself; host only."""
+    from . import _lib
+    m = _lib.TF_RANK_BANK | (_lib.TF_RANK_NO_HALO if no_halo else 0) | (_lib.TF_RANK_INV_NORM if inv_norm else 0)
+    fl = int(flags) | (_lib.TF_ATTN_NO_SPLIT if no_split else 0) | (_lib.TF_ATTN_INJECT if inject else 0)
+    anc = [int(a) for a in (anchors or ())]
+    tab = (ctypes.c_int * max(len(anc), 1))(*anc)
+    return ops._plan_tokens("tf_rank_pivotal_frame_sets_plan", _lib.load().tf_rank_pivotal_frame_sets_plan, int(world), int(rank),
+                            int(K), S, heads, dh, int(radius), ctypes.cast(tab, ctypes.c_void_p), len(anc), m, fl,
+                            ops._DT[dtype])

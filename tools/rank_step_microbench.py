@@ -186,10 +186,18 @@ def main():
                     help="the sliding-window bank of radius R on the shard (pivotal_block(..., window=R): FrameShard and --native; "
                          "one edit).  The exchange of every level is then the sparse row all-to-all of the windowed pass: one arm "
                          "per attention form (the mode labels do not apply); the loopback wire model sees its per-peer row counts")
+    ap.add_argument("--anchors", default=None, metavar="I[,J,...]",
+                    help="beside --window: global anchor keyframes every keyframe sees (pivotal_block(..., window=R, anchors=...)); "
+                         "prints the plan line: frames read, rows per link, frame-banks of attention")
+    ap.add_argument("--anchor-stride", type=int, default=None, metavar="M", help="beside --window: every M-th keyframe as an anchor")
     args = ap.parse_args()
     E = args.edits
     if args.window is not None and E > 1:
         ap.error("--window runs one edit (a windowed shard has no multi-edit form)")
+    if (args.anchors is not None or args.anchor_stride is not None) and args.window is None:
+        ap.error("--anchors / --anchor-stride stand beside --window")
+    if args.anchors is not None and args.anchor_stride is not None:
+        ap.error("--anchors or --anchor-stride, not both")
     mask = (1 << E) - 1 if args.inject_mask is None else args.inject_mask
     if E > 1 and args.world < 2:
         ap.error("--edits needs --world >= 2 (the two-pass rank step)")
@@ -227,11 +235,22 @@ def main():
                 continue
             if args.window is not None:      # every pivotal pass of the step and of the isolated blocks takes the window
                 plain = shard.pivotal_block
-                shard.pivotal_block = lambda *a, _plain=plain, **kw: _plain(*a, **dict(kw, window=args.window))
+                anchors = (tuple(range(0, cfg.K, args.anchor_stride)) if args.anchor_stride
+                           else tuple(int(a) for a in args.anchors.split(",")) if args.anchors else ())
+                shard.pivotal_block = lambda *a, _plain=plain, **kw: _plain(*a, **dict(kw, window=args.window,
+                                                                                      anchors=anchors or None))
                 plan = sharded.window_halo_plan(cfg.K, args.world, args.rank, args.window)
                 print(f"=== sliding-window bank, radius {args.window}: rank {args.rank} reads frames [{plan.lo}, {plan.hi}) "
                       f"({plan.F - plan.Kl} remote of {cfg.K - plan.Kl}); rows out {plan.send_rows}, rows in {plan.recv_rows}",
                       flush=True)
+                if anchors:
+                    plan = sharded.frame_set_halo_plan(cfg.K, args.world, args.rank, args.window, anchors)
+                    banks = sum(bin(m).count("1") for m in plan.sets)
+                    print(f"=== plus anchors {list(anchors)}: rank {args.rank} reads frames {list(plan.U)} ({plan.F - plan.Kl} remote "
+                          f"of {cfg.K - plan.Kl}), q_frame0 {plan.q_frame0}; rows out {plan.send_rows}, rows in {plan.recv_rows}; "
+                          f"{banks} frame-banks of attention (windowed: "
+                          f"{sum(n for _, n in sharded.window_halo_plan(cfg.K, args.world, args.rank, args.window).windows)}, "
+                          f"whole bank: {cfg.K * plan.Kl})", flush=True)
             gen = torch.Generator(device=dev).manual_seed(1234 + args.rank)
             if E > 1:
                 blocks = [EditBlock(cfg, lvl, inj, shard, gen, dev, E) for lvl, inj in workload.BLOCKS]
