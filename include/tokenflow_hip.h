@@ -150,6 +150,16 @@ TF_API const char* tf_last_error(void);
  *
  *   ws: scratch for the transposed V bank (+ key norms, + split-form partials); size from
  *   tf_ext_attn_workspace_bytes.
+ *
+ *   The memory contract of this and of every other entry point that takes a workspace (enforced by
+ *   tests/test_mem_contract_gpu.py):
+ *     - the contents of ws on entry are arbitrary (NaN bit patterns included): a call reads no scratch word it has not
+ *       written itself, so its result does not depend on them;
+ *     - a call writes only [ws, ws + *_workspace_bytes) -- ws_bytes may be exactly that value -- and the rows of `out`
+ *       (and of the other outputs) it owns; rows of branches the selected part does not compute are left as they were;
+ *     - inputs are read only inside their frames' S rows x H*Dh columns (D columns for the NN search and the gather):
+ *       whatever lies in the other columns of a row of stride ld, behind row S - 1 or next to a tensor is never loaded
+ *       into arithmetic, and no input is modified.
  * ------------------------------------------------------------------------ */
 TF_API size_t tf_ext_attn_workspace_bytes(int K, int S, int H, int Dh, int dtype);
 

@@ -63,6 +63,16 @@ def compute_dtype(t: torch.Tensor) -> torch.dtype:
     return t.dtype if t.dtype in (torch.bfloat16, torch.float16) else FP32_AS
 
 
+def _caller_buffer(what: str, name: str, buf: Optional[torch.Tensor], shape, dtype: torch.dtype, device) -> torch.Tensor:
+    """A result tensor: a fresh one, or the caller's `buf` -- contiguous, of exactly this shape, dtype and device."""
+    shape = tuple(shape)
+    if buf is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if tuple(buf.shape) != shape or buf.dtype != dtype or not buf.is_contiguous() or buf.device != device:
+        raise ValueError(f"{what}: `{name}` must be a contiguous {list(shape)} tensor of {dtype} on {device}")
+    return buf
+
+
 _ws_cache = {}
 _attn_ws_bytes = {}   # (K, S, H, Dh, dtype) -> scratch bytes of tf_ext_attn_fwd (a pure function of the shape)
 
@@ -1343,10 +1353,12 @@ def pivot_inv_norm(piv: torch.Tensor, out: Optional[torch.Tensor] = None) -> tor
     return out
 
 
-def nn_search(tgt: torch.Tensor, piv: torch.Tensor, inv_norm: torch.Tensor, kf_ids: Sequence[int]) -> torch.Tensor:
+def nn_search(tgt: torch.Tensor, piv: torch.Tensor, inv_norm: torch.Tensor, kf_ids: Sequence[int],
+              idx: Optional[torch.Tensor] = None) -> torch.Tensor:
     """tgt [n*S, D], piv [K, S, D] (same 16-bit dtype), inv_norm fp32 [K, S]; kf_ids = 1 or 2 keyframe
-    indices in the reference's order [i, i-1] (tokenflow_utils.py:331-333).  Returns int32 [P, n*S]."""
-    dev = _need_gpu(tgt, piv, inv_norm)
+    indices in the reference's order [i, i-1] (tokenflow_utils.py:331-333).  Returns int32 [P, n*S] (written into `idx` when
+    given: a contiguous int32 tensor of that shape)."""
+    dev = _need_gpu(tgt, piv, inv_norm, idx)
     lib = _lib.load()
     tgt, piv = tgt.contiguous(), piv.contiguous()
     K, S, D = piv.shape
@@ -1354,7 +1366,7 @@ def nn_search(tgt: torch.Tensor, piv: torch.Tensor, inv_norm: torch.Tensor, kf_i
     P = len(kf_ids)
     if tgt.dtype != piv.dtype or tgt.shape[1] != D or P not in (1, 2) or any(not 0 <= i < K for i in kf_ids):
         raise ValueError("nn_search: bad arguments")
-    idx = torch.empty(P, n_tgt, dtype=torch.int32, device=tgt.device)
+    idx = _caller_buffer("nn_search", "idx", idx, (P, n_tgt), torch.int32, tgt.device)
     ws = _workspace(lib.tf_nn_search_workspace_bytes(n_tgt, S, D, P), tgt.device, "nn")
     _launch(dev, "tf_nn_search", lib.tf_nn_search, tgt.data_ptr(), piv.data_ptr(), inv_norm.data_ptr(), idx.data_ptr(),
             n_tgt, S, D, P, int(kf_ids[0]), int(kf_ids[1]) if P == 2 else 0, _DT[tgt.dtype], ws.data_ptr(), ws.numel())
@@ -1362,10 +1374,12 @@ def nn_search(tgt: torch.Tensor, piv: torch.Tensor, inv_norm: torch.Tensor, kf_i
 
 
 def gather_blend(kf_out: torch.Tensor, idx: torch.Tensor, w: Optional[torch.Tensor], kf_ids: Sequence[int],
-                 n: int, residual: Optional[torch.Tensor], out_dtype: torch.dtype) -> torch.Tensor:
+                 n: int, residual: Optional[torch.Tensor], out_dtype: torch.dtype,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """kf_out [3K,S,D]; idx int32 [P, n*S]; w fp32 [n] (P == 2); residual [3n,S,D] or None.
-    Returns [3n,S,D] of out_dtype (tokenflow_utils.py:362-397)."""
-    dev = _need_gpu(kf_out, idx, w, residual)
+    Returns [3n,S,D] of out_dtype (tokenflow_utils.py:362-397), written into `out` when given (contiguous, that shape and
+    dtype)."""
+    dev = _need_gpu(kf_out, idx, w, residual, out)
     lib = _lib.load()
     kf_out = kf_out.contiguous()
     BK, S, D = kf_out.shape
@@ -1373,7 +1387,7 @@ def gather_blend(kf_out: torch.Tensor, idx: torch.Tensor, w: Optional[torch.Tens
     P = len(kf_ids)
     if residual is not None:
         residual = residual.contiguous()
-    out = torch.empty(3 * n, S, D, dtype=out_dtype, device=kf_out.device)
+    out = _caller_buffer("gather_blend", "out", out, (3 * n, S, D), out_dtype, kf_out.device)
     _launch(dev, "tf_gather_blend", lib.tf_gather_blend, kf_out.data_ptr(), idx.data_ptr(),
             w.data_ptr() if w is not None else 0, residual.data_ptr() if residual is not None else 0, out.data_ptr(),
             K, n, S, D, P, int(kf_ids[0]), int(kf_ids[1]) if P == 2 else 0, _DT[kf_out.dtype],
@@ -1420,10 +1434,12 @@ def layer_norm(x: torch.Tensor, weight: Optional[torch.Tensor], bias: Optional[t
 
 
 def add_layer_norm(a: torch.Tensor, b: torch.Tensor, weight: Optional[torch.Tensor], bias: Optional[torch.Tensor],
-                   eps: float, out_dtype: torch.dtype):
+                   eps: float, out_dtype: torch.dtype, total: Optional[torch.Tensor] = None,
+                   out: Optional[torch.Tensor] = None):
     """(a + b, LayerNorm(a + b)) in one pass (tf_add_layer_norm): the sum has torch's promoted dtype and rounding, the
-    norm is `layer_norm` of that rounded sum -- bit-identical to the two separate ops."""
-    dev = _need_gpu(a, b, weight, bias)
+    norm is `layer_norm` of that rounded sum -- bit-identical to the two separate ops.
+    total / out: contiguous destination tensors of a's shape (the promoted dtype / out_dtype) to write into."""
+    dev = _need_gpu(a, b, weight, bias, total, out)
     lib = _lib.load()
     if a.shape != b.shape:
         raise ValueError("add_layer_norm: a and b must have one shape")
@@ -1435,8 +1451,8 @@ def add_layer_norm(a: torch.Tensor, b: torch.Tensor, weight: Optional[torch.Tens
     wt = weight if weight is not None else bias
     weight = weight.contiguous() if weight is not None else None
     bias = bias.contiguous() if bias is not None else None
-    total = torch.empty(a.shape, dtype=torch.promote_types(a.dtype, b.dtype), device=a.device)
-    out = torch.empty(a.shape, dtype=out_dtype, device=a.device)
+    total = _caller_buffer("add_layer_norm", "total", total, a.shape, torch.promote_types(a.dtype, b.dtype), a.device)
+    out = _caller_buffer("add_layer_norm", "out", out, a.shape, out_dtype, a.device)
     _launch(dev, "tf_add_layer_norm", lib.tf_add_layer_norm, a.data_ptr(), b.data_ptr(), total.data_ptr(),
             weight.data_ptr() if weight is not None else 0, bias.data_ptr() if bias is not None else 0, out.data_ptr(),
             rows, D, float(eps), _DT[a.dtype], _DT[b.dtype], _DT[total.dtype], _DT[wt.dtype] if wt is not None else 0,
@@ -1454,9 +1470,9 @@ def norm_fusable(kf_out: torch.Tensor, residual: Optional[torch.Tensor], out_dty
             and norm_dtype == dt and out_dtype == (torch.float32 if P == 2 else dt) and kf_out.shape[-1] <= 1536)
 
 
-def _norm_args(norm, like: torch.Tensor, shape):
+def _norm_args(norm, like: torch.Tensor, shape, norm_out: Optional[torch.Tensor] = None):
     """(gamma ptr, beta ptr, eps, w dtype code, norm_out tensor, norm dtype code) of a `norm=(weight, bias, eps,
-    dtype)` argument."""
+    dtype)` argument; the norm output goes into the caller's `norm_out` when given."""
     weight, bias, eps, ndt = norm
     if weight is not None and bias is not None and weight.dtype != bias.dtype:
         bias = bias.to(weight.dtype)
@@ -1465,20 +1481,25 @@ def _norm_args(norm, like: torch.Tensor, shape):
         raise TypeError(f"propagate: norm weight dtype {wt.dtype}")
     weight = weight.contiguous() if weight is not None else None
     bias = bias.contiguous() if bias is not None else None
-    nout = torch.empty(shape, dtype=ndt, device=like.device)
+    nout = _caller_buffer("propagate", "norm_out", norm_out, shape, ndt, like.device)
     return (weight.data_ptr() if weight is not None else 0, bias.data_ptr() if bias is not None else 0, float(eps),
             _DT[wt.dtype] if wt is not None else 0, nout, _DT[ndt], (weight, bias))
 
 
 def propagate(tgt: torch.Tensor, piv: torch.Tensor, inv_norm: torch.Tensor, kf_ids: Sequence[int],
               kf_out: torch.Tensor, w: Optional[torch.Tensor], n: int, residual: Optional[torch.Tensor],
-              out_dtype: torch.dtype, norm=None):
+              out_dtype: torch.dtype, norm=None, out: Optional[torch.Tensor] = None,
+              norm_out: Optional[torch.Tensor] = None):
     """nn_search + gather_blend of one chunk in one call (tokenflow_utils.py:329-397): same arguments, same
     results bit for bit, one launch less (the gather merges the search's per-split candidates itself).
     norm = (weight, bias, eps, dtype) of the block's next LayerNorm (see `norm_fusable`): returns
     (result, LayerNorm(result) in `dtype`) from one gather launch -- tf_nn_gather_blend_norm, both bit-identical to
-    the separate calls."""
-    dev = _need_gpu(tgt, piv, inv_norm, kf_out, w, residual)
+    the separate calls.
+    out / norm_out: contiguous destination tensors of the result's shape ([3n,S,D]; out_dtype / the norm's dtype) to write
+    into; norm_out needs `norm`."""
+    dev = _need_gpu(tgt, piv, inv_norm, kf_out, w, residual, out, norm_out)
+    if norm_out is not None and norm is None:
+        raise ValueError("propagate: `norm_out` without `norm`")
     lib = _lib.load()
     tgt, piv, kf_out = tgt.contiguous(), piv.contiguous(), kf_out.contiguous()
     K, S, D = piv.shape
@@ -1489,12 +1510,12 @@ def propagate(tgt: torch.Tensor, piv: torch.Tensor, inv_norm: torch.Tensor, kf_i
         raise ValueError("propagate: bad arguments")
     if residual is not None:
         residual = residual.contiguous()
-    out = torch.empty(3 * n, S, D, dtype=out_dtype, device=kf_out.device)
+    out = _caller_buffer("propagate", "out", out, (3 * n, S, D), out_dtype, kf_out.device)
     ws = _workspace(lib.tf_nn_gather_blend_workspace_bytes(n_tgt, S, D, P), tgt.device, "nn")
     if norm is not None:
         if not norm_fusable(kf_out, residual, out_dtype, P, norm[3]):
             raise TypeError("propagate: these dtypes have no fused-norm form (ops.norm_fusable)")
-        g, b, eps, wdt, nout, ndt, _keep = _norm_args(norm, kf_out, (3 * n, S, D))
+        g, b, eps, wdt, nout, ndt, _keep = _norm_args(norm, kf_out, (3 * n, S, D), norm_out)
         _launch(dev, "tf_nn_gather_blend_norm", lib.tf_nn_gather_blend_norm, tgt.data_ptr(), piv.data_ptr(),
                 inv_norm.data_ptr(), kf_out.data_ptr(), w.data_ptr() if w is not None else 0, residual.data_ptr(),
                 out.data_ptr(), K, n, S, D, P, int(kf_ids[0]), int(kf_ids[1]) if P == 2 else 0, _DT[tgt.dtype],
@@ -1511,12 +1532,15 @@ def propagate(tgt: torch.Tensor, piv: torch.Tensor, inv_norm: torch.Tensor, kf_i
 
 def propagate_chunks(tgt: torch.Tensor, piv: torch.Tensor, inv_norm: torch.Tensor, kf_out: torch.Tensor,
                      w: torch.Tensor, n: int, n_chunks: int, slot0: int, first_single: bool,
-                     residual: Optional[torch.Tensor], out_dtype: torch.dtype, norm=None):
+                     residual: Optional[torch.Tensor], out_dtype: torch.dtype, norm=None,
+                     out: Optional[torch.Tensor] = None, norm_out: Optional[torch.Tensor] = None):
     """`propagate` for a run of `n_chunks` consecutive chunks of n frames in one call (tf_nn_gather_blend_chunks):
     tgt [n_chunks*n*S, D] chunk-major, residual / result [3*n_chunks*n, S, D]; chunk j matches keyframe slots
     slot0 + j and slot0 + j - 1 of piv / inv_norm / kf_out; first_single: chunk 0 of the run is chunk 0 of the
-    video (one keyframe).  Bit-identical to n_chunks calls of `propagate`."""
-    dev = _need_gpu(tgt, piv, inv_norm, kf_out, w, residual)
+    video (one keyframe).  Bit-identical to n_chunks calls of `propagate`.  out / norm_out as there."""
+    dev = _need_gpu(tgt, piv, inv_norm, kf_out, w, residual, out, norm_out)
+    if norm_out is not None and norm is None:
+        raise ValueError("propagate_chunks: `norm_out` without `norm`")
     lib = _lib.load()
     tgt, piv, kf_out = tgt.contiguous(), piv.contiguous(), kf_out.contiguous()
     K, S, D = piv.shape
@@ -1524,7 +1548,7 @@ def propagate_chunks(tgt: torch.Tensor, piv: torch.Tensor, inv_norm: torch.Tenso
     if C == 1:
         ids = [slot0] if first_single else [slot0, slot0 - 1]
         return propagate(tgt, piv, inv_norm, ids, kf_out, None if first_single else w, n, residual, out_dtype,
-                         norm=norm)
+                         norm=norm, out=out, norm_out=norm_out)
     if (tgt.dtype != piv.dtype or tgt.shape != (C * n * S, D) or kf_out.shape != (3 * K, S, D) or w is None
             or slot0 + C > K or slot0 < (0 if first_single else 1)):
         raise ValueError("propagate_chunks: bad arguments")
@@ -1532,12 +1556,12 @@ def propagate_chunks(tgt: torch.Tensor, piv: torch.Tensor, inv_norm: torch.Tenso
         residual = residual.contiguous()
     # what the reference's single-keyframe pass would emit for chunk 0: kf dtype (+ residual), torch promotion
     single_dtype = kf_out.dtype if residual is None else torch.promote_types(kf_out.dtype, residual.dtype)
-    out = torch.empty(3 * C * n, S, D, dtype=out_dtype, device=kf_out.device)
+    out = _caller_buffer("propagate_chunks", "out", out, (3 * C * n, S, D), out_dtype, kf_out.device)
     ws = _workspace(lib.tf_nn_gather_blend_chunks_workspace_bytes(n * S, S, D, C), tgt.device, "nn")
     if norm is not None:
         if not norm_fusable(kf_out, residual, out_dtype, 2, norm[3]):
             raise TypeError("propagate_chunks: these dtypes have no fused-norm form (ops.norm_fusable)")
-        g, b, eps, wdt, nout, ndt, _keep = _norm_args(norm, kf_out, (3 * C * n, S, D))
+        g, b, eps, wdt, nout, ndt, _keep = _norm_args(norm, kf_out, (3 * C * n, S, D), norm_out)
         _launch(dev, "tf_nn_gather_blend_chunks_norm", lib.tf_nn_gather_blend_chunks_norm, tgt.data_ptr(),
                 piv.data_ptr(), inv_norm.data_ptr(), kf_out.data_ptr(), w.data_ptr(), residual.data_ptr(),
                 out.data_ptr(), K, n, C, S, D, int(slot0), 1 if first_single else 0, _DT[tgt.dtype], _DT[kf_out.dtype],
@@ -1554,17 +1578,21 @@ def propagate_chunks(tgt: torch.Tensor, piv: torch.Tensor, inv_norm: torch.Tenso
 
 def propagate_chunks_segments(tgt: torch.Tensor, piv: torch.Tensor, inv_norm: torch.Tensor, kf_out: torch.Tensor,
                               w: torch.Tensor, n: int, n_chunks: int, slot0: int, single_mask: int,
-                              residual: Optional[torch.Tensor], out_dtype: torch.dtype, norm=None):
+                              residual: Optional[torch.Tensor], out_dtype: torch.dtype, norm=None,
+                              out: Optional[torch.Tensor] = None, norm_out: Optional[torch.Tensor] = None):
     """`propagate_chunks` for a run of chunks that crosses scene cuts (tf_nn_gather_blend_chunks_segments): bit j of
     `single_mask` = chunk j of the run is the first chunk of a keyframe segment, a one-keyframe chunk matching slot0 + j
     alone (its rows rounded as chunk 0's of a video are); every other chunk j matches slots slot0 + j and slot0 + j - 1.
     One search and one gather for the whole run.  Masks 1 and 0 are `propagate_chunks` with and without first_single; one
-    chunk is `propagate`."""
+    chunk is `propagate`.  out / norm_out as there."""
     C = int(n_chunks)
     m = _single_mask("propagate_chunks_segments", single_mask, C)
     if C == 1:
-        return propagate_chunks(tgt, piv, inv_norm, kf_out, w, n, C, slot0, bool(m & 1), residual, out_dtype, norm=norm)
-    dev = _need_gpu(tgt, piv, inv_norm, kf_out, w, residual)
+        return propagate_chunks(tgt, piv, inv_norm, kf_out, w, n, C, slot0, bool(m & 1), residual, out_dtype, norm=norm,
+                                out=out, norm_out=norm_out)
+    dev = _need_gpu(tgt, piv, inv_norm, kf_out, w, residual, out, norm_out)
+    if norm_out is not None and norm is None:
+        raise ValueError("propagate_chunks_segments: `norm_out` without `norm`")
     lib = _lib.load()
     tgt, piv, kf_out = tgt.contiguous(), piv.contiguous(), kf_out.contiguous()
     K, S, D = piv.shape
@@ -1574,7 +1602,7 @@ def propagate_chunks_segments(tgt: torch.Tensor, piv: torch.Tensor, inv_norm: to
     if residual is not None:
         residual = residual.contiguous()
     single_dtype = kf_out.dtype if residual is None else torch.promote_types(kf_out.dtype, residual.dtype)
-    out = torch.empty(3 * C * n, S, D, dtype=out_dtype, device=kf_out.device)
+    out = _caller_buffer("propagate_chunks_segments", "out", out, (3 * C * n, S, D), out_dtype, kf_out.device)
     ws = _workspace(lib.tf_nn_gather_blend_chunks_workspace_bytes(n * S, S, D, C), tgt.device, "nn")
     head = (tgt.data_ptr(), piv.data_ptr(), inv_norm.data_ptr(), kf_out.data_ptr(), w.data_ptr(),
             residual.data_ptr() if residual is not None else 0, out.data_ptr(), K, n, C, S, D, int(slot0), m, _DT[tgt.dtype],
@@ -1582,7 +1610,7 @@ def propagate_chunks_segments(tgt: torch.Tensor, piv: torch.Tensor, inv_norm: to
     if norm is not None:
         if not norm_fusable(kf_out, residual, out_dtype, 2, norm[3]):
             raise TypeError("propagate_chunks_segments: these dtypes have no fused-norm form (ops.norm_fusable)")
-        g, b, eps, wdt, nout, ndt, _keep = _norm_args(norm, kf_out, (3 * C * n, S, D))
+        g, b, eps, wdt, nout, ndt, _keep = _norm_args(norm, kf_out, (3 * C * n, S, D), norm_out)
         _launch(dev, "tf_nn_gather_blend_chunks_norm_segments", lib.tf_nn_gather_blend_chunks_norm_segments, *head, g, b, eps,
                 wdt, nout.data_ptr(), ndt, ws.data_ptr(), ws.numel())
         return out, nout
@@ -1593,12 +1621,16 @@ def propagate_chunks_segments(tgt: torch.Tensor, piv: torch.Tensor, inv_norm: to
 
 def propagate_chunks_edits(tgt: torch.Tensor, piv: torch.Tensor, inv_norm: torch.Tensor, kf_out: torch.Tensor,
                            w: Optional[torch.Tensor], n: int, n_chunks: int, slot0: int, first_single: bool,
-                           residual: Optional[torch.Tensor], out_dtype: torch.dtype, n_edits: int, norm=None):
+                           residual: Optional[torch.Tensor], out_dtype: torch.dtype, n_edits: int, norm=None,
+                           out: Optional[torch.Tensor] = None, norm_out: Optional[torch.Tensor] = None):
     """`propagate_chunks` (n_chunks = 1: `propagate`) for a multi-edit batch of B = 1 + 2*n_edits branches: kf_out [B*K,S,D],
     residual / result [B*n_chunks*n, S, D]; tgt (the source branch's rows), piv, inv_norm, w as there.  ONE search -- it
     reads the source branch only -- and one gather over all B branches on the same candidates; every branch of the result
-    is bit-identical to the same branch of the single-edit call on [source | uncond_e | cond_e].  norm= as `propagate`."""
-    dev = _need_gpu(tgt, piv, inv_norm, kf_out, w, residual)
+    is bit-identical to the same branch of the single-edit call on [source | uncond_e | cond_e].
+    norm=, out / norm_out ([B*n_chunks*n, S, D]) as `propagate`."""
+    dev = _need_gpu(tgt, piv, inv_norm, kf_out, w, residual, out, norm_out)
+    if norm_out is not None and norm is None:
+        raise ValueError("propagate_chunks_edits: `norm_out` without `norm`")
     lib = _lib.load()
     E = int(n_edits)
     if not 1 <= E <= _lib.TF_MAX_EDITS:
@@ -1616,7 +1648,7 @@ def propagate_chunks_edits(tgt: torch.Tensor, piv: torch.Tensor, inv_norm: torch
         if residual.shape != (nbr * C * n, S, D):
             raise ValueError("propagate_chunks_edits: residual must be [B*n_chunks*n, S, D]")
     single_dtype = kf_out.dtype if residual is None else torch.promote_types(kf_out.dtype, residual.dtype)
-    out = torch.empty(nbr * C * n, S, D, dtype=out_dtype, device=kf_out.device)
+    out = _caller_buffer("propagate_chunks_edits", "out", out, (nbr * C * n, S, D), out_dtype, kf_out.device)
     ws = _workspace(max(lib.tf_nn_gather_blend_chunks_workspace_bytes(n * S, S, D, C),
                         lib.tf_nn_gather_blend_workspace_bytes(n * S, S, D, 1) if single else 0), tgt.device, "nn")
     head = (tgt.data_ptr(), piv.data_ptr(), inv_norm.data_ptr(), kf_out.data_ptr(), w.data_ptr() if w is not None else 0,
@@ -1626,7 +1658,7 @@ def propagate_chunks_edits(tgt: torch.Tensor, piv: torch.Tensor, inv_norm: torch
     if norm is not None:
         if not norm_fusable(kf_out, residual, out_dtype, 1 if single else 2, norm[3]):
             raise TypeError("propagate_chunks_edits: these dtypes have no fused-norm form (ops.norm_fusable)")
-        g, b, eps, wdt, nout, ndt, _keep = _norm_args(norm, kf_out, (nbr * C * n, S, D))
+        g, b, eps, wdt, nout, ndt, _keep = _norm_args(norm, kf_out, (nbr * C * n, S, D), norm_out)
         _launch(dev, "tf_nn_gather_blend_chunks_norm_edits", lib.tf_nn_gather_blend_chunks_norm_edits, *head, g, b, eps, wdt,
                 nout.data_ptr(), ndt, ws.data_ptr(), ws.numel())
         return out, nout
