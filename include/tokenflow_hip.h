@@ -481,6 +481,25 @@ TF_API int tf_frame_set_halo_pack(const void* const* slabs, const int64_t* frame
                            const uint64_t* masks, int Kl, int S, int D, int64_t ld, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Halo pack of a windowed / anchored frame shard that carries a MULTI-EDIT batch (additive to ABI 11;
+ * tf_rank_pivotal_frame_sets_edits below).  The work of tf_frame_set_halo_pack -- per peer a 64-bit mask over the Kl <= 64 local
+ * frames, send rows in ascending member order, masks and row prefix in the kernel arguments -- for up to 4 * TF_MAX_EDITS slabs
+ * (the compact k slots and two value slabs per edit).  A plain window's ranges are contiguous masks: this one entry serves the
+ * windowed and the anchored pass.
+ * In extra workgroups behind the packing ones the SAME launch copies nq <= 1 + 2 * TF_MAX_EDITS compact q slabs ([Kl, S, ld_q]
+ * tensors with their own frame strides) into the dense staging region q_stage [nq][Kl][S][D]: what a mixed injection mask needs
+ * (the source's q beside the non-injecting edits', under ONE branch stride).  nq = 0 launches none of them and ignores
+ * q_slabs / q_frame_strides / q_stage / ld_q.  No send rows and nq = 0: no launch.
+ * Validation and error codes of tf_frame_set_halo_pack: 16-bit elements only (TF_ERR_DTYPE); D, ld (and ld_q) multiples of 8
+ * elements, ns outside 1 .. 4 * TF_MAX_EDITS, nq outside 0 .. 1 + 2 * TF_MAX_EDITS, Kl > 64, a mask bit at or above Kl:
+ * TF_ERR_SHAPE; pointers and frame strides 16-byte aligned: TF_ERR_ALIGN.  All checked before anything touches the device.
+ * tf_window_halo_pack and tf_frame_set_halo_pack are untouched (ns <= 6).
+ * ------------------------------------------------------------------------ */
+TF_API int tf_edit_halo_pack(const void* const* slabs, const int64_t* frame_strides, int ns, void* send, int n_peer,
+                      const uint64_t* masks, const void* const* q_slabs, const int64_t* q_frame_strides, int nq, void* q_stage,
+                      int Kl, int S, int D, int64_t ld, int64_t ld_q, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------
  * Nearest-neighbour token search  --  replaces batch_cosine_sim + chunk + argmax:
  * util.py:61-69 and tokenflow_utils.py:335-343.
  *
@@ -936,6 +955,57 @@ TF_API int tf_ext_attn_frame_sets_edits_plan(int K, int Kq, int q_frame0, int S,
                                       int flags, int dtype, const uint64_t* sets, char* buf, size_t len);
 
 /* ------------------------------------------------------------------------
+ * The BANK PART of a windowed / frame-set MULTI-EDIT pass (additive to ABI 11): all E edits' bank branches over one table in one
+ * call -- what a frame-sharded rank with several prompts runs over its halo- or anchor-extended receive buffer, instead of E
+ * single-edit part calls.  Opt-in: no existing call reaches these entry points.
+ *
+ * tf_ext_attn_fwd_windows_edits_part takes the arguments of tf_ext_attn_fwd_windows_edits plus qk_compact (behind inject_mask, as in
+ *   tf_ext_attn_fwd_edits_part: q and k hold slot 0 = the source, then (uncond, cond) of every NON-injecting edit in ascending
+ *   order).  TF_ATTN_BANK_ONLY is accepted: v and out are addressed as [source | uncond_1 | cond_1 | ...] and the source slabs
+ *   are never touched.  Without a part flag the call IS tf_ext_attn_fwd_windows_edits (dense q / k: qk_compact = 1 is refused
+ *   there).  TF_ATTN_SOURCE_ONLY is refused (TF_ERR_SHAPE): the source part of a windowed pass is window-free -- it is
+ *   tf_ext_attn_fwd_edits_part(TF_ATTN_SOURCE_ONLY).  Otherwise refused: what tf_ext_attn_fwd_windows_edits refuses of its table,
+ *   its mask and its other flags (TF_ATTN_FOLD_SCALE, TF_ATTN_RUN_MULTI_V), and qk_compact outside 0 .. 1.  The four-bank hints
+ *   stay accepted, under the rule of the windowed multi-edit call.
+ * tf_ext_attn_fwd_frame_sets_edits_part: the same beside tf_ext_attn_fwd_frame_sets_edits (a HOST array of Kq 64-bit masks, K <= 64).
+ *   Launches.  Where every edit's bank part takes the fused small-problem kernel (S <= 256 under TF_ATTN_NO_SPLIT), ALL of them
+ *   run in ONE launch of E tensor sets under the one table, which rides in the kernel arguments: plan token
+ *   fused[qw=..,kw=..,qb=..,prec=..,sets=E,win] / fused[..,sets=E,set], planned for K' = the longest window / largest set.  A
+ *   (query, head)'s arithmetic in that kernel depends on KW and PREC only, so under TF_ATTN_NO_SPLIT the joint launch equals the E
+ *   one-set fused[..,win] / fused[..,set] launches of tf_ext_attn_fwd_windows_part / tf_ext_attn_fwd_frame_sets_part BIT FOR BIT.
+ *   Everything else is the streaming composition of the non-part call without its source launches: ONE V^T pre-pass over the
+ *   streaming branches, the injecting edits (pairs in the four-bank form where it is selected), then the others.
+ *   Canonical forms: same launches, same bits, same plan tokens.  n_edits = 1 IS tf_ext_attn_fwd_windows_part /
+ *   tf_ext_attn_fwd_frame_sets_part (TF_ATTN_INJECT iff mask = 1).  Every set a contiguous range IS
+ *   tf_ext_attn_fwd_windows_edits_part on the equivalent (lo, n) table.  Every window or set the whole bank IS
+ *   tf_ext_attn_fwd_edits_part.
+ *   Identity.  This call with TF_ATTN_BANK_ONLY plus tf_ext_attn_fwd_edits_part(TF_ATTN_SOURCE_ONLY) equal
+ *   tf_ext_attn_fwd_windows_edits / tf_ext_attn_fwd_frame_sets_edits(TF_ATTN_NO_MULTI_V) on the same tensors bit for bit under
+ *   TF_ATTN_NO_SPLIT wherever the plans name the same kernel form, and lie within the attention bound of it everywhere.
+ *   ws: tf_ext_attn_edits_workspace_bytes(K, ...), unchanged.
+ * tf_ext_attn_windows_edits_part_plan / tf_ext_attn_frame_sets_edits_part_plan: the launches for dense tensors (host only).
+ *   NOT BUILT: segments on a shard; run forms over windows.  The single-GPU calls tf_ext_attn_fwd_windows_edits /
+ *   tf_ext_attn_fwd_frame_sets_edits keep issuing one fused launch per edit (their plan tests pin it).
+ * ------------------------------------------------------------------------ */
+TF_API int tf_ext_attn_fwd_windows_edits_part(const void* q, const void* k, const void* v, void* out, int K, int Kq, int q_frame0,
+                                       int S, int H, int Dh, int64_t ld, const int64_t* strides, float scale, int flags,
+                                       int dtype, int n_edits, unsigned inject_mask, int qk_compact, const int* win_lo,
+                                       const int* win_n, void* ws, size_t ws_bytes, void* stream);
+
+TF_API int tf_ext_attn_windows_edits_part_plan(int K, int Kq, int q_frame0, int S, int H, int Dh, int n_edits,
+                                        unsigned inject_mask, int qk_compact, int flags, int dtype, const int* win_lo,
+                                        const int* win_n, char* buf, size_t len);
+
+TF_API int tf_ext_attn_fwd_frame_sets_edits_part(const void* q, const void* k, const void* v, void* out, int K, int Kq,
+                                          int q_frame0, int S, int H, int Dh, int64_t ld, const int64_t* strides, float scale,
+                                          int flags, int dtype, int n_edits, unsigned inject_mask, int qk_compact,
+                                          const uint64_t* sets, void* ws, size_t ws_bytes, void* stream);
+
+TF_API int tf_ext_attn_frame_sets_edits_part_plan(int K, int Kq, int q_frame0, int S, int H, int Dh, int n_edits,
+                                           unsigned inject_mask, int qk_compact, int flags, int dtype, const uint64_t* sets,
+                                           char* buf, size_t len);
+
+/* ------------------------------------------------------------------------
  * Row LayerNorm producer  --  the `norm1` call of TokenFlowBlock.forward
  * (tokenflow_utils.py:313-323; also norm2 / norm3 of the same forward, 399-417)
  * when the block runs in 16 bit:  out[r] = (x[r] - mean) / sqrt(var + eps) * gamma + beta
@@ -1271,6 +1341,47 @@ TF_API int tf_rank_pivotal_frame_sets(tf_rank* rk, const void* q, const void* k,
                                size_t ws_bytes, void* stream);
 TF_API int tf_rank_pivotal_frame_sets_plan(int world, int rank, int K, int S, int H, int Dh, int radius, const int* anchors,
                                     int n_anchors, int mode, int flags, int dtype, char* buf, size_t len);
+
+/* ------------------------------------------------------------------------
+ * The rank executor for a MULTI-EDIT batch over a windowed / anchored bank (additive to ABI 11): several prompts on one long
+ * video across GPUs in ONE sharded pass -- per block one pack, the same collectives, one bank part; only the payload grows with
+ * E.  Opt-in: no existing call reaches it.
+ *
+ * Arguments of tf_rank_pivotal_frame_sets plus n_edits and inject_mask as in tf_rank_pivotal_edits: q, k, v hold B = 1 + 2E
+ * branches [source | uncond_1 | cond_1 | ...] of the rank's Kl keyframes, kfo_ext is [B, Kl + o, S, D].  The geometry is that
+ * of tf_rank_pivotal_window / tf_rank_pivotal_frame_sets: it does not depend on E.
+ * Schedule of ONE call (W > 1, radius < K - 1, E > 1):
+ *   0. the inverse norms under TF_RANK_INV_NORM, a launch of their own;
+ *   1. ONE tf_edit_halo_pack of the compact k slots (slot 0 where some edit injects + 2 per non-injecting edit) and the 2E value
+ *      slabs, with the compact q staging under a mixed mask in the same launch; the source's v and every q stay at home;
+ *   2. the source part, tf_ext_attn_fwd_edits_part(TF_ATTN_SOURCE_ONLY), on the auxiliary stream, forked behind the pack
+ *      (TOKENFLOW_RANK_SRC_AUX=0 keeps it in line behind the exchange);
+ *   3. ONE tf_all_to_all_rows with the sparse counts;
+ *   4. the bank part of ALL edits over the receive buffer [F][ns][S][D] in place (TF_ATTN_BANK_ONLY, qk_compact = 1, Kq = Kl,
+ *      q_frame0 and table as in the single-edit calls): no anchors tf_ext_attn_fwd_windows_edits_part (F < 2^16), anchors
+ *      tf_ext_attn_fwd_frame_sets_edits_part (F <= 64);
+ *   5. join;  6. the neighbour halo with 2 + B messages.
+ * Canonical forms: n_edits = 1 IS tf_rank_pivotal_frame_sets (TF_ATTN_INJECT iff mask = 1); radius >= K - 1 IS
+ * tf_rank_pivotal_edits(TF_RANK_BANK); one rank is tf_ext_attn_fwd_windows_edits / tf_ext_attn_fwd_frame_sets_edits.
+ * Results: the bits of one process issuing the bank part call and the source-only edits part on the full tensors under
+ * TF_ATTN_NO_SPLIT; edit e's slices equal the single-edit windowed / anchored pass on [source | uncond_e | cond_e] with
+ * inject = bit e wherever both plans name the same kernel form (four-bank form off).
+ * Refused before anything touches the device: what both parent calls refuse, and every mode but TF_RANK_BANK (with
+ * TF_RANK_NO_HALO / TF_RANK_INV_NORM).
+ *   ws: tf_rank_pivotal_frame_sets_edits_workspace_bytes -- one size query, never below either parent's for the same arguments,
+ *   0 for arguments the call refuses.
+ * tf_rank_pivotal_frame_sets_edits_plan (host only): inv_norm; edit_pack[ns=N,nq=M]; a2a[slabs=N,send=..,recv=..]; the tokens of
+ *   the source part; the tokens of the bank part; halo[n=2+B].
+ * ------------------------------------------------------------------------ */
+TF_API size_t tf_rank_pivotal_frame_sets_edits_workspace_bytes(const tf_rank* rk, int S, int H, int Dh, int dtype, int radius,
+                                                        const int* anchors, int n_anchors, int n_edits);
+TF_API int tf_rank_pivotal_frame_sets_edits(tf_rank* rk, const void* q, const void* k, const void* v, const int64_t* strides,
+                                     void* piv_ext, float* inv_ext, void* kfo_ext, int S, int H, int Dh, float scale, int flags,
+                                     int dtype, int mode, int slot, int radius, const int* anchors, int n_anchors, int n_edits,
+                                     unsigned inject_mask, void* ws, size_t ws_bytes, void* stream);
+TF_API int tf_rank_pivotal_frame_sets_edits_plan(int world, int rank, int K, int S, int H, int Dh, int radius, const int* anchors,
+                                          int n_anchors, int n_edits, unsigned inject_mask, int mode, int flags, int dtype,
+                                          char* buf, size_t len);
 
 #ifdef __cplusplus
 }

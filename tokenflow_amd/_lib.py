@@ -191,6 +191,27 @@ _SIGNATURES = {
     "tf_rank_pivotal_frame_sets": (_c.c_int, [_c.c_void_p] * 8 + [_c.c_int] * 3 + [_c.c_float] + [_c.c_int] * 5 +
                                    [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "tf_rank_pivotal_frame_sets_plan": (_c.c_int, [_c.c_int] * 7 + [_c.c_void_p] + [_c.c_int] * 4 + [_c.c_char_p, _c.c_size_t]),
+    # the bank part of a windowed / frame-set multi-edit pass: all edits under one table (additive to ABI 11)
+    "tf_ext_attn_fwd_windows_edits_part": (_c.c_int, [_c.c_void_p] * 4 + [_c.c_int] * 6 + [_c.c_int64, _c.c_void_p, _c.c_float,
+                                                      _c.c_int, _c.c_int, _c.c_int, _c.c_uint, _c.c_int, _c.c_void_p,
+                                                      _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "tf_ext_attn_windows_edits_part_plan": (_c.c_int, [_c.c_int] * 7 + [_c.c_uint, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p,
+                                                       _c.c_void_p, _c.c_char_p, _c.c_size_t]),
+    "tf_ext_attn_fwd_frame_sets_edits_part": (_c.c_int, [_c.c_void_p] * 4 + [_c.c_int] * 6 + [_c.c_int64, _c.c_void_p, _c.c_float,
+                                                         _c.c_int, _c.c_int, _c.c_int, _c.c_uint, _c.c_int, _c.c_void_p,
+                                                         _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "tf_ext_attn_frame_sets_edits_part_plan": (_c.c_int, [_c.c_int] * 7 + [_c.c_uint, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p,
+                                                          _c.c_char_p, _c.c_size_t]),
+    # ... on a frame shard: ONE pack of a multi-edit halo, the rank executor (additive to ABI 11)
+    "tf_edit_halo_pack": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p,
+                                     _c.c_void_p, _c.c_int, _c.c_void_p] + [_c.c_int] * 3 + [_c.c_int64, _c.c_int64, _c.c_int,
+                                                                                              _c.c_void_p]),
+    "tf_rank_pivotal_frame_sets_edits_workspace_bytes": (_c.c_size_t, [_c.c_void_p] + [_c.c_int] * 5 + [_c.c_void_p, _c.c_int,
+                                                                                                         _c.c_int]),
+    "tf_rank_pivotal_frame_sets_edits": (_c.c_int, [_c.c_void_p] * 8 + [_c.c_int] * 3 + [_c.c_float] + [_c.c_int] * 5 +
+                                         [_c.c_void_p, _c.c_int, _c.c_int, _c.c_uint, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "tf_rank_pivotal_frame_sets_edits_plan": (_c.c_int, [_c.c_int] * 7 + [_c.c_void_p, _c.c_int, _c.c_int, _c.c_uint] +
+                                              [_c.c_int] * 3 + [_c.c_char_p, _c.c_size_t]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

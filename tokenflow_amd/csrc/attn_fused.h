@@ -41,10 +41,14 @@ extern thread_local int tf_plan_sets_note;
 TfFusedPlan tf_attn_fused_plan(const TfAttnSet* sets, int n_sets, int S, int Dh, int dtype, int flags);
 
 // One launch over every (set, branch, frame, head, query tile) problem.  No workspace, no pre-pass, no merge launch.
-// `win` (one set only; tf_ext_attn_fwd_windows): the bank branches of query frame i read the bank frames of window i,
+// `win` (tf_ext_attn_fwd_windows): the bank branches of query frame i read the bank frames of window i,
 // win[i] = first frame | frames << 16, sets[0].Kq entries that ride in the kernel arguments; plan token fused[..,win].
-// `frame_set` (one set only, instead of `win`; tf_ext_attn_fwd_frame_sets): the bank branches of query frame i read the bank
+// `frame_set` (instead of `win`; tf_ext_attn_fwd_frame_sets): the bank branches of query frame i read the bank
 // frames whose bits are set in frame_set[i], in ascending order; plan token fused[..,set].
+// Either table with n_sets > 1 (the parts of a windowed / frame-set multi-edit pass): every bank problem of every set reads entry
+// i of the ONE table, a source set (b0 = 0, nb = 1) ignores it; the bank sets must agree in Kq, q_frame0 and Kb (TF_ERR_SHAPE
+// otherwise).  Plan tokens fused[..,sets=N,win] / fused[..,sets=N,set].  The arithmetic of a (query, head) is that of the one-set
+// launches with the same KW and PREC.
 int tf_attn_fused_launch(const TfAttnSet* sets, int n_sets, int S, int Dh, float scale, int flags, int dtype,
                          const TfFusedPlan& plan, hipStream_t st, const unsigned* win = nullptr,
                          const uint64_t* frame_set = nullptr);

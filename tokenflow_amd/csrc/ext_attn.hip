@@ -657,12 +657,18 @@ static int attn_fwd_edits_masked(const char* name, const void* q, const void* k,
         }
         if (do_src) add(0, 0, 1, false);
         const int fl = base;   // no launch-wide TF_ATTN_INJECT: every set carries its own
+        // a windowed / frame-set part (tf_ext_attn_fwd_windows_edits_part, tf_ext_attn_fwd_frame_sets_edits_part): planned for the
+        // longest window / largest set, as the one-set windowed launch is, and launched under the ONE table all edits share
+        const int K_plan = wn ? wn->K_max : fs ? fs->K_max : K;
+        for (int i = 0; i < n_sets; ++i) sets[i].Kb = K_plan;
         const TfFusedPlan plan = tf_attn_fused_plan(sets, n_sets, S, Dh, dtype, fl);
+        for (int i = 0; i < n_sets; ++i) sets[i].Kb = K;
         // (the default mode decides per grid: where the joint grid leaves the fused kernel's range, the parts run as below)
         if (plan.use) {
             TF_ARG(Kq > 0 && q_frame0 >= 0 && q_frame0 + Kq <= K && K > 0 && S > 0 && H > 0, TF_ERR_SHAPE,
                    "%s: query frames [%d, %d) outside the %d-frame bank", name, q_frame0, q_frame0 + Kq, K);
-            return tf_attn_fused_launch(sets, n_sets, S, Dh, scale, fl, dtype, plan, reinterpret_cast<hipStream_t>(stream));
+            return tf_attn_fused_launch(sets, n_sets, S, Dh, scale, fl, dtype, plan, reinterpret_cast<hipStream_t>(stream),
+                                        do_bank && wn ? wn->win : nullptr, do_bank && fs ? fs->set : nullptr);
         }
     }
     // ONE pre-pass over the span of the streaming branches; key norms of every packed branch whose OWN keys a launch reads
@@ -1473,6 +1479,60 @@ extern "C" int tf_ext_attn_windows_edits_plan(int K, int Kq, int q_frame0, int S
     return rec.n;
 }
 
+// The bank part of a windowed multi-edit pass (include/tokenflow_hip.h): tf_ext_attn_fwd_windows_edits with TF_ATTN_BANK_ONLY
+// accepted and q / k dense or compact as in tf_ext_attn_fwd_edits_part -- what a frame-sharded rank would run over its
+// halo-extended receive buffer for all E edits at once.  The masked composition as a part call with the window table: where every
+// edit's bank part takes the fused small-problem kernel they share ONE launch under the one table (fused[..,sets=E,win]); the
+// streaming regime is the composition of tf_ext_attn_fwd_windows_edits without its source launches.  The source part of a
+// windowed pass is window-free: tf_ext_attn_fwd_edits_part(TF_ATTN_SOURCE_ONLY).
+extern "C" int tf_ext_attn_fwd_windows_edits_part(const void* q, const void* k, const void* v, void* out, int K, int Kq,
+                                                  int q_frame0, int S, int H, int Dh, int64_t ld, const int64_t* strides,
+                                                  float scale, int flags, int dtype, int n_edits, unsigned inject_mask,
+                                                  int qk_compact, const int* win_lo, const int* win_n, void* ws, size_t ws_bytes,
+                                                  void* stream) {
+    const char* const name = "tf_ext_attn_fwd_windows_edits_part";
+    TF_ARG(qk_compact == 0 || qk_compact == 1, TF_ERR_SHAPE, "%s: qk_compact=%d (0 or 1)", name, qk_compact);
+    if (!(flags & TF_ATTN_BANK_ONLY)) {   // without the flag the call IS tf_ext_attn_fwd_windows_edits (which refuses the source flag)
+        TF_ARG(!qk_compact || (flags & TF_ATTN_SOURCE_ONLY), TF_ERR_SHAPE,
+               "%s: qk_compact=1 without TF_ATTN_BANK_ONLY (the whole call reads dense q / k)", name);
+        return tf_ext_attn_fwd_windows_edits(q, k, v, out, K, Kq, q_frame0, S, H, Dh, ld, strides, scale, flags, dtype, n_edits,
+                                             inject_mask, win_lo, win_n, ws, ws_bytes, stream);
+    }
+    unsigned win[TF_MAX_WINDOW_FRAMES];
+    int K_max = 0;
+    bool full = true;
+    if (const int rc = windows_pack(name, K, Kq, q_frame0, win_lo, win_n, win, &K_max, &full)) return rc;
+    constexpr int REFUSED = TF_ATTN_SOURCE_ONLY | TF_ATTN_FOLD_SCALE | TF_ATTN_RUN_MULTI_V;
+    TF_ARG(!(flags & REFUSED), TF_ERR_SHAPE,
+           "%s: flags 0x%x -- TF_ATTN_SOURCE_ONLY (the source part of a windowed pass is tf_ext_attn_fwd_edits_part) / "
+           "TF_ATTN_FOLD_SCALE / TF_ATTN_RUN_MULTI_V have no windowed form", name, flags & REFUSED);
+    // (n_edits = 1: the masked composition is attn_fwd_core with the part flag and the window table: tf_ext_attn_fwd_windows_part)
+    const WinPart wn{win, K_max};
+    // every window = [0, K): tf_ext_attn_fwd_edits_part itself
+    return attn_fwd_edits_masked(name, q, k, v, out, K, Kq, q_frame0, S, H, Dh, ld, strides, scale, flags, dtype, n_edits,
+                                 inject_mask, ws, ws_bytes, stream, true, qk_compact, full ? nullptr : &wn);
+}
+
+// Launch plan of tf_ext_attn_fwd_windows_edits_part for dense tensors (q / k dense or compact: the plan does not depend on it).
+extern "C" int tf_ext_attn_windows_edits_part_plan(int K, int Kq, int q_frame0, int S, int H, int Dh, int n_edits,
+                                                   unsigned inject_mask, int qk_compact, int flags, int dtype, const int* win_lo,
+                                                   const int* win_n, char* buf, size_t len) {
+    TF_ARG(K > 0 && S > 0 && H > 0 && Kq > 0 && Kq <= K, TF_ERR_SHAPE, "tf_ext_attn_windows_edits_part_plan: K=%d Kq=%d S=%d H=%d",
+           K, Kq, S, H);
+    void* const ph = reinterpret_cast<void*>((uintptr_t)1 << 12);
+    const int64_t ld = (int64_t)H * Dh, fs = (int64_t)S * ld;
+    const int64_t strides[9] = {Kq * fs, fs, K * fs, fs, K * fs, fs, Kq * fs, fs, ld};
+    TfPlanRec rec{buf, len, 0, 0};
+    if (buf && len) buf[0] = 0;
+    tf_plan_rec = &rec;
+    const int rc = tf_ext_attn_fwd_windows_edits_part(ph, ph, ph, ph, K, Kq, q_frame0, S, H, Dh, ld, strides, 1.0f, flags, dtype,
+                                                      n_edits, inject_mask, qk_compact, win_lo, win_n, ph, (size_t)-1, nullptr);
+    tf_plan_rec = nullptr;
+    if (rc) return rc;
+    TF_ARG(rec.used < len, TF_ERR_WORKSPACE, "tf_ext_attn_windows_edits_part_plan: the plan needs %zu bytes", rec.used + 1);
+    return rec.n;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Frame-set keyframe bank (include/tokenflow_hip.h): the uncond / cond branches of query frame i attend to the keys of the bank
 // frames whose bits are set in sets[i], in ascending frame order.  A table of contiguous ranges IS tf_ext_attn_fwd_windows on
@@ -1645,5 +1705,60 @@ extern "C" int tf_ext_attn_frame_sets_edits_plan(int K, int Kq, int q_frame0, in
     tf_plan_rec = nullptr;
     if (rc) return rc;
     TF_ARG(rec.used < len, TF_ERR_WORKSPACE, "tf_ext_attn_frame_sets_edits_plan: the plan needs %zu bytes", rec.used + 1);
+    return rec.n;
+}
+
+// The bank part of a frame-set multi-edit pass (include/tokenflow_hip.h): tf_ext_attn_fwd_frame_sets_edits with TF_ATTN_BANK_ONLY
+// accepted and q / k dense or compact as in tf_ext_attn_fwd_edits_part -- what a frame-sharded rank would run over its
+// anchor-extended receive buffer for all E edits at once.  Where every edit's bank part takes the fused small-problem kernel they
+// share ONE launch under the one set table (fused[..,sets=E,set]).  A table of contiguous ranges is handed on as the equivalent
+// window table (tf_ext_attn_fwd_windows_edits_part; tf_ext_attn_fwd_edits_part where every range is the bank).  The source part of a
+// frame-set pass is set-free: tf_ext_attn_fwd_edits_part(TF_ATTN_SOURCE_ONLY).
+extern "C" int tf_ext_attn_fwd_frame_sets_edits_part(const void* q, const void* k, const void* v, void* out, int K, int Kq,
+                                                     int q_frame0, int S, int H, int Dh, int64_t ld, const int64_t* strides,
+                                                     float scale, int flags, int dtype, int n_edits, unsigned inject_mask,
+                                                     int qk_compact, const uint64_t* sets, void* ws, size_t ws_bytes,
+                                                     void* stream) {
+    const char* const name = "tf_ext_attn_fwd_frame_sets_edits_part";
+    TF_ARG(qk_compact == 0 || qk_compact == 1, TF_ERR_SHAPE, "%s: qk_compact=%d (0 or 1)", name, qk_compact);
+    if (!(flags & TF_ATTN_BANK_ONLY)) {   // without the flag the call IS tf_ext_attn_fwd_frame_sets_edits (which refuses the source flag)
+        TF_ARG(!qk_compact || (flags & TF_ATTN_SOURCE_ONLY), TF_ERR_SHAPE,
+               "%s: qk_compact=1 without TF_ATTN_BANK_ONLY (the whole call reads dense q / k)", name);
+        return tf_ext_attn_fwd_frame_sets_edits(q, k, v, out, K, Kq, q_frame0, S, H, Dh, ld, strides, scale, flags, dtype, n_edits,
+                                                inject_mask, sets, ws, ws_bytes, stream);
+    }
+    int win_lo[TF_MAX_WINDOW_FRAMES], win_n[TF_MAX_WINDOW_FRAMES], K_max = 0;
+    bool ranges = true;
+    if (const int rc = frame_sets_check(name, K, Kq, q_frame0, sets, win_lo, win_n, &K_max, &ranges)) return rc;
+    constexpr int REFUSED = TF_ATTN_SOURCE_ONLY | TF_ATTN_FOLD_SCALE | TF_ATTN_RUN_MULTI_V;
+    TF_ARG(!(flags & REFUSED), TF_ERR_SHAPE,
+           "%s: flags 0x%x -- TF_ATTN_SOURCE_ONLY (the source part of a frame-set pass is tf_ext_attn_fwd_edits_part) / "
+           "TF_ATTN_FOLD_SCALE / TF_ATTN_RUN_MULTI_V have no frame-set form", name, flags & REFUSED);
+    if (ranges)   // the windowed part's launches (a checked set table is a valid window table)
+        return tf_ext_attn_fwd_windows_edits_part(q, k, v, out, K, Kq, q_frame0, S, H, Dh, ld, strides, scale, flags, dtype, n_edits,
+                                                  inject_mask, qk_compact, win_lo, win_n, ws, ws_bytes, stream);
+    // (n_edits = 1: the masked composition is attn_fwd_core with the part flag and the set table: tf_ext_attn_fwd_frame_sets_part)
+    const SetPart fs{sets, K_max};
+    return attn_fwd_edits_masked(name, q, k, v, out, K, Kq, q_frame0, S, H, Dh, ld, strides, scale, flags, dtype, n_edits,
+                                 inject_mask, ws, ws_bytes, stream, true, qk_compact, nullptr, &fs);
+}
+
+// Launch plan of tf_ext_attn_fwd_frame_sets_edits_part for dense tensors (q / k dense or compact: the plan does not depend on it).
+extern "C" int tf_ext_attn_frame_sets_edits_part_plan(int K, int Kq, int q_frame0, int S, int H, int Dh, int n_edits,
+                                                      unsigned inject_mask, int qk_compact, int flags, int dtype,
+                                                      const uint64_t* sets, char* buf, size_t len) {
+    TF_ARG(K > 0 && S > 0 && H > 0 && Kq > 0 && Kq <= K, TF_ERR_SHAPE,
+           "tf_ext_attn_frame_sets_edits_part_plan: K=%d Kq=%d S=%d H=%d", K, Kq, S, H);
+    void* const ph = reinterpret_cast<void*>((uintptr_t)1 << 12);
+    const int64_t ld = (int64_t)H * Dh, fs = (int64_t)S * ld;
+    const int64_t strides[9] = {Kq * fs, fs, K * fs, fs, K * fs, fs, Kq * fs, fs, ld};
+    TfPlanRec rec{buf, len, 0, 0};
+    if (buf && len) buf[0] = 0;
+    tf_plan_rec = &rec;
+    const int rc = tf_ext_attn_fwd_frame_sets_edits_part(ph, ph, ph, ph, K, Kq, q_frame0, S, H, Dh, ld, strides, 1.0f, flags, dtype,
+                                                         n_edits, inject_mask, qk_compact, sets, ph, (size_t)-1, nullptr);
+    tf_plan_rec = nullptr;
+    if (rc) return rc;
+    TF_ARG(rec.used < len, TF_ERR_WORKSPACE, "tf_ext_attn_frame_sets_edits_part_plan: the plan needs %zu bytes", rec.used + 1);
     return rec.n;
 }

@@ -125,8 +125,38 @@ struct FusedParamsSet {
     float lag;
     uint64_t fset[TF_MAX_WINDOW_FRAMES];   // query frame i: bit j = its bank branches read bank frame j
 };
+
+// The parts of a windowed / frame-set multi-edit pass (tf_ext_attn_fwd_windows_edits_part, tf_ext_attn_fwd_frame_sets_edits_part):
+// up to 1 + TF_MAX_EDITS sets under ONE table.  Every bank problem (branch > 0) of every set reads entry `f` of it -- all edits
+// share the windows -- so the table is valid only where all bank sets agree in Kq, q_frame0 and Kb (tf_attn_fused_launch checks
+// it); a source set reads its own frame and never looks at the table.  Per-set injection state as in FusedParamsN.  Types of
+// their own again: every other launch keeps its parameter block and its code.  9 x 144 B of sets + 36 B + the table: 1.6 KiB
+// (windows) / 1.9 KiB (sets) of the 4 KiB kernel-argument segment.
+struct FusedParamsWinN {
+    static constexpr int MAX_SETS = 1 + TF_MAX_EDITS;
+    FusedSet set[MAX_SETS];
+    int n_sets, S, nQT, tpf;
+    unsigned tpf_magic;
+    int inject, out_f32;
+    float c;
+    float lag;
+    unsigned win[TF_MAX_WINDOW_FRAMES];   // as FusedParamsWin::win
+};
+struct FusedParamsSetN {
+    static constexpr int MAX_SETS = 1 + TF_MAX_EDITS;
+    FusedSet set[MAX_SETS];
+    int n_sets, S, nQT, tpf;
+    unsigned tpf_magic;
+    int inject, out_f32;
+    float c;
+    float lag;
+    uint64_t fset[TF_MAX_WINDOW_FRAMES];   // as FusedParamsSet::fset
+};
+static_assert(sizeof(FusedParamsWinN) <= 2048 && sizeof(FusedParamsSetN) <= 2048, "kernel-argument segment");
 template <typename P>
-constexpr bool is_fset = std::is_same<P, FusedParamsSet>::value;
+constexpr bool is_win = std::is_same<P, FusedParamsWin>::value || std::is_same<P, FusedParamsWinN>::value;
+template <typename P>
+constexpr bool is_fset = std::is_same<P, FusedParamsSet>::value || std::is_same<P, FusedParamsSetN>::value;
 
 __device__ __forceinline__ float max_xor32(float x) {
     const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
@@ -178,7 +208,7 @@ __device__ __forceinline__ Problem decode_problem(const P& p) {
     pr.bq = (inject && pr.b > 0) ? 0 : pr.b;   // branch whose q and k are used (tokenflow_utils.py:124-130)
     pr.f_lo = pr.b == 0 ? st.q_frame0 + pr.f : 0;
     pr.n_fr = pr.b == 0 ? 1 : st.Kb;
-    if constexpr (std::is_same<P, FusedParamsWin>::value) {   // a bank problem reads its query frame's window
+    if constexpr (is_win<P>) {   // a bank problem reads its query frame's window
         if (pr.b > 0) {
             const unsigned w = p.win[pr.f];
             pr.f_lo = (int)(w & 0xffffu), pr.n_fr = (int)(w >> 16);
@@ -694,6 +724,8 @@ __global__ __launch_bounds__(64 * KW, 1) void ext_attn_fused_wp_kernel(P p) {
 // tf_plan_sets_note, whatever their number)
 template <typename P>
 bool fused_note(const P& p, int qw, int kw, int qb, int prec) {
+    if (P::MAX_SETS > 2 && (is_win<P> || is_fset<P>))   // several sets under one table
+        return tf_plan_note("fused[qw=%d,kw=%d,qb=%d,prec=%d,sets=%d,%s]", qw, kw, qb, prec, p.n_sets, is_win<P> ? "win" : "set");
     if (p.n_sets > 2 || tf_plan_sets_note) return tf_plan_note("fused[qw=%d,kw=%d,qb=%d,prec=%d,sets=%d]", qw, kw, qb, prec, p.n_sets);
     if (std::is_same<P, FusedParamsWin>::value) return tf_plan_note("fused[qw=%d,kw=%d,qb=%d,prec=%d,win]", qw, kw, qb, prec);
     if (is_fset<P>) return tf_plan_note("fused[qw=%d,kw=%d,qb=%d,prec=%d,set]", qw, kw, qb, prec);
@@ -832,10 +864,13 @@ static int fused_launch_sets(const TfAttnSet* sets, int n_sets, int S, int Dh, f
                              const TfFusedPlan& plan, int inject0, hipStream_t st, const unsigned* win = nullptr,
                              const uint64_t* frame_set = nullptr) {
     P p{};
-    if constexpr (std::is_same<P, FusedParamsWin>::value)
-        for (int i = 0; i < sets[0].Kq; ++i) p.win[i] = win[i];
+    int tab_kq = sets[0].Kq;   // entries of the table: the query frames of the bank sets (they agree where there are several)
+    for (int i = n_sets - 1; i >= 0; --i)
+        if (sets[i].b0 + sets[i].nb > 1) tab_kq = sets[i].Kq;
+    if constexpr (is_win<P>)
+        for (int i = 0; i < tab_kq; ++i) p.win[i] = win[i];
     if constexpr (is_fset<P>)
-        for (int i = 0; i < sets[0].Kq; ++i) p.fset[i] = frame_set[i];
+        for (int i = 0; i < tab_kq; ++i) p.fset[i] = frame_set[i];
     p.n_sets = n_sets;
     p.S = S;
     p.nQT = (S + 32 * plan.qw * plan.qb - 1) / (32 * plan.qw * plan.qb);
@@ -871,6 +906,25 @@ static int fused_launch_sets(const TfAttnSet* sets, int n_sets, int S, int Dh, f
 int tf_attn_fused_launch(const TfAttnSet* sets, int n_sets, int S, int Dh, float scale, int flags, int dtype,
                          const TfFusedPlan& plan, hipStream_t st, const unsigned* win, const uint64_t* frame_set) {
     TF_ARG(sets && n_sets >= 1 && n_sets <= 1 + TF_MAX_EDITS, TF_ERR_SHAPE, "tf_ext_attn_fwd(fused): %d tensor sets", n_sets);
+    if ((win || frame_set) && n_sets > 1) {
+        // several sets under ONE table: every bank problem reads entry f of it, so the bank sets must agree in what the entries
+        // mean (query frames, their bank index, the bank); the injection state is the set's
+        TF_ARG(!(win && frame_set), TF_ERR_SHAPE, "tf_ext_attn_fwd(fused): a window table beside a frame-set table");
+        const TfAttnSet* b = nullptr;
+        for (int i = 0; i < n_sets; ++i) {
+            const TfAttnSet& a = sets[i];
+            if (a.b0 + a.nb <= 1) continue;   // a source set reads its own frame whatever the table
+            TF_ARG(!b || (a.Kq == b->Kq && a.q_frame0 == b->q_frame0 && a.Kb == b->Kb), TF_ERR_SHAPE,
+                   "tf_ext_attn_fwd(fused): one table serves bank sets that agree in Kq, q_frame0 and Kb (set %d: %d, %d, %d)", i,
+                   a.Kq, a.q_frame0, a.Kb);
+            if (!b) b = &a;
+        }
+        TF_ARG(b && b->Kq >= 1 && b->Kq <= TF_MAX_WINDOW_FRAMES, TF_ERR_SHAPE,
+               "tf_ext_attn_fwd(fused): a table serves bank sets of at most %d query frames", TF_MAX_WINDOW_FRAMES);
+        TF_ARG(win || b->Kb <= 64, TF_ERR_SHAPE, "tf_ext_attn_fwd(fused): a frame-set table serves at most 64 bank frames");
+        return win ? fused_launch_sets<FusedParamsWinN>(sets, n_sets, S, Dh, scale, flags, dtype, plan, 0, st, win)
+                   : fused_launch_sets<FusedParamsSetN>(sets, n_sets, S, Dh, scale, flags, dtype, plan, 0, st, nullptr, frame_set);
+    }
     if (frame_set) {
         TF_ARG(!win && n_sets == 1 && sets[0].Kq <= TF_MAX_WINDOW_FRAMES, TF_ERR_SHAPE,
                "tf_ext_attn_fwd(fused): a frame-set table serves one set of at most %d query frames", TF_MAX_WINDOW_FRAMES);

@@ -338,3 +338,110 @@ extern "C" int tf_frame_set_halo_pack(const void* const* slabs, const int64_t* f
     TF_LAUNCH_CHECK("tf_frame_set_halo_pack");
     return 0;
 }
+
+// ---------------------------------------------------------------------------------------------
+// Halo pack of a windowed / anchored frame shard that carries a MULTI-EDIT batch (tf_edit_halo_pack): the work of
+// tf_frame_set_halo_pack -- per peer a 64-bit mask over the local frames, send rows in ascending member order -- for up to
+// 4 * TF_MAX_EDITS slabs (the compact k slots and two value slabs per edit), and, in extra workgroup columns behind the packing
+// ones (as head_pack_norm_kernel appends its norm workgroups), the copy of nq compact q slabs into a dense staging region
+// [nq][Kl][S][D]: a mixed injection mask reads the source's q beside the non-injecting edits' and the part call addresses them
+// with ONE branch stride.  A plain window's ranges are contiguous masks, so this one entry serves both passes.
+namespace {
+
+constexpr int MAX_SLABS_E = 4 * TF_MAX_EDITS;
+constexpr int MAX_Q_SLABS = 1 + 2 * TF_MAX_EDITS;
+
+// Column blockIdx.x < rows: ONE send row, as frame_set_halo_pack_kernel.  Column rows + c: frame c % Kl of q slab c / Kl.
+__global__ __launch_bounds__(256) void edit_halo_pack_kernel(SlabPtrs<MAX_SLABS_E> sl, unsigned char* __restrict__ send, HaloSets sg,
+                                                             int ns, int S, int d_pieces, int64_t ld_bytes,
+                                                             SlabPtrs<MAX_Q_SLABS> ql, unsigned char* __restrict__ q_stage, int Kl,
+                                                             int64_t ld_q_bytes) {
+    const int rows = sg.row0[sg.n];
+    const int per_slab = S * d_pieces;
+    if ((int)blockIdx.x >= rows) {
+        const int c = (int)blockIdx.x - rows;
+        const int i = c / Kl, f = c - i * Kl;
+        const unsigned char* src = ql.src[i] + f * ql.fs[i];
+        unsigned char* dst = q_stage + (int64_t)c * per_slab * 16;
+        for (int t = (int)blockIdx.y * 256 + threadIdx.x; t < per_slab; t += (int)gridDim.y * 256) {
+            const int s = t / d_pieces, pc = t - s * d_pieces;
+            st16(dst + (int64_t)t * 16, ld16(src + (int64_t)s * ld_q_bytes + (int64_t)pc * 16));
+        }
+        return;
+    }
+    const int r = (int)blockIdx.x;
+    int seg = 0;
+    while (seg + 1 < sg.n && r >= sg.row0[seg + 1]) ++seg;
+    uint64_t m = sg.mask[seg];
+    for (int j = r - sg.row0[seg]; j > 0; --j) m &= m - 1;   // drop the j lowest members
+    const int f = __builtin_ctzll(m);
+    const int64_t per_row = (int64_t)ns * per_slab;
+    unsigned char* dst = send + (int64_t)r * per_row * 16;
+    for (int64_t g = (int64_t)blockIdx.y * 256 + threadIdx.x; g < per_row; g += (int64_t)gridDim.y * 256) {
+        const int i = (int)(g / per_slab);
+        const int t = (int)(g - (int64_t)i * per_slab);
+        const int s = t / d_pieces, pc = t - s * d_pieces;
+        const unsigned char* src = sl.src[i] + f * sl.fs[i] + (int64_t)s * ld_bytes + (int64_t)pc * 16;
+        st16(dst + g * 16, ld16(src));
+    }
+}
+
+}  // namespace
+
+extern "C" int tf_edit_halo_pack(const void* const* slabs, const int64_t* frame_strides, int ns, void* send, int n_peer,
+                                 const uint64_t* masks, const void* const* q_slabs, const int64_t* q_frame_strides, int nq,
+                                 void* q_stage, int Kl, int S, int D, int64_t ld, int64_t ld_q, int dtype, void* stream) {
+    const char* const name = "tf_edit_halo_pack";
+    TF_ARG(slabs && frame_strides && send && masks, TF_ERR_NULL, "%s: null pointer", name);
+    TF_ARG(dtype == TF_BF16 || dtype == TF_F16, TF_ERR_DTYPE, "%s: dtype %d (bf16/f16 only)", name, dtype);
+    TF_ARG(ns >= 1 && ns <= MAX_SLABS_E && n_peer >= 1 && n_peer <= TF_MAX_WORLD && Kl >= 1 && Kl <= 64 && S >= 1 && D >= 8 &&
+               D % 8 == 0 && ld >= D && ld % 8 == 0 && (int64_t)S * (D / 8) < ((int64_t)1 << 30),
+           TF_ERR_SHAPE, "%s: ns=%d peers=%d Kl=%d S=%d D=%d ld=%lld (D and ld multiples of 8 elements, ld >= D, at most %d "
+           "slabs, %d peers and 64 local frames)", name, ns, n_peer, Kl, S, D, (long long)ld, MAX_SLABS_E, TF_MAX_WORLD);
+    TF_ARG(nq >= 0 && nq <= MAX_Q_SLABS, TF_ERR_SHAPE, "%s: nq=%d (0 .. %d compact q slabs)", name, nq, MAX_Q_SLABS);
+    HaloSets sg{};
+    sg.n = n_peer;
+    int rows = 0;
+    for (int p = 0; p < n_peer; ++p) {
+        TF_ARG(Kl == 64 || !(masks[p] >> Kl), TF_ERR_SHAPE, "%s: mask %d = 0x%llx has bits at or above the %d local keyframes", name,
+               p, (unsigned long long)masks[p], Kl);
+        sg.row0[p] = rows, sg.mask[p] = masks[p];
+        rows += __builtin_popcountll(masks[p]);
+    }
+    sg.row0[n_peer] = rows;
+    TF_ARG(tf_aligned16(send), TF_ERR_ALIGN, "%s: send buffer not 16-byte aligned", name);
+    for (int i = 0; i < ns; ++i) {
+        TF_ARG(slabs[i], TF_ERR_NULL, "%s: slab %d is null", name, i);
+        TF_ARG(tf_aligned16(slabs[i]) && (frame_strides[i] * 2) % 16 == 0, TF_ERR_ALIGN, "%s: slab %d not 16-byte aligned", name, i);
+        // (a frame holds S token rows: the last byte read is inside the slab's Kl frames)
+        TF_ARG(frame_strides[i] >= (int64_t)(S - 1) * ld + D || Kl == 1, TF_ERR_SHAPE, "%s: slab %d: frame stride %lld below a frame",
+               name, i, (long long)frame_strides[i]);
+    }
+    if (nq) {
+        TF_ARG(q_slabs && q_frame_strides && q_stage, TF_ERR_NULL, "%s: null q pointer", name);
+        TF_ARG(ld_q >= D && ld_q % 8 == 0, TF_ERR_SHAPE, "%s: ld_q=%lld (a multiple of 8 elements, >= D)", name, (long long)ld_q);
+        TF_ARG(tf_aligned16(q_stage), TF_ERR_ALIGN, "%s: q staging region not 16-byte aligned", name);
+        for (int i = 0; i < nq; ++i) {
+            TF_ARG(q_slabs[i], TF_ERR_NULL, "%s: q slab %d is null", name, i);
+            TF_ARG(tf_aligned16(q_slabs[i]) && (q_frame_strides[i] * 2) % 16 == 0, TF_ERR_ALIGN, "%s: q slab %d not 16-byte aligned",
+                   name, i);
+            TF_ARG(q_frame_strides[i] >= (int64_t)(S - 1) * ld_q + D || Kl == 1, TF_ERR_SHAPE,
+                   "%s: q slab %d: frame stride %lld below a frame", name, i, (long long)q_frame_strides[i]);
+        }
+    }
+    const int cols = rows + nq * Kl;
+    if (cols == 0) return 0;   // nobody reads this rank's frames, it sends none to itself and stages no q: nothing to launch
+    const int d_pieces = D * 2 / 16;
+    const int64_t per_row = (int64_t)ns * S * d_pieces;
+    // about 2048 workgroups in all (256 CUs x 8 resident), at least one and at most a row's worth per column
+    int64_t ny = (2048 + cols - 1) / cols;
+    if (ny > (per_row + 255) / 256) ny = (per_row + 255) / 256;
+    SlabPtrs<MAX_Q_SLABS> ql{};
+    if (nq) ql = slab_ptrs<MAX_Q_SLABS>(q_slabs, q_frame_strides, nq, 2);
+    hipLaunchKernelGGL(edit_halo_pack_kernel, dim3((unsigned)cols, (unsigned)ny), dim3(256), 0,
+                       reinterpret_cast<hipStream_t>(stream), slab_ptrs<MAX_SLABS_E>(slabs, frame_strides, ns, 2),
+                       static_cast<unsigned char*>(send), sg, ns, S, d_pieces, ld * 2, ql, static_cast<unsigned char*>(q_stage), Kl,
+                       ld_q * 2);
+    TF_LAUNCH_CHECK("tf_edit_halo_pack");
+    return 0;
+}

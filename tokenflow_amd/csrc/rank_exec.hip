@@ -1353,3 +1353,245 @@ extern "C" int tf_rank_pivotal_edits_plan(int world, int rank, int K, int S, int
     TF_ARG(rec.used < len, TF_ERR_WORKSPACE, "tf_rank_pivotal_edits_plan: the plan needs %zu bytes", rec.used + 1);
     return rec.n;
 }
+
+// ---------------------------------------------------------------------------------------------
+// One rank's pivotal pass of a MULTI-EDIT batch over a windowed / anchored bank (include/tokenflow_hip.h): the schedule of
+// tf_rank_pivotal_frame_sets with the payload of tf_rank_pivotal_edits(TF_RANK_BANK) -- per block ONE pack, ONE sparse exchange,
+// ONE bank part over all E edits (tf_ext_attn_fwd_windows_edits_part / tf_ext_attn_fwd_frame_sets_edits_part), the source part
+// beside the exchange.  The geometry does not depend on E: window_geometry / frame_set_geometry as in the single-edit calls.
+namespace {
+
+struct WinEditsLayout {   // exchange buffers of one call inside the caller's workspace; slab counts at their largest
+    size_t send, recv, stage, ws_bank, ws_src, total;
+    size_t ws_bank_bytes, ws_src_bytes;
+};
+
+WinEditsLayout window_edits_layout(const tf_rank* rk, const WinGeom& g, int S, int H, int Dh, int E, int dtype) {
+    const size_t eb = 2, D = (size_t)H * Dh;
+    WinEditsLayout L{};
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        const size_t at = off;
+        off += up256(bytes);
+        return at;
+    };
+    // [k slots | v_1 .. v_2E]: 4E slabs where no edit injects; the compact q of a mixed mask is staged (< 2E slots)
+    L.send = take((size_t)g.send_total * 4 * E * S * D * eb);
+    L.recv = take((size_t)g.F * 4 * E * S * D * eb);
+    L.stage = take((size_t)rk->Kl * 2 * E * S * D * eb);
+    // the bank part and the source part may run concurrently: a workspace each
+    L.ws_bank_bytes = tf_ext_attn_edits_workspace_bytes(g.F, S, H, Dh, E, dtype);
+    L.ws_src_bytes = tf_ext_attn_edits_workspace_bytes(rk->Kl, S, H, Dh, E, dtype);
+    L.ws_bank = take(L.ws_bank_bytes);
+    L.ws_src = take(L.ws_src_bytes);
+    L.total = off;
+    return L;
+}
+
+// the geometry of a call: the anchored one, or -- without anchors -- the windowed one with its segments as contiguous masks
+bool window_edits_geometry(const tf_rank* rk, int R, const int* anc, int na, SetGeom* G) {
+    if (na) return frame_set_geometry(rk, R, anc, na, G);
+    *G = SetGeom{};
+    G->w = window_geometry(rk, R);
+    G->q_frame0 = G->w.hl;
+    for (int p = 0; p < rk->world; ++p) {
+        const int n = G->w.seg_n[p];
+        G->send_mask[p] = n ? (n == 64 ? ~(uint64_t)0 : ((uint64_t)1 << n) - 1) << G->w.seg_f0[p] : 0;
+    }
+    return G->w.F < (1 << 16);
+}
+
+}  // namespace
+
+extern "C" size_t tf_rank_pivotal_frame_sets_edits_workspace_bytes(const tf_rank* rk, int S, int H, int Dh, int dtype, int radius,
+                                                                   const int* anchors, int n_anchors, int n_edits) {
+    if (n_edits < 1 || n_edits > TF_MAX_EDITS) return 0;
+    // never below either parent's for the same arguments, 0 for what either refuses
+    const size_t sets = tf_rank_pivotal_frame_sets_workspace_bytes(rk, S, H, Dh, dtype, radius, anchors, n_anchors);
+    if (!sets) return 0;
+    const size_t edits = tf_rank_pivotal_edits_workspace_bytes(rk, S, H, Dh, n_edits, dtype);
+    if (!edits) return 0;
+    const size_t base = sets > edits ? sets : edits;
+    if (n_edits == 1 || rk->world == 1 || radius >= rk->K - 1 || rk->Kl > TF_MAX_WINDOW_FRAMES) return base;
+    int anc[MAX_ANCHORS], na = 0;
+    if (n_anchors) sorted_anchors("", rk->K, anchors, n_anchors, anc, &na);   // (validated by the size query above)
+    SetGeom G;
+    if (!window_edits_geometry(rk, radius, anc, na, &G)) return 0;
+    const size_t own = window_edits_layout(rk, G.w, S, H, Dh, n_edits, dtype).total;
+    return own > base ? own : base;
+}
+
+extern "C" int tf_rank_pivotal_frame_sets_edits(tf_rank* rk, const void* q, const void* k, const void* v, const int64_t* st_in,
+                                                void* piv_ext, float* inv_ext, void* kfo_ext, int S, int H, int Dh, float scale,
+                                                int flags, int dtype, int mode, int slot, int radius, const int* anchors,
+                                                int n_anchors, int n_edits, unsigned inject_mask, void* ws, size_t ws_bytes,
+                                                void* stream) {
+    const char* const fn = "tf_rank_pivotal_frame_sets_edits";
+    const bool no_halo = (mode & TF_RANK_NO_HALO) != 0, want_inv = (mode & TF_RANK_INV_NORM) != 0;
+    const int mods = mode & (TF_RANK_NO_HALO | TF_RANK_INV_NORM), base = mode & ~(TF_RANK_NO_HALO | TF_RANK_INV_NORM);
+    // ---- arguments first: nothing below this block's end has touched the device
+    TF_ARG(rk && q && k && v && st_in && kfo_ext && ws && (no_halo || (piv_ext && inv_ext)) && (anchors || n_anchors == 0),
+           TF_ERR_NULL, "%s: null pointer", fn);
+    TF_ARG(n_anchors >= 0 && n_anchors <= MAX_ANCHORS, TF_ERR_SHAPE, "%s: %d anchors (0 .. %d)", fn, n_anchors, MAX_ANCHORS);
+    TF_ARG(n_edits >= 1 && n_edits <= TF_MAX_EDITS, TF_ERR_SHAPE, "%s: n_edits=%d (1 .. %d)", fn, n_edits, TF_MAX_EDITS);
+    TF_ARG(!(flags & TF_ATTN_INJECT), TF_ERR_SHAPE, "%s: TF_ATTN_INJECT beside a mask (the mask is the injection state)", fn);
+    TF_ARG(!(inject_mask >> n_edits), TF_ERR_SHAPE, "%s: inject_mask=0x%x has bits at or above n_edits=%d", fn, inject_mask,
+           n_edits);
+    TF_ARG(!(flags & (TF_ATTN_BANK_ONLY | TF_ATTN_SOURCE_ONLY)), TF_ERR_SHAPE, "%s: the part flags are the executor's own", fn);
+    TF_ARG(dtype == TF_BF16 || dtype == TF_F16, TF_ERR_DTYPE, "%s: dtype %d (bf16/f16 only)", fn, dtype);
+    TF_ARG(radius >= 0, TF_ERR_SHAPE, "%s: radius %d (>= 0)", fn, radius);
+    TF_ARG(base == TF_RANK_BANK, TF_ERR_SHAPE,
+           "%s: mode %d (a windowed multi-edit pass has the bank form only: TF_RANK_BANK with TF_RANK_NO_HALO / TF_RANK_INV_NORM)",
+           fn, base);
+    TF_ARG(slot >= 0 && slot < TF_RANK_SLOTS, TF_ERR_SHAPE, "%s: slot %d outside [0, %d)", fn, slot, TF_RANK_SLOTS);
+    TF_ARG(!(want_inv && no_halo), TF_ERR_SHAPE, "%s: TF_RANK_INV_NORM needs the propagation state (no TF_RANK_NO_HALO)", fn);
+    int anc[MAX_ANCHORS], na = 0;
+    if (const int rc = sorted_anchors(fn, rk->K, anchors, n_anchors, anc, &na)) return rc;
+    if (n_edits == 1)   // one edit: the single-edit anchored / windowed pass -- the same launches, the same bits
+        return tf_rank_pivotal_frame_sets(rk, q, k, v, st_in, piv_ext, inv_ext, kfo_ext, S, H, Dh, scale,
+                                          flags | (inject_mask ? TF_ATTN_INJECT : 0), dtype, mode, slot, radius, anchors, n_anchors,
+                                          ws, ws_bytes, stream);
+    if (radius >= rk->K - 1)   // every window is the whole bank: the multi-edit bank pass whatever the anchors
+        return tf_rank_pivotal_edits(rk, q, k, v, st_in, piv_ext, inv_ext, kfo_ext, S, H, Dh, scale, flags, dtype,
+                                     TF_RANK_BANK | mods, slot, n_edits, inject_mask, ws, ws_bytes, stream);
+    TF_ARG(rk->Kl <= TF_MAX_WINDOW_FRAMES, TF_ERR_SHAPE, "%s: %d local keyframes (at most %d carry a window or set)", fn, rk->Kl,
+           TF_MAX_WINDOW_FRAMES);
+    TF_ARG(!(flags & TF_ATTN_FOLD_SCALE), TF_ERR_SHAPE, "%s: TF_ATTN_FOLD_SCALE has no windowed form", fn);
+    SetGeom G;
+    TF_ARG(window_edits_geometry(rk, radius, anc, na, &G), TF_ERR_SHAPE,
+           "%s: the extended bank of rank %d exceeds %d frames (anchors: a set is a 64-bit mask; none: below 65536)", fn, rk->rank,
+           na ? 64 : 65535);
+    const size_t ws_need =
+        tf_rank_pivotal_frame_sets_edits_workspace_bytes(rk, S, H, Dh, dtype, radius, anchors, n_anchors, n_edits);
+    TF_ARG(ws_need, TF_ERR_SHAPE, "%s: S=%d H=%d Dh=%d", fn, S, H, Dh);
+    TF_ARG(ws_bytes >= ws_need, TF_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", fn, ws_bytes, ws_need);
+
+    const int E = n_edits, B = 1 + 2 * E;
+    const int W = rk->world, Kl = rk->Kl, K = rk->K, o = (W > 1 && !no_halo) ? 1 : 0;
+    const int64_t D = (int64_t)H * Dh, SD = (int64_t)S * D;
+    const int64_t q_bs = st_in[0], q_fs = st_in[1], k_bs = st_in[2], k_fs = st_in[3], v_bs = st_in[4], v_fs = st_in[5],
+                  ld_q = st_in[6], ld = st_in[7];
+    typedef unsigned short El;   // any 16-bit element: only pointer arithmetic happens here
+    const El* qe = static_cast<const El*>(q);
+    const El* ke = static_cast<const El*>(k);
+    const El* ve = static_cast<const El*>(v);
+    El* kfo = static_cast<El*>(kfo_ext);
+    El* piv = static_cast<El*>(piv_ext);
+    unsigned char* wsb = static_cast<unsigned char*>(ws);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int64_t o_bs = (int64_t)(Kl + o) * SD;   // branch stride of the halo-extended attention output
+    El* out_loc = kfo + (int64_t)o * SD;           // its local slots
+    if (!no_halo) rk->halo_set[slot] = false;
+    // 0. the inverse norms: a launch of their own (the halo pack kernel carries none)
+    if (want_inv)
+        if (const int rc = do_inv_norm(piv + (int64_t)o * SD, inv_ext + (int64_t)o * S, (int64_t)Kl * S, (int)D, dtype, stream))
+            return rc;
+    const int64_t loc_strides[9] = {q_bs, q_fs, k_bs, k_fs, v_bs, v_fs, o_bs, SD, ld_q};
+    if (W == 1) {   // one rank: the single-GPU multi-edit call straight into kfo_ext (with anchors K <= 64 there)
+        if (na)
+            return tf_ext_attn_fwd_frame_sets_edits(q, k, v, out_loc, K, K, 0, S, H, Dh, ld, loc_strides, scale, flags, dtype, E,
+                                                    inject_mask, G.sets, ws, ws_bytes, stream);
+        return tf_ext_attn_fwd_windows_edits(q, k, v, out_loc, K, K, 0, S, H, Dh, ld, loc_strides, scale, flags, dtype, E,
+                                             inject_mask, G.w.win_lo, G.w.win_n, ws, ws_bytes, stream);
+    }
+    const WinEditsLayout L = window_edits_layout(rk, G.w, S, H, Dh, E, dtype);
+    El* send = reinterpret_cast<El*>(wsb + L.send);
+    El* recv = reinterpret_cast<El*>(wsb + L.recv);
+    // the compact q / k layout of tf_ext_attn_fwd_edits_part: slot 0 the source where some edit injects, then (uncond, cond) of
+    // every edit that does not, ascending; b0 = the first slot that exists
+    int slots[1 + 2 * TF_MAX_EDITS], nq = 0;
+    if (inject_mask) slots[nq++] = 0;
+    for (int e = 0; e < E; ++e)
+        if (!((inject_mask >> e) & 1u)) slots[nq++] = 1 + 2 * e, slots[nq++] = 2 + 2 * e;
+    const int b0 = inject_mask ? 0 : 1;
+    const bool mixed = inject_mask && nq > 1;   // some edits inject, some do not
+    auto slab = [](const El* buf, int64_t first_slab, int first_branch, int64_t unit) {
+        return reinterpret_cast<const El*>(reinterpret_cast<uintptr_t>(buf) +
+                                           (uintptr_t)((first_slab - first_branch) * unit * (int64_t)sizeof(El)));
+    };
+    // 1. ONE pack of what PEERS read: the compact k slots and the 2E value slabs, per peer the members of its mask in ascending
+    //    order; the source's v and every q stay at home.  Under a mixed mask the same launch copies the compact q slots into the
+    //    staging region [nq][Kl][S][D] (the dense q IS the compact layout otherwise)
+    const void* slabs[4 * TF_MAX_EDITS];
+    int64_t fss[4 * TF_MAX_EDITS];
+    const int ns = nq + 2 * E;
+    for (int i = 0; i < nq; ++i) slabs[i] = ke + slots[i] * k_bs, fss[i] = k_fs;
+    for (int j = 0; j < 2 * E; ++j) slabs[nq + j] = ve + (1 + j) * v_bs, fss[nq + j] = v_fs;
+    const void* qs[1 + 2 * TF_MAX_EDITS];
+    int64_t qfs[1 + 2 * TF_MAX_EDITS];
+    const El* qp = qe;
+    int64_t cq_bs = q_bs, cq_fs = q_fs, cq_ld = ld_q;
+    El* stage = reinterpret_cast<El*>(wsb + L.stage);
+    if (mixed) {
+        for (int i = 0; i < nq; ++i) qs[i] = qe + slots[i] * q_bs, qfs[i] = q_fs;
+        qp = stage, cq_bs = (int64_t)Kl * SD, cq_fs = SD, cq_ld = D;
+    }
+    if (!tf_plan_note("edit_pack[ns=%d,nq=%d]", ns, mixed ? nq : 0))
+        if (const int rc = tf_edit_halo_pack(slabs, fss, ns, send, W, G.send_mask, mixed ? qs : nullptr, mixed ? qfs : nullptr,
+                                             mixed ? nq : 0, mixed ? stage : nullptr, Kl, S, (int)D, ld, ld_q, dtype, stream))
+            return rc;
+    // 2. the source part of the local frames (table-free), on the auxiliary compute stream: forked behind the pack, in FRONT of
+    //    the exchange, joined behind the bank part.  TOKENFLOW_RANK_SRC_AUX=0: in line behind the exchange (a recorded plan lists
+    //    that order)
+    auto source_part = [&](hipStream_t on) {
+        return tf_ext_attn_fwd_edits_part(q, k, v, out_loc, Kl, Kl, 0, S, H, Dh, ld, loc_strides, scale,
+                                          flags | TF_ATTN_SOURCE_ONLY, dtype, E, inject_mask, 0, wsb + L.ws_src, L.ws_src_bytes,
+                                          on);
+    };
+    const bool fork = src_aux_enabled() && !tf_plan_rec;
+    if (fork) {
+        if (const int rc = order(rk, st, rk->as, fn)) return rc;
+        if (const int rc = source_part(rk->as)) return rc;
+    }
+    // 3. ONE sparse exchange on the caller's stream: the receive buffer is the extended bank in ascending order
+    if (const int rc = do_a2a_rows(rk, send, recv, G.w, ns, SD, dtype, st)) return rc;
+    if (!fork)
+        if (const int rc = source_part(st)) return rc;
+    // 4. the bank part of ALL edits over the receive buffer [F][ns][S][D] in place: q / k compact, v and out addressed as
+    //    [source | uncond_1 | cond_1 | ...]; no anchors: the windows form, anchors: the set form
+    const int64_t fs_r = ns * SD;
+    const El* kb = slab(recv, 0, b0, SD);
+    const El* vb = slab(recv, nq, 1, SD);
+    const int64_t strides[9] = {cq_bs, cq_fs, SD, fs_r, SD, fs_r, o_bs, SD, cq_ld};
+    if (na) {
+        if (const int rc = tf_ext_attn_fwd_frame_sets_edits_part(qp, kb, vb, out_loc, G.w.F, Kl, G.q_frame0, S, H, Dh, D, strides,
+                                                                 scale, flags | TF_ATTN_BANK_ONLY, dtype, E, inject_mask, 1, G.sets,
+                                                                 wsb + L.ws_bank, L.ws_bank_bytes, stream))
+            return rc;
+    } else if (const int rc = tf_ext_attn_fwd_windows_edits_part(qp, kb, vb, out_loc, G.w.F, Kl, G.w.hl, S, H, Dh, D, strides, scale,
+                                                                 flags | TF_ATTN_BANK_ONLY, dtype, E, inject_mask, 1, G.w.win_lo,
+                                                                 G.w.win_n, wsb + L.ws_bank, L.ws_bank_bytes, stream)) {
+        return rc;
+    }
+    // 5. join
+    if (fork)
+        if (const int rc = order(rk, rk->as, st, fn)) return rc;
+    // 6. the neighbour halo of 2 + B messages
+    if (!no_halo)
+        if (const int rc = halo_exchange(rk, piv, inv_ext, kfo, B, o_bs, SD, S, slot, st, fn)) return rc;
+    return 0;
+}
+
+// The sequence one call issues, recorded by the call itself on a rank that owns no device object (host only).
+extern "C" int tf_rank_pivotal_frame_sets_edits_plan(int world, int rank, int K, int S, int H, int Dh, int radius,
+                                                     const int* anchors, int n_anchors, int n_edits, unsigned inject_mask, int mode,
+                                                     int flags, int dtype, char* buf, size_t len) {
+    TF_ARG(world >= 1 && world <= TF_MAX_WORLD && rank >= 0 && rank < world && K >= world && S > 0 && H > 0 && Dh > 0,
+           TF_ERR_SHAPE, "tf_rank_pivotal_frame_sets_edits_plan: rank %d of %d over %d keyframes, S=%d H=%d Dh=%d", rank, world, K,
+           S, H, Dh);
+    tf_rank rk{};
+    partition(&rk, K, world, rank);
+    void* const ph = reinterpret_cast<void*>((uintptr_t)1 << 40);   // never dereferenced
+    const int64_t D = (int64_t)H * Dh, SD = (int64_t)S * D;
+    const int64_t strides[8] = {rk.Kl * SD, SD, rk.Kl * SD, SD, rk.Kl * SD, SD, D, D};
+    TfPlanRec rec{buf, len, 0, 0};
+    if (buf && len) buf[0] = 0;
+    tf_plan_rec = &rec;
+    const int rc = tf_rank_pivotal_frame_sets_edits(&rk, ph, ph, ph, strides, ph, static_cast<float*>(ph), ph, S, H, Dh, 1.0f, flags,
+                                                    dtype, mode, 0, radius, anchors, n_anchors, n_edits, inject_mask, ph,
+                                                    (size_t)-1, nullptr);
+    tf_plan_rec = nullptr;
+    if (rc) return rc;
+    TF_ARG(rec.used < len, TF_ERR_WORKSPACE, "tf_rank_pivotal_frame_sets_edits_plan: the plan needs %zu bytes", rec.used + 1);
+    return rec.n;
+}

@@ -249,7 +249,8 @@ def _segments(module, K=None):
     return segs
 
 
-def register_bank_window(model, radius, edits=False, anchors=None, anchor_edits=False, shard=False, anchor_shard=False):
+def register_bank_window(model, radius, edits=False, anchors=None, anchor_edits=False, shard=False, anchor_shard=False,
+                         edit_shard=False):
     """Sliding-window keyframe bank (no counterpart in the reference, where every keyframe attends to the whole bank): in the
     pivotal passes that follow, the uncond / cond branches of keyframe i attend to the keyframes i - radius .. i + radius only
     (clamped to the bank; `ops.bank_windows`), the source branch to its own frame as always.  Consistency stays chained along
@@ -289,7 +290,12 @@ def register_bank_window(model, radius, edits=False, anchors=None, anchor_edits=
     every rank fetches the keyframes within `radius` of its own run plus the anchors, at most 64 frames in all, so the cap
     K <= 64 of the single-GPU frame-set call does not hold there.  The anchors resolve against the shard's WHOLE bank: an int
     stride m gives range(0, shard.K, m), an index >= shard.K is a ValueError at the pass.  Without the keyword anchors on a
-    windowed shard stay the ValueError they were."""
+    windowed shard stay the ValueError they were.
+    edit_shard=True (beside shard=True and edits=True; with anchors also anchor_edits=True and anchor_shard=True) opens a
+    MULTI-EDIT batch on a windowed frame shard: where the shard's type reports `supports_window_edits` and the shard was built
+    with `window_edits=True` (`FrameShard`, `NativeEditShard`), the installers call `shard.pivotal_attention(..., n_edits=E,
+    inject_mask=<the step's mask>, window=radius, anchors=resolved)` -- one sharded pass for all prompts, the masks of
+    `register_edit_schedules` included.  Without the keyword n_edits > 1 on a windowed shard stays the ValueError it was."""
     if radius is not None:
         radius = int(radius)
         if radius < 0:
@@ -309,10 +315,12 @@ def register_bank_window(model, radius, edits=False, anchors=None, anchor_edits=
         anchors = tuple(int(a) for a in anchors) or None
     _set_bank_window(_hook_blocks(model.unet), radius, bool(edits) and radius is not None,
                      anchors if radius is not None else None, bool(anchor_edits) and radius is not None,
-                     bool(shard) and radius is not None, bool(anchor_shard) and radius is not None)
+                     bool(shard) and radius is not None, bool(anchor_shard) and radius is not None,
+                     bool(edit_shard) and radius is not None)
 
 
-def _set_bank_window(blocks, radius, edits=False, anchors=None, anchor_edits=False, shard=False, anchor_shard=False):
+def _set_bank_window(blocks, radius, edits=False, anchors=None, anchor_edits=False, shard=False, anchor_shard=False,
+                     edit_shard=False):
     """`bank_window` (`bank_window_edits`, the multi-edit opt-in, `bank_window_anchors`: a tuple of keyframe indices, an
     int stride or None, and `bank_window_anchor_edits`, the opt-in of anchors in a multi-edit batch) on transformer blocks
     and their `attn1` (register_bank_window; tools on a bare block list)."""
@@ -324,6 +332,7 @@ def _set_bank_window(blocks, radius, edits=False, anchors=None, anchor_edits=Fal
             setattr(m, "bank_window_anchors", anchors)
             setattr(m, "bank_window_shard", shard)      # the opt-in of a window on a registered frame shard
             setattr(m, "bank_window_anchor_shard", anchor_shard)      # ... and of anchors beside it
+            setattr(m, "bank_window_edit_shard", edit_shard)      # ... and of a multi-edit batch on it
 
 
 def _bank_window(module, K: int):
@@ -341,7 +350,9 @@ def _bank_window(module, K: int):
         if K_all is None or not getattr(module, "bank_window_shard", False) or not getattr(shard, "supports_window", False):
             raise ValueError("register_bank_window: a sliding-window bank on a registered frame shard is not supported")
         # the opt-in (register_bank_window(..., shard=True)): the shard runs the windowed pass; what it does not generalise
-        if int(getattr(module, "n_edits", 1)) > 1:
+        if int(getattr(module, "n_edits", 1)) > 1 and not (
+                getattr(module, "bank_window_edits", False) and getattr(module, "bank_window_edit_shard", False)
+                and getattr(shard, "supports_window_edits", False) and getattr(shard, "window_edits", False)):
             raise ValueError("register_bank_window: a sliding-window bank on a registered frame shard runs one edit "
                              "(register_edits, n_edits > 1 is not supported there)")
         if getattr(module, "bank_window_anchors", None) is not None and not (
@@ -630,7 +641,11 @@ def _make_sa_forward(self, pnp: bool):
         mask = _inject_mask(self, E) if pnp else 0
         inject = mask != 0
         if shard is not None:     # q, k, v are this rank's keyframes; the bank is everybody's (register_frame_shard)
-            if E > 1:
+            if E > 1 and radius is not None:   # register_bank_window(..., edit_shard=True): all prompts in ONE windowed pass
+                _need_edit_shard(shard)
+                out = shard.pivotal_attention(q, k, v, self.heads, self.scale, False, n_edits=E, inject_mask=mask,
+                                              window=radius, anchors=anchors)
+            elif E > 1:
                 _need_edit_shard(shard)
                 out = shard.pivotal_attention(q, k, v, self.heads, self.scale, False, n_edits=E, inject_mask=mask)
             elif radius is not None:   # register_bank_window(..., shard=True): the rank's keyframes against their windows

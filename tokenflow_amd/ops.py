@@ -982,6 +982,122 @@ def attn_edits_part_plan(K: int, Kq: int, S: int, heads: int, dh: int, n_edits: 
                         int(n_edits), mask, 1 if qk_compact else 0, flags, _DT[dtype])
 
 
+def _edits_table_views(what: str, sym: str, table, q, k, v, out, heads, scale, n_edits, inject_mask, part, qk_compact, branch0,
+                       q_frame0, no_split, fused, multi_v, multi_v64, hints, stream):
+    """`ext_attn_windows_edits_views` / `ext_attn_frame_sets_edits_views`: the checks of `ext_attn_edits_views` for part "bank"
+    or "all", then the entry point `sym` with the table `table(K, Kq)` (a tuple of ctypes arrays) behind qk_compact."""
+    if part not in ("bank", "all"):
+        raise ValueError(f"{what}: part {part!r} (\"bank\" or \"all\": the source part is table-free, "
+                         "`ext_attn_edits_views(..., part=\"source\")`)")
+    if part == "all" and qk_compact:
+        raise ValueError(f"{what}: qk_compact with part \"all\" (the whole call reads dense q / k)")
+    dev = _need_gpu(q, k, v, out)
+    lib = _lib.load()
+    mask = _edit_mask(what, inject_mask, n_edits)
+    E = int(n_edits)
+    S, D = k.shape[2], k.shape[3]
+    K, Kq, dh = k.shape[1], q.shape[1], D // heads
+    dt = _DT.get(q.dtype)
+    if dt is None or dt == _lib.TF_F32 or k.dtype != q.dtype or v.dtype != q.dtype or D % heads:
+        raise TypeError(f"{what}: q/k/v must share dtype bf16 or f16")
+    tab = table(K, Kq)
+    qp, q_bs, q_fs, ld_q = _view_base(q, branch0[0], S, "q")
+    kp, k_bs, k_fs, ld = _view_base(k, branch0[1], S, "k")
+    vp, v_bs, v_fs, ld_v = _view_base(v, branch0[2], S, "v")
+    op, o_bs, o_fs, ld_o = _view_base(out, branch0[3], S, "out")
+    if ld_v != ld or ld_o != D or out.shape[1] != Kq or v.shape[1] != K:
+        raise ValueError(f"{what}: k and v need one token stride, out a dense one; frames of v = frames of k")
+    if out.dtype not in (q.dtype, torch.float32):
+        raise TypeError(f"{what}: out dtype")
+    # the branches each view must hold for this part, as in `ext_attn_edits_views`
+    nbr = 1 + 2 * E
+    n_non = E - bin(mask).count("1")
+    n_qk = (1 + 2 * n_non) if qk_compact else nbr
+    lo_vo, hi_vo = (1, nbr) if part == "bank" else (0, nbr)
+    lo_qk = 0 if (part != "bank" or mask) else 1
+    hi_qk = n_qk if n_non else 1
+    for t, b0, lo, hi, name in ((q, branch0[0], lo_qk, hi_qk, "q"), (k, branch0[1], lo_qk, hi_qk, "k"),
+                                (v, branch0[2], lo_vo, hi_vo, "v"), (out, branch0[3], lo_vo, hi_vo, "out")):
+        if b0 > lo or b0 + t.shape[0] < hi:
+            raise ValueError(f"{what}: {name} holds branches [{b0}, {b0 + t.shape[0]}), part '{part}' of {E} edits with mask "
+                             f"{mask:#x} reads [{lo}, {hi})")
+    flags = _attn_flags(False, part, out.dtype == torch.float32, False, no_split, fused, hints) | _multi_v_bits(multi_v, multi_v64)
+    ws = _workspace(lib.tf_ext_attn_edits_workspace_bytes(K, S, heads, dh, E, dt), q.device, stream=stream)
+    strides = (ctypes.c_int64 * 9)(q_bs, q_fs, k_bs, k_fs, v_bs, v_fs, o_bs, o_fs, ld_q)
+    _launch(dev, sym, getattr(lib, sym), qp, kp, vp, op, K, Kq, int(q_frame0), S, heads, dh, ld,
+            ctypes.cast(strides, ctypes.c_void_p), float(scale), flags, dt, E, mask, 1 if qk_compact else 0,
+            *[ctypes.cast(t, ctypes.c_void_p) for t in tab], ws.data_ptr(), ws.numel(), stream=stream)
+    return out
+
+
+def ext_attn_windows_edits_views(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, heads: int, scale: float,
+                                 n_edits: int, inject_mask: int, windows, part: str = "bank", qk_compact: bool = False,
+                                 branch0=(0, 0, 0, 0), q_frame0: int = 0, no_split: Optional[bool] = None,
+                                 fused: Optional[bool] = None, multi_v: Optional[bool] = None, hints: int = 0,
+                                 stream: Optional[int] = None, multi_v64: Optional[bool] = None) -> torch.Tensor:
+    """`ext_attn_windows_edits` on strided 4-D views [branches, frames, S, D] (tf_ext_attn_fwd_windows_edits_part): the views,
+    n_edits, inject_mask, qk_compact and branch0 of `ext_attn_edits_views`, the `windows` and q_frame0 of
+    `ext_attn_windows_views` (one (first frame, frames) pair per QUERY frame in bank coordinates; all edits share them).
+    part "bank": the bank branches of EVERY edit over the one table -- where they all take the fused small-problem kernel, in
+    ONE launch ('fused[..,sets=E,win]'), bit-identical under no_split=True to the E `ext_attn_windows_views` calls; part "all":
+    `ext_attn_windows_edits` on views.  The source part of a windowed pass is window-free:
+    `ext_attn_edits_views(..., part="source")`."""
+    what = "ext_attn_windows_edits_views"
+    return _edits_table_views(what, "tf_ext_attn_fwd_windows_edits_part", lambda K, Kq: _windows(what, windows, K, Kq, int(q_frame0)),
+                              q, k, v, out, heads, scale, n_edits, inject_mask, part, qk_compact, branch0, q_frame0, no_split,
+                              fused, multi_v, multi_v64, hints, stream)
+
+
+def ext_attn_frame_sets_edits_views(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, heads: int,
+                                    scale: float, n_edits: int, inject_mask: int, sets, part: str = "bank",
+                                    qk_compact: bool = False, branch0=(0, 0, 0, 0), q_frame0: int = 0,
+                                    no_split: Optional[bool] = None, fused: Optional[bool] = None,
+                                    multi_v: Optional[bool] = None, hints: int = 0, stream: Optional[int] = None,
+                                    multi_v64: Optional[bool] = None) -> torch.Tensor:
+    """`ext_attn_frame_sets_edits` on strided 4-D views (tf_ext_attn_fwd_frame_sets_edits_part): as
+    `ext_attn_windows_edits_views`, with one int mask per QUERY frame over the K = k.shape[1] <= 64 bank frames; the joint
+    fused launch is 'fused[..,sets=E,set]'.  Sets that are all ranges are `ext_attn_windows_edits_views`."""
+    what = "ext_attn_frame_sets_edits_views"
+    return _edits_table_views(what, "tf_ext_attn_fwd_frame_sets_edits_part",
+                              lambda K, Kq: (_frame_sets(what, sets, K, Kq, int(q_frame0)),), q, k, v, out, heads, scale, n_edits,
+                              inject_mask, part, qk_compact, branch0, q_frame0, no_split, fused, multi_v, multi_v64, hints, stream)
+
+
+def attn_windows_edits_part_plan(K: int, Kq: int, q_frame0: int, windows, S: int, heads: int, dh: int, n_edits: int,
+                                 inject_mask: int, part: str = "bank", qk_compact: bool = False,
+                                 dtype: torch.dtype = torch.bfloat16, out_dtype: Optional[torch.dtype] = None,
+                                 no_split: Optional[bool] = None, fused: Optional[bool] = None, multi_v: Optional[bool] = None,
+                                 multi_v64: Optional[bool] = None, hints: int = 0) -> list:
+    """The launches `ext_attn_windows_edits_views` makes for dense tensors, as tokens (tf_ext_attn_windows_edits_part_plan):
+    those of `attn_windows_edits_plan` without the source launches, or -- where every edit's bank part takes the fused kernel --
+    ONE token such as 'fused[qw=1,kw=4,qb=1,prec=1,sets=2,win]'.  Host only: needs no GPU."""
+    if part not in ("bank", "all"):
+        raise ValueError(f"attn_windows_edits_part_plan: part {part!r} (\"bank\" or \"all\": the source part is window-free)")
+    lo, n = _windows("attn_windows_edits_part_plan", windows, K, Kq, int(q_frame0))
+    mask = _edit_mask("attn_windows_edits_part_plan", inject_mask, n_edits)
+    flags = _attn_flags(False, part, out_dtype == torch.float32, False, no_split, fused, hints) | _multi_v_bits(multi_v, multi_v64)
+    return _plan_tokens("tf_ext_attn_windows_edits_part_plan", _lib.load().tf_ext_attn_windows_edits_part_plan, K, Kq,
+                        int(q_frame0), S, heads, dh, int(n_edits), mask, 1 if qk_compact else 0, flags, _DT[dtype],
+                        ctypes.cast(lo, ctypes.c_void_p), ctypes.cast(n, ctypes.c_void_p))
+
+
+def attn_frame_sets_edits_part_plan(K: int, Kq: int, q_frame0: int, sets, S: int, heads: int, dh: int, n_edits: int,
+                                    inject_mask: int, part: str = "bank", qk_compact: bool = False,
+                                    dtype: torch.dtype = torch.bfloat16, out_dtype: Optional[torch.dtype] = None,
+                                    no_split: Optional[bool] = None, fused: Optional[bool] = None,
+                                    multi_v: Optional[bool] = None, multi_v64: Optional[bool] = None, hints: int = 0) -> list:
+    """The launches `ext_attn_frame_sets_edits_views` makes for dense tensors, as tokens
+    (tf_ext_attn_frame_sets_edits_part_plan); the joint fused launch is 'fused[..,sets=E,set]'.  Host only: needs no GPU."""
+    if part not in ("bank", "all"):
+        raise ValueError(f"attn_frame_sets_edits_part_plan: part {part!r} (\"bank\" or \"all\": the source part is set-free)")
+    tab = _frame_sets("attn_frame_sets_edits_part_plan", sets, K, Kq, int(q_frame0))
+    mask = _edit_mask("attn_frame_sets_edits_part_plan", inject_mask, n_edits)
+    flags = _attn_flags(False, part, out_dtype == torch.float32, False, no_split, fused, hints) | _multi_v_bits(multi_v, multi_v64)
+    return _plan_tokens("tf_ext_attn_frame_sets_edits_part_plan", _lib.load().tf_ext_attn_frame_sets_edits_part_plan, K, Kq,
+                        int(q_frame0), S, heads, dh, int(n_edits), mask, 1 if qk_compact else 0, flags, _DT[dtype],
+                        ctypes.cast(tab, ctypes.c_void_p))
+
+
 def _run_flags(inject: bool, bank_only: bool, out_f32: bool, fold_scale: Optional[bool], no_split: bool, hints: int) -> int:
     """The TF_ATTN_* bit mask of a run / merge call (the module default TOKENFLOW_ATTN_NO_SPLIT does not apply: a run set is
     a split form by construction; no_split=True only keeps a run from splitting itself further)."""
@@ -1318,6 +1434,42 @@ def frame_set_halo_pack(slabs: Sequence[torch.Tensor], masks, out: Optional[torc
             ctypes.cast(fs, ctypes.c_void_p), ns, out.data_ptr(), len(ms), ctypes.cast(tab, ctypes.c_void_p), Kl, S, D, ld,
             -1 if dt is None else dt)
     return out
+
+
+def edit_halo_pack(slabs: Sequence[torch.Tensor], masks, q_slabs: Sequence[torch.Tensor] = (),
+                   out: Optional[torch.Tensor] = None, q_out: Optional[torch.Tensor] = None):
+    """`frame_set_halo_pack` for a MULTI-EDIT batch (tf_edit_halo_pack, one launch): up to 4 * TF_MAX_EDITS slabs [Kl, S, D] (the
+    compact k slots and two value slabs per edit) -> the send buffer [rows, ns, S, D], rows = the members of every peer's mask
+    in ascending order; a plain window's ranges are contiguous masks.  q_slabs: up to 1 + 2 * TF_MAX_EDITS [Kl, S, D] views
+    (sharing one token stride) copied by extra workgroups of the SAME launch into the dense staging tensor [nq, Kl, S, D] -- the
+    compact q of a mixed injection mask.  Returns (send buffer, staging tensor or None)."""
+    dev = _need_gpu(*slabs, *q_slabs)
+    lib = _lib.load()
+    Kl, S, D = slabs[0].shape
+    ns, nq = len(slabs), len(q_slabs)
+    ld = slabs[0].stride(1)
+    dt = _DT.get(slabs[0].dtype)
+    if any(t.shape != (Kl, S, D) or t.stride(2) != 1 or t.stride(1) != ld or t.dtype != slabs[0].dtype for t in slabs):
+        raise ValueError("edit_halo_pack: slabs must be [Kl, S, D] views sharing dtype and token stride")
+    ld_q = q_slabs[0].stride(1) if nq else ld
+    if any(t.shape != (Kl, S, D) or t.stride(2) != 1 or t.stride(1) != ld_q or t.dtype != slabs[0].dtype for t in q_slabs):
+        raise ValueError("edit_halo_pack: q_slabs must be [Kl, S, D] views of the slabs' dtype sharing one token stride")
+    ms = [int(m) for m in masks]
+    if not ms or Kl > 64 or any(m < 0 or m >> Kl for m in ms):
+        raise ValueError(f"edit_halo_pack: masks {[hex(m) for m in ms]} (bits below the {Kl} <= 64 local frames, one mask per peer)")
+    rows = sum(bin(m).count("1") for m in ms)
+    out = _caller_buffer("edit_halo_pack", "out", out, (rows, ns, S, D), slabs[0].dtype, slabs[0].device)
+    q_out = _caller_buffer("edit_halo_pack", "q_out", q_out, (nq, Kl, S, D), slabs[0].dtype, slabs[0].device) if nq else None
+    ptrs = (ctypes.c_void_p * ns)(*[t.data_ptr() for t in slabs])
+    fs = (ctypes.c_int64 * ns)(*[t.stride(0) for t in slabs])
+    qptrs = (ctypes.c_void_p * max(nq, 1))(*[t.data_ptr() for t in q_slabs])
+    qfs = (ctypes.c_int64 * max(nq, 1))(*[t.stride(0) for t in q_slabs])
+    tab = (ctypes.c_uint64 * len(ms))(*ms)
+    _launch(dev, "tf_edit_halo_pack", lib.tf_edit_halo_pack, ctypes.cast(ptrs, ctypes.c_void_p), ctypes.cast(fs, ctypes.c_void_p),
+            ns, out.data_ptr() if rows else slabs[0].data_ptr(), len(ms), ctypes.cast(tab, ctypes.c_void_p),
+            ctypes.cast(qptrs, ctypes.c_void_p) if nq else None, ctypes.cast(qfs, ctypes.c_void_p) if nq else None, nq,
+            q_out.data_ptr() if nq else None, Kl, S, D, ld, ld_q, -1 if dt is None else dt)
+    return out, q_out
 
 
 def head_unpack(recv: torch.Tensor, dsts: Sequence[torch.Tensor]) -> None:

@@ -258,7 +258,19 @@ class FrameShard:
     def __init__(self, K: int, group: Optional[dist.ProcessGroup] = None, comm=None,
                  attn_split: Optional[bool] = None, halo_group: Optional[dist.ProcessGroup] = None, halo_comm=None,
                  bank_runs: Optional[bool] = None, edit_runs: Optional[bool] = None,
-                 edit_runs_multi_v: Optional[bool] = None):
+                 edit_runs_multi_v: Optional[bool] = None, window_edits: Optional[bool] = None,
+                 window_edits_multi_v: Optional[bool] = None):
+        # window_edits: opt-in for a MULTI-EDIT batch over a sliding-window / anchored bank (`_pivotal_window_edits`): window=
+        # with n_edits > 1 runs instead of raising.  None reads TOKENFLOW_SHARD_WINDOW_EDITS.  Off: today's answers.
+        if window_edits is None:
+            window_edits = os.environ.get("TOKENFLOW_SHARD_WINDOW_EDITS", "0") not in ("", "0")
+        self.window_edits = bool(window_edits)
+        # window_edits_multi_v: the four-bank launches of that pass for pairs of injecting edits (TF_ATTN_MULTI_V at head dim
+        # 40, TF_ATTN_MULTI_V64 at 64; within the attention bound, not bit-stable per edit).  Without it the pass sets
+        # TF_ATTN_NO_MULTI_V.  None reads TOKENFLOW_SHARD_WINDOW_EDITS_MULTI_V.
+        if window_edits_multi_v is None:
+            window_edits_multi_v = os.environ.get("TOKENFLOW_SHARD_WINDOW_EDITS_MULTI_V", "0") not in ("", "0")
+        self.window_edits_multi_v = bool(window_edits_multi_v)
         # bank_runs: opt-in for `auto_mode` (mode=None callers, the hook path): "bank_runs" where it would answer "bank"
         # and S >= BANK_RUNS_MIN_S.  None reads TOKENFLOW_SHARD_BANK_RUNS.  Off: today's answers.
         if bank_runs is None:
@@ -477,7 +489,8 @@ class FrameShard:
         """Extended attention for the local keyframes against all K keyframes -> [3*Kl,S,D].
         window = R: a sliding-window bank (`_pivotal_window`; NOT TokenFlow's result): the bank branches of keyframe g attend
         to the keyframes g - R .. g + R only, of which the rank fetches just those within R of its own run.  None, or a radius
-        that covers the bank (R >= K - 1), is the pass without the keyword; one edit only.
+        that covers the bank (R >= K - 1), is the pass without the keyword; one edit only unless the shard was built with
+        `window_edits=True` (`_pivotal_window_edits`: n_edits > 1 in ONE windowed / anchored pass).
         anchors (beside window): GLOBAL keyframe indices every keyframe sees beside its window (`_pivotal_frame_sets`); none
         is the windowed pass itself.
         mode: "heads" | "bank" | "bank_runs" | None (= `auto_mode`, chosen per block).
@@ -489,6 +502,9 @@ class FrameShard:
         one-pass form."""
         anc = self._anchors(window, anchors)
         if self._window(window, n_edits, mode) is not None:
+            if int(n_edits) != 1:      # (the window_edits opt-in)
+                return self._pivotal_window_edits(q_local, k_local, v_local, heads, scale, inject, int(window), anc, out4,
+                                                  int(n_edits), inject_mask)
             if anc:
                 return self._pivotal_frame_sets(q_local, k_local, v_local, heads, scale, inject, int(window), anc, out4)
             return self._pivotal_window(q_local, k_local, v_local, heads, scale, inject, int(window), out4)
@@ -528,7 +544,7 @@ class FrameShard:
         if mode is not None:
             raise ValueError(f"FrameShard: mode={mode!r} beside window={R}: the windowed pass has one exchange pattern of its "
                              "own (pass mode=None)")
-        if int(n_edits) != 1:
+        if int(n_edits) != 1 and not getattr(self, "window_edits", False):      # (opt-in: window_edits=True)
             raise ValueError("FrameShard: a sliding-window bank on a frame shard runs one edit (n_edits > 1 with window= is "
                              "not supported)")
         from . import _lib
@@ -631,6 +647,79 @@ class FrameShard:
             ops.ext_attn_frame_sets_views(q3, rp[0:2], rp[2:4], out, heads, scale, False, plan.sets, "bank",
                                           branch0=(0, 1, 1, 0), q_frame0=plan.q_frame0, no_split=ns_)
         return out.view(3 * Kl, S, D) if out4 is None else out4
+
+    # ------------------------------------------------------------------ ... for a multi-edit batch (the window_edits opt-in)
+    supports_window_edits = True      # window= / anchors= beside n_edits > 1 (hooks.register_bank_window(edit_shard=True))
+
+    def _window_edits_hints(self, dh: int) -> dict:
+        """The four-bank keywords of the windowed multi-edit pass: off (bit-stable per edit) unless the shard opts in."""
+        if not getattr(self, "window_edits_multi_v", False):
+            return dict(multi_v=False)
+        return dict(multi_v=True) if dh == 40 else dict(multi_v64=True) if dh == 64 else {}
+
+    def _pivotal_window_edits(self, q_local, k_local, v_local, heads, scale, inject, R, anchors, out4, E, inject_mask):
+        """`_pivotal_window` / `_pivotal_frame_sets` for E edits: the same pack, exchange and two part calls as the native
+        executor's tf_rank_pivotal_frame_sets_edits, filling the same buffers with the same bits on the same transport:
+          1. ONE `ops.edit_halo_pack` of the compact k slots and the 2E value slabs for the frames each peer reads (the source's
+             v and every q stay at home); under a mixed mask the same launch stages the compact q slots;
+          2. ONE row all-to-all with the sparse counts: the receive buffer is the extended bank [F, slabs, S, D];
+          3. the source part of the local frames, table-free (`ops.ext_attn_edits_views(part="source")`);
+          4. the bank part of ALL edits over the receive buffer in place: `ops.ext_attn_windows_edits_views` (no anchors) or
+             `ops.ext_attn_frame_sets_edits_views`, compact q / k, Kq = Kl, q_frame0 and the table of the plan."""
+        B = 1 + 2 * E
+        if inject_mask is None:
+            mask = (1 << E) - 1 if inject else 0
+        else:
+            mask = int(inject_mask)
+            if inject or mask < 0 or mask >> E:
+                raise ValueError(f"FrameShard.pivotal_attention: inject_mask {mask:#x} for {E} edits (bits below n_edits; "
+                                 f"`inject` must be False beside a mask)")
+        _, S, D = q_local.shape
+        Kl = self.Kl
+        ns_ = not self.attn_split
+        mv = self._window_edits_hints(D // heads)
+        if self.world == 1:
+            out = None if out4 is None else out4.view(q_local.shape)
+            if anchors:
+                return ops.ext_attn_frame_sets_edits(q_local, k_local, v_local, heads, scale, False, E,
+                                                     ops.bank_frame_sets(self.K, R, anchors), inject_mask=mask, out=out,
+                                                     no_split=ns_, **mv)
+            return ops.ext_attn_windows_edits(q_local, k_local, v_local, heads, scale, False, E, ops.bank_windows(self.K, R),
+                                              inject_mask=mask, out=out, no_split=ns_, **mv)
+        plan = frame_set_halo_plan(self.K, self.world, self.rank, R, anchors)      # (no anchors: the windowed plan)
+        dev, dt = q_local.device, q_local.dtype
+
+        def frames(t):     # [B*Kl, S, D] (token stride free) -> [B, Kl, S, D] view
+            if t.stride(2) != 1 or t.stride(0) != S * t.stride(1):
+                t = t.contiguous()
+            return t.view(B, Kl, S, D) if t.is_contiguous() else t.unflatten(0, (B, Kl))
+        q4, k4, v4 = frames(q_local), frames(k_local), frames(v_local)
+        if k4.stride(2) != v4.stride(2):
+            k4, v4 = k4.contiguous(), v4.contiguous()
+        slots = ([0] if mask else []) + [b for e in range(E) if not (mask >> e) & 1 for b in (1 + 2 * e, 2 + 2 * e)]
+        b0 = 0 if mask else 1
+        nq = len(slots)
+        mixed = bool(mask) and nq > 1
+        slabs = [k4[b] for b in slots] + [v4[b] for b in range(1, B)]
+        ns = len(slabs)
+        # what each peer reads of this rank, as a mask over the local frames (a plain window's ranges are contiguous masks)
+        masks = plan.send if anchors else [((1 << n) - 1) << f0 for f0, n in plan.send]
+        send, qst = ops.edit_halo_pack(slabs, masks, [q4[b] for b in slots] if mixed else (),
+                                       out=self._buf("wine_send", (sum(plan.send_rows), ns, S, D), dt, dev),
+                                       q_out=self._buf("wine_q", (nq, Kl, S, D), dt, dev) if mixed else None)
+        recv = self._buf("wine_recv", (plan.F, ns, S, D), dt, dev)
+        self._a2a(recv.view(plan.F, -1), send.view(send.shape[0], -1), plan.recv_rows, plan.send_rows)
+        out = torch.empty(B, Kl, S, D, dtype=dt, device=dev) if out4 is None else out4
+        ops.ext_attn_edits_views(q4[0:1], k4[0:1], v4[0:1], out[0:1], heads, scale, E, mask, "source", no_split=ns_)
+        rp = recv.permute(1, 0, 2, 3)                                   # [ns, F, S, D] views: frame stride ns*S*D
+        qc = qst if mixed else q4[b0:]      # the dense tensor is the compact layout already unless the mask is mixed
+        if anchors:
+            ops.ext_attn_frame_sets_edits_views(qc, rp[0:nq], rp[nq:], out[1:], heads, scale, E, mask, plan.sets, "bank", True,
+                                                branch0=(b0, b0, 1, 1), q_frame0=plan.q_frame0, no_split=ns_, **mv)
+        else:
+            ops.ext_attn_windows_edits_views(qc, rp[0:nq], rp[nq:], out[1:], heads, scale, E, mask, plan.windows, "bank", True,
+                                             branch0=(b0, b0, 1, 1), q_frame0=plan.hl, no_split=ns_, **mv)
+        return out.view(B * Kl, S, D) if out4 is None else out4
 
     # ------------------------------------------------------------------ pivotal pass of a multi-edit batch
     def _pivotal_edits(self, q_local, k_local, v_local, heads, scale, inject, mode, out4, E, inject_mask):
@@ -891,7 +980,7 @@ class FrameShard:
         anc = self._anchors(window, anchors)
         if self._window(window, n_edits, mode) is not None:
             self.pivotal_attention(q_local, k_local, v_local, heads, scale, inject, out4=kfo[:, o:], window=window,
-                                   anchors=anc or None)
+                                   anchors=anc or None, **(dict(n_edits=n_edits, inject_mask=inject_mask) if n_edits != 1 else {}))
         elif n_edits == 1:
             self.pivotal_attention(q_local, k_local, v_local, heads, scale, inject, mode=mode, out4=kfo[:, o:])
         else:
@@ -1074,11 +1163,14 @@ class NativeShard(FrameShard):
     other methods are `FrameShard`'s own on the same communicator.  tf_rank_pivotal runs one edit: no multi-edit batches."""
 
     supports_edits = False
+    supports_window_edits = False      # tf_rank_pivotal_window / _frame_sets run one edit; `NativeEditShard` has the multi-edit call
 
     def __init__(self, K: int, comm, halo_comm=None, attn_split: Optional[bool] = None, bank_runs: Optional[bool] = None,
-                 edit_runs: Optional[bool] = None, edit_runs_multi_v: Optional[bool] = None):
+                 edit_runs: Optional[bool] = None, edit_runs_multi_v: Optional[bool] = None,
+                 window_edits: Optional[bool] = None, window_edits_multi_v: Optional[bool] = None):
         super().__init__(K, comm=comm, attn_split=attn_split, halo_comm=halo_comm, bank_runs=bank_runs, edit_runs=edit_runs,
-                         edit_runs_multi_v=edit_runs_multi_v)
+                         edit_runs_multi_v=edit_runs_multi_v, window_edits=window_edits,
+                         window_edits_multi_v=window_edits_multi_v)
         from . import _lib
         lib = _lib.load()
         h = ctypes.c_void_p()
@@ -1218,14 +1310,19 @@ class NativeEditShard(NativeShard):
     Modes "heads" and "bank" (`auto_mode` answers "bank" in place of "bank_runs" for E > 1; the explicit "bank_runs" raises as
     on `FrameShard`) -- unless the shard opts in with `edit_runs`: "bank_runs" is then the executor's TF_RANK_BANK_EDIT_RUNS,
     the native form of `FrameShard._pivotal_bank_runs_edits` with the local run beside the gather (`edit_runs_multi_v`: with
-    TF_ATTN_RUN_MULTI_V).  `ext_alloc`, `halo_block`, `halo_finish`, `propagate_all` are `FrameShard`'s, with n_edits."""
+    TF_ATTN_RUN_MULTI_V).  `window_edits`: window= / anchors= beside n_edits > 1 is ONE tf_rank_pivotal_frame_sets_edits call,
+    the native form of `FrameShard._pivotal_window_edits`.  `ext_alloc`, `halo_block`, `halo_finish`, `propagate_all` are
+    `FrameShard`'s, with n_edits."""
 
     supports_edits = True
+    supports_window_edits = True      # window= / anchors= beside n_edits > 1: ONE tf_rank_pivotal_frame_sets_edits call
 
     def __init__(self, K: int, comm, halo_comm=None, attn_split: Optional[bool] = None, bank_runs: Optional[bool] = None,
-                 edit_runs: Optional[bool] = None, edit_runs_multi_v: Optional[bool] = None):
+                 edit_runs: Optional[bool] = None, edit_runs_multi_v: Optional[bool] = None,
+                 window_edits: Optional[bool] = None, window_edits_multi_v: Optional[bool] = None):
         super().__init__(K, comm, halo_comm=halo_comm, attn_split=attn_split, bank_runs=bank_runs, edit_runs=edit_runs,
-                         edit_runs_multi_v=edit_runs_multi_v)
+                         edit_runs_multi_v=edit_runs_multi_v, window_edits=window_edits,
+                         window_edits_multi_v=window_edits_multi_v)
         self._news = {}
 
     @staticmethod
@@ -1242,29 +1339,32 @@ class NativeEditShard(NativeShard):
                           mode: Optional[str] = None, out4: Optional[torch.Tensor] = None, n_edits: int = 1,
                           inject_mask: Optional[int] = None, window: Optional[int] = None, anchors=None):
         """`FrameShard.pivotal_attention` with n_edits / inject_mask; E > 1 is one tf_rank_pivotal_edits call with
-        TF_RANK_NO_HALO (what the hook path calls from `attn1`).  window= / anchors=: one edit only, `NativeShard`'s passes."""
+        TF_RANK_NO_HALO (what the hook path calls from `attn1`).  window= / anchors=: with one edit `NativeShard`'s passes; with
+        E > 1 (the shard's `window_edits` opt-in) ONE tf_rank_pivotal_frame_sets_edits call."""
         E = int(n_edits)
-        self._anchors(window, anchors)
-        self._window(window, E, mode)      # (a windowed multi-edit batch raises)
+        anc = self._anchors(window, anchors)
+        R = self._window(window, E, mode)      # (a windowed multi-edit batch raises without the window_edits opt-in)
         if E == 1:
             return super().pivotal_attention(q_local, k_local, v_local, heads, scale, inject, mode=mode, out4=out4,
                                              window=window, anchors=anchors)
         if self.world == 1 or out4 is not None or not q_local.is_cuda or q_local.dtype not in (torch.bfloat16,
                                                                                                 torch.float16):
+            win = dict(window=R, anchors=anc or None) if R is not None else {}
             return FrameShard.pivotal_attention(self, q_local, k_local, v_local, heads, scale, inject, mode=mode, out4=out4,
-                                                n_edits=E, inject_mask=inject_mask)
+                                                n_edits=E, inject_mask=inject_mask, **win)
         mask = self._mask(E, inject, inject_mask)
         B, S, D = q_local.shape
         out = torch.empty(1 + 2 * E, self.Kl, S, D, dtype=q_local.dtype, device=q_local.device)
-        self._native_edits(q_local, k_local, v_local, heads, scale, E, mask, mode, None, None, out, no_halo=True)
+        self._native_edits(q_local, k_local, v_local, heads, scale, E, mask, mode, None, None, out, no_halo=True, window=R,
+                           anchors=anc if R is not None else ())
         return out.view(B, S, D)
 
     def pivotal_block(self, q_local, k_local, v_local, heads: int, scale: float, inject: bool, ext,
                       mode: Optional[str] = None, inv_norm: bool = False, n_edits: int = 1,
                       inject_mask: Optional[int] = None, window: Optional[int] = None, anchors=None):
         E = int(n_edits)
-        self._anchors(window, anchors)
-        self._window(window, E, mode)      # (a windowed multi-edit batch raises)
+        anc = self._anchors(window, anchors)
+        R = self._window(window, E, mode)      # (a windowed multi-edit batch raises without the window_edits opt-in)
         if E == 1:
             return super().pivotal_block(q_local, k_local, v_local, heads, scale, inject, ext, mode=mode, inv_norm=inv_norm,
                                          window=window, anchors=anchors)
@@ -1273,15 +1373,19 @@ class NativeEditShard(NativeShard):
         _, S, D = q_local.shape
         o = 1 if self.world > 1 else 0
         slot = self._native_edits(q_local, k_local, v_local, heads, scale, E, mask, mode, piv, inv, kfo, no_halo=False,
-                                  inv_norm=inv_norm)
+                                  inv_norm=inv_norm, window=R, anchors=anc if R is not None else ())
         reqs = [_SlotWait(self, slot, q_local.device)] if self.world > 1 else []
         return piv, inv, kfo.view((1 + 2 * E) * (self.Kl + o), S, D), reqs
 
-    def _native_edits(self, q_local, k_local, v_local, heads, scale, E, mask, mode, piv, inv, kfo, no_halo, inv_norm=False):
+    def _native_edits(self, q_local, k_local, v_local, heads, scale, E, mask, mode, piv, inv, kfo, no_halo, inv_norm=False,
+                      window=None, anchors=()):
         from . import _lib
         lib = _lib.load()
         _, S, D = q_local.shape
         Kl, B = self.Kl, 1 + 2 * E
+        if window is not None:      # the windowed / anchored multi-edit pass: ONE tf_rank_pivotal_frame_sets_edits call
+            return self._native_window_edits(q_local, k_local, v_local, heads, scale, E, mask, piv, inv, kfo, no_halo, inv_norm,
+                                             int(window), tuple(anchors))
         if mode is None:
             mode = self.auto_mode(heads, S, E)
         runs = mode == "bank_runs"
@@ -1326,6 +1430,73 @@ class NativeEditShard(NativeShard):
         if rc:
             _lib.check(rc, "tf_rank_pivotal_edits")
         return slot
+
+    def _native_window_edits(self, q_local, k_local, v_local, heads, scale, E, mask, piv, inv, kfo, no_halo, inv_norm, R, anchors):
+        from . import _lib
+        lib = _lib.load()
+        _, S, D = q_local.shape
+        Kl, B = self.Kl, 1 + 2 * E
+        dt = ops._DT.get(q_local.dtype)
+        if dt is None or dt == _lib.TF_F32 or not (q_local.is_cuda and kfo.is_contiguous()
+                                                    and (no_halo or (piv.is_contiguous() and inv.is_contiguous()))):
+            raise TypeError("NativeEditShard: 16-bit GPU tensors, contiguous (halo-extended) buffers")
+
+        def frames(t):     # [B*Kl, S, D] (token stride free) -> [B, Kl, S, D] view
+            if t.stride(2) != 1 or t.stride(0) != S * t.stride(1):
+                t = t.contiguous()
+            return t.view(B, Kl, S, D) if t.is_contiguous() else t.unflatten(0, (B, Kl))
+        q4, k4, v4 = frames(q_local), frames(k_local), frames(v_local)
+        if k4.stride(2) != v4.stride(2):
+            k4, v4 = k4.contiguous(), v4.contiguous()
+        strides = (ctypes.c_int64 * 8)(q4.stride(0), q4.stride(1), k4.stride(0), k4.stride(1), v4.stride(0), v4.stride(1),
+                                       q4.stride(2), k4.stride(2))
+        dh = D // heads
+        anc = (ctypes.c_int * max(len(anchors), 1))(*anchors)
+        key = (S, heads, dh, dt, q_local.device, E, "window", R, anchors)
+        ws = self._news.get(key)
+        if ws is None:
+            plan = frame_set_halo_plan(self.K, self.world, self.rank, R, anchors)      # (raises what is refused)
+            nbytes = lib.tf_rank_pivotal_frame_sets_edits_workspace_bytes(self._rk, S, heads, dh, dt, R,
+                                                                          ctypes.cast(anc, ctypes.c_void_p), len(anchors), E)
+            assert nbytes > 0, plan
+            ws = self._news[key] = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=q_local.device)
+        # the flags of `FrameShard._pivotal_window_edits`: bit-stable unless attn_split; the four-bank form off unless opted in
+        hint = self._window_edits_hints(dh)
+        flags = ((0 if self.attn_split else _lib.TF_ATTN_NO_SPLIT)
+                 | (_lib.TF_ATTN_NO_MULTI_V if hint.get("multi_v") is False else 0)
+                 | (_lib.TF_ATTN_MULTI_V if hint.get("multi_v") else 0) | (_lib.TF_ATTN_MULTI_V64 if hint.get("multi_v64") else 0))
+        slot = self._slot
+        if not no_halo:
+            self._slot = (slot + 1) % _lib.TF_RANK_SLOTS
+        m = _lib.TF_RANK_BANK | (_lib.TF_RANK_NO_HALO if no_halo else 0) | (_lib.TF_RANK_INV_NORM if inv_norm else 0)
+        rc = lib.tf_rank_pivotal_frame_sets_edits(self._rk, q4.data_ptr(), k4.data_ptr(), v4.data_ptr(), strides,
+                                                  None if piv is None else piv.data_ptr(),
+                                                  None if inv is None else inv.data_ptr(), kfo.data_ptr(), S, heads, dh,
+                                                  float(scale), flags, dt, m, slot, R, ctypes.cast(anc, ctypes.c_void_p),
+                                                  len(anchors), E, mask, ws.data_ptr(), ws.numel(),
+                                                  torch.cuda.current_stream(q_local.device).cuda_stream)
+        if rc:
+            _lib.check(rc, "tf_rank_pivotal_frame_sets_edits")
+        return slot
+
+
+def rank_window_edits_plan(world: int, rank: int, K: int, S: int, heads: int, dh: int, radius: int, anchors=(), n_edits: int = 2,
+                           inject_mask: int = 0, dtype: torch.dtype = torch.bfloat16, no_split: bool = True,
+                           no_halo: bool = False, inv_norm: bool = False, flags: int = 0, mode: Optional[int] = None) -> list:
+    """The sequence ONE windowed / anchored multi-edit `NativeEditShard` block call issues on `rank` of `world` ranks, as tokens
+    (tf_rank_pivotal_frame_sets_edits_plan: e.g. ['edit_pack[ns=7,nq=3]', 'a2a[slabs=7,send=3/1,recv=3/1]', <source tokens>,
+    'fused[qw=1,kw=4,qb=1,prec=1,sets=2,win]', 'halo[n=7]']).  n_edits = 1 gives `rank_frame_sets_plan`, a covering radius
+    `rank_edits_plan(mode="bank")`.  Recorded by the executing code itself; host only.  mode: a raw TF_RANK_* value instead of
+    TF_RANK_BANK (the refusals)."""
+    from . import _lib
+    m = ((_lib.TF_RANK_BANK if mode is None else int(mode)) | (_lib.TF_RANK_NO_HALO if no_halo else 0)
+         | (_lib.TF_RANK_INV_NORM if inv_norm else 0))
+    fl = int(flags) | (_lib.TF_ATTN_NO_SPLIT if no_split else 0)
+    anc = [int(a) for a in (anchors or ())]
+    tab = (ctypes.c_int * max(len(anc), 1))(*anc)
+    return ops._plan_tokens("tf_rank_pivotal_frame_sets_edits_plan", _lib.load().tf_rank_pivotal_frame_sets_edits_plan,
+                            int(world), int(rank), int(K), S, heads, dh, int(radius), ctypes.cast(tab, ctypes.c_void_p), len(anc),
+                            int(n_edits), int(inject_mask), m, fl, ops._DT[dtype])
 
 
 def rank_edits_plan(world: int, rank: int, K: int, S: int, heads: int, dh: int, n_edits: int, inject_mask: int,

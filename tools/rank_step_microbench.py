@@ -18,7 +18,11 @@ Target: step <= single-GPU step / 6.
 --native, `FrameShard` without, both on the library's loopback transport so that --no-copies and --wire-model apply to
 either); the injected blocks of an inject=1 step run with mask M (default: every edit injects).  The yardstick is E times the
 --edits 1 step.  With --edits, the modes bank_runs and auto+runs build the shard with edit_runs=True (the run form of a multi-edit
-batch: TF_RANK_BANK_EDIT_RUNS with --native)."""
+batch: TF_RANK_BANK_EDIT_RUNS with --native).
+
+--window R [--anchors ..] --edits E: ONE windowed / anchored multi-edit pass per step (the shard's window_edits opt-in:
+tf_rank_pivotal_frame_sets_edits with --native, `FrameShard._pivotal_window_edits` without); prints the executor's plan line per
+level.  The yardstick is E single-edit windowed steps (--window R --edits 1)."""
 import argparse
 import os
 import statistics
@@ -184,7 +188,7 @@ def main():
                     help="--edits: the injection mask of the injected blocks in an inject=1 step (default: every edit)")
     ap.add_argument("--window", type=int, default=None, metavar="R",
                     help="the sliding-window bank of radius R on the shard (pivotal_block(..., window=R): FrameShard and --native; "
-                         "one edit).  The exchange of every level is then the sparse row all-to-all of the windowed pass: one arm "
+                         "with --edits E > 1 the shard's window_edits opt-in).  The exchange of every level is then the sparse row all-to-all of the windowed pass: one arm "
                          "per attention form (the mode labels do not apply); the loopback wire model sees its per-peer row counts")
     ap.add_argument("--anchors", default=None, metavar="I[,J,...]",
                     help="beside --window: global anchor keyframes every keyframe sees (pivotal_block(..., window=R, anchors=...)); "
@@ -192,8 +196,7 @@ def main():
     ap.add_argument("--anchor-stride", type=int, default=None, metavar="M", help="beside --window: every M-th keyframe as an anchor")
     args = ap.parse_args()
     E = args.edits
-    if args.window is not None and E > 1:
-        ap.error("--window runs one edit (a windowed shard has no multi-edit form)")
+    win_e = args.window is not None and E > 1      # the windowed multi-edit pass (the shard's window_edits opt-in)
     if (args.anchors is not None or args.anchor_stride is not None) and args.window is None:
         ap.error("--anchors / --anchor-stride stand beside --window")
     if args.anchors is not None and args.anchor_stride is not None:
@@ -222,10 +225,11 @@ def main():
                 comm.bytes = 0
                 hcomm = HipComm.loopback(args.rank, args.world, copies=not args.no_copies, wire=wire)
                 if E > 1:
-                    shard = (sharded.NativeEditShard(cfg.K, comm, hcomm, attn_split=split, bank_runs=opt_in, edit_runs=runs_e)
+                    shard = (sharded.NativeEditShard(cfg.K, comm, hcomm, attn_split=split, bank_runs=opt_in, edit_runs=runs_e,
+                                                     window_edits=win_e)
                              if args.native else
                              sharded.FrameShard(cfg.K, comm=comm, halo_comm=hcomm, attn_split=split, bank_runs=opt_in,
-                                                edit_runs=runs_e))
+                                                edit_runs=runs_e, window_edits=win_e))
                 else:
                     shard = sharded.NativeShard(cfg.K, comm, hcomm, attn_split=split, bank_runs=opt_in)
             else:
@@ -251,10 +255,18 @@ def main():
                           f"{banks} frame-banks of attention (windowed: "
                           f"{sum(n for _, n in sharded.window_halo_plan(cfg.K, args.world, args.rank, args.window).windows)}, "
                           f"whole bank: {cfg.K * plan.Kl})", flush=True)
+                if win_e:      # the plan line: what ONE block call of the executor issues, per level (host only)
+                    for lvl, (S_, D_, h_) in enumerate(cfg.levels):
+                        for m_ in sorted({0, mask}):
+                            toks = sharded.rank_window_edits_plan(args.world, args.rank, cfg.K, S_, h_, D_ // h_, args.window,
+                                                                  anchors, E, m_, no_split=not split, inv_norm=True,
+                                                                  flags=_lib.TF_ATTN_NO_MULTI_V)
+                            print(f"=== plan level {lvl} (S={S_}) mask {m_:#x}: {len(toks)} launches / collectives: "
+                                  f"{'; '.join(toks)}", flush=True)
             gen = torch.Generator(device=dev).manual_seed(1234 + args.rank)
             if E > 1:
                 blocks = [EditBlock(cfg, lvl, inj, shard, gen, dev, E) for lvl, inj in workload.BLOCKS]
-                modes = [mode or shard.auto_mode(l[2], l[0], E) for l in cfg.levels]
+                modes = [f"window {args.window}" if win_e else mode or shard.auto_mode(l[2], l[0], E) for l in cfg.levels]
                 step = lambda inj_: run_edit_step(cfg, blocks, shard, inj_, w, E, mask, exchange=mode)
                 print(f"=== ONE multi-edit pass per step: {E} edits, mask {mask:#x} on the injected blocks of an inject=1 step, "
                       f"{'NativeEditShard' if args.native else 'FrameShard'} on the loopback transport", flush=True)
