@@ -160,6 +160,13 @@ TF_API const char* tf_last_error(void);
  *     - inputs are read only inside their frames' S rows x H*Dh columns (D columns for the NN search and the gather):
  *       whatever lies in the other columns of a row of stride ld, behind row S - 1 or next to a tensor is never loaded
  *       into arithmetic, and no input is modified.
+ *
+ *   The issue contract of every entry point (enforced by tests/test_issue_contract_gpu.py): every launch of a call goes
+ *   to `stream`, or to a stream of the library's own behind an event edge from `stream` and joined back in front of
+ *   what the call leaves on it (the rank executor); the call returns without waiting for the GPU; it can be captured
+ *   into a HIP graph and replayed on other contents of the same tensors; two calls on two streams with two workspaces
+ *   share nothing.  The tests issue every call on a busy side stream behind inputs that arrive late, read the stream's
+ *   state when the call returns, replay a capture next to reused scratch, and run a call beside itself.
  * ------------------------------------------------------------------------ */
 TF_API size_t tf_ext_attn_workspace_bytes(int K, int S, int H, int Dh, int dtype);
 

@@ -9,7 +9,11 @@ is fixed, so the whole pass is captured ONCE into a HIP graph and replayed: one 
 
 Every `tf_*` entry point is capture-safe (asynchronous on the caller's stream, no allocation, no
 synchronisation; `ops._workspace` hands out graph-owned scratch while a capture is running), so a capture taken
-through `torch.cuda.graph` contains the library's kernels next to torch's own.
+through `torch.cuda.graph` contains the library's kernels next to torch's own.  tests/test_issue_contract_gpu.py
+captures and replays every single-stream entry point -- attention in all its forms (windows, frame sets, edits,
+segments, runs, the `_views` / `_part` forms, `stream=` the capturing stream included), the NN search, the
+propagation family, the small kernels and the halo packs -- and found none that is not capturable.  The `streams=`
+form of the run wrappers and the rank executors fork streams of their own and are not captured there.
 
     cache = GraphCache()
     y = cache.run(("chunk", batch_idx, injecting), unet_pass, x)       # captures on first use, replays after

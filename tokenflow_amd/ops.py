@@ -77,24 +77,39 @@ _ws_cache = {}
 _attn_ws_bytes = {}   # (K, S, H, Dh, dtype) -> scratch bytes of tf_ext_attn_fwd (a pure function of the shape)
 
 
-def _workspace(nbytes: int, device, tag: str = "attn", stream: Optional[int] = None) -> torch.Tensor:
-    """Scratch for one launch, cached per (purpose, device, stream).  While a HIP graph is being captured the
-    buffer comes from the graph's private pool and must live and die with that graph: never cached."""
-    if stream is None:
-        if device.index != torch.cuda.current_device():      # capture state is a property of the TENSORS' device's stream
-            with torch.cuda.device(device):
-                capturing = torch.cuda.is_current_stream_capturing()
-        else:
-            capturing = torch.cuda.is_current_stream_capturing()
-        if capturing:
-            return torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device)
-        stream = torch.cuda.current_stream(device).cuda_stream
-    key = (tag, device.index, stream)
+def _scratch(nbytes: int, device, key) -> torch.Tensor:
+    """`_workspace` with the launch's stream (of the tensors' device) current."""
+    if torch.cuda.is_current_stream_capturing():
+        return torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device)
     ws = _ws_cache.get(key)
     if ws is None or ws.numel() < nbytes:
-        ws = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=device)
-        _ws_cache[key] = ws
+        ws = _ws_cache[key] = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=device)
     return ws
+
+
+def _workspace(nbytes: int, device, tag: str = "attn", stream: Optional[int] = None) -> torch.Tensor:
+    """Scratch for one launch, cached per (purpose, device, stream).  While a HIP graph is being captured the
+    buffer comes from the graph's private pool and must live and die with that graph: never cached.
+    stream: the raw HIP stream the launch goes to when that is not torch's current one.  Capture state and allocation are
+    then THAT stream's: the buffer is allocated with `stream` current, so torch's allocator ties the block to it and --
+    dropped or outgrown -- hands it out again in that stream's order only, never to the current stream while launches
+    on `stream` that use it are still queued."""
+    cur = torch.cuda.current_stream(device)
+    other_device = device.index != torch.cuda.current_device()      # capture state is a property of the TENSORS' device's stream
+    if stream is None or stream == cur.cuda_stream:
+        if other_device:
+            with torch.cuda.device(device):
+                return _scratch(nbytes, device, (tag, device.index, cur.cuda_stream))
+        return _scratch(nbytes, device, (tag, device.index, cur.cuda_stream))
+    ext = torch.cuda.ExternalStream(stream, device=device)
+    if other_device:
+        with torch.cuda.stream(ext):
+            return _scratch(nbytes, device, (tag, device.index, stream))
+    torch.cuda.set_stream(ext)      # (the context manager costs several microseconds more per call)
+    try:
+        return _scratch(nbytes, device, (tag, device.index, stream))
+    finally:
+        torch.cuda.set_stream(cur)
 
 
 def drop_workspaces(stream=None) -> None:
