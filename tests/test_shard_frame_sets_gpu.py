@@ -422,7 +422,8 @@ def test_frame_set_halo_pack_64_frames_and_refusals():
     for masks in ([1 << 63], [(1 << 64) - 1], [1 << 63, (1 << 64) - 1, 0, 1]):
         got = ops.frame_set_halo_pack(slabs, masks)
         assert torch.equal(got, _pack_want(slabs, masks)[1]), masks
-    # rows of more 16-byte pieces than one workgroup holds: several workgroups per row, each striding over the row
+    # rows of more 16-byte pieces than one workgroup holds: several workgroups per row (ny = 141 for 36000 pieces: every thread
+    # copies at most one piece, none strides -- tests/test_grid_stride_gpu.py has the rows whose workgroups do)
     big = [torch.randn(5, 300, 320, generator=g).bfloat16().cuda() for _ in range(3)]
     masks = [0b10110, 0b00001, 0, 0b11111]
     assert torch.equal(ops.frame_set_halo_pack(big, masks), _pack_want(big, masks)[1])
