@@ -724,6 +724,59 @@ TF_API int tf_nn_gather_blend_chunks_norm_segments(const void* tgt, const void* 
 TF_API int tf_nn_gather_blend_segments_plan(int n, int C, int S, int D, uint64_t single_mask, char* buf, size_t len);
 
 /* ------------------------------------------------------------------------
+ * RAGGED chunk runs (additive to ABI 11): one propagation call for chunks of UNEQUAL frame count -- the tail of a video whose
+ * length is no multiple of the chunk size, scenes whose lengths are whatever the cuts give.  Chunk j of the call has
+ * chunk_frames[j] >= 1 frames (a HOST array of C ints, 1 <= C <= 64); F = sum_j chunk_frames[j].  Everything else is
+ * tf_nn_gather_blend_chunks_segments: single_mask, slots slot0 + j and slot0 + j - 1, single_dtype rounding of the
+ * one-keyframe chunks.
+ *
+ *   tgt : [F*S, D] chunk-major;   resid, out, norm_out : [B, F, S, D], B = 1 + 2*n_edits;   kf_out : [B, K, S, D].
+ *   n_edits = 1 is the 3-branch gather; n_edits > 1 (<= TF_MAX_EDITS) the multi-edit form of tf_nn_gather_blend_chunks_edits,
+ *   for which only bit 0 of single_mask may be set (segments and multi-edit batches do not combine).
+ *   w : a DEVICE array of F floats, one per frame of the CALL: the entry of frame i of chunk j is the blend weight of index i
+ *   at chunk size chunk_frames[j] (the caller concatenates the per-size weight vectors; with equal sizes the first n entries
+ *   are today's w[n]).
+ *
+ * Semantics: the rows of chunk j equal what the one-chunk call computes on chunk j's tensors alone -- tf_nn_gather_blend
+ * with n = chunk_frames[j], that size's w, P = 1 where bit j of the mask is set.  The gather arithmetic is that call's bit
+ * for bit; the indices are that call's wherever the two searches take the same kernel form (the caveat of every chunk form).
+ *
+ * Launches.  Equal frame counts ARE today's call: tf_nn_gather_blend_chunks_segments (n_edits = 1) or
+ * tf_nn_gather_blend_chunks_edits -- same launches, same plan tokens, same bits.  Otherwise ONE search and ONE gather:
+ *   - kernel form: the one the uniform C-chunk search takes at the MEAN chunk size, tf_nn_search_plan(ceil(F*S / C), S, D,
+ *     2, C) -- a host-only rule on (chunk_frames, S, D);
+ *   - grid.x = sum_j ceil(chunk_frames[j]*S / TN) target panels of that form: a chunk's last panel is partial, no panel
+ *     straddles two chunks; the pivot-range split is the form's rule applied to that workgroup count;
+ *   - chunk descriptor: two prefix tables (targets, panels) and the mask in the kernel-argument segment, about 0.5 KiB; a
+ *     workgroup of the search bisects the panel table with scalar loads, a thread of the gather the target table.  The call
+ *     copies nothing to the device: it issues kernels only and can be captured.
+ * Plan tokens (tf_nn_gather_blend_ragged_plan, host only): the search token with ",ragged" in its brackets, e.g.
+ * rb[splits=1,ragged], then gather[branches=B,ragged] (gather_norm[branches=B,ragged] for the norm form's gather).
+ *
+ * Refusals, all before anything touches the device: TF_ERR_SHAPE for C outside 1..64, a chunk of less than one frame, a mask
+ * bit at or above C, slot0 + C > K, slot0 < 1 without bit 0, F*S >= 2^31, n_edits outside 1..TF_MAX_EDITS, a mask above 1 with
+ * n_edits > 1; alignment, dtype and workspace errors as the segments form.  Workspace:
+ * tf_nn_gather_blend_ragged_workspace_bytes (0 for a refused shape).
+ * ------------------------------------------------------------------------ */
+TF_API size_t tf_nn_gather_blend_ragged_workspace_bytes(const int* chunk_frames, int C, int S, int D);
+
+TF_API int tf_nn_gather_blend_chunks_ragged(const void* tgt, const void* piv, const float* inv_norm, const void* kf_out,
+                                     const float* w, const void* resid, void* out, int K, const int* chunk_frames, int C,
+                                     int S, int D, int slot0, uint64_t single_mask, int search_dtype, int in_dtype,
+                                     int res_dtype, int out_dtype, int single_dtype, int n_edits, void* ws, size_t ws_bytes,
+                                     void* stream);
+
+TF_API int tf_nn_gather_blend_chunks_norm_ragged(const void* tgt, const void* piv, const float* inv_norm, const void* kf_out,
+                                          const float* w, const void* resid, void* out, int K, const int* chunk_frames,
+                                          int C, int S, int D, int slot0, uint64_t single_mask, int search_dtype,
+                                          int in_dtype, int res_dtype, int out_dtype, int single_dtype, int n_edits,
+                                          const void* gamma, const void* beta, float eps, int w_dtype, void* norm_out,
+                                          int norm_dtype, void* ws, size_t ws_bytes, void* stream);
+
+TF_API int tf_nn_gather_blend_ragged_plan(const int* chunk_frames, int C, int S, int D, uint64_t single_mask, int n_edits,
+                                   char* buf, size_t len);
+
+/* ------------------------------------------------------------------------
  * Sliding-window keyframe BANK (additive to ABI 11): the extended attention of long videos.  A keyframe's uncond / cond
  * branches attend to the keys of its NEIGHBOURING keyframes only -- overlapping windows, where keyframe segments are disjoint
  * ones -- so the pivotal pass costs sum_i win_n[i] frame-banks instead of K * Kq.  This CHANGES THE RESULT relative to

@@ -150,6 +150,16 @@ _SIGNATURES = {
                                                                   _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_size_t,
                                                                   _c.c_void_p]),
     "tf_nn_gather_blend_segments_plan": (_c.c_int, [_c.c_int] * 4 + [_c.c_uint64, _c.c_char_p, _c.c_size_t]),
+    # ragged chunk runs: one propagation call for chunks of unequal frame count (additive to ABI 11)
+    "tf_nn_gather_blend_ragged_workspace_bytes": (_c.c_size_t, [_c.c_void_p] + [_c.c_int] * 3),
+    "tf_nn_gather_blend_chunks_ragged": (_c.c_int, [_c.c_void_p] * 7 + [_c.c_int, _c.c_void_p] + [_c.c_int] * 4 +
+                                         [_c.c_uint64] + [_c.c_int] * 6 + [_c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "tf_nn_gather_blend_chunks_norm_ragged": (_c.c_int, [_c.c_void_p] * 7 + [_c.c_int, _c.c_void_p] + [_c.c_int] * 4 +
+                                              [_c.c_uint64] + [_c.c_int] * 6 +
+                                              [_c.c_void_p, _c.c_void_p, _c.c_float, _c.c_int, _c.c_void_p, _c.c_int,
+                                               _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "tf_nn_gather_blend_ragged_plan": (_c.c_int, [_c.c_void_p] + [_c.c_int] * 3 + [_c.c_uint64, _c.c_int, _c.c_char_p,
+                                                                                  _c.c_size_t]),
     # sliding-window keyframe bank: a keyframe attends to its neighbouring keyframes only (additive to ABI 11)
     "tf_ext_attn_fwd_windows": (_c.c_int, [_c.c_void_p] * 4 + [_c.c_int] * 6 + [_c.c_int64, _c.c_void_p, _c.c_float, _c.c_int,
                                            _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),

@@ -112,6 +112,24 @@ struct GbChunks {
     uint64_t single_mask;   // bit j: chunk j of the call has one keyframe (chunks at or above 64: never)
 };
 __device__ __forceinline__ bool gb_chunk_single(const GbChunks& ch, int j) { return j < 64 && ((ch.single_mask >> j) & 1); }
+// chunk of a token; `frame` (of the whole call) becomes the frame inside the chunk, the index of the chunk's weight
+__device__ __forceinline__ int gb_chunk_of(const GbChunks& ch, int64_t, int& frame) {
+    const int j = frame / ch.nc;
+    frame -= j * ch.nc;
+    return j;
+}
+
+// Ragged call (tf_nn_gather_blend_chunks_ragged): C <= 64 chunks of unequal frame count.  A token's chunk is found in the
+// target prefix table of the launch (tf_common.h, NnRagged) -- a per-thread bisection whose six reads are vector loads from
+// the kernel-argument segment: no private array, no device table to copy in.  `w` holds one weight per frame of the CALL
+// (the caller concatenates the weights of every chunk size), so the frame index stays global.
+struct GbRagged {
+    int single_dtype;
+    uint64_t single_mask;
+    int row0[TF_RAGGED_MAX_CHUNKS + 1];
+};
+__device__ __forceinline__ bool gb_chunk_single(const GbRagged& ch, int j) { return (ch.single_mask >> j) & 1; }
+__device__ __forceinline__ int gb_chunk_of(const GbRagged& ch, int64_t t, int&) { return tf_ragged_find(ch.row0, (int)t); }
 
 // MERGE: the indices come as the search's per-split partial results (tf_nn_gather_blend: no finalize launch
 // in between); every thread of a token merges them itself -- `splits` 8-byte reads, broadcast from cache.
@@ -119,13 +137,15 @@ __device__ __forceinline__ bool gb_chunk_single(const GbChunks& ch, int j) { ret
 // DYN: the number of branches is the argument `nb` (multi-edit batches, [source | uncond_1 | cond_1 | ... ]: the *_edits
 // entry points) instead of the constant 3; the arithmetic of a branch is the same code, so branch b of a DYN launch is
 // bit-identical to branch b of the 3-branch launch on the same tensors.
-template <typename TIn, typename TRes, typename TOut, int P, bool MERGE, bool CH = false, bool DYN = false>
+// CHT: the chunk descriptor of a CH launch, GbChunks (equal chunks) or GbRagged.
+template <typename TIn, typename TRes, typename TOut, int P, bool MERGE, bool CH = false, bool DYN = false,
+          typename CHT = GbChunks>
 __global__ __launch_bounds__(256) void gather_blend_kernel(const TIn* __restrict__ kf_out,
                                                            const int32_t* __restrict__ idx,
                                                            const NnPartial* __restrict__ part, int splits,
                                                            const float* __restrict__ w, const TRes* __restrict__ resid,
                                                            TOut* __restrict__ out, int K, int n, int S, int D, int kf0,
-                                                           int kf1, GbChunks ch, int nb) {
+                                                           int kf1, CHT ch, int nb) {
     const int ppr = D >> 3;  // pieces per row
     const int64_t nS = (int64_t)n * S;
     const int64_t total = nS * ppr;
@@ -144,8 +164,7 @@ __global__ __launch_bounds__(256) void gather_blend_kernel(const TIn* __restrict
         int64_t coff = 0;        // CH: offset of this chunk's keyframe pair from (kf0, kf1)
         bool single = false;     // CH: this token belongs to the one-keyframe chunk
         if constexpr (CH) {
-            const int j = frame / ch.nc;
-            frame -= j * ch.nc;
+            const int j = gb_chunk_of(ch, t, frame);
             coff = j * frame_in;
             single = gb_chunk_single(ch, j);
         }
@@ -200,11 +219,11 @@ __global__ __launch_bounds__(256) void gather_blend_kernel(const TIn* __restrict
 // in the 16-bit type the Linear reads.
 // Always the MERGE form (indices from the search's partial results).  T16 = the 16-bit model type (cached attention
 // output, residual, norm output); TOut = result type: float (two keyframes) or T16 (the one-keyframe chunk alone).
-template <typename T16, typename TOut, int LPR, int NP, int P, bool CH>
+template <typename T16, typename TOut, int LPR, int NP, int P, bool CH, typename CHT = GbChunks>
 __global__ __launch_bounds__(256) void gather_blend_norm_kernel(
     const T16* __restrict__ kf_out, const NnPartial* __restrict__ part, int splits, const float* __restrict__ w,
     const T16* __restrict__ resid, TOut* __restrict__ out, T16* __restrict__ norm_out, const void* __restrict__ gamma,
-    const void* __restrict__ beta, int w_dtype, float eps, int K, int n, int S, int D, int kf0, int kf1, GbChunks ch,
+    const void* __restrict__ beta, int w_dtype, float eps, int K, int n, int S, int D, int kf0, int kf1, CHT ch,
     int nb) {
     constexpr int RPW = 64 / LPR;
     __shared__ __attribute__((aligned(16))) float sw[2][LPR * 8 * NP];
@@ -232,8 +251,7 @@ __global__ __launch_bounds__(256) void gather_blend_norm_kernel(
         int64_t coff = 0;
         bool single = false;
         if constexpr (CH) {
-            const int j = frame / ch.nc;
-            frame -= j * ch.nc;
+            const int j = gb_chunk_of(ch, t, frame);
             coff = j * frame_in;
             single = gb_chunk_single(ch, j);
         }
@@ -322,10 +340,13 @@ struct GbArgs {
     float eps = 0.f;
     int nb = 3;         // branches; dyn: the *_edits entry points (branch count as a kernel argument)
     bool dyn = false;
+    const GbRagged* rg = nullptr;   // ragged call: the descriptor in the place of `ch`
 };
+static const GbChunks& gb_desc(const GbArgs& a, const GbChunks*) { return a.ch; }
+static const GbRagged& gb_desc(const GbArgs& a, const GbRagged*) { return *a.rg; }
 
 // fused-norm form: T16 in / residual / norm out, result float (P = 2) or T16 (P = 1)
-template <typename T16, typename TOut, int P, bool CH>
+template <typename T16, typename TOut, int P, bool CH, typename CHT = GbChunks>
 void launch_gbn(const GbArgs& a) {
     const int64_t rows = (int64_t)a.nb * a.n * a.S;
     auto go = [&](auto kern, int lpr) {
@@ -334,21 +355,21 @@ void launch_gbn(const GbArgs& a) {
         if (blocks > 256 * 16) blocks = 256 * 16;
         hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, a.st, (const T16*)a.kf_out, a.part, a.splits, a.w,
                            (const T16*)a.resid, (TOut*)a.out, (T16*)a.norm_out, a.gamma, a.beta, a.w_dtype, a.eps, a.K,
-                           a.n, a.S, a.D, a.kf0, P == 2 ? a.kf1 : a.kf0, a.ch, a.nb);
+                           a.n, a.S, a.D, a.kf0, P == 2 ? a.kf1 : a.kf0, gb_desc(a, (const CHT*)nullptr), a.nb);
     };
-    if (tf_plan_note("gather_norm[branches=%d]", a.nb)) return;
+    if (tf_plan_note(a.rg ? "gather_norm[branches=%d,ragged]" : "gather_norm[branches=%d]", a.nb)) return;
     // lanes per row as tf_layer_norm has them (ln_row.h): the norm's bits depend on it.  3 pieces per lane cover the
     // model's widths (D = 320 / 640 / 1280) and everything up to D = 384 / 768 / 1536 at 16 / 32 / 64 lanes; the widths
     // between (D <= 512 at 16 lanes, <= 1024 at 32) take the 4-piece instantiation
     const int pieces = a.D >> 3, lpr = ln_lanes_per_row(a.D);
     if (lpr == 16) {
-        if (pieces <= 48) go(gather_blend_norm_kernel<T16, TOut, 16, 3, P, CH>, 16);
-        else go(gather_blend_norm_kernel<T16, TOut, 16, LN_MAXP, P, CH>, 16);
+        if (pieces <= 48) go(gather_blend_norm_kernel<T16, TOut, 16, 3, P, CH, CHT>, 16);
+        else go(gather_blend_norm_kernel<T16, TOut, 16, LN_MAXP, P, CH, CHT>, 16);
     } else if (lpr == 32) {
-        if (pieces <= 96) go(gather_blend_norm_kernel<T16, TOut, 32, 3, P, CH>, 32);
-        else go(gather_blend_norm_kernel<T16, TOut, 32, LN_MAXP, P, CH>, 32);
+        if (pieces <= 96) go(gather_blend_norm_kernel<T16, TOut, 32, 3, P, CH, CHT>, 32);
+        else go(gather_blend_norm_kernel<T16, TOut, 32, LN_MAXP, P, CH, CHT>, 32);
     } else {
-        go(gather_blend_norm_kernel<T16, TOut, 64, 3, P, CH>, 64);
+        go(gather_blend_norm_kernel<T16, TOut, 64, 3, P, CH, CHT>, 64);
     }
 }
 
@@ -360,7 +381,8 @@ static bool gbn_supported(int D, int P, int in_dtype, int res_dtype, int out_dty
 
 template <typename T16>
 void dispatch_gbn(const GbArgs& a) {
-    if (a.ch.nc > 0) launch_gbn<T16, float, 2, true>(a);
+    if (a.rg) launch_gbn<T16, float, 2, true, GbRagged>(a);
+    else if (a.ch.nc > 0) launch_gbn<T16, float, 2, true>(a);
     else if (a.P == 2) launch_gbn<T16, float, 2, false>(a);
     else launch_gbn<T16, T16, 1, false>(a);
 }
@@ -374,8 +396,15 @@ void launch_gb(const GbArgs& a) {
         hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, a.st, (const TIn*)a.kf_out, a.idx, a.part,
                            a.splits, a.w, (const TRes*)a.resid, (TOut*)a.out, a.K, a.n, a.S, a.D, a.kf0, kf1, a.ch, a.nb);
     };
-    if (tf_plan_note("gather[branches=%d]", a.nb)) return;
-    if (a.dyn) {   // multi-edit batch: the chunk form, or the one-keyframe chunk alone
+    if (tf_plan_note(a.rg ? "gather[branches=%d,ragged]" : "gather[branches=%d]", a.nb)) return;
+    if (a.rg) {   // ragged call: the chunk forms over the prefix table
+        auto go_rg = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, a.st, (const TIn*)a.kf_out, a.idx, a.part,
+                               a.splits, a.w, (const TRes*)a.resid, (TOut*)a.out, a.K, a.n, a.S, a.D, a.kf0, a.kf1, *a.rg, a.nb);
+        };
+        if (a.dyn) go_rg(gather_blend_kernel<TIn, TRes, TOut, 2, true, true, true, GbRagged>);
+        else go_rg(gather_blend_kernel<TIn, TRes, TOut, 2, true, true, false, GbRagged>);
+    } else if (a.dyn) {   // multi-edit batch: the chunk form, or the one-keyframe chunk alone
         if (a.ch.nc > 0) go(gather_blend_kernel<TIn, TRes, TOut, 2, true, true, true>, a.kf1);
         else go(gather_blend_kernel<TIn, TRes, TOut, 1, true, false, true>, a.kf0);
     } else if (a.ch.nc > 0) {
@@ -718,6 +747,166 @@ extern "C" int tf_nn_gather_blend_edits_plan(int n, int C, int S, int D, int fir
     tf_plan_rec = nullptr;
     if (rc) return rc;
     TF_ARG(rec.used < len, TF_ERR_WORKSPACE, "tf_nn_gather_blend_edits_plan: the plan needs %zu bytes", rec.used + 1);
+    return rec.n;
+}
+
+// Ragged chunk runs (include/tokenflow_hip.h): chunk j of the call has its own frame count.  Equal counts ARE today's calls
+// (the segments form for n_edits = 1, the edits form above it); everything else is one ragged search and one ragged gather.
+static bool ragged_uniform(const int* frames, int C) {
+    for (int j = 1; j < C; ++j)
+        if (frames[j] != frames[0]) return false;
+    return true;
+}
+// the shape refusals every ragged entry point shares; *rows = targets of the call
+static int ragged_check(const char* name, const int* frames, int C, int S, int D, uint64_t single_mask, int64_t* rows) {
+    TF_ARG(frames, TF_ERR_NULL, "%s: null chunk_frames", name);
+    TF_ARG(C >= 1 && C <= TF_RAGGED_MAX_CHUNKS && S > 0 && D > 0 && D % 8 == 0, TF_ERR_SHAPE,
+           "%s: C=%d S=%d D=%d (1 <= C <= %d)", name, C, S, D, TF_RAGGED_MAX_CHUNKS);
+    TF_ARG(C == 64 || !(single_mask >> C), TF_ERR_SHAPE, "%s: C=%d single_mask=0x%llx (no bit at or above C)", name, C,
+           (unsigned long long)single_mask);
+    int64_t r = 0;
+    for (int j = 0; j < C; ++j) {
+        TF_ARG(frames[j] >= 1, TF_ERR_SHAPE, "%s: chunk %d has %d frames (>= 1)", name, j, frames[j]);
+        r += (int64_t)frames[j] * S;
+        TF_ARG(r <= (int64_t)INT32_MAX, TF_ERR_SHAPE, "%s: the call's targets (sum of frames * S) must stay below 2^31", name);
+    }
+    *rows = r;
+    return 0;
+}
+
+extern "C" size_t tf_nn_gather_blend_ragged_workspace_bytes(const int* chunk_frames, int C, int S, int D) {
+    int64_t rows = 0;
+    if (ragged_check("tf_nn_gather_blend_ragged_workspace_bytes", chunk_frames, C, S, D, 0, &rows)) return 0;
+    size_t b;
+    if (ragged_uniform(chunk_frames, C)) {
+        const int64_t nS = (int64_t)chunk_frames[0] * S;
+        b = tf_nn_gather_blend_chunks_workspace_bytes(nS, S, D, C);
+        if (C == 1) {   // the one-keyframe chunk alone of a multi-edit batch searches one keyframe
+            const size_t b1 = tf_nn_gather_blend_workspace_bytes(nS, S, D, 1);
+            b = b1 > b ? b1 : b;
+        }
+    } else {
+        b = tf_nn_partials_bytes_ragged(chunk_frames, C, S, D);
+    }
+    return b < 256 ? 256 : b;
+}
+
+static int nn_gather_blend_ragged_impl(const char* name, const void* tgt, const void* piv, const float* inv_norm,
+                                       const void* kf_out, const float* w, const void* resid, void* out, int K,
+                                       const int* frames, int C, int S, int D, int slot0, uint64_t single_mask,
+                                       int search_dtype, int in_dtype, int res_dtype, int out_dtype, int single_dtype,
+                                       int n_edits, void* ws, size_t ws_bytes, void* stream, const NormArgs& nm) {
+    int64_t rows = 0;
+    const int rc0 = ragged_check(name, frames, C, S, D, single_mask, &rows);
+    if (rc0) return rc0;
+    TF_ARG(n_edits >= 1 && n_edits <= TF_MAX_EDITS, TF_ERR_SHAPE, "%s: n_edits=%d (1 .. %d)", name, n_edits, TF_MAX_EDITS);
+    TF_ARG(n_edits == 1 || single_mask <= 1, TF_ERR_SHAPE,
+           "%s: single_mask=0x%llx with %d edits (segments and multi-edit batches do not combine: bit 0 only)", name,
+           (unsigned long long)single_mask, n_edits);
+    const bool first_single = single_mask & 1;
+    TF_ARG(K > 0 && slot0 + C <= K && slot0 >= (first_single ? 0 : 1), TF_ERR_SHAPE, "%s: K=%d C=%d slot0=%d first_single=%d",
+           name, K, C, slot0, (int)first_single);
+    if (ragged_uniform(frames, C)) {   // today's call: same launches, same plan tokens, same bits
+        if (n_edits == 1)
+            return nn_gather_blend_chunks_impl(name, tgt, piv, inv_norm, kf_out, w, resid, out, K, frames[0], C, S, D, slot0,
+                                               single_mask, search_dtype, in_dtype, res_dtype, out_dtype, single_dtype, ws,
+                                               ws_bytes, stream, nm, 0, true);
+        return nn_gather_blend_edits(name, tgt, piv, inv_norm, kf_out, w, resid, out, K, frames[0], C, S, D, slot0,
+                                     first_single, search_dtype, in_dtype, res_dtype, out_dtype, single_dtype, ws, ws_bytes,
+                                     stream, nm, n_edits);
+    }
+    TF_ARG(tgt && piv && inv_norm && kf_out && out && ws && w, TF_ERR_NULL, "%s: null pointer", name);
+    TF_ARG(search_dtype == TF_BF16 || search_dtype == TF_F16, TF_ERR_DTYPE, "%s: search dtype %d (bf16/f16 only)", name,
+           search_dtype);
+    auto okdt = [](int d) { return d == TF_BF16 || d == TF_F16 || d == TF_F32; };
+    TF_ARG(okdt(in_dtype) && okdt(out_dtype) && okdt(single_dtype) && (!resid || okdt(res_dtype)), TF_ERR_DTYPE,
+           "%s: dtypes in=%d res=%d out=%d single=%d", name, in_dtype, res_dtype, out_dtype, single_dtype);
+    TF_ARG(tf_aligned16(tgt) && tf_aligned16(piv) && tf_aligned16(kf_out) && tf_aligned16(out) &&
+               tf_aligned16(resid) && tf_aligned16(ws) && tf_aligned16(inv_norm),
+           TF_ERR_ALIGN, "%s: tensors not 16-byte aligned (inv_norm included)", name);
+    if (nm.out) {
+        TF_ARG((!nm.gamma && !nm.beta) || okdt(nm.w_dtype), TF_ERR_DTYPE, "%s: norm weight dtype %d", name, nm.w_dtype);
+        TF_ARG(gbn_supported(D, 2, in_dtype, res_dtype, out_dtype, nm.dtype, resid != nullptr), TF_ERR_DTYPE,
+               "%s: the fused norm needs a 16-bit cached output, a residual and a norm output of that same type and the "
+               "result in fp32; D <= 1536", name);
+        TF_ARG(tf_aligned16(nm.out) && tf_aligned16(nm.gamma) && tf_aligned16(nm.beta), TF_ERR_ALIGN,
+               "%s: norm tensors not 16-byte aligned", name);
+    }
+    const size_t need = tf_nn_gather_blend_ragged_workspace_bytes(frames, C, S, D);
+    TF_ARG(ws_bytes >= need, TF_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", name, ws_bytes, need);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    NnPartial* part = reinterpret_cast<NnPartial*>(ws);
+    int splits = 1;
+    const int rc = tf_nn_search_partials_ragged(tgt, piv, inv_norm, part, frames, C, S, D, slot0, slot0 - 1, search_dtype, st,
+                                                &splits, single_mask);
+    if (rc) return rc;
+    GbRagged rg;
+    rg.single_dtype = single_dtype, rg.single_mask = single_mask;
+    int64_t row = 0;
+    for (int j = 0; j <= TF_RAGGED_MAX_CHUNKS; ++j) {
+        rg.row0[j] = j <= C ? (int)row : INT32_MAX;
+        if (j < C) row += (int64_t)frames[j] * S;
+    }
+    GbArgs a{kf_out, nullptr, part, splits, w, resid, out, K, (int)(rows / S), S, D, 2, slot0, slot0 - 1, st, GbChunks{0, 0, 0}};
+    a.rg = &rg;
+    a.nb = 1 + 2 * n_edits, a.dyn = n_edits > 1;
+    if (nm.out) {
+        a.norm_out = nm.out, a.gamma = nm.gamma, a.beta = nm.beta, a.w_dtype = nm.w_dtype, a.eps = nm.eps;
+        if (in_dtype == TF_BF16) dispatch_gbn<__bf16>(a);
+        else dispatch_gbn<_Float16>(a);
+    } else {
+        switch (in_dtype) {
+            case TF_BF16: dispatch_res<__bf16>(a, res_dtype, out_dtype); break;
+            case TF_F16: dispatch_res<_Float16>(a, res_dtype, out_dtype); break;
+            default: dispatch_res<float>(a, res_dtype, out_dtype); break;
+        }
+    }
+    if (tf_plan_rec) return 0;   // plan recording: nothing was launched
+    TF_LAUNCH_CHECK(name);
+    return 0;
+}
+
+extern "C" int tf_nn_gather_blend_chunks_ragged(const void* tgt, const void* piv, const float* inv_norm, const void* kf_out,
+                                                const float* w, const void* resid, void* out, int K, const int* chunk_frames,
+                                                int C, int S, int D, int slot0, uint64_t single_mask, int search_dtype,
+                                                int in_dtype, int res_dtype, int out_dtype, int single_dtype, int n_edits,
+                                                void* ws, size_t ws_bytes, void* stream) {
+    return nn_gather_blend_ragged_impl("tf_nn_gather_blend_chunks_ragged", tgt, piv, inv_norm, kf_out, w, resid, out, K,
+                                       chunk_frames, C, S, D, slot0, single_mask, search_dtype, in_dtype, res_dtype, out_dtype,
+                                       single_dtype, n_edits, ws, ws_bytes, stream, NormArgs{});
+}
+
+extern "C" int tf_nn_gather_blend_chunks_norm_ragged(const void* tgt, const void* piv, const float* inv_norm,
+                                                     const void* kf_out, const float* w, const void* resid, void* out, int K,
+                                                     const int* chunk_frames, int C, int S, int D, int slot0,
+                                                     uint64_t single_mask, int search_dtype, int in_dtype, int res_dtype,
+                                                     int out_dtype, int single_dtype, int n_edits, const void* gamma,
+                                                     const void* beta, float eps, int w_dtype, void* norm_out, int norm_dtype,
+                                                     void* ws, size_t ws_bytes, void* stream) {
+    TF_ARG(norm_out, TF_ERR_NULL, "tf_nn_gather_blend_chunks_norm_ragged: null norm_out");
+    NormArgs nm;
+    nm.out = norm_out, nm.gamma = gamma, nm.beta = beta, nm.eps = eps, nm.w_dtype = w_dtype, nm.dtype = norm_dtype;
+    return nn_gather_blend_ragged_impl("tf_nn_gather_blend_chunks_norm_ragged", tgt, piv, inv_norm, kf_out, w, resid, out, K,
+                                       chunk_frames, C, S, D, slot0, single_mask, search_dtype, in_dtype, res_dtype, out_dtype,
+                                       single_dtype, n_edits, ws, ws_bytes, stream, nm);
+}
+
+// Launch plan of tf_nn_gather_blend_chunks_ragged (host only): the entry point itself under the plan recorder.
+extern "C" int tf_nn_gather_blend_ragged_plan(const int* chunk_frames, int C, int S, int D, uint64_t single_mask, int n_edits,
+                                              char* buf, size_t len) {
+    void* const ph = reinterpret_cast<void*>((uintptr_t)1 << 12);
+    const float* const phf = reinterpret_cast<const float*>(ph);
+    TfPlanRec rec{buf, len, 0, 0};
+    if (buf && len) buf[0] = 0;
+    tf_plan_rec = &rec;
+    // the one-keyframe chunk alone of a multi-edit batch is stored in the dtype its own pass produces
+    const bool one_single = C == 1 && (single_mask & 1) && n_edits > 1;
+    const int rc = tf_nn_gather_blend_chunks_ragged(ph, ph, phf, ph, phf, ph, ph, C + 1, chunk_frames, C, S, D,
+                                                    (single_mask & 1) ? 0 : 1, single_mask, TF_BF16, TF_BF16, TF_BF16,
+                                                    one_single ? TF_BF16 : TF_F32, TF_BF16, n_edits, ph, (size_t)-1, nullptr);
+    tf_plan_rec = nullptr;
+    if (rc) return rc;
+    TF_ARG(rec.used < len, TF_ERR_WORKSPACE, "tf_nn_gather_blend_ragged_plan: the plan needs %zu bytes", rec.used + 1);
     return rec.n;
 }
 

@@ -59,13 +59,13 @@ __global__ __launch_bounds__(256) void pivot_inv_norm_kernel(const typename T::e
 // BK = D chunk per barrier interval: 64, or 128 / 256 for small problems (few workgroups, where the per-iteration
 //      global-load latency is exposed: halving the iteration count halves the run time).
 // TM = pivots per tile: 128, or 64 with BK = 256 (the LDS holds two (TM + TN) x BK stages).
-template <typename T, int WN, int BK, int TM>
+template <typename T, int WN, int BK, int TM, typename CHT = NnChunks>
 __global__ __launch_bounds__(256) void nn_search_kernel(const typename T::elem* __restrict__ tgt,
                                                         const typename T::elem* __restrict__ piv,
                                                         const float* __restrict__ inv_norm,
                                                         int32_t* __restrict__ idx_out,
                                                         NnPartial* __restrict__ part_out, int64_t n_tgt, int S,
-                                                        int D, int kf0, int kf1, int tiles_per_split, NnChunks ch) {
+                                                        int D, int kf0, int kf1, int tiles_per_split, CHT ch) {
     typedef typename T::vec8 vec8;
     constexpr int TN = 64 * WN;
     constexpr int NI = TM / 64;              // 32-pivot sub-tiles per wave
@@ -94,13 +94,15 @@ __global__ __launch_bounds__(256) void nn_search_kernel(const typename T::elem* 
     const int p = blockIdx.y;
     // chunk of the video this target panel belongs to (0 in the single-chunk call): chunk j matches keyframe
     // slots kf0 + j and kf1 + j; the first chunk of the video has ONE keyframe (tokenflow_utils.py:331-333)
-    const int chunk = blockIdx.x / ch.ppc;
+    // (ragged launches, CHT = NnRagged: the chunk comes from the panel prefix table instead of the division)
+    const NnPanel pan = nn_panel<TN>(ch, blockIdx.x);
+    const int chunk = pan.chunk;
     if (p == 1 && nn_chunk_single(ch, chunk)) return;
     const int kf = (p == 0 ? kf0 : kf1) + chunk;
     const typename T::elem* pv = piv + (int64_t)kf * S * D;
     const float* inv = inv_norm + (int64_t)kf * S;
-    const int64_t t0 = chunk * (int64_t)ch.nS + (int64_t)(blockIdx.x - chunk * ch.ppc) * TN;
-    const int64_t t_end = (chunk + 1) * (int64_t)ch.nS;   // targets of this chunk: [chunk * nS, t_end)
+    const int64_t t0 = pan.t0;
+    const int64_t t_end = pan.t_end;   // targets of this chunk: [t_end - its n * S, t_end)
 
     const int n_mt_all = (S + TM - 1) / TM;
     const int mt0 = blockIdx.z * tiles_per_split;           // this workgroup's slice of the pivot tiles
@@ -290,13 +292,13 @@ __global__ __launch_bounds__(256) void nn_search_kernel(const typename T::elem* 
 // SH (round 6, last session): the wave's 64 x 128 tile as 4 x 8 sub-tiles of v_mfma_f32_16x16x32 instead of 2 x 4 of 32x32x16 -- same
 // images, same bytes through the LDS, same matrix-pipe clocks and accumulator registers; the short shape sustains more on these
 // power-limited boxes (see nn_search_rbs_kernel).  32 features per MFMA: scores differ from the SH = false kernel's in the last bit.
-template <typename T, bool SH = false>
+template <typename T, bool SH = false, typename CHT = NnChunks>
 __global__ __launch_bounds__(512, 2) void nn_search_glds_kernel(const typename T::elem* __restrict__ tgt,
                                                                 const typename T::elem* __restrict__ piv,
                                                                 const float* __restrict__ inv_norm,
                                                                 int32_t* __restrict__ idx_out,
                                                                 NnPartial* __restrict__ part_out, int64_t n_tgt, int S,
-                                                                int D, int kf0, int kf1, int tiles_per_split, NnChunks ch) {
+                                                                int D, int kf0, int kf1, int tiles_per_split, CHT ch) {
     typedef typename T::vec8 vec8;
     typedef typename T::elem E;
     constexpr int TM = 256, TN = 256, BK = 64, NI = 2, WN = 4;
@@ -322,13 +324,14 @@ __global__ __launch_bounds__(512, 2) void nn_search_glds_kernel(const typename T
     constexpr int NB = SH ? 2 * WN : WN;        // running (max, argmax) pairs per lane: one per target sub-tile
 
     const int p = blockIdx.y;
-    const int chunk = blockIdx.x / ch.ppc;
+    const NnPanel pan = nn_panel<TN>(ch, blockIdx.x);
+    const int chunk = pan.chunk;
     if (p == 1 && nn_chunk_single(ch, chunk)) return;
     const int kf = (p == 0 ? kf0 : kf1) + chunk;
     const E* pv = piv + (int64_t)kf * S * D;
     const float* inv = inv_norm + (int64_t)kf * S;
-    const int64_t t0 = chunk * (int64_t)ch.nS + (int64_t)(blockIdx.x - chunk * ch.ppc) * TN;
-    const int64_t t_end = (chunk + 1) * (int64_t)ch.nS;
+    const int64_t t0 = pan.t0;
+    const int64_t t_end = pan.t_end;
 
     const int n_mt_all = (S + TM - 1) / TM;
     const int mt0 = blockIdx.z * tiles_per_split;
@@ -554,17 +557,18 @@ __global__ __launch_bounds__(512, 2) void nn_search_glds_kernel(const typename T
 
 // ---------------------------------------------------------------------------
 // Register-B variant for D = 16*DK: one wave = 32 targets whose B fragments stay in registers.
-template <typename T, int DK>
+template <typename T, int DK, typename CHT = NnChunks>
 __global__ __launch_bounds__(256, 3) void nn_search_rb_kernel(const typename T::elem* __restrict__ tgt,
                                                            const typename T::elem* __restrict__ piv,
                                                            const float* __restrict__ inv_norm,
                                                            int32_t* __restrict__ idx_out,
                                                            NnPartial* __restrict__ part_out, int64_t n_tgt, int S,
-                                                           int kf0, int kf1, int tiles_per_split, NnChunks ch) {
+                                                           int kf0, int kf1, int tiles_per_split, CHT ch) {
     typedef typename T::elem E;
     typedef typename T::vec8 vec8;
     constexpr int D = 16 * DK;
     constexpr int TMR = 32;                  // pivots per tile
+    constexpr int PANEL = 128;               // targets per workgroup
     constexpr int RS = D + 8;                // LDS row stride (elements): odd number of 16-B slots
     constexpr int PPR = D / 8;               // 16-B pieces per row
     constexpr int NP = (TMR * PPR + 255) / 256;
@@ -580,13 +584,14 @@ __global__ __launch_bounds__(256, 3) void nn_search_rb_kernel(const typename T::
     const int hi = lane >> 5;
     const int l31 = lane & 31;
     const int p = blockIdx.y;
-    const int chunk = blockIdx.x / ch.ppc;       // see nn_search_kernel
+    const NnPanel pan = nn_panel<PANEL>(ch, blockIdx.x);   // see nn_search_kernel
+    const int chunk = pan.chunk;
     if (p == 1 && nn_chunk_single(ch, chunk)) return;
     const int kf = (p == 0 ? kf0 : kf1) + chunk;
     const E* pv = piv + (int64_t)kf * S * D;
     const float* inv = inv_norm + (int64_t)kf * S;
-    const int64_t t_end = (chunk + 1) * (int64_t)ch.nS;
-    const int64_t t_row = chunk * (int64_t)ch.nS + (int64_t)(blockIdx.x - chunk * ch.ppc) * 128 + wave * 32 + l31;
+    const int64_t t_end = pan.t_end;
+    const int64_t t_row = pan.t0 + wave * 32 + l31;
 
     const int n_mt_all = (S + TMR - 1) / TMR;
     const int mt0 = blockIdx.z * tiles_per_split;
@@ -682,17 +687,18 @@ __global__ __launch_bounds__(256, 3) void nn_search_rb_kernel(const typename T::
 // every pivot fragment read from LDS feeds TWO MFMAs on two independent accumulator chains, and a barrier interval carries
 // twice the matrix work -- half the LDS traffic and half the barriers per MFMA; 2 waves per SIMD instead of 3.  The
 // arithmetic of a (target, pivot) pair is unchanged (same contraction order): the kernels are interchangeable bit for bit.
-template <typename T, int DK, int TT = 1>
+template <typename T, int DK, int TT = 1, typename CHT = NnChunks>
 __global__ __launch_bounds__(256, TT == 1 ? 3 : 2) void nn_search_rbg_kernel(const typename T::elem* __restrict__ tgt,
                                                            const typename T::elem* __restrict__ piv,
                                                            const float* __restrict__ inv_norm,
                                                            int32_t* __restrict__ idx_out,
                                                            NnPartial* __restrict__ part_out, int64_t n_tgt, int S,
-                                                           int kf0, int kf1, int tiles_per_split, NnChunks ch) {
+                                                           int kf0, int kf1, int tiles_per_split, CHT ch) {
     typedef typename T::elem E;
     typedef typename T::vec8 vec8;
     constexpr int D = 16 * DK;
     constexpr int TMR = 32;                  // pivots per tile
+    constexpr int PANEL = 128 * TT;          // targets per workgroup
     constexpr int RS = D;                    // LDS row stride (elements): the DMA image is dense
     static_assert((D / 8) % 8 == 0, "the swizzle permutes inside groups of 8 pieces");
     constexpr int NPIECE = TMR * D * 2 / 1024;   // 1 KB DMA pieces per tile (20 at D = 320)
@@ -709,16 +715,17 @@ __global__ __launch_bounds__(256, TT == 1 ? 3 : 2) void nn_search_rbg_kernel(con
     const int hi = lane >> 5;
     const int l31 = lane & 31;
     const int p = blockIdx.y;
-    const int chunk = blockIdx.x / ch.ppc;       // see nn_search_kernel
+    const NnPanel pan = nn_panel<PANEL>(ch, blockIdx.x);   // see nn_search_kernel
+    const int chunk = pan.chunk;
     if (p == 1 && nn_chunk_single(ch, chunk)) return;
     const int kf = (p == 0 ? kf0 : kf1) + chunk;
     const E* pv = piv + (int64_t)kf * S * D;
     const float* inv = inv_norm + (int64_t)kf * S;
-    const int64_t t_end = (chunk + 1) * (int64_t)ch.nS;
+    const int64_t t_end = pan.t_end;
     int64_t t_row[TT];
 #pragma unroll
     for (int tt = 0; tt < TT; ++tt)
-        t_row[tt] = chunk * (int64_t)ch.nS + (int64_t)(blockIdx.x - chunk * ch.ppc) * (128 * TT) + (wave * TT + tt) * 32 + l31;
+        t_row[tt] = pan.t0 + (wave * TT + tt) * 32 + l31;
 
     const int n_mt_all = (S + TMR - 1) / TMR;
     const int mt0 = blockIdx.z * tiles_per_split;
@@ -836,19 +843,20 @@ __global__ __launch_bounds__(256, TT == 1 ? 3 : 2) void nn_search_rbg_kernel(con
 // instruction sequence on the same data) and the first index wins as everywhere (ascending rows, strict '>').
 // The tile loop is software-pipelined: fragment addresses as base + immediate, a ring of fragments read ahead
 // of their MFMAs with counted waits, and half-tile phases whose argmax fold runs beside the MFMAs of the next half.
-template <typename T, int DK, int TJ = 4>
+template <typename T, int DK, int TJ = 4, typename CHT = NnChunks>
 __global__ __launch_bounds__(256, TJ == 4 ? 2 : 3) void nn_search_rbs_kernel(const typename T::elem* __restrict__ tgt,
                                                                const typename T::elem* __restrict__ piv,
                                                                const float* __restrict__ inv_norm,
                                                                int32_t* __restrict__ idx_out,
                                                                NnPartial* __restrict__ part_out, int64_t n_tgt, int S,
-                                                               int kf0, int kf1, int tiles_per_split, NnChunks ch) {
+                                                               int kf0, int kf1, int tiles_per_split, CHT ch) {
     typedef typename T::elem E;
     typedef typename T::vec8 vec8;
     constexpr int D = 16 * DK;
     constexpr int KS32 = D / 32;             // 32-wide k-steps
     static_assert(D % 32 == 0 && (D / 8) % 8 == 0, "32-wide k-steps; the swizzle permutes inside groups of 8 pieces");
     constexpr int TMR = 32;                  // pivots per tile
+    constexpr int PANEL = 64 * TJ;           // targets per workgroup
     constexpr int NPIECE = TMR * D * 2 / 1024;
     static_assert(NPIECE % 4 == 0, "pieces split evenly over the 4 waves");
     constexpr int A_ELEMS = TMR * D;
@@ -862,16 +870,17 @@ __global__ __launch_bounds__(256, TJ == 4 ? 2 : 3) void nn_search_rbs_kernel(con
     const int g = lane >> 4;      // 16-lane row: the k-block of the A / B fragments, the row group of C
     const int n16 = lane & 15;    // A: pivot row of the 16-row sub-tile; B / C: target of the 16-target sub-tile
     const int p = blockIdx.y;
-    const int chunk = blockIdx.x / ch.ppc;       // see nn_search_kernel
+    const NnPanel pan = nn_panel<PANEL>(ch, blockIdx.x);   // see nn_search_kernel
+    const int chunk = pan.chunk;
     if (p == 1 && nn_chunk_single(ch, chunk)) return;
     const int kf = (p == 0 ? kf0 : kf1) + chunk;
     const E* pv = piv + (int64_t)kf * S * D;
     const float* inv = inv_norm + (int64_t)kf * S;
-    const int64_t t_end = (chunk + 1) * (int64_t)ch.nS;
+    const int64_t t_end = pan.t_end;
     int64_t t_row[TJ];
 #pragma unroll
     for (int j = 0; j < TJ; ++j)
-        t_row[j] = chunk * (int64_t)ch.nS + (int64_t)(blockIdx.x - chunk * ch.ppc) * (64 * TJ) + wave * (16 * TJ) + 16 * j + n16;
+        t_row[j] = pan.t0 + wave * (16 * TJ) + 16 * j + n16;
 
     const int n_mt_all = (S + TMR - 1) / TMR;
     const int mt0 = blockIdx.z * tiles_per_split;
@@ -1104,23 +1113,38 @@ static int nn_min_wgs(int C) {
     return C > 1 ? env : 1024;
 }
 
+// The pivot-range split of every form but the LDS-DMA one: `wgs` = workgroups of the launch before splitting (target
+// panels of all chunks x keyframes), tm = pivots per tile.  Returns the workgroups of the split launch.
+static int64_t nn_split(NnPlan& pl, int64_t wgs, int S, int tm, int C) {
+    const int n_tiles = (S + tm - 1) / tm;
+    int splits = 1;
+    // a multi-chunk launch keeps >= 128 pivots per split: below that the per-workgroup fixed cost (target
+    // fragments, partial results, their merge) outweighs the finer tail (cfg1 level 0: 41.8 us at 128 pivots /
+    // split, 72 us at 32)
+    const int min_tiles = C > 1 ? (128 + tm - 1) / tm : 1;
+    while (wgs * splits < nn_min_wgs(C) && splits * 2 <= n_tiles && n_tiles / (splits * 2) >= min_tiles)
+        splits *= 2;
+    pl.tiles_per_split = (n_tiles + splits - 1) / splits;
+    pl.splits = (n_tiles + pl.tiles_per_split - 1) / pl.tiles_per_split;
+    return wgs * pl.splits;
+}
+// The LDS-DMA form's: one workgroup per CU, aim at >= `rounds` rounds of workgroups (tail), never below one tile per split
+static void nn_split_glds(NnPlan& pl, int64_t wgs, int S) {
+    static const int rounds = [] { const char* e = getenv("TF_NN_GLDS_ROUNDS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 3; }();
+    const int n_tiles = (S + 255) / 256;
+    int splits = 1;
+    while (wgs * splits < rounds * 256 && splits * 2 <= n_tiles) splits *= 2;
+    pl.tiles_per_split = (n_tiles + splits - 1) / splits;
+    pl.splits = (n_tiles + pl.tiles_per_split - 1) / pl.tiles_per_split;
+}
+
 // splits of the pivot range so that the grid has >= nn_min_wgs workgroups while every split keeps >= 1 tile.
 // n_tgt = targets of ONE chunk, C = chunks in the launch (grid.x = C * panels).
 static NnPlan nn_plan(int64_t n_tgt, int S, int D, int P, int C = 1) {
     NnPlan pl;
     auto shape = [&](int tn, int tm) {
         pl.panels = (n_tgt + tn - 1) / tn;
-        const int n_tiles = (S + tm - 1) / tm;
-        int splits = 1;
-        // a multi-chunk launch keeps >= 128 pivots per split: below that the per-workgroup fixed cost (target
-        // fragments, partial results, their merge) outweighs the finer tail (cfg1 level 0: 41.8 us at 128 pivots /
-        // split, 72 us at 32)
-        const int min_tiles = C > 1 ? (128 + tm - 1) / tm : 1;
-        while (pl.panels * C * P * splits < nn_min_wgs(C) && splits * 2 <= n_tiles && n_tiles / (splits * 2) >= min_tiles)
-            splits *= 2;
-        pl.tiles_per_split = (n_tiles + splits - 1) / splits;
-        pl.splits = (n_tiles + pl.tiles_per_split - 1) / pl.tiles_per_split;
-        return pl.panels * C * P * pl.splits;   // workgroups of the launch
+        return nn_split(pl, pl.panels * C * P, S, tm, C);   // workgroups of the launch
     };
 #ifndef TF_TUNE_NN_NO_GLDS   // A/B switch of tools/build_variants.sh
     // LDS-DMA kernel (256-target panels, 256-pivot tiles, one 8-wave workgroup per CU): where the launch still has
@@ -1130,17 +1154,12 @@ static NnPlan nn_plan(int64_t n_tgt, int S, int D, int P, int C = 1) {
     // keyframe (BASELINE config 1, level 0) its 32-pivot tiles are mostly prologue: 44 -> 33 us (profiles/r05_nn_glds_ab.txt)
     if (D % 64 == 0 && (D >= glds_min_d || (D == 320 && S <= 1024)) && S % 4 == 0) {
         static const int min_wgs = [] { const char* e = getenv("TF_NN_GLDS_MIN_WGS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 160; }();
-        static const int rounds = [] { const char* e = getenv("TF_NN_GLDS_ROUNDS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 3; }();
         const int64_t panels = (n_tgt + 255) / 256;
         const int n_tiles = (S + 255) / 256;
         if (panels * C * P * n_tiles >= min_wgs) {
             pl.kern = NN_GLDS;
             pl.panels = panels;
-            // one workgroup per CU: aim at >= 3 rounds of workgroups (tail), never below one tile per split
-            int splits = 1;
-            while (panels * C * P * splits < rounds * 256 && splits * 2 <= n_tiles) splits *= 2;
-            pl.tiles_per_split = (n_tiles + splits - 1) / splits;
-            pl.splits = (n_tiles + pl.tiles_per_split - 1) / pl.tiles_per_split;
+            nn_split_glds(pl, panels * C * P, S);
             return pl;
         }
     }
@@ -1180,6 +1199,30 @@ static NnPlan nn_plan(int64_t n_tgt, int S, int D, int P, int C = 1) {
     return pl;
 }
 
+// targets per panel / pivots per tile of a kernel form
+static int nn_form_tn(int kern) { return kern == NN_RB2 || kern == NN_GLDS ? 256 : kern == NN_RB || kern == NN_WIDE ? 128 : 64; }
+static int nn_form_tm(int kern) {
+    return kern == NN_RB || kern == NN_RB2 ? 32 : kern == NN_GLDS ? 256 : kern == NN_DEEP ? 64 : 128;
+}
+
+// A RAGGED launch: C chunks of frames[j] * S targets, two keyframes (the p = 1 half of a one-keyframe chunk exits at once).
+// The rule (host only, a function of the frame counts, S and D):
+//   - the kernel FORM is the one the uniform C-chunk launch takes at the MEAN chunk size, ceil(sum_j frames[j] * S / C)
+//     targets per chunk: nn_plan(mean, S, D, 2, C).kern;
+//   - grid.x = sum_j ceil(frames[j] * S / TN) panels of that form (a chunk's last panel is partial, none straddles two
+//     chunks), and the pivot-range split is the form's own rule applied to THAT workgroup count.
+// pl.panels = grid.x.  Equal frame counts never come here: the entry points hand them to the uniform launch.
+static NnPlan nn_plan_ragged(const int* frames, int C, int S, int D) {
+    int64_t rows = 0;
+    for (int j = 0; j < C; ++j) rows += (int64_t)frames[j] * S;
+    NnPlan pl = nn_plan((rows + C - 1) / C, S, D, 2, C);
+    const int tn = nn_form_tn(pl.kern);
+    pl.panels = 0;
+    for (int j = 0; j < C; ++j) pl.panels += ((int64_t)frames[j] * S + tn - 1) / tn;
+    if (pl.kern == NN_GLDS) nn_split_glds(pl, pl.panels * 2, S);
+    else nn_split(pl, pl.panels * 2, S, nn_form_tm(pl.kern), C);
+    return pl;
+}
 static int finalize(const NnPartial* part, int32_t* idx, int64_t total, int splits, hipStream_t st) {
     if (tf_plan_note("finalize")) return 0;
     hipLaunchKernelGGL(nn_finalize_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, part, idx, total,
@@ -1312,7 +1355,85 @@ int dispatch_nn(const void* tgt, const void* piv, const float* inv_norm, int32_t
     }
 }
 
+// The ragged launch (nn_plan_ragged): the NnRagged instantiation of the form's kernel, partial results only (the gather
+// merges them), P = 2.  Plan tokens are the uniform launch's with ",ragged" in the place of ",chunks".
+template <typename T>
+int dispatch_nn_ragged(const void* tgt, const void* piv, const float* inv_norm, NnPartial* ws, const int* frames, int C,
+                       int S, int D, int kf0, int kf1, hipStream_t st, uint64_t single_mask) {
+    typedef const typename T::elem* EP;
+    const NnPlan pl = nn_plan_ragged(frames, C, S, D);
+    const int splits = pl.splits, tps = pl.tiles_per_split;
+    int64_t rows = 0;
+    for (int j = 0; j < C; ++j) rows += (int64_t)frames[j] * S;
+    const dim3 grid((unsigned)pl.panels, 2u, (unsigned)splits);
+    const NnRagged ch = nn_ragged(frames, C, S, nn_form_tn(pl.kern), single_mask);
+    // kernels that take D as an argument (generic, LDS-DMA) / as a template parameter (register-B family)
+    auto go_d = [&](auto kern, const char* form, unsigned threads, size_t lds) {
+        if (tf_plan_note("%s[splits=%d,ragged]", form, splits)) return 0;
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(kern, grid, dim3(threads), lds, st, (EP)tgt, (EP)piv, inv_norm, (int32_t*)nullptr, ws, rows, S, D,
+                           kf0, kf1, tps, ch);
+        TF_LAUNCH_CHECK("tf_nn_search(ragged)");
+        return 0;
+    };
+    auto go_rb = [&](auto kern, const char* form, size_t lds) {
+        if (tf_plan_note("%s[splits=%d,ragged]", form, splits)) return 0;
+        hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, (EP)tgt, (EP)piv, inv_norm, (int32_t*)nullptr, ws, rows, S, kf0,
+                           kf1, tps, ch);
+        TF_LAUNCH_CHECK("tf_nn_search(ragged)");
+        return 0;
+    };
+    auto lds_nn = [](int tn, int bk, int tm) { return (size_t)2 * (tm + tn) * bk * 2 + 2 * tm * 4 + 2 * tn * 8; };
+    switch (pl.kern) {
+        case NN_RB:
+        case NN_RB2: {   // the choices of launch_nn_rb
+            constexpr int DK = 20;
+            const size_t lds_g = 2 * 32 * (16 * DK) * 2 + 2 * 32 * 4;
+            if (pl.kern == NN_RB2) {
+#ifndef TF_TUNE_NN_NO_RBS
+                return go_rb(nn_search_rbs_kernel<T, DK, 4, NnRagged>, "rbs<TJ=4>", lds_g);
+#else
+                return go_rb(nn_search_rbg_kernel<T, DK, 2, NnRagged>, "rbg<TT=2>", lds_g);
+#endif
+            }
+            static const bool dma = [] { const char* e = getenv("TF_NN_RB_GLDS"); return !e || atoi(e) != 0; }();
+            if (dma && S % 32 == 0) {
+#ifndef TF_TUNE_NN_NO_RBS
+                return go_rb(nn_search_rbs_kernel<T, DK, 2, NnRagged>, "rbs<TJ=2>", lds_g);
+#else
+                return go_rb(nn_search_rbg_kernel<T, DK, 1, NnRagged>, "rbg<TT=1>", lds_g);
+#endif
+            }
+            return go_rb(nn_search_rb_kernel<T, DK, NnRagged>, "rb", 2 * 32 * (16 * DK + 8) * 2 + 2 * 32 * 4);
+        }
+        case NN_GLDS:
+#ifndef TF_TUNE_NN_NO_GLDS_SH
+            return go_d(nn_search_glds_kernel<T, true, NnRagged>, "glds", 512, 2 * (256 + 256) * 64 * 2 + 2 * 256 * 4 + 4 * 256 * 8);
+#else
+            return go_d(nn_search_glds_kernel<T, false, NnRagged>, "glds", 512, 2 * (256 + 256) * 64 * 2 + 2 * 256 * 4 + 4 * 256 * 8);
+#endif
+        case NN_WIDE: return go_d(nn_search_kernel<T, 2, 64, 128, NnRagged>, "wide", 256, lds_nn(128, 64, 128));
+        case NN_DEEP: return go_d(nn_search_kernel<T, 1, 256, 64, NnRagged>, "deep", 256, lds_nn(64, 256, 64));
+        case NN_BK128: return go_d(nn_search_kernel<T, 1, 128, 128, NnRagged>, "bk128", 256, lds_nn(64, 128, 128));
+        default: return go_d(nn_search_kernel<T, 1, 64, 128, NnRagged>, "bk64", 256, lds_nn(64, 64, 128));
+    }
+}
+
 }  // namespace
+
+int tf_nn_search_partials_ragged(const void* tgt, const void* piv, const float* inv_norm, NnPartial* part,
+                                 const int* frames, int C, int S, int D, int kf0, int kf1, int dtype, hipStream_t st,
+                                 int* splits, uint64_t single_mask) {
+    *splits = nn_plan_ragged(frames, C, S, D).splits;
+    return dtype == TF_BF16 ? dispatch_nn_ragged<BF16>(tgt, piv, inv_norm, part, frames, C, S, D, kf0, kf1, st, single_mask)
+                            : dispatch_nn_ragged<F16>(tgt, piv, inv_norm, part, frames, C, S, D, kf0, kf1, st, single_mask);
+}
+
+size_t tf_nn_partials_bytes_ragged(const int* frames, int C, int S, int D) {
+    int64_t rows = 0;
+    for (int j = 0; j < C; ++j) rows += (int64_t)frames[j] * S;
+    return (size_t)nn_plan_ragged(frames, C, S, D).splits * 2 * rows * sizeof(NnPartial);
+}
 
 extern "C" int tf_pivot_inv_norm(const void* piv, float* inv_norm, int64_t rows, int D, int dtype, void* stream) {
     TF_ARG(piv && inv_norm, TF_ERR_NULL, "tf_pivot_inv_norm: null pointer");

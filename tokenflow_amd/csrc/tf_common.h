@@ -118,6 +118,67 @@ static inline NnChunks nn_chunks(int64_t nS, int ppc, uint64_t single_mask) {
 __device__ __forceinline__ bool nn_chunk_single(const NnChunks& ch, int chunk) {
     return chunk < 64 && (((chunk < 32 ? ch.single_lo : ch.single_hi) >> (chunk & 31)) & 1u);
 }
+// The target panel of a workgroup: its chunk and the targets [t0, t_end) it may touch (t0 + TN may pass t_end: the
+// chunk's last panel is partial).  TN = targets per panel of the kernel.
+struct NnPanel {
+    int chunk;
+    int64_t t0, t_end;
+};
+template <int TN>
+__device__ __forceinline__ NnPanel nn_panel(const NnChunks& ch, int bx) {
+    const int chunk = bx / ch.ppc;
+    return NnPanel{chunk, chunk * (int64_t)ch.nS + (int64_t)(bx - chunk * ch.ppc) * TN, (chunk + 1) * (int64_t)ch.nS};
+}
+
+// A launch over C <= 64 consecutive chunks of UNEQUAL frame count (tf_nn_gather_blend_chunks_ragged): the division of
+// NnChunks becomes two prefix tables that ride in the kernel-argument segment (about 0.5 KiB).  Chunk j owns targets
+// row0[j] .. row0[j + 1] - 1 and target panels panel0[j] .. panel0[j + 1] - 1 of the kernel form the launch uses; a panel
+// never straddles two chunks.  Entries behind C + 1 hold INT32_MAX, so a bisection needs no bound check.
+#define TF_RAGGED_MAX_CHUNKS 64
+struct NnRagged {
+    unsigned single_lo, single_hi;              // the single mask, as in NnChunks
+    int row0[TF_RAGGED_MAX_CHUNKS + 1];         // target prefix (total targets < 2^31, checked by the entry points)
+    int panel0[TF_RAGGED_MAX_CHUNKS + 1];       // panel prefix
+};
+__device__ __forceinline__ bool nn_chunk_single(const NnRagged& ch, int chunk) {
+    return ((chunk < 32 ? ch.single_lo : ch.single_hi) >> (chunk & 31)) & 1u;
+}
+// largest j in 0..63 with tab[j] <= x (tab ascending, tab[0] = 0 <= x): six steps.  With a workgroup-uniform x the
+// table reads are scalar loads from the kernel arguments; with a per-thread x they are vector loads of the same
+// constant memory -- never a private copy of the table.
+__device__ __forceinline__ int tf_ragged_find(const int (&tab)[TF_RAGGED_MAX_CHUNKS + 1], int x) {
+    int j = 0;
+#pragma unroll
+    for (int s = TF_RAGGED_MAX_CHUNKS / 2; s >= 1; s >>= 1)
+        if (tab[j + s] <= x) j += s;
+    return j;
+}
+template <int TN>
+__device__ __forceinline__ NnPanel nn_panel(const NnRagged& ch, int bx) {
+    const int chunk = tf_ragged_find(ch.panel0, bx);   // bx = blockIdx.x: uniform
+    return NnPanel{chunk, ch.row0[chunk] + (int64_t)(bx - ch.panel0[chunk]) * TN, (int64_t)ch.row0[chunk + 1]};
+}
+// Host side: the tables of `C` chunks of frames[j] * S targets in panels of `tn` targets.
+static inline NnRagged nn_ragged(const int* frames, int C, int S, int tn, uint64_t single_mask) {
+    NnRagged r;
+    r.single_lo = (unsigned)single_mask, r.single_hi = (unsigned)(single_mask >> 32);
+    int64_t row = 0, panel = 0;
+    for (int j = 0; j <= TF_RAGGED_MAX_CHUNKS; ++j) {
+        r.row0[j] = j <= C ? (int)row : INT32_MAX;
+        r.panel0[j] = j <= C ? (int)panel : INT32_MAX;
+        if (j < C) {
+            const int64_t t = (int64_t)frames[j] * S;
+            row += t;
+            panel += (t + tn - 1) / tn;
+        }
+    }
+    return r;
+}
+int tf_nn_search_partials_ragged(const void* tgt, const void* piv, const float* inv_norm, NnPartial* part,
+                                 const int* frames, int C, int S, int D, int kf0, int kf1, int dtype, hipStream_t st,
+                                 int* splits, uint64_t single_mask);
+size_t tf_nn_partials_bytes_ragged(const int* frames, int C, int S, int D);
+
 // Search only (no finalize launch): partial results [splits][P][C * n_tgt] into `part`; arguments already validated.
 // n_tgt = targets per chunk.
 int tf_nn_search_partials(const void* tgt, const void* piv, const float* inv_norm, NnPartial* part, int64_t n_tgt,

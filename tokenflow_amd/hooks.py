@@ -39,7 +39,7 @@ __all__ = [
     "register_pivotal", "register_batch_idx", "register_time", "load_source_latents_t",
     "register_conv_injection", "register_extended_attention_pnp", "register_extended_attention",
     "make_tokenflow_attention_block", "set_tokenflow", "isinstance_str", "batch_cosine_sim",
-    "register_frame_shard", "join_frame_shard", "register_edits", "register_segments",
+    "register_frame_shard", "join_frame_shard", "register_edits", "register_segments", "register_chunk_frames",
     "register_bank_window",
 ]
 
@@ -247,6 +247,61 @@ def _segments(module, K=None):
     if K is not None and sum(segs) != K:
         raise ValueError(f"register_segments: the segments {list(segs)} hold {sum(segs)} keyframes, the pivotal pass {K}")
     return segs
+
+
+def register_chunk_frames(model, frames_per_chunk):
+    """Ragged chunk runs (no counterpart in the reference, which drops the tail of a video whose length is no multiple of
+    batch_size): `frames_per_chunk` = the frame count of EVERY chunk of the video in global chunk order, each >= 1; `None`
+    clears.  Opt-in -- without it every path stays as it is, the error for a run whose frames do not split evenly included.
+    Sets `chunk_frames` on the 16 blocks.  With it a run pass `register_batch_idx(model, range(c0, c1))` must carry
+    sum(frames_per_chunk[c0:c1]) frames per branch (ValueError otherwise) and becomes ONE `ops.propagate_chunks_ragged`: chunk j
+    of the run blends with the weights of ITS frame count; it takes the segment-start mask where `register_segments` is
+    active and n_edits = E under `register_edits`.  A run whose chunks are of equal size issues today's ops; one-chunk
+    passes are untouched (they never needed equal sizes).
+    Not generalised, ValueError at a ragged run: a registered frame shard, the AdaLayerNormZero gated path, capture for
+    `tokenflow_amd.graphs.GraphCache` replay (and segments together with E > 1, refused as everywhere)."""
+    frames = None
+    if frames_per_chunk is not None:
+        frames = tuple(int(n) for n in frames_per_chunk)
+        if not frames or any(n < 1 for n in frames):
+            raise ValueError(f"register_chunk_frames: {list(frames)} (the frame count of every chunk, each >= 1)")
+    for tb in _hook_blocks(model.unet):
+        setattr(tb, "chunk_frames", frames)
+
+
+def _ragged_run(module, c0: int, n_chunks: int, n_frames: int):
+    """The frame counts of the chunks c0 .. c0 + n_chunks - 1 of a run pass when they are registered (register_chunk_frames)
+    AND unequal, else None = today's path; the combinations that are not generalised raise."""
+    frames = getattr(module, "chunk_frames", None)
+    if frames is None or n_chunks == 1:
+        return None
+    if c0 + n_chunks > len(frames):
+        raise ValueError(f"register_chunk_frames: chunks {c0}..{c0 + n_chunks - 1} of a video of {len(frames)} chunks")
+    run = frames[c0:c0 + n_chunks]
+    if sum(run) != n_frames:
+        raise ValueError(f"register_chunk_frames: chunks {c0}..{c0 + n_chunks - 1} hold {sum(run)} frames, the pass carries "
+                         f"{n_frames} per branch")
+    if len(set(run)) == 1:
+        return None
+    if n_chunks > 64:
+        raise ValueError(f"register_chunk_frames: a ragged run of {n_chunks} chunks (at most 64 per pass)")
+    if module.__dict__.get("_tf_shard") is not None:
+        raise ValueError("register_chunk_frames: ragged chunk runs on a registered frame shard are not supported")
+    if getattr(module, "use_ada_layer_norm_zero", False):
+        raise ValueError("register_chunk_frames: ragged chunk runs through the AdaLayerNormZero gated path are not supported")
+    if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+        raise ValueError("register_chunk_frames: a ragged chunk run cannot be captured for graphs.py replay yet")
+    return run
+
+
+def _ragged_weights(run, device) -> torch.Tensor:
+    """One blend weight per frame of a ragged run: the cached `_blend_weights(n_j)` of every chunk, concatenated; cached per
+    (frames of the run, device)."""
+    key = (tuple(run), str(device))
+    w = _weights_cache.get(key)
+    if w is None:
+        w = _weights_cache[key] = torch.cat([_blend_weights(n, device) for n in run]).contiguous()
+    return w
 
 
 def register_bank_window(model, radius, edits=False, anchors=None, anchor_edits=False, shard=False, anchor_shard=False,
@@ -880,6 +935,8 @@ def make_tokenflow_attention_block(block_class: Type[torch.nn.Module]) -> Type[t
                 if batch_size % nbr:
                     raise ValueError(f"register_edits: batch of {batch_size} does not hold {nbr} branches ({E} edits)")
             n_frames = batch_size // nbr
+            if not self.pivotal_pass and getattr(self, "chunk_frames", None) is not None:
+                _ragged_run(self, *_chunk_run(self.batch_idx), n_frames)   # register_chunk_frames: the refusals, up front
             if self.pivotal_pass:
                 # register_bank_window: the combinations that are not generalised raise here
                 if _bank_window(self, n_frames) is not None:
@@ -978,7 +1035,9 @@ def make_tokenflow_attention_block(block_class: Type[torch.nn.Module]) -> Type[t
                 segs = _segments(self, self.kf_attn_output.shape[0] // nbr)
                 starts = {0} if segs is None else {sum(segs[:v]) for v in range(len(segs))}
                 first_single = c0 in starts
-                if n_frames % n_chunks:
+                # register_chunk_frames: the frame counts of a run of UNEQUAL chunks (None: today's paths)
+                run = _ragged_run(self, c0, n_chunks, n_frames)
+                if run is None and n_frames % n_chunks:
                     raise ValueError(f"{n_frames} frames per branch do not split into {n_chunks} chunks")
                 n = n_frames // n_chunks
                 kf = self.kf_attn_output
@@ -1021,7 +1080,7 @@ def make_tokenflow_attention_block(block_class: Type[torch.nn.Module]) -> Type[t
                 two = n_chunks > 1 or not first_single           # some chunk blends two keyframes (a run: its fp32 form)
                 blend_dtype = torch.float32 if two else kf.dtype
                 out_dtype = torch.promote_types(blend_dtype, hidden_states.dtype)
-                w = _blend_weights(n, kf.device) if two else None
+                w = (_ragged_weights(run, kf.device) if run is not None else _blend_weights(n, kf.device)) if two else None
                 resid = hidden_states.reshape(batch_size, sequence_length, dim)
                 if kf_base:      # gated copy holds keyframes kf_base.. only: search the same window of the pivots
                     piv, inv = piv[kf_base:kf_base + K], inv[kf_base:kf_base + K]
@@ -1038,7 +1097,11 @@ def make_tokenflow_attention_block(block_class: Type[torch.nn.Module]) -> Type[t
                     ndt = _fused_norm_dtype(nxt[1], resid, out_dtype)
                     if ndt is not None and ops.norm_fusable(kf, resid, out_dtype, 2 if two else 1, ndt):
                         fuse = (nxt[1].weight, nxt[1].bias, nxt[1].eps, ndt)
-                if E > 1:       # one search, one gather over all 1 + 2E branches
+                if run is not None:     # chunks of unequal frame count: one ragged search, one ragged gather
+                    single_mask = sum(1 << j for j in range(n_chunks) if c0 + j in starts)
+                    res = ops.propagate_chunks_ragged(tgt, piv, inv, kf, w, run, s0, single_mask, resid, out_dtype, n_edits=E,
+                                                      norm=fuse)
+                elif E > 1:     # one search, one gather over all 1 + 2E branches
                     res = ops.propagate_chunks_edits(tgt, piv, inv, kf, w, n, n_chunks, s0 - kf_base, first_single, resid,
                                                      out_dtype, E, norm=fuse)
                 elif n_chunks == 1:

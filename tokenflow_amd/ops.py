@@ -393,6 +393,24 @@ def propagate_segments_plan(n: int, n_chunks: int, S: int, D: int, single_mask: 
                         int(n_chunks), S, D, _single_mask("propagate_segments_plan", single_mask, int(n_chunks)))
 
 
+def _chunk_frames(what: str, chunk_frames):
+    """The frames per chunk of a ragged run as (list, ctypes int array): 1 .. 64 chunks of >= 1 frames."""
+    fr = [int(x) for x in chunk_frames]
+    if not 1 <= len(fr) <= 64 or any(x < 1 for x in fr):
+        raise ValueError(f"{what}: chunk_frames {fr} (1 .. 64 chunks of >= 1 frames)")
+    return fr, (ctypes.c_int * len(fr))(*fr)
+
+
+def propagate_ragged_plan(chunk_frames, S: int, D: int, single_mask: int = 0, n_edits: int = 1) -> list:
+    """The launches of `propagate_chunks_ragged` (tf_nn_gather_blend_ragged_plan).  Equal frame counts: the tokens of
+    `propagate_segments_plan` (n_edits = 1) or `propagate_edits_plan`.  Otherwise the search token of the form the rule
+    picks -- `nn_plan(ceil(sum(frames) * S / C), S, D, 2, C)`'s, the split taken on the real panel count -- with ',ragged'
+    in its brackets, then 'gather[branches=B,ragged]'.  Host only."""
+    fr, arr = _chunk_frames("propagate_ragged_plan", chunk_frames)
+    return _plan_tokens("tf_nn_gather_blend_ragged_plan", _lib.load().tf_nn_gather_blend_ragged_plan, arr, len(fr), S, D,
+                        _single_mask("propagate_ragged_plan", single_mask, len(fr)), int(n_edits))
+
+
 def nn_plan(n_tgt: int, S: int, D: int, P: int, C: int = 1) -> list:
     """The search launches of `nn_search` (C = 1) or of `propagate_chunks` over C > 1 chunks of n_tgt targets (P = 2),
     as tokens (tf_nn_search_plan: e.g. ['glds[splits=2]', 'finalize']).  Host only: needs no GPU."""
@@ -1830,6 +1848,64 @@ def propagate_chunks_edits(tgt: torch.Tensor, piv: torch.Tensor, inv_norm: torch
                 nout.data_ptr(), ndt, ws.data_ptr(), ws.numel())
         return out, nout
     _launch(dev, "tf_nn_gather_blend_chunks_edits", lib.tf_nn_gather_blend_chunks_edits, *head, ws.data_ptr(), ws.numel())
+    return out
+
+
+def propagate_chunks_ragged(tgt: torch.Tensor, piv: torch.Tensor, inv_norm: torch.Tensor, kf_out: torch.Tensor,
+                            w: torch.Tensor, chunk_frames, slot0: int, single_mask: int,
+                            residual: Optional[torch.Tensor], out_dtype: torch.dtype, n_edits: int = 1, norm=None,
+                            out: Optional[torch.Tensor] = None, norm_out: Optional[torch.Tensor] = None):
+    """`propagate_chunks_segments` / `propagate_chunks_edits` for a run of chunks of UNEQUAL frame count
+    (tf_nn_gather_blend_chunks_ragged): chunk j has chunk_frames[j] frames, F = sum(chunk_frames).  tgt [F*S, D] chunk-major,
+    kf_out [B*K, S, D], residual / result [B*F, S, D] with B = 1 + 2*n_edits; slot0 and single_mask as
+    `propagate_chunks_segments` (n_edits > 1: bit 0 only).  w: F floats on the device, one per frame of the run -- the blend
+    weights of each chunk's own size, concatenated.  The rows of chunk j are what `propagate` computes on that chunk alone
+    with n = chunk_frames[j].  ONE search and one gather; equal frame counts issue today's calls.  norm=, out / norm_out as
+    `propagate`."""
+    what = "propagate_chunks_ragged"
+    fr, arr = _chunk_frames(what, chunk_frames)
+    C, F = len(fr), sum(fr)
+    m = _single_mask(what, single_mask, C)
+    E = int(n_edits)
+    if not 1 <= E <= _lib.TF_MAX_EDITS:
+        raise ValueError(f"{what}: n_edits={n_edits} (1 .. {_lib.TF_MAX_EDITS})")
+    if E > 1 and m > 1:
+        raise ValueError(f"{what}: single_mask {m:#x} with {E} edits (segments and multi-edit batches do not combine)")
+    if C == 1:      # one chunk: today's one-chunk paths
+        if E == 1:
+            return propagate_chunks(tgt, piv, inv_norm, kf_out, w, fr[0], 1, slot0, bool(m & 1), residual, out_dtype,
+                                    norm=norm, out=out, norm_out=norm_out)
+        return propagate_chunks_edits(tgt, piv, inv_norm, kf_out, w, fr[0], 1, slot0, bool(m & 1), residual, out_dtype, E,
+                                      norm=norm, out=out, norm_out=norm_out)
+    dev = _need_gpu(tgt, piv, inv_norm, kf_out, w, residual, out, norm_out)
+    if norm_out is not None and norm is None:
+        raise ValueError(f"{what}: `norm_out` without `norm`")
+    lib = _lib.load()
+    nbr = 1 + 2 * E
+    tgt, piv, kf_out = tgt.contiguous(), piv.contiguous(), kf_out.contiguous()
+    K, S, D = piv.shape
+    if (tgt.dtype != piv.dtype or tgt.shape != (F * S, D) or kf_out.shape != (nbr * K, S, D) or w is None
+            or w.dtype != torch.float32 or w.numel() != F or not w.is_contiguous()
+            or slot0 + C > K or slot0 < (0 if m & 1 else 1)):
+        raise ValueError(f"{what}: bad arguments")
+    if residual is not None:
+        residual = residual.contiguous()
+        if residual.shape != (nbr * F, S, D):
+            raise ValueError(f"{what}: residual must be [B*sum(chunk_frames), S, D]")
+    single_dtype = kf_out.dtype if residual is None else torch.promote_types(kf_out.dtype, residual.dtype)
+    out = _caller_buffer(what, "out", out, (nbr * F, S, D), out_dtype, kf_out.device)
+    ws = _workspace(lib.tf_nn_gather_blend_ragged_workspace_bytes(arr, C, S, D), tgt.device, "nn")
+    head = (tgt.data_ptr(), piv.data_ptr(), inv_norm.data_ptr(), kf_out.data_ptr(), w.data_ptr(),
+            residual.data_ptr() if residual is not None else 0, out.data_ptr(), K, arr, C, S, D, int(slot0), m, _DT[tgt.dtype],
+            _DT[kf_out.dtype], _DT[residual.dtype] if residual is not None else 0, _DT[out_dtype], _DT[single_dtype], E)
+    if norm is not None:
+        if not norm_fusable(kf_out, residual, out_dtype, 2, norm[3]):
+            raise TypeError(f"{what}: these dtypes have no fused-norm form (ops.norm_fusable)")
+        g, b, eps, wdt, nout, ndt, _keep = _norm_args(norm, kf_out, (nbr * F, S, D), norm_out)
+        _launch(dev, "tf_nn_gather_blend_chunks_norm_ragged", lib.tf_nn_gather_blend_chunks_norm_ragged, *head, g, b, eps, wdt,
+                nout.data_ptr(), ndt, ws.data_ptr(), ws.numel())
+        return out, nout
+    _launch(dev, "tf_nn_gather_blend_chunks_ragged", lib.tf_nn_gather_blend_chunks_ragged, *head, ws.data_ptr(), ws.numel())
     return out
 
 
