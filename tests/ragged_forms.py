@@ -22,7 +22,7 @@ SMALL = [(45, 320, "rb"), (96, 320, "rbs<TJ=2>"), (45, 72, "bk64"), (45, 640, "b
 LARGE = [(11808, 320, "rbs<TJ=4>"), (2180, 640, "glds"), (4040, 72, "wide")]
 SMALL_FRAMES = [[3, 1, 2, 5], [1, 1, 1], [2, 5, 1, 3, 2]]
 LARGE_FRAMES = [[2, 3, 2], [3, 2, 3, 2]]
-# targets per panel of a form (nn_search.hip: nn_form_tn)
+# targets per panel of a form (nn_search.hip: `tn` of the form descriptions)
 PANEL = {"rb": 128, "rbs<TJ=2>": 128, "rbs<TJ=4>": 256, "glds": 256, "wide": 128, "bk64": 64, "bk128": 64, "deep": 64}
 
 

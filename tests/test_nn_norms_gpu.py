@@ -34,7 +34,7 @@ from tests.test_kernels_gpu import NN_TAU
 
 pytestmark = pytest.mark.gpu
 
-# pivot rows per tile of every kernel family (csrc/nn_search.hip: TMR = 32, TM of launch_nn<...>, 256 of the LDS-DMA kernel)
+# pivot rows per tile of every kernel family (csrc/nn_search.hip: `tm` of the form descriptions)
 PIVOT_TILE = {"rb": 32, "rbs<TJ=2>": 32, "rbs<TJ=4>": 32, "glds": 256, "wide": 128, "bk64": 128, "bk128": 128, "deep": 64}
 TIE_EXPONENTS = (-3, 1, 2)
 GUARD_ROWS, GUARD_SCALE = 256, 2.0 ** -8

@@ -392,29 +392,28 @@ void launch_gb(const GbArgs& a) {
     const int64_t total = (int64_t)a.n * a.S * (a.D >> 3);
     int64_t blocks = (total + 255) / 256;
     if (blocks > 256 * 16) blocks = 256 * 16;
-    auto go = [&](auto kern, int kf1) {
+    auto go = [&](auto kern, int kf1, auto* desc) {   // desc: the descriptor type of `kern` (gb_desc)
         hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, a.st, (const TIn*)a.kf_out, a.idx, a.part,
-                           a.splits, a.w, (const TRes*)a.resid, (TOut*)a.out, a.K, a.n, a.S, a.D, a.kf0, kf1, a.ch, a.nb);
+                           a.splits, a.w, (const TRes*)a.resid, (TOut*)a.out, a.K, a.n, a.S, a.D, a.kf0, kf1, gb_desc(a, desc),
+                           a.nb);
     };
+    const GbChunks* const chunks = nullptr;
+    const GbRagged* const ragged = nullptr;
     if (tf_plan_note(a.rg ? "gather[branches=%d,ragged]" : "gather[branches=%d]", a.nb)) return;
     if (a.rg) {   // ragged call: the chunk forms over the prefix table
-        auto go_rg = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, a.st, (const TIn*)a.kf_out, a.idx, a.part,
-                               a.splits, a.w, (const TRes*)a.resid, (TOut*)a.out, a.K, a.n, a.S, a.D, a.kf0, a.kf1, *a.rg, a.nb);
-        };
-        if (a.dyn) go_rg(gather_blend_kernel<TIn, TRes, TOut, 2, true, true, true, GbRagged>);
-        else go_rg(gather_blend_kernel<TIn, TRes, TOut, 2, true, true, false, GbRagged>);
+        if (a.dyn) go(gather_blend_kernel<TIn, TRes, TOut, 2, true, true, true, GbRagged>, a.kf1, ragged);
+        else go(gather_blend_kernel<TIn, TRes, TOut, 2, true, true, false, GbRagged>, a.kf1, ragged);
     } else if (a.dyn) {   // multi-edit batch: the chunk form, or the one-keyframe chunk alone
-        if (a.ch.nc > 0) go(gather_blend_kernel<TIn, TRes, TOut, 2, true, true, true>, a.kf1);
-        else go(gather_blend_kernel<TIn, TRes, TOut, 1, true, false, true>, a.kf0);
+        if (a.ch.nc > 0) go(gather_blend_kernel<TIn, TRes, TOut, 2, true, true, true>, a.kf1, chunks);
+        else go(gather_blend_kernel<TIn, TRes, TOut, 1, true, false, true>, a.kf0, chunks);
     } else if (a.ch.nc > 0) {
-        go(gather_blend_kernel<TIn, TRes, TOut, 2, true, true>, a.kf1);
+        go(gather_blend_kernel<TIn, TRes, TOut, 2, true, true>, a.kf1, chunks);
     } else if (a.part) {
-        if (a.P == 2) go(gather_blend_kernel<TIn, TRes, TOut, 2, true>, a.kf1);
-        else go(gather_blend_kernel<TIn, TRes, TOut, 1, true>, a.kf0);
+        if (a.P == 2) go(gather_blend_kernel<TIn, TRes, TOut, 2, true>, a.kf1, chunks);
+        else go(gather_blend_kernel<TIn, TRes, TOut, 1, true>, a.kf0, chunks);
     } else {
-        if (a.P == 2) go(gather_blend_kernel<TIn, TRes, TOut, 2, false>, a.kf1);
-        else go(gather_blend_kernel<TIn, TRes, TOut, 1, false>, a.kf0);
+        if (a.P == 2) go(gather_blend_kernel<TIn, TRes, TOut, 2, false>, a.kf1, chunks);
+        else go(gather_blend_kernel<TIn, TRes, TOut, 1, false>, a.kf0, chunks);
     }
 }
 
@@ -437,14 +436,23 @@ void dispatch_res(const GbArgs& a, int res_dtype, int out_dtype) {
     }
 }
 
+void dispatch_in(const GbArgs& a, int in_dtype, int res_dtype, int out_dtype) {
+    switch (in_dtype) {
+        case TF_BF16: dispatch_res<__bf16>(a, res_dtype, out_dtype); break;
+        case TF_F16: dispatch_res<_Float16>(a, res_dtype, out_dtype); break;
+        default: dispatch_res<float>(a, res_dtype, out_dtype); break;
+    }
+}
+
+bool gb_okdt(int d) { return d == TF_BF16 || d == TF_F16 || d == TF_F32; }
+
 }  // namespace
 
 extern "C" int tf_gather_blend(const void* kf_out, const int32_t* idx, const float* w, const void* resid, void* out,
                                int K, int n, int S, int D, int P, int kf0, int kf1, int in_dtype, int res_dtype,
                                int out_dtype, void* stream) {
     TF_ARG(kf_out && idx && out && (P == 1 || w), TF_ERR_NULL, "tf_gather_blend: null pointer");
-    auto okdt = [](int d) { return d == TF_BF16 || d == TF_F16 || d == TF_F32; };
-    TF_ARG(okdt(in_dtype) && okdt(out_dtype) && (!resid || okdt(res_dtype)), TF_ERR_DTYPE,
+    TF_ARG(gb_okdt(in_dtype) && gb_okdt(out_dtype) && (!resid || gb_okdt(res_dtype)), TF_ERR_DTYPE,
            "tf_gather_blend: dtypes in=%d res=%d out=%d", in_dtype, res_dtype, out_dtype);
     TF_ARG(K > 0 && n > 0 && S > 0 && D > 0 && D % 8 == 0 && (P == 1 || P == 2) && kf0 >= 0 && kf0 < K &&
                (P == 1 || (kf1 >= 0 && kf1 < K)),
@@ -453,11 +461,7 @@ extern "C" int tf_gather_blend(const void* kf_out, const int32_t* idx, const flo
            "tf_gather_blend: tensors not 16-byte aligned");
     GbArgs a{kf_out, idx, nullptr, 0, w, resid, out, K, n, S, D, P, kf0, kf1, reinterpret_cast<hipStream_t>(stream),
              GbChunks{0, 0, 0}};
-    switch (in_dtype) {
-        case TF_BF16: dispatch_res<__bf16>(a, res_dtype, out_dtype); break;
-        case TF_F16: dispatch_res<_Float16>(a, res_dtype, out_dtype); break;
-        default: dispatch_res<float>(a, res_dtype, out_dtype); break;
-    }
+    dispatch_in(a, in_dtype, res_dtype, out_dtype);
     TF_LAUNCH_CHECK("tf_gather_blend");
     return 0;
 }
@@ -475,64 +479,106 @@ struct NormArgs {   // the block's next LayerNorm, fused behind the gather (all 
     float eps = 0.f;
     int w_dtype = 0, dtype = 0;
 };
+// of a *_norm* entry point, in the order these have the arguments
+static NormArgs norm_args(const void* gamma, const void* beta, float eps, int w_dtype, void* norm_out, int norm_dtype) {
+    NormArgs nm;
+    nm.out = norm_out, nm.gamma = gamma, nm.beta = beta, nm.eps = eps, nm.w_dtype = w_dtype, nm.dtype = norm_dtype;
+    return nm;
+}
 
-static int nn_gather_blend_impl(const char* name, const void* tgt, const void* piv, const float* inv_norm,
-                                const void* kf_out, const float* w, const void* resid, void* out, int K, int n, int S,
-                                int D, int P, int kf0, int kf1, int search_dtype, int in_dtype, int res_dtype,
-                                int out_dtype, void* ws, size_t ws_bytes, void* stream, const NormArgs& nm,
-                                int n_edits = 0) {   // n_edits >= 1: a multi-edit batch of 1 + 2*n_edits branches
-    TF_ARG(tgt && piv && inv_norm && kf_out && out && ws && (P == 1 || w), TF_ERR_NULL, "%s: null pointer", name);
-    TF_ARG(search_dtype == TF_BF16 || search_dtype == TF_F16, TF_ERR_DTYPE, "%s: search dtype %d (bf16/f16 only)", name,
-           search_dtype);
-    auto okdt = [](int d) { return d == TF_BF16 || d == TF_F16 || d == TF_F32; };
-    TF_ARG(okdt(in_dtype) && okdt(out_dtype) && (!resid || okdt(res_dtype)), TF_ERR_DTYPE,
-           "%s: dtypes in=%d res=%d out=%d", name, in_dtype, res_dtype, out_dtype);
-    TF_ARG(K > 0 && n > 0 && S > 0 && D > 0 && D % 8 == 0 && (P == 1 || P == 2) && kf0 >= 0 && kf0 < K &&
-               (P == 1 || (kf1 >= 0 && kf1 < K)),
-           TF_ERR_SHAPE, "%s: K=%d n=%d S=%d D=%d P=%d kf=(%d,%d)", name, K, n, S, D, P, kf0, kf1);
-    TF_ARG(tf_aligned16(tgt) && tf_aligned16(piv) && tf_aligned16(kf_out) && tf_aligned16(out) &&
-               tf_aligned16(resid) && tf_aligned16(ws) && tf_aligned16(inv_norm),
-           TF_ERR_ALIGN, "%s: tensors not 16-byte aligned (inv_norm included)", name);
+// What every tf_nn_gather_blend* entry point is called with; `name` is the entry point's own, for its refusals.
+struct GbCall {
+    const char* name;
+    const void *tgt, *piv;
+    const float* inv_norm;
+    const void* kf_out;
+    const float* w;
+    const void* resid;
+    void* out;
+    int search_dtype, in_dtype, res_dtype, out_dtype;
+    void* ws;
+    size_t ws_bytes;
+    void* stream;
+    NormArgs nm;
+};
+
+// The refusals the three impls below share, in two halves: each impl has its shape refusals where it always had them,
+// between the halves or in front of both.  First half: null pointers (w_ok: the blend weights, which a one-keyframe call
+// goes without), the search dtype, the tensor dtypes (single_dtype: null for a call that has none).
+static int gb_check_types(const GbCall& c, bool w_ok, const int* single_dtype) {
+    TF_ARG(c.tgt && c.piv && c.inv_norm && c.kf_out && c.out && c.ws && w_ok, TF_ERR_NULL, "%s: null pointer", c.name);
+    TF_ARG(c.search_dtype == TF_BF16 || c.search_dtype == TF_F16, TF_ERR_DTYPE, "%s: search dtype %d (bf16/f16 only)", c.name,
+           c.search_dtype);
+    const bool ok = gb_okdt(c.in_dtype) && gb_okdt(c.out_dtype) && (!c.resid || gb_okdt(c.res_dtype));
+    if (single_dtype)
+        TF_ARG(ok && gb_okdt(*single_dtype), TF_ERR_DTYPE, "%s: dtypes in=%d res=%d out=%d single=%d", c.name, c.in_dtype,
+               c.res_dtype, c.out_dtype, *single_dtype);
+    else
+        TF_ARG(ok, TF_ERR_DTYPE, "%s: dtypes in=%d res=%d out=%d", c.name, c.in_dtype, c.res_dtype, c.out_dtype);
+    return 0;
+}
+// Second half: 16-byte alignment, the fused norm of a P-keyframe gather (norm_result: how the impl words the result type
+// it needs) and the workspace of `need` bytes.
+static int gb_check_rest(const GbCall& c, int D, int P, const char* norm_result, size_t need) {
+    TF_ARG(tf_aligned16(c.tgt) && tf_aligned16(c.piv) && tf_aligned16(c.kf_out) && tf_aligned16(c.out) &&
+               tf_aligned16(c.resid) && tf_aligned16(c.ws) && tf_aligned16(c.inv_norm),
+           TF_ERR_ALIGN, "%s: tensors not 16-byte aligned (inv_norm included)", c.name);
+    const NormArgs& nm = c.nm;
     if (nm.out) {
-        TF_ARG((!nm.gamma && !nm.beta) || okdt(nm.w_dtype), TF_ERR_DTYPE, "%s: norm weight dtype %d", name, nm.w_dtype);
-        TF_ARG(gbn_supported(D, P, in_dtype, res_dtype, out_dtype, nm.dtype, resid != nullptr), TF_ERR_DTYPE,
-               "%s: the fused norm needs a 16-bit cached output, a residual and a norm output of that same type, and "
-               "the result in fp32 (two keyframes) or that type (one); D <= 1536", name);
+        TF_ARG((!nm.gamma && !nm.beta) || gb_okdt(nm.w_dtype), TF_ERR_DTYPE, "%s: norm weight dtype %d", c.name, nm.w_dtype);
+        TF_ARG(gbn_supported(D, P, c.in_dtype, c.res_dtype, c.out_dtype, nm.dtype, c.resid != nullptr), TF_ERR_DTYPE,
+               "%s: the fused norm needs a 16-bit cached output, a residual and a norm output of that same type%s; D <= 1536",
+               c.name, norm_result);
         TF_ARG(tf_aligned16(nm.out) && tf_aligned16(nm.gamma) && tf_aligned16(nm.beta), TF_ERR_ALIGN,
-               "%s: norm tensors not 16-byte aligned", name);
+               "%s: norm tensors not 16-byte aligned", c.name);
     }
-    const int64_t n_tgt = (int64_t)n * S;
-    TF_ARG(ws_bytes >= tf_nn_gather_blend_workspace_bytes(n_tgt, S, D, P), TF_ERR_WORKSPACE,
-           "%s: workspace %zu < %zu bytes", name, ws_bytes, tf_nn_gather_blend_workspace_bytes(n_tgt, S, D, P));
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    NnPartial* part = reinterpret_cast<NnPartial*>(ws);
-    int splits = 1;
-    const int rc = tf_nn_search_partials(tgt, piv, inv_norm, part, n_tgt, S, D, P, kf0, kf1, search_dtype, st, &splits);
-    if (rc) return rc;
-    GbArgs a{kf_out, nullptr, part, splits, w, resid, out, K, n, S, D, P, kf0, kf1, st, GbChunks{0, 0, 0}};
-    if (n_edits > 0) a.nb = 1 + 2 * n_edits, a.dyn = true;
+    TF_ARG(c.ws_bytes >= need, TF_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", c.name, c.ws_bytes, need);
+    return 0;
+}
+
+// The gather behind the search of all three impls: plain or with the fused norm.  (While a plan is recorded nothing was
+// launched: no launch check.)
+static int run_gather(const GbCall& c, GbArgs& a) {
+    const NormArgs& nm = c.nm;
     if (nm.out) {
         a.norm_out = nm.out, a.gamma = nm.gamma, a.beta = nm.beta, a.w_dtype = nm.w_dtype, a.eps = nm.eps;
-        if (in_dtype == TF_BF16) dispatch_gbn<__bf16>(a);
+        if (c.in_dtype == TF_BF16) dispatch_gbn<__bf16>(a);
         else dispatch_gbn<_Float16>(a);
     } else {
-        switch (in_dtype) {
-            case TF_BF16: dispatch_res<__bf16>(a, res_dtype, out_dtype); break;
-            case TF_F16: dispatch_res<_Float16>(a, res_dtype, out_dtype); break;
-            default: dispatch_res<float>(a, res_dtype, out_dtype); break;
-        }
+        dispatch_in(a, c.in_dtype, c.res_dtype, c.out_dtype);
     }
-    if (tf_plan_rec) return 0;   // plan recording: nothing was launched
-    TF_LAUNCH_CHECK(name);
+    if (tf_plan_rec) return 0;
+    TF_LAUNCH_CHECK(c.name);
     return 0;
+}
+
+static int nn_gather_blend_impl(const GbCall& c, int K, int n, int S, int D, int P, int kf0, int kf1,
+                                int n_edits = 0) {   // n_edits >= 1: a multi-edit batch of 1 + 2*n_edits branches
+    if (const int rc = gb_check_types(c, P == 1 || c.w, nullptr)) return rc;
+    TF_ARG(K > 0 && n > 0 && S > 0 && D > 0 && D % 8 == 0 && (P == 1 || P == 2) && kf0 >= 0 && kf0 < K &&
+               (P == 1 || (kf1 >= 0 && kf1 < K)),
+           TF_ERR_SHAPE, "%s: K=%d n=%d S=%d D=%d P=%d kf=(%d,%d)", c.name, K, n, S, D, P, kf0, kf1);
+    const int64_t n_tgt = (int64_t)n * S;
+    if (const int rc = gb_check_rest(c, D, P, ", and the result in fp32 (two keyframes) or that type (one)",
+                                     tf_nn_gather_blend_workspace_bytes(n_tgt, S, D, P)))
+        return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(c.stream);
+    NnPartial* part = reinterpret_cast<NnPartial*>(c.ws);
+    int splits = 1;
+    if (const int rc = tf_nn_search_partials(c.tgt, c.piv, c.inv_norm, part, n_tgt, S, D, P, kf0, kf1, c.search_dtype, st, &splits))
+        return rc;
+    GbArgs a{c.kf_out, nullptr, part, splits, c.w, c.resid, c.out, K, n, S, D, P, kf0, kf1, st, GbChunks{0, 0, 0}};
+    if (n_edits > 0) a.nb = 1 + 2 * n_edits, a.dyn = true;
+    return run_gather(c, a);
 }
 
 extern "C" int tf_nn_gather_blend(const void* tgt, const void* piv, const float* inv_norm, const void* kf_out,
                                   const float* w, const void* resid, void* out, int K, int n, int S, int D, int P,
                                   int kf0, int kf1, int search_dtype, int in_dtype, int res_dtype, int out_dtype,
                                   void* ws, size_t ws_bytes, void* stream) {
-    return nn_gather_blend_impl("tf_nn_gather_blend", tgt, piv, inv_norm, kf_out, w, resid, out, K, n, S, D, P, kf0, kf1,
-                                search_dtype, in_dtype, res_dtype, out_dtype, ws, ws_bytes, stream, NormArgs{});
+    return nn_gather_blend_impl({"tf_nn_gather_blend", tgt, piv, inv_norm, kf_out, w, resid, out, search_dtype, in_dtype,
+                                 res_dtype, out_dtype, ws, ws_bytes, stream, NormArgs{}},
+                                K, n, S, D, P, kf0, kf1);
 }
 
 extern "C" int tf_nn_gather_blend_norm(const void* tgt, const void* piv, const float* inv_norm, const void* kf_out,
@@ -541,10 +587,10 @@ extern "C" int tf_nn_gather_blend_norm(const void* tgt, const void* piv, const f
                                        const void* gamma, const void* beta, float eps, int w_dtype, void* norm_out,
                                        int norm_dtype, void* ws, size_t ws_bytes, void* stream) {
     TF_ARG(norm_out, TF_ERR_NULL, "tf_nn_gather_blend_norm: null norm_out");
-    NormArgs nm;
-    nm.out = norm_out, nm.gamma = gamma, nm.beta = beta, nm.eps = eps, nm.w_dtype = w_dtype, nm.dtype = norm_dtype;
-    return nn_gather_blend_impl("tf_nn_gather_blend_norm", tgt, piv, inv_norm, kf_out, w, resid, out, K, n, S, D, P, kf0,
-                                kf1, search_dtype, in_dtype, res_dtype, out_dtype, ws, ws_bytes, stream, nm);
+    return nn_gather_blend_impl({"tf_nn_gather_blend_norm", tgt, piv, inv_norm, kf_out, w, resid, out, search_dtype, in_dtype,
+                                 res_dtype, out_dtype, ws, ws_bytes, stream,
+                                 norm_args(gamma, beta, eps, w_dtype, norm_out, norm_dtype)},
+                                K, n, S, D, P, kf0, kf1);
 }
 
 extern "C" size_t tf_nn_gather_blend_chunks_workspace_bytes(int64_t n_tgt_chunk, int S, int D, int C) {
@@ -553,64 +599,32 @@ extern "C" size_t tf_nn_gather_blend_chunks_workspace_bytes(int64_t n_tgt_chunk,
     return b < 256 ? 256 : b;
 }
 
-static int nn_gather_blend_chunks_impl(const char* name, const void* tgt, const void* piv, const float* inv_norm,
-                                       const void* kf_out, const float* w, const void* resid, void* out, int K, int n,
-                                       int C, int S, int D, int slot0, uint64_t single_mask, int search_dtype,
-                                       int in_dtype, int res_dtype, int out_dtype, int single_dtype, void* ws,
-                                       size_t ws_bytes, void* stream, const NormArgs& nm, int n_edits = 0,
+static int nn_gather_blend_chunks_impl(const GbCall& c, int K, int n, int C, int S, int D, int slot0, uint64_t single_mask,
+                                       int single_dtype, int n_edits = 0,
                                        bool segments = false) {   // segments: the mask of the *_segments entry points
-    TF_ARG(tgt && piv && inv_norm && kf_out && out && ws && w, TF_ERR_NULL, "%s: null pointer", name);
-    TF_ARG(search_dtype == TF_BF16 || search_dtype == TF_F16, TF_ERR_DTYPE, "%s: search dtype %d (bf16/f16 only)", name,
-           search_dtype);
-    auto okdt = [](int d) { return d == TF_BF16 || d == TF_F16 || d == TF_F32; };
-    TF_ARG(okdt(in_dtype) && okdt(out_dtype) && okdt(single_dtype) && (!resid || okdt(res_dtype)), TF_ERR_DTYPE,
-           "%s: dtypes in=%d res=%d out=%d single=%d", name, in_dtype, res_dtype, out_dtype, single_dtype);
+    if (const int rc = gb_check_types(c, c.w != nullptr, &single_dtype)) return rc;
     // chunk j reads keyframe slots slot0 + j and slot0 + j - 1 (the one-keyframe chunk only slot0)
     const bool first_single = single_mask & 1;
     TF_ARG(K > 0 && n > 0 && C > 0 && S > 0 && D > 0 && D % 8 == 0 && slot0 + C <= K &&
                slot0 >= (first_single ? 0 : 1) && (segments || C > 1 || !first_single),
-           TF_ERR_SHAPE, "%s: K=%d n=%d C=%d S=%d D=%d slot0=%d first_single=%d", name, K, n, C, S, D, slot0,
+           TF_ERR_SHAPE, "%s: K=%d n=%d C=%d S=%d D=%d slot0=%d first_single=%d", c.name, K, n, C, S, D, slot0,
            (int)first_single);
     // a chunk that starts a keyframe segment matches slot0 + j alone: one bit per chunk of the call
     TF_ARG(!segments || (C <= 64 && (C == 64 || !(single_mask >> C))), TF_ERR_SHAPE,
-           "%s: C=%d single_mask=0x%llx (C <= 64, no bit at or above C)", name, C, (unsigned long long)single_mask);
-    TF_ARG(tf_aligned16(tgt) && tf_aligned16(piv) && tf_aligned16(kf_out) && tf_aligned16(out) &&
-               tf_aligned16(resid) && tf_aligned16(ws) && tf_aligned16(inv_norm),
-           TF_ERR_ALIGN, "%s: tensors not 16-byte aligned (inv_norm included)", name);
-    if (nm.out) {
-        TF_ARG((!nm.gamma && !nm.beta) || okdt(nm.w_dtype), TF_ERR_DTYPE, "%s: norm weight dtype %d", name, nm.w_dtype);
-        TF_ARG(gbn_supported(D, 2, in_dtype, res_dtype, out_dtype, nm.dtype, resid != nullptr), TF_ERR_DTYPE,
-               "%s: the fused norm needs a 16-bit cached output, a residual and a norm output of that same type and the "
-               "result in fp32; D <= 1536", name);
-        TF_ARG(tf_aligned16(nm.out) && tf_aligned16(nm.gamma) && tf_aligned16(nm.beta), TF_ERR_ALIGN,
-               "%s: norm tensors not 16-byte aligned", name);
-    }
+           "%s: C=%d single_mask=0x%llx (C <= 64, no bit at or above C)", c.name, C, (unsigned long long)single_mask);
     const int64_t n_tgt = (int64_t)n * S;   // per chunk
-    TF_ARG(ws_bytes >= tf_nn_gather_blend_chunks_workspace_bytes(n_tgt, S, D, C), TF_ERR_WORKSPACE,
-           "%s: workspace %zu < %zu bytes", name, ws_bytes, tf_nn_gather_blend_chunks_workspace_bytes(n_tgt, S, D, C));
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    NnPartial* part = reinterpret_cast<NnPartial*>(ws);
+    if (const int rc = gb_check_rest(c, D, 2, " and the result in fp32", tf_nn_gather_blend_chunks_workspace_bytes(n_tgt, S, D, C)))
+        return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(c.stream);
+    NnPartial* part = reinterpret_cast<NnPartial*>(c.ws);
     int splits = 1;
-    const int rc = tf_nn_search_partials(tgt, piv, inv_norm, part, n_tgt, S, D, 2, slot0, slot0 - 1, search_dtype, st,
-                                         &splits, C, single_mask);
-    if (rc) return rc;
-    GbArgs a{kf_out, nullptr, part, splits, w, resid, out, K, n * C, S, D, 2, slot0, slot0 - 1, st,
+    if (const int rc = tf_nn_search_partials(c.tgt, c.piv, c.inv_norm, part, n_tgt, S, D, 2, slot0, slot0 - 1, c.search_dtype, st,
+                                             &splits, C, single_mask))
+        return rc;
+    GbArgs a{c.kf_out, nullptr, part, splits, c.w, c.resid, c.out, K, n * C, S, D, 2, slot0, slot0 - 1, st,
              GbChunks{n, single_dtype, single_mask}};
     if (n_edits > 0) a.nb = 1 + 2 * n_edits, a.dyn = true;
-    if (nm.out) {
-        a.norm_out = nm.out, a.gamma = nm.gamma, a.beta = nm.beta, a.w_dtype = nm.w_dtype, a.eps = nm.eps;
-        if (in_dtype == TF_BF16) dispatch_gbn<__bf16>(a);
-        else dispatch_gbn<_Float16>(a);
-    } else {
-        switch (in_dtype) {
-            case TF_BF16: dispatch_res<__bf16>(a, res_dtype, out_dtype); break;
-            case TF_F16: dispatch_res<_Float16>(a, res_dtype, out_dtype); break;
-            default: dispatch_res<float>(a, res_dtype, out_dtype); break;
-        }
-    }
-    if (tf_plan_rec) return 0;   // plan recording: nothing was launched
-    TF_LAUNCH_CHECK(name);
-    return 0;
+    return run_gather(c, a);
 }
 
 extern "C" int tf_nn_gather_blend_chunks(const void* tgt, const void* piv, const float* inv_norm, const void* kf_out,
@@ -618,9 +632,9 @@ extern "C" int tf_nn_gather_blend_chunks(const void* tgt, const void* piv, const
                                          int D, int slot0, int first_single, int search_dtype, int in_dtype,
                                          int res_dtype, int out_dtype, int single_dtype, void* ws, size_t ws_bytes,
                                          void* stream) {
-    return nn_gather_blend_chunks_impl("tf_nn_gather_blend_chunks", tgt, piv, inv_norm, kf_out, w, resid, out, K, n, C, S,
-                                       D, slot0, first_single ? 1 : 0, search_dtype, in_dtype, res_dtype, out_dtype,
-                                       single_dtype, ws, ws_bytes, stream, NormArgs{});
+    return nn_gather_blend_chunks_impl({"tf_nn_gather_blend_chunks", tgt, piv, inv_norm, kf_out, w, resid, out, search_dtype,
+                                        in_dtype, res_dtype, out_dtype, ws, ws_bytes, stream, NormArgs{}},
+                                       K, n, C, S, D, slot0, first_single ? 1 : 0, single_dtype);
 }
 
 extern "C" int tf_nn_gather_blend_chunks_norm(const void* tgt, const void* piv, const float* inv_norm,
@@ -630,11 +644,10 @@ extern "C" int tf_nn_gather_blend_chunks_norm(const void* tgt, const void* piv, 
                                               const void* gamma, const void* beta, float eps, int w_dtype,
                                               void* norm_out, int norm_dtype, void* ws, size_t ws_bytes, void* stream) {
     TF_ARG(norm_out, TF_ERR_NULL, "tf_nn_gather_blend_chunks_norm: null norm_out");
-    NormArgs nm;
-    nm.out = norm_out, nm.gamma = gamma, nm.beta = beta, nm.eps = eps, nm.w_dtype = w_dtype, nm.dtype = norm_dtype;
-    return nn_gather_blend_chunks_impl("tf_nn_gather_blend_chunks_norm", tgt, piv, inv_norm, kf_out, w, resid, out, K, n,
-                                       C, S, D, slot0, first_single ? 1 : 0, search_dtype, in_dtype, res_dtype, out_dtype,
-                                       single_dtype, ws, ws_bytes, stream, nm);
+    return nn_gather_blend_chunks_impl({"tf_nn_gather_blend_chunks_norm", tgt, piv, inv_norm, kf_out, w, resid, out,
+                                        search_dtype, in_dtype, res_dtype, out_dtype, ws, ws_bytes, stream,
+                                        norm_args(gamma, beta, eps, w_dtype, norm_out, norm_dtype)},
+                                       K, n, C, S, D, slot0, first_single ? 1 : 0, single_dtype);
 }
 
 // Keyframe segments (include/tokenflow_hip.h): the chunk forms with one bit per chunk in the place of first_single -- every
@@ -644,9 +657,9 @@ extern "C" int tf_nn_gather_blend_chunks_segments(const void* tgt, const void* p
                                                   int n, int C, int S, int D, int slot0, uint64_t single_mask,
                                                   int search_dtype, int in_dtype, int res_dtype, int out_dtype,
                                                   int single_dtype, void* ws, size_t ws_bytes, void* stream) {
-    return nn_gather_blend_chunks_impl("tf_nn_gather_blend_chunks_segments", tgt, piv, inv_norm, kf_out, w, resid, out, K, n,
-                                       C, S, D, slot0, single_mask, search_dtype, in_dtype, res_dtype, out_dtype,
-                                       single_dtype, ws, ws_bytes, stream, NormArgs{}, 0, true);
+    return nn_gather_blend_chunks_impl({"tf_nn_gather_blend_chunks_segments", tgt, piv, inv_norm, kf_out, w, resid, out,
+                                        search_dtype, in_dtype, res_dtype, out_dtype, ws, ws_bytes, stream, NormArgs{}},
+                                       K, n, C, S, D, slot0, single_mask, single_dtype, 0, true);
 }
 
 extern "C" int tf_nn_gather_blend_chunks_norm_segments(const void* tgt, const void* piv, const float* inv_norm,
@@ -657,51 +670,43 @@ extern "C" int tf_nn_gather_blend_chunks_norm_segments(const void* tgt, const vo
                                                        int w_dtype, void* norm_out, int norm_dtype, void* ws,
                                                        size_t ws_bytes, void* stream) {
     TF_ARG(norm_out, TF_ERR_NULL, "tf_nn_gather_blend_chunks_norm_segments: null norm_out");
-    NormArgs nm;
-    nm.out = norm_out, nm.gamma = gamma, nm.beta = beta, nm.eps = eps, nm.w_dtype = w_dtype, nm.dtype = norm_dtype;
-    return nn_gather_blend_chunks_impl("tf_nn_gather_blend_chunks_norm_segments", tgt, piv, inv_norm, kf_out, w, resid, out,
-                                       K, n, C, S, D, slot0, single_mask, search_dtype, in_dtype, res_dtype, out_dtype,
-                                       single_dtype, ws, ws_bytes, stream, nm, 0, true);
+    return nn_gather_blend_chunks_impl({"tf_nn_gather_blend_chunks_norm_segments", tgt, piv, inv_norm, kf_out, w, resid, out,
+                                        search_dtype, in_dtype, res_dtype, out_dtype, ws, ws_bytes, stream,
+                                        norm_args(gamma, beta, eps, w_dtype, norm_out, norm_dtype)},
+                                       K, n, C, S, D, slot0, single_mask, single_dtype, 0, true);
 }
+
+// placeholder tensors of the *_plan queries: aligned, never dereferenced
+static void* const gb_ph = reinterpret_cast<void*>((uintptr_t)1 << 12);
+static const float* const gb_phf = reinterpret_cast<const float*>(gb_ph);
 
 // Launch plan of tf_nn_gather_blend_chunks_segments (host only): the entry point itself under the plan recorder.
 extern "C" int tf_nn_gather_blend_segments_plan(int n, int C, int S, int D, uint64_t single_mask, char* buf, size_t len) {
     TF_ARG(n > 0 && C > 0 && S > 0 && D > 0 && D % 8 == 0, TF_ERR_SHAPE,
            "tf_nn_gather_blend_segments_plan: n=%d C=%d S=%d D=%d", n, C, S, D);
-    void* const ph = reinterpret_cast<void*>((uintptr_t)1 << 12);
-    const float* const phf = reinterpret_cast<const float*>(ph);
-    TfPlanRec rec{buf, len, 0, 0};
-    if (buf && len) buf[0] = 0;
-    tf_plan_rec = &rec;
-    const int rc = tf_nn_gather_blend_chunks_segments(ph, ph, phf, ph, phf, ph, ph, C + 1, n, C, S, D, (single_mask & 1) ? 0 : 1,
-                                                      single_mask, TF_BF16, TF_BF16, TF_BF16, TF_F32, TF_BF16, ph,
-                                                      (size_t)-1, nullptr);
-    tf_plan_rec = nullptr;
-    if (rc) return rc;
-    TF_ARG(rec.used < len, TF_ERR_WORKSPACE, "tf_nn_gather_blend_segments_plan: the plan needs %zu bytes", rec.used + 1);
-    return rec.n;
+    return tf_record_plan("tf_nn_gather_blend_segments_plan", buf, len, [&] {
+        return tf_nn_gather_blend_chunks_segments(gb_ph, gb_ph, gb_phf, gb_ph, gb_phf, gb_ph, gb_ph, C + 1, n, C, S, D,
+                                                  (single_mask & 1) ? 0 : 1, single_mask, TF_BF16, TF_BF16, TF_BF16, TF_F32,
+                                                  TF_BF16, gb_ph, (size_t)-1, nullptr);
+    });
 }
 
 // Multi-edit batches (include/tokenflow_hip.h): the chunk forms over B = 1 + 2*n_edits branches.  ONE search (the launches of the
 // 3-branch call: the search reads the source branch only), then the gather loops the B branches on the same candidates.
 // C == 1 is served by the one-chunk forms (the one-keyframe chunk 0 of the video: P = 1; any other chunk: P = 2).
-static int nn_gather_blend_edits(const char* name, const void* tgt, const void* piv, const float* inv_norm,
-                                 const void* kf_out, const float* w, const void* resid, void* out, int K, int n, int C, int S,
-                                 int D, int slot0, int first_single, int search_dtype, int in_dtype, int res_dtype,
-                                 int out_dtype, int single_dtype, void* ws, size_t ws_bytes, void* stream,
-                                 const NormArgs& nm, int n_edits) {
-    TF_ARG(n_edits >= 1 && n_edits <= TF_MAX_EDITS, TF_ERR_SHAPE, "%s: n_edits=%d (1 .. %d)", name, n_edits, TF_MAX_EDITS);
+static int nn_gather_blend_edits(const GbCall& c, int K, int n, int C, int S, int D, int slot0, int first_single,
+                                 int single_dtype, int n_edits) {
+    TF_ARG(n_edits >= 1 && n_edits <= TF_MAX_EDITS, TF_ERR_SHAPE, "%s: n_edits=%d (1 .. %d)", c.name, n_edits, TF_MAX_EDITS);
     if (C == 1 && first_single) {
-        TF_ARG(slot0 >= 0 && slot0 < K, TF_ERR_SHAPE, "%s: slot0=%d outside the %d keyframes", name, slot0, K);
-        TF_ARG(out_dtype == single_dtype, TF_ERR_DTYPE,
-               "%s: the one-keyframe chunk alone is stored in the dtype its own pass produces (out=%d single=%d)", name,
-               out_dtype, single_dtype);
-        return nn_gather_blend_impl(name, tgt, piv, inv_norm, kf_out, nullptr, resid, out, K, n, S, D, 1, slot0, 0,
-                                    search_dtype, in_dtype, res_dtype, out_dtype, ws, ws_bytes, stream, nm, n_edits);
+        TF_ARG(slot0 >= 0 && slot0 < K, TF_ERR_SHAPE, "%s: slot0=%d outside the %d keyframes", c.name, slot0, K);
+        TF_ARG(c.out_dtype == single_dtype, TF_ERR_DTYPE,
+               "%s: the one-keyframe chunk alone is stored in the dtype its own pass produces (out=%d single=%d)", c.name,
+               c.out_dtype, single_dtype);
+        GbCall one = c;
+        one.w = nullptr;
+        return nn_gather_blend_impl(one, K, n, S, D, 1, slot0, 0, n_edits);
     }
-    return nn_gather_blend_chunks_impl(name, tgt, piv, inv_norm, kf_out, w, resid, out, K, n, C, S, D, slot0,
-                                       first_single ? 1 : 0, search_dtype, in_dtype, res_dtype, out_dtype, single_dtype, ws,
-                                       ws_bytes, stream, nm, n_edits);
+    return nn_gather_blend_chunks_impl(c, K, n, C, S, D, slot0, first_single ? 1 : 0, single_dtype, n_edits);
 }
 
 extern "C" int tf_nn_gather_blend_chunks_edits(const void* tgt, const void* piv, const float* inv_norm, const void* kf_out,
@@ -709,9 +714,9 @@ extern "C" int tf_nn_gather_blend_chunks_edits(const void* tgt, const void* piv,
                                                int D, int slot0, int first_single, int search_dtype, int in_dtype,
                                                int res_dtype, int out_dtype, int single_dtype, int n_edits, void* ws,
                                                size_t ws_bytes, void* stream) {
-    return nn_gather_blend_edits("tf_nn_gather_blend_chunks_edits", tgt, piv, inv_norm, kf_out, w, resid, out, K, n, C, S, D,
-                                 slot0, first_single, search_dtype, in_dtype, res_dtype, out_dtype, single_dtype, ws,
-                                 ws_bytes, stream, NormArgs{}, n_edits);
+    return nn_gather_blend_edits({"tf_nn_gather_blend_chunks_edits", tgt, piv, inv_norm, kf_out, w, resid, out, search_dtype,
+                                  in_dtype, res_dtype, out_dtype, ws, ws_bytes, stream, NormArgs{}},
+                                 K, n, C, S, D, slot0, first_single, single_dtype, n_edits);
 }
 
 extern "C" int tf_nn_gather_blend_chunks_norm_edits(const void* tgt, const void* piv, const float* inv_norm,
@@ -722,11 +727,10 @@ extern "C" int tf_nn_gather_blend_chunks_norm_edits(const void* tgt, const void*
                                                     float eps, int w_dtype, void* norm_out, int norm_dtype, void* ws,
                                                     size_t ws_bytes, void* stream) {
     TF_ARG(norm_out, TF_ERR_NULL, "tf_nn_gather_blend_chunks_norm_edits: null norm_out");
-    NormArgs nm;
-    nm.out = norm_out, nm.gamma = gamma, nm.beta = beta, nm.eps = eps, nm.w_dtype = w_dtype, nm.dtype = norm_dtype;
-    return nn_gather_blend_edits("tf_nn_gather_blend_chunks_norm_edits", tgt, piv, inv_norm, kf_out, w, resid, out, K, n, C,
-                                 S, D, slot0, first_single, search_dtype, in_dtype, res_dtype, out_dtype, single_dtype, ws,
-                                 ws_bytes, stream, nm, n_edits);
+    return nn_gather_blend_edits({"tf_nn_gather_blend_chunks_norm_edits", tgt, piv, inv_norm, kf_out, w, resid, out,
+                                  search_dtype, in_dtype, res_dtype, out_dtype, ws, ws_bytes, stream,
+                                  norm_args(gamma, beta, eps, w_dtype, norm_out, norm_dtype)},
+                                 K, n, C, S, D, slot0, first_single, single_dtype, n_edits);
 }
 
 // Launch plan of tf_nn_gather_blend_chunks_edits (host only): the entry point itself under the plan recorder.
@@ -734,20 +738,12 @@ extern "C" int tf_nn_gather_blend_edits_plan(int n, int C, int S, int D, int fir
                                              size_t len) {
     TF_ARG(n > 0 && C > 0 && S > 0 && D > 0 && D % 8 == 0, TF_ERR_SHAPE, "tf_nn_gather_blend_edits_plan: n=%d C=%d S=%d D=%d",
            n, C, S, D);
-    void* const ph = reinterpret_cast<void*>((uintptr_t)1 << 12);
-    const float* const phf = reinterpret_cast<const float*>(ph);
-    TfPlanRec rec{buf, len, 0, 0};
-    if (buf && len) buf[0] = 0;
-    tf_plan_rec = &rec;
-    const int K = C + 1;
-    const int rc = tf_nn_gather_blend_chunks_edits(ph, ph, phf, ph, phf, ph, ph, K, n, C, S, D, first_single ? 0 : 1,
-                                                   first_single, TF_BF16, TF_BF16, TF_BF16,
-                                                   (C == 1 && first_single) ? TF_BF16 : TF_F32, TF_BF16, n_edits, ph,
-                                                   (size_t)-1, nullptr);
-    tf_plan_rec = nullptr;
-    if (rc) return rc;
-    TF_ARG(rec.used < len, TF_ERR_WORKSPACE, "tf_nn_gather_blend_edits_plan: the plan needs %zu bytes", rec.used + 1);
-    return rec.n;
+    return tf_record_plan("tf_nn_gather_blend_edits_plan", buf, len, [&] {
+        return tf_nn_gather_blend_chunks_edits(gb_ph, gb_ph, gb_phf, gb_ph, gb_phf, gb_ph, gb_ph, C + 1, n, C, S, D,
+                                               first_single ? 0 : 1, first_single, TF_BF16, TF_BF16, TF_BF16,
+                                               (C == 1 && first_single) ? TF_BF16 : TF_F32, TF_BF16, n_edits, gb_ph, (size_t)-1,
+                                               nullptr);
+    });
 }
 
 // Ragged chunk runs (include/tokenflow_hip.h): chunk j of the call has its own frame count.  Equal counts ARE today's calls
@@ -791,55 +787,30 @@ extern "C" size_t tf_nn_gather_blend_ragged_workspace_bytes(const int* chunk_fra
     return b < 256 ? 256 : b;
 }
 
-static int nn_gather_blend_ragged_impl(const char* name, const void* tgt, const void* piv, const float* inv_norm,
-                                       const void* kf_out, const float* w, const void* resid, void* out, int K,
-                                       const int* frames, int C, int S, int D, int slot0, uint64_t single_mask,
-                                       int search_dtype, int in_dtype, int res_dtype, int out_dtype, int single_dtype,
-                                       int n_edits, void* ws, size_t ws_bytes, void* stream, const NormArgs& nm) {
+static int nn_gather_blend_ragged_impl(const GbCall& c, int K, const int* frames, int C, int S, int D, int slot0,
+                                       uint64_t single_mask, int single_dtype, int n_edits) {
     int64_t rows = 0;
-    const int rc0 = ragged_check(name, frames, C, S, D, single_mask, &rows);
-    if (rc0) return rc0;
-    TF_ARG(n_edits >= 1 && n_edits <= TF_MAX_EDITS, TF_ERR_SHAPE, "%s: n_edits=%d (1 .. %d)", name, n_edits, TF_MAX_EDITS);
+    if (const int rc = ragged_check(c.name, frames, C, S, D, single_mask, &rows)) return rc;
+    TF_ARG(n_edits >= 1 && n_edits <= TF_MAX_EDITS, TF_ERR_SHAPE, "%s: n_edits=%d (1 .. %d)", c.name, n_edits, TF_MAX_EDITS);
     TF_ARG(n_edits == 1 || single_mask <= 1, TF_ERR_SHAPE,
-           "%s: single_mask=0x%llx with %d edits (segments and multi-edit batches do not combine: bit 0 only)", name,
+           "%s: single_mask=0x%llx with %d edits (segments and multi-edit batches do not combine: bit 0 only)", c.name,
            (unsigned long long)single_mask, n_edits);
     const bool first_single = single_mask & 1;
     TF_ARG(K > 0 && slot0 + C <= K && slot0 >= (first_single ? 0 : 1), TF_ERR_SHAPE, "%s: K=%d C=%d slot0=%d first_single=%d",
-           name, K, C, slot0, (int)first_single);
+           c.name, K, C, slot0, (int)first_single);
     if (ragged_uniform(frames, C)) {   // today's call: same launches, same plan tokens, same bits
-        if (n_edits == 1)
-            return nn_gather_blend_chunks_impl(name, tgt, piv, inv_norm, kf_out, w, resid, out, K, frames[0], C, S, D, slot0,
-                                               single_mask, search_dtype, in_dtype, res_dtype, out_dtype, single_dtype, ws,
-                                               ws_bytes, stream, nm, 0, true);
-        return nn_gather_blend_edits(name, tgt, piv, inv_norm, kf_out, w, resid, out, K, frames[0], C, S, D, slot0,
-                                     first_single, search_dtype, in_dtype, res_dtype, out_dtype, single_dtype, ws, ws_bytes,
-                                     stream, nm, n_edits);
+        if (n_edits == 1) return nn_gather_blend_chunks_impl(c, K, frames[0], C, S, D, slot0, single_mask, single_dtype, 0, true);
+        return nn_gather_blend_edits(c, K, frames[0], C, S, D, slot0, first_single, single_dtype, n_edits);
     }
-    TF_ARG(tgt && piv && inv_norm && kf_out && out && ws && w, TF_ERR_NULL, "%s: null pointer", name);
-    TF_ARG(search_dtype == TF_BF16 || search_dtype == TF_F16, TF_ERR_DTYPE, "%s: search dtype %d (bf16/f16 only)", name,
-           search_dtype);
-    auto okdt = [](int d) { return d == TF_BF16 || d == TF_F16 || d == TF_F32; };
-    TF_ARG(okdt(in_dtype) && okdt(out_dtype) && okdt(single_dtype) && (!resid || okdt(res_dtype)), TF_ERR_DTYPE,
-           "%s: dtypes in=%d res=%d out=%d single=%d", name, in_dtype, res_dtype, out_dtype, single_dtype);
-    TF_ARG(tf_aligned16(tgt) && tf_aligned16(piv) && tf_aligned16(kf_out) && tf_aligned16(out) &&
-               tf_aligned16(resid) && tf_aligned16(ws) && tf_aligned16(inv_norm),
-           TF_ERR_ALIGN, "%s: tensors not 16-byte aligned (inv_norm included)", name);
-    if (nm.out) {
-        TF_ARG((!nm.gamma && !nm.beta) || okdt(nm.w_dtype), TF_ERR_DTYPE, "%s: norm weight dtype %d", name, nm.w_dtype);
-        TF_ARG(gbn_supported(D, 2, in_dtype, res_dtype, out_dtype, nm.dtype, resid != nullptr), TF_ERR_DTYPE,
-               "%s: the fused norm needs a 16-bit cached output, a residual and a norm output of that same type and the "
-               "result in fp32; D <= 1536", name);
-        TF_ARG(tf_aligned16(nm.out) && tf_aligned16(nm.gamma) && tf_aligned16(nm.beta), TF_ERR_ALIGN,
-               "%s: norm tensors not 16-byte aligned", name);
-    }
-    const size_t need = tf_nn_gather_blend_ragged_workspace_bytes(frames, C, S, D);
-    TF_ARG(ws_bytes >= need, TF_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", name, ws_bytes, need);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    NnPartial* part = reinterpret_cast<NnPartial*>(ws);
+    if (const int rc = gb_check_types(c, c.w != nullptr, &single_dtype)) return rc;
+    if (const int rc = gb_check_rest(c, D, 2, " and the result in fp32", tf_nn_gather_blend_ragged_workspace_bytes(frames, C, S, D)))
+        return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(c.stream);
+    NnPartial* part = reinterpret_cast<NnPartial*>(c.ws);
     int splits = 1;
-    const int rc = tf_nn_search_partials_ragged(tgt, piv, inv_norm, part, frames, C, S, D, slot0, slot0 - 1, search_dtype, st,
-                                                &splits, single_mask);
-    if (rc) return rc;
+    if (const int rc = tf_nn_search_partials_ragged(c.tgt, c.piv, c.inv_norm, part, frames, C, S, D, slot0, slot0 - 1,
+                                                    c.search_dtype, st, &splits, single_mask))
+        return rc;
     GbRagged rg;
     rg.single_dtype = single_dtype, rg.single_mask = single_mask;
     int64_t row = 0;
@@ -847,23 +818,11 @@ static int nn_gather_blend_ragged_impl(const char* name, const void* tgt, const 
         rg.row0[j] = j <= C ? (int)row : INT32_MAX;
         if (j < C) row += (int64_t)frames[j] * S;
     }
-    GbArgs a{kf_out, nullptr, part, splits, w, resid, out, K, (int)(rows / S), S, D, 2, slot0, slot0 - 1, st, GbChunks{0, 0, 0}};
+    GbArgs a{c.kf_out, nullptr, part, splits, c.w, c.resid, c.out, K, (int)(rows / S), S, D, 2, slot0, slot0 - 1, st,
+             GbChunks{0, 0, 0}};
     a.rg = &rg;
     a.nb = 1 + 2 * n_edits, a.dyn = n_edits > 1;
-    if (nm.out) {
-        a.norm_out = nm.out, a.gamma = nm.gamma, a.beta = nm.beta, a.w_dtype = nm.w_dtype, a.eps = nm.eps;
-        if (in_dtype == TF_BF16) dispatch_gbn<__bf16>(a);
-        else dispatch_gbn<_Float16>(a);
-    } else {
-        switch (in_dtype) {
-            case TF_BF16: dispatch_res<__bf16>(a, res_dtype, out_dtype); break;
-            case TF_F16: dispatch_res<_Float16>(a, res_dtype, out_dtype); break;
-            default: dispatch_res<float>(a, res_dtype, out_dtype); break;
-        }
-    }
-    if (tf_plan_rec) return 0;   // plan recording: nothing was launched
-    TF_LAUNCH_CHECK(name);
-    return 0;
+    return run_gather(c, a);
 }
 
 extern "C" int tf_nn_gather_blend_chunks_ragged(const void* tgt, const void* piv, const float* inv_norm, const void* kf_out,
@@ -871,9 +830,9 @@ extern "C" int tf_nn_gather_blend_chunks_ragged(const void* tgt, const void* piv
                                                 int C, int S, int D, int slot0, uint64_t single_mask, int search_dtype,
                                                 int in_dtype, int res_dtype, int out_dtype, int single_dtype, int n_edits,
                                                 void* ws, size_t ws_bytes, void* stream) {
-    return nn_gather_blend_ragged_impl("tf_nn_gather_blend_chunks_ragged", tgt, piv, inv_norm, kf_out, w, resid, out, K,
-                                       chunk_frames, C, S, D, slot0, single_mask, search_dtype, in_dtype, res_dtype, out_dtype,
-                                       single_dtype, n_edits, ws, ws_bytes, stream, NormArgs{});
+    return nn_gather_blend_ragged_impl({"tf_nn_gather_blend_chunks_ragged", tgt, piv, inv_norm, kf_out, w, resid, out,
+                                        search_dtype, in_dtype, res_dtype, out_dtype, ws, ws_bytes, stream, NormArgs{}},
+                                       K, chunk_frames, C, S, D, slot0, single_mask, single_dtype, n_edits);
 }
 
 extern "C" int tf_nn_gather_blend_chunks_norm_ragged(const void* tgt, const void* piv, const float* inv_norm,
@@ -884,30 +843,22 @@ extern "C" int tf_nn_gather_blend_chunks_norm_ragged(const void* tgt, const void
                                                      const void* beta, float eps, int w_dtype, void* norm_out, int norm_dtype,
                                                      void* ws, size_t ws_bytes, void* stream) {
     TF_ARG(norm_out, TF_ERR_NULL, "tf_nn_gather_blend_chunks_norm_ragged: null norm_out");
-    NormArgs nm;
-    nm.out = norm_out, nm.gamma = gamma, nm.beta = beta, nm.eps = eps, nm.w_dtype = w_dtype, nm.dtype = norm_dtype;
-    return nn_gather_blend_ragged_impl("tf_nn_gather_blend_chunks_norm_ragged", tgt, piv, inv_norm, kf_out, w, resid, out, K,
-                                       chunk_frames, C, S, D, slot0, single_mask, search_dtype, in_dtype, res_dtype, out_dtype,
-                                       single_dtype, n_edits, ws, ws_bytes, stream, nm);
+    return nn_gather_blend_ragged_impl({"tf_nn_gather_blend_chunks_norm_ragged", tgt, piv, inv_norm, kf_out, w, resid, out,
+                                        search_dtype, in_dtype, res_dtype, out_dtype, ws, ws_bytes, stream,
+                                        norm_args(gamma, beta, eps, w_dtype, norm_out, norm_dtype)},
+                                       K, chunk_frames, C, S, D, slot0, single_mask, single_dtype, n_edits);
 }
 
 // Launch plan of tf_nn_gather_blend_chunks_ragged (host only): the entry point itself under the plan recorder.
 extern "C" int tf_nn_gather_blend_ragged_plan(const int* chunk_frames, int C, int S, int D, uint64_t single_mask, int n_edits,
                                               char* buf, size_t len) {
-    void* const ph = reinterpret_cast<void*>((uintptr_t)1 << 12);
-    const float* const phf = reinterpret_cast<const float*>(ph);
-    TfPlanRec rec{buf, len, 0, 0};
-    if (buf && len) buf[0] = 0;
-    tf_plan_rec = &rec;
     // the one-keyframe chunk alone of a multi-edit batch is stored in the dtype its own pass produces
     const bool one_single = C == 1 && (single_mask & 1) && n_edits > 1;
-    const int rc = tf_nn_gather_blend_chunks_ragged(ph, ph, phf, ph, phf, ph, ph, C + 1, chunk_frames, C, S, D,
-                                                    (single_mask & 1) ? 0 : 1, single_mask, TF_BF16, TF_BF16, TF_BF16,
-                                                    one_single ? TF_BF16 : TF_F32, TF_BF16, n_edits, ph, (size_t)-1, nullptr);
-    tf_plan_rec = nullptr;
-    if (rc) return rc;
-    TF_ARG(rec.used < len, TF_ERR_WORKSPACE, "tf_nn_gather_blend_ragged_plan: the plan needs %zu bytes", rec.used + 1);
-    return rec.n;
+    return tf_record_plan("tf_nn_gather_blend_ragged_plan", buf, len, [&] {
+        return tf_nn_gather_blend_chunks_ragged(gb_ph, gb_ph, gb_phf, gb_ph, gb_phf, gb_ph, gb_ph, C + 1, chunk_frames, C, S, D,
+                                                (single_mask & 1) ? 0 : 1, single_mask, TF_BF16, TF_BF16, TF_BF16,
+                                                one_single ? TF_BF16 : TF_F32, TF_BF16, n_edits, gb_ph, (size_t)-1, nullptr);
+    });
 }
 
 extern "C" int tf_inject_copy(void* x, int64_t elems_per_branch, int elem_bytes, void* stream) {

@@ -1085,6 +1085,92 @@ __global__ __launch_bounds__(256) void nn_finalize_kernel(const NnPartial* __res
     idx_out[g] = b.i;
 }
 
+// ---- the kernel forms ---------------------------------------------------------------------------
+// One description per form: targets per panel (tn), pivots per tile (tm), threads, dynamic LDS bytes, the name in the
+// plan token, whether D is a kernel argument (d_arg; the register-B family has it as a template parameter), whether
+// the launcher raises the kernel's dynamic-LDS limit first (lds_attr: the forms that can pass the default 64 KiB) and
+// the kernel itself for an element type T and a chunk descriptor CHT (NnChunks / NnRagged).  The plan and the launcher
+// read a form's geometry from here and nowhere else.
+template <int WN, int BK, int TM>
+struct NnGeneric {
+    static constexpr int tn = 64 * WN, tm = TM, threads = 256;
+    static constexpr size_t lds = 2 * (TM + tn) * BK * 2 + 2 * TM * 4 + 2 * tn * 8;
+    static constexpr bool d_arg = true, lds_attr = true;
+    template <typename T, typename CHT>
+    static constexpr auto kernel() { return nn_search_kernel<T, WN, BK, TM, CHT>; }
+};
+struct NnWide : NnGeneric<2, 64, 128> { static constexpr const char* name = "wide"; };
+struct NnDeep : NnGeneric<1, 256, 64> { static constexpr const char* name = "deep"; };
+struct NnBk128 : NnGeneric<1, 128, 128> { static constexpr const char* name = "bk128"; };
+struct NnBk64 : NnGeneric<1, 64, 128> { static constexpr const char* name = "bk64"; };
+struct NnGlds {
+    static constexpr int tn = 256, tm = 256, threads = 512;
+    static constexpr size_t lds = 2 * (tm + tn) * 64 * 2 + 2 * tm * 4 + 4 * tn * 8;
+    static constexpr bool d_arg = true, lds_attr = true;
+    static constexpr const char* name = "glds";
+    template <typename T, typename CHT>
+    static constexpr auto kernel() {
+#ifndef TF_TUNE_NN_NO_GLDS_SH   // A/B switch of tools/build_variants.sh
+        return nn_search_glds_kernel<T, true, CHT>;    // short MFMAs (round 6, last session)
+#else
+        return nn_search_glds_kernel<T, false, CHT>;
+#endif
+    }
+};
+// the register-B family (D = 16 * DK = 320): 32-pivot tiles in LDS rows of D + PAD elements
+template <int PAD>
+struct NnRbFamily {
+    static constexpr int DK = 20, tm = 32, threads = 256;
+    static constexpr size_t lds = 2 * tm * (16 * DK + PAD) * 2 + 2 * tm * 4;
+    static constexpr bool d_arg = false, lds_attr = false;   // 42 KiB of LDS
+};
+struct NnRb : NnRbFamily<8> {   // pivot tiles staged through registers
+    static constexpr int tn = 128;
+    static constexpr const char* name = "rb";
+    template <typename T, typename CHT>
+    static constexpr auto kernel() { return nn_search_rb_kernel<T, DK, CHT>; }
+};
+template <int TJ>
+struct NnRbs : NnRbFamily<0> {   // pivot tiles by LDS-DMA, short MFMAs (16x16x32), TJ target tiles per wave
+    static constexpr int tn = 64 * TJ;
+    static constexpr const char* name = TJ == 4 ? "rbs<TJ=4>" : "rbs<TJ=2>";
+    template <typename T, typename CHT>
+    static constexpr auto kernel() { return nn_search_rbs_kernel<T, DK, TJ, CHT>; }
+};
+template <int TT>
+struct NnRbg : NnRbFamily<0> {   // pivot tiles by LDS-DMA, 32x32x16 MFMAs, TT target tiles per wave
+    static constexpr int tn = 128 * TT;
+    static constexpr const char* name = TT == 2 ? "rbg<TT=2>" : "rbg<TT=1>";
+    template <typename T, typename CHT>
+    static constexpr auto kernel() { return nn_search_rbg_kernel<T, DK, TT, CHT>; }
+};
+// The LDS-DMA members of the family, 128- and 256-target panels.  A/B switch of tools/build_variants.sh: rbg in the
+// place of rbs.
+#ifndef TF_TUNE_NN_NO_RBS
+typedef NnRbs<2> NnRbDma;
+typedef NnRbs<4> NnRb2Dma;
+// (the NnChunks instantiations of rbg have been part of this build all along, launched or not; they stay in it until
+// the form is retired)
+__attribute__((used)) const void* const nn_rbg_kept[] = {
+    (const void*)NnRbg<1>::kernel<BF16, NnChunks>(), (const void*)NnRbg<1>::kernel<F16, NnChunks>(),
+    (const void*)NnRbg<2>::kernel<BF16, NnChunks>(), (const void*)NnRbg<2>::kernel<F16, NnChunks>()};
+#else
+typedef NnRbg<1> NnRbDma;
+typedef NnRbg<2> NnRb2Dma;
+#endif
+
+// "read an int from the environment, else a default" (unset or not positive: the default).  The callers keep the result
+// in a function-local static, so every variable is read once per process.
+static int env_int(const char* name, int def) {
+    const char* e = getenv(name);
+    return e && atoi(e) > 0 ? atoi(e) : def;
+}
+// TF_NN_RB_GLDS=0: the register-B family never stages its pivot tiles by LDS-DMA
+static bool nn_rb_dma() {
+    static const bool on = [] { const char* e = getenv("TF_NN_RB_GLDS"); return !e || atoi(e) != 0; }();
+    return on;
+}
+
 // Launch plan shared by the launchers and tf_nn_search_workspace_bytes.
 enum NnKernel {
     NN_RB,      // register-B kernel (D == 320): 128-target panels, 32-pivot tiles
@@ -1097,112 +1183,114 @@ enum NnKernel {
 };
 struct NnPlan {
     int kern;
+    int tn, tm;   // targets per panel / pivots per tile of the form
     int64_t panels;
     int splits, tiles_per_split;
 };
 
+// The form a plan launches, handed to `f` as a value of its description type.  The one place that resolves the
+// register-B family: NN_RB2 is the 256-target LDS-DMA member (the plan has checked S % 32 == 0); NN_RB is the
+// 128-target one where every pivot tile is full (S % 32 == 0: +1.4 % at cfg2 / cfg4 level 0,
+// profiles/r05_nn_glds_ab.txt: 1028 -> 1014 us, 8826 -> 8746 us per block), else the register-staged kernel.
+template <typename Fn>
+int nn_with_form(const NnPlan& pl, int S, Fn&& f) {
+    switch (pl.kern) {
+        case NN_RB2: return f(NnRb2Dma{});
+        case NN_RB: return nn_rb_dma() && S % 32 == 0 ? f(NnRbDma{}) : f(NnRb{});
+        case NN_GLDS: return f(NnGlds{});
+        case NN_WIDE: return f(NnWide{});
+        case NN_DEEP: return f(NnDeep{});
+        case NN_BK128: return f(NnBk128{});
+        default: return f(NnBk64{});
+    }
+}
+
 // Grid target of the pivot-range split: workgroups the launch should have at least.  1024 = 4 per CU for one chunk.
-// A multi-chunk launch is C times larger; it keeps splitting up to TF_NN_MIN_WGS (environment, read once; default
-// 4096) so that the last round of workgroups is a small fraction of the launch.
+// A multi-chunk launch is C times larger; it keeps splitting up to TF_NN_MIN_WGS (environment; default 4096) so that
+// the last round of workgroups is a small fraction of the launch.
 static int nn_min_wgs(int C) {
-    static const int env = [] {
-        const char* e = getenv("TF_NN_MIN_WGS");
-        const int v = e ? atoi(e) : 0;
-        return v > 0 ? v : 4096;
-    }();
+    static const int env = env_int("TF_NN_MIN_WGS", 4096);
     return C > 1 ? env : 1024;
 }
 
-// The pivot-range split of every form but the LDS-DMA one: `wgs` = workgroups of the launch before splitting (target
-// panels of all chunks x keyframes), tm = pivots per tile.  Returns the workgroups of the split launch.
-static int64_t nn_split(NnPlan& pl, int64_t wgs, int S, int tm, int C) {
-    const int n_tiles = (S + tm - 1) / tm;
+// The pivot-range split of a plan whose form (kern, tn, tm) is set: `wgs` = workgroups of the launch before splitting
+// (target panels of all chunks x keyframes).  Returns the workgroups of the split launch.
+static int64_t nn_split(NnPlan& pl, int64_t wgs, int S, int C) {
+    const int n_tiles = (S + pl.tm - 1) / pl.tm;
     int splits = 1;
-    // a multi-chunk launch keeps >= 128 pivots per split: below that the per-workgroup fixed cost (target
-    // fragments, partial results, their merge) outweighs the finer tail (cfg1 level 0: 41.8 us at 128 pivots /
-    // split, 72 us at 32)
-    const int min_tiles = C > 1 ? (128 + tm - 1) / tm : 1;
-    while (wgs * splits < nn_min_wgs(C) && splits * 2 <= n_tiles && n_tiles / (splits * 2) >= min_tiles)
-        splits *= 2;
+    if (pl.kern == NN_GLDS) {
+        // one workgroup per CU, aim at >= `rounds` rounds of workgroups (tail), never below one tile per split
+        static const int rounds = env_int("TF_NN_GLDS_ROUNDS", 3);
+        while (wgs * splits < rounds * 256 && splits * 2 <= n_tiles) splits *= 2;
+    } else {
+        // a multi-chunk launch keeps >= 128 pivots per split: below that the per-workgroup fixed cost (target
+        // fragments, partial results, their merge) outweighs the finer tail (cfg1 level 0: 41.8 us at 128 pivots /
+        // split, 72 us at 32)
+        const int min_tiles = C > 1 ? (128 + pl.tm - 1) / pl.tm : 1;
+        while (wgs * splits < nn_min_wgs(C) && splits * 2 <= n_tiles && n_tiles / (splits * 2) >= min_tiles)
+            splits *= 2;
+    }
     pl.tiles_per_split = (n_tiles + splits - 1) / splits;
     pl.splits = (n_tiles + pl.tiles_per_split - 1) / pl.tiles_per_split;
     return wgs * pl.splits;
-}
-// The LDS-DMA form's: one workgroup per CU, aim at >= `rounds` rounds of workgroups (tail), never below one tile per split
-static void nn_split_glds(NnPlan& pl, int64_t wgs, int S) {
-    static const int rounds = [] { const char* e = getenv("TF_NN_GLDS_ROUNDS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 3; }();
-    const int n_tiles = (S + 255) / 256;
-    int splits = 1;
-    while (wgs * splits < rounds * 256 && splits * 2 <= n_tiles) splits *= 2;
-    pl.tiles_per_split = (n_tiles + splits - 1) / splits;
-    pl.splits = (n_tiles + pl.tiles_per_split - 1) / pl.tiles_per_split;
 }
 
 // splits of the pivot range so that the grid has >= nn_min_wgs workgroups while every split keeps >= 1 tile.
 // n_tgt = targets of ONE chunk, C = chunks in the launch (grid.x = C * panels).
 static NnPlan nn_plan(int64_t n_tgt, int S, int D, int P, int C = 1) {
     NnPlan pl;
-    auto shape = [&](int tn, int tm) {
-        pl.panels = (n_tgt + tn - 1) / tn;
-        return nn_split(pl, pl.panels * C * P, S, tm, C);   // workgroups of the launch
+    auto shape = [&](int kern, auto form) {   // the plan with this form; returns the workgroups of the launch
+        pl.kern = kern, pl.tn = form.tn, pl.tm = form.tm;
+        pl.panels = (n_tgt + pl.tn - 1) / pl.tn;
+        return nn_split(pl, pl.panels * C * P, S, C);
     };
 #ifndef TF_TUNE_NN_NO_GLDS   // A/B switch of tools/build_variants.sh
     // LDS-DMA kernel (256-target panels, 256-pivot tiles, one 8-wave workgroup per CU): where the launch still has
     // >= TF_NN_GLDS_MIN_WGS workgroups after splitting the pivot range down to one tile per workgroup
-    static const int glds_min_d = [] { const char* e = getenv("TF_NN_GLDS_MIN_D"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 512; }();
+    static const int glds_min_d = env_int("TF_NN_GLDS_MIN_D", 512);
     // D = 320 keeps the register-B kernel at the large levels (1.00 vs 1.12 ms at cfg2 level 0); with <= 1024 pivots per
     // keyframe (BASELINE config 1, level 0) its 32-pivot tiles are mostly prologue: 44 -> 33 us (profiles/r05_nn_glds_ab.txt)
     if (D % 64 == 0 && (D >= glds_min_d || (D == 320 && S <= 1024)) && S % 4 == 0) {
-        static const int min_wgs = [] { const char* e = getenv("TF_NN_GLDS_MIN_WGS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 160; }();
-        const int64_t panels = (n_tgt + 255) / 256;
-        const int n_tiles = (S + 255) / 256;
+        static const int min_wgs = env_int("TF_NN_GLDS_MIN_WGS", 160);
+        const int64_t panels = (n_tgt + NnGlds::tn - 1) / NnGlds::tn;
+        const int n_tiles = (S + NnGlds::tm - 1) / NnGlds::tm;
         if (panels * C * P * n_tiles >= min_wgs) {
-            pl.kern = NN_GLDS;
-            pl.panels = panels;
-            nn_split_glds(pl, panels * C * P, S);
+            shape(NN_GLDS, NnGlds{});
             return pl;
         }
     }
 #endif
-    if (D == 320) {
+    if (D == 16 * NnRb::DK) {
 #ifndef TF_TUNE_NN_NO_RB2
         // two target tiles per wave where the launch still has >= 2 rounds of its 512 resident workgroups (2 per CU) AND a
         // workgroup streams >= 24 pivot tiles: its 160 VGPRs of target fragments are a fixed cost per workgroup (one chunk of
         // cfg5, 32 tiles per workgroup: 196 -> 163 us; one chunk of cfg2, 16 tiles: 123 -> 125 us, profiles/r06_nn_rb2_ab.txt)
-        static const int rb2_min = [] { const char* e = getenv("TF_NN_RB2_MIN_WGS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 1024; }();
-        static const bool dma_ok = [] { const char* e = getenv("TF_NN_RB_GLDS"); return !e || atoi(e) != 0; }();
-        if (dma_ok && S % 32 == 0 && shape(256, 32) >= rb2_min && pl.tiles_per_split >= 24) {
-            pl.kern = NN_RB2;
-            return pl;
-        }
+        static const int rb2_min = env_int("TF_NN_RB2_MIN_WGS", 1024);
+        if (nn_rb_dma() && S % 32 == 0 && shape(NN_RB2, NnRb2Dma{}) >= rb2_min && pl.tiles_per_split >= 24) return pl;
 #endif
-        pl.kern = NN_RB;
-        shape(128, 32);
+        shape(NN_RB, NnRb{});
         return pl;
     }
     // 128-target panels halve the pivot re-reads; they pay as soon as the grid still fills the GPU after
     // splitting the pivot range (measured at cfg2 level 1, 5120 targets x 2 keyframes: 34.6 vs 39.8 us)
-    if (((n_tgt + 127) / 128) * P * C >= 64) {
-        pl.kern = NN_WIDE;
-        shape(128, 128);
+    if (((n_tgt + NnWide::tn - 1) / NnWide::tn) * P * C >= 64) {
+        shape(NN_WIDE, NnWide{});
         return pl;
     }
     // few workgroups and a long contraction: the loop is a chain of load -> LDS -> barrier -> MFMA steps whose
     // latency nothing hides -> wider D chunks (fewer steps)
 #ifndef TF_TUNE_NN_NO_DEEP   // A/B switch of tools/build_variants.sh
-    if (D >= 1024 && shape(64, 64) <= 512) {
-        pl.kern = NN_DEEP;
-        return pl;
-    }
+    if (D >= 1024 && shape(NN_DEEP, NnDeep{}) <= 512) return pl;
 #endif
-    pl.kern = (shape(64, 128) <= 512 && D >= 512) ? NN_BK128 : NN_BK64;
+    if (shape(NN_BK128, NnBk128{}) > 512 || D < 512) shape(NN_BK64, NnBk64{});
     return pl;
 }
 
-// targets per panel / pivots per tile of a kernel form
-static int nn_form_tn(int kern) { return kern == NN_RB2 || kern == NN_GLDS ? 256 : kern == NN_RB || kern == NN_WIDE ? 128 : 64; }
-static int nn_form_tm(int kern) {
-    return kern == NN_RB || kern == NN_RB2 ? 32 : kern == NN_GLDS ? 256 : kern == NN_DEEP ? 64 : 128;
+// the targets of a ragged call
+static int64_t nn_ragged_rows(const int* frames, int C, int S) {
+    int64_t rows = 0;
+    for (int j = 0; j < C; ++j) rows += (int64_t)frames[j] * S;
+    return rows;
 }
 
 // A RAGGED launch: C chunks of frames[j] * S targets, two keyframes (the p = 1 half of a one-keyframe chunk exits at once).
@@ -1213,16 +1301,13 @@ static int nn_form_tm(int kern) {
 //     chunks), and the pivot-range split is the form's own rule applied to THAT workgroup count.
 // pl.panels = grid.x.  Equal frame counts never come here: the entry points hand them to the uniform launch.
 static NnPlan nn_plan_ragged(const int* frames, int C, int S, int D) {
-    int64_t rows = 0;
-    for (int j = 0; j < C; ++j) rows += (int64_t)frames[j] * S;
-    NnPlan pl = nn_plan((rows + C - 1) / C, S, D, 2, C);
-    const int tn = nn_form_tn(pl.kern);
+    NnPlan pl = nn_plan((nn_ragged_rows(frames, C, S) + C - 1) / C, S, D, 2, C);
     pl.panels = 0;
-    for (int j = 0; j < C; ++j) pl.panels += ((int64_t)frames[j] * S + tn - 1) / tn;
-    if (pl.kern == NN_GLDS) nn_split_glds(pl, pl.panels * 2, S);
-    else nn_split(pl, pl.panels * 2, S, nn_form_tm(pl.kern), C);
+    for (int j = 0; j < C; ++j) pl.panels += ((int64_t)frames[j] * S + pl.tn - 1) / pl.tn;
+    nn_split(pl, pl.panels * 2, S, C);
     return pl;
 }
+
 static int finalize(const NnPartial* part, int32_t* idx, int64_t total, int splits, hipStream_t st) {
     if (tf_plan_note("finalize")) return 0;
     hipLaunchKernelGGL(nn_finalize_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, part, idx, total,
@@ -1231,208 +1316,82 @@ static int finalize(const NnPartial* part, int32_t* idx, int64_t total, int spli
     return 0;
 }
 
-// n_tgt = targets per chunk; C chunks per launch (C = 1, single_mask = 0: the plain single-chunk search).
-// Partial results / indices are laid out over all C * n_tgt targets.
-template <typename T, int WN, int BK, int TM>
-int launch_nn(const void* tgt, const void* piv, const float* inv_norm, int32_t* idx, NnPartial* ws, int64_t n_tgt,
-              int S, int D, int P, int kf0, int kf1, hipStream_t st, bool fin, int C, uint64_t single_mask) {
-    constexpr int TN = 64 * WN;
-    constexpr size_t lds = 2 * (TM + TN) * BK * 2 + 2 * TM * 4 + 2 * TN * 8;
-    static_assert(lds <= 160 * 1024, "LDS");
-    const NnPlan pl = nn_plan(n_tgt, S, D, P, C);
-    const int splits = pl.splits, tps = pl.tiles_per_split;
-    dim3 grid((unsigned)(pl.panels * C), (unsigned)P, (unsigned)splits);
-    if (tf_plan_note("%s[splits=%d%s]", pl.kern == NN_WIDE ? "wide" : pl.kern == NN_DEEP ? "deep" : pl.kern == NN_BK128 ? "bk128" : "bk64",
-                     splits, C > 1 ? ",chunks" : ""))
-        return (fin && splits > 1) ? finalize(ws, idx, n_tgt * C * P, splits, st) : 0;
-    auto kern = nn_search_kernel<T, WN, BK, TM>;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    const NnChunks ch = nn_chunks(n_tgt, (int)pl.panels, single_mask);
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, reinterpret_cast<const typename T::elem*>(tgt),
-                       reinterpret_cast<const typename T::elem*>(piv), inv_norm, idx,
-                       (splits > 1 || !fin) ? ws : nullptr, n_tgt * C, S, D, kf0, kf1, tps, ch);
-    TF_LAUNCH_CHECK("tf_nn_search");
-    return (fin && splits > 1) ? finalize(ws, idx, n_tgt * C * P, splits, st) : 0;
+// One search launch.  total = targets of all chunks of the call (partial results / indices are laid out over them);
+// fin: indices are wanted, so a split launch is followed by the finalize launch (never a ragged one: the gather merges).
+struct NnLaunch {
+    const void *tgt, *piv;
+    const float* inv_norm;
+    int32_t* idx;
+    NnPartial* ws;
+    int64_t total;
+    int S, D, P, kf0, kf1;
+    hipStream_t st;
+    bool fin;
+    NnPlan pl;
+    unsigned grid_x;       // target panels of all chunks
+    const char* suffix;    // of the plan token: "" / ",chunks" / ",ragged"
+    const char* label;     // of a failed launch
+};
+
+template <typename T, typename CHT>
+int nn_launch_as(const NnLaunch& a, const CHT& ch) {
+    typedef const typename T::elem* EP;
+    const int splits = a.pl.splits;
+    const int rc = nn_with_form(a.pl, a.S, [&](auto form) {
+        typedef decltype(form) F;
+        static_assert(F::lds <= 160 * 1024, "LDS");
+        if (tf_plan_note("%s[splits=%d%s]", F::name, splits, a.suffix)) return 0;
+        auto kern = F::template kernel<T, CHT>();
+        const dim3 grid(a.grid_x, (unsigned)a.P, (unsigned)splits);
+        NnPartial* const ws = (splits > 1 || !a.fin) ? a.ws : nullptr;
+        if constexpr (F::lds_attr)
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)F::lds);
+        if constexpr (F::d_arg) {
+            hipLaunchKernelGGL(kern, grid, dim3(F::threads), F::lds, a.st, (EP)a.tgt, (EP)a.piv, a.inv_norm, a.idx, ws, a.total,
+                               a.S, a.D, a.kf0, a.kf1, a.pl.tiles_per_split, ch);
+        } else {
+            hipLaunchKernelGGL(kern, grid, dim3(F::threads), F::lds, a.st, (EP)a.tgt, (EP)a.piv, a.inv_norm, a.idx, ws, a.total,
+                               a.S, a.kf0, a.kf1, a.pl.tiles_per_split, ch);
+        }
+        TF_LAUNCH_CHECK(a.label);
+        return 0;
+    });
+    return (rc == 0 && a.fin && splits > 1) ? finalize(a.ws, a.idx, a.total * a.P, splits, a.st) : rc;
+}
+template <typename CHT>
+int nn_launch(int dtype, const NnLaunch& a, const CHT& ch) {
+    return dtype == TF_BF16 ? nn_launch_as<BF16>(a, ch) : nn_launch_as<F16>(a, ch);
 }
 
-template <typename T>
-int launch_nn_glds(const void* tgt, const void* piv, const float* inv_norm, int32_t* idx, NnPartial* ws, int64_t n_tgt,
-                   int S, int D, int P, int kf0, int kf1, hipStream_t st, bool fin, int C, uint64_t single_mask) {
-    constexpr size_t lds = 2 * (256 + 256) * 64 * 2 + 2 * 256 * 4 + 4 * 256 * 8;
-    static_assert(lds <= 160 * 1024, "LDS");
-    const NnPlan pl = nn_plan(n_tgt, S, D, P, C);
-    const int splits = pl.splits, tps = pl.tiles_per_split;
-    dim3 grid((unsigned)(pl.panels * C), (unsigned)P, (unsigned)splits);
-    if (tf_plan_note("glds[splits=%d%s]", splits, C > 1 ? ",chunks" : "")) return (fin && splits > 1) ? finalize(ws, idx, n_tgt * C * P, splits, st) : 0;
-#ifndef TF_TUNE_NN_NO_GLDS_SH
-    auto kern = nn_search_glds_kernel<T, true>;    // short MFMAs (round 6, last session)
-#else
-    auto kern = nn_search_glds_kernel<T, false>;
-#endif
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    const NnChunks ch = nn_chunks(n_tgt, (int)pl.panels, single_mask);
-    hipLaunchKernelGGL(kern, grid, dim3(512), lds, st, reinterpret_cast<const typename T::elem*>(tgt),
-                       reinterpret_cast<const typename T::elem*>(piv), inv_norm, idx,
-                       (splits > 1 || !fin) ? ws : nullptr, n_tgt * C, S, D, kf0, kf1, tps, ch);
-    TF_LAUNCH_CHECK("tf_nn_search");
-    return (fin && splits > 1) ? finalize(ws, idx, n_tgt * C * P, splits, st) : 0;
-}
-
-template <typename T, int DK>
-int launch_nn_rb(const void* tgt, const void* piv, const float* inv_norm, int32_t* idx, NnPartial* ws, int64_t n_tgt,
-                 int S, int P, int kf0, int kf1, hipStream_t st, bool fin, int C, uint64_t single_mask) {
-    constexpr int D = 16 * DK;
-    const size_t lds = 2 * 32 * (D + 8) * 2 + 2 * 32 * 4;
-    const NnPlan pl = nn_plan(n_tgt, S, D, P, C);
-    const int splits = pl.splits, tps = pl.tiles_per_split;
-    dim3 grid((unsigned)(pl.panels * C), (unsigned)P, (unsigned)splits);
-    const NnChunks ch = nn_chunks(n_tgt, (int)pl.panels, single_mask);
-    if (pl.kern == NN_RB2) {   // 256-target panels, two target tiles per wave (the plan has checked S % 32 == 0)
-        const size_t lds_g = 2 * 32 * D * 2 + 2 * 32 * 4;
-#ifndef TF_TUNE_NN_NO_RBS
-        if (tf_plan_note("rbs<TJ=4>[splits=%d%s]", splits, C > 1 ? ",chunks" : "")) return (fin && splits > 1) ? finalize(ws, idx, n_tgt * C * P, splits, st) : 0;
-        // round 6, last session: the same kernel with short MFMAs (16x16x32), see nn_search_rbs_kernel
-        hipLaunchKernelGGL((nn_search_rbs_kernel<T, DK>), grid, dim3(256), lds_g, st,
-                           reinterpret_cast<const typename T::elem*>(tgt), reinterpret_cast<const typename T::elem*>(piv),
-                           inv_norm, idx, (splits > 1 || !fin) ? ws : nullptr, n_tgt * C, S, kf0, kf1, tps, ch);
-        TF_LAUNCH_CHECK("tf_nn_search");
-        return (fin && splits > 1) ? finalize(ws, idx, n_tgt * C * P, splits, st) : 0;
-#endif
-        if (tf_plan_note("rbg<TT=2>[splits=%d%s]", splits, C > 1 ? ",chunks" : "")) return (fin && splits > 1) ? finalize(ws, idx, n_tgt * C * P, splits, st) : 0;
-        hipLaunchKernelGGL((nn_search_rbg_kernel<T, DK, 2>), grid, dim3(256), lds_g, st,
-                           reinterpret_cast<const typename T::elem*>(tgt), reinterpret_cast<const typename T::elem*>(piv),
-                           inv_norm, idx, (splits > 1 || !fin) ? ws : nullptr, n_tgt * C, S, kf0, kf1, tps, ch);
-        TF_LAUNCH_CHECK("tf_nn_search");
-        return (fin && splits > 1) ? finalize(ws, idx, n_tgt * C * P, splits, st) : 0;
-    }
-    // pivot tiles by LDS-DMA where every tile is full (S % 32 == 0): +1.4 % at cfg2 / cfg4 level 0
-    // (profiles/r05_nn_glds_ab.txt: 1028 -> 1014 us, 8826 -> 8746 us per block); TF_NN_RB_GLDS=0: the register-staged kernel
-    static const bool dma = [] { const char* e = getenv("TF_NN_RB_GLDS"); return !e || atoi(e) != 0; }();
-    if (dma && S % 32 == 0) {
-        const size_t lds_g = 2 * 32 * D * 2 + 2 * 32 * 4;
-#ifndef TF_TUNE_NN_NO_RBS
-        if (tf_plan_note("rbs<TJ=2>[splits=%d%s]", splits, C > 1 ? ",chunks" : "")) return (fin && splits > 1) ? finalize(ws, idx, n_tgt * C * P, splits, st) : 0;
-        hipLaunchKernelGGL((nn_search_rbs_kernel<T, DK, 2>), grid, dim3(256), lds_g, st,
-                           reinterpret_cast<const typename T::elem*>(tgt), reinterpret_cast<const typename T::elem*>(piv),
-                           inv_norm, idx, (splits > 1 || !fin) ? ws : nullptr, n_tgt * C, S, kf0, kf1, tps, ch);
-        TF_LAUNCH_CHECK("tf_nn_search");
-        return (fin && splits > 1) ? finalize(ws, idx, n_tgt * C * P, splits, st) : 0;
-#endif
-        if (tf_plan_note("rbg<TT=1>[splits=%d%s]", splits, C > 1 ? ",chunks" : "")) return (fin && splits > 1) ? finalize(ws, idx, n_tgt * C * P, splits, st) : 0;
-        hipLaunchKernelGGL((nn_search_rbg_kernel<T, DK>), grid, dim3(256), lds_g, st,
-                           reinterpret_cast<const typename T::elem*>(tgt), reinterpret_cast<const typename T::elem*>(piv),
-                           inv_norm, idx, (splits > 1 || !fin) ? ws : nullptr, n_tgt * C, S, kf0, kf1, tps, ch);
-        TF_LAUNCH_CHECK("tf_nn_search");
-        return (fin && splits > 1) ? finalize(ws, idx, n_tgt * C * P, splits, st) : 0;
-    }
-    if (tf_plan_note("rb[splits=%d%s]", splits, C > 1 ? ",chunks" : "")) return (fin && splits > 1) ? finalize(ws, idx, n_tgt * C * P, splits, st) : 0;
-    hipLaunchKernelGGL((nn_search_rb_kernel<T, DK>), grid, dim3(256), lds, st,
-                       reinterpret_cast<const typename T::elem*>(tgt), reinterpret_cast<const typename T::elem*>(piv),
-                       inv_norm, idx, (splits > 1 || !fin) ? ws : nullptr, n_tgt * C, S, kf0, kf1, tps, ch);
-    TF_LAUNCH_CHECK("tf_nn_search");
-    return (fin && splits > 1) ? finalize(ws, idx, n_tgt * C * P, splits, st) : 0;
-}
-
-template <typename T>
-int dispatch_nn(const void* tgt, const void* piv, const float* inv_norm, int32_t* idx, NnPartial* ws, int64_t n_tgt,
-                int S, int D, int P, int kf0, int kf1, hipStream_t st, bool fin, int C = 1, uint64_t single_mask = 0) {
+// The uniform call: C chunks of n_tgt targets each (C = 1, single_mask = 0: the plain single-chunk search), `pl` their plan.
+int nn_search_chunks(const void* tgt, const void* piv, const float* inv_norm, int32_t* idx, NnPartial* ws, int64_t n_tgt, int S,
+                     int D, int P, int kf0, int kf1, int dtype, hipStream_t st, bool fin, int C, uint64_t single_mask,
+                     const NnPlan& pl) {
     // the chunk descriptor of a launch carries the targets per chunk in 32 bits (NnChunks)
     TF_ARG(n_tgt <= (int64_t)INT32_MAX, TF_ERR_SHAPE, "tf_nn_search: %lld targets per chunk (< 2^31)", (long long)n_tgt);
-    switch (nn_plan(n_tgt, S, D, P, C).kern) {
-        case NN_RB:
-        case NN_RB2:
-            return launch_nn_rb<T, 20>(tgt, piv, inv_norm, idx, ws, n_tgt, S, P, kf0, kf1, st, fin, C, single_mask);
-        case NN_GLDS:
-            return launch_nn_glds<T>(tgt, piv, inv_norm, idx, ws, n_tgt, S, D, P, kf0, kf1, st, fin, C, single_mask);
-        case NN_WIDE:
-            return launch_nn<T, 2, 64, 128>(tgt, piv, inv_norm, idx, ws, n_tgt, S, D, P, kf0, kf1, st, fin, C, single_mask);
-        case NN_DEEP:
-            return launch_nn<T, 1, 256, 64>(tgt, piv, inv_norm, idx, ws, n_tgt, S, D, P, kf0, kf1, st, fin, C, single_mask);
-        case NN_BK128:
-            return launch_nn<T, 1, 128, 128>(tgt, piv, inv_norm, idx, ws, n_tgt, S, D, P, kf0, kf1, st, fin, C, single_mask);
-        default:
-            return launch_nn<T, 1, 64, 128>(tgt, piv, inv_norm, idx, ws, n_tgt, S, D, P, kf0, kf1, st, fin, C, single_mask);
-    }
+    const NnLaunch a{tgt, piv, inv_norm, idx, ws, n_tgt * C, S, D, P, kf0, kf1, st, fin, pl, (unsigned)(pl.panels * C),
+                     C > 1 ? ",chunks" : "", "tf_nn_search"};
+    return nn_launch(dtype, a, nn_chunks(n_tgt, (int)pl.panels, single_mask));
 }
 
-// The ragged launch (nn_plan_ragged): the NnRagged instantiation of the form's kernel, partial results only (the gather
-// merges them), P = 2.  Plan tokens are the uniform launch's with ",ragged" in the place of ",chunks".
-template <typename T>
-int dispatch_nn_ragged(const void* tgt, const void* piv, const float* inv_norm, NnPartial* ws, const int* frames, int C,
-                       int S, int D, int kf0, int kf1, hipStream_t st, uint64_t single_mask) {
-    typedef const typename T::elem* EP;
-    const NnPlan pl = nn_plan_ragged(frames, C, S, D);
-    const int splits = pl.splits, tps = pl.tiles_per_split;
-    int64_t rows = 0;
-    for (int j = 0; j < C; ++j) rows += (int64_t)frames[j] * S;
-    const dim3 grid((unsigned)pl.panels, 2u, (unsigned)splits);
-    const NnRagged ch = nn_ragged(frames, C, S, nn_form_tn(pl.kern), single_mask);
-    // kernels that take D as an argument (generic, LDS-DMA) / as a template parameter (register-B family)
-    auto go_d = [&](auto kern, const char* form, unsigned threads, size_t lds) {
-        if (tf_plan_note("%s[splits=%d,ragged]", form, splits)) return 0;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(kern, grid, dim3(threads), lds, st, (EP)tgt, (EP)piv, inv_norm, (int32_t*)nullptr, ws, rows, S, D,
-                           kf0, kf1, tps, ch);
-        TF_LAUNCH_CHECK("tf_nn_search(ragged)");
-        return 0;
-    };
-    auto go_rb = [&](auto kern, const char* form, size_t lds) {
-        if (tf_plan_note("%s[splits=%d,ragged]", form, splits)) return 0;
-        hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, (EP)tgt, (EP)piv, inv_norm, (int32_t*)nullptr, ws, rows, S, kf0,
-                           kf1, tps, ch);
-        TF_LAUNCH_CHECK("tf_nn_search(ragged)");
-        return 0;
-    };
-    auto lds_nn = [](int tn, int bk, int tm) { return (size_t)2 * (tm + tn) * bk * 2 + 2 * tm * 4 + 2 * tn * 8; };
-    switch (pl.kern) {
-        case NN_RB:
-        case NN_RB2: {   // the choices of launch_nn_rb
-            constexpr int DK = 20;
-            const size_t lds_g = 2 * 32 * (16 * DK) * 2 + 2 * 32 * 4;
-            if (pl.kern == NN_RB2) {
-#ifndef TF_TUNE_NN_NO_RBS
-                return go_rb(nn_search_rbs_kernel<T, DK, 4, NnRagged>, "rbs<TJ=4>", lds_g);
-#else
-                return go_rb(nn_search_rbg_kernel<T, DK, 2, NnRagged>, "rbg<TT=2>", lds_g);
-#endif
-            }
-            static const bool dma = [] { const char* e = getenv("TF_NN_RB_GLDS"); return !e || atoi(e) != 0; }();
-            if (dma && S % 32 == 0) {
-#ifndef TF_TUNE_NN_NO_RBS
-                return go_rb(nn_search_rbs_kernel<T, DK, 2, NnRagged>, "rbs<TJ=2>", lds_g);
-#else
-                return go_rb(nn_search_rbg_kernel<T, DK, 1, NnRagged>, "rbg<TT=1>", lds_g);
-#endif
-            }
-            return go_rb(nn_search_rb_kernel<T, DK, NnRagged>, "rb", 2 * 32 * (16 * DK + 8) * 2 + 2 * 32 * 4);
-        }
-        case NN_GLDS:
-#ifndef TF_TUNE_NN_NO_GLDS_SH
-            return go_d(nn_search_glds_kernel<T, true, NnRagged>, "glds", 512, 2 * (256 + 256) * 64 * 2 + 2 * 256 * 4 + 4 * 256 * 8);
-#else
-            return go_d(nn_search_glds_kernel<T, false, NnRagged>, "glds", 512, 2 * (256 + 256) * 64 * 2 + 2 * 256 * 4 + 4 * 256 * 8);
-#endif
-        case NN_WIDE: return go_d(nn_search_kernel<T, 2, 64, 128, NnRagged>, "wide", 256, lds_nn(128, 64, 128));
-        case NN_DEEP: return go_d(nn_search_kernel<T, 1, 256, 64, NnRagged>, "deep", 256, lds_nn(64, 256, 64));
-        case NN_BK128: return go_d(nn_search_kernel<T, 1, 128, 128, NnRagged>, "bk128", 256, lds_nn(64, 128, 128));
-        default: return go_d(nn_search_kernel<T, 1, 64, 128, NnRagged>, "bk64", 256, lds_nn(64, 64, 128));
-    }
-}
+size_t nn_partials_bytes(const NnPlan& pl, int64_t targets, int P) { return (size_t)pl.splits * P * targets * sizeof(NnPartial); }
 
 }  // namespace
 
+// The ragged call (nn_plan_ragged): the NnRagged instantiation of the form's kernel, partial results only, P = 2.  Plan
+// tokens are the uniform launch's with ",ragged" in the place of ",chunks".
 int tf_nn_search_partials_ragged(const void* tgt, const void* piv, const float* inv_norm, NnPartial* part,
                                  const int* frames, int C, int S, int D, int kf0, int kf1, int dtype, hipStream_t st,
                                  int* splits, uint64_t single_mask) {
-    *splits = nn_plan_ragged(frames, C, S, D).splits;
-    return dtype == TF_BF16 ? dispatch_nn_ragged<BF16>(tgt, piv, inv_norm, part, frames, C, S, D, kf0, kf1, st, single_mask)
-                            : dispatch_nn_ragged<F16>(tgt, piv, inv_norm, part, frames, C, S, D, kf0, kf1, st, single_mask);
+    const NnPlan pl = nn_plan_ragged(frames, C, S, D);
+    *splits = pl.splits;
+    const NnLaunch a{tgt, piv, inv_norm, nullptr, part, nn_ragged_rows(frames, C, S), S, D, 2, kf0, kf1, st, false, pl,
+                     (unsigned)pl.panels, ",ragged", "tf_nn_search(ragged)"};
+    return nn_launch(dtype, a, nn_ragged(frames, C, S, pl.tn, single_mask));
 }
 
 size_t tf_nn_partials_bytes_ragged(const int* frames, int C, int S, int D) {
-    int64_t rows = 0;
-    for (int j = 0; j < C; ++j) rows += (int64_t)frames[j] * S;
-    return (size_t)nn_plan_ragged(frames, C, S, D).splits * 2 * rows * sizeof(NnPartial);
+    return nn_partials_bytes(nn_plan_ragged(frames, C, S, D), nn_ragged_rows(frames, C, S), 2);
 }
 
 extern "C" int tf_pivot_inv_norm(const void* piv, float* inv_norm, int64_t rows, int D, int dtype, void* stream) {
@@ -1454,25 +1413,24 @@ extern "C" int tf_pivot_inv_norm(const void* piv, float* inv_norm, int64_t rows,
 }
 
 // Launch plan of tf_nn_search (C = 1) or of the search launches of tf_nn_gather_blend_chunks (C > 1, P = 2): the real
-// dispatch under the plan recorder (csrc/tf_common.h).  No device, no allocation.
+// launch path under the plan recorder (csrc/tf_common.h).  No device, no allocation.
 extern "C" int tf_nn_search_plan(int64_t n_tgt, int S, int D, int P, int C, char* buf, size_t len) {
     TF_ARG(n_tgt > 0 && S > 0 && D > 0 && D % 8 == 0 && (P == 1 || P == 2) && C >= 1 && (C == 1 || P == 2), TF_ERR_SHAPE,
            "tf_nn_search_plan: n_tgt=%lld S=%d D=%d P=%d C=%d", (long long)n_tgt, S, D, P, C);
-    TfPlanRec rec{buf, len, 0, 0};
-    if (buf && len) buf[0] = 0;
-    tf_plan_rec = &rec;
-    const int rc = dispatch_nn<BF16>(nullptr, nullptr, nullptr, nullptr, nullptr, n_tgt, S, D, P, 0, 1, nullptr, C == 1, C, 0);
-    tf_plan_rec = nullptr;
-    if (rc) return rc;
-    TF_ARG(rec.used < len, TF_ERR_WORKSPACE, "tf_nn_search_plan: the plan needs %zu bytes", rec.used + 1);
-    return rec.n;
+    return tf_record_plan("tf_nn_search_plan", buf, len, [&] {
+        return nn_search_chunks(nullptr, nullptr, nullptr, nullptr, nullptr, n_tgt, S, D, P, 0, 1, TF_BF16, nullptr, C == 1, C, 0,
+                                nn_plan(n_tgt, S, D, P, C));
+    });
 }
 
+// scratch of tf_nn_search under plan `pl`; never 0: the caller always passes a valid pointer
+static size_t nn_search_ws_bytes(const NnPlan& pl, int64_t n_tgt, int P) {
+    const size_t bytes = pl.splits > 1 ? nn_partials_bytes(pl, n_tgt, P) : 0;
+    return bytes < 256 ? 256 : bytes;
+}
 extern "C" size_t tf_nn_search_workspace_bytes(int64_t n_tgt, int S, int D, int P) {
     if (n_tgt <= 0 || S <= 0 || D <= 0 || P <= 0) return 0;
-    const NnPlan pl = nn_plan(n_tgt, S, D, P);
-    const size_t bytes = pl.splits > 1 ? (size_t)pl.splits * P * n_tgt * sizeof(NnPartial) : 0;
-    return bytes < 256 ? 256 : bytes;   // never 0: the caller always passes a valid pointer
+    return nn_search_ws_bytes(nn_plan(n_tgt, S, D, P), n_tgt, P);
 }
 
 extern "C" int tf_nn_search(const void* tgt, const void* piv, const float* inv_norm, int32_t* idx, int64_t n_tgt,
@@ -1484,23 +1442,21 @@ extern "C" int tf_nn_search(const void* tgt, const void* piv, const float* inv_n
            TF_ERR_SHAPE, "tf_nn_search: n_tgt=%lld S=%d D=%d P=%d kf=(%d,%d)", (long long)n_tgt, S, D, P, kf0, kf1);
     TF_ARG(tf_aligned16(tgt) && tf_aligned16(piv) && tf_aligned16(ws) && tf_aligned16(inv_norm), TF_ERR_ALIGN,
            "tf_nn_search: inputs not 16-byte aligned (inv_norm included: the LDS-DMA kernel fetches it in 16-byte pieces)");
-    TF_ARG(ws_bytes >= tf_nn_search_workspace_bytes(n_tgt, S, D, P), TF_ERR_WORKSPACE,
-           "tf_nn_search: workspace %zu < %zu bytes", ws_bytes, tf_nn_search_workspace_bytes(n_tgt, S, D, P));
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    NnPartial* part = reinterpret_cast<NnPartial*>(ws);
-    return dtype == TF_BF16 ? dispatch_nn<BF16>(tgt, piv, inv_norm, idx, part, n_tgt, S, D, P, kf0, kf1, st, true)
-                            : dispatch_nn<F16>(tgt, piv, inv_norm, idx, part, n_tgt, S, D, P, kf0, kf1, st, true);
+    const NnPlan pl = nn_plan(n_tgt, S, D, P);
+    TF_ARG(ws_bytes >= nn_search_ws_bytes(pl, n_tgt, P), TF_ERR_WORKSPACE, "tf_nn_search: workspace %zu < %zu bytes", ws_bytes,
+           nn_search_ws_bytes(pl, n_tgt, P));
+    return nn_search_chunks(tgt, piv, inv_norm, idx, reinterpret_cast<NnPartial*>(ws), n_tgt, S, D, P, kf0, kf1, dtype,
+                            reinterpret_cast<hipStream_t>(stream), true, 1, 0, pl);
 }
 
 int tf_nn_search_partials(const void* tgt, const void* piv, const float* inv_norm, NnPartial* part, int64_t n_tgt,
                           int S, int D, int P, int kf0, int kf1, int dtype, hipStream_t st, int* splits, int C,
                           uint64_t single_mask) {
-    *splits = nn_plan(n_tgt, S, D, P, C).splits;
-    return dtype == TF_BF16
-               ? dispatch_nn<BF16>(tgt, piv, inv_norm, nullptr, part, n_tgt, S, D, P, kf0, kf1, st, false, C, single_mask)
-               : dispatch_nn<F16>(tgt, piv, inv_norm, nullptr, part, n_tgt, S, D, P, kf0, kf1, st, false, C, single_mask);
+    const NnPlan pl = nn_plan(n_tgt, S, D, P, C);
+    *splits = pl.splits;
+    return nn_search_chunks(tgt, piv, inv_norm, nullptr, part, n_tgt, S, D, P, kf0, kf1, dtype, st, false, C, single_mask, pl);
 }
 
 size_t tf_nn_partials_bytes(int64_t n_tgt, int S, int D, int P, int C) {
-    return (size_t)nn_plan(n_tgt, S, D, P, C).splits * P * n_tgt * C * sizeof(NnPartial);
+    return nn_partials_bytes(nn_plan(n_tgt, S, D, P, C), n_tgt * C, P);
 }

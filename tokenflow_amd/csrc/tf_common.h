@@ -211,6 +211,20 @@ bool tf_plan_note(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
         }                                  \
     } while (0)
 
+// The body of a `*_plan` query `name`: runs `call` (the entry point itself, on placeholder pointers) under a recorder
+// over buf / len and returns the number of launches recorded, or the call's error.
+template <typename Call>
+static inline int tf_record_plan(const char* name, char* buf, size_t len, Call&& call) {
+    TfPlanRec rec{buf, len, 0, 0};
+    if (buf && len) buf[0] = 0;
+    tf_plan_rec = &rec;
+    const int rc = call();
+    tf_plan_rec = nullptr;
+    if (rc) return rc;
+    TF_ARG(rec.used < len, TF_ERR_WORKSPACE, "%s: the plan needs %zu bytes", name, rec.used + 1);
+    return rec.n;
+}
+
 #define TF_LAUNCH_CHECK(name)                                                   \
     do {                                                                        \
         hipError_t e_ = hipGetLastError();                                      \

@@ -1671,6 +1671,52 @@ def _norm_args(norm, like: torch.Tensor, shape, norm_out: Optional[torch.Tensor]
             _DT[wt.dtype] if wt is not None else 0, nout, _DT[ndt], (weight, bias))
 
 
+def _propagate_begin(what: str, tgt, piv, inv_norm, kf_out, w, residual, out, norm, norm_out):
+    """What every propagation wrapper checks first; returns (device, library)."""
+    dev = _need_gpu(tgt, piv, inv_norm, kf_out, w, residual, out, norm_out)
+    if norm_out is not None and norm is None:
+        raise ValueError(f"{what}: `norm_out` without `norm`")
+    return dev, _lib.load()
+
+
+def _propagate_call(what: str, dev, lib, name: str, name_norm: str, tgt, piv, inv_norm, kf_out, w, residual, out_dtype,
+                    norm, out, norm_out, *, rows: int, P: int, ws_bytes: int, shape_args: tuple, single_dtype: bool = True,
+                    tail: tuple = (), residual_is: Optional[str] = None, codes_first: bool = False):
+    """The body of every propagation wrapper behind its own shape check: contiguous inputs, the result of `rows` frames,
+    the scratch of `ws_bytes`, then entry point `name`, or `name_norm` with the fused norm of a P-keyframe gather.
+    The entry points take: the seven tensors, `shape_args`, the four dtype codes, the dtype of a one-keyframe chunk's own
+    pass (`single_dtype`: the chunk forms), `tail`, then the norm's arguments and the scratch.
+    residual_is: the shape to name when the residual is not [rows, S, D] (None: the C entry point's business).
+    codes_first: the dtype codes are looked up before the fused-norm checks, not behind them (the segments, edits and
+    ragged wrappers always did: an unsupported dtype is their KeyError even where the norm would be refused too)."""
+    tgt, piv, kf_out = tgt.contiguous(), piv.contiguous(), kf_out.contiguous()
+    shape = (rows,) + tuple(piv.shape[1:])
+    if residual is not None:
+        residual = residual.contiguous()
+        if residual_is is not None and residual.shape != shape:
+            raise ValueError(f"{what}: residual must be {residual_is}")
+    out = _caller_buffer(what, "out", out, shape, out_dtype, kf_out.device)
+    ws = _workspace(ws_bytes, tgt.device, "nn")
+    # what the reference's single-keyframe pass would emit for a one-keyframe chunk: kf dtype (+ residual), torch promotion
+    single = (kf_out.dtype if residual is None else torch.promote_types(kf_out.dtype, residual.dtype),) if single_dtype else ()
+
+    def codes():    # an unsupported dtype is a KeyError here
+        return (_DT[tgt.dtype], _DT[kf_out.dtype], _DT[residual.dtype] if residual is not None else 0, _DT[out_dtype],
+                *(_DT[dt] for dt in single))
+
+    dts = codes() if codes_first else None
+    nout = None
+    if norm is not None:
+        if not norm_fusable(kf_out, residual, out_dtype, P, norm[3]):
+            raise TypeError(f"{what}: these dtypes have no fused-norm form (ops.norm_fusable)")
+        g, b, eps, wdt, nout, ndt, _keep = _norm_args(norm, kf_out, shape, norm_out)
+        name, tail = name_norm, tail + (g, b, eps, wdt, nout.data_ptr(), ndt)
+    _launch(dev, name, getattr(lib, name), tgt.data_ptr(), piv.data_ptr(), inv_norm.data_ptr(), kf_out.data_ptr(),
+            w.data_ptr() if w is not None else 0, residual.data_ptr() if residual is not None else 0, out.data_ptr(),
+            *shape_args, *(dts or codes()), *tail, ws.data_ptr(), ws.numel())
+    return out if nout is None else (out, nout)
+
+
 def propagate(tgt: torch.Tensor, piv: torch.Tensor, inv_norm: torch.Tensor, kf_ids: Sequence[int],
               kf_out: torch.Tensor, w: Optional[torch.Tensor], n: int, residual: Optional[torch.Tensor],
               out_dtype: torch.dtype, norm=None, out: Optional[torch.Tensor] = None,
@@ -1682,37 +1728,18 @@ def propagate(tgt: torch.Tensor, piv: torch.Tensor, inv_norm: torch.Tensor, kf_i
     the separate calls.
     out / norm_out: contiguous destination tensors of the result's shape ([3n,S,D]; out_dtype / the norm's dtype) to write
     into; norm_out needs `norm`."""
-    dev = _need_gpu(tgt, piv, inv_norm, kf_out, w, residual, out, norm_out)
-    if norm_out is not None and norm is None:
-        raise ValueError("propagate: `norm_out` without `norm`")
-    lib = _lib.load()
-    tgt, piv, kf_out = tgt.contiguous(), piv.contiguous(), kf_out.contiguous()
+    what = "propagate"
+    dev, lib = _propagate_begin(what, tgt, piv, inv_norm, kf_out, w, residual, out, norm, norm_out)
     K, S, D = piv.shape
     n_tgt = tgt.shape[0]
     P = len(kf_ids)
     if (tgt.dtype != piv.dtype or tgt.shape[1] != D or P not in (1, 2) or any(not 0 <= i < K for i in kf_ids)
             or n_tgt != n * S or kf_out.shape != (3 * K, S, D)):
         raise ValueError("propagate: bad arguments")
-    if residual is not None:
-        residual = residual.contiguous()
-    out = _caller_buffer("propagate", "out", out, (3 * n, S, D), out_dtype, kf_out.device)
-    ws = _workspace(lib.tf_nn_gather_blend_workspace_bytes(n_tgt, S, D, P), tgt.device, "nn")
-    if norm is not None:
-        if not norm_fusable(kf_out, residual, out_dtype, P, norm[3]):
-            raise TypeError("propagate: these dtypes have no fused-norm form (ops.norm_fusable)")
-        g, b, eps, wdt, nout, ndt, _keep = _norm_args(norm, kf_out, (3 * n, S, D), norm_out)
-        _launch(dev, "tf_nn_gather_blend_norm", lib.tf_nn_gather_blend_norm, tgt.data_ptr(), piv.data_ptr(),
-                inv_norm.data_ptr(), kf_out.data_ptr(), w.data_ptr() if w is not None else 0, residual.data_ptr(),
-                out.data_ptr(), K, n, S, D, P, int(kf_ids[0]), int(kf_ids[1]) if P == 2 else 0, _DT[tgt.dtype],
-                _DT[kf_out.dtype], _DT[residual.dtype], _DT[out_dtype], g, b, eps, wdt, nout.data_ptr(), ndt,
-                ws.data_ptr(), ws.numel())
-        return out, nout
-    _launch(dev, "tf_nn_gather_blend", lib.tf_nn_gather_blend, tgt.data_ptr(), piv.data_ptr(), inv_norm.data_ptr(),
-            kf_out.data_ptr(), w.data_ptr() if w is not None else 0,
-            residual.data_ptr() if residual is not None else 0, out.data_ptr(),
-            K, n, S, D, P, int(kf_ids[0]), int(kf_ids[1]) if P == 2 else 0, _DT[tgt.dtype], _DT[kf_out.dtype],
-            _DT[residual.dtype] if residual is not None else 0, _DT[out_dtype], ws.data_ptr(), ws.numel())
-    return out
+    return _propagate_call(what, dev, lib, "tf_nn_gather_blend", "tf_nn_gather_blend_norm", tgt, piv, inv_norm, kf_out, w,
+                           residual, out_dtype, norm, out, norm_out, rows=3 * n, P=P,
+                           ws_bytes=lib.tf_nn_gather_blend_workspace_bytes(n_tgt, S, D, P),
+                           shape_args=(K, n, S, D, P, int(kf_ids[0]), int(kf_ids[1]) if P == 2 else 0), single_dtype=False)
 
 
 def propagate_chunks(tgt: torch.Tensor, piv: torch.Tensor, inv_norm: torch.Tensor, kf_out: torch.Tensor,
@@ -1723,11 +1750,8 @@ def propagate_chunks(tgt: torch.Tensor, piv: torch.Tensor, inv_norm: torch.Tenso
     tgt [n_chunks*n*S, D] chunk-major, residual / result [3*n_chunks*n, S, D]; chunk j matches keyframe slots
     slot0 + j and slot0 + j - 1 of piv / inv_norm / kf_out; first_single: chunk 0 of the run is chunk 0 of the
     video (one keyframe).  Bit-identical to n_chunks calls of `propagate`.  out / norm_out as there."""
-    dev = _need_gpu(tgt, piv, inv_norm, kf_out, w, residual, out, norm_out)
-    if norm_out is not None and norm is None:
-        raise ValueError("propagate_chunks: `norm_out` without `norm`")
-    lib = _lib.load()
-    tgt, piv, kf_out = tgt.contiguous(), piv.contiguous(), kf_out.contiguous()
+    what = "propagate_chunks"
+    dev, lib = _propagate_begin(what, tgt, piv, inv_norm, kf_out, w, residual, out, norm, norm_out)
     K, S, D = piv.shape
     C = int(n_chunks)
     if C == 1:
@@ -1737,28 +1761,10 @@ def propagate_chunks(tgt: torch.Tensor, piv: torch.Tensor, inv_norm: torch.Tenso
     if (tgt.dtype != piv.dtype or tgt.shape != (C * n * S, D) or kf_out.shape != (3 * K, S, D) or w is None
             or slot0 + C > K or slot0 < (0 if first_single else 1)):
         raise ValueError("propagate_chunks: bad arguments")
-    if residual is not None:
-        residual = residual.contiguous()
-    # what the reference's single-keyframe pass would emit for chunk 0: kf dtype (+ residual), torch promotion
-    single_dtype = kf_out.dtype if residual is None else torch.promote_types(kf_out.dtype, residual.dtype)
-    out = _caller_buffer("propagate_chunks", "out", out, (3 * C * n, S, D), out_dtype, kf_out.device)
-    ws = _workspace(lib.tf_nn_gather_blend_chunks_workspace_bytes(n * S, S, D, C), tgt.device, "nn")
-    if norm is not None:
-        if not norm_fusable(kf_out, residual, out_dtype, 2, norm[3]):
-            raise TypeError("propagate_chunks: these dtypes have no fused-norm form (ops.norm_fusable)")
-        g, b, eps, wdt, nout, ndt, _keep = _norm_args(norm, kf_out, (3 * C * n, S, D), norm_out)
-        _launch(dev, "tf_nn_gather_blend_chunks_norm", lib.tf_nn_gather_blend_chunks_norm, tgt.data_ptr(),
-                piv.data_ptr(), inv_norm.data_ptr(), kf_out.data_ptr(), w.data_ptr(), residual.data_ptr(),
-                out.data_ptr(), K, n, C, S, D, int(slot0), 1 if first_single else 0, _DT[tgt.dtype], _DT[kf_out.dtype],
-                _DT[residual.dtype], _DT[out_dtype], _DT[single_dtype], g, b, eps, wdt, nout.data_ptr(), ndt,
-                ws.data_ptr(), ws.numel())
-        return out, nout
-    _launch(dev, "tf_nn_gather_blend_chunks", lib.tf_nn_gather_blend_chunks, tgt.data_ptr(), piv.data_ptr(),
-            inv_norm.data_ptr(), kf_out.data_ptr(), w.data_ptr(), residual.data_ptr() if residual is not None else 0,
-            out.data_ptr(), K, n, C, S, D, int(slot0), 1 if first_single else 0, _DT[tgt.dtype], _DT[kf_out.dtype],
-            _DT[residual.dtype] if residual is not None else 0, _DT[out_dtype], _DT[single_dtype],
-            ws.data_ptr(), ws.numel())
-    return out
+    return _propagate_call(what, dev, lib, "tf_nn_gather_blend_chunks", "tf_nn_gather_blend_chunks_norm", tgt, piv, inv_norm,
+                           kf_out, w, residual, out_dtype, norm, out, norm_out, rows=3 * C * n, P=2,
+                           ws_bytes=lib.tf_nn_gather_blend_chunks_workspace_bytes(n * S, S, D, C),
+                           shape_args=(K, n, C, S, D, int(slot0), 1 if first_single else 0))
 
 
 def propagate_chunks_segments(tgt: torch.Tensor, piv: torch.Tensor, inv_norm: torch.Tensor, kf_out: torch.Tensor,
@@ -1775,33 +1781,16 @@ def propagate_chunks_segments(tgt: torch.Tensor, piv: torch.Tensor, inv_norm: to
     if C == 1:
         return propagate_chunks(tgt, piv, inv_norm, kf_out, w, n, C, slot0, bool(m & 1), residual, out_dtype, norm=norm,
                                 out=out, norm_out=norm_out)
-    dev = _need_gpu(tgt, piv, inv_norm, kf_out, w, residual, out, norm_out)
-    if norm_out is not None and norm is None:
-        raise ValueError("propagate_chunks_segments: `norm_out` without `norm`")
-    lib = _lib.load()
-    tgt, piv, kf_out = tgt.contiguous(), piv.contiguous(), kf_out.contiguous()
+    what = "propagate_chunks_segments"
+    dev, lib = _propagate_begin(what, tgt, piv, inv_norm, kf_out, w, residual, out, norm, norm_out)
     K, S, D = piv.shape
     if (tgt.dtype != piv.dtype or tgt.shape != (C * n * S, D) or kf_out.shape != (3 * K, S, D) or w is None
             or slot0 + C > K or slot0 < (0 if m & 1 else 1)):
         raise ValueError("propagate_chunks_segments: bad arguments")
-    if residual is not None:
-        residual = residual.contiguous()
-    single_dtype = kf_out.dtype if residual is None else torch.promote_types(kf_out.dtype, residual.dtype)
-    out = _caller_buffer("propagate_chunks_segments", "out", out, (3 * C * n, S, D), out_dtype, kf_out.device)
-    ws = _workspace(lib.tf_nn_gather_blend_chunks_workspace_bytes(n * S, S, D, C), tgt.device, "nn")
-    head = (tgt.data_ptr(), piv.data_ptr(), inv_norm.data_ptr(), kf_out.data_ptr(), w.data_ptr(),
-            residual.data_ptr() if residual is not None else 0, out.data_ptr(), K, n, C, S, D, int(slot0), m, _DT[tgt.dtype],
-            _DT[kf_out.dtype], _DT[residual.dtype] if residual is not None else 0, _DT[out_dtype], _DT[single_dtype])
-    if norm is not None:
-        if not norm_fusable(kf_out, residual, out_dtype, 2, norm[3]):
-            raise TypeError("propagate_chunks_segments: these dtypes have no fused-norm form (ops.norm_fusable)")
-        g, b, eps, wdt, nout, ndt, _keep = _norm_args(norm, kf_out, (3 * C * n, S, D), norm_out)
-        _launch(dev, "tf_nn_gather_blend_chunks_norm_segments", lib.tf_nn_gather_blend_chunks_norm_segments, *head, g, b, eps,
-                wdt, nout.data_ptr(), ndt, ws.data_ptr(), ws.numel())
-        return out, nout
-    _launch(dev, "tf_nn_gather_blend_chunks_segments", lib.tf_nn_gather_blend_chunks_segments, *head, ws.data_ptr(),
-            ws.numel())
-    return out
+    return _propagate_call(what, dev, lib, "tf_nn_gather_blend_chunks_segments", "tf_nn_gather_blend_chunks_norm_segments",
+                           tgt, piv, inv_norm, kf_out, w, residual, out_dtype, norm, out, norm_out, rows=3 * C * n, P=2,
+                           ws_bytes=lib.tf_nn_gather_blend_chunks_workspace_bytes(n * S, S, D, C),
+                           shape_args=(K, n, C, S, D, int(slot0), m), codes_first=True)
 
 
 def propagate_chunks_edits(tgt: torch.Tensor, piv: torch.Tensor, inv_norm: torch.Tensor, kf_out: torch.Tensor,
@@ -1813,42 +1802,25 @@ def propagate_chunks_edits(tgt: torch.Tensor, piv: torch.Tensor, inv_norm: torch
     reads the source branch only -- and one gather over all B branches on the same candidates; every branch of the result
     is bit-identical to the same branch of the single-edit call on [source | uncond_e | cond_e].
     norm=, out / norm_out ([B*n_chunks*n, S, D]) as `propagate`."""
-    dev = _need_gpu(tgt, piv, inv_norm, kf_out, w, residual, out, norm_out)
-    if norm_out is not None and norm is None:
-        raise ValueError("propagate_chunks_edits: `norm_out` without `norm`")
-    lib = _lib.load()
+    what = "propagate_chunks_edits"
+    dev, lib = _propagate_begin(what, tgt, piv, inv_norm, kf_out, w, residual, out, norm, norm_out)
     E = int(n_edits)
     if not 1 <= E <= _lib.TF_MAX_EDITS:
         raise ValueError(f"propagate_chunks_edits: n_edits={n_edits} (1 .. {_lib.TF_MAX_EDITS})")
     nbr = 1 + 2 * E
-    tgt, piv, kf_out = tgt.contiguous(), piv.contiguous(), kf_out.contiguous()
     K, S, D = piv.shape
     C = int(n_chunks)
     single = C == 1 and first_single           # the one-keyframe chunk 0 of the video alone: P = 1
     if (tgt.dtype != piv.dtype or tgt.shape != (C * n * S, D) or kf_out.shape != (nbr * K, S, D)
             or (w is None and not single) or slot0 + C > K or slot0 < (0 if first_single else 1)):
         raise ValueError("propagate_chunks_edits: bad arguments")
-    if residual is not None:
-        residual = residual.contiguous()
-        if residual.shape != (nbr * C * n, S, D):
-            raise ValueError("propagate_chunks_edits: residual must be [B*n_chunks*n, S, D]")
-    single_dtype = kf_out.dtype if residual is None else torch.promote_types(kf_out.dtype, residual.dtype)
-    out = _caller_buffer("propagate_chunks_edits", "out", out, (nbr * C * n, S, D), out_dtype, kf_out.device)
-    ws = _workspace(max(lib.tf_nn_gather_blend_chunks_workspace_bytes(n * S, S, D, C),
-                        lib.tf_nn_gather_blend_workspace_bytes(n * S, S, D, 1) if single else 0), tgt.device, "nn")
-    head = (tgt.data_ptr(), piv.data_ptr(), inv_norm.data_ptr(), kf_out.data_ptr(), w.data_ptr() if w is not None else 0,
-            residual.data_ptr() if residual is not None else 0, out.data_ptr(), K, n, C, S, D, int(slot0),
-            1 if first_single else 0, _DT[tgt.dtype], _DT[kf_out.dtype],
-            _DT[residual.dtype] if residual is not None else 0, _DT[out_dtype], _DT[single_dtype], E)
-    if norm is not None:
-        if not norm_fusable(kf_out, residual, out_dtype, 1 if single else 2, norm[3]):
-            raise TypeError("propagate_chunks_edits: these dtypes have no fused-norm form (ops.norm_fusable)")
-        g, b, eps, wdt, nout, ndt, _keep = _norm_args(norm, kf_out, (nbr * C * n, S, D), norm_out)
-        _launch(dev, "tf_nn_gather_blend_chunks_norm_edits", lib.tf_nn_gather_blend_chunks_norm_edits, *head, g, b, eps, wdt,
-                nout.data_ptr(), ndt, ws.data_ptr(), ws.numel())
-        return out, nout
-    _launch(dev, "tf_nn_gather_blend_chunks_edits", lib.tf_nn_gather_blend_chunks_edits, *head, ws.data_ptr(), ws.numel())
-    return out
+    return _propagate_call(what, dev, lib, "tf_nn_gather_blend_chunks_edits", "tf_nn_gather_blend_chunks_norm_edits", tgt, piv,
+                           inv_norm, kf_out, w, residual, out_dtype, norm, out, norm_out, rows=nbr * C * n,
+                           P=1 if single else 2,
+                           ws_bytes=max(lib.tf_nn_gather_blend_chunks_workspace_bytes(n * S, S, D, C),
+                                        lib.tf_nn_gather_blend_workspace_bytes(n * S, S, D, 1) if single else 0),
+                           shape_args=(K, n, C, S, D, int(slot0), 1 if first_single else 0), tail=(E,),
+                           residual_is="[B*n_chunks*n, S, D]", codes_first=True)
 
 
 def propagate_chunks_ragged(tgt: torch.Tensor, piv: torch.Tensor, inv_norm: torch.Tensor, kf_out: torch.Tensor,
@@ -1877,36 +1849,18 @@ def propagate_chunks_ragged(tgt: torch.Tensor, piv: torch.Tensor, inv_norm: torc
                                     norm=norm, out=out, norm_out=norm_out)
         return propagate_chunks_edits(tgt, piv, inv_norm, kf_out, w, fr[0], 1, slot0, bool(m & 1), residual, out_dtype, E,
                                       norm=norm, out=out, norm_out=norm_out)
-    dev = _need_gpu(tgt, piv, inv_norm, kf_out, w, residual, out, norm_out)
-    if norm_out is not None and norm is None:
-        raise ValueError(f"{what}: `norm_out` without `norm`")
-    lib = _lib.load()
+    dev, lib = _propagate_begin(what, tgt, piv, inv_norm, kf_out, w, residual, out, norm, norm_out)
     nbr = 1 + 2 * E
-    tgt, piv, kf_out = tgt.contiguous(), piv.contiguous(), kf_out.contiguous()
     K, S, D = piv.shape
     if (tgt.dtype != piv.dtype or tgt.shape != (F * S, D) or kf_out.shape != (nbr * K, S, D) or w is None
             or w.dtype != torch.float32 or w.numel() != F or not w.is_contiguous()
             or slot0 + C > K or slot0 < (0 if m & 1 else 1)):
         raise ValueError(f"{what}: bad arguments")
-    if residual is not None:
-        residual = residual.contiguous()
-        if residual.shape != (nbr * F, S, D):
-            raise ValueError(f"{what}: residual must be [B*sum(chunk_frames), S, D]")
-    single_dtype = kf_out.dtype if residual is None else torch.promote_types(kf_out.dtype, residual.dtype)
-    out = _caller_buffer(what, "out", out, (nbr * F, S, D), out_dtype, kf_out.device)
-    ws = _workspace(lib.tf_nn_gather_blend_ragged_workspace_bytes(arr, C, S, D), tgt.device, "nn")
-    head = (tgt.data_ptr(), piv.data_ptr(), inv_norm.data_ptr(), kf_out.data_ptr(), w.data_ptr(),
-            residual.data_ptr() if residual is not None else 0, out.data_ptr(), K, arr, C, S, D, int(slot0), m, _DT[tgt.dtype],
-            _DT[kf_out.dtype], _DT[residual.dtype] if residual is not None else 0, _DT[out_dtype], _DT[single_dtype], E)
-    if norm is not None:
-        if not norm_fusable(kf_out, residual, out_dtype, 2, norm[3]):
-            raise TypeError(f"{what}: these dtypes have no fused-norm form (ops.norm_fusable)")
-        g, b, eps, wdt, nout, ndt, _keep = _norm_args(norm, kf_out, (nbr * F, S, D), norm_out)
-        _launch(dev, "tf_nn_gather_blend_chunks_norm_ragged", lib.tf_nn_gather_blend_chunks_norm_ragged, *head, g, b, eps, wdt,
-                nout.data_ptr(), ndt, ws.data_ptr(), ws.numel())
-        return out, nout
-    _launch(dev, "tf_nn_gather_blend_chunks_ragged", lib.tf_nn_gather_blend_chunks_ragged, *head, ws.data_ptr(), ws.numel())
-    return out
+    return _propagate_call(what, dev, lib, "tf_nn_gather_blend_chunks_ragged", "tf_nn_gather_blend_chunks_norm_ragged", tgt, piv,
+                           inv_norm, kf_out, w, residual, out_dtype, norm, out, norm_out, rows=nbr * F, P=2,
+                           ws_bytes=lib.tf_nn_gather_blend_ragged_workspace_bytes(arr, C, S, D),
+                           shape_args=(K, arr, C, S, D, int(slot0), m), tail=(E,),
+                           residual_is="[B*sum(chunk_frames), S, D]", codes_first=True)
 
 
 def inject_copy_edits_(x: torch.Tensor, n_edits: int, edit_mask: Optional[int] = None) -> torch.Tensor:
